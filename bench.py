@@ -12,6 +12,10 @@ lanes (strong scaling) and every reduced gradient / Hessian-vector / scalar vect
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the K periods and prints the line; `--full` adds what the headline does not need
+(the per-kernel profile of the last timed period(s) behind `roofline` / `phases`, the standalone env-step kernel, the
+CPU baseline).  `--dump-outputs DIR` writes what the last timed period computed as DIR/<name>.npy.
+
 Rank 0 prints ONE JSON line (see the driver contract in the task statement).
 """
 import argparse
@@ -89,7 +93,41 @@ def parse_args():
                          "collectives, rank 0 prints one JSON line, nothing else runs (tests/test_bench_launch.py)")
     ap.add_argument("--cpu-sample-steps", type=int, default=262144,
                     help="total env-steps of the bounded CPU-baseline sample (split over the host cores)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the HIP-event profile of the last "
+                         "--profile-steps timed period(s) (`roofline`, `roofline_policy`, `phases`, "
+                         "`allreduce_per_rank`), the standalone env-step kernel (`roofline_env_step`) and the CPU "
+                         "baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed periods, write what the last one computed as DIR/<name>.npy (float32 / "
+                         "float64): both parameter vectors, the two update statistics and the trajectory on a fixed, "
+                         "seeded sample of lanes")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(path, policy, critic, traj, last, max_bytes=48 << 20):
+    """What the last timed period handed its caller: the updated policy and critic parameters, the TRPO and critic
+    statistics, and the trajectory it trained on (rollout, critic values, GAE advantages, returns) on a fixed sample of
+    lanes (seeded, sorted; `sample_lanes` names them) sized so that the files stay under `max_bytes`."""
+    import relearn_amd as ra
+    fields = (("obs", ra.TRAJ_OBS), ("term_obs", ra.TRAJ_TERM_OBS), ("action", ra.TRAJ_ACTION),
+              ("reward", ra.TRAJ_REWARD), ("flag", ra.TRAJ_FLAG), ("values", ra.TRAJ_VALUES),
+              ("advantages", ra.TRAJ_ADVANTAGES), ("returns", ra.TRAJ_RETURNS))
+    per_lane = sum(4 * int(np.prod(traj.shape(f)[:-1])) for _, f in fields) + 8
+    n_sample = max(1, min(traj.n, 4096, max_bytes // per_lane))
+    lanes = np.sort(np.random.default_rng(0).choice(traj.n, size=n_sample, replace=False))
+    out = {"policy_params": policy.get_params(), "critic_params": critic.get_params(),
+           "trpo_stats": np.array([getattr(last["trpo"], k) for k, _ in ra.TrpoStats._fields_], dtype=np.float64),
+           "critic_stats": np.array([getattr(last["critic"], k) for k, _ in ra.CriticStats._fields_], dtype=np.float64),
+           "sample_lanes": lanes.astype(np.float64)}
+    for name, field in fields:
+        out["traj_" + name] = np.ascontiguousarray(traj.read(field)[..., lanes], dtype=np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def cpu_baseline(args):
@@ -504,9 +542,9 @@ def main():
     periods(args.warmup)
     barrier()
     # Per-kernel HIP events (two per launch) cost ~2 ms of host time per period when they wrap all ~220 launches, so
-    # they are switched on for the LAST `--profile-steps` periods of the timed region only; `roofline` / `phases`
-    # are averages over those periods' launches.
-    prof_steps = 0 if args.no_kernel_profile else max(1, min(args.profile_steps, args.steps))
+    # they are switched on for the LAST `--profile-steps` periods of the timed region only, and only with --full;
+    # `roofline` / `phases` are averages over those periods' launches.
+    prof_steps = 0 if args.no_kernel_profile or not args.full else max(1, min(args.profile_steps, args.steps))
     eng.profile_read(reset=True)
     barrier()
     enter("timed periods (%s collective)" % comm_kind)
@@ -522,11 +560,13 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     enter("after the timed region")
-    prof = eng.profile_read(reset=True) if not args.no_kernel_profile else None
+    prof = eng.profile_read(reset=True) if prof_steps else None
     eng.profile_enable(False)
     eng.set_serial_update(args.serial_update)
     if ctl is not None:
         elapsed = float(ctl.all_max(elapsed))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, policy, critic, trajs[(args.steps - 1) % len(trajs)], last)
 
     total_steps = args.envs * T * args.steps
     value = total_steps / elapsed
@@ -654,7 +694,7 @@ def main():
 
     # ---- standalone env-step kernel: 100 B/env-step, HBM roofline --------------------------
     env_step = None
-    if rank == 0:
+    if rank == 0 and args.full:
         reps = 200
         env.upload_actions(np.random.default_rng(0).integers(0, 2, size=n_local).astype(np.uint8))
         for _ in range(20):
@@ -689,7 +729,7 @@ def main():
             env_step["filled"] = {"error": str(exc)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     # replicas must still be bit-identical after the timed region: every rank applied the same all-reduced vectors
@@ -706,7 +746,7 @@ def main():
         ctl.barrier()
     # what the collective cost each rank (launches and time per period), so that a scaling run explains itself
     allreduce_per_rank = None
-    if ctl is not None:
+    if ctl is not None and args.full:
         mine = None
         if prof is not None and prof.get("allreduce", (0.0, 0))[1]:
             ar_ms, ar_n = prof["allreduce"]
@@ -735,8 +775,9 @@ def main():
                 "n_envs_total": args.envs, "n_envs_per_gpu": n_local, "horizon": T, "hidden": H,
                 "critic_steps": args.critic_steps,
                 "update_chains": ("policy and critic chains one after the other" if args.serial_update else
-                                  "policy and critic chains side by side on two streams (the %d profiled period(s) of "
-                                  "the timed region run them in turn)" % prof_steps),
+                                  "policy and critic chains side by side on two streams" +
+                                  (" (the %d profiled period(s) of the timed region run them in turn)" % prof_steps
+                                   if prof_steps else "")),
                 "pipeline": ("period k+1's rollout enqueued after TRPO k, under critic chain k (two trajectories; %d of "
                              "the %d timed rollouts have a chain to hide under)" % (
                                  max(args.steps - prof_steps - 1, 0), args.steps) if pipelined else "none"),

@@ -11,19 +11,19 @@ PART="${2:-all}"   # part1: the headline configuration (bench lines, kernel trac
 [ "$PART" = "part2" ] || rm -rf "$OUT"
 mkdir -p "$OUT"
 if [ "$PART" != "part2" ]; then
-python3 bench.py > "$OUT/bench_65536.json" 2> "$OUT/bench_65536.err" || echo "bench 65536 failed"
+python3 bench.py --full > "$OUT/bench_65536.json" 2> "$OUT/bench_65536.err" || echo "bench 65536 failed"
 # one rank's share of the headline at 2 / 4 / 8 / 16 GPUs (the projection is built from these)
 for n in 32768 16384 8192 4096; do
-  python3 bench.py --envs $n --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" || echo "bench $n failed"
+  python3 bench.py --full --envs $n --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" || echo "bench $n failed"
 done
 for n in 65536 8192 4096; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$n" -- python3 bench.py --envs $n --steps 3 --warmup 1 --no-cpu-baseline \
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$n" -- python3 bench.py --full --envs $n --steps 3 --warmup 1 --no-cpu-baseline \
     > "$OUT/bench_under_rocprof_$n.json" 2> "$OUT/stats_$n.log" || echo "rocprof stats $n failed"
 done
 # the same command with the two update chains in turn: per-kernel averages that agree with the HIP-event figures of the
 # bench line (its profiled period runs the chains in turn; side by side, a launch's span includes the other chain's work)
 for n in 65536 8192; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_serial_$n" -- python3 bench.py --envs $n --steps 3 --warmup 1 --no-cpu-baseline --serial-update \
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_serial_$n" -- python3 bench.py --full --envs $n --steps 3 --warmup 1 --no-cpu-baseline --serial-update \
     > "$OUT/bench_under_rocprof_serial_$n.json" 2> "$OUT/stats_serial_$n.log" || echo "rocprof serial stats $n failed"
 done
 bash scripts/pmc_passes.sh "${TAG}_65536" scripts/path_once.py 65536 2 80 > "$OUT/pmc_65536.log" 2>&1 || echo "pmc failed"
@@ -33,7 +33,7 @@ cp "$OUT/pmc_65536_summary.json" "profiles/${TAG}_pmc_65536_summary.json" 2>/dev
 # which launches of the two update chains ran side by side (the non-profiled periods of the traced bench run)
 python3 scripts/overlap_summary.py "$OUT/stats_65536" "$OUT/overlap_trace_65536.csv" "$OUT/overlap_65536.json" > /dev/null 2>&1 || echo "overlap 65536 failed"
 python3 scripts/overlap_summary.py "$OUT/stats_8192" "$OUT/overlap_trace_8192.csv" "$OUT/overlap_8192.json" > /dev/null 2>&1 || echo "overlap 8192 failed"
-python3 bench.py > "$OUT/bench_65536_with_counters.json" 2> "$OUT/bench_65536_with_counters.err" || echo "bench (with counters) failed"
+python3 bench.py --full > "$OUT/bench_65536_with_counters.json" 2> "$OUT/bench_65536_with_counters.err" || echo "bench (with counters) failed"
 python3 scripts/rccl_floor.py 8192 20 "$OUT/rccl_one_rank_floor_8192.json" > "$OUT/rccl_floor.log" 2>&1 || echo "rccl floor failed"
 fi
 [ "$PART" = "part1" ] && { echo "collect_profiles part1 done"; exit 0; }

@@ -247,16 +247,18 @@ def poisoned_torch(tmp_path):
 
 
 def run_bench(world, extra_env=None, workload=("--envs", "2048", "--horizon", "32", "--critic-steps", "5"), limit=150,
-              launcher="self"):
+              launcher="self", full=True):
     """bench.py on a small workload, one process per rank: `launcher` "self" = `python bench.py --gpus N` (bench.py starts
-    its own ranks), "torchrun" = exactly as the driver launches it (torch.distributed.run)"""
+    its own ranks), "torchrun" = exactly as the driver launches it (torch.distributed.run); `full`: with --full, whose
+    line carries `phases` and `allreduce_per_rank`"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     # ONE period: the rollouts of the two runs are then identical and only the order of the f32 sums differs (a second
     # period would start from policies that already differ by TRPO's amplified rounding, and drift apart from there)
-    args = ["--gpus", str(world), "--steps", "1", "--warmup", "0", "--no-cpu-baseline"] + list(workload)
+    args = (["--gpus", str(world), "--steps", "1", "--warmup", "0", "--no-cpu-baseline"] +
+            (["--full"] if full else []) + list(workload))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **(extra_env or {}))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "RELEARN_RDZV_PORT"):
         env.pop(k, None)
@@ -780,6 +782,31 @@ def test_bench_pipelined_periods_report_the_same_update_as_the_plain_sequence():
     assert "two trajectories" in piped["config"]["pipeline"] and plain["config"]["pipeline"] == "none"
     assert plain["last_update"] == piped["last_update"]
     assert plain["last_update"]["trpo_status"] == ra.OPT_OK
+
+
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """A plain `bench.py` (no --full) times the periods and measures nothing else; `--dump-outputs DIR` writes what the
+    last timed period computed as float32 / float64 .npy files, under 64 MB.  The plain and the full run compute the
+    same periods (the full run's profiled last period runs the two chains in turn): the same files, bit for bit."""
+    common = ("--envs", "4096", "--horizon", "32", "--critic-steps", "10", "--steps", "3", "--warmup", "1")
+    plain = run_bench(1, workload=common + ("--dump-outputs", str(tmp_path / "plain")), full=False)
+    full = run_bench(1, workload=common + ("--dump-outputs", str(tmp_path / "full")))
+    for key in ("roofline", "roofline_policy", "roofline_env_step", "phases", "cpu_baseline"):
+        assert plain[key] is None, key
+    assert full["phases"] is not None and full["roofline_env_step"] is not None
+    assert plain["steps"] == 3 and abs(plain["value"] * plain["ms_per_step"] * 1e-3 - 4096 * 32) < 1e-6 * 4096 * 32
+    names = sorted(os.listdir(str(tmp_path / "plain")))
+    assert names == sorted(os.listdir(str(tmp_path / "full")))
+    assert {"policy_params.npy", "critic_params.npy", "traj_advantages.npy", "trpo_stats.npy"} <= set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(str(tmp_path / "plain" / name)), np.load(str(tmp_path / "full" / name))
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, name
+        assert np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert plain["last_update"] == full["last_update"] and plain["last_update"]["trpo_status"] == ra.OPT_OK
+    assert np.load(str(tmp_path / "plain" / "trpo_stats.npy"))[-2] == plain["last_update"]["trpo_status"]
 
 
 def test_a_stalled_rank_ends_the_bench_with_the_phase_it_was_stuck_in():
