@@ -6,7 +6,9 @@
 //
 //   build:  g++ -std=c++17 -O2 -I. examples/cartpole_trpo.cpp -o cartpole_trpo -Lrelearn_amd -lrelearn_hip
 //           (one line, plus -Wl,-rpath,$PWD/relearn_amd)
-//   train:  ./cartpole_trpo [--lanes N] [--periods P] [--out DIR]
+//   train:  ./cartpole_trpo [--lanes N] [--periods P] [--out DIR] [--summary]
+//           (--summary: log the reference's full per-period StepsSummary — episode reward and length mean / stddev,
+//           step reward mean / stddev — computed on the device, instead of the mean-length estimate)
 //   eval :  ./cartpole_trpo DIR/actor.cbor
 #include <sys/stat.h>
 
@@ -36,9 +38,13 @@ static int evaluate(Engine &eng, const std::string &actor_path) {
   module_from_cbor(*policy, doc, eng);
   DeviceHistory history(eng, 64, 160, 5);
   check(rl_rollout(env.handle(), policy->handle(), history.handle()), eng.handle());
+  // println!("\nEvaluation Stats\n{:.3}", summary) of the reference, from the device summary of the rollout
+  StepsSummaryLanes summary(eng, 64);
+  summary.push(history);
+  std::printf("\nEvaluation Stats\n%s\n", summary.read().display(3).c_str());
   uint64_t episodes = 0;
   for (uint8_t f : history.successors()) episodes += f != RL_SUCC_CONTINUE;
-  std::printf("\nEvaluation Stats\nsteps %llu  episodes %llu  mean episode length (= reward) %.3f\n",
+  std::printf("steps %llu  episodes %llu  mean episode length (= reward) %.3f\n",
               (unsigned long long)history.num_steps(), (unsigned long long)episodes,
               (double)history.num_steps() / (double)(episodes ? episodes : 1));
   return 0;
@@ -46,14 +52,16 @@ static int evaluate(Engine &eng, const std::string &actor_path) {
 
 int main(int argc, char **argv) {
   uint64_t lanes = 4096, periods = 50;
+  bool with_summary = false;
   std::string out_dir, actor_path;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--lanes" && i + 1 < argc) lanes = std::strtoull(argv[++i], nullptr, 10);
     else if (a == "--periods" && i + 1 < argc) periods = std::strtoull(argv[++i], nullptr, 10);
     else if (a == "--out" && i + 1 < argc) out_dir = argv[++i];
+    else if (a == "--summary") with_summary = true;
     else if (a.rfind("--", 0) == 0) {
-      std::fprintf(stderr, "Usage: %s [--lanes N] [--periods P] [--out DIR] | %s saved_actor.cbor\n", argv[0], argv[0]);
+      std::fprintf(stderr, "Usage: %s [--lanes N] [--periods P] [--out DIR] [--summary] | %s saved_actor.cbor\n", argv[0], argv[0]);
       return 2;
     } else actor_path = a;
   }
@@ -83,7 +91,12 @@ int main(int argc, char **argv) {
       DisplayLogger<ByCounter> display(ByCounter("agent_update/count", 2));
       TensorBoardLogger<ByCounter> board(ByCounter("agent_update/count", 1), out_dir);
       TeeLogger logger(display, board);
-      train_batched(*agent, env, history, periods, logger);
+      if (with_summary) {  // the period's full StepsSummary, computed on the device
+        StepsSummaryLanes summary(eng, lanes);
+        train_batched(*agent, env, history, periods, logger, summary);
+      } else {
+        train_batched(*agent, env, history, periods, logger);
+      }
     }  // the loggers flush when they go out of scope
 
     const std::string path = out_dir + "/actor.cbor";

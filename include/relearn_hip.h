@@ -33,9 +33,10 @@
 extern "C" {
 #endif
 
-/* Incremented whenever an entry point is added or removed, an argument list or a struct layout changes, or a status code
- * is renumbered: a binding checks rl_abi_version() against the value it was generated from.  6 (round 6): covers the two
- * entry points round 5 added under the old number (rl_actor_critic_update_begin / _finish); nothing was added since. */
+/* Incremented whenever an entry point is removed, an argument list or a struct layout changes, or a status code is
+ * renumbered: a binding checks rl_abi_version() against the value it was generated from.  Purely additive entry
+ * points (new symbols, new structs; nothing existing changes) keep the number: a binding finds them by symbol lookup.
+ * 6 (round 6): covers rl_actor_critic_update_begin / _finish; the step summaries (rl_summary_*) came later under it. */
 #define RL_ABI_VERSION 6
 
 /* ---------------------------------------------------------------------------------------------
@@ -77,6 +78,7 @@ typedef struct rl_mlp rl_mlp;
 typedef struct rl_traj rl_traj;
 typedef struct rl_adam rl_adam;
 typedef struct rl_dqn rl_dqn;
+typedef struct rl_summary rl_summary;
 
 /* ---------------------------------------------------------------------------------------------
  * Engine (one per GPU).  Stands in for `Device::cuda_if_available()` + the libtorch runtime the
@@ -614,6 +616,53 @@ int32_t rl_dqn_minibatch_read(rl_dqn *dqn, int32_t field, void *host, uint64_t b
 int32_t rl_dqn_minibatch_gradient(rl_dqn *dqn, float *grad_out, float *loss_out);
 /* word position of the agent Prng (stream 0 of agent_key) */
 int32_t rl_dqn_agent_rng_pos(rl_dqn *dqn, uint64_t *pos_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Step statistics of collected experience: the StepsSummary that train_parallel logs after every collection
+ * (src/simulation/train.rs:160-175) and the example's evaluation prints (examples/cartpole-trpo.rs:82-93).
+ *   OnlineMeanVariance<f64> (population variance; Chan et al.'s merge)   src/utils/stats.rs:11-15,119-203
+ *   StepsSummary { step_feedback, episode_feedback, episode_length }      src/simulation/summary.rs:11-18
+ *   OnlineStepsSummary::push                                             src/simulation/summary.rs:198-214
+ *   RewardSummary (step and episode reward statistics)                   src/feedback/reward.rs:130-143
+ * An rl_summary keeps, on the device, one OnlineStepsSummary per lane (the episode in progress: its length and its
+ * return, f64) and the completed StepsSummary of everything pushed since the last clear.  Every pushed step adds its
+ * reward (f32 widened to f64) to step_reward and to the lane's return, and 1 to the lane's length; a TERMINATE or
+ * INTERRUPT successor pushes the lane's length and return as one episode and zeroes them.  Lanes persist across pushes
+ * (the engine's lanes persist across periods): an episode that straddles pushes is counted once, in the push where it
+ * ends, with its full length and return; the horizon cut leaves CONTINUE and ends nothing.  Results are bit-identical
+ * from run to run for the same inputs and lane count (fixed merge tree, no atomics).
+ * Deviation: merging with an empty side returns the other side unchanged (the reference's Add divides 0 / 0 into NaN
+ * when both sides are empty, stats.rs:184-209). */
+typedef struct {
+  double mean;
+  double squared_residual_sum;
+  uint64_t count;
+} rl_mean_variance; /* OnlineMeanVariance<f64>, src/utils/stats.rs:11-15 */
+typedef struct {
+  rl_mean_variance step_reward;
+  rl_mean_variance episode_reward;
+  rl_mean_variance episode_length;
+} rl_steps_summary; /* StepsSummary<Reward>, src/simulation/summary.rs:11-18 */
+/* per-lane carry zeroed, completed statistics empty; n_lanes = lanes of the trajectories / DQN agent pushed (this rank) */
+int32_t rl_summary_create(rl_engine *engine, uint64_t n_lanes, rl_summary **out);
+int32_t rl_summary_destroy(rl_summary *s);
+/* OnlineStepsSummary::push for every step of the trajectory's reward and flag planes (summary.rs:198-214), time order
+ * per lane.  Enqueues only (two launches on the engine's main stream); n_lanes must match.  It reads nothing but those
+ * two planes, which no update writes: the intended spot is right after rl_rollout, and it may also sit between
+ * rl_actor_critic_update_begin and _finish, where it does not wait for the critic chain (header above). */
+int32_t rl_summary_push(rl_summary *s, const rl_traj *traj);
+/* The same for the steps of the last rl_dqn_collect: successor codes from RL_REPLAY_LAST_FLAGS, each step's reward
+ * from the replay record the collection wrote (ring slot (total - horizon + t) mod capacity, replay.rs:89-115).
+ * RL_ERR_INVALID_ARGUMENT before the first collection or when the collection was longer than the ring. */
+int32_t rl_summary_push_dqn(rl_summary *s, const rl_dqn *dqn);
+/* the completed StepsSummary since the last clear (synchronises) */
+int32_t rl_summary_read(rl_summary *s, rl_steps_summary *out);
+/* empties the completed statistics (a new period: `OnlineStepsSummary::default().completed`); the episodes in progress
+ * are kept unless forget_episodes_in_progress != 0 (after rl_env_reset: every lane starts a new episode) */
+int32_t rl_summary_clear(rl_summary *s, int32_t forget_episodes_in_progress);
+/* `impl Add for StepsSummary` (summary.rs; stats.rs:184-209) on the host, no engine: combines the summaries of ranks
+ * or periods; `out` may alias `a` or `b` */
+int32_t rl_steps_summary_merge(const rl_steps_summary *a, const rl_steps_summary *b, rl_steps_summary *out);
 
 /* ---------------------------------------------------------------------------------------------
  * Actor serialisation in the reference's on-disk format: the CBOR document that

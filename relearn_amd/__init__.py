@@ -7,6 +7,7 @@ fallback: importing works anywhere (so the symbol table can be checked without a
 """
 import atexit
 import ctypes as C
+import math
 import os
 import subprocess
 import sys
@@ -56,6 +57,8 @@ ABI_SYMBOLS = [
     "rl_dqn_min_update_size", "rl_dqn_collect", "rl_dqn_update", "rl_dqn_replay_field_bytes", "rl_dqn_replay_read",
     "rl_dqn_minibatch_sample", "rl_dqn_minibatch_read", "rl_dqn_minibatch_gradient", "rl_dqn_agent_rng_pos",
     "rl_chain_tabular_q_train", "rl_chain_tabular_q_eval",
+    "rl_summary_create", "rl_summary_destroy", "rl_summary_push", "rl_summary_push_dqn", "rl_summary_read",
+    "rl_summary_clear", "rl_steps_summary_merge",
 ]
 
 
@@ -181,7 +184,7 @@ def _register(obj):
 @atexit.register
 def _close_all():
     objs = list(_live)
-    order = {"Dqn": -1, "Adam": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "Mlp": 3, "GruMlp": 3,
+    order = {"StepsSummary": -1, "Dqn": -1, "Adam": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "Mlp": 3, "GruMlp": 3,
              "Engine": 4}
     for o in sorted(objs, key=lambda o: order.get(type(o).__name__, 2)):
         o.close()
@@ -919,6 +922,71 @@ class Dqn(_Handle):
         p = C.c_uint64()
         _check(lib().rl_dqn_agent_rng_pos(self.h, C.byref(p)), self.eng.h)
         return p.value
+
+
+class MeanVariance(C.Structure):
+    """OnlineMeanVariance<f64> (src/utils/stats.rs:11-15): population variance, None while empty"""
+    _fields_ = [("mean", C.c_double), ("squared_residual_sum", C.c_double), ("count", C.c_uint64)]
+
+    def mean_or_none(self):
+        return self.mean if self.count > 0 else None
+
+    def variance(self):
+        return self.squared_residual_sum / self.count if self.count > 0 else None
+
+    def stddev(self):
+        v = self.variance()
+        return None if v is None else math.sqrt(v)
+
+    def __repr__(self):
+        return "(mean = %r; squared_residual_sum = %r; n = %d)" % (self.mean, self.squared_residual_sum, self.count)
+
+
+class StepsSummaryStats(C.Structure):
+    """rl_steps_summary = StepsSummary<Reward> (src/simulation/summary.rs:11-18)"""
+    _fields_ = [("step_reward", MeanVariance), ("episode_reward", MeanVariance), ("episode_length", MeanVariance)]
+
+    def __repr__(self):
+        return "StepsSummaryStats(step_reward=%r, episode_reward=%r, episode_length=%r)" % (
+            self.step_reward, self.episode_reward, self.episode_length)
+
+
+class StepsSummary(_Handle):
+    """One OnlineStepsSummary per lane and the completed StepsSummary, on the device (rl_summary_*): push
+    trajectories (or the last DQN collection) of `n_lanes` lanes, read the statistics, clear them per period."""
+
+    def __init__(self, engine, n_lanes):
+        self.eng, self.n = engine, n_lanes
+        self.h = C.c_void_p()
+        _check(lib().rl_summary_create(engine.h, C.c_uint64(n_lanes), C.byref(self.h)), engine.h)
+        _register(self)
+
+    def close(self):
+        if self.h:
+            lib().rl_summary_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def push(self, traj):
+        _check(lib().rl_summary_push(self.h, traj.h), self.eng.h)
+
+    def push_dqn(self, dqn):
+        _check(lib().rl_summary_push_dqn(self.h, dqn.h), self.eng.h)
+
+    def read(self):
+        out = StepsSummaryStats()
+        _check(lib().rl_summary_read(self.h, C.byref(out)), self.eng.h)
+        return out
+
+    def clear(self, forget=False):
+        """a new period; forget=True also drops the episodes in progress (after an env reset)"""
+        _check(lib().rl_summary_clear(self.h, C.c_int32(1 if forget else 0)), self.eng.h)
+
+
+def steps_summary_merge(a, b):
+    """`StepsSummary + StepsSummary` on the host (no engine); an empty side returns the other side"""
+    out = StepsSummaryStats()
+    _check(lib().rl_steps_summary_merge(C.byref(a), C.byref(b), C.byref(out)))
+    return out
 
 
 class PpoConfig(C.Structure):

@@ -16,6 +16,8 @@
 //   train_parallel's period loop and its metric names   src/simulation/train.rs:68-186
 #pragma once
 #include <chrono>
+#include <cmath>
+#include <cstdio>
 #include <cstdint>
 #include <cstring>
 #include <map>
@@ -402,6 +404,103 @@ class DeviceHistory {
  private:
   rl_traj *h_ = nullptr;
   uint64_t n_, T_;
+};
+
+// ---------------------------------------------------------------- step statistics (src/simulation/summary.rs)
+// OnlineMeanVariance<f64> (src/utils/stats.rs:11-15,93-118): population variance; no value while empty
+struct MeanVariance {
+  rl_mean_variance s{};
+  uint64_t count() const { return s.count; }
+  std::optional<double> mean() const { return s.count ? std::optional<double>(s.mean) : std::nullopt; }
+  std::optional<double> variance() const {
+    return s.count ? std::optional<double>(s.squared_residual_sum / (double)s.count) : std::nullopt;
+  }
+  std::optional<double> stddev() const {
+    const auto v = variance();
+    return v ? std::optional<double>(std::sqrt(*v)) : std::nullopt;
+  }
+  // `impl Display` (stats.rs:28-46) with `{:.precision}`: "(μ = m; σ = s; n = c)", "-" for a missing value
+  std::string display(int precision) const {
+    auto num = [precision](const std::optional<double> &v) {
+      if (!v) return std::string("-");
+      char buf[64];
+      std::snprintf(buf, sizeof buf, "%.*f", precision, *v);
+      return std::string(buf);
+    };
+    return "(\u03bc = " + num(mean()) + "; \u03c3 = " + num(stddev()) + "; n = " + std::to_string(count()) + ")";
+  }
+};
+
+// StepsSummary<Reward> (summary.rs:11-18): statistics of the step rewards, episode rewards and episode lengths
+struct StepsSummary {
+  MeanVariance step_reward, episode_reward, episode_length;
+  StepsSummary() = default;
+  explicit StepsSummary(const rl_steps_summary &s) {
+    step_reward.s = s.step_reward;
+    episode_reward.s = s.episode_reward;
+    episode_length.s = s.episode_length;
+  }
+  rl_steps_summary raw() const { return rl_steps_summary{step_reward.s, episode_reward.s, episode_length.s}; }
+  uint64_t num_steps() const { return step_reward.count(); }
+  uint64_t num_episodes() const { return episode_length.count(); }
+  // `impl Add` (summary.rs; stats.rs:184-209): ranks or periods combined; an empty side returns the other side
+  StepsSummary operator+(const StepsSummary &o) const {
+    const rl_steps_summary a = raw(), b = o.raw();
+    rl_steps_summary r{};
+    check(rl_steps_summary_merge(&a, &b, &r));
+    return StepsSummary(r);
+  }
+  // `impl Display` (summary.rs:37-52), as examples/cartpole-trpo.rs:92 prints it with {:.3}
+  std::string display(int precision) const {
+    return "step_feedback: " + step_reward.display(precision) + "\nepisode_feedback: " +
+           episode_reward.display(precision) + "\nepisode_length: " + episode_length.display(precision);
+  }
+  // train.rs:160-175 under the "sim" scope: ep/fbk/reward/{mean,stddev}, ep/length_{mean,stddev} (when an episode
+  // ended), ep/count, step/fbk/reward/{mean,stddev} (RewardSummary::log, feedback/reward.rs:130-143), step/count
+  void log(StatsLogger &sim) const {
+    ScopedLogger ep(sim, "ep");
+    if (num_episodes() > 0) {
+      ep.log_scalar("fbk/reward/mean", *episode_reward.mean());
+      ep.log_scalar("fbk/reward/stddev", *episode_reward.stddev());
+      ep.log_scalar("length_mean", *episode_length.mean());
+      ep.log_scalar("length_stddev", *episode_length.stddev());
+    }
+    ep.log_counter_increment("count", num_episodes());
+    ScopedLogger step(sim, "step");
+    if (num_steps() > 0) {
+      step.log_scalar("fbk/reward/mean", *step_reward.mean());
+      step.log_scalar("fbk/reward/stddev", *step_reward.stddev());
+    }
+    step.log_counter_increment("count", num_steps());
+  }
+};
+
+// One OnlineStepsSummary per lane (summary.rs:166-214) kept on the device, plus the completed StepsSummary of everything
+// pushed since the last clear (rl_summary_*).  Lanes persist across pushes: an episode is counted where it ends.
+class StepsSummaryLanes {
+ public:
+  StepsSummaryLanes(Engine &eng, uint64_t n_lanes) : eng_(eng) {
+    check(rl_summary_create(eng.handle(), n_lanes, &h_), eng.handle());
+  }
+  ~StepsSummaryLanes() { rl_summary_destroy(h_); }
+  StepsSummaryLanes(const StepsSummaryLanes &) = delete;
+  StepsSummaryLanes &operator=(const StepsSummaryLanes &) = delete;
+  rl_summary *handle() const { return h_; }
+  void push(const DeviceHistory &history) { check(rl_summary_push(h_, history.handle()), eng_.handle()); }
+  void push_dqn(const rl_dqn *dqn) { check(rl_summary_push_dqn(h_, dqn), eng_.handle()); }
+  StepsSummary read() const {
+    rl_steps_summary s{};
+    check(rl_summary_read(h_, &s), eng_.handle());
+    return StepsSummary(s);
+  }
+  // a new period (the episodes in progress are kept); forget = true also drops them (after an env reset)
+  void clear(bool forget_episodes_in_progress = false) {
+    check(rl_summary_clear(h_, forget_episodes_in_progress ? 1 : 0), eng_.handle());
+  }
+
+ private:
+  Engine &eng_;
+  rl_summary *h_ = nullptr;
 };
 
 // ---------------------------------------------------------------- policies and critics
@@ -815,6 +914,19 @@ class DqnAgent {
     sim.log_counter_increment("step/count", st.steps);           // train.rs:175
     sim.log_counter_increment("ep/count", st.episodes_ended);    // train.rs:171
   }
+  // the same collection with the period's StepsSummary (train.rs:160-175) from the device: pushes the collection into
+  // `summary`, logs the full set and clears the completed statistics (the episodes in progress carry over)
+  void collect(StatsLogger &logger, StepsSummaryLanes &summary) {
+    const Bound b = min_update_size();
+    const uint64_t horizon = (b.min_steps + n_lanes_ - 1) / n_lanes_;
+    check(rl_dqn_collect(dqn_, horizon, nullptr), eng_.handle());
+    summary.push_dqn(dqn_);
+    const StepsSummary s = summary.read();
+    summary.clear();
+    LogGroup group(logger);
+    ScopedLogger sim(group, "sim");
+    s.log(sim);
+  }
   void batch_update(StatsLogger &logger) {  // dqn.rs:263-337
     logger.log_scalar("exploration_rate", exploration_rate(ActorMode::Training));  // :268-272
     rl_dqn_update_stats st{};
@@ -894,6 +1006,31 @@ inline void train_batched(ActorCriticAgent &agent, EnvLanes &env, DeviceHistory 
       if (episodes > 0) sim.log_scalar("ep/length_mean", (double)history.num_steps() / (double)episodes);
       sim.log_counter_increment("ep/count", episodes);                 // train.rs:171
       sim.log_counter_increment("step/count", history.num_steps());    // train.rs:175
+      sim.log_duration("time", std::chrono::duration<double>(std::chrono::steady_clock::now() - collect_start).count());
+    }
+    const auto update_start = std::chrono::steady_clock::now();
+    agent.batch_update(history, logger);
+    ScopedLogger up(logger, "agent_update");
+    up.log_duration("time", std::chrono::duration<double>(std::chrono::steady_clock::now() - update_start).count());
+    up.log_counter_increment("count", 1);  // train.rs:182-184
+  }
+}
+
+// The same loop with the period's StepsSummary computed on the device: `summary` (one lane per env lane) takes every
+// collection, the full set of train.rs:160-175 is logged with the reference's definitions, and the completed
+// statistics are cleared for the next period while the episodes in progress carry over (lanes persist).
+inline void train_batched(ActorCriticAgent &agent, EnvLanes &env, DeviceHistory &history, uint64_t num_periods,
+                          StatsLogger &logger, StepsSummaryLanes &summary) {
+  for (uint64_t period = 0; period < num_periods; ++period) {
+    const auto collect_start = std::chrono::steady_clock::now();
+    agent.collect(env, history);
+    summary.push(history);
+    const StepsSummary s = summary.read();  // (synchronises)
+    summary.clear();
+    {
+      LogGroup group(logger);
+      ScopedLogger sim(group, "sim");
+      s.log(sim);
       sim.log_duration("time", std::chrono::duration<double>(std::chrono::steady_clock::now() - collect_start).count());
     }
     const auto update_start = std::chrono::steady_clock::now();
