@@ -1,6 +1,4 @@
 // abi_update.hip — extern "C" entry points of include/relearn_hip.h, part: policy / critic updates (TRPO, PPO, REINFORCE, value fitting) (host side only; kernels live in kernels_*.hip).
-#include <chrono>
-
 #include "abi_internal.hpp"
 
 extern "C" {
@@ -603,34 +601,19 @@ static void actor_critic_begin(rl_mlp *policy, rl_mlp *critic, rl_adam *critic_o
     // waiting for the HOST (measured: profiles/r04_overlap_trace_8192.csv, the policy chain starts when the critic
     // chain is nearly done).  So: a few critic steps to give the device something to do, the TRPO chain's head, the
     // rest of the critic chain, and only then the TRPO chain's read-backs.
-    uint64_t K0 = K < 6 ? K : 6;
-    // (A/B on one rank only — the ranks of a job must enqueue their collectives in one order: K = the whole critic chain
-    // first, round 4's order)
-    if (const char *k0 = e->n_ranks == 1 ? std::getenv("RELEARN_CRITIC_HEAD_STEPS") : nullptr) {
-      const long long v = std::atoll(k0);
-      K0 = v < 0 ? 0 : ((uint64_t)v > K ? K : (uint64_t)v);
-    }
-    static const bool marks = std::getenv("RELEARN_HOST_MARKS") != nullptr;  // debugging aid: host time of each phase
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = marks ? now() : 0.0;
+    const uint64_t K0 = K < 6 ? K : 6;
     {
       AuxChain aux(traj);
       values_opt_targets(critic, traj, ccfg);
       critic_enqueue_steps(critic, critic_opt, traj, K0);
     }
-    const double t1 = marks ? now() : 0.0;
     const TrpoProgress pr = trpo_update_head(policy, traj, pcfg);
-    const double t2 = marks ? now() : 0.0;
     {
       AuxChain aux(traj);
       critic_enqueue_steps(critic, critic_opt, traj, K, K0);
     }
     RL_HIP_CHECK(hipEventRecord(e->ev_join, e->aux_stream));
-    const double t3 = marks ? now() : 0.0;
     trpo_update_tail(policy, traj, pcfg, pr, pstats);  // (its read-backs wait for the main stream only)
-    if (marks)
-      std::fprintf(stderr, "relearn_hip host marks (us): critic head %.0f, trpo head %.0f, critic rest %.0f, trpo tail %.0f\n",
-                   t1 - t0, t2 - t1, t3 - t2, now() - t3);
   } catch (...) {
     (void)hipStreamSynchronize(e->aux_stream);  // nothing of this update may still be running when the error returns
     (void)hipStreamSynchronize(e->main_stream);

@@ -48,7 +48,7 @@ constexpr int NT = 4;     // 32-unit hidden tiles (H = 128)
 // younger wave ran the rest alone, with nothing to overlap its matrix instructions with.  An older wave now plays
 // SHARE_OLD virtual waves, a younger one SHARE_YOUNG; 5 : 3 lets both finish within 8 us of each other at the headline
 // size and keeps the tile counts integral at every power-of-two lane count (9:7, 12:7, 7:4, 16:9, 9:5, 11:6, 2:1, 7:3, 3:1
-// measured: none better; profiles/r06_critic_step_timeline.txt).  RL_CRITIC_SHARES=a:b overrides at run time.
+// measured: none better; profiles/r06_critic_step_timeline.txt).
 constexpr uint32_t SHARE_OLD = 5, SHARE_YOUNG = 3;
 constexpr int COLS = 19;  // piece columns of the backward: pcol(k) + p, k = input feature (5 = bias), p = piece; the three
                           // pieces of a feature stay inside one 16-lane row (column 15 is unused), so the flush adds them
@@ -123,71 +123,6 @@ __device__ __forceinline__ float row_sum16v(const float *row) {
   const float a0 = ((q0.x + q1.x) + q2.x) + q3.x, a1 = ((q0.y + q1.y) + q2.y) + q3.y;
   const float a2 = ((q0.z + q1.z) + q2.z) + q3.z, a3 = ((q0.w + q1.w) + q2.w) + q3.w;
   return (a0 + a1) + (a2 + a3);
-}
-
-// Sums over the 32 unit lanes of a half WITHOUT LDS (round 5).  An accumulator tile has the hidden unit on the lane and
-// the sample in the registers; the output layer needs, for each of the 16 rows, the sum over the half's 32 lanes.  Through
-// LDS that is a transpose: 8 ds_write2 + 4 ds_read_b128 per tile, and an LDS instruction holds the SIMD's issue port for
-// ~18 cycles (profiles/r03_slot_cost.txt).  Here the rows are folded across the lanes by a halving butterfly in registers:
-//   level 1  partner lane ^ 8 (row_ror:8): lanes with bit 3 clear keep rows 0..7, the others rows 8..15 — one
-//            v_add_f32_dpp per row and lane group, the groups separated by the instruction's bank mask (16 issues -> 8 rows)
-//   level 2  partner lane ^ 7 (row_half_mirror; it preserves bit 3): groups by bit 2, again a bank mask (8 issues -> 4)
-//   level 3  partner lane ^ 2 (quad_perm), groups by bit 1: inside a bank, so two sums and a select (6 -> 2 rows)
-//   level 4  partner lane ^ 1, groups by bit 0 (3 -> 1 row)
-//   level 5  the other 16-lane row of the half (v_permlane16_swap, 3)
-// after which lane L of a half holds the half-wide sum of ITS row L & 15 (36 vector instructions, no memory).  The sums
-// reach the sample-owning lanes through one ds_bpermute_b32 (row_sums_to_samples).  Every level adds each pair in the
-// same order on both partners, so the result does not depend on which lane ends up holding it.
-// The DPP instructions are inline asm (the bank-masked second write into the same destination cannot be expressed with
-// the builtins); a DPP read of a register needs two wait states after the vector instruction that wrote it, which the
-// compiler does not track into asm statements: every statement starts with s_nop 1.
-__device__ __forceinline__ float fold_rows16(const float (&v)[16], int lane) {
-  float a[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc"
-        : "=&v"(a[i])
-        : "v"(v[i]), "v"(v[i + 8]));
-  float b[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_f32_dpp %0, %2, %2 row_half_mirror row_mask:0xf bank_mask:0xa"
-        : "=&v"(b[i])
-        : "v"(a[i]), "v"(a[i + 4]));
-  const bool bit1 = (lane & 2) != 0, bit0 = (lane & 1) != 0;
-  float c[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    float lo, hi;
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %3, %3 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
-        : "=&v"(lo), "=&v"(hi)
-        : "v"(b[i]), "v"(b[i + 2]));
-    c[i] = bit1 ? hi : lo;
-  }
-  float lo, hi;
-  asm("s_nop 1\n\t"
-      "v_add_f32_dpp %0, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %1, %3, %3 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
-      : "=&v"(lo), "=&v"(hi)
-      : "v"(c[0]), "v"(c[1]));
-  float d = bit0 ? hi : lo;
-  // the two 16-lane rows of the half: the instruction swaps the odd rows of its first operand with the even rows of its
-  // second (fed one value twice: the first then holds the even rows' values everywhere, the second the odd rows')
-  float e = d;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(d), "+v"(e));
-  return d + e;
-}
-// byte address (for ds_bpermute_b32) of the lane that holds, after fold_rows16, the sum of sample n's row: the half that
-// owns the sample (accumulator rows of half h are the samples with bit 2 == h) and its row index there
-__device__ __forceinline__ int row_sum_source(int n) { return 4 * (32 * ((n >> 2) & 1) + ((n & 3) | ((n >> 3) << 2))); }
-__device__ __forceinline__ float row_sums_to_samples(float folded, int src_addr) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_addr, __builtin_bit_cast(int, folded)));
 }
 
 // ---- tile operands through buffer loads: a raw buffer resource over a device array (loads past `bytes` return 0), a
@@ -642,16 +577,8 @@ __device__ __forceinline__ void backward(const Frag (&ga)[NT][2], const Frag (&u
 __device__ __forceinline__ void flush(f32x16 (&dm)[NT], double *acc64, int stride, int n, int hf, bool first = false) {
   const bool owner = (n < 15 && (n % 3) == 0) || n == 16;
   const int k = n == 16 ? 5 : n / 3;
-  // -DRL_FLUSH_ADD_DPP (A/B build, round 6): the row shifts ride on the additions themselves (v_add_f32_dpp; the compiler
-  // keeps a v_mov_b32_dpp per shift when they are written with the builtin — 128 more vector instructions per flush, a
-  // quarter of it).  Inline asm, so the matrix instructions' results get their wait states by hand (no interlock, and the
-  // hazard recogniser does not look into asm): one statement that names all accumulator tiles and idles 20 cycles comes
-  // first, every addition after it in program order through its operand.  Measured: the flush of a wave goes from 1.94
-  // to 1.75 us (profiles/r06_critic_step_timeline.txt), the critic chain per step stays where it was at 4,096 / 8,192 /
-  // 65,536 lanes (three runs each on one box, to the microsecond) — the default keeps the compiler-scheduled form.
-#ifdef RL_FLUSH_ADD_DPP
-  asm volatile("s_nop 15\n\ts_nop 3" : "+v"(dm[0]), "+v"(dm[1]), "+v"(dm[2]), "+v"(dm[3]));
-#endif
+  // (the shifts are v_mov_b32_dpp; riding them on the additions as inline-asm v_add_f32_dpp was measured in round 6 —
+  // the flush of a wave 1.94 -> 1.75 us, the critic chain per step unchanged — and removed: DESIGN 18)
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     float tot[16];
@@ -659,21 +586,12 @@ __device__ __forceinline__ void flush(f32x16 (&dm)[NT], double *acc64, int strid
     for (int r = 0; r < 16; ++r) {
       // row_shl:1 / row_shl:2: lane i reads lane i + 1 / i + 2 of its 16-lane row (0 past the end of the row);
       // tot = (v + v1) + v2 in this order (float addition commutes bit for bit: the shifted operand is source 0)
-#ifdef RL_FLUSH_ADD_DPP
-      float sum;
-      asm("v_add_f32_dpp %0, %1, %1 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-          "v_add_f32_dpp %0, %1, %0 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-          : "=&v"(sum)
-          : "v"(dm[t][r]));
-      tot[r] = sum;
-#else  // (default: the shifts as v_mov_b32_dpp)
       const float v = dm[t][r];
       const float v1 = __builtin_bit_cast(
           float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xf, 0xf, true));
       const float v2 = __builtin_bit_cast(
           float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x102, 0xf, 0xf, true));
       tot[r] = (v + v1) + v2;
-#endif
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) dm[t][r] = 0.0f;

@@ -17,10 +17,7 @@
 // loses here: 0.259 against 0.219 ms per step; this kernel has one |pre| chain to replace, not a second layer-1 product
 // with its LDS-resident operands, and 16 more matrix instructions per tile push it against the matrix pipe.)
 // Algorithmic flops per sample: 3 x (2*5*128 + 2*128) = 4608 (forward + 2 x backward of the 5-128-1 MLP).
-#include <algorithm>
-#include <cstdio>
 #include <type_traits>
-#include <vector>
 
 #include "bf16_tile.hpp"
 #include "device_fns.hpp"
@@ -36,24 +33,7 @@ using bt::Frag;
 constexpr int CRITIC_WAVES = 8;  // waves per workgroup, one workgroup per CU (two waves per SIMD: the
                                                // tile state — 64 accumulators of each pass, 48 weight-piece registers —
                                                // does not fit three)
-#ifndef RL_C_FLUSH
-#define RL_C_FLUSH 64
-#endif
-constexpr int C_FLUSH = RL_C_FLUSH;                     // f32 -> f64 flush period in tiles (2048 samples per accumulator: the accumulated error stays below a 128-sample f32 fma chain's, scripts/probe/mfma_bf16_mask.hip)
-
-// -DRL_CRITIC_TIMESTAMPS (a timing build, scripts/build_variant.sh): wave 0 of every workgroup records the constant
-// 100 MHz clock at seven points of the launch; the launcher prints the averages over the workgroups (round 6: where the
-// ~7 us a launch costs beyond its tiles go)
-#ifdef RL_CRITIC_TIMESTAMPS
-__device__ uint64_t g_critic_ts[1024 * 8];
-__device__ uint64_t g_critic_wave_end[1024 * 8];  // when each wave of a workgroup has finished its tiles
-#define RL_TS(k)                                                                                   \
-  do {                                                                                             \
-    if (threadIdx.x == 0) g_critic_ts[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime();    \
-  } while (0)
-#else
-#define RL_TS(k)
-#endif
+constexpr int C_FLUSH = 64;  // f32 -> f64 flush period in tiles (2048 samples per accumulator: the accumulated error stays below a 128-sample f32 fma chain's, scripts/probe/mfma_bf16_mask.hip)
 
 // CH = 1: the critic step (above).  CH = 2 (round 6): the DQN gradient — mean((Q(s)[a] - target)^2) of the 5-128-2
 // action-value MLP, dqn.rs:316-326 — as TWO critic steps side by side: the loss reaches the hidden layer through row a_s
@@ -71,9 +51,7 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
                        uint32_t share_old, uint32_t share_young) {
   constexpr int D = 5, H = 128, NT = bt::NT;
   constexpr int IMG = H * 7 + 2;  // per hidden unit: M[0..5] (slot 6 unused); then db2, loss
-#ifndef RL_CRITIC_Y_IN_REGISTERS
   __shared__ __attribute__((aligned(16))) float Ysh[CRITIC_WAVES][32][bt::YROW];
-#endif
   __shared__ double Acc[CRITIC_WAVES][IMG];  // f64 level of the two-level accumulation, one image per wave
 
   const int lane = threadIdx.x & 63;
@@ -85,7 +63,6 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
   const size_t B = (size_t)tr.T * tr.n;
   const size_t plane = (size_t)(tr.T + 1) * tr.n;
   double *acc64 = Acc[wave];
-  RL_TS(0);
   // (the wave's f64 image is not zeroed: its first flush stores — bt::flush — and every wave flushes at least once)
   bool flushed = false;
 
@@ -127,7 +104,6 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
                                          // of every sum over samples here
   bt::wave_lds_fence();
 
-  RL_TS(1);  // (after the weights have arrived: the cross-lane sums above wait for them)
   Frag selb[2];  // piece-column selection (B operand of the routing product)
   bt::sel_frags(lane, selb);
   // Tiles: the full ones in the loop, a ragged last one (B not a multiple of 32) after it on the wave whose turn it
@@ -156,9 +132,6 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
   const uint32_t off_a = ((uint32_t)(2 * hf) * plane32 + (uint32_t)n) * 4u, off_b = off_a + plane32 * 4u;
   const uint32_t off_c = (4u * plane32 + (uint32_t)n) * 4u, off_t = (uint32_t)n * 4u;
   int since_flush = 0;
-#ifdef RL_CRITIC_Y_IN_REGISTERS
-  const int ysrc = bt::row_sum_source(n);  // where fold_rows16 leaves the output-layer sum of sample n
-#endif
   // per lane: features 2 hf, 2 hf + 1 and 4 of sample n, and its target
   struct TileOp {
     float xa, xb, xc, tgt;
@@ -202,8 +175,8 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
       bt::mask_tile(c, ga[t]);  // relu'(pre): one conversion per two values
       c = cn;
     }
-#ifndef RL_CRITIC_Y_IN_REGISTERS
-    // ---- y: transpose the 16 partial sums per lane through LDS (row = sample, column = source lane)
+    // ---- y: transpose the 16 partial sums per lane through LDS (row = sample, column = source lane; folding them in
+    // registers instead was measured in round 5 — the same time per step — and removed: DESIGN 17)
 #pragma unroll
     for (int r = 0; r < 16; ++r) Ysh[wave][(r & 3) + 8 * (r >> 2) + 4 * hf][n] = yp[r];
     bt::wave_lds_fence();
@@ -217,19 +190,6 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
     float p0, p1;
     bt::both_halves(part, p0, p1);
     const float y = 0.5f * (p0 + p1) + b2;
-#else
-    // ---- y (A/B build, -DRL_CRITIC_Y_IN_REGISTERS): the 16 partial sums per lane folded over the half's 32 unit lanes in
-    // registers (bf16_tile.hpp fold_rows16), then one permute brings sample n's sum to both lanes that own sample n.
-    // Measured in round 5: 11 LDS instructions fewer, 18 vector instructions and 21 wait states more per tile — the same
-    // 0.20 ms per step (scripts/critic_only.py, both builds on one box): the LDS round trip was not what the tile waits for.
-    const float abs_sum = bt::row_sums_to_samples(bt::fold_rows16(yp, lane), ysrc);
-    float lin = lv[0] * op.xa;  // the linear half of relu: this half's inputs of sample n, then the other half's
-    lin = __builtin_fmaf(lv[1], op.xb, lin);
-    lin = __builtin_fmaf(lv[2], hf == 0 ? op.xc : 1.0f, lin);
-    float l0, l1;
-    bt::both_halves(lin, l0, l1);
-    const float y = 0.5f * (abs_sum + (l0 + l1)) + b2;
-#endif
     const float d = y - op.tgt;
     // (CH = 2: only the samples whose action is this wave's channel count — loss, db2 and the backward alike)
     const bool mine = CH == 2 ? valid && op.act == (uint32_t)chan : valid;
@@ -243,9 +203,7 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
     Frag ub[2];
     bt::piece_frags_mfma(dy, op.xa, op.xb, op.xc, hf, selb, ub);
     bt::backward(ga, ub, dm);
-#ifndef RL_CRITIC_Y_IN_REGISTERS
     bt::wave_lds_fence();  // Ysh is rewritten by the next tile
-#endif
     if (++since_flush == C_FLUSH) {
       since_flush = 0;
       bt::flush(dm, acc64, 7, n, hf, !flushed);
@@ -264,10 +222,6 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
     // loop unrolled three times — is SLOWER, 0.237 against 0.220 ms per step, although a timing build without the loads
     // runs in 0.197: what the loads cost is issue slots, not exposed latency.)
     TileOp op_a = load_tile(wave_id), op_b = op_a;
-#ifdef RL_CRITIC_TIMESTAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RL_TS(2);  // (the first tile's operands are here)
-#endif
     for (uint32_t g = wave_id; g < n_full; g += 2 * n_waves) {
       const uint32_t g1 = g + n_waves, g2 = g1 + n_waves;
       op_b = load_tile(g1 < n_full ? g1 : g);
@@ -279,10 +233,6 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
    }
    if (tail != 0 && n_full % n_waves == wave_id) tile(std::true_type{}, load_tile(n_full));
   }
-  RL_TS(3);
-#ifdef RL_CRITIC_TIMESTAMPS
-  if (lane == 0) g_critic_wave_end[blockIdx.x * 8 + wave] = __builtin_amdgcn_s_memrealtime();
-#endif
   if (since_flush != 0 || !flushed) {  // (a wave whose tile count is a multiple of the flush period has nothing left: at
                                        // the headline size every wave owns exactly 2 x C_FLUSH tiles, and this was a
                                        // third flush of zeros; a wave without tiles still defines its image)
@@ -307,9 +257,7 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
     acc64[H * 7] = bsum;   // db2
     acc64[H * 7 + 1] = l;  // loss partial
   }
-  RL_TS(4);
   __syncthreads();
-  RL_TS(5);
   // sum the per-wave images in wave order, turn M into gradients and write the workgroup's slab row
   for (uint32_t p = threadIdx.x; p <= P; p += CRITIC_WAVES * 64) {
     auto tot = [&](int src) {
@@ -362,10 +310,6 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
     else slabB[(size_t)blockIdx.x * 4 + 0] = s;
   }
   if (threadIdx.x < 3) slabB[(size_t)blockIdx.x * 4 + 1 + threadIdx.x] = 0.0;
-#ifdef RL_CRITIC_TIMESTAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  RL_TS(6);
-#endif
 }
 
 // ---------------------------------------------------------------- launcher
@@ -384,48 +328,12 @@ bool launch_critic_step_v2(rl_traj *traj, const rl_mlp *critic, uint64_t B_total
   if (nb > cus) nb = cus;
   traj->nbC = (uint32_t)nb;
   traj->last_rows = traj->nbC;
-  // shares of the tiles for the older / the younger wave of a SIMD (the kernel says why); RL_CRITIC_SHARES=a:b overrides
-  uint32_t share_old = bt::SHARE_OLD, share_young = bt::SHARE_YOUNG;
-  if (const char *sh = std::getenv("RL_CRITIC_SHARES")) {
-    unsigned a = 0, b = 0;
-    if (std::sscanf(sh, "%u:%u", &a, &b) == 2 && a >= 1 && b >= 1 && a <= 64 && b <= 64) share_old = a, share_young = b;
-  }
   TrajDev d = traj->d;
   if (!traj->guard_next_critic) d.range = nullptr;  // (the range guard: first critic launch of the call only, engine.hpp)
   traj->guard_next_critic = false;
   hipLaunchKernelGGL(k_critic_step_mfma<1>, dim3(traj->nbC), dim3(CRITIC_WAVES * 64), 0, traj->eng->stream, d,
-                     critic->d_params, wimg, traj->slabA, traj->slabB, two_over_B, (uint32_t)critic->P, share_old,
-                     share_young);
-#ifdef RL_CRITIC_TIMESTAMPS
-  if (std::getenv("RL_CRITIC_TS_PRINT")) {
-    static int calls = 0;
-    if (++calls % 16 == 0) {  // (every 16th launch: the host synchronises for it)
-      std::vector<uint64_t> h(1024 * 8);
-      (void)hipStreamSynchronize(traj->eng->stream);
-      (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_critic_ts), h.size() * 8);
-      double sum[7] = {0}, first = 1e300, last = 0;
-      for (uint32_t b = 0; b < traj->nbC; ++b) {
-        for (int k = 0; k < 7; ++k) sum[k] += (double)(h[b * 8 + k] - h[b * 8]) * 0.01;
-        first = std::min(first, (double)h[b * 8] * 0.01);
-        last = std::max(last, (double)h[b * 8 + 6] * 0.01);
-      }
-      {
-        std::vector<uint64_t> we(1024 * 8);
-        (void)hipMemcpyFromSymbol(we.data(), HIP_SYMBOL(g_critic_wave_end), we.size() * 8);
-        double per[8] = {0};
-        for (uint32_t b = 0; b < traj->nbC; ++b)
-          for (int w = 0; w < 8; ++w) per[w] += (double)(we[b * 8 + w] - h[b * 8]) * 0.01;
-        std::fprintf(stderr, "critic ts: tiles of wave 0..7 done at (us, mean over workgroups):");
-        for (int w = 0; w < 8; ++w) std::fprintf(stderr, " %.1f", per[w] / traj->nbC);
-        std::fprintf(stderr, "\n");
-      }
-      std::fprintf(stderr, "critic ts (us from a workgroup's start, mean of %u): weights %.2f  first tile %.2f  loop end %.2f  "
-                   "flushed %.2f  barrier %.2f  end %.2f | first start to last end %.2f\n", traj->nbC,
-                   sum[1] / traj->nbC, sum[2] / traj->nbC, sum[3] / traj->nbC, sum[4] / traj->nbC, sum[5] / traj->nbC,
-                   sum[6] / traj->nbC, last - first);
-    }
-  }
-#endif
+                     critic->d_params, wimg, traj->slabA, traj->slabB, two_over_B, (uint32_t)critic->P,
+                     bt::SHARE_OLD, bt::SHARE_YOUNG);  // (shares of the tiles: the kernel says why)
   return true;
 }
 

@@ -778,10 +778,10 @@ void launch_dqn_build_all(rl_engine *eng, const ReplayDev &rp, uint32_t n_batche
 constexpr int DQN_WAVES = 4;
 constexpr int DQN_FLUSH = 16;  // f32 -> f64 flush period in tiles
 
-// TD: the workspace holds rewards instead of targets (`adv`), successor codes (`flag`) and the successor observation in
-// time slot 1 of the T = 1 layout; the one-step TD target r + gamma max_a Q(s') (0 beyond a Terminate; critics/mod.rs:
+// The kernel of the in-kernel one-step TD targets (given targets take k_critic_step_mfma<2>, kernels_critic.hip): the
+// workspace holds rewards instead of targets (`adv`), successor codes (`flag`) and the successor observation in time
+// slot 1 of the T = 1 layout; the one-step TD target r + gamma max_a Q(s') (0 beyond a Terminate; critics/mod.rs:
 // 139-150, 203-229) comes from a second forward with the same parameters (torch's no_grad target of dqn.rs:299-311).
-template <bool TD>
 __global__ void __launch_bounds__(DQN_WAVES * 64)
     k_dqn_step_bf16(TrajDev tr, const float *__restrict__ params, const uint32_t *__restrict__ wimg,
                     double *__restrict__ slabA,
@@ -849,7 +849,7 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
   int since_flush = 0;
   struct TileOp {
     float xa, xb, xc, tgt;
-    float na, nb, nc;  // (TD) the successor observation
+    float na, nb, nc;  // the successor observation
     int act, succ;
     bool valid;
   };
@@ -867,18 +867,14 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
     o.xc = o.valid ? xc : 0.0f;
     o.tgt = o.valid ? tg : 0.0f;
     o.act = o.valid ? act : 0;
-    o.na = o.nb = o.nc = 0.0f;
-    o.succ = RL_SUCC_TERMINATE;
-    if (TD) {
-      const uint32_t s1 = B32 + sc;  // time slot 1
-      const float na = tr.obs[(uint32_t)(2 * hf) * plane32 + s1], nb = tr.obs[(uint32_t)(2 * hf + 1) * plane32 + s1];
-      const float nc = tr.obs[4u * plane32 + s1];
-      const int succ = (int)tr.flag[sc];
-      o.na = o.valid ? na : 0.0f;
-      o.nb = o.valid ? nb : 0.0f;
-      o.nc = o.valid ? nc : 0.0f;
-      o.succ = o.valid ? succ : RL_SUCC_TERMINATE;
-    }
+    const uint32_t s1 = B32 + sc;  // time slot 1
+    const float na = tr.obs[(uint32_t)(2 * hf) * plane32 + s1], nb = tr.obs[(uint32_t)(2 * hf + 1) * plane32 + s1];
+    const float nc = tr.obs[4u * plane32 + s1];
+    const int succ = (int)tr.flag[sc];
+    o.na = o.valid ? na : 0.0f;
+    o.nb = o.valid ? nb : 0.0f;
+    o.nc = o.valid ? nc : 0.0f;
+    o.succ = o.valid ? succ : RL_SUCC_TERMINATE;
     return o;
   };
   auto flush_all = [&]() {
@@ -937,14 +933,11 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
       }
       bt::wave_lds_fence();  // Ysh is rewritten by the next forward
     };
-    float tgt = op.tgt;
-    if (TD) {
-      float qn[A];
-      forward(op.na, op.nb, op.nc, false, qn);
-      const float vnext = op.succ == RL_SUCC_TERMINATE ? 0.0f : (qn[1] > qn[0] ? qn[1] : qn[0]);  // amax(-1)
-      const float dn = gamma * vnext;
-      tgt = op.tgt + dn;  // (op.tgt holds the reward)
-    }
+    float qn[A];
+    forward(op.na, op.nb, op.nc, false, qn);
+    const float vnext = op.succ == RL_SUCC_TERMINATE ? 0.0f : (qn[1] > qn[0] ? qn[1] : qn[0]);  // amax(-1)
+    const float dn = gamma * vnext;
+    const float tgt = op.tgt + dn;  // (op.tgt holds the reward)
     float qv[A];
     forward(op.xa, op.xb, op.xc, true, qv);
     const float d = (op.act == 0 ? qv[0] : qv[1]) - tgt;
@@ -1015,7 +1008,7 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
 }
 
 // returns false when the kernel is not built for this shape (the caller falls back to the f32 passes)
-bool launch_dqn_step_bf16(rl_traj *mb, const rl_mlp *qnet, uint64_t B_total, bool td_in_kernel, float gamma) {
+bool launch_dqn_step_bf16(rl_traj *mb, const rl_mlp *qnet, uint64_t B_total, float gamma) {
   if (mb->d.D != 5 || qnet->hidden != 128 || qnet->out_dim != 2 || qnet->general) return false;
   if ((uint64_t)(mb->d.T + 1) * mb->d.n * 5 >= (1ull << 30)) return false;  // 32-bit element offsets in the kernel
   const uint32_t *wimg = wimg_ensure(qnet);
@@ -1027,12 +1020,8 @@ bool launch_dqn_step_bf16(rl_traj *mb, const rl_mlp *qnet, uint64_t B_total, boo
   TrajDev d = mb->d;
   if (!mb->guard_next_policy) d.range = nullptr;  // (the range guard: first step of an update only, engine.hpp)
   mb->guard_next_policy = false;
-  if (td_in_kernel)
-    hipLaunchKernelGGL(k_dqn_step_bf16<true>, dim3((uint32_t)nb), dim3(DQN_WAVES * 64), 0, mb->eng->stream, d,
-                       qnet->d_params, wimg, mb->slabA, mb->slabB, 2.0f / (float)B_total, (uint32_t)qnet->P, gamma);
-  else
-    hipLaunchKernelGGL(k_dqn_step_bf16<false>, dim3((uint32_t)nb), dim3(DQN_WAVES * 64), 0, mb->eng->stream, d,
-                       qnet->d_params, wimg, mb->slabA, mb->slabB, 2.0f / (float)B_total, (uint32_t)qnet->P, gamma);
+  hipLaunchKernelGGL(k_dqn_step_bf16, dim3((uint32_t)nb), dim3(DQN_WAVES * 64), 0, mb->eng->stream, d, qnet->d_params,
+                     wimg, mb->slabA, mb->slabB, 2.0f / (float)B_total, (uint32_t)qnet->P, gamma);
   RL_HIP_CHECK(hipGetLastError());
   return true;
 }

@@ -384,10 +384,6 @@ __global__ void __launch_bounds__(GWAVES * 64)
   float *tbias = bias + NL * 32 * GW;                                                               // (JVP) of the tangent
   constexpr bool BWD = MODE != PASS_EVAL;
   if (skip != nullptr && *skip != 0) return;
-#ifdef GM_FIXED_RELU
-  g.act = RL_ACT_RELU;
-  g.out_act = RL_ACT_IDENTITY;
-#endif
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m = lane & 31, kb = lane >> 5;
   auto Kof = [&](int l) { return l == 0 ? g.in_dim : g.width[l - 1]; };
@@ -1200,8 +1196,7 @@ bool launch_gen_mfma(rl_traj *t, const rl_mlp *m, int mode, const float *d_tange
   const int NL = (int)m->n_hidden, gw = gm_width_tiles(m);
   const float inv_B = (mode == RL_GEN_CRITIC ? 2.0f : 1.0f) / (float)B_total;
   gen_ensure(t, m, 0, false, true);  // the P-sized vectors of the update workspace follow the module
-  static const bool one_wave = getenv("RELEARN_GEN_ONE_WAVE") != nullptr;  // measurement override: the one-wave kernel
-  if (gw == 2 && mode != PASS_EVAL && gp_lds_bytes(NL, GP_PAIRS, mode == PASS_JVP) <= 160 * 1024 && !one_wave) {
+  if (gw == 2 && mode != PASS_EVAL && gp_lds_bytes(NL, GP_PAIRS, mode == PASS_JVP) <= 160 * 1024) {
     // a tile per pair of waves, two waves per SIMD
     uint64_t nwg = (n_tiles + GP_PAIRS - 1) / GP_PAIRS;
     if (nwg > cus) nwg = cus;
@@ -1213,8 +1208,7 @@ bool launch_gen_mfma(rl_traj *t, const rl_mlp *m, int mode, const float *d_tange
     else gp_launch_nl<PASS_JVP>(t, g, NL, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
     return true;
   }
-  // (only reachable for a pass the pair kernel was admitted for when RELEARN_GEN_ONE_WAVE forces this kernel: the caller
-  // then takes the per-layer path)
+  // (the one-wave kernel's image must fit the LDS: otherwise the caller takes the per-layer path)
   if (gm_lds_bytes(gw, NL, mode == PASS_JVP) > 160 * 1024) return false;
   uint64_t nwg = (n_tiles + GWAVES - 1) / GWAVES;
   if (nwg > cus) nwg = cus;

@@ -1,10 +1,9 @@
 // kernels_mfma.hip — the fused full-batch policy passes (gradient, Fisher-vector product, evaluation) of the 5-128-2
 // categorical policy on the bf16 matrix pipe.  The tile machinery is bf16_tile.hpp; the critic step (one output) is
-// kernels_critic.hip, the DQN gradient (two outputs, two backward channels) is k_dqn_step_bf16 in kernels_dqn.hip.
+// kernels_critic.hip, which also holds the DQN gradient (two outputs, k_critic_step_mfma<2>); with in-kernel TD targets
+// the DQN gradient is k_dqn_step_bf16 in kernels_dqn.hip.
 // (Rounds 1-2 ran these passes on the f32 MFMA with the backward on the VALU; that kernel is gone — its last user was
 // the DQN gradient.)
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "bf16_tile.hpp"
@@ -445,17 +444,12 @@ bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float
   dim3 g(traj->nbV2), b(V2_WAVES * 64);
   hipStream_t s = traj->eng->stream;
   uint32_t P = (uint32_t)policy->P;
-  uint32_t share_old = bt::SHARE_OLD, share_young = bt::SHARE_YOUNG;  // (RL_CRITIC_SHARES=a:b: A/B runs)
-  if (const char *sh = std::getenv("RL_CRITIC_SHARES")) {
-    unsigned a = 0, b2 = 0;
-    if (std::sscanf(sh, "%u:%u", &a, &b2) == 2 && a >= 1 && b2 >= 1 && a <= 64 && b2 <= 64) share_old = a, share_young = b2;
-  }
   TrajDev d = traj->d;
   if (!traj->guard_next_policy) d.range = nullptr;  // (the range guard: first policy launch of the call only, engine.hpp)
   traj->guard_next_policy = false;
 #define BLAUNCH(MM)                                                                                                  \
   hipLaunchKernelGGL((k_policy_bf16<MM, V2_WAVES>), g, b, 0, s, d, policy->d_params, wimg, d_tangent, traj->lp0,       \
-                     traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo, clip_hi, share_old, share_young)
+                     traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo, clip_hi, bt::SHARE_OLD, bt::SHARE_YOUNG)
   if (mode == PASS_INIT) BLAUNCH(PASS_INIT);
   else if (mode == PASS_JVP) BLAUNCH(PASS_JVP);
   else if (mode == PASS_PPO) BLAUNCH(PASS_PPO);

@@ -2,8 +2,6 @@
 //
 // Layout: one env per lane, struct-of-arrays state in HBM, time-major trajectory planes so that every
 // global access of a wavefront is one contiguous 256-B (f32) / 64-B (u8) segment.
-#include <cstdlib>
-
 #include "bf16_tile.hpp"
 #include "device_fns.hpp"
 #include "kernels.hpp"
@@ -470,7 +468,6 @@ void launch_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   const uint64_t simds = 4ull * (uint64_t)env->eng->prop.multiProcessorCount, n = env->cfg.n_lanes;
   int G = 1;
   while (G < 16 && n * (uint64_t)(2 * G) <= (2 * G >= 8 ? 1 : 2) * simds * 64) G *= 2;
-  if (const char *o = std::getenv("RELEARN_ROLLOUT_G")) G = std::atoi(o);  // measurement override
 #define ROLL(DD)                                                   \
   switch (G) {                                                     \
     case 16: launch_rollout_g<DD, 16>(env, policy, traj); break;   \

@@ -771,17 +771,11 @@ void launch_mlp_backward(rl_traj *traj, const rl_mlp *mlp, const int32_t *d_skip
 }
 
 // columns of the reduced vector per workgroup of the slab reductions: 16 (57 - 65 workgroups pull the slab, a lane has
-// four loads in flight; round 6: 6.4 -> 4.5 us per reduce + Adam launch, scripts/critic_only.py) — or 64, the form of
-// rounds 1-5, with RL_REDUCE_WIDTH=64 (A/B runs).  The mailbox exchange keeps the wide form: its chunks are 64 columns.
+// four loads in flight; round 6: 6.4 -> 4.5 us per reduce + Adam launch against 64, the form of rounds 1-5,
+// scripts/critic_only.py).  The mailbox exchange keeps the wide form: its chunks are 64 columns.
 // (vectors of more than 2,048 entries — the recurrent chains, wide general MLPs — are bandwidth-, not latency-bound and
 // keep the wide form)
-static int reduce_width(uint32_t P) {
-  static const int w = [] {
-    const char *e = std::getenv("RL_REDUCE_WIDTH");
-    return e != nullptr && std::atoi(e) == 64 ? 64 : 16;
-  }();
-  return P + 4 > 2048 ? 64 : w;
-}
+static int reduce_width(uint32_t P) { return P + 4 > 2048 ? 64 : 16; }
 
 void launch_reduce(rl_traj *traj, uint32_t P, bool useA, bool useB, uint32_t rowsA, uint32_t rowsB) {
   ProfScope ps(traj->eng, RL_K_REDUCE);

@@ -71,7 +71,7 @@ out.update({
     "kernel_launches_per_update": {k: v[1] / updates for k, v in prof.items() if v[1]},
 })
 # ---- roofline of the dominant kernel, as bench.py reports it for config 4: the DQN gradient — k_critic_step_mfma<2>
-# (two critic-step channels per SIMD, round 6; k_dqn_step_bf16 with RL_DQN_SINGLE_WAVE=1 or in-kernel TD targets) —, one
+# (two critic-step channels per SIMD, round 6; k_dqn_step_bf16 for in-kernel TD targets) —, one
 # launch = forward + loss + backward of the 5-128-2 action-value network over a minibatch.  Algorithmic: 3 x 2 x (5*128 + 128*2) = 5,376
 # flop and 25 B (five f32 features, the action, the target) per sample.
 import roofline_util as ru  # noqa: E402
@@ -81,8 +81,7 @@ if k_n:
     us = 1e3 * k_ms / k_n
     flop, alg_bytes = 5376.0 * mb, 25.0 * mb
     kernels, src = ru.pmc_kernels("r06_pmc_dqn_summary.json")
-    single = os.environ.get("RL_DQN_SINGLE_WAVE") is not None or os.environ.get("DQN_TD") == "1"
-    kname = "k_dqn_step_bf16" if single else "k_critic_step_mfma<2>"
+    kname = "k_dqn_step_bf16" if os.environ.get("DQN_TD") == "1" else "k_critic_step_mfma<2>"
     traffic, _ = ru.traffic_of(kernels if src["applies"] else {}, {kname: 1.0})
     ach = flop / (us * 1e-6) / 1e12
     out["roofline"] = {

@@ -19,4 +19,4 @@ eng.timer_begin()
 for _ in range(reps):
     ra.rollout(env, pol, traj)
 ms = eng.timer_end() / reps
-print("rollout %d lanes x 128 steps: %.3f ms (G=%s)" % (n, ms, os.environ.get("RELEARN_ROLLOUT_G", "auto")))
+print("rollout %d lanes x 128 steps: %.3f ms" % (n, ms))
