@@ -444,6 +444,54 @@ int32_t rl_adam_destroy(rl_adam *opt);
 /* one optimizer step from a host gradient (parity tests) */
 int32_t rl_adam_step_host(rl_adam *opt, const float *grad);
 
+/* The other first-order rules.  Every first-order update of the reference is generic over its optimiser configuration
+ * (`optimizer_config: OC` in ValuesOptConfig, PpoConfig, ReinforceConfig, DqnConfig), and OC is one of the four COptimizer
+ * configurations of src/torch/optimizers/coptimizer.rs: SgdConfig (:49-87), RmsPropConfig (:89-132), AdamConfig
+ * (:134-168), AdamWConfig (:170-205).  The handle type stays rl_adam: an optimiser built here with any rule is passed
+ * unchanged wherever the prototypes take `rl_adam *` (critic, values-opt, actor-critic, PPO, REINFORCE and DQN updates),
+ * and is freed by the destroy call above.  Arithmetic is f32 in the operation order of libtorch 1.12's C++ optimisers
+ * (what tch 0.8 binds; the reference passes its fields straight through, coptimizer.rs:76-86,120-131,158-167,195-204);
+ * with g the gradient entry, p the parameter, k the 1-based count of applied steps:
+ *   SGD      wd != 0: g = g + wd*p;  momentum != 0: buf = (k == 1) ? g : buf*momentum + (1-dampening)*g,
+ *            g = nesterov ? g + momentum*buf : buf;  p = p + (-lr)*g
+ *   RMSProp  wd != 0: g = g + wd*p;  sq = sq*alpha + ((1-alpha)*g)*g;  centered: ga = ga*alpha + (1-alpha)*g,
+ *            avg = sqrt(sq - ga*ga) + eps, otherwise avg = sqrt(sq) + eps;  momentum > 0: buf = buf*momentum + g/avg,
+ *            p = p + (-lr)*buf, otherwise p = p + (-lr)*(g/avg)
+ *   AdamW    p = p*(1 - lr*wd), then Adam's moments and step without wd*p in the gradient (eps 1e-8, amsgrad off)
+ * A refused step (range guard, failed exchange) changes nothing: parameters, every state slot and the step count stay,
+ * so SGD's first-step rule applies to the first step that IS applied.
+ * With several ranks on the peer-mailbox transport (EXPERIMENTAL, rl_comm_init_ipc above) the exchange fused into the
+ * reduction launch is built for Adam only; the other rules take the two-launch route there (reduce, stand-alone exchange,
+ * step kernel).
+ * tests/test_gpu_optimizers.py, tests/optim_ref.py. */
+enum { RL_OPTIMIZER_ADAM = 0, RL_OPTIMIZER_ADAMW = 1, RL_OPTIMIZER_SGD = 2, RL_OPTIMIZER_RMSPROP = 3 };
+typedef struct {
+  int32_t kind;               /* RL_OPTIMIZER_* */
+  int32_t nesterov;           /* SgdConfig */
+  int32_t centered;           /* RmsPropConfig */
+  int32_t reserved;           /* 0 */
+  double learning_rate, weight_decay;
+  double beta1, beta2;        /* AdamConfig, AdamWConfig */
+  double eps;                 /* Adam, AdamW (libtorch default 1e-8, not a field in the reference), RmsPropConfig */
+  double momentum, dampening; /* SgdConfig; momentum also RmsPropConfig */
+  double alpha;               /* RmsPropConfig */
+} rl_optimizer_config;
+/* the reference's Default impls: SGD lr 1e-2, momentum 0, dampening 0, wd 0, nesterov false (coptimizer.rs:64-74);
+ * RMSProp lr 1e-2, momentum 0, alpha 0.99, eps 1e-8, centered false, wd 0 (:107-118); Adam and AdamW lr 1e-3, betas
+ * 0.9 / 0.999, wd 0 (:147-156, :184-193; AdamW's 0 is the reference's default, not libtorch's 1e-2) */
+int32_t rl_optimizer_config_default(int32_t kind, rl_optimizer_config *cfg);
+/* RL_ERR_INVALID_ARGUMENT, naming the field, for what libtorch rejects: negative learning_rate, momentum, weight_decay,
+ * eps or alpha; a beta outside [0, 1); nesterov with momentum <= 0 or dampening != 0; an unknown kind.  The configuration
+ * is checked before the module is looked at.  Kind RL_OPTIMIZER_ADAM builds what the Adam create call above builds. */
+int32_t rl_optimizer_create(rl_mlp *module, const rl_optimizer_config *cfg, rl_adam **out);
+/* one optimizer step of the handle's rule from a host gradient */
+int32_t rl_optimizer_step_host(rl_adam *opt, const float *grad);
+/* state slot 0..2 of the rule -> host[0..n), n = the module's parameter count (Adam / AdamW: m, v; SGD: momentum buffer;
+ * RMSProp: square average, momentum buffer, gradient average), and the device's step count (either may be NULL; without `host`,
+ * `slot` and `n` are not looked at).  A slot the configuration does not have (it is not allocated) ->
+ * RL_ERR_INVALID_ARGUMENT. */
+int32_t rl_optimizer_state_read(rl_adam *opt, int32_t slot, float *host, uint64_t n, uint64_t *step_out);
+
 typedef struct {
   double loss_first, loss_last; /* loss before the first / last optimisation step */
   uint64_t steps;

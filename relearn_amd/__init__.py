@@ -30,6 +30,7 @@ LIMIT_NONE, LIMIT_LATENT, LIMIT_VISIBLE = 0, 1, 2
 (TRAJ_OBS, TRAJ_ACTION, TRAJ_REWARD, TRAJ_FLAG, TRAJ_TERM_OBS, TRAJ_VALUES, TRAJ_ADVANTAGES,
  TRAJ_RETURNS, TRAJ_TARGETS) = range(9)
 VALUE_TARGET_REWARD_TO_GO, VALUE_TARGET_ONE_STEP_TD = 0, 1
+OPTIMIZER_ADAM, OPTIMIZER_ADAMW, OPTIMIZER_SGD, OPTIMIZER_RMSPROP = 0, 1, 2, 3
 KERNEL_CLASSES = ["env_step", "rollout", "values", "gae", "policy_pass", "backward", "reduce", "small",
                   "critic_fwd", "allreduce", "critic_fused", "policy_fused", "policy_fvp"]
 
@@ -48,6 +49,7 @@ ABI_SYMBOLS = [
     "rl_rollout", "rl_gae",
     "rl_trpo_config_default", "rl_trpo_update", "rl_policy_gradient", "rl_policy_fvp", "rl_policy_loss_kl",
     "rl_adam_config_default", "rl_adam_create", "rl_adam_destroy", "rl_adam_step_host",
+    "rl_optimizer_config_default", "rl_optimizer_create", "rl_optimizer_step_host", "rl_optimizer_state_read",
     "rl_critic_update", "rl_critic_gradient", "rl_values_opt_config_default", "rl_values_opt_update",
     "rl_actor_critic_update", "rl_actor_critic_update_begin", "rl_actor_critic_update_finish", "rl_engine_set_serial_update",
     "rl_ppo_config_default", "rl_ppo_update", "rl_reinforce_update", "rl_reward_to_go",
@@ -101,6 +103,13 @@ class TrpoStats(C.Structure):
 class AdamConfig(C.Structure):
     _fields_ = [("learning_rate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
                 ("weight_decay", C.c_double), ("eps", C.c_double)]
+
+
+class OptimizerConfig(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("nesterov", C.c_int32), ("centered", C.c_int32), ("reserved", C.c_int32),
+                ("learning_rate", C.c_double), ("weight_decay", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("momentum", C.c_double), ("dampening", C.c_double),
+                ("alpha", C.c_double)]
 
 
 class CriticStats(C.Structure):
@@ -184,7 +193,7 @@ def _register(obj):
 @atexit.register
 def _close_all():
     objs = list(_live)
-    order = {"StepsSummary": -1, "Dqn": -1, "Adam": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "Mlp": 3, "GruMlp": 3,
+    order = {"StepsSummary": -1, "Dqn": -1, "Adam": 0, "Optimizer": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "Mlp": 3, "GruMlp": 3,
              "Engine": 4}
     for o in sorted(objs, key=lambda o: order.get(type(o).__name__, 2)):
         o.close()
@@ -731,6 +740,43 @@ class Adam(_Handle):
     def step_host(self, grad):
         g, gp = _ptr(grad, np.float32)
         _check(lib().rl_adam_step_host(self.h, gp), self.mod.eng.h)
+
+
+def optimizer_config_default(kind):
+    """the reference's Default impl of the rule's configuration (SgdConfig, RmsPropConfig, AdamConfig, AdamWConfig)"""
+    c = OptimizerConfig()
+    _check(lib().rl_optimizer_config_default(C.c_int32(kind), C.byref(c)))
+    return c
+
+
+class Optimizer(Adam):
+    """a first-order optimiser of any rule (OPTIMIZER_*): usable wherever an ``Adam`` is"""
+
+    def __init__(self, module, cfg):
+        self.mod = module
+        self.cfg = cfg
+        self.h = C.c_void_p()
+        _check(lib().rl_optimizer_create(module.h, C.byref(cfg), C.byref(self.h)), module.eng.h)
+        _register(self)
+
+    def step_host(self, grad):
+        g, gp = _ptr(grad, np.float32)
+        _check(lib().rl_optimizer_step_host(self.h, gp), self.mod.eng.h)
+
+    def state(self, slot):
+        """state slot 0..2 (Adam / AdamW: m, v; SGD: momentum buffer; RMSProp: square average, momentum buffer,
+        gradient average); raises for a slot the configuration does not have"""
+        out = np.zeros(self.mod.P, dtype=np.float32)
+        _check(lib().rl_optimizer_state_read(self.h, C.c_int32(slot), out.ctypes.data_as(C.c_void_p),
+                                             C.c_uint64(self.mod.P), None), self.mod.eng.h)
+        return out
+
+    @property
+    def step_count(self):
+        """the number of steps applied, as the device counts them"""
+        n = C.c_uint64()
+        _check(lib().rl_optimizer_state_read(self.h, C.c_int32(0), None, C.c_uint64(0), C.byref(n)), self.mod.eng.h)
+        return n.value
 
 
 def critic_update(critic, opt, traj, opt_steps=80, want_losses=False):

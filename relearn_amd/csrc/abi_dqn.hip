@@ -463,18 +463,21 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
     rl_traj *mb = q->mb;
     // With pipelined draws a sampler error can surface in a LATER chunk, after the earlier chunks' optimisation steps
     // have run: the update is all or nothing, so the network and the optimiser state are saved first and put back then
-    // (four device copies of <= 4 KB; the one-launch draw validates every minibatch before the first step).
+    // (a few device copies of <= 4 KB; the one-launch draw validates every minibatch before the first step).
     const uint64_t Pq = q->qnet->P, host_step0 = q->opt->host_step;
     // (the fused gradient kernel's range guard reports after the steps it could not vouch for have run: the same
     // all-or-nothing rule — saved, and put back when the guard fires)
     const bool fused_shape = e->kernel_variant == 0 && D == 5 && q->qnet->hidden == 128 && !q->qnet->general;
     const bool snapshot = pipelined || fused_shape;
     if (snapshot) {
-      if (!q->snap) q->snap = dalloc<float>(3 * Pq + 2);
+      // (every state slot the optimiser's rule has: none for plain SGD, three for centered RMSProp with momentum)
+      if (!q->snap) q->snap = dalloc<float>(4 * Pq + 2);
       RL_HIP_CHECK(hipMemcpyAsync(q->snap, q->qnet->d_params, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-      RL_HIP_CHECK(hipMemcpyAsync(q->snap + Pq, q->opt->d_m, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-      RL_HIP_CHECK(hipMemcpyAsync(q->snap + 2 * Pq, q->opt->d_v, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-      RL_HIP_CHECK(hipMemcpyAsync(q->snap + 3 * Pq, q->opt->d_step, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
+      for (int s = 0; s < 3; ++s)
+        if (q->opt->d_state[s])
+          RL_HIP_CHECK(hipMemcpyAsync(q->snap + (s + 1) * Pq, q->opt->d_state[s], Pq * sizeof(float),
+                                      hipMemcpyDeviceToDevice, e->stream));
+      RL_HIP_CHECK(hipMemcpyAsync(q->snap + 4 * Pq, q->opt->d_step, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
     }
     try {
       for (size_t c = 0; c < chunk_end.size(); ++c) {
@@ -532,9 +535,11 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
         if (pipelined) (void)hipStreamSynchronize(q->draw_stream);  // the later chunks' draws still advance the agent's Prng
         (void)hipMemcpyAsync(q->qnet->d_params, q->snap, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
         wimg_invalidate(q->qnet);
-        (void)hipMemcpyAsync(q->opt->d_m, q->snap + Pq, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
-        (void)hipMemcpyAsync(q->opt->d_v, q->snap + 2 * Pq, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
-        (void)hipMemcpyAsync(q->opt->d_step, q->snap + 3 * Pq, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream);
+        for (int s = 0; s < 3; ++s)
+          if (q->opt->d_state[s])
+            (void)hipMemcpyAsync(q->opt->d_state[s], q->snap + (s + 1) * Pq, Pq * sizeof(float), hipMemcpyDeviceToDevice,
+                                 e->stream);
+        (void)hipMemcpyAsync(q->opt->d_step, q->snap + 4 * Pq, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream);
         (void)hipStreamSynchronize(e->stream);
         q->opt->host_step = host_step0;
       }

@@ -293,26 +293,115 @@ int32_t rl_adam_config_default(rl_adam_config *c) {
   });
 }
 
+// SgdConfig / RmsPropConfig / AdamConfig / AdamWConfig::default (coptimizer.rs:64-74, 107-118, 147-156, 184-193)
+static void optimizer_config_default(int32_t kind, rl_optimizer_config *c) {
+  std::memset(c, 0, sizeof(*c));
+  c->kind = kind;
+  c->eps = 1e-8;  // libtorch AdamOptions / AdamWOptions default; RmsPropConfig::default
+  if (kind == RL_OPTIMIZER_ADAM || kind == RL_OPTIMIZER_ADAMW) {
+    c->learning_rate = 1e-3;
+    c->beta1 = 0.9;
+    c->beta2 = 0.999;
+  } else if (kind == RL_OPTIMIZER_SGD) {
+    c->learning_rate = 1e-2;
+  } else if (kind == RL_OPTIMIZER_RMSPROP) {
+    c->learning_rate = 1e-2;
+    c->alpha = 0.99;
+  } else {
+    throw RlError(RL_ERR_INVALID_ARGUMENT, "optimizer config: unknown kind");
+  }
+}
+
+int32_t rl_optimizer_config_default(int32_t kind, rl_optimizer_config *c) {
+  return guarded(nullptr, [&] {
+    RL_REQUIRE(c, "cfg is NULL");
+    optimizer_config_default(kind, c);
+  });
+}
+
+// what libtorch's option checks reject (torch/csrc/api/src/optim/{sgd,rmsprop,adam,adamw}.cpp of 1.12, third party); a
+// NaN fails every one of these comparisons and is rejected with them
+static void optimizer_config_check(const rl_optimizer_config &c) {
+  const int32_t k = c.kind;
+  RL_REQUIRE(k == RL_OPTIMIZER_ADAM || k == RL_OPTIMIZER_ADAMW || k == RL_OPTIMIZER_SGD || k == RL_OPTIMIZER_RMSPROP,
+             "optimizer config: unknown kind");
+  RL_REQUIRE(c.learning_rate >= 0.0, "optimizer config: invalid learning_rate (negative)");
+  RL_REQUIRE(c.weight_decay >= 0.0, "optimizer config: invalid weight_decay (negative)");
+  if (k == RL_OPTIMIZER_ADAM || k == RL_OPTIMIZER_ADAMW) {
+    RL_REQUIRE(c.eps >= 0.0, "optimizer config: invalid eps (negative)");
+    RL_REQUIRE(c.beta1 >= 0.0 && c.beta1 < 1.0, "optimizer config: invalid beta1 (outside [0, 1))");
+    RL_REQUIRE(c.beta2 >= 0.0 && c.beta2 < 1.0, "optimizer config: invalid beta2 (outside [0, 1))");
+  } else if (k == RL_OPTIMIZER_SGD) {
+    RL_REQUIRE(c.momentum >= 0.0, "optimizer config: invalid momentum (negative)");
+    RL_REQUIRE(!c.nesterov || (c.momentum > 0.0 && c.dampening == 0.0),
+               "optimizer config: nesterov requires a momentum > 0 and zero dampening");
+  } else {
+    RL_REQUIRE(c.eps >= 0.0, "optimizer config: invalid eps (negative)");
+    RL_REQUIRE(c.momentum >= 0.0, "optimizer config: invalid momentum (negative)");
+    RL_REQUIRE(c.alpha >= 0.0, "optimizer config: invalid alpha (negative)");
+  }
+}
+
+// which state slots a configuration has (kernels_update.hip opt_has_slot says the same from the step's flags)
+static bool optimizer_has_slot(const rl_optimizer_config &c, int slot) {
+  if (c.kind == RL_OPTIMIZER_ADAM || c.kind == RL_OPTIMIZER_ADAMW) return slot < 2;
+  if (c.kind == RL_OPTIMIZER_SGD) return slot == 0 && c.momentum != 0.0;
+  return slot == 0 || (slot == 1 && c.momentum > 0.0) || (slot == 2 && c.centered != 0);
+}
+
+static void optimizer_free(rl_adam *o) {
+  for (float *s : o->d_state) dfree(s);
+  dfree(o->d_step);
+  delete o;
+}
+
+static void optimizer_create(rl_mlp *module, const rl_optimizer_config &cfg, rl_adam **out) {
+  rl_engine *e = module->eng;
+  RL_HIP_CHECK(hipSetDevice(e->device));
+  rl_adam *o = new rl_adam();
+  try {
+    o->eng = e;
+    o->mod = module;
+    o->cfg = cfg;
+    o->error_epoch = e->error_epoch;
+    for (int s = 0; s < 3; ++s)
+      if (optimizer_has_slot(cfg, s)) {
+        o->d_state[s] = dalloc<float>(module->P);
+        RL_HIP_CHECK(hipMemsetAsync(o->d_state[s], 0, module->P * sizeof(float), e->stream));
+      }
+    o->d_step = dalloc<uint64_t>(1);
+    RL_HIP_CHECK(hipMemsetAsync(o->d_step, 0, sizeof(uint64_t), e->stream));
+    sync(e);
+  } catch (...) {
+    optimizer_free(o);
+    throw;
+  }
+  e->live_handles += 1;
+  *out = o;
+}
+
 int32_t rl_adam_create(rl_mlp *module, const rl_adam_config *cfg, rl_adam **out) {
   return guarded(module ? module->eng : nullptr, [&] {
     RL_REQUIRE(module && cfg && out, "NULL argument");
     *out = nullptr;
-    rl_engine *e = module->eng;
-    RL_HIP_CHECK(hipSetDevice(e->device));
-    std::unique_ptr<rl_adam> o(new rl_adam());
-    o->eng = e;
-    o->mod = module;
-    o->cfg = *cfg;
-    o->error_epoch = e->error_epoch;
-    o->d_m = dalloc<float>(module->P);
-    o->d_v = dalloc<float>(module->P);
-    o->d_step = dalloc<uint64_t>(1);
-    RL_HIP_CHECK(hipMemsetAsync(o->d_m, 0, module->P * sizeof(float), e->stream));
-    RL_HIP_CHECK(hipMemsetAsync(o->d_v, 0, module->P * sizeof(float), e->stream));
-    RL_HIP_CHECK(hipMemsetAsync(o->d_step, 0, sizeof(uint64_t), e->stream));
-    sync(e);
-    e->live_handles += 1;
-    *out = o.release();
+    rl_optimizer_config c;  // (the fields as given: this entry point has never checked them)
+    optimizer_config_default(RL_OPTIMIZER_ADAM, &c);
+    c.learning_rate = cfg->learning_rate;
+    c.beta1 = cfg->beta1;
+    c.beta2 = cfg->beta2;
+    c.weight_decay = cfg->weight_decay;
+    c.eps = cfg->eps;
+    optimizer_create(module, c, out);
+  });
+}
+
+int32_t rl_optimizer_create(rl_mlp *module, const rl_optimizer_config *cfg, rl_adam **out) {
+  return guarded(module ? module->eng : nullptr, [&] {
+    RL_REQUIRE(cfg, "cfg is NULL");
+    optimizer_config_check(*cfg);  // before the module is looked at
+    RL_REQUIRE(module && out, "NULL argument");
+    *out = nullptr;
+    optimizer_create(module, *cfg, out);
   });
 }
 
@@ -321,16 +410,13 @@ int32_t rl_adam_destroy(rl_adam *o) {
   (void)hipSetDevice(o->eng->device);
   (void)hipStreamSynchronize(o->eng->stream);
   (void)hipStreamSynchronize(o->eng->aux_stream);  // (a critic chain left in flight by rl_actor_critic_update_begin)
-  dfree(o->d_m);
-  dfree(o->d_v);
-  dfree(o->d_step);
   rl_engine *eng = o->eng;
-  delete o;
+  optimizer_free(o);
   engine_release_child(eng);
   return RL_OK;
 }
 
-int32_t rl_adam_step_host(rl_adam *o, const float *grad) {
+int32_t rl_optimizer_step_host(rl_adam *o, const float *grad) {
   return guarded(o ? o->mod->eng : nullptr, [&] {
     RL_REQUIRE(o && grad, "NULL argument");
     rl_engine *e = o->mod->eng;
@@ -344,6 +430,19 @@ int32_t rl_adam_step_host(rl_adam *o, const float *grad) {
       throw;
     }
     dfree(d_g);
+  });
+}
+
+int32_t rl_adam_step_host(rl_adam *o, const float *grad) { return rl_optimizer_step_host(o, grad); }
+
+int32_t rl_optimizer_state_read(rl_adam *o, int32_t slot, float *host, uint64_t n, uint64_t *step_out) {
+  return guarded(o ? o->eng : nullptr, [&] {
+    RL_REQUIRE(o, "NULL argument");
+    RL_REQUIRE(host == nullptr || (slot >= 0 && slot < 3 && o->d_state[slot] != nullptr),
+               "optimizer state: the rule has no such slot");
+    RL_REQUIRE(host == nullptr || n == o->mod->P, "optimizer state: n is not the module's parameter count");
+    if (host) d2h(o->eng, host, o->d_state[slot], n * sizeof(float));
+    if (step_out) d2h(o->eng, step_out, o->d_step, sizeof(uint64_t));
   });
 }
 
@@ -381,8 +480,9 @@ static void critic_enqueue_steps(rl_mlp *critic, rl_adam *opt, rl_traj *traj, ui
   // no separate all-reduce between the reduction and the (elementwise) optimiser step: one rank, or the peer-mailbox
   // transport, whose exchange runs inside the reduction launch
   const rl_engine *eng = traj->eng;
+  // (that exchange is built for Adam only: another rule on the mailbox transport reduces, exchanges and steps in turn)
   const bool mailbox = eng->ipc_active && !eng->comm && !eng->loopback && !eng->host_allreduce &&
-                       ipc_allreduce_fits(eng, critic->P + 4);
+                       ipc_allreduce_fits(eng, critic->P + 4) && opt->cfg.kind == RL_OPTIMIZER_ADAM;
   const bool fused = critic->kind == RL_MODULE_MLP && (!eng->has_collective() || mailbox);
   for (uint64_t k = first; k < opt_steps; ++k) {
     if (fused) {  // no all-reduce between the reduction and the (elementwise) optimiser step: one launch

@@ -172,7 +172,7 @@ constexpr float FWD_SCALE = 0x1p96f, FWD_UNSCALE = 0x1p-96f;  // ("relu' in half
 // ---- the weight image (round 6).  Every fused launch used to rebuild its weight-piece fragments from the flat parameter
 // vector in every wave: 20 strided loads and ~330 vector instructions (twelve three-piece splits and their packing) per
 // wave before the first tile — a third of a wave's instructions when a rank holds 8,192 lanes (16 tiles per wave), most
-// of them for a DQN minibatch (3 tiles per wave).  The kernels that WRITE the parameters (k_reduce_adam, k_adam_step,
+// of them for a DQN minibatch (3 tiles per wave).  The kernels that WRITE the parameters (k_reduce_opt, k_opt_step,
 // k_ls_set_params: one lane owns one parameter) now also store that parameter's three 2^96-scaled pieces where the
 // consumers' lanes will load them, so a consumer's prologue is 12 x 16-byte loads per lane plus 5 raw floats per hidden
 // tile.  Same numbers as weight_frags(2^96 w ...): the consumers compute bit for bit what they computed before.

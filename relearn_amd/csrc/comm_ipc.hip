@@ -16,7 +16,7 @@
 // object load, a host stall, a profiler — is far below that).  A peer that never arrives sets the engine's STICKY error
 // word; the exchange is FAIL-STOP: the wave that timed out returns before it stores anything, every later collective
 // fails fast without publishing, every kernel that writes parameters or optimiser state from a reduced vector tests the
-// word first (k_reduce_adam's fused exchange; k_adam_step, k_ls_set_params and k_ls_finalize behind the stand-alone
+// word first (k_reduce_opt's fused exchange; k_opt_step, k_ls_set_params and k_ls_finalize behind the stand-alone
 // k_ipc_allreduce, which leaves LOCAL sums in the vector when it fails — kernels_update.hip: a TRPO update ends on the
 // parameters it started from), and the host raises RL_ERR_COMM at its next synchronising call.  The decision is taken
 // per 64-element chunk: when a peer never publishes, nothing is stepped anywhere (tests/test_gpu_multirank.py, both

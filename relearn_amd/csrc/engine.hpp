@@ -329,13 +329,39 @@ struct GenDev {
   uint64_t cap_act = 0, cap_tact = 0, cap_delta = 0, cap_z = 0, cap_tz = 0;
 };
 
+// What the optimiser kernels (kernels_update.hip) get by value.  OptStep: the constants of one step, each formed in f64 on
+// the host and rounded to f32 once (adam_next_step); a rule reads the ones it names.  OptState: the rule's state slots.
+enum : uint32_t {
+  OPT_WEIGHT_DECAY = 1u,  // weight_decay != 0
+  OPT_MOMENTUM = 2u,      // SGD: momentum != 0; RMSProp: momentum > 0
+  OPT_NESTEROV = 4u,      // SGD
+  OPT_CENTERED = 8u,      // RMSProp
+  OPT_FIRST_STEP = 16u,   // SGD: the momentum buffer starts as a copy of the gradient
+};
+struct OptStep {
+  float neg_lr;            // Adam, AdamW: -(float)(lr / (1 - beta1^step)); SGD, RMSProp: (float)(-lr)
+  float sqrt_bc2;          // Adam, AdamW: (float)sqrt(1 - beta2^step)
+  float b1, b2, omb1, omb2;  // Adam, AdamW: the betas and (float)(1 - beta)
+  float eps, wd;
+  float decay;             // AdamW: (float)(1 - lr * weight_decay)
+  float momentum, omd;     // SGD, RMSProp: momentum; SGD: (float)(1 - dampening)
+  float alpha, oma;        // RMSProp: alpha, (float)(1 - alpha)
+  uint32_t flags;          // OPT_*
+};
+struct OptState {
+  float *s0, *s1, *s2;  // NULL where the configuration has no such slot
+};
+
+// A first-order optimiser of any rule (the handle keeps the name of the rule it began with: no prototype changes).
 struct rl_adam {
   rl_engine *eng;  // kept separately: the module may be destroyed before its optimizer
   rl_mlp *mod;
-  rl_adam_config cfg;
-  float *d_m = nullptr, *d_v = nullptr;
+  rl_optimizer_config cfg;  // cfg.kind is the rule
+  // state slots, allocated where the configuration has them — Adam / AdamW: m, v; SGD: momentum buffer (momentum != 0);
+  // RMSProp: square average, momentum buffer (momentum > 0), gradient average (centered)
+  float *d_state[3] = {nullptr, nullptr, nullptr};
   uint64_t *d_step = nullptr;
-  uint64_t host_step = 0;  // == *d_step once the stream has drained (every Adam launch increments both)
+  uint64_t host_step = 0;  // == *d_step once the stream has drained (every optimiser launch increments both)
   // ... unless a launch was vetoed on the device (a failed exchange, the range guard): the entry point then returned an
   // error, and the first step after an error on this engine re-reads the count (rl_engine::error_epoch, adam_next_step)
   uint64_t error_epoch = 0;
@@ -415,7 +441,7 @@ struct rl_dqn {
   float *d_q = nullptr, *d_q_next = nullptr;  // module outputs of a collection step [2][N] / at a minibatch's successor
                                               // observations (action-value modules on the per-layer kernels)
   uint64_t cap_q_next = 0;
-  float *snap = nullptr;             // parameters + Adam moments + step count as of the start of a pipelined update
+  float *snap = nullptr;             // parameters + optimiser state slots + step count as of the start of a pipelined update
   // ... `mb` then points into them (the last minibatch stays readable); its own arrays, for the one-at-a-time builder:
   float *own_obs = nullptr, *own_target = nullptr;
   uint8_t *own_action = nullptr, *own_flag = nullptr;

@@ -382,6 +382,67 @@ struct AdamConfig {  // optimizers/coptimizer.rs:136-156
   }
 };
 
+// The other three COptimizer configurations (coptimizer.rs:49-132, 170-205): the same handle type with another rule
+// (rl_optimizer_create), so the update loops take them unchanged.
+class RuleOptimizer final : public Optimizer {
+ public:
+  RuleOptimizer(Module &m, Engine &eng, const rl_optimizer_config &c) {
+    check(rl_optimizer_create(m.handle(), &c, &h_), eng.handle());
+  }
+  ~RuleOptimizer() override { rl_adam_destroy(h_); }
+  RuleOptimizer(const RuleOptimizer &) = delete;
+  RuleOptimizer &operator=(const RuleOptimizer &) = delete;
+  rl_adam *handle() const override { return h_; }
+
+ private:
+  rl_adam *h_ = nullptr;
+};
+
+struct SgdConfig {  // optimizers/coptimizer.rs:49-87
+  double learning_rate = 1e-2, momentum = 0.0, weight_decay = 0.0, dampening = 0.0;
+  bool nesterov = false;
+  std::unique_ptr<Optimizer> build_optimizer(Module &m, Engine &eng) const {
+    rl_optimizer_config c;
+    check(rl_optimizer_config_default(RL_OPTIMIZER_SGD, &c));
+    c.learning_rate = learning_rate;
+    c.momentum = momentum;
+    c.weight_decay = weight_decay;
+    c.dampening = dampening;
+    c.nesterov = nesterov ? 1 : 0;
+    return std::unique_ptr<Optimizer>(new RuleOptimizer(m, eng, c));
+  }
+};
+
+struct RmsPropConfig {  // optimizers/coptimizer.rs:89-132
+  double learning_rate = 1e-2, momentum = 0.0, alpha = 0.99, eps = 1e-8;
+  bool centered = false;
+  double weight_decay = 0.0;
+  std::unique_ptr<Optimizer> build_optimizer(Module &m, Engine &eng) const {
+    rl_optimizer_config c;
+    check(rl_optimizer_config_default(RL_OPTIMIZER_RMSPROP, &c));
+    c.learning_rate = learning_rate;
+    c.momentum = momentum;
+    c.alpha = alpha;
+    c.eps = eps;
+    c.centered = centered ? 1 : 0;
+    c.weight_decay = weight_decay;
+    return std::unique_ptr<Optimizer>(new RuleOptimizer(m, eng, c));
+  }
+};
+
+struct AdamWConfig {  // optimizers/coptimizer.rs:170-205
+  double learning_rate = 1e-3, beta1 = 0.9, beta2 = 0.999, weight_decay = 0.0;
+  std::unique_ptr<Optimizer> build_optimizer(Module &m, Engine &eng) const {
+    rl_optimizer_config c;
+    check(rl_optimizer_config_default(RL_OPTIMIZER_ADAMW, &c));
+    c.learning_rate = learning_rate;
+    c.beta1 = beta1;
+    c.beta2 = beta2;
+    c.weight_decay = weight_decay;
+    return std::unique_ptr<Optimizer>(new RuleOptimizer(m, eng, c));
+  }
+};
+
 // ---------------------------------------------------------------- device-resident history (VecBuffer's stand-in)
 class DeviceHistory {
  public:
@@ -633,10 +694,10 @@ struct TrpoConfig {  // policies/trpo.rs:18-41
                                             optimizer_config.build_optimizer(), max_policy_step_kl));
   }
 };
-template <typename MB = MlpConfig>
+template <typename MB = MlpConfig, typename OC = AdamConfig>
 struct PpoConfig {  // policies/ppo.rs:13-41
   MB policy_fn_config;
-  AdamConfig optimizer_config;
+  OC optimizer_config;
   uint64_t opt_steps_per_update = 10;
   double clip_distance = 0.2;
   std::unique_ptr<Policy> build_policy(Engine &eng, uint32_t in_dim, uint32_t out_dim, uint64_t seed) const {
@@ -645,10 +706,10 @@ struct PpoConfig {  // policies/ppo.rs:13-41
     return std::unique_ptr<Policy>(new Ppo(eng, std::move(m), std::move(o), opt_steps_per_update, clip_distance));
   }
 };
-template <typename MB = MlpConfig>
+template <typename MB = MlpConfig, typename OC = AdamConfig>
 struct ReinforceConfig {  // policies/reinforce.rs
   MB policy_fn_config;
-  AdamConfig optimizer_config;
+  OC optimizer_config;
   std::unique_ptr<Policy> build_policy(Engine &eng, uint32_t in_dim, uint32_t out_dim, uint64_t seed) const {
     std::unique_ptr<Module> m = policy_fn_config.build_module(eng, in_dim, out_dim, seed);
     std::unique_ptr<Optimizer> o = optimizer_config.build_optimizer(*m, eng);
@@ -721,10 +782,10 @@ class RewardToGo final : public Critic {  // critics/rtg.rs:22-40
   float gamma_;
 };
 
-template <typename MB = MlpConfig>
+template <typename MB = MlpConfig, typename OC = AdamConfig>
 struct ValuesOptConfig {  // critics/opt.rs:13-37
   MB state_value_fn_config;
-  AdamConfig optimizer_config;
+  OC optimizer_config;
   double gae_lambda = 0.95;          // AdvantageFn::Gae { lambda }
   StepValueTarget target = StepValueTarget::RewardToGo;
   uint64_t opt_steps_per_update = 80;
@@ -873,10 +934,10 @@ struct ActorCriticConfig {  // actor_critic.rs:20-45
 };
 
 // ---------------------------------------------------------------- DQN (src/torch/agents/dqn.rs)
-template <typename VB = MlpConfig>
+template <typename VB = MlpConfig, typename OC = AdamConfig>
 struct DqnConfig {  // dqn.rs:26-72
   VB action_value_fn_config;
-  AdamConfig optimizer_config;
+  OC optimizer_config;
   bool one_step_td = false;  // StepValueTarget::{RewardToGo, OneStepTd}
   double exploration_start = 1.0, exploration_end = 0.1;
   uint64_t exploration_period = 10000000;
@@ -886,8 +947,8 @@ struct DqnConfig {  // dqn.rs:26-72
 };
 
 class DqnAgent;
-template <typename VB>
-std::unique_ptr<DqnAgent> build_dqn_agent(const DqnConfig<VB> &c, EnvLanes &env, uint64_t seed, const uint32_t (&agent_key)[8]);
+template <typename VB, typename OC>
+std::unique_ptr<DqnAgent> build_dqn_agent(const DqnConfig<VB, OC> &c, EnvLanes &env, uint64_t seed, const uint32_t (&agent_key)[8]);
 
 class DqnAgent {
  public:
@@ -937,8 +998,8 @@ class DqnAgent {
   uint64_t global_steps() const { return global_steps_; }
 
  private:
-  template <typename VB>
-  friend std::unique_ptr<DqnAgent> build_dqn_agent(const DqnConfig<VB> &, EnvLanes &, uint64_t, const uint32_t (&)[8]);
+  template <typename VB, typename OC>
+  friend std::unique_ptr<DqnAgent> build_dqn_agent(const DqnConfig<VB, OC> &, EnvLanes &, uint64_t, const uint32_t (&)[8]);
   explicit DqnAgent(Engine &eng) : eng_(eng) {}
   Engine &eng_;
   std::unique_ptr<Module> q_;
@@ -948,8 +1009,8 @@ class DqnAgent {
 };
 
 // BuildAgent for DqnConfig (dqn.rs:74-96); `agent_key` is the 32-byte seed `Prng::from_rng(rng)` draws
-template <typename VB>
-std::unique_ptr<DqnAgent> build_dqn_agent(const DqnConfig<VB> &c, EnvLanes &env, uint64_t seed, const uint32_t (&agent_key)[8]) {
+template <typename VB, typename OC>
+std::unique_ptr<DqnAgent> build_dqn_agent(const DqnConfig<VB, OC> &c, EnvLanes &env, uint64_t seed, const uint32_t (&agent_key)[8]) {
   Engine &eng = env.engine();
   std::unique_ptr<DqnAgent> a(new DqnAgent(eng));
   a->n_lanes_ = env.num_lanes();

@@ -1,7 +1,7 @@
 // kernels_critic.hip — the fused critic step: forward + MSE loss + backward of the 5-128-1 value MLP over all samples.
 //
 // Reference semantics: ValuesOpt::update (src/torch/agents/critics/opt.rs:100-126): loss = mse_loss(V(obs), targets,
-// Mean); backward; the Adam step itself is k_reduce_adam / k_adam_step (kernels_update.hip).
+// Mean); backward; the optimiser step itself is k_reduce_opt / k_opt_step (kernels_update.hip).
 //
 // Tile machinery (layer 1 and the masked-sum backward on the bf16 matrix pipe with exact three-piece splits — no
 // reduced precision): bf16_tile.hpp.  On top of it, per 32-sample tile and wave:

@@ -291,7 +291,7 @@ __global__ void __launch_bounds__(1024) k_reduce(const double *__restrict__ slab
   }
 }
 
-// k_reduce with narrower workgroups (round 6; k_reduce_adam_narrow below says why): CW columns per workgroup, the 64 / CW
+// k_reduce with narrower workgroups (round 6; k_reduce_opt_narrow below says why): CW columns per workgroup, the 64 / CW
 // lane groups of a wave on different rows
 template <int CW>
 __global__ void __launch_bounds__(1024) k_reduce_narrow(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
@@ -518,70 +518,148 @@ __global__ void __launch_bounds__(SB) k_ls_finalize(float *__restrict__ params, 
     for (uint32_t i = threadIdx.x; i < P; i += SB) params[i] = prev[i];
 }
 
-// torch::optim::Adam::step of libtorch 1.12 (third party; COptimizer::adam, coptimizer.rs:158-167).  The bias
-// corrections come from the host, which tracks the step count (rl_adam.host_step): neg_step_size = -(float)(lr /
-// (1 - beta1^step)), sqrt_bc2 = (float)sqrt(1 - beta2^step) — the same numbers for this kernel and for k_reduce_adam.
-__global__ void __launch_bounds__(SB) k_adam_step(float *__restrict__ params, const float *__restrict__ grad,
-                                                  float *__restrict__ m, float *__restrict__ v, uint64_t *step_ptr,
-                                                  uint32_t P, uint64_t step, float neg_step_size, float sqrt_bc2,
-                                                  double beta1, double beta2, double eps, double weight_decay,
-                                                  const float *__restrict__ loss_sum, double inv_B,
-                                                  float *__restrict__ loss_out, const int32_t *comm_err,
-                                                  uint32_t *__restrict__ wimg, int A,
-                                                  const uint32_t *__restrict__ veto) {
+// ---------------------------------------------------------------- first-order optimiser rules
+// The four COptimizer configurations of the reference (src/torch/optimizers/coptimizer.rs: SgdConfig :49-87,
+// RmsPropConfig :89-132, AdamConfig :134-168, AdamWConfig :170-205) in the operation order of libtorch 1.12's C++
+// optimisers (third party; what tch 0.8 binds, the reference passes its config fields straight through).  One function per
+// rule: (old parameter, gradient entry, the column's state words, the step's constants) -> new parameter, state words
+// updated in place.  f32, one rounding per written operation.  The kernels below are templated on the rule and the host
+// picks the instantiation; what branches remain inside a rule are on OptStep::flags, uniform over the launch.
+// A rule's state slots (rl_adam::d_state): Adam / AdamW m, v; SGD momentum buffer; RMSProp square average, momentum buffer,
+// gradient average.  Which of them a configuration has follows from the flags: opt_has_slot.
+
+// torch::optim::Adam::step (COptimizer::adam, coptimizer.rs:158-167).  The bias corrections come from the host, which
+// tracks the step count (rl_adam.host_step): neg_lr = -(float)(lr / (1 - beta1^step)), sqrt_bc2 = (float)sqrt(1 -
+// beta2^step) — the same numbers for k_opt_step and for k_reduce_opt.
+__device__ __forceinline__ float rule_adam(float p, float g, float &m, float &v, const OptStep &k) {
+  if (k.flags & OPT_WEIGHT_DECAY) g = g + k.wd * p;
+  const float mi = m * k.b1 + k.omb1 * g;
+  const float vi = v * k.b2 + k.omb2 * g * g;
+  m = mi;
+  v = vi;
+  const float denom = __fsqrt_rn(vi) / k.sqrt_bc2 + k.eps;
+  return p + (k.neg_lr * mi) / denom;
+}
+
+// torch::optim::AdamW::step (COptimizer::adamw, coptimizer.rs:195-204): the decay multiplies the parameter first
+// (decay = (float)(1 - lr * wd); exactly 1 without decay) and never reaches the gradient
+__device__ __forceinline__ float rule_adamw(float p, float g, float &m, float &v, const OptStep &k) {
+  p = p * k.decay;
+  const float mi = m * k.b1 + k.omb1 * g;
+  const float vi = v * k.b2 + k.omb2 * g * g;
+  m = mi;
+  v = vi;
+  const float denom = __fsqrt_rn(vi) / k.sqrt_bc2 + k.eps;
+  return p + (k.neg_lr * mi) / denom;
+}
+
+// torch::optim::SGD::step (COptimizer::sgd, coptimizer.rs:76-86).  On the optimiser's first step (OPT_FIRST_STEP: the
+// step count the host prepared is 1) the buffer is a copy of the decayed gradient, without dampening.
+__device__ __forceinline__ float rule_sgd(float p, float g, float &buf, const OptStep &k) {
+  if (k.flags & OPT_WEIGHT_DECAY) g = g + k.wd * p;
+  if (k.flags & OPT_MOMENTUM) {
+    const float b = (k.flags & OPT_FIRST_STEP) ? g : buf * k.momentum + k.omd * g;
+    buf = b;
+    g = (k.flags & OPT_NESTEROV) ? g + k.momentum * b : b;
+  }
+  return p + k.neg_lr * g;
+}
+
+// torch::optim::RMSprop::step (COptimizer::rms_prop, coptimizer.rs:120-131).  The square root is the correctly rounded one
+// (__builtin_sqrtf: the compiler's IEEE expansion; __fsqrt_rn of this toolchain is the native instruction, good to one
+// ulp, which the Adam rules keep for the bits they have always produced): every operation of this rule is then a correctly
+// rounded f32 operation, and the rule equals a float32 restatement bit for bit (tests/optim_ref.py).
+__device__ __forceinline__ float rule_rmsprop(float p, float g, float &sq, float &buf, float &ga, const OptStep &k) {
+  if (k.flags & OPT_WEIGHT_DECAY) g = g + k.wd * p;
+  const float s = sq * k.alpha + k.oma * g * g;
+  sq = s;
+  float avg;
+  if (k.flags & OPT_CENTERED) {
+    const float a = ga * k.alpha + k.oma * g;
+    ga = a;
+    avg = __builtin_sqrtf(s + -1.0f * a * a) + k.eps;
+  } else {
+    avg = __builtin_sqrtf(s) + k.eps;
+  }
+  if (k.flags & OPT_MOMENTUM) {
+    const float b = buf * k.momentum + g / avg;
+    buf = b;
+    return p + k.neg_lr * b;
+  }
+  return p + k.neg_lr * (g / avg);
+}
+
+// whether a configuration of RULE keeps state slot `slot` (a constant for Adam and AdamW)
+template <int RULE>
+__device__ __forceinline__ bool opt_has_slot(int slot, uint32_t flags) {
+  if (RULE == RL_OPTIMIZER_ADAM || RULE == RL_OPTIMIZER_ADAMW) return slot < 2;
+  if (RULE == RL_OPTIMIZER_SGD) return slot == 0 && (flags & OPT_MOMENTUM) != 0u;
+  return slot == 0 || (slot == 1 && (flags & OPT_MOMENTUM) != 0u) || (slot == 2 && (flags & OPT_CENTERED) != 0u);
+}
+
+template <int RULE>
+__device__ __forceinline__ float opt_apply(float p, float g, float &s0, float &s1, float &s2, const OptStep &k) {
+  if (RULE == RL_OPTIMIZER_ADAM) return rule_adam(p, g, s0, s1, k);
+  if (RULE == RL_OPTIMIZER_ADAMW) return rule_adamw(p, g, s0, s1, k);
+  if (RULE == RL_OPTIMIZER_SGD) return rule_sgd(p, g, s0, k);
+  return rule_rmsprop(p, g, s0, s1, s2, k);
+}
+
+// The stand-alone step: behind an all-reduce, a recurrent or general module's reduction, or a host gradient.
+template <int RULE>
+__global__ void __launch_bounds__(SB) k_opt_step(float *__restrict__ params, const float *__restrict__ grad, OptState st,
+                                                 uint64_t *step_ptr, uint32_t P, uint64_t step, OptStep k,
+                                                 const float *__restrict__ loss_sum, double inv_B,
+                                                 float *__restrict__ loss_out, const int32_t *comm_err,
+                                                 uint32_t *__restrict__ wimg, int A,
+                                                 const uint32_t *__restrict__ veto) {
   if (comm_failed(comm_err)) return;  // `grad` holds local sums: no step, no step count
   if (veto != nullptr && *veto != 0u) return;  // the range guard refused the pass `grad` comes from: nothing is applied
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     *step_ptr = step;
     if (loss_out) *loss_out = (float)((double)(*loss_sum) * inv_B);
   }
-  float b1 = (float)beta1, b2 = (float)beta2;
-  float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
-  float epsf = (float)eps;
-  float wd = (float)weight_decay;
   for (uint32_t i = blockIdx.x * SB + threadIdx.x; i < P; i += gridDim.x * SB) {  // (elementwise: any grid)
-    float g = grad[i];
-    if (weight_decay != 0.0) g = g + wd * params[i];
-    float mi = m[i] * b1 + omb1 * g;
-    float vi = v[i] * b2 + omb2 * g * g;
-    m[i] = mi;
-    v[i] = vi;
-    float denom = __fsqrt_rn(vi) / sqrt_bc2 + epsf;
-    const float w = params[i] + (neg_step_size * mi) / denom;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    if (opt_has_slot<RULE>(0, k.flags)) s0 = st.s0[i];
+    if (opt_has_slot<RULE>(1, k.flags)) s1 = st.s1[i];
+    if (opt_has_slot<RULE>(2, k.flags)) s2 = st.s2[i];
+    const float w = opt_apply<RULE>(params[i], grad[i], s0, s1, s2, k);
+    if (opt_has_slot<RULE>(0, k.flags)) st.s0[i] = s0;
+    if (opt_has_slot<RULE>(1, k.flags)) st.s1[i] = s1;
+    if (opt_has_slot<RULE>(2, k.flags)) st.s2[i] = s2;
     params[i] = w;
     if (wimg) bt::wimg_store_param(wimg, i, w, A);  // (the module's weight image stays current, bf16_tile.hpp)
   }
 }
 
-// k_reduce followed by the Adam update of the 64 entries each workgroup has just reduced (Adam is elementwise, so
-// no second launch is needed when no all-reduce sits between the two: single-rank runs).  Same arithmetic as
-// k_reduce + k_adam_step; `step` is the 1-based step index, tracked by the host.
+// k_reduce followed by the optimiser step on the 64 entries each workgroup has just reduced (every rule is elementwise,
+// so no second launch is needed when no all-reduce sits between the two: single-rank runs).  Same arithmetic as
+// k_reduce + k_opt_step; `step` is the 1-based step index, tracked by the host.
 // XCHG: with several ranks on the peer-mailbox transport, wave 0 exchanges the 64 reduced columns of the workgroup (one
 // chunk of the collective, comm_ipc.hpp) between the reduction and the optimiser step — the multi-rank critic loop stays
-// at two launches per step
-template <bool XCHG>
-__global__ void __launch_bounds__(1024) k_reduce_adam(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
-                                                      const double *__restrict__ slabB, uint32_t nbB,
-                                                      float *__restrict__ vec, float *__restrict__ params,
-                                                      float *__restrict__ m, float *__restrict__ v,
-                                                      uint64_t *step_ptr, uint64_t step, float neg_step_size,
-                                                      float sqrt_bc2, double beta1, double beta2, double eps,
-                                                      double weight_decay, double inv_B,
-                                                      float *__restrict__ loss_out, IpcPeers peers,
-                                                      uint32_t *__restrict__ wimg, int A,
-                                                      const uint32_t *__restrict__ veto) {
+// at two launches per step (built for Adam only; the other rules take reduce, exchange, k_opt_step)
+template <int RULE, bool XCHG>
+__global__ void __launch_bounds__(1024) k_reduce_opt(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
+                                                     const double *__restrict__ slabB, uint32_t nbB,
+                                                     float *__restrict__ vec, float *__restrict__ params, OptState st,
+                                                     uint64_t *step_ptr, uint64_t step, OptStep k, double inv_B,
+                                                     float *__restrict__ loss_out, IpcPeers peers,
+                                                     uint32_t *__restrict__ wimg, int A,
+                                                     const uint32_t *__restrict__ veto) {
   __shared__ double part[16][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint32_t p = blockIdx.x * 64 + lane;
-  // the optimiser state of this column is requested first, so that it arrives under the slab loads — and the range
-  // guard's veto word with it (set by the fused launch this one reduces, or an earlier one of the call: the sums are then
-  // not to be applied; bf16_tile.hpp range_guard)
+  // the optimiser state of this column (none to three words, by the rule) is requested first, so that it arrives under
+  // the slab loads — and the range guard's veto word with it (set by the fused launch this one reduces, or an earlier one
+  // of the call: the sums are then not to be applied; bf16_tile.hpp range_guard)
   const uint32_t vetoed = veto != nullptr ? *veto : 0u;
-  float p_old = 0.0f, m_old = 0.0f, v_old = 0.0f;
+  float p_old = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
   if (w == 0 && p < P) {
     p_old = params[p];
-    m_old = m[p];
-    v_old = v[p];
+    if (opt_has_slot<RULE>(0, k.flags)) s0 = st.s0[p];
+    if (opt_has_slot<RULE>(1, k.flags)) s1 = st.s1[p];
+    if (opt_has_slot<RULE>(2, k.flags)) s2 = st.s2[p];
   }
   double acc = 0.0;
   if (p < P) acc = column_partial(slabA, nbA, P, p, w);
@@ -591,9 +669,9 @@ __global__ void __launch_bounds__(1024) k_reduce_adam(const double *__restrict__
   if (w != 0) return;
   double t = part[0][lane];
 #pragma unroll
-  for (int k = 1; k < 16; ++k) t = t + part[k][lane];
+  for (int r = 1; r < 16; ++r) t = t + part[r][lane];
   float gsum = (float)t;
-  if (XCHG) {  // all 64 lanes; a failed exchange (sticky error word, comm_ipc.hpp) leaves vec, params and moments alone
+  if (XCHG) {  // all 64 lanes; a failed exchange (sticky error word, comm_ipc.hpp) leaves vec, params and state alone
     float total;
     if (!ipc_exchange_chunk(peers, blockIdx.x, (uint32_t)lane, p < P + 4 ? gsum : 0.0f, total)) return;
     gsum = total;
@@ -604,20 +682,12 @@ __global__ void __launch_bounds__(1024) k_reduce_adam(const double *__restrict__
     if (p == P && loss_out) *loss_out = (float)((double)gsum * inv_B);
     return;
   }
-  if (vetoed != 0u) return;  // parameters, moments and step count stay as they are
+  if (vetoed != 0u) return;  // parameters, optimiser state and step count stay as they are
   if (p == 0) *step_ptr = step;
-  // neg_step_size = -(float)(lr / (1 - beta1^step)), sqrt_bc2 = (float)sqrt(1 - beta2^step): the host knows the step
-  const float b1 = (float)beta1, b2 = (float)beta2;
-  const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
-  const float epsf = (float)eps;
-  float g = gsum;
-  if (weight_decay != 0.0) g = g + (float)weight_decay * p_old;
-  const float mi = m_old * b1 + omb1 * g;
-  const float vi = v_old * b2 + omb2 * g * g;
-  m[p] = mi;
-  v[p] = vi;
-  const float denom = __fsqrt_rn(vi) / sqrt_bc2 + epsf;
-  const float w_new = p_old + (neg_step_size * mi) / denom;
+  const float w_new = opt_apply<RULE>(p_old, gsum, s0, s1, s2, k);
+  if (opt_has_slot<RULE>(0, k.flags)) st.s0[p] = s0;
+  if (opt_has_slot<RULE>(1, k.flags)) st.s1[p] = s1;
+  if (opt_has_slot<RULE>(2, k.flags)) st.s2[p] = s2;
   params[p] = w_new;
   // the next fused launch reads the weights as piece fragments: this lane owns parameter p, it also owns p's pieces in
   // the module's weight image (bf16_tile.hpp; NULL when this call has built none)
@@ -629,27 +699,26 @@ __global__ void __launch_bounds__(1024) k_reduce_adam(const double *__restrict__
 // the bytes, and a lane has 4 (8) loads in flight instead of 16.  A column's partial sums are per row group r, r + RG, ...
 // (RG = 16 x 64 / CW groups) in row order, combined in group order: deterministic, another order than the wide form.
 // (No mailbox exchange here: its chunks are 64 columns.)
-template <int CW>
-__global__ void __launch_bounds__(1024) k_reduce_adam_narrow(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
-                                                             const double *__restrict__ slabB, uint32_t nbB,
-                                                             float *__restrict__ vec, float *__restrict__ params,
-                                                             float *__restrict__ m, float *__restrict__ v,
-                                                             uint64_t *step_ptr, uint64_t step, float neg_step_size,
-                                                             float sqrt_bc2, double beta1, double beta2, double eps,
-                                                             double weight_decay, double inv_B,
-                                                             float *__restrict__ loss_out, uint32_t *__restrict__ wimg,
-                                                             int A, const uint32_t *__restrict__ veto) {
+template <int RULE, int CW>
+__global__ void __launch_bounds__(1024) k_reduce_opt_narrow(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
+                                                            const double *__restrict__ slabB, uint32_t nbB,
+                                                            float *__restrict__ vec, float *__restrict__ params,
+                                                            OptState st, uint64_t *step_ptr, uint64_t step, OptStep k,
+                                                            double inv_B, float *__restrict__ loss_out,
+                                                            uint32_t *__restrict__ wimg, int A,
+                                                            const uint32_t *__restrict__ veto) {
   constexpr int GPW = 64 / CW, RG = 16 * GPW;  // row groups per wave, per workgroup
   __shared__ double part[RG][CW];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c = lane & (CW - 1), rg = w * GPW + lane / CW;
   const uint32_t p = blockIdx.x * CW + (uint32_t)c;
-  const uint32_t vetoed = veto != nullptr ? *veto : 0u;  // (the range guard's veto: k_reduce_adam)
-  float p_old = 0.0f, m_old = 0.0f, v_old = 0.0f;
+  const uint32_t vetoed = veto != nullptr ? *veto : 0u;  // (the range guard's veto: k_reduce_opt)
+  float p_old = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
   if (threadIdx.x < CW && p < P) {  // the optimiser state of this column arrives under the slab loads
     p_old = params[p];
-    m_old = m[p];
-    v_old = v[p];
+    if (opt_has_slot<RULE>(0, k.flags)) s0 = st.s0[p];
+    if (opt_has_slot<RULE>(1, k.flags)) s1 = st.s1[p];
+    if (opt_has_slot<RULE>(2, k.flags)) s2 = st.s2[p];
   }
   auto partial = [&](const double *__restrict__ slab, uint32_t nb, uint32_t stride, uint32_t col) {
     constexpr int U = 256 / RG;  // loads in flight per lane: one memory round trip for <= 256 rows
@@ -674,7 +743,7 @@ __global__ void __launch_bounds__(1024) k_reduce_adam_narrow(const double *__res
   if (threadIdx.x >= CW || p >= P + 4) return;
   double t = part[0][c];
 #pragma unroll
-  for (int k = 1; k < RG; ++k) t = t + part[k][c];
+  for (int r = 1; r < RG; ++r) t = t + part[r][c];
   const float gsum = (float)t;
   vec[p] = gsum;
   if (p >= P) {
@@ -683,17 +752,10 @@ __global__ void __launch_bounds__(1024) k_reduce_adam_narrow(const double *__res
   }
   if (vetoed != 0u) return;
   if (p == 0) *step_ptr = step;
-  const float b1 = (float)beta1, b2 = (float)beta2;
-  const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
-  const float epsf = (float)eps;
-  float g = gsum;
-  if (weight_decay != 0.0) g = g + (float)weight_decay * p_old;
-  const float mi = m_old * b1 + omb1 * g;
-  const float vi = v_old * b2 + omb2 * g * g;
-  m[p] = mi;
-  v[p] = vi;
-  const float denom = __fsqrt_rn(vi) / sqrt_bc2 + epsf;
-  const float w_new = p_old + (neg_step_size * mi) / denom;
+  const float w_new = opt_apply<RULE>(p_old, gsum, s0, s1, s2, k);
+  if (opt_has_slot<RULE>(0, k.flags)) st.s0[p] = s0;
+  if (opt_has_slot<RULE>(1, k.flags)) st.s1[p] = s1;
+  if (opt_has_slot<RULE>(2, k.flags)) st.s2[p] = s2;
   params[p] = w_new;
   if (wimg) bt::wimg_store_param(wimg, p, w_new, A);
 }
@@ -850,8 +912,9 @@ void launch_ls_finalize(rl_traj *traj, rl_mlp *policy, double max_kl, int accept
   wimg_invalidate(policy);  // (a rollback rewrites the parameters without the image)
 }
 
-// bias corrections of the optimiser's NEXT step (advances the host's step count)
-static void adam_next_step(rl_adam *opt, float *neg_step_size, float *sqrt_bc2) {
+// The constants of the optimiser's NEXT step (advances the host's step count): every rule's scalars are formed in f64 here
+// and rounded to f32 once; Adam's and AdamW's bias corrections and SGD's first-step flag follow the step count.
+static OptStep adam_next_step(rl_adam *opt) {
   if (opt->error_epoch != opt->eng->error_epoch) {
     // an entry point failed on this engine since this optimiser last stepped: launches of it may have been vetoed on the
     // device (a failed exchange, the range guard) after the host had counted them — the device's count is the truth
@@ -865,63 +928,98 @@ static void adam_next_step(rl_adam *opt, float *neg_step_size, float *sqrt_bc2) 
     opt->error_epoch = e->error_epoch;
   }
   opt->host_step += 1;
-  const double bc1 = 1.0 - std::pow(opt->cfg.beta1, (double)opt->host_step);
-  const double bc2 = 1.0 - std::pow(opt->cfg.beta2, (double)opt->host_step);
-  *neg_step_size = -(float)(opt->cfg.learning_rate / bc1);
-  *sqrt_bc2 = (float)std::sqrt(bc2);
+  const rl_optimizer_config &c = opt->cfg;
+  OptStep k{};
+  k.eps = (float)c.eps;
+  k.wd = (float)c.weight_decay;
+  if (c.weight_decay != 0.0) k.flags |= OPT_WEIGHT_DECAY;
+  if (c.kind == RL_OPTIMIZER_ADAM || c.kind == RL_OPTIMIZER_ADAMW) {
+    const double bc1 = 1.0 - std::pow(c.beta1, (double)opt->host_step);
+    const double bc2 = 1.0 - std::pow(c.beta2, (double)opt->host_step);
+    k.neg_lr = -(float)(c.learning_rate / bc1);
+    k.sqrt_bc2 = (float)std::sqrt(bc2);
+    k.b1 = (float)c.beta1;
+    k.b2 = (float)c.beta2;
+    k.omb1 = (float)(1.0 - c.beta1);
+    k.omb2 = (float)(1.0 - c.beta2);
+    k.decay = (float)(1.0 - c.learning_rate * c.weight_decay);
+  } else {
+    k.neg_lr = (float)(-c.learning_rate);
+    k.momentum = (float)c.momentum;
+    k.omd = (float)(1.0 - c.dampening);
+    k.alpha = (float)c.alpha;
+    k.oma = (float)(1.0 - c.alpha);
+    if (c.kind == RL_OPTIMIZER_SGD ? c.momentum != 0.0 : c.momentum > 0.0) k.flags |= OPT_MOMENTUM;
+    if (c.kind == RL_OPTIMIZER_SGD && c.nesterov) k.flags |= OPT_NESTEROV;
+    if (c.kind == RL_OPTIMIZER_RMSPROP && c.centered) k.flags |= OPT_CENTERED;
+    if (opt->host_step == 1) k.flags |= OPT_FIRST_STEP;
+  }
+  return k;
 }
+
+// the instantiation of the optimiser's rule (the rule is never a branch inside a kernel)
+#define RL_WITH_RULE(KIND, CALL)                                                      \
+  switch (KIND) {                                                                     \
+    case RL_OPTIMIZER_ADAM: { constexpr int RULE = RL_OPTIMIZER_ADAM; CALL; } break;   \
+    case RL_OPTIMIZER_ADAMW: { constexpr int RULE = RL_OPTIMIZER_ADAMW; CALL; } break; \
+    case RL_OPTIMIZER_SGD: { constexpr int RULE = RL_OPTIMIZER_SGD; CALL; } break;     \
+    case RL_OPTIMIZER_RMSPROP: { constexpr int RULE = RL_OPTIMIZER_RMSPROP; CALL; } break; \
+    default: throw RlError(RL_ERR_INVALID_ARGUMENT, "optimizer: unknown kind");       \
+  }
 
 void launch_reduce_adam(rl_traj *traj, rl_adam *opt, uint32_t rowsA, uint32_t rowsB, int loss_slot,
                         uint64_t B_total) {
   ProfScope ps(traj->eng, RL_K_REDUCE);
   uint32_t P = (uint32_t)opt->mod->P;
-  float neg_step_size, sqrt_bc2;
-  adam_next_step(opt, &neg_step_size, &sqrt_bc2);
   rl_engine *e = traj->eng;
+  RL_REQUIRE(!e->ipc_active || opt->cfg.kind == RL_OPTIMIZER_ADAM,
+             "the exchange inside the reduction launch is built for Adam only");
+  const OptStep k = adam_next_step(opt);
+  const OptState st{opt->d_state[0], opt->d_state[1], opt->d_state[2]};
   float *loss_out = loss_slot >= 0 ? traj->losses + loss_slot : (float *)nullptr;
   if (e->ipc_active) {
     ProfScope pa(e, RL_K_ALLREDUCE);  // counted as a collective as well: the exchange runs inside this launch
     const IpcPeers peers = ipc_peers_next(e);
-    hipLaunchKernelGGL(k_reduce_adam<true>, dim3(cdiv(P + 4, 64)), dim3(1024), 0, e->stream, traj->slabA, rowsA, P,
-                       traj->slabB, rowsB, traj->vec, opt->mod->d_params, opt->d_m, opt->d_v, opt->d_step,
-                       opt->host_step, neg_step_size, sqrt_bc2, opt->cfg.beta1, opt->cfg.beta2, opt->cfg.eps,
-                       opt->cfg.weight_decay, 1.0 / (double)B_total, loss_out, peers, wimg_if_current(opt->mod),
+    hipLaunchKernelGGL((k_reduce_opt<RL_OPTIMIZER_ADAM, true>), dim3(cdiv(P + 4, 64)), dim3(1024), 0, e->stream,
+                       traj->slabA, rowsA, P, traj->slabB, rowsB, traj->vec, opt->mod->d_params, st, opt->d_step,
+                       opt->host_step, k, 1.0 / (double)B_total, loss_out, peers, wimg_if_current(opt->mod),
                        (int)opt->mod->out_dim, veto_word(traj, opt->mod));
   } else if (reduce_width(P) != 64) {
-    hipLaunchKernelGGL(k_reduce_adam_narrow<16>, dim3(cdiv(P + 4, 16)), dim3(1024), 0, e->stream, traj->slabA, rowsA, P,
-                       traj->slabB, rowsB, traj->vec, opt->mod->d_params, opt->d_m, opt->d_v, opt->d_step,
-                       opt->host_step, neg_step_size, sqrt_bc2, opt->cfg.beta1, opt->cfg.beta2, opt->cfg.eps,
-                       opt->cfg.weight_decay, 1.0 / (double)B_total, loss_out, wimg_if_current(opt->mod),
-                       (int)opt->mod->out_dim, veto_word(traj, opt->mod));
+    RL_WITH_RULE(opt->cfg.kind,
+                 hipLaunchKernelGGL((k_reduce_opt_narrow<RULE, 16>), dim3(cdiv(P + 4, 16)), dim3(1024), 0, e->stream,
+                                    traj->slabA, rowsA, P, traj->slabB, rowsB, traj->vec, opt->mod->d_params, st,
+                                    opt->d_step, opt->host_step, k, 1.0 / (double)B_total, loss_out,
+                                    wimg_if_current(opt->mod), (int)opt->mod->out_dim, veto_word(traj, opt->mod)));
   } else {
-    hipLaunchKernelGGL(k_reduce_adam<false>, dim3(cdiv(P + 4, 64)), dim3(1024), 0, e->stream, traj->slabA, rowsA, P,
-                       traj->slabB, rowsB, traj->vec, opt->mod->d_params, opt->d_m, opt->d_v, opt->d_step,
-                       opt->host_step, neg_step_size, sqrt_bc2, opt->cfg.beta1, opt->cfg.beta2, opt->cfg.eps,
-                       opt->cfg.weight_decay, 1.0 / (double)B_total, loss_out, IpcPeers{}, wimg_if_current(opt->mod),
-                       (int)opt->mod->out_dim, veto_word(traj, opt->mod));
+    RL_WITH_RULE(opt->cfg.kind,
+                 hipLaunchKernelGGL((k_reduce_opt<RULE, false>), dim3(cdiv(P + 4, 64)), dim3(1024), 0, e->stream,
+                                    traj->slabA, rowsA, P, traj->slabB, rowsB, traj->vec, opt->mod->d_params, st,
+                                    opt->d_step, opt->host_step, k, 1.0 / (double)B_total, loss_out, IpcPeers{},
+                                    wimg_if_current(opt->mod), (int)opt->mod->out_dim, veto_word(traj, opt->mod)));
   }
+}
+
+static void launch_opt_step(rl_adam *opt, hipStream_t stream, const float *d_grad, const float *loss_sum, double inv_B,
+                            float *loss_out, const int32_t *comm_err, const uint32_t *veto) {
+  uint32_t P = (uint32_t)opt->mod->P;
+  const OptStep k = adam_next_step(opt);
+  const OptState st{opt->d_state[0], opt->d_state[1], opt->d_state[2]};
+  RL_WITH_RULE(opt->cfg.kind,
+               hipLaunchKernelGGL(k_opt_step<RULE>, dim3((P + SB - 1) / SB), dim3(SB), 0, stream, opt->mod->d_params,
+                                  d_grad, st, opt->d_step, P, opt->host_step, k, loss_sum, inv_B, loss_out, comm_err,
+                                  wimg_if_current(opt->mod), (int)opt->mod->out_dim, veto));
 }
 
 void launch_adam_step(rl_traj *traj, rl_adam *opt, int loss_slot, uint64_t B_total) {
   ProfScope ps(traj->eng, RL_K_SMALL);
   uint32_t P = (uint32_t)opt->mod->P;
-  float neg_step_size, sqrt_bc2;
-  adam_next_step(opt, &neg_step_size, &sqrt_bc2);
-  hipLaunchKernelGGL(k_adam_step, dim3((P + SB - 1) / SB), dim3(SB), 0, traj->eng->stream, opt->mod->d_params, traj->vec, opt->d_m,
-                     opt->d_v, opt->d_step, P, opt->host_step, neg_step_size, sqrt_bc2, opt->cfg.beta1, opt->cfg.beta2,
-                     opt->cfg.eps, opt->cfg.weight_decay, traj->vec + P, 1.0 / (double)B_total,
-                     loss_slot >= 0 ? traj->losses + loss_slot : (float *)nullptr, comm_err_word(traj->eng),
-                     wimg_if_current(opt->mod), (int)opt->mod->out_dim, veto_word(traj, opt->mod));
+  launch_opt_step(opt, traj->eng->stream, traj->vec, traj->vec + P, 1.0 / (double)B_total,
+                  loss_slot >= 0 ? traj->losses + loss_slot : (float *)nullptr, comm_err_word(traj->eng),
+                  veto_word(traj, opt->mod));
 }
 
 void launch_adam_step_vec(rl_adam *opt, const float *d_grad) {
   ProfScope ps(opt->mod->eng, RL_K_SMALL);
-  uint32_t P = (uint32_t)opt->mod->P;
-  float neg_step_size, sqrt_bc2;
-  adam_next_step(opt, &neg_step_size, &sqrt_bc2);
-  hipLaunchKernelGGL(k_adam_step, dim3((P + SB - 1) / SB), dim3(SB), 0, opt->mod->eng->stream, opt->mod->d_params, d_grad, opt->d_m,
-                     opt->d_v, opt->d_step, P, opt->host_step, neg_step_size, sqrt_bc2, opt->cfg.beta1, opt->cfg.beta2,
-                     opt->cfg.eps, opt->cfg.weight_decay, (const float *)nullptr, 0.0, (float *)nullptr,
-                     (const int32_t *)nullptr, wimg_if_current(opt->mod), (int)opt->mod->out_dim,
-                     (const uint32_t *)nullptr);
+  launch_opt_step(opt, opt->mod->eng->stream, d_grad, (const float *)nullptr, 0.0, (float *)nullptr,
+                  (const int32_t *)nullptr, (const uint32_t *)nullptr);
 }
