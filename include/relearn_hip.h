@@ -195,9 +195,12 @@ typedef struct {
   uint64_t seed_actor;   /* actor stream seed (the `rng_actor` of Steps) */
   rl_cartpole_params cartpole;
   uint64_t chain_size;   /* RL_ENV_CHAIN: number of states (Chain::default: 5; the kernels are built for 5); 0 = 5 */
-  /* RL_ENV_MEMORY: MemoryGame { num_actions, history_len } (memory.rs:24-40).  The device kernels are built for 2
-   * actions and 5 observation features, i.e. MemoryGame::new(2, 3); other sizes -> RL_ERR_BUILD_ENV (the scalar host
-   * env takes any).  0 / 0 = (2, 3).  Episodes last history_len + 1 steps; the only random draw is
+  /* RL_ENV_MEMORY: MemoryGame { num_actions, history_len } (memory.rs:24-40): any num_actions >= 2 and history_len >= 1
+   * with num_actions + history_len >= 4 whose observation — one-hot(num_actions + history_len), + 1 feature under a
+   * VisibleStepLimit — fits the trajectory's 8 features; other sizes, among them MemoryGame::default() = (2, 1) with its
+   * three features, -> RL_ERR_BUILD_ENV (the scalar host env takes any).  0 / 0 = (2, 3), the size the fused
+   * rollouts are built for; every other size steps through the standalone env kernels (feed-forward policies of
+   * out_dim = num_actions: rl_mlp_create_layers).  Episodes last history_len + 1 steps; the only random draw is
    * `gen_range(0..num_actions)` in initial_state, taken sequentially from the lane's env stream. */
   uint64_t memory_num_actions, memory_history_len;
   /* RL_ENV_BANDIT: DeterministicBandit::from_values([v0, v1]) (src/envs/bandits.rs:109-116; Bandit::step :66-77): one
@@ -207,6 +210,13 @@ typedef struct {
 } rl_env_config;
 
 int32_t rl_env_create(rl_engine *engine, const rl_env_config *cfg, rl_env **out);
+/* DeterministicBandit::from_values(values) (src/envs/bandits.rs:109-116) for `n_arms` in 2..8 — rl_env_config's
+ * bandit_values holds two.  `cfg`: kind RL_ENV_BANDIT, no step limit; it supplies the lanes, the lane offset and the
+ * seeds, its bandit_values are not read.  Action space IndexSpace::new(n_arms); observation and termination as in the
+ * two-armed lanes (one-hot(5) of the single state, every step terminates, reward = values[action] as f32).  Anything
+ * else -> RL_ERR_BUILD_ENV. */
+int32_t rl_env_create_bandit(rl_engine *engine, const rl_env_config *cfg, const double *values, uint32_t n_arms,
+                             rl_env **out);
 int32_t rl_env_destroy(rl_env *env);
 /* number of observation features (CartPole 4, +1 `remaining` under VisibleStepLimit) and actions */
 int32_t rl_env_dims(const rl_env *env, uint32_t *obs_dim, uint32_t *n_actions);
@@ -214,8 +224,8 @@ int32_t rl_env_dims(const rl_env *env, uint32_t *obs_dim, uint32_t *n_actions);
 int32_t rl_env_reset(rl_env *env);
 /* Environment::observe -> feature vectors, SoA [obs_dim][n_lanes] f32 (host buffer) */
 int32_t rl_env_observe(rl_env *env, float *obs_out);
-/* Environment::step for every lane with host-side actions (u8 indices); lanes whose episode ends start
- * a new one.  Outputs (host, may be NULL): reward[n] f32, flag[n] u8, next observation features
+/* Environment::step for every lane with host-side actions (u8 indices below the env's action count, anything else ->
+ * RL_ERR_INVALID_ARGUMENT; rl_env_upload_actions checks the same); lanes whose episode ends start a new one.  Outputs (host, may be NULL): reward[n] f32, flag[n] u8, next observation features
  * [obs_dim][n] (of the NEW episode when the lane was reset), interrupt successor features [obs_dim][n]
  * (valid where flag == RL_SUCC_INTERRUPT). */
 int32_t rl_env_step(rl_env *env, const uint8_t *actions, float *reward_out, uint8_t *flag_out, float *obs_out,
@@ -260,8 +270,11 @@ typedef enum {
  * hidden_sizes[0] -> ... -> out_dim with `activation` after every hidden layer and `output_activation` on the output;
  * parameters flat as [W, b] per layer in layer order.  `n_hidden` in [0, 4], every width in [1, 256], in_dim in [1, 8]
  * (the envs of this library have 4 or 5 features: other widths work on host-made histories, rl_traj_write),
- * out_dim in {1, 2}, activations from rl_activation; anything else -> RL_ERR_BUILD_AGENT.  One hidden layer of at most
- * 128 units with the reference's defaults (Relu, Identity) is rl_mlp_create — the fused kernels every BASELINE
+ * out_dim in [1, 8], activations from rl_activation; anything else -> RL_ERR_BUILD_AGENT.  out_dim > 2 is a categorical
+ * policy over IndexSpace::new(out_dim) (spaces/index.rs:19-22): rollouts, rl_policy_gradient / _fvp / _loss_kl, TRPO, PPO,
+ * REINFORCE and the actor-critic update take it on envs and trajectories of that many actions (a mismatch ->
+ * RL_ERR_INVALID_ARGUMENT); DQN over more than two actions -> RL_ERR_UNSUPPORTED.  One hidden layer of at most
+ * 128 units with the reference's defaults (Relu, Identity) and at most two outputs is rl_mlp_create — the fused kernels every BASELINE
  * configuration runs on, which are built for exactly that; any other shape or activation runs per-layer kernels
  * (relearn_amd/csrc/kernels_general.hip: the general path, not the fast one) behind the same entry points — rollouts,
  * GAE, TRPO / PPO / REINFORCE and critic updates, DQN (collection one launch sequence per step), row-wise forward,

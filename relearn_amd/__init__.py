@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "rl_last_error", "rl_engine_info", "rl_engine_set_kernel_variant", "rl_timer_begin", "rl_timer_end", "rl_profile_enable", "rl_profile_read",
     "rl_comm_available", "rl_comm_library_paths", "rl_comm_unique_id", "rl_comm_init", "rl_comm_destroy", "rl_comm_init_host",
     "rl_comm_ipc_handle", "rl_comm_init_ipc", "rl_comm_selftest",
-    "rl_cartpole_params_default", "rl_env_create", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
+    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
@@ -425,6 +425,8 @@ class ChainEnv(_Handle):
     reset = CartPoleEnv.reset
     observe = CartPoleEnv.observe
     step = CartPoleEnv.step
+    upload_actions = CartPoleEnv.upload_actions
+    step_resident = CartPoleEnv.step_resident
 
     def get_state(self):
         """(state index, steps_remaining, reset_count) per lane"""
@@ -433,8 +435,9 @@ class ChainEnv(_Handle):
 
 
 class BanditEnv(ChainEnv):
-    """N DeterministicBandit lanes (src/envs/bandits.rs:109-116) — `DeterministicBandit::from_values([v0, v1])`: every step
-    is a whole episode, the reward is the chosen arm's value.  Observations: one-hot(5) of the single state."""
+    """N DeterministicBandit lanes (src/envs/bandits.rs:109-116) — `DeterministicBandit::from_values(values)`, 2..8 arms
+    (more than two through rl_env_create_bandit): every step is a whole episode, the reward is the chosen arm's value.
+    Observations: one-hot(5) of the single state."""
 
     def __init__(self, engine, n_lanes, values=(0.0, 1.0), lane_offset=0, seed_env=0, seed_actor=1):
         self.eng = engine
@@ -446,10 +449,17 @@ class BanditEnv(ChainEnv):
         cfg.seed_env = seed_env
         cfg.seed_actor = seed_actor
         cfg.cartpole = cartpole_params_default()
-        cfg.bandit_values[0], cfg.bandit_values[1] = values
+        values = [float(v) for v in values]
+        if len(values) == 2:
+            cfg.bandit_values[0], cfg.bandit_values[1] = values
         self.cfg = cfg
         self.h = C.c_void_p()
-        _check(lib().rl_env_create(engine.h, C.byref(cfg), C.byref(self.h)), engine.h)
+        if len(values) == 2:
+            _check(lib().rl_env_create(engine.h, C.byref(cfg), C.byref(self.h)), engine.h)
+        else:
+            arr = (C.c_double * max(len(values), 1))(*values)
+            _check(lib().rl_env_create_bandit(engine.h, C.byref(cfg), arr, C.c_uint32(len(values)), C.byref(self.h)),
+                   engine.h)
         _register(self)
         self.n = n_lanes
         d, a = C.c_uint32(), C.c_uint32()
@@ -458,9 +468,10 @@ class BanditEnv(ChainEnv):
 
 
 class MemoryEnv(ChainEnv):
-    """N MemoryGame lanes (src/envs/memory.rs) — `MemoryGame::new(2, 3)`, optionally wrapped in a step limit: the lane
-    starts in state 0 or 1 at random, walks through states 2, 3, 4 whatever the action, and on the step from state 4
-    earns +1 iff the action equals the state it started in (else -1); that step terminates the episode."""
+    """N MemoryGame lanes (src/envs/memory.rs) — `MemoryGame::new(num_actions, history_len)`, optionally wrapped in a step
+    limit: the lane starts in one of the states 0 .. num_actions - 1 at random, walks through the history_len states
+    behind them whatever the action, and on the step from the last one earns +1 iff the action equals the state it started
+    in (else -1); that step terminates the episode.  4 <= num_actions + history_len, (+ 1 under a visible limit) <= 8."""
 
     def __init__(self, engine, n_lanes, num_actions=2, history_len=3, max_steps=0, limit=LIMIT_NONE, lane_offset=0,
                  seed_env=0, seed_actor=1):
@@ -566,7 +577,9 @@ class Mlp(_Handle):
         self.eng = engine
         self.h = C.c_void_p()
         self.activation, self.output_activation, self.bias = activation, output_activation, bias
-        if isinstance(hidden, (list, tuple)) or (activation, output_activation) != ("Relu", "Identity") or not bias:
+        # (out_dim > 2, up to 8: a categorical policy over IndexSpace::new(out_dim), always on the per-layer kernels)
+        if (isinstance(hidden, (list, tuple)) or (activation, output_activation) != ("Relu", "Identity") or not bias
+                or out_dim > 2):
             hidden = list(hidden) if isinstance(hidden, (list, tuple)) else [hidden]
             sizes = (C.c_uint32 * max(len(hidden), 1))(*hidden)
             # bias = False: LinearConfig::bias_init = None, layers without a bias vector (rl_mlp_create_config)

@@ -657,7 +657,9 @@ static void env_release_device(rl_env *env) {
   env->d_reward = env->d_obs = env->d_term_obs = nullptr;
 }
 
-int32_t rl_env_create(rl_engine *e, const rl_env_config *cfg, rl_env **out) {
+// `arm_values` / `n_arms`: DeterministicBandit::from_values for rl_env_create_bandit (NULL: cfg->bandit_values, two arms)
+static int32_t env_create(rl_engine *e, const rl_env_config *cfg, const double *arm_values, uint32_t n_arms,
+                          rl_env **out) {
   return guarded(e, [&] {
     RL_REQUIRE(e && cfg && out, "NULL argument");
     *out = nullptr;
@@ -666,8 +668,19 @@ int32_t rl_env_create(rl_engine *e, const rl_env_config *cfg, rl_env **out) {
       throw RlError(RL_ERR_BUILD_ENV, "unknown env kind");
     const uint64_t mem_actions = cfg->memory_num_actions ? cfg->memory_num_actions : 2;
     const uint64_t mem_history = cfg->memory_num_actions || cfg->memory_history_len ? cfg->memory_history_len : 3;
-    if (cfg->kind == RL_ENV_MEMORY && !(mem_actions == 2 && mem_history == 3))
-      throw RlError(RL_ERR_BUILD_ENV, "the MemoryGame kernels are built for MemoryGame::new(2, 3) (5 observation features)");
+    // MemoryGame::new(num_actions, history_len) (memory.rs:40-50): num_actions + history_len states, one observation
+    // feature each [+ the remaining-steps feature of a VisibleStepLimit], within the widths the env kernels are built for:
+    // 4 (the narrowest env of this library, CartPole without a visible limit) .. 8 (the trajectory's widest observation).
+    // MemoryGame::default() = (2, 1) has three and stays refused (tests/test_gpu_memory.py pins that answer).
+    const uint64_t mem_states = mem_actions + mem_history;
+    if (cfg->kind == RL_ENV_MEMORY &&
+        !(mem_actions >= 2 && mem_history >= 1 && mem_actions <= RL_TRAJ_MAX_OBS_DIM && mem_history <= RL_TRAJ_MAX_OBS_DIM &&
+          mem_states >= RL_ENV_MIN_OBS_DIM &&
+          mem_states + (cfg->limit_kind == RL_LIMIT_VISIBLE ? 1 : 0) <= RL_TRAJ_MAX_OBS_DIM))
+      throw RlError(RL_ERR_BUILD_ENV, "MemoryGame lanes: num_actions >= 2, history_len >= 1, and 4..8 observation "
+                                      "features (num_actions + history_len >= 4; + 1 under a VisibleStepLimit <= 8)");
+    if (arm_values != nullptr && (cfg->kind != RL_ENV_BANDIT || n_arms < 2 || n_arms > 8))
+      throw RlError(RL_ERR_BUILD_ENV, "bandit lanes: kind RL_ENV_BANDIT with 2..8 arm values");
     if (cfg->kind == RL_ENV_CHAIN && !(cfg->chain_size == 0 || cfg->chain_size == 5))
       throw RlError(RL_ERR_BUILD_ENV, "the Chain kernels are built for Chain::default (5 states)");
     if (cfg->limit_kind != RL_LIMIT_NONE && (cfg->max_steps == 0 || cfg->max_steps >= (1ull << 32)))
@@ -680,11 +693,12 @@ int32_t rl_env_create(rl_engine *e, const rl_env_config *cfg, rl_env **out) {
     env->kind = cfg->kind;
     if (cfg->kind == RL_ENV_BANDIT && cfg->limit_kind != RL_LIMIT_NONE)
       throw RlError(RL_ERR_BUILD_ENV, "bandit lanes take no step limit (every step ends the episode)");
+    const uint32_t n_states = cfg->kind == RL_ENV_MEMORY ? (uint32_t)mem_states : 5u;
     if (cfg->kind == RL_ENV_CHAIN || cfg->kind == RL_ENV_MEMORY || cfg->kind == RL_ENV_BANDIT)
-      env->D = 5 + (cfg->limit_kind == RL_LIMIT_VISIBLE ? 1 : 0);  // one-hot(5) [+ remaining]
+      env->D = n_states + (cfg->limit_kind == RL_LIMIT_VISIBLE ? 1 : 0);  // one-hot(states) [+ remaining]
     else
       env->D = cfg->limit_kind == RL_LIMIT_VISIBLE ? 5 : 4;
-    env->A = 2;
+    env->A = cfg->kind == RL_ENV_MEMORY ? (uint32_t)mem_actions : (arm_values != nullptr ? n_arms : 2u);
     const rl_cartpole_params &p = cfg->cartpole;
     CartPoleDev &d = env->dev;
     d.gravity = p.gravity;
@@ -708,11 +722,12 @@ int32_t rl_env_create(rl_engine *e, const rl_env_config *cfg, rl_env **out) {
     d.lane_offset = cfg->lane_offset;
     d.max_steps = cfg->max_steps < (1ull << 32) ? (uint32_t)cfg->max_steps : 0u;
     d.limit_kind = cfg->limit_kind;
-    d.chain_size = 5;
+    d.chain_size = n_states;
     d.mem_actions = cfg->kind == RL_ENV_MEMORY ? (uint32_t)mem_actions : 0u;
     d.bandit = cfg->kind == RL_ENV_BANDIT ? 1u : 0u;
-    d.bandit_r[0] = (float)cfg->bandit_values[0];  // Reward -> f32 feedback, as every env's reward record
-    d.bandit_r[1] = (float)cfg->bandit_values[1];
+    for (uint32_t a = 0; a < 8; ++a)  // Reward -> f32 feedback, as every env's reward record
+      d.bandit_r[a] = arm_values != nullptr ? (a < n_arms ? (float)arm_values[a] : 0.0f)
+                                            : (a < 2 ? (float)cfg->bandit_values[a] : 0.0f);
     size_t n = cfg->n_lanes;
     try {
     env->st.x = dalloc<double>(n);
@@ -742,6 +757,22 @@ int32_t rl_env_create(rl_engine *e, const rl_env_config *cfg, rl_env **out) {
     e->live_handles += 1;
     *out = env.release();
   });
+}
+
+int32_t rl_env_create(rl_engine *e, const rl_env_config *cfg, rl_env **out) {
+  return env_create(e, cfg, nullptr, 0, out);
+}
+
+int32_t rl_env_create_bandit(rl_engine *e, const rl_env_config *cfg, const double *values, uint32_t n_arms,
+                             rl_env **out) {
+  if (values == nullptr) return guarded(e, [&] { RL_REQUIRE(values, "NULL argument"); });
+  return env_create(e, cfg, values, n_arms, out);
+}
+
+// Index::from_index of the env's action space: an index >= num_actions is no action
+static void check_actions(const rl_env *env, const uint8_t *actions) {
+  for (uint64_t i = 0; i < env->cfg.n_lanes; ++i)
+    RL_REQUIRE(actions[i] < env->A, "action index outside the env's action space");
 }
 
 int32_t rl_env_destroy(rl_env *env) {
@@ -817,6 +848,7 @@ int32_t rl_debug_stream_words(rl_engine *engine, uint64_t seed, uint64_t stream,
 int32_t rl_env_upload_actions(rl_env *env, const uint8_t *actions) {
   return guarded(env ? env->eng : nullptr, [&] {
     RL_REQUIRE(env && actions, "NULL argument");
+    check_actions(env, actions);
     h2d(env->eng, env->d_actions, actions, env->cfg.n_lanes);
   });
 }
@@ -833,6 +865,7 @@ int32_t rl_env_step(rl_env *env, const uint8_t *actions, float *reward_out, uint
                     float *term_obs_out) {
   return guarded(env ? env->eng : nullptr, [&] {
     RL_REQUIRE(env && actions, "NULL argument");
+    check_actions(env, actions);
     rl_engine *e = env->eng;
     size_t n = env->cfg.n_lanes;
     RL_HIP_CHECK(hipMemcpyAsync(env->d_actions, actions, n, hipMemcpyHostToDevice, e->stream));
@@ -925,18 +958,19 @@ static int32_t mlp_create_config(rl_engine *e, uint32_t in_dim, const uint32_t *
                                  uint32_t out_dim, int32_t activation, int32_t output_activation, bool has_bias,
                                  rl_mlp **out) {
   // one hidden layer of at most 128 units, Relu inside and Identity on the output, with biases: the fused kernels
+  // (more than two outputs — a categorical policy over IndexSpace::new(3..8) — always the per-layer kernels)
   if (has_bias && e && out && hidden_sizes && n_hidden == 1 && hidden_sizes[0] <= 128 && activation == RL_ACT_RELU &&
-      output_activation == RL_ACT_IDENTITY && (in_dim == 4 || in_dim == 5))
+      output_activation == RL_ACT_IDENTITY && (in_dim == 4 || in_dim == 5) && out_dim <= 2)
     return rl_mlp_create(e, in_dim, hidden_sizes[0], out_dim, out);
   return guarded(e, [&] {
     RL_REQUIRE(e && out && (hidden_sizes || n_hidden == 0), "NULL argument");
     *out = nullptr;
     // (the envs of this library have 4 or 5 features; other widths serve host-made histories: rl_traj_write)
-    bool ok = in_dim >= 1 && in_dim <= RL_TRAJ_MAX_OBS_DIM && (out_dim == 1 || out_dim == 2) && n_hidden <= RL_MLP_MAX_HIDDEN;
+    bool ok = in_dim >= 1 && in_dim <= RL_TRAJ_MAX_OBS_DIM && out_dim >= 1 && out_dim <= RL_MLP_MAX_OUT && n_hidden <= RL_MLP_MAX_HIDDEN;
     for (uint32_t l = 0; ok && l < n_hidden; ++l) ok = hidden_sizes[l] >= 1 && hidden_sizes[l] <= RL_MLP_MAX_WIDTH;
     if (!ok)
       throw RlError(RL_ERR_BUILD_AGENT, "supported MLP shapes: in_dim 1..8, at most 4 hidden layers of 1..256 units, "
-                                        "out_dim in {1,2}");
+                                        "out_dim 1..8");
     if (activation < RL_ACT_IDENTITY || activation > RL_ACT_TANH || output_activation < RL_ACT_IDENTITY ||
         output_activation > RL_ACT_TANH)
       throw RlError(RL_ERR_BUILD_AGENT, "activation / output_activation must be one of rl_activation "
@@ -1549,6 +1583,13 @@ int32_t rl_traj_write(rl_traj *t, int32_t field, const void *host, uint64_t byte
     traj_field(t, field, &p, &need);
     RL_REQUIRE(bytes == need, "byte count mismatch for trajectory field");
     h2d(t->eng, p, host, bytes);
+    if (field == RL_TRAJ_ACTION) {  // host-made actions: no env names their space; a policy must at least cover them
+      const uint8_t *a = static_cast<const uint8_t *>(host);
+      uint8_t hi = 0;
+      for (uint64_t i = 0; i < bytes; ++i) hi = a[i] > hi ? a[i] : hi;
+      t->n_actions = 0;
+      t->max_action = hi;
+    }
     if (field == RL_TRAJ_OBS) t->range_valid = t->range_reset = false;  // (the range guard reads the planes' magnitudes)
     t->rtg_scan_valid = false;  // (whatever was written, the return plane is no longer known to match the rewards)
   });
@@ -1640,11 +1681,20 @@ int32_t rl_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     traj->range_valid = traj->range_reset = false;  // new observations: the range guard has them measured again
     traj->rtg_scan_valid = false;                   // new rewards: the return plane belongs to the old ones
     RL_REQUIRE(traj->d.n == env->cfg.n_lanes && traj->d.D == env->D, "trajectory shape does not match the env");
+    if (rl_module_is_recurrent(policy->kind) && env->A > 2)
+      throw RlError(RL_ERR_UNSUPPORTED, "recurrent chains are built for two actions: this env has more");
     RL_REQUIRE(policy->in_dim == env->D && policy->out_dim == env->A, "policy shape does not match the env");
-    if (policy->general) {  // any hidden_sizes: one launch sequence per step, either env family (advances t_global)
+    traj->n_actions = env->A;
+    // the fused index-env kernels are built for five states (Chain::default, MemoryGame::new(2, 3), the bandit's
+    // one-hot(5)): a MemoryGame of another size steps through the standalone env kernels
+    const bool fused_index_env = env->kind == RL_ENV_CARTPOLE || env->dev.chain_size == 5;
+    if (policy->general || (policy->kind == RL_MODULE_MLP && !fused_index_env)) {
+      // any hidden_sizes: one launch sequence per step, either env family (advances t_global)
       launch_gen_rollout(env, policy, traj);
       return;
     }
+    if (!fused_index_env && !policy->lane_kernels())
+      throw RlError(RL_ERR_UNSUPPORTED, "the fused recurrent rollout is built for index envs of five states");
     if (rl_module_is_recurrent(policy->kind) && policy->lane_kernels()) {  // a launch sequence per step
       seq_ensure(traj, policy, false);
       launch_stack_rollout(env, policy, traj);  // (advances t_global)

@@ -220,7 +220,13 @@ int32_t rl_actor_to_cbor(rl_env *env, rl_mlp *module, int32_t actor_kind, double
     w.key("observation_space");
     cbor_observation_space(w, env);
     w.key("action_space");
-    cbor_indexed_type_space(w);
+    if (env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT) {
+      w.map(1);  // IndexSpace { size } (memory.rs:66-68, bandits.rs:45-47; spaces/index.rs:19-22)
+      w.key("size");
+      w.uint(env->A);
+    } else {
+      cbor_indexed_type_space(w);  // CartPole, Chain: IndexedTypeSpace<..>
+    }
     w.key(actor_kind == RL_ACTOR_DQN ? "action_value_fn" : "policy_module");
     cbor_module(w, module, p);
     if (actor_kind == RL_ACTOR_DQN) {

@@ -124,6 +124,7 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
     rl_engine *e = env->eng;
     RL_REQUIRE(qnet->eng == e && opt->eng == e, "handles belong to different engines");
     RL_REQUIRE(opt->mod == qnet, "optimizer does not belong to the action-value module");
+    if (qnet->out_dim > 2) throw RlError(RL_ERR_UNSUPPORTED, "DQN kernels are built for 2 actions");
     RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A, "action-value module does not match the env");
     RL_REQUIRE(env->A == 2, "DQN kernels are built for 2-action envs");
     // DqnConfig<MB> is generic over the module (dqn.rs:26-39): feed-forward modules of any MlpConfig build (the fused

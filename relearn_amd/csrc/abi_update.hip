@@ -90,7 +90,14 @@ int32_t rl_trpo_config_default(rl_trpo_config *c) {
 static void check_policy(const rl_mlp *policy, const rl_traj *traj) {
   RL_REQUIRE(policy && traj, "NULL argument");
   RL_REQUIRE(policy->eng == traj->eng, "handles belong to different engines");
-  RL_REQUIRE(policy->in_dim == traj->d.D && policy->out_dim == 2, "policy shape does not match the trajectory");
+  RL_REQUIRE(policy->in_dim == traj->d.D && policy->out_dim >= 2, "policy shape does not match the trajectory");
+  // the action space of the recorded steps: the env's of the rollout that wrote them, or — a host-written action plane —
+  // at least the largest index it holds
+  RL_REQUIRE(traj->n_actions == 0 || policy->out_dim == traj->n_actions,
+             "policy outputs do not match the action count of the env this trajectory was collected on");
+  RL_REQUIRE(policy->out_dim > traj->max_action, "the trajectory holds an action index the policy has no output for");
+  if (policy->out_dim > 2 && policy->kind != RL_MODULE_MLP)
+    throw RlError(RL_ERR_UNSUPPORTED, "recurrent chains are built for two actions");
 }
 
 // gradient pass: PASS_INIT -> backward -> reduce(A+B) -> allreduce

@@ -39,10 +39,11 @@ struct CartPoleDev {
   uint64_t lane_offset;
   uint32_t max_steps;
   int32_t limit_kind;
-  uint32_t chain_size;   // RL_ENV_CHAIN / RL_ENV_MEMORY: number of states = one-hot width
+  uint32_t chain_size;   // RL_ENV_CHAIN / RL_ENV_MEMORY: number of states = one-hot width (MemoryGame: num_actions +
+                         // history_len)
   uint32_t mem_actions;  // RL_ENV_MEMORY: num_actions (0 selects Chain in the shared lane code)
   uint32_t bandit;       // RL_ENV_BANDIT: != 0; reward = bandit_r[action], every step terminates
-  float bandit_r[2];
+  float bandit_r[8];     // DeterministicBandit::from_values, 2..8 arms
 };
 
 struct EnvStateDev {
@@ -226,7 +227,9 @@ inline uint64_t rl_module_gates(int kind) { return kind == RL_MODULE_LSTM_MLP ? 
 
 constexpr uint32_t RL_MLP_MAX_HIDDEN = 4;   // hidden layers of a general MlpConfig
 constexpr uint32_t RL_MLP_MAX_WIDTH = 256;  // widest hidden layer
-constexpr uint32_t RL_TRAJ_MAX_OBS_DIM = 8;  // observation features of a trajectory (the envs here have 4 or 5)
+constexpr uint32_t RL_MLP_MAX_OUT = 8;      // outputs of a general MLP: a categorical policy over IndexSpace::new(2..8)
+constexpr uint32_t RL_TRAJ_MAX_OBS_DIM = 8;  // observation features of a trajectory (the envs here have 4 to 8)
+constexpr uint32_t RL_ENV_MIN_OBS_DIM = 4;   // narrowest observation the env kernels are built for
 constexpr uint32_t RL_RNN_MAX_LAYERS = 4;   // RnnBaseConfig::num_layers of a recurrent chain
 
 struct rl_mlp {
@@ -324,7 +327,7 @@ struct SeqDev {
 struct GenDev {
   float *act = nullptr, *tact = nullptr;  // [hidden units][rows]: activations of the last forward, their tangents
   float *delta = nullptr;                 // [2][widest layer][rows]: backward deltas (ping-pong)
-  float *z = nullptr, *tz = nullptr;      // [2][rows]: outputs and tangent outputs
+  float *z = nullptr, *tz = nullptr;      // [max(2, out_dim)][rows]: outputs and tangent outputs
   int32_t *no_interrupt = nullptr;        // != 0: the trajectory holds no Interrupt (the successor-value forward is skipped)
   uint64_t cap_act = 0, cap_tact = 0, cap_delta = 0, cap_z = 0, cap_tz = 0;
 };
@@ -372,8 +375,12 @@ struct rl_traj {
   TrajDev d;
   uint64_t B;  // T * n
   // update workspace
-  float *lp0 = nullptr;     // [2][B]
-  float *dz = nullptr;      // [2][B]
+  float *lp0 = nullptr;     // [act_planes][B]
+  float *dz = nullptr;      // [act_planes][B]
+  uint32_t act_planes = 2;  // one plane per action of the widest policy used so far (traj_ensure_action_planes)
+  // the action count of the env the last rollout recorded (0: the planes were written by the host, rl_traj_write), and
+  // the largest action index a host-written action plane holds: what a policy's out_dim is checked against
+  uint32_t n_actions = 0, max_action = 0;
   double *slabA = nullptr;  // [nbA][Pmax] per-workgroup partial sums (f64)
   double *slabB = nullptr;  // [nbB][4]
   float *vec = nullptr;     // reduced vector [Pmax + 4]

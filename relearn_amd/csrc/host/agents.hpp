@@ -117,6 +117,12 @@ class EnvLanes {
     check(rl_env_create(eng.handle(), &cfg_, &h_), eng.handle());
     check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
   }
+  // bandit lanes of any number of arms (rl_env_create_bandit)
+  EnvLanes(Engine &eng, const rl_env_config &cfg, const std::vector<double> &arm_values, double discount)
+      : eng_(eng), cfg_(cfg), discount_(discount) {
+    check(rl_env_create_bandit(eng.handle(), &cfg_, arm_values.data(), (uint32_t)arm_values.size(), &h_), eng.handle());
+    check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
+  }
   Engine &eng_;
   rl_env_config cfg_;
   rl_env *h_ = nullptr;
@@ -169,7 +175,9 @@ class ChainLanes : public EnvLanes {
   }
 };
 
-// `MemoryGame::new(2, 3)` x n_lanes, optionally under a step limit (src/envs/memory.rs); discount factor 1.0
+// `MemoryGame::new(num_actions, history_len)` x n_lanes, optionally under a step limit (src/envs/memory.rs); discount
+// factor 1.0.  4 <= num_actions + history_len, (+ 1 under a visible limit) <= 8 observation features; a policy for it has
+// num_actions outputs (MlpConfig::build_module(env.num_observation_features(), env.num_actions()))
 class MemoryGameLanes : public EnvLanes {
  public:
   MemoryGameLanes(Engine &eng, uint64_t n_lanes, uint64_t num_actions = 2, uint64_t history_len = 3,
@@ -196,7 +204,7 @@ class MemoryGameLanes : public EnvLanes {
   }
 };
 
-// `DeterministicBandit::from_values([v0, v1])` x n_lanes (src/envs/bandits.rs:109-116): every step is an episode,
+// `DeterministicBandit::from_values(values)` x n_lanes, 2..8 arms (src/envs/bandits.rs:109-116): every step is an episode,
 // reward = the chosen arm's value, discount factor 1.0 (bandits.rs:52-54).  The environment of the reference's universal
 // agent test (`train_deterministic_bandit`, src/agents/testing.rs:14-64).
 class DeterministicBanditLanes : public EnvLanes {
@@ -204,6 +212,9 @@ class DeterministicBanditLanes : public EnvLanes {
   DeterministicBanditLanes(Engine &eng, uint64_t n_lanes, double value0 = 0.0, double value1 = 1.0,
                            uint64_t seed_env = 0, uint64_t seed_actor = 1, uint64_t lane_offset = 0)
       : EnvLanes(eng, config(n_lanes, value0, value1, seed_env, seed_actor, lane_offset), 1.0) {}
+  DeterministicBanditLanes(Engine &eng, uint64_t n_lanes, const std::vector<double> &values, uint64_t seed_env = 0,
+                           uint64_t seed_actor = 1, uint64_t lane_offset = 0)
+      : EnvLanes(eng, config(n_lanes, 0.0, 0.0, seed_env, seed_actor, lane_offset), values, 1.0) {}
 
  private:
   static rl_env_config config(uint64_t n, double v0, double v1, uint64_t se, uint64_t sa, uint64_t off) {

@@ -119,6 +119,7 @@ void launch_gen_policy_pass(rl_traj *t, const rl_mlp *m, int mode, const float *
 void launch_gen_critic_fwd(rl_traj *t, const rl_mlp *m, uint64_t B_total);
 void launch_gen_backward(rl_traj *t, const rl_mlp *m, const int32_t *d_skip);
 void traj_ensure_slabs(rl_traj *t, uint64_t rowsA, uint64_t P, uint64_t rowsB);
+void traj_ensure_action_planes(rl_traj *t, uint32_t n_actions);  // lp0, dz: [n_actions][B]
 // kernels_gen_mfma.hip: the passes of a several-hidden-layer MLP as one fused matrix-pipe launch (false: shape not built)
 constexpr int RL_GEN_CRITIC = 100;  // mode: mean((V - target)^2); else PASS_INIT / PASS_PPO / PASS_EVAL / PASS_JVP
 bool gen_mfma_fits(const rl_traj *t, const rl_mlp *m);

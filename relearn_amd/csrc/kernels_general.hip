@@ -254,8 +254,9 @@ __global__ void __launch_bounds__(256) k_gen_wgrad(const float *__restrict__ dY,
   }
 }
 
-// per-sample policy terms from stored logits (and tangent logits): the arithmetic of k_policy_pass
-template <int MODE>
+// per-sample policy terms from stored logits (and tangent logits): the arithmetic of k_policy_pass, over the A logit
+// planes (and A tangent planes) of a categorical policy on IndexSpace::new(A)
+template <int MODE, int A>
 __global__ void __launch_bounds__(256) k_gen_policy_terms(TrajDev tr, const float *__restrict__ z,
                                                           const float *__restrict__ tz, float *__restrict__ lp0,
                                                           float *__restrict__ dz, double *__restrict__ slabB,
@@ -266,8 +267,12 @@ __global__ void __launch_bounds__(256) k_gen_policy_terms(TrajDev tr, const floa
   const size_t B = (size_t)tr.T * tr.n;
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
   for (size_t b = (size_t)blockIdx.x * 256 + threadIdx.x; b < B; b += (size_t)gridDim.x * 256) {
-    const float zz[2] = {z[b], z[B + b]};
-    const float tt[2] = {MODE == PASS_JVP ? tz[b] : 0.0f, MODE == PASS_JVP ? tz[B + b] : 0.0f};
+    float zz[A], tt[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+      zz[a] = z[(size_t)a * B + b];
+      tt[a] = MODE == PASS_JVP ? tz[(size_t)a * B + b] : 0.0f;
+    }
     policy_sample_terms<MODE>(zz, tt, (int)tr.action[b], MODE == PASS_JVP ? 0.0f : tr.adv[b], b, B, lp0, dz, inv_B, clip_lo,
                               clip_hi, s0, s1, s2);
   }
@@ -330,7 +335,8 @@ __global__ void __launch_bounds__(256) k_gen_any_interrupt(TrajDev tr, int32_t *
 }
 
 // PolicyActor::act for one step of every lane from stored logits: Categorical::new + the inverse-CDF draw with word
-// `word` of the lane's actor stream (the fused rollouts' arithmetic, kernels_rollout.hip)
+// `word` of the lane's actor stream (the fused rollouts' arithmetic, kernels_rollout.hip); A logit planes
+template <int A>
 __global__ void __launch_bounds__(256) k_gen_sample_actions(CartPoleDev c, const float *__restrict__ z, uint32_t n,
                                                             uint64_t word, uint8_t *__restrict__ actions) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -342,10 +348,11 @@ __global__ void __launch_bounds__(256) k_gen_sample_actions(CartPoleDev c, const
   for (int k = 0; k < 16; ++k)
     if (k == (int)(word & 15)) v = w[k];
   const float u = rl_u32_to_unit_f32(v);
-  const float zz[2] = {z[i], z[n + i]};
-  float lp[2];
-  log_softmax_lane<2>(zz, lp);
-  actions[i] = (uint8_t)categorical_sample_lane<2>(lp, u);
+  float zz[A], lp[A];
+#pragma unroll
+  for (int a = 0; a < A; ++a) zz[a] = z[(size_t)a * n + i];
+  log_softmax_lane<A>(zz, lp);
+  actions[i] = (uint8_t)categorical_sample_lane<A>(lp, u);
 }
 
 // one step's record: the observation the step started from, then what the env's step kernel left in its buffers
@@ -643,7 +650,7 @@ void dense(rl_engine *e, const DenseArgs &a) {
 
 // ---------------------------------------------------------------- workspace
 // activation planes [hidden unit][rows], tangent planes, two delta planes of the widest layer, outputs and tangent
-// outputs [2][rows]; grown on demand
+// outputs [max(2, out_dim)][rows]; grown on demand
 void gen_ensure(rl_traj *t, const rl_mlp *m, uint64_t rows, bool tangent, bool backward) {
   GenDev &g = t->gen;
   const uint64_t units = m->hidden_units() ? m->hidden_units() : 1;
@@ -658,12 +665,14 @@ void gen_ensure(rl_traj *t, const rl_mlp *m, uint64_t rows, bool tangent, bool b
     cap = need;
   };
   grow(g.act, g.cap_act, units * rows);
-  grow(g.z, g.cap_z, 2 * rows);
+  const uint64_t outs = m->out_dim > 2 ? m->out_dim : 2;  // (two planes at least: launch_gen_values keeps two value rows)
+  grow(g.z, g.cap_z, outs * rows);
   if (tangent) {
     grow(g.tact, g.cap_tact, units * rows);
-    grow(g.tz, g.cap_tz, 2 * rows);
+    grow(g.tz, g.cap_tz, outs * rows);
   }
   if (backward) grow(g.delta, g.cap_delta, 2ull * wmax * rows);
+  if (backward) traj_ensure_action_planes(t, m->out_dim);
   // the P-sized vectors and the slab of the update workspace grow with the module (training passes only).  The slab is
   // tracked on its own: the recurrent path grows the vectors too, but keeps its partials elsewhere
   if (backward && t->Pmax < m->P) {
@@ -704,6 +713,21 @@ void traj_ensure_slabs(rl_traj *t, uint64_t rowsA, uint64_t P, uint64_t rowsB) {
     t->slabB = dalloc<double>(rowsB * 4);
     t->cap_slabB = rowsB * 4;
   }
+}
+
+// lp0 and dz hold one plane of B samples per action: two from rl_traj_create, regrown the first time a wider policy's
+// pass runs on the trajectory (before that pass has written anything: what the planes held belongs to another policy)
+void traj_ensure_action_planes(rl_traj *t, uint32_t n_actions) {
+  if (n_actions <= t->act_planes) return;
+  for (float **p : {&t->lp0, &t->dz}) {
+    dfree(*p);
+    *p = nullptr;
+  }
+  t->act_planes = 0;
+  const uint64_t samples = (uint64_t)t->d.n * t->d.T;  // (the allocation's B; a resizable workspace plans smaller ones)
+  t->lp0 = dalloc<float>(n_actions * samples);
+  t->dz = dalloc<float>(n_actions * samples);
+  t->act_planes = n_actions;
 }
 
 void gen_free(rl_traj *t) {
@@ -772,14 +796,32 @@ void launch_gen_policy_pass(rl_traj *t, const rl_mlp *m, int mode, const float *
   float inv_B = 1.0f / (float)B_total;
   if (mode == PASS_DQN) inv_B = 2.0f / (float)B_total;
   dim3 grid(t->nbB), blk(256);
-#define TERMS(MM)                                                                                                \
-  hipLaunchKernelGGL((k_gen_policy_terms<MM>), grid, blk, 0, t->eng->stream, t->d, g.z, g.tz, t->lp0, t->dz, t->slabB, \
+#define TERMS(MM, AA)                                                                                                \
+  hipLaunchKernelGGL((k_gen_policy_terms<MM, AA>), grid, blk, 0, t->eng->stream, t->d, g.z, g.tz, t->lp0, t->dz, t->slabB, \
                      inv_B, d_skip, clip_lo, clip_hi)
-  if (mode == PASS_INIT) TERMS(PASS_INIT);
-  else if (mode == PASS_EVAL) TERMS(PASS_EVAL);
-  else if (mode == PASS_DQN) TERMS(PASS_DQN);
-  else if (mode == PASS_PPO) TERMS(PASS_PPO);
-  else TERMS(PASS_JVP);
+#define TERMS_A(AA)                                  \
+  case AA:                                           \
+    if (mode == PASS_INIT) TERMS(PASS_INIT, AA);     \
+    else if (mode == PASS_EVAL) TERMS(PASS_EVAL, AA); \
+    else if (mode == PASS_PPO) TERMS(PASS_PPO, AA);  \
+    else TERMS(PASS_JVP, AA);                        \
+    break
+  if (mode == PASS_DQN) {
+    RL_REQUIRE(m->out_dim == 2, "the DQN terms are built for two actions");
+    TERMS(PASS_DQN, 2);
+  } else {
+    switch (m->out_dim) {
+      TERMS_A(2);
+      TERMS_A(3);
+      TERMS_A(4);
+      TERMS_A(5);
+      TERMS_A(6);
+      TERMS_A(7);
+      TERMS_A(8);
+      default: throw RlError(RL_ERR_UNSUPPORTED, "policy pass: categorical policies over 2..8 actions are built");
+    }
+  }
+#undef TERMS_A
 #undef TERMS
   RL_HIP_CHECK(hipGetLastError());
   if (m->out_act != RL_ACT_IDENTITY && mode != PASS_EVAL) {
@@ -902,7 +944,7 @@ void launch_gen_rollout(rl_env *env, const rl_mlp *policy, rl_traj *t) {
 }
 
 // T steps of every lane as launch sequences: `forward(step)` leaves the policy's logits for env->d_obs ([D][n]) in z
-// ([2][n]); the rest of a step is PolicyActor::act, the env's step kernel and the step's record.  Advances t_global.
+// ([A][n], A = the env's action count); the rest of a step is PolicyActor::act, the env's step kernel and the step's record.  Advances t_global.
 void launch_rollout_stepwise(rl_env *env, rl_traj *t, const float *z, const std::function<void(uint32_t)> &forward) {
   rl_engine *e = env->eng;
   const uint32_t n = t->d.n, T = t->d.T;
@@ -927,7 +969,21 @@ void launch_rollout_stepwise(rl_env *env, rl_traj *t, const float *z, const std:
   for (uint32_t step = 0; step < T; ++step) {
     hipLaunchKernelGGL(k_gen_record_obs, grid, blk, 0, e->stream, t->d, env->d_obs, step);
     forward(step);
-    hipLaunchKernelGGL(k_gen_sample_actions, grid, blk, 0, e->stream, env->dev, z, n, env->t_global, env->d_actions);
+    switch (env->A) {
+#define SAMPLE(AA)                                                                                                      \
+  case AA:                                                                                                              \
+    hipLaunchKernelGGL(k_gen_sample_actions<AA>, grid, blk, 0, e->stream, env->dev, z, n, env->t_global, env->d_actions); \
+    break
+      SAMPLE(2);
+      SAMPLE(3);
+      SAMPLE(4);
+      SAMPLE(5);
+      SAMPLE(6);
+      SAMPLE(7);
+      SAMPLE(8);
+#undef SAMPLE
+      default: throw RlError(RL_ERR_UNSUPPORTED, "rollout: envs of 2..8 actions are built");
+    }
     launch_env_step(env);  // leaves reward, flag, the next observation and the interrupted successor in the env's buffers
     env->t_global += 1;
     hipLaunchKernelGGL(k_gen_record_step, grid, blk, 0, e->stream, t->d, env->d_actions, env->d_reward, env->d_flag,

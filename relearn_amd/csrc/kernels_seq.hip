@@ -54,6 +54,16 @@ __device__ __forceinline__ void chain_features(const CartPoleDev &c, const Chain
   if (D == 6) f[5] = (float)((double)s.steps_remaining / (double)c.max_steps);
 }
 
+// the same for any number of states (MemoryGame::new(num_actions, history_len): D = num_actions + history_len [+ 1]):
+// the remaining-steps feature follows the one-hot.  The standalone env kernels use it; the fused rollouts are built for
+// five states and keep chain_features.
+template <int D>
+__device__ __forceinline__ void index_features(const CartPoleDev &c, const ChainLane &s, float (&f)[D]) {
+#pragma unroll
+  for (int d = 0; d < D; ++d) f[d] = (uint32_t)d == s.state ? 1.0f : 0.0f;
+  if (c.limit_kind == RL_LIMIT_VISIBLE) f[D - 1] = (float)((double)s.steps_remaining / (double)c.max_steps);
+}
+
 // rand 0.8.5 `gen_range(0..range)` for u64/usize (UniformInt::sample_single): widening multiply, accept when the low
 // half is inside the zone `(range << leading_zeros(range)) - 1`; every attempt reads one u64 = stream words
 // (pos, pos + 1), low word first.  The loop ends with probability 1; 64 attempts bound it (each fails w.p. <= 1/2).
@@ -94,7 +104,7 @@ __device__ __forceinline__ void chain_reset(const CartPoleDev &c, ChainLane &s, 
 __device__ __forceinline__ int chain_step(const CartPoleDev &c, ChainLane &s, int action, uint32_t word,
                                           float &reward) {
   if (c.bandit) {  // Bandit::step (bandits.rs:66-77): Deterministic::sample draws nothing
-    reward = c.bandit_r[action];
+    reward = c.bandit_r[action & 7];
     return RL_SUCC_TERMINATE;
   }
   if (c.mem_actions) {
@@ -181,7 +191,7 @@ __global__ void k_chain_observe(CartPoleDev c, EnvStateDev st, uint32_t n, float
   ChainLane s;
   chain_load(st, i, s);
   float f[D];
-  chain_features<D>(c, s, f);
+  index_features<D>(c, s, f);
 #pragma unroll
   for (int d = 0; d < D; ++d) obs[(size_t)d * n + i] = f[d];
 }
@@ -199,12 +209,12 @@ __global__ void __launch_bounds__(256) k_chain_step(CartPoleDev c, EnvStateDev s
   int succ = chain_step(c, s, actions[i], stream_word(c.key_env, c.lane_offset + i, t_global), r);
   float f[D];
   if (succ == RL_SUCC_INTERRUPT) {
-    chain_features<D>(c, s, f);
+    index_features<D>(c, s, f);
 #pragma unroll
     for (int d = 0; d < D; ++d) term_obs[(size_t)d * n + i] = f[d];
   }
   if (succ != RL_SUCC_CONTINUE) chain_reset(c, s, c.lane_offset + i);
-  chain_features<D>(c, s, f);
+  index_features<D>(c, s, f);
 #pragma unroll
   for (int d = 0; d < D; ++d) obs_next[(size_t)d * n + i] = f[d];
   reward[i] = r;
@@ -974,23 +984,39 @@ void launch_chain_reset(rl_env *env) {
 void launch_chain_observe(rl_env *env, float *d_obs) {
   ProfScope ps(env->eng, RL_K_SMALL);
   uint32_t n = (uint32_t)env->cfg.n_lanes;
-  if (env->D == 5)
-    hipLaunchKernelGGL(k_chain_observe<5>, dim3(cdiv_s(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n,
-                       d_obs);
-  else
-    hipLaunchKernelGGL(k_chain_observe<6>, dim3(cdiv_s(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n,
-                       d_obs);
+  switch (env->D) {  // Chain, bandit: 5 or 6; MemoryGame: num_actions + history_len [+ 1], 4..8
+#define OBSERVE(DD)                                                                                                     \
+  case DD:                                                                                                              \
+    hipLaunchKernelGGL(k_chain_observe<DD>, dim3(cdiv_s(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n, \
+                       d_obs);                                                                                          \
+    break
+    OBSERVE(4);
+    OBSERVE(5);
+    OBSERVE(6);
+    OBSERVE(7);
+    OBSERVE(8);
+#undef OBSERVE
+    default: throw RlError(RL_ERR_UNSUPPORTED, "index env lanes: 4..8 observation features");
+  }
 }
 
 void launch_chain_step(rl_env *env) {
   ProfScope ps(env->eng, RL_K_ENV_STEP);
   uint32_t n = (uint32_t)env->cfg.n_lanes;
-  if (env->D == 5)
-    hipLaunchKernelGGL(k_chain_step<5>, dim3(cdiv_s(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n,
-                       env->t_global, env->d_actions, env->d_reward, env->d_flag, env->d_obs, env->d_term_obs);
-  else
-    hipLaunchKernelGGL(k_chain_step<6>, dim3(cdiv_s(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n,
-                       env->t_global, env->d_actions, env->d_reward, env->d_flag, env->d_obs, env->d_term_obs);
+  switch (env->D) {
+#define STEP(DD)                                                                                                     \
+  case DD:                                                                                                           \
+    hipLaunchKernelGGL(k_chain_step<DD>, dim3(cdiv_s(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n, \
+                       env->t_global, env->d_actions, env->d_reward, env->d_flag, env->d_obs, env->d_term_obs);      \
+    break
+    STEP(4);
+    STEP(5);
+    STEP(6);
+    STEP(7);
+    STEP(8);
+#undef STEP
+    default: throw RlError(RL_ERR_UNSUPPORTED, "index env lanes: 4..8 observation features");
+  }
 }
 
 void launch_rollout_gru(rl_env *env, const rl_mlp *policy, rl_traj *traj) {

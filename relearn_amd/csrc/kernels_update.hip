@@ -774,7 +774,9 @@ static const uint32_t *veto_word(const rl_traj *traj, const rl_mlp *m) {
 void launch_policy_pass(rl_traj *traj, const rl_mlp *policy, int mode, const float *d_tangent, uint64_t B_total,
                         const int32_t *d_skip, float clip_lo, float clip_hi) {
   ProfScope ps(traj->eng, RL_K_POLICY_PASS);
-  RL_REQUIRE(policy->out_dim == 2, "policy pass: only 2-action categorical policies are built");
+  // more than two actions: the per-layer kernels (rl_mlp_create_layers makes such a module general); the fused
+  // single-layer pass below is built for two
+  RL_REQUIRE(policy->out_dim == 2 || policy->general, "policy pass: the fused kernels are built for 2-action policies");
   if (policy->general) return launch_gen_policy_pass(traj, policy, mode, d_tangent, B_total, d_skip, clip_lo, clip_hi);
   float inv_B = 1.0f / (float)B_total;
   dim3 g(traj->nbB), b(256);

@@ -9,14 +9,27 @@
 
 #include <cfloat>
 
+// v[act] of a register array without dynamic indexing (which would put the array in scratch): a compare-select chain
+// over the unrolled index.  A = 2: `act == 0 ? v[0] : v[1]`.
+template <int A>
+__device__ __forceinline__ float select_action(const float (&v)[A], int act) {
+  float r = v[A - 1];
+#pragma unroll
+  for (int a = A - 2; a >= 0; --a) r = act == a ? v[a] : r;
+  return r;
+}
+
 // z: logits; dzt: tangent logits (PASS_JVP); act: the action taken; adv: advantage (DQN: the target).
 // Writes dz[a * B + b] (and lp0 in PASS_INIT); adds to the f64 sums s0, s1, s2 of the pass.
-template <int MODE>
-__device__ __forceinline__ void policy_sample_terms(const float (&z)[2], const float (&dzt)[2], int act, float adv,
+// A: the number of actions (IndexSpace::new(A)), 2..8, deduced from the logits; the fused single-layer kernels call it
+// at A = 2.  PASS_DQN is built for two actions.
+template <int MODE, int A>
+__device__ __forceinline__ void policy_sample_terms(const float (&z)[A], const float (&dzt)[A], int act, float adv,
                                                 size_t b, size_t B, float *__restrict__ lp0, float *__restrict__ dz,
                                                 float inv_B, float clip_lo, float clip_hi, double &s0, double &s1,
                                                 double &s2) {
-  constexpr int A = 2;
+  static_assert(A >= 2 && A <= 8, "categorical policies over 2..8 actions");
+  static_assert(MODE != PASS_DQN || A == 2, "the DQN terms are built for two actions");
   if (MODE == PASS_JVP) {
   float lp[A], p[A];
   log_softmax_lane<A>(z, lp);
@@ -45,7 +58,7 @@ __device__ __forceinline__ void policy_sample_terms(const float (&z)[2], const f
     // clipped surrogate of Ppo::update (policies/ppo.rs:124-137) and its torch-autograd gradient: minimum()
     // splits a tie between its arguments, clamp() passes the gradient inside [lo, hi] (bounds included)
     float l0a = lp0[(size_t)act * B + b];
-    float lpa = act == 0 ? lp[0] : lp[1];
+    float lpa = select_action<A>(lp, act);
     float ratio = rl_expf(lpa - l0a);
     float clipped = ratio < clip_lo ? clip_lo : (ratio > clip_hi ? clip_hi : ratio);
     float u1 = ratio * adv, u2 = clipped * adv;
@@ -61,7 +74,7 @@ __device__ __forceinline__ void policy_sample_terms(const float (&z)[2], const f
     return;
   }
   if (MODE == PASS_INIT) {
-    float lpa = act == 0 ? lp[0] : lp[1];
+    float lpa = select_action<A>(lp, act);
     s2 += (double)(lpa * adv);
     float ratio = rl_expf(lpa - lpa);
     float c = -(ratio * adv) * inv_B;
@@ -81,8 +94,8 @@ __device__ __forceinline__ void policy_sample_terms(const float (&z)[2], const f
     float l0[A];
 #pragma unroll
     for (int a = 0; a < A; ++a) l0[a] = lp0[(size_t)a * B + b];
-    float lpa = act == 0 ? lp[0] : lp[1];
-    float l0a = act == 0 ? l0[0] : l0[1];
+    float lpa = select_action<A>(lp, act);
+    float l0a = select_action<A>(l0, act);
     float ratio = rl_expf(lpa - l0a);
     float kl = 0.0f;
 #pragma unroll
