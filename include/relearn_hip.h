@@ -251,6 +251,11 @@ int32_t rl_env_set_state(rl_env *env, const double *state4, const int32_t *nv_po
  * library or the oracle. */
 int32_t rl_debug_stream_words(rl_engine *engine, uint64_t seed, uint64_t stream, uint64_t first_word, uint32_t n_words,
                               uint32_t *words_out);
+/* Test hook for the handles' device memory: bytes and allocations of device memory that the child handles of this
+ * process (envs, modules, optimisers, trajectories, DQN agents, summaries) and the scoped temporaries of the entry
+ * points hold at this moment.  Process-wide, so it takes no engine; either pointer may be NULL.  Whatever is created
+ * and destroyed between two reads leaves both numbers as they were (tests/test_gpu_device_memory.py). */
+int32_t rl_debug_device_memory(uint64_t *live_bytes, uint64_t *live_allocations);
 
 /* ---------------------------------------------------------------------------------------------
  * Modules.  `MlpConfig::build_module` with one hidden layer, ReLU, identity output

@@ -36,7 +36,7 @@ KERNEL_CLASSES = ["env_step", "rollout", "values", "gae", "policy_pass", "backwa
 
 # every symbol include/relearn_hip.h declares (checked by tests/test_abi_symbols.py against the header)
 ABI_SYMBOLS = [
-    "rl_abi_version", "rl_debug_stream_words", "rl_device_count", "rl_engine_create", "rl_engine_destroy", "rl_engine_sync",
+    "rl_abi_version", "rl_debug_stream_words", "rl_debug_device_memory", "rl_device_count", "rl_engine_create", "rl_engine_destroy", "rl_engine_sync",
     "rl_last_error", "rl_engine_info", "rl_engine_set_kernel_variant", "rl_timer_begin", "rl_timer_end", "rl_profile_enable", "rl_profile_read",
     "rl_comm_available", "rl_comm_library_paths", "rl_comm_unique_id", "rl_comm_init", "rl_comm_destroy", "rl_comm_init_host",
     "rl_comm_ipc_handle", "rl_comm_init_ipc", "rl_comm_selftest",
@@ -168,6 +168,13 @@ def lib():
         L.rl_last_error.argtypes = [C.c_void_p]
         _lib = L
     return _lib
+
+
+def debug_device_memory():
+    """(live bytes, live allocations) of device memory held by the handles of this process (test hook)"""
+    nbytes, count = C.c_uint64(), C.c_uint64()
+    _check(lib().rl_debug_device_memory(C.byref(nbytes), C.byref(count)))
+    return nbytes.value, count.value
 
 
 def _check(code, eng=None):

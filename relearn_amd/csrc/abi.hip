@@ -11,6 +11,32 @@
 
 thread_local std::string g_last_error_no_engine;
 
+// ---------------------------------------------------------------- the allocator behind DevMem (dev_mem.hpp)
+// live device bytes and allocations of the whole process: what rl_debug_device_memory reads
+static std::atomic<uint64_t> g_device_bytes{0}, g_device_allocations{0};
+
+void *rl_device_alloc(uint64_t bytes) {
+  void *p = nullptr;
+  RL_HIP_CHECK(hipMalloc(&p, bytes));
+  g_device_bytes += bytes;
+  g_device_allocations += 1;
+  return p;
+}
+
+void rl_device_free(void *p, uint64_t bytes) {
+  (void)hipFree(p);
+  g_device_bytes -= bytes;
+  g_device_allocations -= 1;
+}
+
+void *rl_host_alloc(uint64_t bytes, bool mapped) {
+  void *p = nullptr;
+  RL_HIP_CHECK(hipHostMalloc(&p, bytes, mapped ? hipHostMallocMapped : hipHostMallocDefault));
+  return p;
+}
+
+void rl_host_free(void *p) { (void)hipHostFree(p); }
+
 // ---------------------------------------------------------------- profiling scope
 ProfScope::ProfScope(rl_engine *eng, int c) : e(eng), cls(c) {
   if (!e->profiling) return;
@@ -216,17 +242,14 @@ void comm_agree(rl_engine *e) {
     return;
   }
   float h[2] = {mine ? 1.0f : 0.0f, 1.0f};
-  float *d = dalloc<float>(2);
-  try {
+  {
+    DevMem tmp;
+    float *d = tmp.alloc<float>(2);
     h2d(e, d, h, sizeof(h));
     rl_allreduce_sum_f32(e, d, 2);
     d2h(e, h, d, sizeof(h));
     ipc_check(e);
-  } catch (...) {
-    dfree(d);
-    throw;
   }
-  dfree(d);
   if (h[1] != (float)e->n_ranks)
     throw RlError(RL_ERR_COMM, "the collective's first all-reduce counted " + std::to_string((int)h[1]) + " of " +
                                    std::to_string(e->n_ranks) + " ranks");
@@ -447,7 +470,7 @@ int32_t rl_comm_init(rl_engine *e, int32_t rank, int32_t n_ranks, const uint8_t 
         grp->n_ranks = n_ranks;
         grp->bufs.assign(n_ranks, nullptr);
         RL_HIP_CHECK(hipSetDevice(e->device));
-        grp->d_bufs = dalloc<float *>(n_ranks);
+        RL_HIP_CHECK(hipMalloc((void **)&grp->d_bufs, n_ranks * sizeof(float *)));  // (lives as long as the process)
         if (const char *tw = std::getenv("RELEARN_LOOPBACK_TEST_WEIGHT")) {
           int r = -1;
           float w = 1.0f;
@@ -491,7 +514,8 @@ int32_t rl_comm_init(rl_engine *e, int32_t rank, int32_t n_ranks, const uint8_t 
       for (int i = 0; i < 128; ++i) h_id[i] = rank == 0 && id_ok ? (float)(unsigned char)id2.bytes[i] : 0.0f;
       h_id[128] = rank == 0 && !id_ok ? 1.0f : 0.0f;  // rank 0 has no id to offer
       h_id[129] = want_aux ? 0.0f : 1.0f;             // this rank declines
-      float *d_id = dalloc<float>(130);
+      DevMem tmp;
+      float *d_id = tmp.alloc<float>(130);
       void *comm2 = nullptr;
       try {
         h2d(e, d_id, h_id, sizeof(h_id));
@@ -519,11 +543,9 @@ int32_t rl_comm_init(rl_engine *e, int32_t rank, int32_t n_ranks, const uint8_t 
         }
       } catch (...) {
         if (comm2) g_rccl.CommDestroy(comm2);
-        dfree(d_id);
         throw;
       }
       if (comm2) g_rccl.CommDestroy(comm2);  // created here, but not everywhere
-      dfree(d_id);
       comm_agree(e);
     } catch (...) {  // the first communicator could not even carry the agreement: no collective at all
       if (e->comm_aux) g_rccl.CommDestroy(e->comm_aux);
@@ -575,30 +597,25 @@ int32_t rl_comm_selftest(rl_engine *e) {
     RL_REQUIRE(e, "engine is NULL");
     const uint32_t sizes[5] = {2048, 1030, 901, 64, 4};  // IPC_CAP; policy gradient + scalars; critic; one chunk; scalars
     std::vector<float> h(2048);
-    float *d = dalloc<float>(2048);
-    try {
-      for (uint32_t round = 0; round < 240; ++round) {
-        const uint32_t count = sizes[round % 5];
-        for (uint32_t i = 0; i < count; ++i) h[i] = (float)selftest_payload(round, (uint32_t)e->rank, i);
-        h2d(e, d, h.data(), count * sizeof(float));
-        rl_allreduce_sum_f32(e, d, count);
-        if (round % 16 == 15 || round == 239) {  // (between checks the collectives run back to back, as in an update)
-          d2h(e, h.data(), d, count * sizeof(float));
-          ipc_check(e);
-          for (uint32_t i = 0; i < count; ++i) {
-            int32_t want = 0;
-            for (int r = 0; r < e->n_ranks; ++r) want += selftest_payload(round, (uint32_t)r, i);
-            if (h[i] != (float)want)
-              throw RlError(RL_ERR_COMM, "collective self-test: wrong sum at element " + std::to_string(i) + " of round " +
-                                             std::to_string(round));
-          }
+    DevMem tmp;
+    float *d = tmp.alloc<float>(2048);
+    for (uint32_t round = 0; round < 240; ++round) {
+      const uint32_t count = sizes[round % 5];
+      for (uint32_t i = 0; i < count; ++i) h[i] = (float)selftest_payload(round, (uint32_t)e->rank, i);
+      h2d(e, d, h.data(), count * sizeof(float));
+      rl_allreduce_sum_f32(e, d, count);
+      if (round % 16 == 15 || round == 239) {  // (between checks the collectives run back to back, as in an update)
+        d2h(e, h.data(), d, count * sizeof(float));
+        ipc_check(e);
+        for (uint32_t i = 0; i < count; ++i) {
+          int32_t want = 0;
+          for (int r = 0; r < e->n_ranks; ++r) want += selftest_payload(round, (uint32_t)r, i);
+          if (h[i] != (float)want)
+            throw RlError(RL_ERR_COMM, "collective self-test: wrong sum at element " + std::to_string(i) + " of round " +
+                                           std::to_string(round));
         }
       }
-    } catch (...) {
-      dfree(d);
-      throw;
     }
-    dfree(d);
   });
 }
 
@@ -645,16 +662,6 @@ int32_t rl_cartpole_params_default(rl_cartpole_params *p) {
     p->max_angle = 12.0 * (3.14159265358979323846 / 180.0);  // 12.0f64.to_radians()
     p->discount_factor = 0.99;
   });
-}
-
-// every device allocation of an env handle (also the clean-up of a failed rl_env_create)
-static void env_release_device(rl_env *env) {
-  void *ptrs[] = {env->st.x, env->st.xdot, env->st.th, env->st.thdot, env->st.nv_pos, env->st.steps_remaining,
-                  env->st.reset_count, env->d_actions, env->d_flag, env->d_reward, env->d_obs, env->d_term_obs};
-  for (void *p : ptrs) dfree(p);
-  env->st = EnvStateDev{};
-  env->d_actions = env->d_flag = nullptr;
-  env->d_reward = env->d_obs = env->d_term_obs = nullptr;
 }
 
 // `arm_values` / `n_arms`: DeterministicBandit::from_values for rl_env_create_bandit (NULL: cfg->bandit_values, two arms)
@@ -729,19 +736,19 @@ static int32_t env_create(rl_engine *e, const rl_env_config *cfg, const double *
       d.bandit_r[a] = arm_values != nullptr ? (a < n_arms ? (float)arm_values[a] : 0.0f)
                                             : (a < 2 ? (float)cfg->bandit_values[a] : 0.0f);
     size_t n = cfg->n_lanes;
-    try {
-    env->st.x = dalloc<double>(n);
-    env->st.xdot = dalloc<double>(n);
-    env->st.th = dalloc<double>(n);
-    env->st.thdot = dalloc<double>(n);
-    env->st.nv_pos = dalloc<uint8_t>(n);
-    env->st.steps_remaining = dalloc<uint32_t>(n);
-    env->st.reset_count = dalloc<uint32_t>(n);
-    env->d_actions = dalloc<uint8_t>(n);
-    env->d_flag = dalloc<uint8_t>(n);
-    env->d_reward = dalloc<float>(n);
-    env->d_obs = dalloc<float>(n * env->D);
-    env->d_term_obs = dalloc<float>(n * env->D);
+    DevMem &mem = env->mem;
+    env->st.x = mem.alloc<double>(n);
+    env->st.xdot = mem.alloc<double>(n);
+    env->st.th = mem.alloc<double>(n);
+    env->st.thdot = mem.alloc<double>(n);
+    env->st.nv_pos = mem.alloc<uint8_t>(n);
+    env->st.steps_remaining = mem.alloc<uint32_t>(n);
+    env->st.reset_count = mem.alloc<uint32_t>(n);
+    env->d_actions = mem.alloc<uint8_t>(n);
+    env->d_flag = mem.alloc<uint8_t>(n);
+    env->d_reward = mem.alloc<float>(n);
+    env->d_obs = mem.alloc<float>(n * env->D);
+    env->d_term_obs = mem.alloc<float>(n * env->D);
     RL_HIP_CHECK(hipMemsetAsync(env->st.reset_count, 0, n * sizeof(uint32_t), e->stream));
     for (double *p : {env->st.x, env->st.xdot, env->st.th, env->st.thdot})
       RL_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(double), e->stream));
@@ -750,10 +757,6 @@ static int32_t env_create(rl_engine *e, const rl_env_config *cfg, const double *
     RL_HIP_CHECK(hipMemsetAsync(env->d_term_obs, 0, n * env->D * sizeof(float), e->stream));
     launch_env_reset(env.get());
     sync(e);
-    } catch (...) {  // (unique_ptr frees the host struct only)
-      env_release_device(env.get());
-      throw;
-    }
     e->live_handles += 1;
     *out = env.release();
   });
@@ -780,7 +783,6 @@ int32_t rl_env_destroy(rl_env *env) {
   (void)hipSetDevice(env->eng->device);
   (void)hipStreamSynchronize(env->eng->stream);
   (void)hipStreamSynchronize(env->eng->aux_stream);
-  env_release_device(env);
   rl_engine *eng = env->eng;
   delete env;
   engine_release_child(eng);
@@ -831,18 +833,21 @@ int32_t rl_debug_stream_words(rl_engine *engine, uint64_t seed, uint64_t stream,
     RL_REQUIRE(n_words > 0 && n_words <= (1u << 20), "n_words must be in [1, 2^20]");
     AgentKey key;
     rl_seed_from_u64(seed, key.w);
-    uint32_t *d = dalloc<uint32_t>(n_words);
-    try {
-      hipLaunchKernelGGL(k_debug_stream_words, dim3((n_words + 255) / 256), dim3(256), 0, engine->stream, key, stream,
-                         first_word, n_words, d);
-      RL_HIP_CHECK(hipGetLastError());
-      d2h(engine, words_out, d, (size_t)n_words * sizeof(uint32_t));
-    } catch (...) {
-      dfree(d);
-      throw;
-    }
-    dfree(d);
+    DevMem tmp;
+    uint32_t *d = tmp.alloc<uint32_t>(n_words);
+    hipLaunchKernelGGL(k_debug_stream_words, dim3((n_words + 255) / 256), dim3(256), 0, engine->stream, key, stream,
+                       first_word, n_words, d);
+    RL_HIP_CHECK(hipGetLastError());
+    d2h(engine, words_out, d, (size_t)n_words * sizeof(uint32_t));
   });
+}
+
+// live device memory of the whole process — every allocation a handle's DevMem has made and not yet freed (test hook:
+// what is created is released, on every path)
+int32_t rl_debug_device_memory(uint64_t *live_bytes, uint64_t *live_allocations) {
+  if (live_bytes) *live_bytes = g_device_bytes.load();
+  if (live_allocations) *live_allocations = g_device_allocations.load();
+  return RL_OK;
 }
 
 int32_t rl_env_upload_actions(rl_env *env, const uint8_t *actions) {
@@ -946,7 +951,7 @@ int32_t rl_mlp_create(rl_engine *e, uint32_t in_dim, uint32_t hidden, uint32_t o
     m->out_dim = out_dim;
     m->widths[0] = hidden;
     m->P = (uint64_t)hidden * in_dim + hidden + (uint64_t)out_dim * hidden + out_dim;
-    m->d_params = dalloc<float>(m->P);
+    m->d_params = m->mem.alloc<float>(m->P);
     RL_HIP_CHECK(hipMemsetAsync(m->d_params, 0, m->P * sizeof(float), e->stream));
     sync(e);
     e->live_handles += 1;
@@ -990,7 +995,7 @@ static int32_t mlp_create_config(rl_engine *e, uint32_t in_dim, const uint32_t *
     m->P = m->layer_offset(m->n_layers());
     // (bias-less layers read their dot products' starting value from zeros behind the parameters: rl_mlp::bias_offset)
     const size_t alloc = m->P + (has_bias ? 0 : RL_MLP_MAX_WIDTH);
-    m->d_params = dalloc<float>(alloc);
+    m->d_params = m->mem.alloc<float>(alloc);
     RL_HIP_CHECK(hipMemsetAsync(m->d_params, 0, alloc * sizeof(float), e->stream));
     sync(e);
     e->live_handles += 1;
@@ -1025,7 +1030,8 @@ static void seq_module_create(rl_engine *e, int kind, uint32_t in_dim, uint32_t 
     throw RlError(RL_ERR_BUILD_AGENT,
                   "supported recurrent chain shapes: in_dim 1..8, recurrent hidden 1..256, mlp_hidden 1..256, out_dim in {1,2}");
   RL_HIP_CHECK(hipSetDevice(e->device));
-  auto make = [&](uint32_t D, uint32_t H, uint32_t H2, uint32_t layers, bool bias) {
+  // (`mem`: who owns the parameters — the module itself, or the module a twin belongs to)
+  auto make = [&](DevMem *mem, uint32_t D, uint32_t H, uint32_t H2, uint32_t layers, bool bias) {
     std::unique_ptr<rl_mlp> m(new rl_mlp());
     m->eng = e;
     m->kind = kind;
@@ -1039,26 +1045,16 @@ static void seq_module_create(rl_engine *e, int kind, uint32_t in_dim, uint32_t 
     m->P = m->rnn_layer_offset(m->rnn_layers) + (uint64_t)H2 * H + H2 + A * H2 + A;
     // (bias-less recurrent weights: the gate rows start from zeros kept behind the parameters)
     const size_t alloc = m->P + (m->has_bias ? 0 : 4 * RL_MLP_MAX_WIDTH);
-    m->d_params = dalloc<float>(alloc);
+    m->d_params = (mem ? mem : &m->mem)->alloc<float>(alloc);
     RL_HIP_CHECK(hipMemsetAsync(m->d_params, 0, alloc * sizeof(float), e->stream));
     return m;
   };
-  std::unique_ptr<rl_mlp> m = make(in_dim, rnn_hidden, mlp_hidden, num_layers, rnn_bias);
+  std::unique_ptr<rl_mlp> m = make(nullptr, in_dim, rnn_hidden, mlp_hidden, num_layers, rnn_bias);
   if (!m->lane_kernels() && (in_dim != 5 || rnn_hidden != 128 || mlp_hidden != 128)) {
-    std::unique_ptr<rl_mlp> x;
-    try {
-      x = make(5, 128, 128, 1, true);  // every padding entry stays 0 for the life of the module
-      m->x_tmp = dalloc<float>(x->P);
-      m->x_tan = dalloc<float>(x->P);
-      RL_HIP_CHECK(hipMemsetAsync(m->x_tan, 0, x->P * sizeof(float), e->stream));
-    } catch (...) {
-      if (x) dfree(x->d_params);
-      dfree(m->x_tmp);
-      dfree(m->x_tan);
-      dfree(m->d_params);
-      throw;
-    }
-    m->exec = x.release();
+    m->exec = make(&m->mem, 5, 128, 128, 1, true).release();  // every padding entry stays 0 for the life of the module
+    m->x_tmp = m->mem.alloc<float>(m->exec->P);
+    m->x_tan = m->mem.alloc<float>(m->exec->P);
+    RL_HIP_CHECK(hipMemsetAsync(m->x_tan, 0, m->exec->P * sizeof(float), e->stream));
   }
   sync(e);
   e->live_handles += 1;
@@ -1232,16 +1228,8 @@ int32_t rl_mlp_destroy(rl_mlp *m) {
   (void)hipSetDevice(m->eng->device);
   (void)hipStreamSynchronize(m->eng->stream);
   (void)hipStreamSynchronize(m->eng->aux_stream);  // (a critic chain left in flight by rl_actor_critic_update_begin)
-  dfree(m->d_params);
-  dfree(m->d_wimg);
-  if (m->exec) {
-    dfree(m->exec->d_params);
-    delete m->exec;
-  }
-  dfree(m->x_tmp);
-  dfree(m->x_tan);
   rl_engine *eng = m->eng;
-  delete m;
+  delete m;  // (the twin of a narrow recurrent chain goes with it: ~rl_mlp)
   engine_release_child(eng);
   return RL_OK;
 }
@@ -1376,31 +1364,18 @@ int32_t rl_mlp_forward(rl_mlp *m, const float *rows, uint64_t n_rows, float *out
     std::vector<float> soa((size_t)n_rows * m->in_dim), res((size_t)n_rows * m->out_dim);
     for (uint64_t r = 0; r < n_rows; ++r)
       for (uint32_t d = 0; d < m->in_dim; ++d) soa[(size_t)d * n_rows + r] = rows[r * m->in_dim + d];
-    float *d_in = dalloc<float>(soa.size()), *d_out = dalloc<float>(res.size());
-    try {
-      h2d(e, d_in, soa.data(), soa.size() * sizeof(float));
-      if (m->general) {
-        rl_traj scratch{};  // (only the workspace of the per-layer kernels is used)
-        scratch.eng = e;
-        try {
-          launch_gen_forward(&scratch, m, d_in, n_rows, n_rows, d_out);
-          sync(e);
-        } catch (...) {
-          gen_free(&scratch);
-          throw;
-        }
-        gen_free(&scratch);
-      } else {
-        launch_mlp_forward_host_rows(m, d_in, n_rows, d_out);
-      }
-      d2h(e, res.data(), d_out, res.size() * sizeof(float));
-    } catch (...) {
-      dfree(d_in);
-      dfree(d_out);
-      throw;
+    DevMem tmp;
+    float *d_in = tmp.alloc<float>(soa.size()), *d_out = tmp.alloc<float>(res.size());
+    h2d(e, d_in, soa.data(), soa.size() * sizeof(float));
+    if (m->general) {
+      rl_traj scratch{};  // (only the workspace of the per-layer kernels is used; it goes with scratch.mem)
+      scratch.eng = e;
+      launch_gen_forward(&scratch, m, d_in, n_rows, n_rows, d_out);
+      sync(e);
+    } else {
+      launch_mlp_forward_host_rows(m, d_in, n_rows, d_out);
     }
-    dfree(d_in);
-    dfree(d_out);
+    d2h(e, res.data(), d_out, res.size() * sizeof(float));
     for (uint64_t r = 0; r < n_rows; ++r)
       for (uint32_t a = 0; a < m->out_dim; ++a) out[r * m->out_dim + a] = res[(size_t)a * n_rows + r];
   });
@@ -1469,30 +1444,29 @@ rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t o
   // (at least five observation planes whatever the logical width: the fused recurrent kernels are built for five features
   // and read the planes past the module's in_dim as zeros)
   uint64_t n = n_lanes, T = horizon, D = obs_dim > 5 ? obs_dim : 5;
-  t->d.obs = dalloc<float>(D * (T + 1) * n);
+  DevMem &mem = t->mem;
+  t->d.obs = mem.alloc<float>(D * (T + 1) * n);
   RL_HIP_CHECK(hipMemsetAsync(t->d.obs, 0, D * (T + 1) * n * 4, e->stream));
-  t->d.action = dalloc<uint8_t>(T * n);
-  t->d.reward = dalloc<float>(T * n);
-  t->d.flag = dalloc<uint8_t>(T * n);
-  t->d.term_obs = dalloc<float>(D * T * n);
-  t->d.values = dalloc<float>((T + 1) * n);
-  t->d.adv = dalloc<float>(T * n);
-  t->d.rtg = dalloc<float>(T * n);
+  t->d.action = mem.alloc<uint8_t>(T * n);
+  t->d.reward = mem.alloc<float>(T * n);
+  t->d.flag = mem.alloc<uint8_t>(T * n);
+  t->d.term_obs = mem.alloc<float>(D * T * n);
+  t->d.values = mem.alloc<float>((T + 1) * n);
+  t->d.adv = mem.alloc<float>(T * n);
+  t->d.rtg = mem.alloc<float>(T * n);
   t->d.tgt = t->d.rtg;  // the critic regresses on the returns unless rl_values_opt_update selects other targets
-  t->d.range = dalloc<uint32_t>(RL_RANGE_ALLOC_WORDS);
+  t->d.range = mem.alloc<uint32_t>(RL_RANGE_ALLOC_WORDS);
   RL_HIP_CHECK(hipMemsetAsync(t->d.range, 0, RL_RANGE_ALLOC_WORDS * sizeof(uint32_t), e->stream));
   {
-    void *hp = nullptr;
-    RL_HIP_CHECK(hipHostMalloc(&hp, 64, hipHostMallocMapped));
-    static_cast<volatile uint32_t *>(hp)[RL_GUARD_POLICY] = 0u;
-    static_cast<volatile uint32_t *>(hp)[RL_GUARD_CRITIC] = 0u;
+    t->h_range_err = mem.alloc_host<uint32_t>(16, /*mapped=*/true);
+    static_cast<volatile uint32_t *>(t->h_range_err)[RL_GUARD_POLICY] = 0u;
+    static_cast<volatile uint32_t *>(t->h_range_err)[RL_GUARD_CRITIC] = 0u;
     void *dp = nullptr;
-    RL_HIP_CHECK(hipHostGetDevicePointer(&dp, hp, 0));
-    t->h_range_err = static_cast<uint32_t *>(hp);
+    RL_HIP_CHECK(hipHostGetDevicePointer(&dp, t->h_range_err, 0));
     t->d.range_err = static_cast<uint32_t *>(dp);
   }
-  t->lp0 = dalloc<float>(2 * n * T);
-  t->dz = dalloc<float>(2 * n * T);
+  t->lp0 = mem.alloc<float>(2 * n * T);
+  t->dz = mem.alloc<float>(2 * n * T);
   t->Pmax = 128 * 5 + 128 + 2 * 128 + 2;
   traj_plan(t.get(), n * T);
   uint32_t rows = t->nbA;
@@ -1504,19 +1478,17 @@ rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t o
     if (cap < 2048) cap = 2048;
     rows = rowsB = cap;
   }
-  t->slabA = dalloc<double>((size_t)rows * t->Pmax);
-  t->slabB = dalloc<double>((size_t)rowsB * 4);
-  t->cap_slabA = (uint64_t)rows * t->Pmax;
-  t->cap_slabB = (uint64_t)rowsB * 4;
-  t->vec = dalloc<float>(t->Pmax + 4);
-  t->cg_x = dalloc<float>(t->Pmax);
-  t->cg_r = dalloc<float>(t->Pmax);
-  t->cg_p = dalloc<float>(t->Pmax);
-  t->prev_params = dalloc<float>(t->Pmax);
-  t->descent = dalloc<float>(t->Pmax);
+  t->slabA = mem.alloc<double>((size_t)rows * t->Pmax);
+  t->slabB = mem.alloc<double>((size_t)rowsB * 4);
+  t->vec = mem.alloc<float>(t->Pmax + 4);
+  t->cg_x = mem.alloc<float>(t->Pmax);
+  t->cg_r = mem.alloc<float>(t->Pmax);
+  t->cg_p = mem.alloc<float>(t->Pmax);
+  t->prev_params = mem.alloc<float>(t->Pmax);
+  t->descent = mem.alloc<float>(t->Pmax);
   t->max_losses = 4096;
-  t->losses = dalloc<float>(t->max_losses);
-  t->trpo = dalloc<TrpoStateDev>(1);
+  t->losses = mem.alloc<float>(t->max_losses);
+  t->trpo = mem.alloc<TrpoStateDev>(1);
   RL_HIP_CHECK(hipMemsetAsync(t->d.term_obs, 0, D * T * n * 4, e->stream));
   RL_HIP_CHECK(hipMemsetAsync(t->d.values, 0, (T + 1) * n * 4, e->stream));
   RL_HIP_CHECK(hipMemsetAsync(t->d.adv, 0, T * n * 4, e->stream));
@@ -1535,21 +1507,12 @@ int32_t rl_traj_create(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_
   });
 }
 
-static void seq_free(rl_traj *t);
-
 int32_t rl_traj_destroy(rl_traj *t) {
   if (!t) return RL_OK;
   (void)hipSetDevice(t->eng->device);
   (void)hipStreamSynchronize(t->eng->main_stream);
   (void)hipStreamSynchronize(t->eng->aux_stream);
   if (t->eng->pending.traj == t) t->eng->pending.active = false;  // (its pending update dies with it)
-  void *ptrs[] = {t->d.obs, t->d.action, t->d.reward, t->d.flag, t->d.term_obs, t->d.values, t->d.adv, t->d.rtg,
-                  t->lp0, t->dz, t->slabA, t->slabB, t->vec, t->cg_x, t->cg_r, t->cg_p, t->prev_params, t->descent,
-                  t->losses, t->trpo, t->td, t->aux_slabA, t->aux_slabB, t->aux_vec, t->d.range};
-  for (void *p : ptrs) dfree(p);
-  if (t->h_range_err) (void)hipHostFree(t->h_range_err);
-  seq_free(t);
-  gen_free(t);
   rl_engine *eng = t->eng;
   delete t;
   engine_release_child(eng);
@@ -1596,20 +1559,20 @@ int32_t rl_traj_write(rl_traj *t, int32_t field, const void *host, uint64_t byte
 }
 
 // ---------------------------------------------------------------- recurrent workspace
-// the P-sized vectors of the update workspace grow with the module
+// the P-sized vectors of the update workspace grow with the module: all six, or none and Pmax = 0 (the next call then
+// starts over instead of finding Pmax large enough and some vectors missing)
 void traj_ensure_pvec(rl_traj *t, uint64_t P) {
   if (t->Pmax >= P) return;
-  for (float **p : {&t->vec, &t->cg_x, &t->cg_r, &t->cg_p, &t->prev_params, &t->descent}) {
-    dfree(*p);
-    *p = nullptr;
+  float **const vecs[] = {&t->vec, &t->cg_x, &t->cg_r, &t->cg_p, &t->prev_params, &t->descent};
+  t->Pmax = 0;
+  for (float **p : vecs) t->mem.release(*p);
+  try {
+    for (float **p : vecs) *p = t->mem.alloc<float>(P + (p == &t->vec ? 4 : 0));
+  } catch (...) {
+    for (float **p : vecs) t->mem.release(*p);
+    throw;
   }
   t->Pmax = (uint32_t)P;
-  t->vec = dalloc<float>(t->Pmax + 4);
-  t->cg_x = dalloc<float>(t->Pmax);
-  t->cg_r = dalloc<float>(t->Pmax);
-  t->cg_p = dalloc<float>(t->Pmax);
-  t->prev_params = dalloc<float>(t->Pmax);
-  t->descent = dalloc<float>(t->Pmax);
 }
 
 void seq_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
@@ -1620,14 +1583,11 @@ void seq_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
   SeqDev &q = t->seq;
   uint64_t n = t->d.n, T = t->d.T;
   q.tiles = (uint32_t)(n / 32);  // (the output planes may already exist: the general-MLP path shares them)
-  if (q.out == nullptr) {
-    q.out = dalloc<float>(2 * T * n);
-    q.succ = dalloc<float>(2 * T * n);
-  }
-  if (training && q.act == nullptr) {
+  seq_ensure_outputs(t);
+  if (training && q.dpre == nullptr) {
     uint64_t blocks = T * q.tiles;
-    q.act = dalloc<float>(blocks * RL_SEQ_ACT_ARRAYS * 128 * 32);
-    q.dpre = dalloc<float>(blocks * RL_SEQ_DPRE_ARRAYS * 128 * 32);
+    t->mem.ensure(q.act, blocks * RL_SEQ_ACT_ARRAYS * 128 * 32);
+    q.dpre = t->mem.alloc<float>(blocks * RL_SEQ_DPRE_ARRAYS * 128 * 32);
     // weight-gradient partials: contiguous runs of (t, tile) blocks per workgroup, <= 1024 workgroups and at most
     // ~2048 samples accumulated in f32 before the f64 reduction
     uint64_t bpc = (blocks + 1023) / 1024;
@@ -1636,21 +1596,11 @@ void seq_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
     q.blocks_per_chunk = (uint32_t)bpc;
     q.chunks = (uint32_t)((blocks + bpc - 1) / bpc);
   }
-  if (training && q.P < mod->P) {
-    dfree(q.wg_slab);
-    q.wg_slab = nullptr;
+  if (training) {
     // + the rows of the head kernel (head columns) and of the backward recurrence (one per tile, input-side columns)
-    q.wg_slab = dalloc<float>((size_t)(q.chunks + (q.tiles > RL_SEQ_HEAD_ROWS ? q.tiles : RL_SEQ_HEAD_ROWS)) * mod->P);
-    q.P = mod->P;
+    t->mem.ensure(q.wg_slab, (uint64_t)(q.chunks + (q.tiles > RL_SEQ_HEAD_ROWS ? q.tiles : RL_SEQ_HEAD_ROWS)) * mod->P);
     traj_ensure_pvec(t, mod->P);
   }
-}
-
-static void seq_free(rl_traj *t) {
-  SeqDev &q = t->seq;
-  for (float *p : {q.act, q.dpre, q.out, q.succ, q.wg_slab}) dfree(p);
-  stack_free(t);
-  q = SeqDev{};
 }
 
 int32_t rl_seq_forward(rl_mlp *mod, rl_traj *traj, float *out, float *succ_out) {

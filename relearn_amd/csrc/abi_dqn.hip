@@ -32,23 +32,23 @@ static double dqn_exploration_rate(const rl_dqn *q, bool training) {
   return frac * (q->cfg.exploration_end - q->cfg.exploration_start) + q->cfg.exploration_start;
 }
 
-static ReplayDev replay_alloc(rl_engine *e, uint32_t N, uint32_t C, uint32_t E, uint32_t D) {
+static ReplayDev replay_alloc(rl_engine *e, DevMem &mem, uint32_t N, uint32_t C, uint32_t E, uint32_t D) {
   ReplayDev r{};
   r.N = N;
   r.C = C;
   r.E = E;
   r.D = D;
   size_t cn = (size_t)C * N;
-  r.rec = dalloc<ReplayRec>(cn);
-  r.next = dalloc<ReplayNext>(cn);
-  r.head = dalloc<uint32_t>(N);
-  r.count = dalloc<uint32_t>(N);
-  r.ep_head = dalloc<uint32_t>(N);
-  r.ep_count = dalloc<uint32_t>(N);
-  r.total = dalloc<uint32_t>(N);
-  r.ep_end = dalloc<uint32_t>((size_t)E * N);
-  r.actor_pos = dalloc<uint64_t>(N);
-  r.error = dalloc<int32_t>(1);
+  r.rec = mem.alloc<ReplayRec>(cn);
+  r.next = mem.alloc<ReplayNext>(cn);
+  r.head = mem.alloc<uint32_t>(N);
+  r.count = mem.alloc<uint32_t>(N);
+  r.ep_head = mem.alloc<uint32_t>(N);
+  r.ep_count = mem.alloc<uint32_t>(N);
+  r.total = mem.alloc<uint32_t>(N);
+  r.ep_end = mem.alloc<uint32_t>((size_t)E * N);
+  r.actor_pos = mem.alloc<uint64_t>(N);
+  r.error = mem.alloc<int32_t>(1);
   uint32_t *zero_u32[] = {r.head, r.count, r.ep_head, r.ep_count, r.total};
   for (uint32_t *p : zero_u32) RL_HIP_CHECK(hipMemsetAsync(p, 0, (size_t)N * 4, e->stream));
   RL_HIP_CHECK(hipMemsetAsync(r.actor_pos, 0, (size_t)N * 8, e->stream));
@@ -57,14 +57,9 @@ static ReplayDev replay_alloc(rl_engine *e, uint32_t N, uint32_t C, uint32_t E, 
   return r;
 }
 
-static void replay_free(ReplayDev &r) {
-  void *ptrs[] = {r.rec, r.next, r.head, r.count, r.ep_head, r.ep_count, r.total, r.ep_end, r.actor_pos, r.error};
-  for (void *p : ptrs) dfree(p);
-  r = ReplayDev{};
-}
-
 // point the minibatch workspace back at its own sample arrays (an all-at-once update leaves it looking at its last
-// minibatch inside the big arrays)
+// minibatch inside the big arrays).  For the builders and readers only: the workspace's pointers are views, and
+// destroying it while they look into the big arrays frees nothing it does not own (DevMem)
 static void dqn_own_arrays(rl_dqn *q) {
   if (!q->mb || !q->own_obs) return;
   q->mb->d.obs = q->own_obs;
@@ -74,35 +69,16 @@ static void dqn_own_arrays(rl_dqn *q) {
   q->td_in_kernel = false;
 }
 
-// every device allocation of a DQN handle (also the clean-up of a failed rl_dqn_create)
-static void dqn_release_device(rl_dqn *q) {
-  replay_free(q->rp);
-  void *ptrs[] = {q->d_agent_pos, q->d_ep_lane, q->d_ep_start, q->d_ep_len, q->d_ep_off, q->d_counts, q->d_flags,
-                  q->all_obs,     q->all_target, q->all_action, q->all_flag};
-  for (void *p : ptrs) dfree(p);
-  q->all_obs = q->all_target = nullptr;
-  q->all_action = q->all_flag = nullptr;
-  if (q->draw_stream) {
-    (void)hipStreamSynchronize(q->draw_stream);
-    (void)hipStreamDestroy(q->draw_stream);
+// what a DQN handle holds besides memory (also the clean-up of a failed rl_dqn_create): the draw stream, the events and
+// the minibatch workspace; the device and pinned memory goes with `mem` after this body
+rl_dqn::~rl_dqn() {
+  if (draw_stream) {
+    (void)hipStreamSynchronize(draw_stream);
+    (void)hipStreamDestroy(draw_stream);
   }
-  q->draw_stream = nullptr;
-  for (hipEvent_t ev : q->draw_events) (void)hipEventDestroy(ev);
-  q->draw_events.clear();
-  if (q->main_event) (void)hipEventDestroy(q->main_event);
-  q->main_event = nullptr;
-  if (q->h_counts) (void)hipHostFree(q->h_counts);
-  dfree(q->snap);
-  dfree(q->d_q);
-  dfree(q->d_q_next);
-  q->h_counts = nullptr;
-  q->d_agent_pos = nullptr;
-  q->d_ep_lane = q->d_ep_start = q->d_ep_len = q->d_ep_off = nullptr;
-  q->d_counts = nullptr;
-  q->d_flags = nullptr;
-  dqn_own_arrays(q);
-  if (q->mb) rl_traj_destroy(q->mb);
-  q->mb = nullptr;
+  for (hipEvent_t ev : draw_events) (void)hipEventDestroy(ev);
+  if (main_event) (void)hipEventDestroy(main_event);
+  if (mb) rl_traj_destroy(mb);
 }
 
 // With several ranks a failure must be raised on ALL of them: a rank that throws before a collective leaves its peers
@@ -149,20 +125,20 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
     q->opt = opt;
     q->cfg = *cfg;
     q->cfg.episode_capacity = E;
-    try {
-    q->rp = replay_alloc(e, (uint32_t)N, (uint32_t)cfg->buffer_capacity, (uint32_t)E, env->D);
-    q->d_agent_pos = dalloc<uint64_t>(1);
+    DevMem &mem = q->mem;
+    q->rp = replay_alloc(e, mem, (uint32_t)N, (uint32_t)cfg->buffer_capacity, (uint32_t)E, env->D);
+    q->d_agent_pos = mem.alloc<uint64_t>(1);
     RL_HIP_CHECK(hipMemsetAsync(q->d_agent_pos, 0, 8, e->stream));
     // take_while accepts episodes while total < minibatch_steps and every episode has >= 1 step
     q->max_eps = (uint32_t)cfg->minibatch_steps;
     q->max_steps_mb = cfg->minibatch_steps - 1 + cfg->buffer_capacity;
     // the episode lists of all opt_steps_per_update minibatches of an update are drawn in one launch
     const size_t nb = cfg->opt_steps_per_update ? cfg->opt_steps_per_update : 1;
-    q->d_ep_lane = dalloc<uint32_t>(nb * q->max_eps);
-    q->d_ep_start = dalloc<uint32_t>(nb * q->max_eps);
-    q->d_ep_len = dalloc<uint32_t>(nb * q->max_eps);
-    q->d_ep_off = dalloc<uint32_t>(nb * q->max_eps);
-    q->d_counts = dalloc<DqnCountsDev>(nb);
+    q->d_ep_lane = mem.alloc<uint32_t>(nb * q->max_eps);
+    q->d_ep_start = mem.alloc<uint32_t>(nb * q->max_eps);
+    q->d_ep_len = mem.alloc<uint32_t>(nb * q->max_eps);
+    q->d_ep_off = mem.alloc<uint32_t>(nb * q->max_eps);
+    q->d_counts = mem.alloc<DqnCountsDev>(nb);
     RL_HIP_CHECK(hipMemsetAsync(q->d_counts, 0, nb * sizeof(DqnCountsDev), e->stream));
     q->mb = traj_alloc(e, q->max_steps_mb, 1, env->D, true);
     {  // the fused step's range guard (bf16_tile.hpp): the words hold the magnitude range of every observation the
@@ -179,10 +155,6 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
     q->own_action = q->mb->d.action;
     q->own_flag = q->mb->d.flag;
     sync(e);
-    } catch (...) {  // (unique_ptr frees the host struct only)
-      dqn_release_device(q.get());
-      throw;
-    }
     e->live_handles += 1;
     *out = q.release();
   });
@@ -193,7 +165,6 @@ int32_t rl_dqn_destroy(rl_dqn *q) {
   (void)hipSetDevice(q->eng->device);
   (void)hipStreamSynchronize(q->eng->stream);
   (void)hipStreamSynchronize(q->eng->aux_stream);
-  dqn_release_device(q);
   rl_engine *eng = q->eng;
   delete q;
   engine_release_child(eng);
@@ -228,13 +199,7 @@ int32_t rl_dqn_collect(rl_dqn *q, uint64_t horizon, rl_dqn_collect_stats *stats)
     RL_REQUIRE(horizon > 0 && horizon < (1ull << 31), "bad horizon");
     rl_engine *e = q->eng;
     uint64_t N = q->rp.N;
-    if (q->flags_cap < horizon * N) {
-      dfree(q->d_flags);
-      q->d_flags = nullptr;
-      q->flags_cap = 0;
-      q->d_flags = dalloc<uint8_t>(horizon * N);
-      q->flags_cap = horizon * N;
-    }
+    q->mem.ensure(q->d_flags, horizon * N);
     // DqnAgent::actor(Training) (dqn.rs:200-211) + Bernoulli::new(p) of rand 0.8.5: p_int = (p * 2^64) as u64,
     // p == 1.0 always true without a draw
     double eps = dqn_exploration_rate(q, true);
@@ -242,7 +207,7 @@ int32_t rl_dqn_collect(rl_dqn *q, uint64_t horizon, rl_dqn_collect_stats *stats)
     int always = eps == 1.0 ? 1 : 0;
     uint64_t p_int = always ? ~0ull : (uint64_t)(eps * 18446744073709551616.0);
     if (q->qnet->general) {
-      if (!q->d_q) q->d_q = dalloc<float>(2 * (size_t)q->rp.N);
+      if (!q->d_q) q->d_q = q->mem.alloc<float>(2 * (size_t)q->rp.N);
       launch_rollout_dqn_general(q->env, q->qnet, q->mb, q->d_q, q->rp, (uint32_t)horizon, p_int, always, q->d_flags);
     } else {
       launch_rollout_dqn(q->env, q->qnet, q->rp, (uint32_t)horizon, p_int, always, q->d_flags, q->mb->d.range);
@@ -346,12 +311,7 @@ static void dqn_build_minibatch(rl_dqn *q, uint32_t k, const DqnCountsDev &c, ui
     launch_dqn_build_all(q->eng, q->rp, 1, c.n_eps, q->max_eps, q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o,
                          q->d_ep_off + o, q->d_counts + k, mb->d.obs, 0, mb->d.action, mb->d.adv, 0,
                          q->cfg.discount_factor, mb->d.flag);
-    if (q->cap_q_next < 2ull * c.n_steps) {
-      dfree(q->d_q_next);
-      q->d_q_next = nullptr;
-      q->d_q_next = dalloc<float>(2ull * q->max_steps_mb);
-      q->cap_q_next = 2ull * q->max_steps_mb;
-    }
+    q->mem.ensure(q->d_q_next, 2ull * q->max_steps_mb);  // (c.n_steps <= max_steps_mb: allocated once)
     launch_gen_forward(mb, q->qnet, mb->d.obs + c.n_steps, (size_t)2 * c.n_steps, c.n_steps, q->d_q_next);
     launch_dqn_td_targets(q->eng, mb->d.adv, mb->d.flag, q->d_q_next, c.n_steps, q->cfg.discount_factor);
     return;
@@ -417,12 +377,12 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
     const bool td = q->cfg.target == RL_DQN_TARGET_ONE_STEP_TD;
     const bool td_fused = td && e->kernel_variant == 0 && D == 5 && q->qnet->hidden == 128 && !q->qnet->general;
     const bool all_at_once = K > 1 && (!td || td_fused) && K * cap * (8 * D + 6) <= (8ull << 30);
-    if (all_at_once && !q->all_obs) {
-      q->all_obs = dalloc<float>(K * D * 2 * cap);
-      q->all_target = dalloc<float>(K * cap);
-      q->all_action = dalloc<uint8_t>(K * cap);
+    if (all_at_once) {  // (allocated by the first such update: K and cap are the handle's constants)
+      q->mem.ensure(q->all_obs, K * D * 2 * cap);
+      q->mem.ensure(q->all_target, K * cap);
+      q->mem.ensure(q->all_action, K * cap);
+      if (td) q->mem.ensure(q->all_flag, K * cap);
     }
-    if (all_at_once && td && !q->all_flag) q->all_flag = dalloc<uint8_t>(K * cap);
     // The draws do not depend on the network either, but they are one sequential chain through the agent's Prng (12 us
     // per minibatch on one CU).  One rank: the chain runs on a second stream in chunks of 2, 4, 8, ... minibatches
     // while the main stream trains on the chunks already drawn — the draw is faster than the training, so only the first
@@ -436,7 +396,7 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
       for (uint64_t first = 0, size = 2; first < K; first += size, size *= 2) chunk_end.push_back((uint32_t)(first + size < K ? first + size : K));
       if (!q->draw_stream) RL_HIP_CHECK(hipStreamCreateWithFlags(&q->draw_stream, hipStreamNonBlocking));
       if (!q->main_event) RL_HIP_CHECK(hipEventCreateWithFlags(&q->main_event, hipEventDisableTiming));
-      if (!q->h_counts) RL_HIP_CHECK(hipHostMalloc((void **)&q->h_counts, K * sizeof(DqnCountsDev), hipHostMallocDefault));
+      if (!q->h_counts) q->h_counts = q->mem.alloc_host<DqnCountsDev>(K, /*mapped=*/false);
       while (q->draw_events.size() < chunk_end.size()) {
         hipEvent_t ev;
         RL_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -472,7 +432,7 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
     const bool snapshot = pipelined || fused_shape;
     if (snapshot) {
       // (every state slot the optimiser's rule has: none for plain SGD, three for centered RMSProp with momentum)
-      if (!q->snap) q->snap = dalloc<float>(4 * Pq + 2);
+      if (!q->snap) q->snap = q->mem.alloc<float>(4 * Pq + 2);
       RL_HIP_CHECK(hipMemcpyAsync(q->snap, q->qnet->d_params, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
       for (int s = 0; s < 3; ++s)
         if (q->opt->d_state[s])
@@ -611,15 +571,10 @@ int32_t rl_dqn_replay_read(rl_dqn *q, int32_t field, void *host, uint64_t bytes)
       return;
     }
     RL_HIP_CHECK(hipSetDevice(q->eng->device));
-    void *planes = dalloc<uint8_t>(bytes);
-    try {
-      launch_replay_planes(q->eng, q->rp, field, planes);
-      d2h(q->eng, host, planes, bytes);
-    } catch (...) {
-      dfree(planes);
-      throw;
-    }
-    dfree(planes);
+    DevMem tmp;
+    void *planes = tmp.alloc<uint8_t>(bytes);
+    launch_replay_planes(q->eng, q->rp, field, planes);
+    d2h(q->eng, host, planes, bytes);
   });
 }
 

@@ -1,5 +1,5 @@
-// abi_internal.hpp — what the translation units of the C ABI (abi*.hip) share: error plumbing, device-memory and
-// copy helpers, and the few functions defined in one unit and used by another.
+// abi_internal.hpp — what the translation units of the C ABI (abi*.hip) share: error plumbing, copy helpers, and the
+// few functions defined in one unit and used by another.
 #pragma once
 #include <cmath>
 #include <cstdlib>
@@ -52,17 +52,6 @@ static inline int32_t guarded(rl_engine *eng, F &&f, bool settle = true) {
     (eng ? eng->last_error : g_last_error_no_engine) = "unknown error";
     return RL_ERR_INVALID_ARGUMENT;
   }
-}
-
-template <typename T>
-static inline T *dalloc(size_t count) {
-  void *p = nullptr;
-  RL_HIP_CHECK(hipMalloc(&p, (count ? count : 1) * sizeof(T)));
-  return (T *)p;
-}
-
-static inline void dfree(void *p) {
-  if (p) (void)hipFree(p);
 }
 
 // ---------------------------------------------------------------- helpers

@@ -4,17 +4,6 @@
 #include "abi_internal.hpp"
 #include "summary.hpp"
 
-static void summary_release_device(rl_summary *s) {
-  dfree(s->carry_len);
-  dfree(s->carry_ret);
-  dfree(s->acc);
-  dfree(s->part);
-  s->carry_len = nullptr;
-  s->carry_ret = nullptr;
-  s->acc = nullptr;
-  s->part = nullptr;
-}
-
 extern "C" {
 
 // OnlineStepsSummary::default per lane (summary.rs:186-194)
@@ -28,19 +17,14 @@ int32_t rl_summary_create(rl_engine *e, uint64_t n_lanes, rl_summary **out) {
     s->eng = e;
     s->n = n_lanes;
     s->max_groups = ((n_lanes + 3) / 4 + 3) / 4;  // workgroups cover at least 4 lane quads (kernels_summary.hip)
-    try {
-      s->carry_len = dalloc<uint64_t>(n_lanes);
-      s->carry_ret = dalloc<double>(n_lanes);
-      s->acc = dalloc<rl_steps_summary>(1);
-      s->part = dalloc<rl_steps_summary>(s->max_groups);
-      RL_HIP_CHECK(hipMemsetAsync(s->carry_len, 0, n_lanes * sizeof(uint64_t), e->stream));
-      RL_HIP_CHECK(hipMemsetAsync(s->carry_ret, 0, n_lanes * sizeof(double), e->stream));
-      RL_HIP_CHECK(hipMemsetAsync(s->acc, 0, sizeof(rl_steps_summary), e->stream));
-      sync(e);
-    } catch (...) {
-      summary_release_device(s.get());
-      throw;
-    }
+    s->carry_len = s->mem.alloc<uint64_t>(n_lanes);
+    s->carry_ret = s->mem.alloc<double>(n_lanes);
+    s->acc = s->mem.alloc<rl_steps_summary>(1);
+    s->part = s->mem.alloc<rl_steps_summary>(s->max_groups);
+    RL_HIP_CHECK(hipMemsetAsync(s->carry_len, 0, n_lanes * sizeof(uint64_t), e->stream));
+    RL_HIP_CHECK(hipMemsetAsync(s->carry_ret, 0, n_lanes * sizeof(double), e->stream));
+    RL_HIP_CHECK(hipMemsetAsync(s->acc, 0, sizeof(rl_steps_summary), e->stream));
+    sync(e);
     e->live_handles += 1;
     *out = s.release();
   });
@@ -50,7 +34,6 @@ int32_t rl_summary_destroy(rl_summary *s) {
   if (!s) return RL_OK;
   (void)hipSetDevice(s->eng->device);
   (void)hipStreamSynchronize(s->eng->main_stream);
-  summary_release_device(s);
   rl_engine *eng = s->eng;
   delete s;
   engine_release_child(eng);

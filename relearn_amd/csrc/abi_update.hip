@@ -356,35 +356,24 @@ static bool optimizer_has_slot(const rl_optimizer_config &c, int slot) {
   return slot == 0 || (slot == 1 && c.momentum > 0.0) || (slot == 2 && c.centered != 0);
 }
 
-static void optimizer_free(rl_adam *o) {
-  for (float *s : o->d_state) dfree(s);
-  dfree(o->d_step);
-  delete o;
-}
-
 static void optimizer_create(rl_mlp *module, const rl_optimizer_config &cfg, rl_adam **out) {
   rl_engine *e = module->eng;
   RL_HIP_CHECK(hipSetDevice(e->device));
-  rl_adam *o = new rl_adam();
-  try {
-    o->eng = e;
-    o->mod = module;
-    o->cfg = cfg;
-    o->error_epoch = e->error_epoch;
-    for (int s = 0; s < 3; ++s)
-      if (optimizer_has_slot(cfg, s)) {
-        o->d_state[s] = dalloc<float>(module->P);
-        RL_HIP_CHECK(hipMemsetAsync(o->d_state[s], 0, module->P * sizeof(float), e->stream));
-      }
-    o->d_step = dalloc<uint64_t>(1);
-    RL_HIP_CHECK(hipMemsetAsync(o->d_step, 0, sizeof(uint64_t), e->stream));
-    sync(e);
-  } catch (...) {
-    optimizer_free(o);
-    throw;
-  }
+  std::unique_ptr<rl_adam> o(new rl_adam());
+  o->eng = e;
+  o->mod = module;
+  o->cfg = cfg;
+  o->error_epoch = e->error_epoch;
+  for (int s = 0; s < 3; ++s)
+    if (optimizer_has_slot(cfg, s)) {
+      o->d_state[s] = o->mem.alloc<float>(module->P);
+      RL_HIP_CHECK(hipMemsetAsync(o->d_state[s], 0, module->P * sizeof(float), e->stream));
+    }
+  o->d_step = o->mem.alloc<uint64_t>(1);
+  RL_HIP_CHECK(hipMemsetAsync(o->d_step, 0, sizeof(uint64_t), e->stream));
+  sync(e);
   e->live_handles += 1;
-  *out = o;
+  *out = o.release();
 }
 
 int32_t rl_adam_create(rl_mlp *module, const rl_adam_config *cfg, rl_adam **out) {
@@ -418,7 +407,7 @@ int32_t rl_adam_destroy(rl_adam *o) {
   (void)hipStreamSynchronize(o->eng->stream);
   (void)hipStreamSynchronize(o->eng->aux_stream);  // (a critic chain left in flight by rl_actor_critic_update_begin)
   rl_engine *eng = o->eng;
-  optimizer_free(o);
+  delete o;
   engine_release_child(eng);
   return RL_OK;
 }
@@ -427,16 +416,11 @@ int32_t rl_optimizer_step_host(rl_adam *o, const float *grad) {
   return guarded(o ? o->mod->eng : nullptr, [&] {
     RL_REQUIRE(o && grad, "NULL argument");
     rl_engine *e = o->mod->eng;
-    float *d_g = dalloc<float>(o->mod->P);
-    try {
-      h2d(e, d_g, grad, o->mod->P * sizeof(float));
-      launch_adam_step_vec(o, d_g);
-      sync(e);
-    } catch (...) {
-      dfree(d_g);
-      throw;
-    }
-    dfree(d_g);
+    DevMem tmp;
+    float *d_g = tmp.alloc<float>(o->mod->P);
+    h2d(e, d_g, grad, o->mod->P * sizeof(float));
+    launch_adam_step_vec(o, d_g);
+    sync(e);
   });
 }
 
@@ -568,7 +552,7 @@ static void check_values_opt(const rl_mlp *critic, const rl_adam *opt, const rl_
 static void values_opt_targets(rl_mlp *critic, rl_traj *traj, const rl_values_opt_config *cfg) {
   if (traj->td == nullptr) {
     RL_HIP_CHECK(hipSetDevice(traj->eng->device));
-    traj->td = dalloc<float>((size_t)traj->d.T * traj->d.n);
+    traj->td = traj->mem.alloc<float>((size_t)traj->d.T * traj->d.n);
   }
   traj->d.tgt = traj->td;
   if (cfg->target == RL_VALUE_TARGET_REWARD_TO_GO && traj->rtg_scan_valid && traj->rtg_gamma == cfg->discount_factor) {
@@ -609,25 +593,12 @@ struct AuxChain {
   rl_engine *e;
   rl_traj *t;
   AuxChain(rl_traj *traj) : e(traj->eng), t(traj) {
-    if (t->aux_vec == nullptr) {  // all three or none: a failed allocation must not leave a half-made workspace behind
+    if (t->aux_slabB == nullptr) {  // (the last of the three: a failed allocation leaves a call that completes the set)
       RL_HIP_CHECK(hipSetDevice(e->device));
-      float *v = nullptr;
-      double *a = nullptr, *b = nullptr;
-      try {
-        v = dalloc<float>(t->Pmax + 4);
-        a = dalloc<double>(t->cap_slabA);
-        b = dalloc<double>(t->cap_slabB);
-      } catch (...) {
-        dfree(v);
-        dfree(a);
-        dfree(b);
-        throw;
-      }
-      t->aux_vec = v;
-      t->aux_slabA = a;
-      t->aux_slabB = b;
-      t->aux_cap_slabA = t->cap_slabA;
-      t->aux_cap_slabB = t->cap_slabB;
+      DevMem &mem = t->mem;
+      mem.ensure(t->aux_vec, (uint64_t)t->Pmax + 4);
+      mem.ensure(t->aux_slabA, mem.count_of(t->slabA));
+      mem.ensure(t->aux_slabB, mem.count_of(t->slabB));
     }
     swap();
     e->stream = e->aux_stream;
@@ -642,8 +613,6 @@ struct AuxChain {
     std::swap(t->vec, t->aux_vec);
     std::swap(t->slabA, t->aux_slabA);
     std::swap(t->slabB, t->aux_slabB);
-    std::swap(t->cap_slabA, t->aux_cap_slabA);
-    std::swap(t->cap_slabB, t->aux_cap_slabB);
     std::swap(t->last_rows, t->aux_last_rows);
   }
 };

@@ -111,7 +111,7 @@ int32_t rl_comm_ipc_handle(rl_engine *e, int32_t n_ranks, uint8_t handle_out[64]
       e->ipc_box = (float *)p;
       e->ipc_box_ranks = n_ranks;
       RL_HIP_CHECK(hipMemsetAsync(p, 0, bytes, e->stream));
-      e->ipc_err = dalloc<int32_t>(1);
+      RL_HIP_CHECK(hipMalloc((void **)&e->ipc_err, sizeof(int32_t)));
       RL_HIP_CHECK(hipMemsetAsync(e->ipc_err, 0, sizeof(int32_t), e->stream));
       sync(e);
       uint64_t ms = IPC_TIMEOUT_MS_DEFAULT;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/relearn_hip.h"
+#include "dev_mem.hpp"
 
 struct RlError : std::runtime_error {
   int32_t code;
@@ -126,8 +127,10 @@ struct TrpoStateDev {
 };
 
 // ---- host-side handle structs ----------------------------------------------------------------------
-struct RcclApi;  // dlopen'ed entry points (comm.cpp)
-struct LoopbackGroup;
+// Every child handle owns its device memory through its `mem` (dev_mem.hpp): `delete handle` frees it, whatever state a
+// failed create or a grown workspace left it in.  The pointer fields beside it, and every pointer in the kernel-visible
+// structs above, are views: they say where a kernel reads and writes, not who frees.
+struct LoopbackGroup;  // the in-process test collective (abi.hip)
 
 constexpr int RL_IPC_MAX_RANKS = 16;
 
@@ -209,6 +212,7 @@ struct rl_engine {
 
 struct rl_env {
   rl_engine *eng;
+  DevMem mem;
   rl_env_config cfg;
   int kind = RL_ENV_CARTPOLE;
   CartPoleDev dev;
@@ -234,6 +238,7 @@ constexpr uint32_t RL_RNN_MAX_LAYERS = 4;   // RnnBaseConfig::num_layers of a re
 
 struct rl_mlp {
   rl_engine *eng;
+  mutable DevMem mem;  // (mutable: the weight image is made on first use by launchers that hold the module const)
   uint32_t in_dim, hidden, out_dim;  // GRU_MLP: hidden = the MLP's hidden width
   uint64_t P;
   float *d_params = nullptr;
@@ -272,7 +277,8 @@ struct rl_mlp {
   // Its parameter image is refreshed from this module's flat vector before a pass (seq_exec, abi.hip); gradients and
   // tangents are gathered / scattered between the two layouts (launch_seq_pad / _unpad).  NULL: the module is the built
   // shape itself.
-  rl_mlp *exec = nullptr;
+  rl_mlp *exec = nullptr;  // (a host struct of its own; its parameter image lives in THIS module's `mem`)
+  ~rl_mlp() { delete exec; }
   float *x_tmp = nullptr, *x_tan = nullptr;  // [exec->P]: gather scratch, padded tangent (zero outside the real entries)
   // layer l (0 .. n_hidden; the last one is the output layer): fan-in, fan-out, offset of its kernel in the flat
   // parameter vector ([W, b] per layer, the reference's order)
@@ -305,8 +311,7 @@ struct SeqDev {
   float *succ = nullptr;    // [2][T][n] outputs at successor observations of cut episodes
   float *wg_slab = nullptr; // [chunks][P] partial weight gradients (f32)
   uint32_t tiles = 0, chunks = 0, blocks_per_chunk = 0;
-  uint64_t P = 0;
-  // stacked layers (kernels_seq_stack.hip; grow-only arrays, capacities in floats)
+  // stacked layers (kernels_seq_stack.hip; grow-only arrays: stack_ensure)
   struct Stack {
     float *st = nullptr;    // [10][L][H][n] per-lane states: two (h, c) sets in turn, the successor evaluation's, two tangent sets
     float *u = nullptr;     // [H2][n] the head's hidden units of the step at hand
@@ -318,18 +323,17 @@ struct SeqDev {
     float *ur = nullptr;    // [H2][B] the head's hidden units
     float *dg = nullptr;    // [L][4H][B] d loss / d pre-activations
     float *du = nullptr;    // [H2][B]
-    uint64_t cap_st = 0, cap_u = 0, cap_din = 0, cap_dst = 0, cap_rec = 0, cap_a1 = 0, cap_ur = 0, cap_dg = 0, cap_du = 0;
     uint32_t wg_rows = 0, wg_chunk = 0;  // weight-gradient partials: slab rows, samples per row
   } stack;
 };
 
-// workspace of the general-MLP path (kernels_general.hip), attached to a trajectory on first use
+// workspace of the general-MLP path (kernels_general.hip), attached to a trajectory on first use and grown with the
+// widest module and the largest row count that have used it (gen_ensure)
 struct GenDev {
   float *act = nullptr, *tact = nullptr;  // [hidden units][rows]: activations of the last forward, their tangents
   float *delta = nullptr;                 // [2][widest layer][rows]: backward deltas (ping-pong)
   float *z = nullptr, *tz = nullptr;      // [max(2, out_dim)][rows]: outputs and tangent outputs
   int32_t *no_interrupt = nullptr;        // != 0: the trajectory holds no Interrupt (the successor-value forward is skipped)
-  uint64_t cap_act = 0, cap_tact = 0, cap_delta = 0, cap_z = 0, cap_tz = 0;
 };
 
 // What the optimiser kernels (kernels_update.hip) get by value.  OptStep: the constants of one step, each formed in f64 on
@@ -358,6 +362,7 @@ struct OptState {
 // A first-order optimiser of any rule (the handle keeps the name of the rule it began with: no prototype changes).
 struct rl_adam {
   rl_engine *eng;  // kept separately: the module may be destroyed before its optimizer
+  DevMem mem;
   rl_mlp *mod;
   rl_optimizer_config cfg;  // cfg.kind is the rule
   // state slots, allocated where the configuration has them — Adam / AdamW: m, v; SGD: momentum buffer (momentum != 0);
@@ -372,6 +377,7 @@ struct rl_adam {
 
 struct rl_traj {
   rl_engine *eng;
+  DevMem mem;  // every array below, the workspaces `seq` and `gen` included; how much each holds: mem.count_of()
   TrajDev d;
   uint64_t B;  // T * n
   // update workspace
@@ -390,11 +396,10 @@ struct rl_traj {
   TrpoStateDev *trpo = nullptr;
   uint32_t nbA = 0, nbB = 0, nbV2 = 0, nbC = 0, Pmax = 0, max_losses = 0;
   uint32_t last_rows = 0;   // slab rows the last fused pass (launch_policy_v2 / launch_critic_step_v2) wrote
-  uint64_t cap_slabA = 0, cap_slabB = 0;  // doubles allocated (traj_ensure_slabs grows them)
-  // the auxiliary chain's own copies (rl_actor_critic_update; swapped in by AuxChain, allocated on first use)
+  // the auxiliary chain's own copies (rl_actor_critic_update; swapped in by AuxChain, allocated on first use at the
+  // sizes the main ones have then)
   double *aux_slabA = nullptr, *aux_slabB = nullptr;
   float *aux_vec = nullptr;
-  uint64_t aux_cap_slabA = 0, aux_cap_slabB = 0;
   uint32_t aux_last_rows = 0;
   // d.range[0..1] describe the current observation planes (false after anything rewrote them: traj_ensure_range, abi.hip);
   // `range_fixed`: the words are constants of the producer (the DQN minibatch workspace: CartPole-generated observations)
@@ -422,6 +427,8 @@ struct rl_traj {
 
 struct rl_dqn {
   rl_engine *eng;
+  DevMem mem;
+  ~rl_dqn();  // abi_dqn.hip: the draw stream, the events and `mb` (the memory goes with `mem`)
   rl_env *env;
   rl_mlp *qnet;
   rl_adam *opt;
@@ -431,7 +438,7 @@ struct rl_dqn {
   uint32_t *d_ep_lane = nullptr, *d_ep_start = nullptr, *d_ep_len = nullptr, *d_ep_off = nullptr;  // [max_eps]
   DqnCountsDev *d_counts = nullptr;
   uint8_t *d_flags = nullptr;        // [T_cap][N] successor codes of the last collection
-  uint64_t flags_cap = 0, last_horizon = 0;
+  uint64_t last_horizon = 0;
   uint32_t max_eps = 0;
   uint64_t max_steps_mb = 0;         // sample capacity of the minibatch workspace
   rl_traj *mb = nullptr;             // minibatch workspace: T = 1, n = current minibatch size
@@ -447,7 +454,6 @@ struct rl_dqn {
   DqnCountsDev *h_counts = nullptr;  // pinned, [K]
   float *d_q = nullptr, *d_q_next = nullptr;  // module outputs of a collection step [2][N] / at a minibatch's successor
                                               // observations (action-value modules on the per-layer kernels)
-  uint64_t cap_q_next = 0;
   float *snap = nullptr;             // parameters + optimiser state slots + step count as of the start of a pipelined update
   // ... `mb` then points into them (the last minibatch stays readable); its own arrays, for the one-at-a-time builder:
   float *own_obs = nullptr, *own_target = nullptr;

@@ -38,6 +38,13 @@ inline uint32_t *wimg_if_current(const rl_mlp *m) {
 }
 inline void wimg_invalidate(const rl_mlp *m) { m->wimg_epoch = 0; }
 
+// the output planes seq.out / seq.succ [2][T][n]: the recurrent paths and the general-MLP value pass share them
+inline void seq_ensure_outputs(rl_traj *t) {
+  const uint64_t B = (uint64_t)t->d.T * t->d.n;
+  t->mem.ensure(t->seq.out, 2 * B);
+  t->mem.ensure(t->seq.succ, 2 * B);
+}
+
 // kernels_update.hip
 enum PolicyPassMode { PASS_INIT = 0, PASS_EVAL = 1, PASS_JVP = 2, PASS_DQN = 3, PASS_PPO = 4 };
 // PASS_INIT : lp0 <- log pi(.|s); dz <- d(-mean(ratio*A))/dz at theta0; slabB <- {sum A, sum entropy}
@@ -112,7 +119,6 @@ void launch_gru_seq_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, floa
                             const int32_t *d_skip = nullptr);
 // kernels_general.hip: MLPs of any hidden_sizes (per-layer kernels; rl_mlp::general)
 void gen_ensure(rl_traj *t, const rl_mlp *m, uint64_t rows, bool tangent, bool backward);
-void gen_free(rl_traj *t);
 void launch_gen_forward(rl_traj *t, const rl_mlp *m, const float *x, size_t x_stride, uint64_t rows, float *out);
 void launch_gen_policy_pass(rl_traj *t, const rl_mlp *m, int mode, const float *d_tangent, uint64_t B_total,
                             const int32_t *d_skip, float clip_lo, float clip_hi);
@@ -134,7 +140,6 @@ void launch_gen_wgrad_planes(rl_traj *t, const float *dY, size_t dys, int N, con
 // kernels_seq_stack.hip: recurrent chains with RnnBaseConfig::num_layers > 1 (one thread per lane, the unit loop of a
 // layer dealt to a workgroup's waves; no lane-tile or width restriction)
 void stack_ensure(rl_traj *t, const rl_mlp *mod, bool training);
-void stack_free(rl_traj *t);
 void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj);
 void launch_stack_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float *d_succ, bool record,
                           const int32_t *d_skip);

@@ -656,39 +656,20 @@ void gen_ensure(rl_traj *t, const rl_mlp *m, uint64_t rows, bool tangent, bool b
   const uint64_t units = m->hidden_units() ? m->hidden_units() : 1;
   uint32_t wmax = 1;
   for (uint32_t l = 0; l < m->n_hidden; ++l) wmax = m->widths[l] > wmax ? m->widths[l] : wmax;
-  auto grow = [&](float *&p, uint64_t &cap, uint64_t need) {
-    if (cap >= need) return;
-    dfree(p);
-    p = nullptr;
-    cap = 0;
-    p = dalloc<float>(need);
-    cap = need;
-  };
-  grow(g.act, g.cap_act, units * rows);
+  DevMem &mem = t->mem;
+  mem.ensure(g.act, units * rows);
   const uint64_t outs = m->out_dim > 2 ? m->out_dim : 2;  // (two planes at least: launch_gen_values keeps two value rows)
-  grow(g.z, g.cap_z, outs * rows);
+  mem.ensure(g.z, outs * rows);
   if (tangent) {
-    grow(g.tact, g.cap_tact, units * rows);
-    grow(g.tz, g.cap_tz, outs * rows);
-  }
-  if (backward) grow(g.delta, g.cap_delta, 2ull * wmax * rows);
-  if (backward) traj_ensure_action_planes(t, m->out_dim);
-  // the P-sized vectors and the slab of the update workspace grow with the module (training passes only).  The slab is
-  // tracked on its own: the recurrent path grows the vectors too, but keeps its partials elsewhere
-  if (backward && t->Pmax < m->P) {
-    for (float **p : {&t->vec, &t->cg_x, &t->cg_r, &t->cg_p, &t->prev_params, &t->descent}) {
-      dfree(*p);
-      *p = nullptr;
-    }
-    t->Pmax = (uint32_t)m->P;
-    t->vec = dalloc<float>(t->Pmax + 4);
-    t->cg_x = dalloc<float>(t->Pmax);
-    t->cg_r = dalloc<float>(t->Pmax);
-    t->cg_p = dalloc<float>(t->Pmax);
-    t->prev_params = dalloc<float>(t->Pmax);
-    t->descent = dalloc<float>(t->Pmax);
+    mem.ensure(g.tact, units * rows);
+    mem.ensure(g.tz, outs * rows);
   }
   if (backward) {
+    mem.ensure(g.delta, 2ull * wmax * rows);
+    traj_ensure_action_planes(t, m->out_dim);
+    // the P-sized vectors and the slab of the update workspace grow with the module (training passes only).  The slab is
+    // tracked on its own: the recurrent path grows the vectors too, but keeps its partials elsewhere
+    traj_ensure_pvec(t, m->P);
     uint32_t rowsA = t->nbA;
     if (t->nbV2 > rowsA) rowsA = t->nbV2;
     if (t->nbC > rowsA) rowsA = t->nbC;
@@ -699,42 +680,19 @@ void gen_ensure(rl_traj *t, const rl_mlp *m, uint64_t rows, bool tangent, bool b
 // room for `rowsA` slab rows of P partial sums and `rowsB` rows of four scalars (the partials of any pass are dead once
 // its reduction has run, so growing drops them)
 void traj_ensure_slabs(rl_traj *t, uint64_t rowsA, uint64_t P, uint64_t rowsB) {
-  if (t->cap_slabA < rowsA * P) {
-    dfree(t->slabA);
-    t->slabA = nullptr;
-    t->cap_slabA = 0;
-    t->slabA = dalloc<double>(rowsA * P);
-    t->cap_slabA = rowsA * P;
-  }
-  if (t->cap_slabB < rowsB * 4) {
-    dfree(t->slabB);
-    t->slabB = nullptr;
-    t->cap_slabB = 0;
-    t->slabB = dalloc<double>(rowsB * 4);
-    t->cap_slabB = rowsB * 4;
-  }
+  t->mem.ensure(t->slabA, rowsA * P);
+  t->mem.ensure(t->slabB, rowsB * 4);
 }
 
 // lp0 and dz hold one plane of B samples per action: two from rl_traj_create, regrown the first time a wider policy's
 // pass runs on the trajectory (before that pass has written anything: what the planes held belongs to another policy)
 void traj_ensure_action_planes(rl_traj *t, uint32_t n_actions) {
   if (n_actions <= t->act_planes) return;
-  for (float **p : {&t->lp0, &t->dz}) {
-    dfree(*p);
-    *p = nullptr;
-  }
-  t->act_planes = 0;
+  t->act_planes = 0;  // (until both exist: a failure between them leaves a call that starts over)
   const uint64_t samples = (uint64_t)t->d.n * t->d.T;  // (the allocation's B; a resizable workspace plans smaller ones)
-  t->lp0 = dalloc<float>(n_actions * samples);
-  t->dz = dalloc<float>(n_actions * samples);
+  t->mem.ensure(t->lp0, n_actions * samples);
+  t->mem.ensure(t->dz, n_actions * samples);
   t->act_planes = n_actions;
-}
-
-void gen_free(rl_traj *t) {
-  GenDev &g = t->gen;
-  for (float *p : {g.act, g.tact, g.delta, g.z, g.tz}) dfree(p);
-  dfree(g.no_interrupt);
-  g = GenDev{};
 }
 
 // ---------------------------------------------------------------- forward (+ tangent) over `rows` samples
@@ -891,16 +849,13 @@ void launch_gen_backward(rl_traj *t, const rl_mlp *m, const int32_t *d_skip) {
 void launch_gen_values(rl_traj *t, const rl_mlp *critic) {
   const uint64_t n = t->d.n, T = t->d.T, B = T * n;
   SeqDev &q = t->seq;
-  if (q.out == nullptr) {
-    q.out = dalloc<float>(2 * B);
-    q.succ = dalloc<float>(2 * B);
-  }
+  seq_ensure_outputs(t);
   gen_ensure(t, critic, B, false, false);
   GenDev &g = t->gen;
   const size_t plane = (size_t)(T + 1) * n;
   // V(term_obs[t][lane]) for every (t, lane) — only the interrupted ones are used, and the whole forward is skipped
   // (device-side flag) when the trajectory holds none — V(obs[T][lane]), then V(obs[t])
-  if (!g.no_interrupt) g.no_interrupt = dalloc<int32_t>(1);
+  if (!g.no_interrupt) g.no_interrupt = t->mem.alloc<int32_t>(1);
   RL_HIP_CHECK(hipMemsetAsync(g.no_interrupt, 1, sizeof(int32_t), t->eng->stream));
   hipLaunchKernelGGL(k_gen_any_interrupt, dim3(256), dim3(256), 0, t->eng->stream, t->d, g.no_interrupt);
   auto fwd = [&](const float *x, size_t xs, uint64_t rows, float *out, const int32_t *skip) {

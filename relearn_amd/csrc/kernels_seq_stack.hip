@@ -588,15 +588,6 @@ StackWs stack_ws(const rl_traj *t) {
   return w;
 }
 
-void grow(float *&p, uint64_t &cap, uint64_t want) {
-  if (cap >= want) return;
-  dfree(p);
-  p = nullptr;
-  cap = 0;
-  p = dalloc<float>(want);
-  cap = want;
-}
-
 inline uint32_t cdiv_k(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 }  // namespace
@@ -607,21 +598,19 @@ void stack_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
   SeqDev &q = t->seq;
   SeqDev::Stack &k = q.stack;
   const uint64_t n = t->d.n, T = t->d.T, B = T * n, L = mod->rnn_layers, H = mod->gru_hidden, H2 = mod->hidden;
-  if (q.out == nullptr) {
-    q.out = dalloc<float>(2 * B);
-    q.succ = dalloc<float>(2 * B);
-  }
-  grow(k.st, k.cap_st, 2 * N_SETS * L * H * n);
-  grow(k.u, k.cap_u, H2 * n);
-  if (k.z == nullptr) k.z = dalloc<float>(2 * n);
+  DevMem &mem = t->mem;
+  seq_ensure_outputs(t);
+  mem.ensure(k.st, 2 * N_SETS * L * H * n);
+  mem.ensure(k.u, H2 * n);
+  if (k.z == nullptr) k.z = mem.alloc<float>(2 * n);
   if (!training) return;
-  grow(k.din, k.cap_din, H * n);
-  grow(k.dst, k.cap_dst, 2 * L * H * n);
-  grow(k.rec, k.cap_rec, L * RPN * H * B);
-  grow(k.a1, k.cap_a1, H * B);
-  grow(k.ur, k.cap_ur, H2 * B);
-  grow(k.dg, k.cap_dg, L * 4 * H * B);
-  grow(k.du, k.cap_du, H2 * B);
+  mem.ensure(k.din, H * n);
+  mem.ensure(k.dst, 2 * L * H * n);
+  mem.ensure(k.rec, L * RPN * H * B);
+  mem.ensure(k.a1, H * B);
+  mem.ensure(k.ur, H2 * B);
+  mem.ensure(k.dg, L * 4 * H * B);
+  mem.ensure(k.du, H2 * B);
   // weight-gradient partials: at most 64 slab rows (the matrices are large: P doubles per row)
   uint64_t rows = t->nbA < 64 ? t->nbA : 64;
   uint64_t chunk = (B + rows - 1) / rows;
@@ -630,12 +619,6 @@ void stack_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
   k.wg_rows = (uint32_t)((B + chunk - 1) / chunk);
   traj_ensure_slabs(t, k.wg_rows, mod->P, t->nbB);
   traj_ensure_pvec(t, mod->P);
-}
-
-void stack_free(rl_traj *t) {
-  SeqDev::Stack &k = t->seq.stack;
-  for (float *p : {k.st, k.u, k.z, k.din, k.dst, k.rec, k.a1, k.ur, k.dg, k.du}) dfree(p);
-  k = SeqDev::Stack{};
 }
 
 void launch_stack_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float *d_succ, bool record,

@@ -886,9 +886,7 @@ const uint32_t *wimg_ensure(const rl_mlp *m) {
   rl_engine *e = m->eng;
   if (m->d_wimg == nullptr) {
     RL_HIP_CHECK(hipSetDevice(e->device));
-    void *p = nullptr;
-    RL_HIP_CHECK(hipMalloc(&p, (size_t)bt::WIMG_WORDS * sizeof(uint32_t)));
-    m->d_wimg = static_cast<uint32_t *>(p);
+    m->d_wimg = m->mem.alloc<uint32_t>(bt::WIMG_WORDS);
     m->wimg_epoch = 0;
   }
   if (m->wimg_epoch != e->call_epoch) {

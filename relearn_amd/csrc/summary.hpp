@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "../../include/relearn_hip.h"
+#include "dev_mem.hpp"
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define RL_SUM_HD __host__ __device__ inline
@@ -39,6 +40,7 @@ struct ReplayRec;
 
 struct rl_summary {
   rl_engine *eng;
+  DevMem mem;
   uint64_t n = 0;
   uint64_t *carry_len = nullptr;  // [n] length of the episode in progress
   double *carry_ret = nullptr;    // [n] its return
