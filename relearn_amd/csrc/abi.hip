@@ -1664,25 +1664,4 @@ int32_t rl_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   }, false);
 }
 
-int32_t rl_gae(rl_traj *traj, const rl_mlp *critic, float gamma, float lambda) {
-  return guarded(traj ? traj->eng : nullptr, [&] {
-    RL_REQUIRE(traj && critic, "NULL argument");
-    RL_REQUIRE(critic->in_dim == traj->d.D && critic->out_dim == 1, "critic shape does not match the trajectory");
-    if (rl_module_is_recurrent(critic->kind)) {
-      SeqScope sc(traj, critic);
-      seq_ensure(traj, sc.x, false);
-      launch_gru_seq_forward(traj, sc.x, traj->seq.out, traj->seq.succ, nullptr);
-      launch_seq_gae(traj, gamma, lambda);
-      return;
-    }
-    if (critic->general) {  // values and successor values as arrays, then the array-fed scan of the recurrent path
-      launch_gen_values(traj, critic);
-      launch_seq_gae(traj, gamma, lambda);
-      return;
-    }
-    launch_values(traj, critic);
-    launch_gae(traj, critic, gamma, lambda);
-  });
-}
-
 }  // extern "C"

@@ -333,8 +333,6 @@ static void dqn_sample_minibatch(rl_dqn *q, int sequential) {
 // between them the reduction and the (elementwise) step are one launch
 static void dqn_gradient(rl_dqn *q, rl_adam *step_opt = nullptr, int loss_slot = -1) {
   rl_traj *mb = q->mb;
-  uint32_t P = (uint32_t)q->qnet->P;
-  uint32_t rowsA, rowsB;
   // targets given (reward-to-go, or one-step TD built beforehand): two critic-step channels per SIMD
   // (kernels_critic.hip, k_critic_step_mfma<2>); targets formed inside the launch (one-step TD on the current network):
   // k_dqn_step_bf16
@@ -342,19 +340,19 @@ static void dqn_gradient(rl_dqn *q, rl_adam *step_opt = nullptr, int loss_slot =
   if (q->eng->kernel_variant == 0)
     fused = q->td_in_kernel ? launch_dqn_step_bf16(mb, q->qnet, q->last_total_steps, q->cfg.discount_factor)
                             : launch_dqn_step_pair(mb, q->qnet, q->last_total_steps);
-  if (fused) {
-    rowsA = rowsB = mb->nbV2;
-  } else {
-    launch_policy_pass(mb, q->qnet, PASS_DQN, nullptr, q->last_total_steps, nullptr);
-    launch_mlp_backward(mb, q->qnet, nullptr);
-    rowsA = mb->nbA;
-    rowsB = mb->nbB;
-  }
+  // the other kernels: the RUN_DQN row of the update passes (abi_update.hip), up to the slabs.  (A drawn minibatch has
+  // at least one step, so the count is never the 0 that would ask for the workspace's own.)
+  PassRequest pass(RUN_DQN);
+  pass.B_total = q->last_total_steps;
+  pass.reduce = false;
+  // (the two fused launchers report their rows in nbV2)
+  const SlabRows rows = fused ? SlabRows{mb->nbV2, mb->nbV2} : run_pass(q->qnet, mb, pass);
   if (step_opt && !q->eng->has_collective()) {
-    launch_reduce_adam(mb, step_opt, rowsA, rowsB, loss_slot, q->last_total_steps);
+    launch_reduce_adam(mb, step_opt, rows.A, rows.B, loss_slot, q->last_total_steps);
     return;
   }
-  launch_reduce(mb, P, true, true, rowsA, rowsB);
+  const uint32_t P = (uint32_t)q->qnet->P;
+  launch_reduce(mb, P, true, true, rows.A, rows.B);
   rl_allreduce_sum_f32(q->eng, mb->vec, P + 4);
   if (step_opt) launch_adam_step(mb, step_opt, loss_slot, q->last_total_steps);
 }
@@ -375,7 +373,11 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
     // (a second forward over the successor observations, which the gather leaves in time slot 1 of the workspace); the
     // other kernels still build those minibatches one step at a time.
     const bool td = q->cfg.target == RL_DQN_TARGET_ONE_STEP_TD;
-    const bool td_fused = td && e->kernel_variant == 0 && D == 5 && q->qnet->hidden == 128 && !q->qnet->general;
+    // Do the fused 5-128-2 kernels take this handle's minibatches?  Asked once per update, before the minibatch sizes
+    // are known: without the element-offset term, which the launchers test per minibatch.  (Two outputs and a
+    // feed-forward module are rl_dqn_create's conditions; the workspace has the store's D features.)
+    const bool fused_shape = e->kernel_variant == 0 && fused_5_128_fits(q->mb, q->qnet, 2, /*offsets=*/false);
+    const bool td_fused = td && fused_shape;
     const bool all_at_once = K > 1 && (!td || td_fused) && K * cap * (8 * D + 6) <= (8ull << 30);
     if (all_at_once) {  // (allocated by the first such update: K and cap are the handle's constants)
       q->mem.ensure(q->all_obs, K * D * 2 * cap);
@@ -428,7 +430,6 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
     const uint64_t Pq = q->qnet->P, host_step0 = q->opt->host_step;
     // (the fused gradient kernel's range guard reports after the steps it could not vouch for have run: the same
     // all-or-nothing rule — saved, and put back when the guard fires)
-    const bool fused_shape = e->kernel_variant == 0 && D == 5 && q->qnet->hidden == 128 && !q->qnet->general;
     const bool snapshot = pipelined || fused_shape;
     if (snapshot) {
       // (every state slot the optimiser's rule has: none for plain SGD, three for centered RMSProp with momentum)

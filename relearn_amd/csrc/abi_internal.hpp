@@ -109,6 +109,28 @@ static inline void range_discard(rl_traj *t) {
   }
 }
 
+// ---------------------------------------------------------------- one gradient / evaluation pass (abi_update.hip)
+// The pass kinds of run_pass; a policy kind is the PolicyPassMode its launchers take.
+enum PassKind { RUN_INIT = PASS_INIT, RUN_EVAL = PASS_EVAL, RUN_JVP = PASS_JVP, RUN_DQN = PASS_DQN, RUN_PPO = PASS_PPO,
+                RUN_CRITIC, RUN_KINDS };
+struct SlabRows {
+  uint32_t A, B;  // rows of slabA / slabB a feed-forward pass wrote
+};
+struct PassRequest {
+  PassRequest(PassKind k) : kind(k) {}  // (a bare kind is a whole request; every other field is set by its name)
+  PassKind kind;
+  const float *tangent = nullptr;     // RUN_JVP: the vector of the product
+  const int32_t *skip = nullptr;      // device flag: the launches are no-ops once it is set (RUN_EVAL, RUN_JVP)
+  float clip_lo = 0.0f, clip_hi = 0.0f;  // RUN_PPO
+  bool forward_only = false;  // a recurrent module's per-sample sums alone, without the backward through time (the
+                              // feed-forward passes are one fused launch and always run whole)
+  bool reduce = true;         // false: stop at the slabs (a caller that fuses the reduction with its optimiser step;
+                              // feed-forward modules)
+  uint64_t B_total = 0;       // samples over all ranks; 0: the trajectory's (b_total)
+};
+// (C++ linkage: shared between abi_update.hip and abi_dqn.hip without an unmangled name in the library's exports)
+SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req);
+
 // ---------------------------------------------------------------- shared between the units (C linkage like the entry
 // points they sit next to)
 extern "C" {

@@ -1,13 +1,33 @@
-// abi_update.hip — extern "C" entry points of include/relearn_hip.h, part: policy / critic updates (TRPO, PPO, REINFORCE, value fitting) (host side only; kernels live in kernels_*.hip).
+// abi_update.hip — extern "C" entry points of include/relearn_hip.h, part: advantages and policy / critic updates (GAE, TRPO, PPO, REINFORCE, value fitting) (host side only; kernels live in kernels_*.hip).
 #include "abi_internal.hpp"
 
-extern "C" {
+// ---------------------------------------------------------------- one gradient / evaluation pass
+// Every update entry point is made of these: choose the kernel family of the module, enqueue forward, backward and slab
+// reduction, all-reduce the slice of traj->vec the pass produced.  What differs between the passes is this table:
+//   backward  there is one, and it leaves the gradient: slab A is reduced (feed-forward) and vec[0..P) all-reduced
+//   sums      the pass leaves per-sample sums: slab B is reduced and vec[P..P+4) all-reduced
+//   fused     the single-launch form to try first (feed-forward modules, kernel variant 0); its range guard's chain
+enum FusedLauncher { FUSED_NONE, FUSED_POLICY /* launch_policy_v2, RL_GUARD_POLICY */,
+                     FUSED_CRITIC /* launch_critic_step_v2, RL_GUARD_CRITIC */ };
+struct PassRow {
+  bool backward, sums;
+  FusedLauncher fused;
+};
+static const PassRow PASS_TABLE[RUN_KINDS] = {
+    /* RUN_INIT   */ {true, true, FUSED_POLICY},
+    /* RUN_EVAL   */ {false, true, FUSED_POLICY},
+    /* RUN_JVP    */ {true, false, FUSED_POLICY},
+    /* RUN_DQN    */ {true, true, FUSED_NONE},  // (abi_dqn.hip has tried the DQN step kernels before it asks)
+    /* RUN_PPO    */ {true, true, FUSED_POLICY},
+    /* RUN_CRITIC */ {true, true, FUSED_CRITIC},
+};
+// (the rows are positional: the kinds alias PolicyPassMode, kernels.hpp)
+static_assert(RUN_INIT == 0 && RUN_EVAL == 1 && RUN_JVP == 2 && RUN_DQN == 3 && RUN_PPO == 4 && RUN_CRITIC == 5 &&
+                  RUN_KINDS == 6,
+              "PASS_TABLE rows are in the order of PassKind");
 
-// ---------------------------------------------------------------- recurrent gradient passes
-// policy: teacher-forced forward (activation record) -> d loss / d logits -> [backward through time -> weight
-// gradients -> reduce] -> traj->vec[0..P) and the per-sample sums in vec[P..P+4)
-// (widths other than the kernels' run on the module's zero-padded twin: SeqScope; the gradient comes back in the twin's
-// layout and is gathered into the module's flat order before anything else touches the vector)
+// a recurrent gradient comes back in the layout of the module the kernels ran (its zero-padded twin, SeqScope) and is
+// gathered into the module's flat order before anything else touches the vector
 static void seq_gradient_to_flat_order(const rl_mlp *mod, rl_traj *traj) {
   if (mod->exec == nullptr) return;
   launch_seq_unpad(mod, traj->vec, mod->x_tmp);
@@ -19,59 +39,66 @@ static float *seq_record(rl_traj *traj, const rl_mlp *mod) {
   return mod->lane_kernels() ? traj->seq.stack.rec : traj->seq.act;
 }
 
-static void seq_policy_pass(rl_mlp *policy, rl_traj *traj, int mode, bool backward, float lo, float hi) {
-  SeqScope sc(traj, policy);
-  seq_ensure(traj, sc.x, true);
-  uint32_t P = (uint32_t)policy->P;
-  launch_gru_seq_forward(traj, sc.x, traj->seq.out, nullptr, backward ? seq_record(traj, sc.x) : nullptr);
-  launch_seq_policy_dlogits(traj, mode, b_total(traj), lo, hi);
-  if (backward) {
-    launch_gru_backward(traj, sc.x);
-    seq_gradient_to_flat_order(policy, traj);
+SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
+  const PassRow &row = PASS_TABLE[req.kind];
+  const bool critic = req.kind == RUN_CRITIC;
+  const uint32_t P = (uint32_t)mod->P;
+  const uint64_t Bt = req.B_total ? req.B_total : b_total(traj);
+  bool grad = row.backward;
+  auto allreduce = [&] {
+    rl_allreduce_sum_f32(traj->eng, traj->vec + (grad ? 0 : P), (grad ? P : 0) + (row.sums ? 4 : 0));
+  };
+  if (rl_module_is_recurrent(mod->kind)) {
+    // teacher-forced forward (activation record) -> d loss / d outputs -> [backward through time -> weight gradients]
+    // -> vec[0..P), and the per-sample sums through slab B.  A Fisher-vector product starts from the record of the last
+    // pass with a backward instead: vec[0..P) <- J^T (diag(p) - p p^T) J v / B
+    RL_REQUIRE(req.reduce, "a recurrent pass reduces its own sums");  // (its gradient never goes through the slabs)
+    grad = row.backward && !req.forward_only;
+    SeqScope sc(traj, mod);
+    seq_ensure(traj, sc.x, true);
+    if (req.kind == RUN_JVP) {
+      const float *tangent = req.tangent;
+      if (mod->exec != nullptr) {  // the tangent in the twin's layout (its padding entries stay zero)
+        launch_seq_pad(mod, mod->x_tan, req.tangent);
+        tangent = mod->x_tan;
+      }
+      launch_gru_tangent(traj, sc.x, tangent, Bt, req.skip);
+    } else {
+      launch_gru_seq_forward(traj, sc.x, traj->seq.out, nullptr, grad ? seq_record(traj, sc.x) : nullptr, req.skip);
+      if (critic) launch_seq_critic_dvalues(traj, Bt);
+      else launch_seq_policy_dlogits(traj, req.kind, Bt, req.clip_lo, req.clip_hi, req.skip);
+    }
+    if (grad) {
+      launch_gru_backward(traj, sc.x, req.skip);
+      seq_gradient_to_flat_order(mod, traj);
+    }
+    if (row.sums) launch_reduce(traj, P, false, true, 0, traj->nbB);
+    allreduce();
+    return SlabRows{0, traj->nbB};
   }
-  launch_reduce(traj, P, false, true, 0, traj->nbB);
-  if (backward) rl_allreduce_sum_f32(traj->eng, traj->vec, P + 4);
-  else rl_allreduce_sum_f32(traj->eng, traj->vec + P, 4);
-}
-
-// (loss, KL) of the current parameters against log pi_0: forward without a record -> sums in vec[P..P+4)
-static void seq_policy_eval(rl_mlp *policy, rl_traj *traj, const int32_t *d_skip) {
-  SeqScope sc(traj, policy);
-  seq_ensure(traj, sc.x, true);
-  uint32_t P = (uint32_t)policy->P;
-  launch_gru_seq_forward(traj, sc.x, traj->seq.out, nullptr, nullptr, d_skip);
-  launch_seq_policy_dlogits(traj, PASS_EVAL, b_total(traj), 0.0f, 0.0f, d_skip);
-  launch_reduce(traj, P, false, true, 0, traj->nbB);
-  rl_allreduce_sum_f32(traj->eng, traj->vec + P, 4);
-}
-
-// Fisher-vector product with the tangent d_v at the parameters whose activation record is in place (the last
-// seq_policy_pass with backward = true): vec[0..P) <- J^T (diag(p) - p p^T) J v / B
-static void seq_policy_fvp(rl_mlp *policy, rl_traj *traj, const float *d_v, const int32_t *d_skip) {
-  SeqScope sc(traj, policy);
-  seq_ensure(traj, sc.x, true);
-  const float *tangent = d_v;
-  if (policy->exec != nullptr) {  // the tangent in the twin's layout (its padding entries stay zero)
-    launch_seq_pad(policy, policy->x_tan, d_v);
-    tangent = policy->x_tan;
+  // feed-forward: the fused single launch where a kernel is built for the shape (the launcher says), else forward,
+  // backward, and the slab rows of those two
+  bool fused = false;
+  if (traj->eng->kernel_variant == 0) {  // (1: the v1 reference kernels only)
+    if (row.fused == FUSED_POLICY)
+      fused = launch_policy_v2(traj, mod, req.kind, req.tangent, Bt, req.skip, req.clip_lo, req.clip_hi);
+    else if (row.fused == FUSED_CRITIC)
+      fused = launch_critic_step_v2(traj, mod, Bt);
   }
-  launch_gru_tangent(traj, sc.x, tangent, b_total(traj), d_skip);
-  launch_gru_backward(traj, sc.x, d_skip);
-  seq_gradient_to_flat_order(policy, traj);
-  rl_allreduce_sum_f32(traj->eng, traj->vec, (uint32_t)policy->P);
+  if (!fused) {
+    if (critic) launch_critic_fwd(traj, mod, Bt);
+    else launch_policy_pass(traj, mod, req.kind, req.tangent, Bt, req.skip, req.clip_lo, req.clip_hi);
+    if (row.backward) launch_mlp_backward(traj, mod, req.skip);
+  }
+  const SlabRows rows = fused ? SlabRows{traj->last_rows, traj->last_rows} : SlabRows{traj->nbA, traj->nbB};
+  if (req.reduce) {
+    launch_reduce(traj, P, row.backward, row.sums, rows.A, rows.B);
+    allreduce();
+  }
+  return rows;
 }
 
-static void seq_critic_pass(rl_mlp *critic, rl_traj *traj) {
-  SeqScope sc(traj, critic);
-  seq_ensure(traj, sc.x, true);
-  uint32_t P = (uint32_t)critic->P;
-  launch_gru_seq_forward(traj, sc.x, traj->seq.out, nullptr, seq_record(traj, sc.x));
-  launch_seq_critic_dvalues(traj, b_total(traj));
-  launch_gru_backward(traj, sc.x);
-  seq_gradient_to_flat_order(critic, traj);
-  launch_reduce(traj, P, false, true, 0, traj->nbB);
-  rl_allreduce_sum_f32(traj->eng, traj->vec, P + 4);
-}
+extern "C" {
 
 // ---------------------------------------------------------------- TRPO
 int32_t rl_trpo_config_default(rl_trpo_config *c) {
@@ -100,54 +127,15 @@ static void check_policy(const rl_mlp *policy, const rl_traj *traj) {
     throw RlError(RL_ERR_UNSUPPORTED, "recurrent chains are built for two actions");
 }
 
-// gradient pass: PASS_INIT -> backward -> reduce(A+B) -> allreduce
-static void run_policy_gradient(rl_mlp *policy, rl_traj *traj) {
-  if (rl_module_is_recurrent(policy->kind)) return seq_policy_pass(policy, traj, PASS_INIT, true, 0.0f, 0.0f);
-  uint32_t P = (uint32_t)policy->P;
-  if (traj->eng->kernel_variant != 1 && launch_policy_v2(traj, policy, PASS_INIT, nullptr, b_total(traj), nullptr)) {
-    launch_reduce(traj, P, true, true, traj->last_rows, traj->last_rows);
-  } else {
-    launch_policy_pass(traj, policy, PASS_INIT, nullptr, b_total(traj), nullptr);
-    launch_mlp_backward(traj, policy, nullptr);
-    launch_reduce(traj, P, true, true, traj->nbA, traj->nbB);
-  }
-  rl_allreduce_sum_f32(traj->eng, traj->vec, P + 4);
-}
-
-// (loss, KL) of the current parameters against lp0: PASS_EVAL -> reduce(B) -> allreduce
-static void run_policy_eval(rl_mlp *policy, rl_traj *traj, const int32_t *d_skip) {
-  if (rl_module_is_recurrent(policy->kind)) return seq_policy_eval(policy, traj, d_skip);
-  uint32_t P = (uint32_t)policy->P;
-  if (traj->eng->kernel_variant != 1 && launch_policy_v2(traj, policy, PASS_EVAL, nullptr, b_total(traj), d_skip)) {
-    launch_reduce(traj, P, false, true, traj->last_rows, traj->last_rows);
-  } else {
-    launch_policy_pass(traj, policy, PASS_EVAL, nullptr, b_total(traj), d_skip);
-    launch_reduce(traj, P, false, true, traj->nbA, traj->nbB);
-  }
-  rl_allreduce_sum_f32(traj->eng, traj->vec + P, 4);
-}
-
-// Fisher/Hessian-vector product pass with tangent d_v: PASS_JVP -> backward -> reduce(A) -> allreduce
-static void run_policy_fvp(rl_mlp *policy, rl_traj *traj, const float *d_v, const int32_t *d_skip) {
-  if (rl_module_is_recurrent(policy->kind)) return seq_policy_fvp(policy, traj, d_v, d_skip);
-  uint32_t P = (uint32_t)policy->P;
-  if (traj->eng->kernel_variant != 1 && launch_policy_v2(traj, policy, PASS_JVP, d_v, b_total(traj), d_skip)) {
-    launch_reduce(traj, P, true, false, traj->last_rows, traj->last_rows);
-  } else {
-    launch_policy_pass(traj, policy, PASS_JVP, d_v, b_total(traj), d_skip);
-    launch_mlp_backward(traj, policy, d_skip);
-    launch_reduce(traj, P, true, false, traj->nbA, traj->nbB);
-  }
-  rl_allreduce_sum_f32(traj->eng, traj->vec, P);
-}
-
 // Trpo::update (trpo.rs:97-164) on the engine's current stream, in two halves.  The head enqueues everything up to and
 // including the first two line-search candidates — about fifty launches without a host round trip; the tail reads the
 // acceptance flag back every second candidate and collects the statistics.  (rl_actor_critic_update enqueues the other
 // chain's launches between the two: the host is then never the reason one chain's kernels start late.)
 static inline void trpo_candidate(rl_mlp *policy, rl_traj *traj, const rl_trpo_config *cfg, uint64_t i, double ratio) {
   launch_ls_set_params(traj, policy, ratio);
-  run_policy_eval(policy, traj, &traj->trpo->ls_accepted);
+  PassRequest eval(RUN_EVAL);
+  eval.skip = &traj->trpo->ls_accepted;
+  run_pass(policy, traj, eval);
   launch_ls_check(traj, (uint32_t)policy->P, b_total(traj), (int)i, ratio, cfg->max_policy_step_kl);
 }
 
@@ -161,16 +149,21 @@ static TrpoProgress trpo_update_head(rl_mlp *policy, rl_traj *traj, const rl_trp
   uint64_t Bt = b_total(traj);
   float reg = (float)cfg->hpv_reg_coeff;
   // loss gradient at theta0 and CG prologue
-  run_policy_gradient(policy, traj);
+  run_pass(policy, traj, RUN_INIT);
   launch_trpo_begin(traj, policy, Bt);
   // x = A^-1 g by `iterations` CG steps (early exit handled on the device)
+  PassRequest fvp(RUN_JVP);
+  fvp.tangent = traj->cg_p;
+  fvp.skip = &traj->trpo->cg_done;
   for (uint64_t it = 0; it < cfg->iterations; ++it) {
-    run_policy_fvp(policy, traj, traj->cg_p, &traj->trpo->cg_done);
+    run_pass(policy, traj, fvp);
     launch_cg_step(traj, P, reg, 1e-10f);
   }
   launch_cg_finish(traj, P);
   // step size from x^T A x
-  run_policy_fvp(policy, traj, traj->cg_x, nullptr);
+  fvp.tangent = traj->cg_x;
+  fvp.skip = nullptr;
+  run_pass(policy, traj, fvp);
   launch_step_size(traj, policy, reg, cfg->max_policy_step_kl);
   // backtracking line search: the first two candidates
   TrpoProgress pr;
@@ -237,7 +230,7 @@ int32_t rl_policy_gradient(rl_mlp *policy, rl_traj *traj, float *grad_out, float
     check_policy(policy, traj);
     RL_REQUIRE(grad_out, "grad_out is NULL");
     uint32_t P = (uint32_t)policy->P;
-    run_policy_gradient(policy, traj);
+    run_pass(policy, traj, RUN_INIT);
     std::vector<float> h(P + 4);
     d2h(traj->eng, h.data(), traj->vec, (P + 4) * sizeof(float));
     range_check(traj, 1u << RL_GUARD_POLICY);
@@ -253,9 +246,11 @@ int32_t rl_policy_fvp(rl_mlp *policy, rl_traj *traj, const float *v, float reg, 
     check_policy(policy, traj);
     RL_REQUIRE(v && out, "NULL argument");
     uint32_t P = (uint32_t)policy->P;
-    run_policy_gradient(policy, traj);  // the product is taken at the current parameters: refresh log pi_0
+    run_pass(policy, traj, RUN_INIT);  // the product is taken at the current parameters: refresh log pi_0
     h2d(traj->eng, traj->cg_x, v, P * sizeof(float));  // (the recurrent pass above has grown the workspace)
-    run_policy_fvp(policy, traj, traj->cg_x, nullptr);
+    PassRequest fvp(RUN_JVP);
+    fvp.tangent = traj->cg_x;
+    run_pass(policy, traj, fvp);
     std::vector<float> h(P);
     d2h(traj->eng, h.data(), traj->vec, P * sizeof(float));
     range_check(traj, 1u << RL_GUARD_POLICY);
@@ -275,10 +270,10 @@ int32_t rl_policy_loss_kl(rl_mlp *policy, rl_traj *traj, const float *params0, f
     d2h(e, cur.data(), policy->d_params, P * sizeof(float));
     h2d(e, policy->d_params, params0, P * sizeof(float));
     wimg_invalidate(policy);  // (the parameters changed under the module's weight image, bf16_tile.hpp)
-    run_policy_gradient(policy, traj);  // fills lp0 under params0
+    run_pass(policy, traj, RUN_INIT);  // fills lp0 under params0
     h2d(e, policy->d_params, cur.data(), P * sizeof(float));
     wimg_invalidate(policy);  // (the parameters changed under the module's weight image, bf16_tile.hpp)
-    run_policy_eval(policy, traj, nullptr);
+    run_pass(policy, traj, RUN_EVAL);
     float h[4];
     d2h(e, h, traj->vec + P, sizeof(h));
     range_check(traj, 1u << RL_GUARD_POLICY);
@@ -443,26 +438,6 @@ static void check_critic(const rl_mlp *critic, const rl_traj *traj) {
   RL_REQUIRE(critic->in_dim == traj->d.D && critic->out_dim == 1, "critic shape does not match the trajectory");
 }
 
-// per-workgroup partial sums of the critic's MSE gradient and loss -> slabA / slabB (feed-forward modules)
-static void critic_slabs(rl_mlp *critic, rl_traj *traj, uint32_t *rowsA, uint32_t *rowsB) {
-  if (traj->eng->kernel_variant != 1 && launch_critic_step_v2(traj, critic, b_total(traj))) {
-    *rowsA = *rowsB = traj->last_rows;
-  } else {
-    launch_critic_fwd(traj, critic, b_total(traj));
-    launch_mlp_backward(traj, critic, nullptr);
-    *rowsA = traj->nbA;
-    *rowsB = traj->nbB;
-  }
-}
-
-static void run_critic_gradient(rl_mlp *critic, rl_traj *traj) {
-  if (rl_module_is_recurrent(critic->kind)) return seq_critic_pass(critic, traj);
-  uint32_t P = (uint32_t)critic->P, rowsA, rowsB;
-  critic_slabs(critic, traj, &rowsA, &rowsB);
-  launch_reduce(traj, P, true, true, rowsA, rowsB);
-  rl_allreduce_sum_f32(traj->eng, traj->vec, P + 4);
-}
-
 // n_backward_steps (src/torch/agents/mod.rs:35-72) of full-batch MSE against traj->d.tgt with Adam: the launches, on the
 // engine's current stream, without any host synchronisation (feed-forward modules on a device-side collective)
 static void critic_enqueue_steps(rl_mlp *critic, rl_adam *opt, rl_traj *traj, uint64_t opt_steps, uint64_t first = 0) {
@@ -475,13 +450,14 @@ static void critic_enqueue_steps(rl_mlp *critic, rl_adam *opt, rl_traj *traj, ui
   const bool mailbox = eng->ipc_active && !eng->comm && !eng->loopback && !eng->host_allreduce &&
                        ipc_allreduce_fits(eng, critic->P + 4) && opt->cfg.kind == RL_OPTIMIZER_ADAM;
   const bool fused = critic->kind == RL_MODULE_MLP && (!eng->has_collective() || mailbox);
+  PassRequest slabs_only(RUN_CRITIC);
+  slabs_only.reduce = false;
   for (uint64_t k = first; k < opt_steps; ++k) {
     if (fused) {  // no all-reduce between the reduction and the (elementwise) optimiser step: one launch
-      uint32_t rowsA, rowsB;
-      critic_slabs(critic, traj, &rowsA, &rowsB);
-      launch_reduce_adam(traj, opt, rowsA, rowsB, (int)k, Bt);
+      const SlabRows rows = run_pass(critic, traj, slabs_only);
+      launch_reduce_adam(traj, opt, rows.A, rows.B, (int)k, Bt);
     } else {
-      run_critic_gradient(critic, traj);
+      run_pass(critic, traj, RUN_CRITIC);
       launch_adam_step(traj, opt, (int)k, Bt);
     }
   }
@@ -548,6 +524,37 @@ static void check_values_opt(const rl_mlp *critic, const rl_adam *opt, const rl_
   RL_REQUIRE(cfg->discount_factor >= 0.0f && cfg->discount_factor <= 1.0f, "discount factor must be in [0, 1]");
 }
 
+// ---------------------------------------------------------------- the value forward
+// V(s_t) and the values at the successor observations of cut episodes, from `critic` as it stands, left where the scans
+// read them — the helper says which of the two places, and with it which scan goes with them:
+//   VALUES_IN_PLANE   traj->d.values [T+1][n] (the fused 5-H-1 forward): launch_gae / launch_value_targets
+//   VALUES_IN_ARRAYS  traj->seq.out / seq.succ (the general and the recurrent forwards): launch_seq_gae /
+//                     launch_seq_value_targets, which read no observation and so need no SeqScope of their own
+enum ValueLayout { VALUES_IN_PLANE, VALUES_IN_ARRAYS };
+static ValueLayout value_forward(rl_traj *traj, const rl_mlp *critic) {
+  if (rl_module_is_recurrent(critic->kind)) {
+    SeqScope sc(traj, critic);
+    seq_ensure(traj, sc.x, false);
+    launch_gru_seq_forward(traj, sc.x, traj->seq.out, traj->seq.succ, nullptr);
+    return VALUES_IN_ARRAYS;
+  }
+  if (critic->general) {
+    launch_gen_values(traj, critic);
+    return VALUES_IN_ARRAYS;
+  }
+  launch_values(traj, critic);
+  return VALUES_IN_PLANE;
+}
+
+int32_t rl_gae(rl_traj *traj, const rl_mlp *critic, float gamma, float lambda) {
+  return guarded(traj ? traj->eng : nullptr, [&] {
+    RL_REQUIRE(traj && critic, "NULL argument");
+    RL_REQUIRE(critic->in_dim == traj->d.D && critic->out_dim == 1, "critic shape does not match the trajectory");
+    if (value_forward(traj, critic) == VALUES_IN_ARRAYS) launch_seq_gae(traj, gamma, lambda);
+    else launch_gae(traj, critic, gamma, lambda);
+  });
+}
+
 // targets: once, from the critic as it stands now (tch::no_grad, opt.rs:101-104) -> traj->td, selected as traj->d.tgt
 static void values_opt_targets(rl_mlp *critic, rl_traj *traj, const rl_values_opt_config *cfg) {
   if (traj->td == nullptr) {
@@ -561,16 +568,9 @@ static void values_opt_targets(rl_mlp *critic, rl_traj *traj, const rl_values_op
     traj->d.tgt = traj->d.rtg;
   } else if (cfg->target == RL_VALUE_TARGET_REWARD_TO_GO) {
     launch_value_targets(traj, nullptr, cfg->discount_factor);
-  } else if (rl_module_is_recurrent(critic->kind)) {
-    SeqScope sc(traj, critic);
-    seq_ensure(traj, sc.x, false);
-    launch_gru_seq_forward(traj, sc.x, traj->seq.out, traj->seq.succ, nullptr);
-    launch_seq_value_targets(traj, cfg->discount_factor);
-  } else if (critic->general) {
-    launch_gen_values(traj, critic);
+  } else if (value_forward(traj, critic) == VALUES_IN_ARRAYS) {
     launch_seq_value_targets(traj, cfg->discount_factor);
   } else {
-    launch_values(traj, critic);
     launch_value_targets(traj, critic, cfg->discount_factor);
   }
   traj->last_targets = traj->d.tgt;  // (what RL_TRAJ_TARGETS reads)
@@ -621,20 +621,15 @@ struct AuxChain {
 // reduced vector out of the trajectory's shared workspace (the fused single-launch passes), and a multi-rank job needs
 // a collective that can serve two streams at once: the mailbox channels, the second RCCL communicator, or one of the
 // host-blocking test transports (which serialise the chains on the host, correctly).
-static bool chains_can_overlap(const rl_mlp *policy, const rl_mlp *critic, const rl_traj *traj,
-                               const rl_values_opt_config *ccfg) {
+static bool chains_can_overlap(const rl_mlp *policy, const rl_mlp *critic, const rl_traj *traj) {
   const rl_engine *e = traj->eng;
   // (with several ranks the environment switch is the one the ranks agreed on when the collective was installed)
   if (e->n_ranks > 1 ? e->agreed_serial_env : std::getenv("RELEARN_SERIAL_UPDATE") != nullptr) return false;
   if (e->serial_update || e->kernel_variant == 1) return false;
-  (void)ccfg;
-  // (general hidden_sizes keep P-sized vectors and activation planes in workspaces both chains would share)
-  auto fused_passes = [&](const rl_mlp *m) {
-    return m->kind == RL_MODULE_MLP && !m->general && traj->d.D == 5 && m->hidden == 128;
-  };
-  if (!fused_passes(policy) || !fused_passes(critic)) return false;
+  // (general hidden_sizes keep P-sized vectors and activation planes in workspaces both chains would share; the output
+  // counts are no further condition here: check_policy leaves a module that is not `general` two, check_critic one)
+  if (!fused_5_128_fits(traj, policy, 2) || !fused_5_128_fits(traj, critic, 1)) return false;
   if (policy->P > traj->Pmax || critic->P > traj->Pmax) return false;  // (the auxiliary vector is sized Pmax + 4)
-  if ((uint64_t)(traj->d.T + 1) * traj->d.n * 5 >= (1ull << 30)) return false;  // (the fused kernels' own limit)
   if (e->comm != nullptr && e->comm_aux == nullptr) return false;
   return true;
 }
@@ -657,7 +652,7 @@ static void actor_critic_begin(rl_mlp *policy, rl_mlp *critic, rl_adam *critic_o
   pu.steps = K;
   pu.stats = rl_critic_stats{};
   pu.losses.assign(K ? K : 1, 0.0f);
-  if (!chains_can_overlap(policy, critic, traj, ccfg)) {
+  if (!chains_can_overlap(policy, critic, traj)) {
     // policy.update, then critic.update (actor_critic.rs:196-208).  A NaN policy step is fatal BEFORE the critic moves,
     // as in the reference (Trpo::update panics inside policy.update)
     trpo_update_impl(policy, traj, pcfg, pstats);
@@ -758,7 +753,7 @@ int32_t rl_critic_gradient(rl_mlp *critic, rl_traj *traj, float *grad_out, float
     RL_REQUIRE(grad_out, "grad_out is NULL");
     uint32_t P = (uint32_t)critic->P;
     traj->d.tgt = traj->d.rtg;  // the documented loss: MSE against RL_TRAJ_RETURNS, whatever targets an update left behind
-    run_critic_gradient(critic, traj);
+    run_pass(critic, traj, RUN_CRITIC);
     std::vector<float> h(P + 4);
     d2h(traj->eng, h.data(), traj->vec, (P + 4) * sizeof(float));
     range_check(traj, 1u << RL_GUARD_CRITIC);
@@ -776,21 +771,6 @@ int32_t rl_ppo_config_default(rl_ppo_config *c) {
   });
 }
 
-// PASS_PPO gradient of the clipped surrogate against lp0 -> vec[0..P), sum of min(...) -> vec[P]
-static void run_policy_ppo(rl_mlp *policy, rl_traj *traj, float lo, float hi) {
-  if (rl_module_is_recurrent(policy->kind)) return seq_policy_pass(policy, traj, PASS_PPO, true, lo, hi);
-  uint32_t P = (uint32_t)policy->P;
-  if (traj->eng->kernel_variant != 1 &&
-      launch_policy_v2(traj, policy, PASS_PPO, nullptr, b_total(traj), nullptr, lo, hi)) {
-    launch_reduce(traj, P, true, true, traj->last_rows, traj->last_rows);
-  } else {
-    launch_policy_pass(traj, policy, PASS_PPO, nullptr, b_total(traj), nullptr, lo, hi);
-    launch_mlp_backward(traj, policy, nullptr);
-    launch_reduce(traj, P, true, true, traj->nbA, traj->nbB);
-  }
-  rl_allreduce_sum_f32(traj->eng, traj->vec, P + 4);
-}
-
 int32_t rl_ppo_update(rl_mlp *policy, rl_adam *opt, rl_traj *traj, const rl_ppo_config *cfg,
                       rl_policy_opt_stats *stats, float *losses_out) {
   return guarded(traj ? traj->eng : nullptr, [&] {
@@ -802,14 +782,20 @@ int32_t rl_ppo_update(rl_mlp *policy, rl_adam *opt, rl_traj *traj, const rl_ppo_
     uint32_t P = (uint32_t)policy->P;
     uint64_t Bt = b_total(traj), K = cfg->opt_steps_per_update;
     // initial_log_probs and the logged entropy (ppo.rs:107-118): the PASS_INIT pass stores log pi_0
-    if (rl_module_is_recurrent(policy->kind)) seq_policy_pass(policy, traj, PASS_INIT, false, 0.0f, 0.0f);
-    else run_policy_gradient(policy, traj);
+    // (only the sums are read: a recurrent module skips the backward through time)
+    PassRequest init(RUN_INIT);
+    init.forward_only = true;
+    run_pass(policy, traj, init);
     float h0[4];
     d2h(e, h0, traj->vec + P, sizeof(h0));
     // clip(1 - d, 1 + d): f64 scalars applied to a Float tensor
     float lo = (float)(1.0 - cfg->clip_distance), hi = (float)(1.0 + cfg->clip_distance);
+    PassRequest ppo(RUN_PPO);
+    ppo.clip_lo = lo;
+    ppo.clip_hi = hi;
     for (uint64_t k = 0; k < K; ++k) {
-      run_policy_ppo(policy, traj, lo, hi);
+      // gradient of the clipped surrogate against lp0 -> vec[0..P), sum of min(...) -> vec[P]
+      run_pass(policy, traj, ppo);
       launch_adam_step(traj, opt, (int)k, Bt);
     }
     std::vector<float> h(K ? K : 1, 0.0f);
@@ -834,7 +820,7 @@ int32_t rl_reinforce_update(rl_mlp *policy, rl_adam *opt, rl_traj *traj, rl_poli
     uint32_t P = (uint32_t)policy->P;
     uint64_t Bt = b_total(traj);
     // d(-mean(log pi(a) A))/d theta equals the surrogate gradient at ratio = 1 that PASS_INIT computes
-    run_policy_gradient(policy, traj);
+    run_pass(policy, traj, RUN_INIT);
     float h0[4];
     d2h(e, h0, traj->vec + P, sizeof(h0));
     launch_adam_step(traj, opt, -1, Bt);

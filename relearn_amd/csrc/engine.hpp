@@ -258,7 +258,7 @@ struct rl_mlp {
   // start from 4 x 256 zeros kept behind the P parameters, like the bias-less MLP layers; the chain's MLP keeps its own)
   bool lane_kernels() const { return rnn_layers > 1 || in_dim > 5 || gru_hidden > 128 || hidden > 128 || !has_bias; }
   uint64_t rnn_layer_offset(uint32_t l) const {  // W_ih of layer l; l == rnn_layers: the head's W1
-    const uint64_t GH = (kind == RL_MODULE_LSTM_MLP ? 4 : 3) * (uint64_t)gru_hidden, nb = has_bias ? 2 * GH : 0;
+    const uint64_t GH = rl_module_gates(kind) * (uint64_t)gru_hidden, nb = has_bias ? 2 * GH : 0;
     if (l == 0) return 0;
     return GH * (in_dim + gru_hidden) + nb + (uint64_t)(l - 1) * (GH * 2 * gru_hidden + nb);
   }

@@ -25,6 +25,17 @@ inline void traj_ensure_range(rl_traj *traj) {
   launch_obs_range(traj);
   traj->range_valid = true;
 }
+// Do the fused 5-128 kernels (kernels_mfma.hip, kernels_critic.hip, kernels_dqn.hip) take module `m` on the planes of
+// `t`?  A feed-forward module with one hidden layer of 128 units and `out_dim` outputs over five observation features,
+// and planes the kernels' 32-bit element offsets reach.  The one statement of it: the launchers decline by it, and the
+// host decisions that have to agree with them (may two chains overlap, is a DQN update snapshotted, are TD targets
+// formed in the kernel) are taken by it.  `offsets` false leaves the last term out, for a decision taken before the
+// sample count is known.  (rl_engine::kernel_variant is not part of it: that is the caller's question, asked where
+// a fused launcher of either family — these kernels or gen_mfma_fits' — is about to be tried.)
+inline bool fused_5_128_fits(const rl_traj *t, const rl_mlp *m, uint32_t out_dim, bool offsets = true) {
+  return m->kind == RL_MODULE_MLP && !m->general && t->d.D == 5 && m->hidden == 128 && m->out_dim == out_dim &&
+         (!offsets || (uint64_t)(t->d.T + 1) * t->d.n * 5 < (1ull << 30));
+}
 
 // The weight image of a 5 -> 128 -> A module (bf16_tile.hpp): valid for one C-ABI call at a time.
 //   wimg_ensure       a fused launcher about to read it: builds it (one small launch on the engine's current stream)
@@ -158,7 +169,7 @@ void launch_gru_train_recur_backward(rl_traj *traj, const rl_mlp *mod, const int
 void launch_gru_train_wgrad(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip);
 constexpr uint32_t RL_SEQ_HEAD_ROWS = 512;  // rows of head-gradient partials behind the weight-gradient kernel's chunks
 void launch_seq_gae(rl_traj *traj, float gamma, float lambda);
-void launch_seq_value_targets(rl_traj *traj, float gamma);  // one-step TD targets from traj->seq.out / succ -> d.tgt  // reads traj->seq.out / succ (plane 0)
+void launch_seq_value_targets(rl_traj *traj, float gamma);  // one-step TD targets from traj->seq.out / succ (plane 0) -> d.tgt
 void launch_seq_policy_dlogits(rl_traj *traj, int mode, uint64_t B_total, float clip_lo, float clip_hi,
                                const int32_t *d_skip = nullptr);
 void launch_seq_critic_dvalues(rl_traj *traj, uint64_t B_total);

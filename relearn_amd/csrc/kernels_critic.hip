@@ -315,8 +315,7 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
 // ---------------------------------------------------------------- launcher
 bool launch_critic_step_v2(rl_traj *traj, const rl_mlp *critic, uint64_t B_total) {
   if (critic->general) return launch_gen_mfma(traj, critic, RL_GEN_CRITIC, nullptr, B_total, nullptr, 0.0f, 0.0f);
-  if (traj->d.D != 5 || critic->hidden != 128 || critic->out_dim != 1) return false;
-  if ((uint64_t)(traj->d.T + 1) * traj->d.n * 5 >= (1ull << 30)) return false;  // 32-bit element offsets in the kernel
+  if (!fused_5_128_fits(traj, critic, 1)) return false;  // (only feed-forward modules are passed here)
   traj_ensure_range(traj);
   const uint32_t *wimg = wimg_ensure(critic);
   ProfScope ps(traj->eng, RL_K_CRITIC_FUSED);
@@ -340,8 +339,7 @@ bool launch_critic_step_v2(rl_traj *traj, const rl_mlp *critic, uint64_t B_total
 // The DQN gradient of a 5-128-2 action-value network over the minibatch workspace `mb` (targets in `adv`, actions in
 // `action`): k_critic_step_mfma<2>.  False: shape not built (the caller has other kernels).
 bool launch_dqn_step_pair(rl_traj *mb, const rl_mlp *qnet, uint64_t B_total) {
-  if (mb->d.D != 5 || qnet->hidden != 128 || qnet->out_dim != 2 || qnet->general) return false;
-  if ((uint64_t)(mb->d.T + 1) * mb->d.n * 5 >= (1ull << 30)) return false;  // 32-bit element offsets in the kernel
+  if (!fused_5_128_fits(mb, qnet, 2)) return false;  // (rl_dqn_create takes feed-forward modules only)
   const uint32_t *wimg = wimg_ensure(qnet);
   ProfScope ps(mb->eng, RL_K_POLICY_FUSED);
   const uint64_t n_tiles = (mb->B + 31) / 32, cus = (uint64_t)mb->eng->prop.multiProcessorCount;

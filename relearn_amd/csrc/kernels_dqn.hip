@@ -1009,8 +1009,7 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
 
 // returns false when the kernel is not built for this shape (the caller falls back to the f32 passes)
 bool launch_dqn_step_bf16(rl_traj *mb, const rl_mlp *qnet, uint64_t B_total, float gamma) {
-  if (mb->d.D != 5 || qnet->hidden != 128 || qnet->out_dim != 2 || qnet->general) return false;
-  if ((uint64_t)(mb->d.T + 1) * mb->d.n * 5 >= (1ull << 30)) return false;  // 32-bit element offsets in the kernel
+  if (!fused_5_128_fits(mb, qnet, 2)) return false;  // (rl_dqn_create takes feed-forward modules only)
   const uint32_t *wimg = wimg_ensure(qnet);
   ProfScope ps(mb->eng, RL_K_POLICY_FUSED);
   const uint64_t n_tiles = (mb->B + 31) / 32, cus = (uint64_t)mb->eng->prop.multiProcessorCount;
