@@ -1,5 +1,7 @@
-// bf16_tile.hpp — the tile machinery shared by the fused update kernels (kernels_critic.hip, kernels_mfma.hip):
-// layer 1 of the 5-128-A MLP and the masked-sum backward on the bf16 matrix pipe, every product exact.
+// bf16_tile.hpp — the tile machinery shared by the fused update kernels (kernels_critic.hip, kernels_mfma.hip,
+// k_dqn_step_bf16 in kernels_dqn.hip): layer 1 of the 5-128-A MLP and the masked-sum backward on the bf16 matrix pipe,
+// every product exact; and, at the end of the file, what those kernels share around their per-sample maths (weight
+// prologue, tile dealing and walk, output transpose, owner-lane reduction, epilogue).
 //
 // What the hardware dictates (measured, scripts/probe/pipe_overlap.hip): v_mfma_f32_32x32x2_f32 runs at the f32 vector
 // rate AND occupies the vector ALU — its time adds to every other wave's VALU time on the SIMD — while the bf16 matrix
@@ -34,6 +36,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
+
+#include "../../include/rl_detmath.h"
 
 namespace bt {
 
@@ -43,6 +48,10 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int NT = 4;     // 32-unit hidden tiles (H = 128)
+// the flat parameter vector of a 5 -> 128 -> A module, [W1 (H x D), b1 (H), W2 (A x H), b2 (A)]: where each part begins
+constexpr int PAR_D = 5, PAR_H = 128;
+constexpr uint32_t PAR_B1 = PAR_H * PAR_D, PAR_W2 = PAR_B1 + PAR_H;
+__host__ __device__ constexpr uint32_t par_b2(int A) { return PAR_W2 + (uint32_t)(A * PAR_H); }
 // How the fused kernels with two waves per SIMD deal their tiles (round 6).  The older wave of a SIMD (waves 0-3 of an
 // eight-wave workgroup) wins the issue arbitration: dealt evenly, it finished its tiles at 0.71 of the launch and the
 // younger wave ran the rest alone, with nothing to overlap its matrix instructions with.  An older wave now plays
@@ -50,10 +59,6 @@ constexpr int NT = 4;     // 32-unit hidden tiles (H = 128)
 // size and keeps the tile counts integral at every power-of-two lane count (9:7, 12:7, 7:4, 16:9, 9:5, 11:6, 2:1, 7:3, 3:1
 // measured: none better; profiles/r06_critic_step_timeline.txt).
 constexpr uint32_t SHARE_OLD = 5, SHARE_YOUNG = 3;
-constexpr int COLS = 19;  // piece columns of the backward: pcol(k) + p, k = input feature (5 = bias), p = piece; the three
-                          // pieces of a feature stay inside one 16-lane row (column 15 is unused), so the flush adds them
-                          // with row shifts
-constexpr int UROW = 36;  // halfwords per row of the piece image [piece column][sample] (72-byte rows: conflict-free)
 
 __device__ __forceinline__ void wave_lds_fence() {
   // LDS operations of one wavefront execute in program order; what is needed is that the compiler keeps that
@@ -146,27 +151,6 @@ union Frag {
   uint4 x;
 };
 
-// B operands of the forward for one hidden unit: its weights for inputs 2 hf, 2 hf + 1, 4 and its bias
-__device__ __forceinline__ void weight_frags(float wa, float wb, float w4, float bias, int hf, Frag (&f)[3]) {
-  uint32_t a0, a1, a2, c0, c1, c2, e0, e1, e2, g0, g1, g2;
-  split3(wa, a0, a1, a2);
-  split3(wb, c0, c1, c2);
-  split3(w4, e0, e1, e2);
-  split3(bias, g0, g1, g2);
-  f[0].u[0] = pk(a0, a1);
-  f[0].u[1] = pk(a2, a0);
-  f[0].u[2] = pk(a1, a2);
-  f[0].u[3] = pk(a0, a1);
-  f[1].u[0] = pk(a2, c0);
-  f[1].u[1] = pk(c1, c2);
-  f[1].u[2] = pk(c0, c1);
-  f[1].u[3] = pk(c2, c0);
-  f[2].u[0] = pk(c1, c2);
-  f[2].u[1] = pk(e0, e1);
-  f[2].u[2] = hf == 0 ? pk(e2, e0) : pk(e2, g0);
-  f[2].u[3] = hf == 0 ? pk(e1, e2) : pk(g1, g2);
-}
-
 constexpr float FWD_SCALE = 0x1p96f, FWD_UNSCALE = 0x1p-96f;  // ("relu' in half an instruction per value", below)
 
 // ---- the weight image (round 6).  Every fused launch used to rebuild its weight-piece fragments from the flat parameter
@@ -175,9 +159,9 @@ constexpr float FWD_SCALE = 0x1p96f, FWD_UNSCALE = 0x1p-96f;  // ("relu' in half
 // of them for a DQN minibatch (3 tiles per wave).  The kernels that WRITE the parameters (k_reduce_opt, k_opt_step,
 // k_ls_set_params: one lane owns one parameter) now also store that parameter's three 2^96-scaled pieces where the
 // consumers' lanes will load them, so a consumer's prologue is 12 x 16-byte loads per lane plus 5 raw floats per hidden
-// tile.  Same numbers as weight_frags(2^96 w ...): the consumers compute bit for bit what they computed before.
+// tile.  Same numbers as a split of 2^96 w in the consumer: the consumers compute bit for bit what they computed before.
 //   frag part   uint4 [NT * 3][64]: entry (3 t + i, lane) = fragment i of hidden tile t for that lane, i.e. the halfword
-//               sequence h = 0..23 of weight_frags — pieces of input 2 hf (h 0..8: p0 p1 p2 three times), of input 2 hf + 1
+//               sequence h = 0..23 of the half's slot list — pieces of input 2 hf (h 0..8: p0 p1 p2 three times), of input 2 hf + 1
 //               (h 9..17), then for half 0 input 4 twice (h 18..23), for half 1 input 4 once and the bias (h 18..23)
 //   raw part    float [NT][WIMG_RAW][64]: the unscaled weights of the lane's unit — inputs 2 hf, 2 hf + 1, then input 4
 //               (half 0) or the bias (half 1), then the unit's output weights W2[0][j] (and W2[1][j] for two outputs)
@@ -193,14 +177,14 @@ __device__ __forceinline__ uint32_t wimg_half_index(int t, int lane, int h) {
 __device__ __forceinline__ uint32_t wimg_raw_index(int t, int lane, int c) {
   return (uint32_t)(WIMG_FRAG_WORDS + (t * WIMG_RAW + c) * 64 + lane);
 }
-// parameter p of a flat [W1 (H x D), b1 (H), W2 (A x H), b2 (A)] vector with H = 128, D = 5 has the new value w
+// parameter p of the flat vector (PAR_*) has the new value w
 __device__ __forceinline__ void wimg_store_param(uint32_t *__restrict__ img, uint32_t p, float w, int A) {
-  constexpr int H = 128, D = 5;
+  constexpr int H = PAR_H, D = PAR_D;
   unsigned short *h16 = reinterpret_cast<unsigned short *>(img);
   float *f32 = reinterpret_cast<float *>(img);
-  if (p >= (uint32_t)(H * D + H + A * H)) return;  // the output biases are read from the vector itself
-  if (p >= (uint32_t)(H * D + H)) {                // W2[a][j]: both halves of unit j
-    const int q = (int)p - (H * D + H), a = q / H, j = q % H;
+  if (p >= par_b2(A)) return;  // the output biases are read from the vector itself
+  if (p >= PAR_W2) {           // W2[a][j]: both halves of unit j
+    const int q = (int)(p - PAR_W2), a = q / H, j = q % H;
     f32[wimg_raw_index(j >> 5, j & 31, 3 + a)] = w;
     f32[wimg_raw_index(j >> 5, 32 + (j & 31), 3 + a)] = w;
     return;
@@ -213,8 +197,8 @@ __device__ __forceinline__ void wimg_store_param(uint32_t *__restrict__ img, uin
     h16[wimg_half_index(t, lane, h + 1)] = q1;
     h16[wimg_half_index(t, lane, h + 2)] = q2;
   };
-  if (p >= (uint32_t)(H * D)) {  // b1[j]: the last three slots of half 1
-    const int j = (int)p - H * D, t = j >> 5, n = j & 31;
+  if (p >= PAR_B1) {  // b1[j]: the last three slots of half 1
+    const int j = (int)(p - PAR_B1), t = j >> 5, n = j & 31;
     put(t, 32 + n, 21);
     f32[wimg_raw_index(t, 32 + n, 2)] = w;
     return;
@@ -279,23 +263,6 @@ __device__ __forceinline__ f32x16 layer1(const Frag (&fa)[3], const Frag (&fw)[3
 #pragma unroll
   for (int i = 0; i < 3; ++i) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i].v, fw[i].v, c, 0, 0, 0);
   return c;
-}
-
-// relu'(pre) of a tile's 16 registers, packed as the two A operands (sample groups s = 0, 1) of the backward
-__device__ __forceinline__ void pack_mask(const float (&gm)[16], Frag (&ga)[2]) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ga[s].u[i] = pack_bf16(gm[8 * s + 2 * i], gm[8 * s + 2 * i + 1]);
-}
-// the same, and keep the packed form (8 registers) live instead of the tile's 16 pre-activations: for kernels whose
-// register budget is the tighter constraint
-__device__ __forceinline__ void pack_mask_now(const float (&gm)[16], Frag (&ga)[2]) {
-  pack_mask(gm, ga);
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(ga[s].u[i]));
 }
 
 // relu' in half an instruction per value (round 3).  The forward weights are scaled by 2^96 (exact: a power of two), so
@@ -486,9 +453,10 @@ __device__ __forceinline__ float l2_dot(const f32x16 &q, float xa, float xb, flo
 // the lane) WITHOUT LDS (round 3; an LDS instruction costs 14-25 cycles of the SIMD's issue port and the write -> read
 // round trip sits in every tile's dependency chain: scripts/probe/slot_cost.hip): each sample lane packs its nine pieces
 // as an A operand — slots 0..7 of k-step 0 and slot 0 of k-step 1 of its half — and a selection matrix (B operand, built
-// once per launch) routes slot (k-step, half, e) to piece column pcol(k) + p: two matrix instructions give the piece
-// image U[sample][column] as an accumulator tile (every entry one exact piece times 1), and eight conversions pack it
-// in the row order of relu' tiles (pack_mask).
+// once per launch) routes slot (k-step, half, e) to piece column 3 k + p (k = input feature; the bias, k = 5, in columns
+// 16..18, so that the three pieces of a feature stay inside one 16-lane row and the flush adds them with row shifts;
+// column 15 is unused): two matrix instructions give the piece image U[sample][column] as an accumulator tile (every
+// entry one exact piece times 1), and eight conversions pack it in the row order of relu' tiles (mask_tile).
 struct Pieces3 {
   uint32_t p[3];
 };
@@ -528,37 +496,6 @@ __device__ __forceinline__ void piece_frags_mfma(float g, float xa, float xb, fl
   for (int s = 0; s < 2; ++s)
 #pragma unroll
     for (int i = 0; i < 4; ++i) ub[s].u[i] = pack_bf16(ut[8 * s + 2 * i], ut[8 * s + 2 * i + 1]);
-}
-
-__device__ __forceinline__ constexpr int pcol(int k) { return k < 5 ? 3 * k : 16; }
-
-// publish u[sample n][k] = g * x~_k for this lane's three k (half 0: k = 0, 1, 4; half 1: k = 2, 3 and 5, where
-// x~_5 = 1) as exact bf16 pieces in the wave's piece image
-__device__ __forceinline__ void publish_pieces(unsigned short (*ubf)[UROW], float g, float xa, float xb, float xc, int n,
-                                               int hf) {
-  const float uv[3] = {g * xa, g * xb, hf == 0 ? g * xc : g};
-  const int cc[3] = {6 * hf, 6 * hf + 3, hf == 0 ? 12 : 16};  // pcol of k = 2 hf, 2 hf + 1, 4 + hf
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    uint32_t q0, q1, q2;
-    split3(uv[q], q0, q1, q2);
-    ubf[cc[q] + 0][n] = (unsigned short)q0;
-    ubf[cc[q] + 1][n] = (unsigned short)q1;
-    ubf[cc[q] + 2][n] = (unsigned short)q2;
-  }
-}
-
-// B operands of the backward: element j of lane half hf = piece[column n][sample 16 s + 8 (j >> 2) + 4 hf + (j & 3)]
-__device__ __forceinline__ void piece_frags(const unsigned short (*ubf)[UROW], int n, int hf, Frag (&ub)[2]) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    ub[s].q[0] = 0;
-    ub[s].q[1] = 0;
-    if (n < COLS && n != 15) {  // column 15 is unused (never written)
-      ub[s].q[0] = *reinterpret_cast<const uint64_t *>(&ubf[n][16 * s + 4 * hf]);
-      ub[s].q[1] = *reinterpret_cast<const uint64_t *>(&ubf[n][16 * s + 8 + 4 * hf]);
-    }
-  }
 }
 
 __device__ __forceinline__ void backward(const Frag (&ga)[NT][2], const Frag (&ub)[2], f32x16 (&dm)[NT]) {
@@ -609,6 +546,163 @@ __device__ __forceinline__ void flush(f32x16 (&dm)[NT], double *acc64, int strid
       }
     }
   }
+}
+
+// ================================================================================================
+// What the fused 5-128 kernels share around their per-sample maths.  A kernel owns its per-sample maths, its
+// accumulator set, its flush period and its LDS layout, and hands them to these as functors: everything is inlined, and
+// nothing is materialised that the kernel does not keep.
+// ================================================================================================
+
+// f64 sum of v over the wave's 32 owner lanes (hf == 0; lane n and lane n + 32 both hold sample n, and only one of them
+// may count it), in every lane; the value moves as two 32-bit halves
+__device__ __forceinline__ double owner_sum(double v, int hf) {
+  double s = hf == 0 ? v : 0.0;
+#pragma unroll
+  for (int m = 16; m > 0; m >>= 1) {
+    const uint64_t bits = rl_f64_bits(s);
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)bits, m, 64);
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(bits >> 32), m, 64);
+    s = s + rl_f64_from_bits(((uint64_t)hi << 32) | lo);
+  }
+  return s;
+}
+// f32 sum over the 32 lanes of this lane's half (the linear half of relu: a half's lanes hold the 32 units of a tile)
+__device__ __forceinline__ float half_sum(float v) {
+#pragma unroll
+  for (int m = 1; m < 32; m <<= 1) v = v + __shfl_xor(v, m, 64);
+  return v;
+}
+
+// The weight prologue: this lane's fragments of every hidden tile from the module's weight image (ready-made, written by
+// whoever wrote the parameters), and fold(t, raw) for what the kernel derives from the raw weights of its unit (the
+// linear half of relu, the output weights with the forward's 2^96 scale taken back out).  Wave 0 of workgroup 0 — one
+// wave sees all 128 units — runs the numeric range guard on chain CHAIN's words when the launch was given them.
+template <int CHAIN, typename F>
+__device__ __forceinline__ void load_weights(const uint32_t *__restrict__ wimg, int wave, int lane, int A, uint32_t *range,
+                                             uint32_t *range_err, Frag (&fw)[NT][3], F fold) {
+  const bool guard = blockIdx.x == 0 && wave == 0 && range != nullptr;
+  float xmin = 0.0f, xmax = 0.0f;
+  if (guard) range_bounds(range, lane, xmin, xmax);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    WRaw r;
+    wimg_load(wimg, t, lane, fw[t], r, A);
+    if (guard) range_guard_img(r, lane >> 5, xmin, xmax, range_err + CHAIN, range_veto(range, CHAIN));
+    fold(t, r);
+  }
+}
+
+// The dealing of tiles to waves.  A launch has gridDim.x * per-workgroup virtual waves; virtual wave v walks the full
+// tiles v, v + n_waves, ...  Of a workgroup's WAVES / CHANNELS tile-walking waves the first half are the older waves of
+// their SIMDs and play share_old virtual waves each, the others share_young (SHARE_OLD above says why); virtual wave ids
+// are workgroup-major, the older waves' first.  With CHANNELS = 2, wave w and wave w + WAVES / 2 walk the same tiles (a
+// SIMD then holds one wave of each channel: that kernel passes 1 : 1).
+struct Dealing {
+  uint32_t share, first, n_waves;  // this wave plays virtual waves first .. first + share - 1 of n_waves
+};
+template <int WAVES, int CHANNELS = 1>
+__device__ __forceinline__ Dealing deal_tiles(int wave, uint32_t share_old, uint32_t share_young) {
+  constexpr int WALKERS = WAVES / CHANNELS, HALF = WALKERS / 2;
+  const int w = CHANNELS == 1 ? wave : wave & (WALKERS - 1);
+  const uint32_t per_wg = HALF * (share_old + share_young);
+  Dealing d;
+  d.share = w < HALF ? share_old : share_young;
+  d.first = blockIdx.x * per_wg +
+            (w < HALF ? (uint32_t)w * share_old : HALF * share_old + (uint32_t)(w - HALF) * share_young);
+  d.n_waves = gridDim.x * per_wg;
+  return d;
+}
+// The tile walk of one wave: the full tiles in the loops — tile(std::false_type{}, operands, g) carries no validity
+// selects — and the ragged last tile (tail = B % 32 samples) after them on the virtual wave whose turn it is, through the
+// same code with std::true_type.  Tile indices are wave-uniform.  load_tile(g) requests a tile's operands; the loads run
+// one tile ahead (past a virtual wave's last tile: that tile again), into two named buffers that take turns — no register
+// moves — or, for a kernel without the registers for a second buffer, into one with a move per operand.
+template <bool TWO_BUFFERS, typename L, typename T>
+__device__ __forceinline__ void walk_tiles(const Dealing &deal, uint32_t n_full, uint32_t tail, L &load_tile, T &tile) {
+  const Dealing d = deal;  // (a copy: the compiler then allocates registers as for the same loops written in the kernel)
+  for (uint32_t vw = 0; vw < d.share; ++vw) {
+    const uint32_t wave_id = d.first + vw;
+    if (wave_id < n_full) {
+      auto op_a = load_tile(wave_id), op_b = op_a;
+      if (!TWO_BUFFERS) {
+        for (uint32_t g = wave_id; g < n_full; g += d.n_waves) {
+          const uint32_t g1 = g + d.n_waves;
+          op_b = load_tile(g1 < n_full ? g1 : g);
+          tile(std::false_type{}, op_a, g);
+          op_a = op_b;
+        }
+      } else {
+        for (uint32_t g = wave_id; g < n_full; g += 2 * d.n_waves) {
+          const uint32_t g1 = g + d.n_waves, g2 = g1 + d.n_waves;
+          op_b = load_tile(g1 < n_full ? g1 : g);
+          tile(std::false_type{}, op_a, g);
+          if (g1 >= n_full) break;
+          op_a = load_tile(g2 < n_full ? g2 : g1);
+          tile(std::false_type{}, op_b, g1);
+        }
+      }
+    }
+    if (tail != 0 && n_full % d.n_waves == wave_id) tile(std::true_type{}, load_tile(n_full), n_full);
+  }
+}
+
+// The output transpose: a lane holds 16 partial outputs yp[r] of the samples row(r, hf) summed over its four hidden units;
+// through LDS tile w of ysh (the wave's: row = sample, column = source lane) to the sum over the 32 source lanes of this
+// half, plus lin() — this half's part of the linear half of relu for sample n, see linear_half — and both halves added:
+// sum_j w2_j (pre_j + |pre_j|) of sample n in lanes n and n + 32.  The caller fences (wave_lds_fence) before the tile is
+// written again.
+template <int W, typename LIN>
+__device__ __forceinline__ float transpose_sum(float (&ysh)[W][32][YROW], int w, const float (&yp)[16], LIN lin, int n,
+                                               int hf) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) ysh[w][(r & 3) + 8 * (r >> 2) + 4 * hf][n] = yp[r];
+  wave_lds_fence();
+  float part = row_sum16v(&ysh[w][n][hf * 16]);
+  part = part + lin();
+  float p0, p1;
+  both_halves(part, p0, p1);
+  return p0 + p1;
+}
+// lv . (this half's inputs of its sample: 2 hf, 2 hf + 1, and 4 or the bias input)
+__device__ __forceinline__ float linear_half(const float (&lv)[3], float xa, float xb, float xc, int hf) {
+  float lin = lv[0] * xa;
+  lin = __builtin_fmaf(lv[1], xb, lin);
+  return __builtin_fmaf(lv[2], hf == 0 ? xc : 1.0f, lin);
+}
+
+// The epilogue, after the workgroup's barrier.  Slot src of the per-wave f64 images acc[0 .. NW - 1], summed in wave order
+template <int NW, int IMG>
+__device__ __forceinline__ double image_sum(const double (*acc)[IMG], int src) {
+  double s = acc[0][src];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) s = s + acc[w][src];
+  return s;
+}
+// dL/dW2[j] of one output from the masked sums m(k) of hidden unit j: b1[j] M[j][5] + sum_k W~1[j][k] M[j][k], k ascending
+template <typename M>
+__device__ __forceinline__ double dw2_sum(const float *__restrict__ W1, const float *__restrict__ b1, int j, M m) {
+  double s = m(5) * (double)b1[j];
+#pragma unroll
+  for (int k = 0; k < PAR_D; ++k) s += m(k) * (double)W1[j * PAR_D + k];
+  return s;
+}
+// Entry p < par_b2(A) of a workgroup's slab row from the summed masked sums m(c, j, k) of CH backward channels:
+//   dW1[j][k] = sum_c coef(c, j) M_c[j][k],  db1[j] the same with k = 5,  dW2[a][j] = dw2_sum of channel a (CH = 1: of
+//   the one channel)
+// (one channel under two outputs is the policy's antisymmetric pair: the caller negates row 1)
+template <int CH, typename M, typename C>
+__device__ __forceinline__ double grad_entry(uint32_t p, const float *__restrict__ params, M m, C coef) {
+  const float *__restrict__ W1 = params, *__restrict__ b1 = params + PAR_B1;
+  auto dw1 = [&](int j, int k) {
+    double s = m(0, j, k) * coef(0, j);
+    if (CH == 2) s = s + m(1, j, k) * coef(1, j);
+    return s;
+  };
+  if (p < PAR_B1) return dw1((int)(p / (uint32_t)PAR_D), (int)(p % (uint32_t)PAR_D));
+  if (p < PAR_W2) return dw1((int)(p - PAR_B1), 5);
+  const int q = (int)(p - PAR_W2), a = q / PAR_H, j = q % PAR_H, c = CH == 1 ? 0 : a;
+  return dw2_sum(W1, b1, j, [&](int k) { return m(c, j, k); });
 }
 
 }  // namespace bt

@@ -36,6 +36,23 @@ inline bool fused_5_128_fits(const rl_traj *t, const rl_mlp *m, uint32_t out_dim
   return m->kind == RL_MODULE_MLP && !m->general && t->d.D == 5 && m->hidden == 128 && m->out_dim == out_dim &&
          (!offsets || (uint64_t)(t->d.T + 1) * t->d.n * 5 < (1ull << 30));
 }
+// The persistent grid of a fused 5-128 launch over the planes of `t`: one workgroup per `walkers` 32-sample tiles (its
+// tile-walking waves), at most one per CU — fewer, fatter workgroups are fewer slab rows for the reduction that follows
+// every launch.
+inline uint32_t fused_grid(const rl_traj *t, uint32_t walkers) {
+  const uint64_t n_tiles = (t->B + 31) / 32, cus = (uint64_t)t->eng->prop.multiProcessorCount;
+  const uint64_t nb = (n_tiles + walkers - 1) / walkers;
+  return (uint32_t)(nb > cus ? cus : nb);
+}
+// The planes a fused 5-128 launch runs on.  The numeric range guard belongs to the first launch of a chain in a call
+// (engine.hpp): `guard_next` is the chain's flag (rl_traj::guard_next_policy / _critic), consumed here; every other launch
+// gets no range words.
+inline TrajDev fused_traj_dev(const rl_traj *t, bool &guard_next) {
+  TrajDev d = t->d;
+  if (!guard_next) d.range = nullptr;
+  guard_next = false;
+  return d;
+}
 
 // The weight image of a 5 -> 128 -> A module (bf16_tile.hpp): valid for one C-ABI call at a time.
 //   wimg_ensure       a fused launcher about to read it: builds it (one small launch on the engine's current stream)
@@ -84,8 +101,9 @@ void launch_adam_step_vec(rl_adam *opt, const float *d_grad);
 // reduce(A + B) and Adam in one launch (single-rank runs: no all-reduce between the two)
 void launch_reduce_adam(rl_traj *traj, rl_adam *opt, uint32_t rowsA, uint32_t rowsB, int loss_slot, uint64_t B_total);
 
-// kernels_mfma.hip ("v2": f32-MFMA layer 1, lane = hidden unit backward; H = 128, D = 5 only)
-// returns false when the shape is not supported (caller falls back to the v1 kernels)
+// kernels_critic.hip, kernels_mfma.hip ("v2"): the fused critic step and policy passes of a 5-128 module on the bf16
+// matrix pipe (bf16_tile.hpp); a module with several hidden layers goes on to launch_gen_mfma
+// return false when the shape is not built (the caller has the v1 kernels)
 bool launch_critic_step_v2(rl_traj *traj, const rl_mlp *critic, uint64_t B_total);
 bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float *d_tangent, uint64_t B_total,
                       const int32_t *d_skip_flag, float clip_lo = 0.0f, float clip_hi = 0.0f);

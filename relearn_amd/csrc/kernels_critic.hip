@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform: tile indices stay scalar
   const int n = lane & 31, hf = lane >> 5;
-  const float *__restrict__ W1 = params, *__restrict__ b1 = W1 + H * D, *__restrict__ W2 = b1 + H;
+  const float *__restrict__ W2 = params + bt::PAR_W2;
   const int chan = CH == 2 ? (wave >= CRITIC_WAVES / 2 ? 1 : 0) : 0;  // (wave-uniform) the output this wave differentiates
   const float b2 = W2[CH * H + chan];
   const size_t B = (size_t)tr.T * tr.n;
@@ -71,30 +71,19 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
   Frag fw[NT][3];
   float w2v[NT];
   float lv[3] = {0.0f, 0.0f, 0.0f};
-  const bool guard = blockIdx.x == 0 && wave == 0 && tr.range != nullptr;  // the numeric range guard (bf16_tile.hpp)
-  float gxmin = 0.0f, gxmax = 0.0f;
-  if (guard) bt::range_bounds(tr.range, lane, gxmin, gxmax);
-  // (the pieces come ready-made from the module's weight image, written by whoever wrote the parameters: bf16_tile.hpp)
+  // (the range guard: the two-channel form is the DQN gradient — the policy chain's words)
+  bt::load_weights<CH == 2 ? bt::GUARD_POLICY : bt::GUARD_CRITIC>(
+      wimg, wave, lane, CH, tr.range, tr.range_err, fw, [&](int t, const bt::WRaw &r) {
+        const float w2 = CH == 2 && chan == 1 ? r.w2[1] : r.w2[0];
+        lv[0] = __builtin_fmaf(w2, r.wa, lv[0]);
+        lv[1] = __builtin_fmaf(w2, r.wb, lv[1]);
+        lv[2] = __builtin_fmaf(w2, r.wc, lv[2]);
+        // the forward runs on weights scaled by 2^96 (relu' by conversion, bf16_tile.hpp); the |pre| chain takes the
+        // scale back out through w2 (both exact)
+        w2v[t] = bt::FWD_UNSCALE * w2;
+      });
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    bt::WRaw r;
-    bt::wimg_load(wimg, t, lane, fw[t], r, CH);
-    const float w2 = CH == 2 && chan == 1 ? r.w2[1] : r.w2[0];
-    lv[0] = __builtin_fmaf(w2, r.wa, lv[0]);
-    lv[1] = __builtin_fmaf(w2, r.wb, lv[1]);
-    lv[2] = __builtin_fmaf(w2, r.wc, lv[2]);
-    // the forward runs on weights scaled by 2^96 (relu' by conversion, bf16_tile.hpp); the |pre| chain takes the scale
-    // back out through w2 (both exact)
-    if (guard) {  // (one wave sees all 128 units; the two-channel form is the DQN gradient: the policy chain's words)
-      constexpr int CHAIN = CH == 2 ? bt::GUARD_POLICY : bt::GUARD_CRITIC;
-      bt::range_guard_img(r, hf, gxmin, gxmax, tr.range_err + CHAIN, bt::range_veto(tr.range, CHAIN));
-    }
-    w2v[t] = bt::FWD_UNSCALE * w2;
-  }
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-#pragma unroll
-    for (int m = 1; m < 32; m <<= 1) lv[q] = lv[q] + __shfl_xor(lv[q], m, 64);  // over the 32 lanes of the half
+  for (int q = 0; q < 3; ++q) lv[q] = bt::half_sum(lv[q]);
   // backward accumulators (matrix pipe): dm[t][r] = sum over samples for hidden unit 32 t + row(r, hf), piece column n
   f32x16 dm[NT];
 #pragma unroll
@@ -106,27 +95,17 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
 
   Frag selb[2];  // piece-column selection (B operand of the routing product)
   bt::sel_frags(lane, selb);
-  // Tiles: the full ones in the loop, a ragged last one (B not a multiple of 32) after it on the wave whose turn it
-  // is, through the same code with a per-lane `valid` — the loop itself carries no validity selects.  Tile indices are
-  // wave-uniform (SGPRs); the operands come through buffer loads with a constant per-lane byte offset and the tile's
-  // offset as the scalar operand: no vector address arithmetic per tile.
+  // Tiles (bt::walk_tiles): indices are wave-uniform (SGPRs); the operands come through buffer loads with a constant
+  // per-lane byte offset and the tile's offset as the scalar operand: no vector address arithmetic per tile.
   const uint32_t B32 = (uint32_t)B, plane32 = (uint32_t)plane;
   const uint32_t n_full = B32 / 32u, tail = B32 & 31u;
   // The two waves of a SIMD do not progress alike: the older one (waves 0-3 of the workgroup, launched first) wins the
   // issue arbitration and used to finish its tiles at 0.71 of the launch, leaving the younger one alone — one wave per
   // SIMD, nothing to overlap its matrix instructions with — for the rest (profiles/r06_critic_step_timeline.txt).  So the
   // tiles are not dealt evenly: an older wave plays `share_old` virtual waves, a younger one `share_young`, and both
-  // finish together.  (Virtual wave ids: workgroup-major, the older waves' first.)
-  // (CH = 2: the two channels walk the same tiles — wave w and wave w + 4 are one virtual wave)
+  // finish together (bt::deal_tiles).  (CH = 2: the two channels walk the same tiles, dealt evenly.)
   if (CH == 2) share_old = share_young = 1u;
-  const uint32_t per_wg = CH == 2 ? (uint32_t)(CRITIC_WAVES / 2) : (CRITIC_WAVES / 2) * (share_old + share_young);
-  const uint32_t my_share = wave < CRITIC_WAVES / 2 ? share_old : share_young;
-  const uint32_t my_first =
-      blockIdx.x * per_wg + (CH == 2 ? (uint32_t)(wave & (CRITIC_WAVES / 2 - 1))
-                                     : wave < CRITIC_WAVES / 2 ? (uint32_t)wave * share_old
-                                                               : (CRITIC_WAVES / 2) * share_old +
-                                                                     (uint32_t)(wave - CRITIC_WAVES / 2) * share_young);
-  const uint32_t n_waves = gridDim.x * per_wg;  // virtual waves of the launch
+  const bt::Dealing deal = bt::deal_tiles<CRITIC_WAVES, CH>(wave, share_old, share_young);
   const bt::rsrc_t obs_r = bt::make_rsrc(tr.obs, (uint32_t)D * plane32 * 4u), tgt_r = bt::make_rsrc(tr.tgt, B32 * 4u);
   const bt::rsrc_t act_r = bt::make_rsrc(tr.action, B32);  // (CH = 2 only: the action taken selects the channel)
   const uint32_t off_a = ((uint32_t)(2 * hf) * plane32 + (uint32_t)n) * 4u, off_b = off_a + plane32 * 4u;
@@ -148,7 +127,7 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
     return o;
   };
 
-  auto tile = [&](auto ragged, TileOp op) {
+  auto tile = [&](auto ragged, TileOp op, uint32_t) {
     constexpr bool RAGGED = decltype(ragged)::value;
     const bool valid = RAGGED ? (uint32_t)n < tail : true;
     if (RAGGED) {  // (the observation planes extend past sample B - 1: what a padding lane read is not zero)
@@ -175,21 +154,10 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
       bt::mask_tile(c, ga[t]);  // relu'(pre): one conversion per two values
       c = cn;
     }
-    // ---- y: transpose the 16 partial sums per lane through LDS (row = sample, column = source lane; folding them in
-    // registers instead was measured in round 5 — the same time per step — and removed: DESIGN 17)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) Ysh[wave][(r & 3) + 8 * (r >> 2) + 4 * hf][n] = yp[r];
-    bt::wave_lds_fence();
-    float part = bt::row_sum16v(&Ysh[wave][n][hf * 16]);
-    {  // the linear half of relu: this half's inputs of sample n
-      float lin = lv[0] * op.xa;
-      lin = __builtin_fmaf(lv[1], op.xb, lin);
-      lin = __builtin_fmaf(lv[2], hf == 0 ? op.xc : 1.0f, lin);
-      part = part + lin;
-    }
-    float p0, p1;
-    bt::both_halves(part, p0, p1);
-    const float y = 0.5f * (p0 + p1) + b2;
+    // ---- y: the 16 partial sums per lane go through an LDS transpose (folding them in registers instead was measured in
+    // round 5 — the same time per step — and removed: DESIGN 17)
+    const float y =
+        0.5f * bt::transpose_sum(Ysh, wave, yp, [&] { return bt::linear_half(lv, op.xa, op.xb, op.xc, hf); }, n, hf) + b2;
     const float d = y - op.tgt;
     // (CH = 2: only the samples whose action is this wave's channel count — loss, db2 and the backward alike)
     const bool mine = CH == 2 ? valid && op.act == (uint32_t)chan : valid;
@@ -214,25 +182,10 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
     }
   };
 
-  for (uint32_t vw = 0; vw < my_share; ++vw) {
-   const uint32_t wave_id = my_first + vw;
-   if (wave_id < n_full) {
-    // global loads run one tile ahead (past the wave's last tile: that tile again), into two named buffers that take
-    // turns — no register moves.  (Two tiles ahead — by register moves or by rotating three named buffers through a
-    // loop unrolled three times — is SLOWER, 0.237 against 0.220 ms per step, although a timing build without the loads
-    // runs in 0.197: what the loads cost is issue slots, not exposed latency.)
-    TileOp op_a = load_tile(wave_id), op_b = op_a;
-    for (uint32_t g = wave_id; g < n_full; g += 2 * n_waves) {
-      const uint32_t g1 = g + n_waves, g2 = g1 + n_waves;
-      op_b = load_tile(g1 < n_full ? g1 : g);
-      tile(std::false_type{}, op_a);
-      if (g1 >= n_full) break;
-      op_a = load_tile(g2 < n_full ? g2 : g1);
-      tile(std::false_type{}, op_b);
-    }
-   }
-   if (tail != 0 && n_full % n_waves == wave_id) tile(std::true_type{}, load_tile(n_full));
-  }
+  // (loading two tiles ahead — by register moves or by rotating three named buffers through a loop unrolled three
+  // times — is SLOWER than the walk's one, 0.237 against 0.220 ms per step, although a timing build without the loads
+  // runs in 0.197: what the loads cost is issue slots, not exposed latency)
+  bt::walk_tiles<true>(deal, n_full, tail, load_tile, tile);
   if (since_flush != 0 || !flushed) {  // (a wave whose tile count is a multiple of the flush period has nothing left: at
                                        // the headline size every wave owns exactly 2 x C_FLUSH tiles, and this was a
                                        // third flush of zeros; a wave without tiles still defines its image)
@@ -240,19 +193,7 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
     loss64 += (double)loss32;
     db2_64 += (double)db2_32;
   }
-  // loss / db2: reduce over the 32 owner lanes of the wave (f64 moved as two 32-bit halves)
-  auto xlane = [](double v, int mask) {
-    uint64_t bits = rl_f64_bits(v);
-    uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)bits, mask, 64);
-    uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(bits >> 32), mask, 64);
-    return rl_f64_from_bits(((uint64_t)hi << 32) | lo);
-  };
-  double l = hf == 0 ? loss64 : 0.0, bsum = hf == 0 ? db2_64 : 0.0;
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) {
-    l = l + xlane(l, s);
-    bsum = bsum + xlane(bsum, s);
-  }
+  const double l = bt::owner_sum(loss64, hf), bsum = bt::owner_sum(db2_64, hf);
   if (lane == 0) {
     acc64[H * 7] = bsum;   // db2
     acc64[H * 7 + 1] = l;  // loss partial
@@ -260,51 +201,17 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
   __syncthreads();
   // sum the per-wave images in wave order, turn M into gradients and write the workgroup's slab row
   for (uint32_t p = threadIdx.x; p <= P; p += CRITIC_WAVES * 64) {
-    auto tot = [&](int src) {
-      double s = Acc[0][src];
-#pragma unroll
-      for (int w = 1; w < CRITIC_WAVES; ++w) s = s + Acc[w][src];
-      return s;
-    };
-    auto totc = [&](int c, int src) {  // CH = 2: the four waves of channel c
-      double s = Acc[4 * c][src];
-#pragma unroll
-      for (int w = 1; w < CRITIC_WAVES / 2; ++w) s = s + Acc[4 * c + w][src];
-      return s;
-    };
+    auto tot = [&](int src) { return bt::image_sum<CRITIC_WAVES>(Acc, src); };
+    auto totc = [&](int c, int src) { return bt::image_sum<CRITIC_WAVES / 2>(Acc + 4 * c, src); };  // channel c's waves
     double s;
-    if (CH == 2) {
-      if (p < (uint32_t)(H * D)) {
-        const int j = p / D, k = p % D;
-        s = totc(0, j * 7 + k) * (double)W2[j] + totc(1, j * 7 + k) * (double)W2[H + j];
-      } else if (p < (uint32_t)(H * D + H)) {
-        const int j = p - H * D;
-        s = totc(0, j * 7 + 5) * (double)W2[j] + totc(1, j * 7 + 5) * (double)W2[H + j];
-      } else if (p < (uint32_t)(H * D + H + 2 * H)) {
-        const int q = p - H * D - H, c = q / H, j = q % H;
-        s = totc(c, j * 7 + 5) * (double)b1[j];
-#pragma unroll
-        for (int k = 0; k < D; ++k) s += totc(c, j * 7 + k) * (double)W1[j * D + k];
-      } else if (p < P) {
-        s = totc((int)(p - (H * D + H + 2 * H)), H * 7);
-      } else {
-        s = tot(H * 7 + 1);
-      }
-    } else if (p < (uint32_t)(H * D)) {
-      int j = p / D, k = p % D;
-      s = tot(j * 7 + k) * (double)W2[j];
-    } else if (p < (uint32_t)(H * D + H)) {
-      int j = p - H * D;
-      s = tot(j * 7 + 5) * (double)W2[j];
-    } else if (p < (uint32_t)(H * D + 2 * H)) {
-      int j = p - H * D - H;
-      s = tot(j * 7 + 5) * (double)b1[j];
-#pragma unroll
-      for (int k = 0; k < D; ++k) s += tot(j * 7 + k) * (double)W1[j * D + k];
-    } else if (p == (uint32_t)(H * D + 2 * H)) {
-      s = tot(H * 7);
+    if (p >= bt::par_b2(CH)) {
+      s = p == P ? tot(H * 7 + 1) : CH == 2 ? totc((int)(p - bt::par_b2(CH)), H * 7) : tot(H * 7);  // loss; db2
+    } else if (CH == 2) {
+      s = bt::grad_entry<2>(p, params, [&](int c, int j, int k) { return totc(c, j * 7 + k); },
+                            [&](int c, int j) { return (double)W2[c * H + j]; });
     } else {
-      s = tot(H * 7 + 1);
+      s = bt::grad_entry<1>(p, params, [&](int, int j, int k) { return tot(j * 7 + k); },
+                            [&](int, int j) { return (double)W2[j]; });
     }
     if (p < P) slabA[(size_t)blockIdx.x * P + p] = s;
     else slabB[(size_t)blockIdx.x * 4 + 0] = s;
@@ -320,16 +227,9 @@ bool launch_critic_step_v2(rl_traj *traj, const rl_mlp *critic, uint64_t B_total
   const uint32_t *wimg = wimg_ensure(critic);
   ProfScope ps(traj->eng, RL_K_CRITIC_FUSED);
   float two_over_B = 2.0f / (float)B_total;
-  // persistent grid: one fat workgroup per CU (fewer, fatter workgroups = fewer slab rows for the reduction that follows
-  // every launch), one 32-sample tile per wave and iteration
-  const uint64_t n_tiles = (traj->B + 31) / 32, cus = (uint64_t)traj->eng->prop.multiProcessorCount;
-  uint64_t nb = (n_tiles + CRITIC_WAVES - 1) / CRITIC_WAVES;
-  if (nb > cus) nb = cus;
-  traj->nbC = (uint32_t)nb;
+  traj->nbC = fused_grid(traj, CRITIC_WAVES);
   traj->last_rows = traj->nbC;
-  TrajDev d = traj->d;
-  if (!traj->guard_next_critic) d.range = nullptr;  // (the range guard: first critic launch of the call only, engine.hpp)
-  traj->guard_next_critic = false;
+  const TrajDev d = fused_traj_dev(traj, traj->guard_next_critic);
   hipLaunchKernelGGL(k_critic_step_mfma<1>, dim3(traj->nbC), dim3(CRITIC_WAVES * 64), 0, traj->eng->stream, d,
                      critic->d_params, wimg, traj->slabA, traj->slabB, two_over_B, (uint32_t)critic->P,
                      bt::SHARE_OLD, bt::SHARE_YOUNG);  // (shares of the tiles: the kernel says why)
@@ -342,15 +242,11 @@ bool launch_dqn_step_pair(rl_traj *mb, const rl_mlp *qnet, uint64_t B_total) {
   if (!fused_5_128_fits(mb, qnet, 2)) return false;  // (rl_dqn_create takes feed-forward modules only)
   const uint32_t *wimg = wimg_ensure(qnet);
   ProfScope ps(mb->eng, RL_K_POLICY_FUSED);
-  const uint64_t n_tiles = (mb->B + 31) / 32, cus = (uint64_t)mb->eng->prop.multiProcessorCount;
-  uint64_t nb = (n_tiles + CRITIC_WAVES / 2 - 1) / (CRITIC_WAVES / 2);  // four tile-walking wave pairs per workgroup
-  if (nb > cus) nb = cus;
-  mb->nbV2 = (uint32_t)nb;  // slab rows of this launch (the slabs are sized for any grid up to 8 x CUs)
-  TrajDev d = mb->d;
+  // four tile-walking wave pairs per workgroup; slab rows of this launch (the slabs are sized for any grid up to 8 x CUs)
+  mb->nbV2 = fused_grid(mb, CRITIC_WAVES / 2);
+  TrajDev d = fused_traj_dev(mb, mb->guard_next_policy);
   d.tgt = mb->d.adv;  // (the minibatch workspace keeps its targets where a trajectory keeps advantages)
-  if (!mb->guard_next_policy) d.range = nullptr;  // (the range guard: first step of an update only, engine.hpp)
-  mb->guard_next_policy = false;
-  hipLaunchKernelGGL(k_critic_step_mfma<2>, dim3((uint32_t)nb), dim3(CRITIC_WAVES * 64), 0, mb->eng->stream, d,
+  hipLaunchKernelGGL(k_critic_step_mfma<2>, dim3(mb->nbV2), dim3(CRITIC_WAVES * 64), 0, mb->eng->stream, d,
                      qnet->d_params, wimg, mb->slabA, mb->slabB, 2.0f / (float)B_total, (uint32_t)qnet->P, 1u, 1u);
   RL_HIP_CHECK(hipGetLastError());
   return true;

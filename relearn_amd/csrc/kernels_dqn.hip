@@ -788,7 +788,7 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
                     double *__restrict__ slabB, float two_over_B, uint32_t P, float gamma) {
   using bt::f32x16;
   using bt::Frag;
-  constexpr int D = 5, H = 128, NT = bt::NT, A = 2;
+  constexpr int H = 128, NT = bt::NT, A = 2;
   constexpr int CH = H * 7;            // one channel's image: per hidden unit M[0..5] (slot 6 unused)
   constexpr int IMG = A * CH + A + 1;  // two channels, db2[0], db2[1], loss
   __shared__ float Ysh[DQN_WAVES][A][32][33];
@@ -796,8 +796,7 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = lane & 31, hf = lane >> 5;
-  const float *__restrict__ W1 = params, *__restrict__ b1 = W1 + H * D, *__restrict__ W2 = b1 + H,
-                           *__restrict__ b2 = W2 + A * H;
+  const float *__restrict__ W2 = params + bt::PAR_W2, *__restrict__ b2 = params + bt::par_b2(A);
   const size_t B = (size_t)tr.T * tr.n;
   const size_t plane = (size_t)(tr.T + 1) * tr.n;
   double *acc64 = Acc[wave];
@@ -810,7 +809,9 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
   float gxmin = 0.0f, gxmax = 0.0f;
   if (guard) bt::range_bounds(tr.range, lane, gxmin, gxmax);
   // (the 2^96-scaled pieces — relu' by conversion, bf16_tile.hpp; the |pre| chains take the scale back out — come
-  // ready-made from the module's weight image, written by whoever wrote the parameters)
+  // ready-made from the module's weight image, written by whoever wrote the parameters.  This is bt::load_weights
+  // written out: through the helper the compiler keeps the fragments of this kernel, the one with the whole register
+  // file, in other registers — 76 more moves and 2 % on a launch, measured.)
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     bt::WRaw r;
@@ -829,9 +830,7 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
 #pragma unroll
   for (int a = 0; a < A; ++a)
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int m = 1; m < 32; m <<= 1) lv[a][q] = lv[a][q] + __shfl_xor(lv[a][q], m, 64);
+    for (int q = 0; q < 3; ++q) lv[a][q] = bt::half_sum(lv[a][q]);
   const float b20 = b2[0], b21 = b2[1];
   f32x16 dm[A][NT];
 #pragma unroll
@@ -961,46 +960,21 @@ __global__ void __launch_bounds__(DQN_WAVES * 64)
   }
   if (since_flush != 0 || !flushed) flush_all();  // (nothing left when the last tile ended a flush period; a wave
                                                   // without tiles still defines its image)
-  auto xlane = [](double v, int mask) {
-    uint64_t bits = rl_f64_bits(v);
-    uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)bits, mask, 64);
-    uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(bits >> 32), mask, 64);
-    return rl_f64_from_bits(((uint64_t)hi << 32) | lo);
-  };
-  double l = hf == 0 ? loss64 : 0.0, s0 = hf == 0 ? db64[0] : 0.0, s1 = hf == 0 ? db64[1] : 0.0;
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) {
-    l = l + xlane(l, s);
-    s0 = s0 + xlane(s0, s);
-    s1 = s1 + xlane(s1, s);
-  }
+  const double l = bt::owner_sum(loss64, hf), s0 = bt::owner_sum(db64[0], hf), s1 = bt::owner_sum(db64[1], hf);
   if (lane == 0) {
     acc64[A * CH] = s0;
     acc64[A * CH + 1] = s1;
     acc64[A * CH + 2] = l;
   }
   __syncthreads();
-  auto tot = [&](int src) {
-    double s = Acc[0][src];
-#pragma unroll
-    for (int w = 1; w < DQN_WAVES; ++w) s = s + Acc[w][src];
-    return s;
-  };
+  auto tot = [&](int src) { return bt::image_sum<DQN_WAVES>(Acc, src); };
   for (uint32_t p = threadIdx.x; p < P; p += DQN_WAVES * 64) {
     double s;
-    if (p < (uint32_t)(H * D)) {
-      const int j = p / D, k = p % D;
-      s = tot(j * 7 + k) * (double)W2[j] + tot(CH + j * 7 + k) * (double)W2[H + j];
-    } else if (p < (uint32_t)(H * D + H)) {
-      const int j = p - H * D;
-      s = tot(j * 7 + 5) * (double)W2[j] + tot(CH + j * 7 + 5) * (double)W2[H + j];
-    } else if (p < (uint32_t)(H * D + H + A * H)) {
-      const int q = p - H * D - H, a = q / H, j = q % H;
-      s = tot(a * CH + j * 7 + 5) * (double)b1[j];
-#pragma unroll
-      for (int k = 0; k < D; ++k) s += tot(a * CH + j * 7 + k) * (double)W1[j * D + k];
+    if (p < bt::par_b2(A)) {
+      s = bt::grad_entry<2>(p, params, [&](int c, int j, int k) { return tot(c * CH + j * 7 + k); },
+                            [&](int c, int j) { return (double)W2[c * H + j]; });
     } else {
-      s = tot(A * CH + (int)(p - (H * D + H + A * H)));
+      s = tot(A * CH + (int)(p - bt::par_b2(A)));  // db2[0], db2[1]
     }
     slabA[(size_t)blockIdx.x * P + p] = s;
   }
@@ -1012,14 +986,9 @@ bool launch_dqn_step_bf16(rl_traj *mb, const rl_mlp *qnet, uint64_t B_total, flo
   if (!fused_5_128_fits(mb, qnet, 2)) return false;  // (rl_dqn_create takes feed-forward modules only)
   const uint32_t *wimg = wimg_ensure(qnet);
   ProfScope ps(mb->eng, RL_K_POLICY_FUSED);
-  const uint64_t n_tiles = (mb->B + 31) / 32, cus = (uint64_t)mb->eng->prop.multiProcessorCount;
-  uint64_t nb = (n_tiles + DQN_WAVES - 1) / DQN_WAVES;
-  if (nb > cus) nb = cus;
-  mb->nbV2 = (uint32_t)nb;  // slab rows of this launch (the slabs are sized for any grid up to 8 x CUs)
-  TrajDev d = mb->d;
-  if (!mb->guard_next_policy) d.range = nullptr;  // (the range guard: first step of an update only, engine.hpp)
-  mb->guard_next_policy = false;
-  hipLaunchKernelGGL(k_dqn_step_bf16, dim3((uint32_t)nb), dim3(DQN_WAVES * 64), 0, mb->eng->stream, d, qnet->d_params,
+  mb->nbV2 = fused_grid(mb, DQN_WAVES);  // slab rows of this launch (the slabs are sized for any grid up to 8 x CUs)
+  const TrajDev d = fused_traj_dev(mb, mb->guard_next_policy);
+  hipLaunchKernelGGL(k_dqn_step_bf16, dim3(mb->nbV2), dim3(DQN_WAVES * 64), 0, mb->eng->stream, d, qnet->d_params,
                      wimg, mb->slabA, mb->slabB, 2.0f / (float)B_total, (uint32_t)qnet->P, gamma);
   RL_HIP_CHECK(hipGetLastError());
   return true;

@@ -685,19 +685,8 @@ __global__ void __launch_bounds__(GWAVES * 64)
     op = next;
   }
   // the wave's scalar sums: over its 32 owner lanes
-  auto xlane = [](double v, int mask) {
-    uint64_t bits = rl_f64_bits(v);
-    uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)bits, mask, 64);
-    uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(bits >> 32), mask, 64);
-    return rl_f64_from_bits(((uint64_t)hi << 32) | lo);
-  };
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    double s = kb == 0 ? sum64[q] : 0.0;
-#pragma unroll
-    for (int sft = 16; sft > 0; sft >>= 1) s = s + xlane(s, sft);
-    sum64[q] = s;
-  }
+  for (int q = 0; q < 3; ++q) sum64[q] = bt::owner_sum(sum64[q], kb);
   if (lane == 0) {
     double *sb = slabB + wave_id * 4;
     sb[0] = sum64[0];
@@ -1073,19 +1062,8 @@ __global__ void __launch_bounds__(PAIRS * 128)
     op = next;
   }
   if (h != 0) return;  // the scalar sums live on wave 0 of the pair
-  auto xlane = [](double v, int mask) {
-    uint64_t bits = rl_f64_bits(v);
-    uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)bits, mask, 64);
-    uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(bits >> 32), mask, 64);
-    return rl_f64_from_bits(((uint64_t)hi << 32) | lo);
-  };
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    double s = kb == 0 ? sum64[q] : 0.0;
-#pragma unroll
-    for (int sft = 16; sft > 0; sft >>= 1) s = s + xlane(s, sft);
-    sum64[q] = s;
-  }
+  for (int q = 0; q < 3; ++q) sum64[q] = bt::owner_sum(sum64[q], kb);
   if (lane == 0) {
     double *sb = slabB + pair_id * 4;
     sb[0] = sum64[0];

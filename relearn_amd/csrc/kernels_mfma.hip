@@ -2,8 +2,6 @@
 // categorical policy on the bf16 matrix pipe.  The tile machinery is bf16_tile.hpp; the critic step (one output) is
 // kernels_critic.hip, which also holds the DQN gradient (two outputs, k_critic_step_mfma<2>); with in-kernel TD targets
 // the DQN gradient is k_dqn_step_bf16 in kernels_dqn.hip.
-// (Rounds 1-2 ran these passes on the f32 MFMA with the backward on the VALU; that kernel is gone — its last user was
-// the DQN gradient.)
 #include <type_traits>
 
 #include "bf16_tile.hpp"
@@ -57,8 +55,8 @@ __global__ void __launch_bounds__(WAVES * 64)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform: tile indices stay scalar
   const int n = lane & 31, hf = lane >> 5;
-  const float *__restrict__ W1 = params, *__restrict__ b1 = W1 + H * D, *__restrict__ W2 = b1 + H,
-                           *__restrict__ b2 = W2 + A * H;
+  const float *__restrict__ W1 = params, *__restrict__ b1 = W1 + bt::PAR_B1, *__restrict__ W2 = params + bt::PAR_W2,
+                           *__restrict__ b2 = params + bt::par_b2(A);
   const size_t B = (size_t)tr.T * tr.n;
   const size_t plane = (size_t)(tr.T + 1) * tr.n;
   double *acc64 = Acc[wave];
@@ -71,22 +69,13 @@ __global__ void __launch_bounds__(WAVES * 64)
   float w2d[NT];
   float lvd[3] = {0.0f, 0.0f, 0.0f};  // the linear half of relu (bf16_tile.hpp) for the differenced logit
   float tb2d = 0.0f;
-  const bool guard = blockIdx.x == 0 && wave == 0 && tr.range != nullptr;  // the numeric range guard (bf16_tile.hpp)
-  float gxmin = 0.0f, gxmax = 0.0f;
-  if (guard) bt::range_bounds(tr.range, lane, gxmin, gxmax);
-  // (the pieces come ready-made from the module's weight image, written by whoever wrote the parameters: bf16_tile.hpp)
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    bt::WRaw r;
-    bt::wimg_load(wimg, t, lane, fw[t], r, 2);
-    // the forward runs on weights scaled by 2^96 (relu' by conversion, bf16_tile.hpp); the |pre| chain of the gradient /
-    // evaluation passes takes the scale back out through w2d (both exact); the Fisher-vector pass only needs the masks
-    if (guard)  // (one wave sees all 128 units)
-      bt::range_guard_img(r, hf, gxmin, gxmax, tr.range_err + bt::GUARD_POLICY, bt::range_veto(tr.range, bt::GUARD_POLICY));
+  bt::load_weights<bt::GUARD_POLICY>(wimg, wave, lane, 2, tr.range, tr.range_err, fw, [&](int t, const bt::WRaw &r) {
     if (FW_LDS && wave == t) {
 #pragma unroll
       for (int i = 0; i < 3; ++i) Fw[t * 3 + i][lane] = fw[t][i].x;
     }
+    // the forward runs on weights scaled by 2^96 (relu' by conversion, bf16_tile.hpp); the |pre| chain of the gradient /
+    // evaluation passes takes the scale back out through w2d (both exact); the Fisher-vector pass only needs the masks
     const float wd = r.w2[0] - r.w2[1];
     if (!JVP) {
       lvd[0] = __builtin_fmaf(wd, r.wa, lvd[0]);
@@ -94,11 +83,11 @@ __global__ void __launch_bounds__(WAVES * 64)
       lvd[2] = __builtin_fmaf(wd, r.wc, lvd[2]);
     }
     w2d[t] = bt::FWD_UNSCALE * wd;
-  }
+  });
   if (JVP) {
     // Z_jk = w2d_j V~1[j][k] + t2d_j W~1[j][k] (k = 5: the bias row): the tangent logit difference is
     // sum_j relu'(pre_j) (x~ . Z_j) + (vb2_0 - vb2_1) = sum_k x~_k q_k + ..., q = the masked sum of Z's rows
-    const float *__restrict__ V1 = tangent, *__restrict__ vb1 = V1 + H * D, *__restrict__ V2 = vb1 + H;
+    const float *__restrict__ V1 = tangent, *__restrict__ vb1 = V1 + bt::PAR_B1, *__restrict__ V2 = tangent + bt::PAR_W2;
     bt::l2_build(Fz, (int)threadIdx.x, WAVES * 64, [&](int j, int k) {
       const float wd = W2[j] - W2[H + j], t2d = V2[j] - V2[H + j];
       const float w = k < D ? W1[j * D + k] : b1[j], v = k < D ? V1[j * D + k] : vb1[j];
@@ -107,13 +96,11 @@ __global__ void __launch_bounds__(WAVES * 64)
   }
   if (JVP || FW_LDS) __syncthreads();
   if (JVP) {
-    const float *__restrict__ vb2 = tangent + H * D + H + A * H;
+    const float *__restrict__ vb2 = tangent + bt::par_b2(A);
     tb2d = vb2[0] - vb2[1];
   } else {
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int m = 1; m < 32; m <<= 1) lvd[q] = lvd[q] + __shfl_xor(lvd[q], m, 64);
+    for (int q = 0; q < 3; ++q) lvd[q] = bt::half_sum(lvd[q]);
   }
   const float b2d = b2[0] - b2[1];
   Frag selb[2], idb[2];  // piece-column selection, identity (B operands of the routing / transposing products)
@@ -136,34 +123,14 @@ __global__ void __launch_bounds__(WAVES * 64)
   };
   bt::wave_lds_fence();
 
-  // sum over the 32 source lanes of 16 per-lane partials (+ this half's linear part): LDS transpose, the result for
-  // sample n in both halves
-  auto lane_sum = [&](const float(&yp)[16], float lin) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) Ysh[JVP ? 0 : wave][(r & 3) + 8 * (r >> 2) + 4 * hf][n] = yp[r];
-    bt::wave_lds_fence();
-    float part = bt::row_sum16v(&Ysh[JVP ? 0 : wave][n][hf * 16]);
-    part = part + lin;
-    float p0, p1;
-    bt::both_halves(part, p0, p1);
-    bt::wave_lds_fence();
-    return p0 + p1;
-  };
-
-  // Tiles: the full ones in the loop, a ragged last one (B not a multiple of 32) after it on the wave whose turn it is,
-  // through the same code with a per-lane `valid` — the loop carries no validity selects.  Tile indices are wave-uniform
-  // (SGPRs); the operands come through buffer loads with a constant per-lane byte offset and the tile's offset as the
-  // scalar operand: no vector address arithmetic per tile (kernels_critic.hip has the same loop).
+  // Tiles (bt::walk_tiles): indices are wave-uniform (SGPRs); the operands come through buffer loads with a constant
+  // per-lane byte offset and the tile's offset as the scalar operand: no vector address arithmetic per tile.
   const uint32_t B32 = (uint32_t)B, plane32 = (uint32_t)plane;
   const uint32_t n_full = B32 / 32u, tail = B32 & 31u;
   // (the tiles are dealt 5 : 3 between the older and the younger wave of a SIMD: bf16_tile.hpp SHARE_OLD; the
   // sixteen-wave evaluation pass deals evenly — its launcher passes 1 : 1)
-  if (WAVES != 8) share_old = share_young = 1u;  // (compile-time for the sixteen-wave form: its loop below folds away)
-  const uint32_t per_wg = (WAVES / 2) * (share_old + share_young);
-  const uint32_t my_share = wave < WAVES / 2 ? share_old : share_young;
-  const uint32_t my_first = blockIdx.x * per_wg + (wave < WAVES / 2 ? (uint32_t)wave * share_old
-                                                   : (WAVES / 2) * share_old + (uint32_t)(wave - WAVES / 2) * share_young);
-  const uint32_t n_waves = gridDim.x * per_wg;  // virtual waves of the launch
+  if (WAVES != 8) share_old = share_young = 1u;  // (compile-time for the sixteen-wave form: the walk's outer loop folds away)
+  const bt::Dealing deal = bt::deal_tiles<WAVES>(wave, share_old, share_young);
   const bt::rsrc_t obs_r = bt::make_rsrc(tr.obs, (uint32_t)D * plane32 * 4u), lp0_r = bt::make_rsrc(lp0, 2u * B32 * 4u);
   const bt::rsrc_t adv_r = bt::make_rsrc(tr.adv, B32 * 4u), act_r = bt::make_rsrc(tr.action, B32);
   const uint32_t off_a = ((uint32_t)(2 * hf) * plane32 + (uint32_t)n) * 4u, off_b = off_a + plane32 * 4u;
@@ -245,10 +212,9 @@ __global__ void __launch_bounds__(WAVES * 64)
       bt::both_halves(bt::l2_dot(q, op.xa, op.xb, hf == 0 ? op.xc : 1.0f), p0, p1);
       s0 = p0 + p1;
     } else {
-      float lin = lvd[0] * op.xa;
-      lin = __builtin_fmaf(lvd[1], op.xb, lin);
-      lin = __builtin_fmaf(lvd[2], hf == 0 ? op.xc : 1.0f, lin);
-      s0 = 0.5f * lane_sum(y0, lin);
+      s0 = 0.5f * bt::transpose_sum(
+                      Ysh, JVP ? 0 : wave, y0, [&] { return bt::linear_half(lvd, op.xa, op.xb, op.xc, hf); }, n, hf);
+      bt::wave_lds_fence();  // Ysh is rewritten by the next tile
     }
     // ---- per-sample math on the owner lanes (lane n and n + 32 both hold sample n)
     float dz0 = 0.0f, dz1 = 0.0f;
@@ -330,52 +296,15 @@ __global__ void __launch_bounds__(WAVES * 64)
       fold();
     }
   };
-  for (uint32_t vw = 0; vw < my_share; ++vw) {
-   const uint32_t wave_id = my_first + vw;
-   if (wave_id < n_full) {
-    // loads run one tile ahead (past the wave's last tile: that tile again), into two named buffers that take turns
-    // (the Fisher-vector pass has no registers for a second buffer: one buffer and a move per operand there)
-    TileOp op_a = load_tile(wave_id), op_b = op_a;
-    if (JVP) {
-      for (uint32_t g = wave_id; g < n_full; g += n_waves) {
-        const uint32_t g1 = g + n_waves;
-        op_b = load_tile(g1 < n_full ? g1 : g);
-        tile(std::false_type{}, op_a, g);
-        op_a = op_b;
-      }
-    } else {
-      for (uint32_t g = wave_id; g < n_full; g += 2 * n_waves) {
-        const uint32_t g1 = g + n_waves, g2 = g1 + n_waves;
-        op_b = load_tile(g1 < n_full ? g1 : g);
-        tile(std::false_type{}, op_a, g);
-        if (g1 >= n_full) break;
-        op_a = load_tile(g2 < n_full ? g2 : g1);
-        tile(std::false_type{}, op_b, g1);
-      }
-    }
-   }
-   if (tail != 0 && n_full % n_waves == wave_id) tile(std::true_type{}, load_tile(n_full), n_full);
-  }
+  // (the Fisher-vector pass has no registers for a second operand buffer)
+  bt::walk_tiles<!JVP>(deal, n_full, tail, load_tile, tile);
   if (BWD && (since_flush != 0 || !flushed)) bt::flush(dm, acc64, IW, n, hf, !flushed);  // (nothing left when the last
                                                                 // tile ended a flush period; a wave without tiles
                                                                 // still defines its image)
   fold();
-  auto xlane = [](double v, int mask) {
-    uint64_t bits = rl_f64_bits(v);
-    uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)bits, mask, 64);
-    uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(bits >> 32), mask, 64);
-    return rl_f64_from_bits(((uint64_t)hi << 32) | lo);
-  };
-  double r0 = hf == 0 ? sum0 : 0.0, r1 = hf == 0 ? sum1 : 0.0, r2 = hf == 0 ? db2_0 : 0.0, r3 = hf == 0 ? db2_1 : 0.0;
-  double r4 = hf == 0 ? sum2 : 0.0;
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) {
-    r0 = r0 + xlane(r0, s);
-    r1 = r1 + xlane(r1, s);
-    r2 = r2 + xlane(r2, s);
-    r3 = r3 + xlane(r3, s);
-    if (MODE == PASS_INIT) r4 = r4 + xlane(r4, s);
-  }
+  const double r0 = bt::owner_sum(sum0, hf), r1 = bt::owner_sum(sum1, hf);
+  const double r2 = bt::owner_sum(db2_0, hf), r3 = bt::owner_sum(db2_1, hf);
+  const double r4 = MODE == PASS_INIT ? bt::owner_sum(sum2, hf) : 0.0;
   constexpr int TAIL = BWD ? H * IW : 0;
   if (lane == 0) {
     if (BWD) {
@@ -390,29 +319,16 @@ __global__ void __launch_bounds__(WAVES * 64)
     }
   }
   __syncthreads();
-  auto tot = [&](int src) {
-    double s = Acc[0][src];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) s = s + Acc[w][src];
-    return s;
-  };
+  auto tot = [&](int src) { return bt::image_sum<WAVES>(Acc, src); };
   if (BWD) {
     for (uint32_t p = threadIdx.x; p < P; p += WAVES * 64) {
-      double s = 0.0;
-      if (p < (uint32_t)(H * D)) {  // M_0 = M_d, M_1 = -M_d
-        int j = p / D, k = p % D;
-        s = tot(j * IW + k) * ((double)W2[j] - (double)W2[H + j]);
-      } else if (p < (uint32_t)(H * D + H)) {
-        int j = p - H * D;
-        s = tot(j * IW + 5) * ((double)W2[j] - (double)W2[H + j]);
-      } else if (p < (uint32_t)(H * D + H + A * H)) {
-        int q = p - H * D - H, a = q / H, j = q % H;
-        s = tot(j * IW + 5) * (double)b1[j];
-#pragma unroll
-        for (int k = 0; k < D; ++k) s += tot(j * IW + k) * (double)W1[j * D + k];
-        if (a == 1) s = -s;
+      double s;
+      if (p < bt::par_b2(A)) {  // M_0 = M_d, M_1 = -M_d
+        s = bt::grad_entry<1>(p, params, [&](int, int j, int k) { return tot(j * IW + k); },
+                              [&](int, int j) { return (double)W2[j] - (double)W2[H + j]; });
+        if (p >= bt::PAR_W2 + H) s = -s;
       } else {
-        s = tot(TAIL + (int)(p - (H * D + H + A * H)));
+        s = tot(TAIL + (int)(p - bt::par_b2(A)));
       }
       slabA[(size_t)blockIdx.x * P + p] = s;
     }
@@ -439,13 +355,12 @@ bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float
   const uint32_t *wimg = wimg_ensure(policy);
   ProfScope ps(traj->eng, mode == PASS_JVP ? RL_K_POLICY_FVP : RL_K_POLICY_FUSED);
   float inv_B = 1.0f / (float)B_total;
+  traj->nbV2 = fused_grid(traj, V2_WAVES);  // (what traj_plan planned: one tile per wave and iteration)
   traj->last_rows = traj->nbV2;
   dim3 g(traj->nbV2), b(V2_WAVES * 64);
   hipStream_t s = traj->eng->stream;
   uint32_t P = (uint32_t)policy->P;
-  TrajDev d = traj->d;
-  if (!traj->guard_next_policy) d.range = nullptr;  // (the range guard: first policy launch of the call only, engine.hpp)
-  traj->guard_next_policy = false;
+  const TrajDev d = fused_traj_dev(traj, traj->guard_next_policy);
 #define BLAUNCH(MM)                                                                                                  \
   hipLaunchKernelGGL((k_policy_bf16<MM, V2_WAVES>), g, b, 0, s, d, policy->d_params, wimg, d_tangent, traj->lp0,       \
                      traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo, clip_hi, bt::SHARE_OLD, bt::SHARE_YOUNG)
