@@ -33,7 +33,9 @@ def variant(engine, request):
 
 
 def make(engine, n=256, hidden=128, capacity=64, minibatch=500, max_steps=23, td=False, opt_steps=4, limit=None,
-         eps=("const", 0.3), lane_offset=0, episode_capacity=0):
+         eps=("const", 0.3), lane_offset=0, episode_capacity=0, opt=None, key=KEY):
+    """`opt`: builds the device agent's optimiser from its module (default: Adam, as the oracle's update has);
+    `key`: the seed of the agent's Prng, which draws the minibatches' episodes"""
     limit = ra.LIMIT_VISIBLE if limit is None else limit
     D = 5 if limit == ra.LIMIT_VISIBLE else 4
     env = ra.CartPoleEnv(engine, n, max_steps=max_steps, limit=limit, seed_env=21, seed_actor=34,
@@ -42,7 +44,7 @@ def make(engine, n=256, hidden=128, capacity=64, minibatch=500, max_steps=23, td
     qs = O.MlpShape(D, hidden, 2)
     q = ra.Mlp(engine, D, hidden, 2)
     q.init(77)
-    opt = ra.Adam(q)
+    opt = ra.Adam(q) if opt is None else opt(q)
     cfg = ra.dqn_config_default()
     cfg.target = ra.DQN_TARGET_ONE_STEP_TD if td else ra.DQN_TARGET_REWARD_TO_GO
     if eps[0] == "const":
@@ -55,10 +57,10 @@ def make(engine, n=256, hidden=128, capacity=64, minibatch=500, max_steps=23, td
     cfg.buffer_capacity = capacity
     cfg.episode_capacity = episode_capacity
     cfg.discount_factor = 0.99
-    for i, k in enumerate(KEY):
+    for i, k in enumerate(key):
         cfg.agent_key[i] = k
     dqn = ra.Dqn(env, q, opt, cfg)
-    osim = O.DqnSim(sim, qs, O.mlp_init(qs, 77), capacity, KEY, minibatch, gamma=np.float32(0.99), one_step_td=td)
+    osim = O.DqnSim(sim, qs, O.mlp_init(qs, 77), capacity, key, minibatch, gamma=np.float32(0.99), one_step_td=td)
     return dqn, osim
 
 
@@ -132,14 +134,16 @@ def test_update_on_an_empty_store_fails_before_any_step(engine, td):
     assert not np.array_equal(dqn.qnet.get_params(), before)
 
 
-def test_a_sampler_failure_in_a_later_chunk_leaves_the_agent_as_it_was(engine):
+@pytest.mark.parametrize("td", [False, True], ids=["reward-to-go", "one-step-td"])
+def test_a_sampler_failure_in_a_later_chunk_leaves_the_agent_as_it_was(engine, td):
     """With pipelined draws the chunks of an update are validated one by one while earlier chunks already train.  A
     failure in a later chunk (injected: RELEARN_DQN_FAIL_CHUNK) must still leave network, Adam moments and step count as
     they were before the call — the update is all or nothing — so that the next update does exactly what
-    it does for an agent that never saw the failure."""
+    it does for an agent that never saw the failure.  (One-step TD: the targets are formed inside the gradient launch
+    from the module's weight image, which the restore must invalidate for the next update to see the restored weights.)"""
     import os
-    ref, _ = make(engine, n=256, capacity=64, minibatch=400, opt_steps=12)
-    dqn, _ = make(engine, n=256, capacity=64, minibatch=400, opt_steps=12)
+    ref, _ = make(engine, n=256, capacity=64, minibatch=400, opt_steps=12, td=td)
+    dqn, _ = make(engine, n=256, capacity=64, minibatch=400, opt_steps=12, td=td)
     ref.collect(40)
     dqn.collect(40)
     before = dqn.qnet.get_params()
@@ -266,6 +270,32 @@ def test_update_builds_all_minibatches_at_once(engine, limit):
     obs_o, act_o, tgt_o = osim.minibatch(lanes, starts, lens)
     assert np.array_equal(dqn.minibatch_read(ra.MB_OBS).T, obs_o)
     assert np.array_equal(dqn.minibatch_read(ra.MB_TARGET), tgt_o)
+
+
+def test_td_update_leaves_its_last_minibatch_readable(engine):
+    """An all-at-once one-step-TD update forms its targets inside the gradient launches (the workspace holds rewards), so
+    its last minibatch is built once more afterwards, with the targets of the parameters the update ends on: what is
+    readable then is bit-identical to the oracle's minibatch at those parameters (the bars of
+    test_sampling_and_targets_bit_exact)."""
+    dqn, osim = make(engine, n=64, capacity=64, minibatch=600, td=True, opt_steps=3)
+    dqn.collect(40)
+    osim.collect(40, 0.3)
+    p0 = dqn.qnet.get_params()
+    st = dqn.update()
+    for _ in range(2):
+        osim.sample()
+    lanes, starts, lens, ns = osim.sample()
+    assert st.opt_steps == 3 and st.last_minibatch_steps == ns and st.last_minibatch_episodes == len(lanes)
+    assert dqn.agent_rng_pos() == osim.agent_pos()
+    osim.qparams[:] = dqn.qnet.get_params()
+    assert not np.array_equal(osim.qparams, p0)
+    obs_o, act_o, tgt_o = osim.minibatch(lanes, starts, lens)
+    assert np.array_equal(dqn.minibatch_read(ra.MB_EP_LEN), lens)
+    assert np.array_equal(dqn.minibatch_read(ra.MB_OBS).T, obs_o)
+    assert np.array_equal(dqn.minibatch_read(ra.MB_ACTION), act_o.astype(np.uint8))
+    assert np.array_equal(dqn.minibatch_read(ra.MB_TARGET), tgt_o)
+    osim.qparams[:] = p0  # (the targets are those of the final parameters, not of the ones the update began on)
+    assert not np.array_equal(osim.minibatch(lanes, starts, lens)[2], tgt_o)
 
 
 def test_cartpole_dqn_learns_something(engine):
