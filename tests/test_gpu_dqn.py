@@ -214,7 +214,9 @@ def test_sampling_and_targets_bit_exact(engine, td):
         assert np.array_equal(dqn.minibatch_read(ra.MB_TARGET), tgt_o)
 
 
-@pytest.mark.parametrize("hidden,limit", [(128, ra.LIMIT_VISIBLE), (64, ra.LIMIT_VISIBLE), (128, ra.LIMIT_NONE)])
+# (100 and 37 units: four and five units past the last block of 16; tests/test_gpu_narrow_mlp.py has their collection)
+@pytest.mark.parametrize("hidden,limit", [(128, ra.LIMIT_VISIBLE), (64, ra.LIMIT_VISIBLE), (128, ra.LIMIT_NONE),
+                                          (100, ra.LIMIT_VISIBLE), (37, ra.LIMIT_NONE)])
 def test_minibatch_gradient(engine, variant, hidden, limit):
     dqn, osim = make(engine, n=256, hidden=hidden, capacity=96, minibatch=6000, limit=limit, td=True)
     dqn.collect(60)
