@@ -8,6 +8,7 @@
 #include <mutex>
 
 #include "abi_internal.hpp"
+#include "env_lanes.hpp"
 
 thread_local std::string g_last_error_no_engine;
 
@@ -818,12 +819,7 @@ __global__ void k_debug_stream_words(AgentKey key, uint64_t stream, uint64_t fir
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_words) return;
   const uint64_t w = first_word + i;
-  uint32_t words[16];
-  rl_chacha_block(key.w, w >> 4, stream, 4, words);
-  uint32_t v = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) v = (uint32_t)(w & 15) == (uint32_t)k ? words[k] : v;
-  out[i] = v;
+  out[i] = stream_word(key.w, stream, w);
 }
 
 int32_t rl_debug_stream_words(rl_engine *engine, uint64_t seed, uint64_t stream, uint64_t first_word, uint32_t n_words,

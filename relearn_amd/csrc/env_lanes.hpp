@@ -1,0 +1,407 @@
+// env_lanes.hpp — one env per lane, device code only: the lane state of every env kind, the `Env` policy structs the
+// kernels are written over, the one statement of "step a lane and record it" (lane_step), the sinks a record goes to,
+// and word `w` of a lane's ChaCha stream (stream_word, LaneActorRng).  DESIGN.md §25 lists who calls what.
+//
+// Adding an env to a kernel is one ops struct here and one instantiation there.  An ops struct gives
+//   State                              the lane's registers
+//   load / store (st, i, s)            the lane's words of the struct-of-arrays state in HBM
+//   features<D>(c, s, f)               the observation's features
+//   step(c, s, a, glane, word, reward) Environment::step + the step-limit tail -> RL_SUCC_*; `word` is the global step
+//                                      (an env that draws in its step reads that word of the lane's env stream)
+//   reset(c, s, glane)                 Environment::initial_state from the lane's env stream
+// Arithmetic contract: device_fns.hpp.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/rl_chacha.h"
+#include "../../include/rl_detmath.h"
+#include "engine.hpp"
+
+// ---------------------------------------------------------------- word `w` of a lane's ChaCha stream
+// uncached: the block is recomputed on every call (kernels that take one word per launch or per step of a tile)
+__device__ __forceinline__ uint32_t stream_word(const uint32_t *key, uint64_t stream, uint64_t word) {
+  uint32_t w[16];
+  rl_chacha_block(key, word >> 4, stream, 4, w);
+  uint32_t v = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k)
+    if (k == (int)(word & 15)) v = w[k];
+  return v;
+}
+
+// cached: sequential per-lane generator, ChaCha8(key), stream = global lane id, next word `pos` (the `rng_actor: Prng` of
+// Steps, src/simulation/steps.rs:15-28; a fused rollout starts it at t_global, the DQN collection keeps it in HBM between
+// launches).  The current 16-word block is parked in a lane-private LDS column (no bank conflicts: threads are consecutive
+// in the fastest dimension) and regenerated every 16 words.
+template <int BLOCK>
+struct LaneActorRng {
+  uint32_t *col;  // &lds[threadIdx.x], stride BLOCK
+  const uint32_t *key;
+  uint64_t lane, pos, cur_block;
+  // the column holds the block of word `pos`
+  __device__ void fill() {
+    const uint64_t blk = pos >> 4;
+    if (blk != cur_block) {
+      uint32_t w[16];
+      rl_chacha_block(key, blk, lane, 4, w);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) col[k * BLOCK] = w[k];
+      cur_block = blk;
+    }
+  }
+  // word `pos` after fill() (a kernel that fills before a barrier and draws after it)
+  __device__ uint32_t take() {
+    const uint32_t v = col[(uint32_t)(pos & 15) * BLOCK];
+    pos += 1;
+    return v;
+  }
+  __device__ uint32_t next_u32() {
+    fill();
+    return take();
+  }
+  // BlockRng::next_u64: two consecutive words, low first
+  __device__ uint64_t next_u64() {
+    const uint64_t lo = next_u32();
+    const uint64_t hi = next_u32();
+    return (hi << 32) | lo;
+  }
+};
+
+// ---------------------------------------------------------------- CartPole physics
+// InternalPhysicalConstants::{next_state, angular_acceleration, normal_force}
+// (reference src/envs/cartpole.rs:306-446).  f64 throughout, operation order preserved.
+__device__ __forceinline__ double cp_angular_acceleration(const CartPoleDev &c, double thdot, double applied_force,
+                                                          double signed_cart_friction, double w2, double sin_a,
+                                                          double cos_a) {
+  double alpha =
+      (-applied_force - c.mass_length_pole * w2 * (sin_a + signed_cart_friction * cos_a)) * c.inv_total_mass;
+  double beta = c.friction_pole * thdot / c.mass_length_pole;
+  double numerator = c.gravity * sin_a + cos_a * (alpha + c.gravity * signed_cart_friction) - beta;
+  double denominator =
+      c.length_half_pole * (4.0 / 3.0 - c.mass_pole * cos_a * c.inv_total_mass * (cos_a - signed_cart_friction));
+  return numerator / denominator;
+}
+
+__device__ __forceinline__ double cp_normal_force(const CartPoleDev &c, double acc, double w2, double sin_a,
+                                                  double cos_a) {
+  return c.total_weight - c.mass_length_pole * (acc * sin_a + w2 * cos_a);
+}
+
+struct LaneState {
+  double x, xdot, th, thdot;
+  uint32_t nv_pos;
+  uint32_t steps_remaining;
+  uint32_t reset_count;
+};
+
+// CartPole::step (cartpole.rs:128-154) + Wrapped<_, StepLimit>::step tail (wrappers/step_limit.rs:216-222).
+// Returns the successor code; on Continue/Interrupt `s` holds the next state.
+__device__ __forceinline__ int cp_step(const CartPoleDev &c, LaneState &s, int action) {
+  double applied_force = action == 0 ? -c.action_force : c.action_force;
+  double signed_cart_friction = s.nv_pos ? c.friction_cart : -c.friction_cart;
+  double sin_a, cos_a;
+  rl_sincos(s.th, &sin_a, &cos_a);
+  double w2 = s.thdot * s.thdot;
+  double acc = cp_angular_acceleration(c, s.thdot, applied_force, signed_cart_friction, w2, sin_a, cos_a);
+  double nf = cp_normal_force(c, acc, w2, sin_a, cos_a);
+  uint32_t nv_pos = (rl_f64_bits(nf * s.xdot) >> 63) ? 0u : 1u;  // is_sign_positive
+  if (nv_pos != s.nv_pos) {
+    signed_cart_friction = -signed_cart_friction;
+    acc = cp_angular_acceleration(c, s.thdot, applied_force, signed_cart_friction, w2, sin_a, cos_a);
+    nf = cp_normal_force(c, acc, w2, sin_a, cos_a);
+  }
+  double force_pole = c.mass_length_pole * (w2 * sin_a + acc * cos_a);
+  double force_friction = -signed_cart_friction * nf;
+  double net_force = applied_force + force_pole + force_friction;
+  double cart_acc = net_force * c.inv_total_mass;
+  double xdot = s.xdot + c.time_step * cart_acc;
+  double x = s.x + c.time_step * xdot;
+  double thdot = s.thdot + c.time_step * acc;
+  double th = s.th + c.time_step * s.thdot;
+  bool terminal = __builtin_fabs(x) > c.max_pos || __builtin_fabs(th) > c.max_angle;
+  if (terminal) return RL_SUCC_TERMINATE;
+  s.x = x;
+  s.xdot = xdot;
+  s.th = th;
+  s.thdot = thdot;
+  s.nv_pos = nv_pos;
+  if (c.limit_kind != RL_LIMIT_NONE) {
+    s.steps_remaining -= 1;
+    if (s.steps_remaining == 0) return RL_SUCC_INTERRUPT;
+  }
+  return RL_SUCC_CONTINUE;
+}
+
+// features_out of StepLimitObsSpace<CartPolePhysicalStateSpace> (spaces/interval.rs:108-116,
+// wrappers/step_limit.rs:127-140,194-200): each field `as f32`, `remaining` last.
+template <int D>
+__device__ __forceinline__ void cp_features(const CartPoleDev &c, const LaneState &s, float (&f)[D]) {
+  f[0] = (float)s.x;
+  f[1] = (float)s.xdot;
+  f[2] = (float)s.th;
+  f[3] = (float)s.thdot;
+  if (D == 5) f[4] = (float)((double)s.steps_remaining / (double)c.max_steps);
+}
+
+// CartPole::initial_state (cartpole.rs:103-115) from the lane's env stream: reset k reads words [8k, 8k+8).
+// Of the lane it reads `reset_count` alone and writes every field.
+__device__ __forceinline__ void cp_reset(const CartPoleDev &c, LaneState &s, uint64_t global_lane) {
+  uint32_t w[16];
+  uint32_t k = s.reset_count;
+  rl_chacha_block(c.key_env, (uint64_t)(k >> 1), global_lane, 4, w);
+  // the upper or the lower half of the block by a bit select per word (v_bfi_b32): an index that depends on the lane
+  // would put the block into scratch memory
+  const uint32_t hi = 0u - (k & 1u);
+  uint32_t v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = (w[8 + i] & hi) | (w[i] & ~hi);
+  s.x = rl_uniform_f64_from_u64(((uint64_t)v[1] << 32) | v[0], c.init_low, c.init_scale);
+  s.xdot = rl_uniform_f64_from_u64(((uint64_t)v[3] << 32) | v[2], c.init_low, c.init_scale);
+  s.th = rl_uniform_f64_from_u64(((uint64_t)v[5] << 32) | v[4], c.init_low, c.init_scale);
+  s.thdot = rl_uniform_f64_from_u64(((uint64_t)v[7] << 32) | v[6], c.init_low, c.init_scale);
+  s.nv_pos = 1;
+  s.steps_remaining = c.max_steps;
+  s.reset_count = k + 1;
+}
+
+__device__ __forceinline__ void lane_load(const EnvStateDev &st, uint32_t i, LaneState &s) {
+  s.x = st.x[i];
+  s.xdot = st.xdot[i];
+  s.th = st.th[i];
+  s.thdot = st.thdot[i];
+  s.nv_pos = st.nv_pos[i];
+  s.steps_remaining = st.steps_remaining[i];
+  s.reset_count = st.reset_count[i];
+}
+
+__device__ __forceinline__ void lane_store(const EnvStateDev &st, uint32_t i, const LaneState &s) {
+  st.x[i] = s.x;
+  st.xdot[i] = s.xdot;
+  st.th[i] = s.th;
+  st.thdot[i] = s.thdot;
+  st.nv_pos[i] = (uint8_t)s.nv_pos;
+  st.steps_remaining[i] = s.steps_remaining;
+  st.reset_count[i] = s.reset_count;
+}
+
+// ---------------------------------------------------------------- lanes of the IndexSpace-observation envs
+// Chain (chain.rs), MemoryGame (memory.rs) and the deterministic bandit (bandits.rs) share the lane code: `c.mem_actions`
+// == 0 selects Chain, `c.bandit` the bandit (launch-uniform branches).  MemoryGame keeps (current_state, initial_state)
+// and the word position of the lane's env stream: its only random draw is `rng.gen_range(0..num_actions)` in
+// initial_state, taken SEQUENTIALLY from the lane's stream like one worker's env Prng in the reference (a rejection
+// loop, so the number of words per reset is not fixed).
+struct ChainLane {
+  uint32_t state, steps_remaining, reset_count;
+  uint32_t initial;   // MemoryGame: the state the episode started in
+  uint64_t env_pos;   // MemoryGame: next unread word of the lane's env stream (always even: u64 draws only)
+};
+
+__device__ __forceinline__ void chain_load(const EnvStateDev &st, uint32_t i, ChainLane &s) {
+  s.state = (uint32_t)st.x[i];
+  s.initial = (uint32_t)st.xdot[i];
+  s.env_pos = (uint64_t)st.th[i];
+  s.steps_remaining = st.steps_remaining[i];
+  s.reset_count = st.reset_count[i];
+}
+
+__device__ __forceinline__ void chain_store(const EnvStateDev &st, uint32_t i, const ChainLane &s) {
+  st.x[i] = (double)s.state;
+  st.xdot[i] = (double)s.initial;
+  st.th[i] = (double)s.env_pos;  // exact below 2^53 words
+  st.steps_remaining[i] = s.steps_remaining;
+  st.reset_count[i] = s.reset_count;
+}
+
+// features of StepLimit-wrapped IndexSpace observations: one-hot (spaces/index.rs:104-116) [+ remaining]
+template <int D>
+__device__ __forceinline__ void chain_features(const CartPoleDev &c, const ChainLane &s, float (&f)[D]) {
+#pragma unroll
+  for (int d = 0; d < D; ++d) f[d] = (uint32_t)d == s.state ? 1.0f : 0.0f;
+  if (D == 6) f[5] = (float)((double)s.steps_remaining / (double)c.max_steps);
+}
+
+// the same for any number of states (MemoryGame::new(num_actions, history_len): D = num_actions + history_len [+ 1]):
+// the remaining-steps feature follows the one-hot.  The standalone env kernels use it; the fused rollouts are built for
+// five states and keep chain_features.
+template <int D>
+__device__ __forceinline__ void index_features(const CartPoleDev &c, const ChainLane &s, float (&f)[D]) {
+#pragma unroll
+  for (int d = 0; d < D; ++d) f[d] = (uint32_t)d == s.state ? 1.0f : 0.0f;
+  if (c.limit_kind == RL_LIMIT_VISIBLE) f[D - 1] = (float)((double)s.steps_remaining / (double)c.max_steps);
+}
+
+// rand 0.8.5 `gen_range(0..range)` for u64/usize (UniformInt::sample_single): widening multiply, accept when the low
+// half is inside the zone `(range << leading_zeros(range)) - 1`; every attempt reads one u64 = stream words
+// (pos, pos + 1), low word first.  The loop ends with probability 1; 64 attempts bound it (each fails w.p. <= 1/2).
+// (the block is the purpose here: both words of an attempt come from one)
+__device__ __forceinline__ uint32_t lane_gen_range(const uint32_t *key, uint64_t glane, uint64_t &pos, uint64_t range) {
+  const uint64_t zone = (range << __clzll((long long)range)) - 1;
+  uint64_t hi = 0;
+  for (int attempt = 0; attempt < 64; ++attempt) {
+    uint32_t w[16];
+    rl_chacha_block(key, pos >> 4, glane, 4, w);
+    uint32_t lo32 = 0, hi32 = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k += 2)
+      if (k == (int)(pos & 15)) {
+        lo32 = w[k];
+        hi32 = w[k + 1];
+      }
+    pos += 2;
+    const uint64_t v = ((uint64_t)hi32 << 32) | lo32;
+    hi = __umul64hi(v, range);
+    if (v * range <= zone) break;
+  }
+  return (uint32_t)hi;
+}
+
+__device__ __forceinline__ void chain_reset(const CartPoleDev &c, ChainLane &s, uint64_t glane) {
+  if (c.mem_actions) {  // MemoryGame::initial_state (memory.rs:87-90)
+    s.state = lane_gen_range(c.key_env, glane, s.env_pos, c.mem_actions);
+    s.initial = s.state;
+  } else {
+    s.state = 0;  // Chain::initial_state (chain.rs:75-77), no random draw
+  }
+  s.steps_remaining = c.max_steps;
+  s.reset_count += 1;
+}
+
+// Chain::step (chain.rs:83-105) / MemoryGame::step (memory.rs:96-114) + the step-limit tail; `word` is the lane's
+// env-stream word for this global step (Chain's slip draw)
+__device__ __forceinline__ int chain_step(const CartPoleDev &c, ChainLane &s, int action, uint32_t word,
+                                          float &reward) {
+  if (c.bandit) {  // Bandit::step (bandits.rs:66-77): Deterministic::sample draws nothing
+    reward = c.bandit_r[action & 7];
+    return RL_SUCC_TERMINATE;
+  }
+  if (c.mem_actions) {
+    if (s.state == c.chain_size - 1) {  // the last of num_actions + history_len states: the answer step
+      reward = (uint32_t)action == s.initial ? 1.0f : -1.0f;
+      return RL_SUCC_TERMINATE;  // passes through the step limit untouched (step_limit.rs:216-222)
+    }
+    s.state = s.state < c.mem_actions ? c.mem_actions : s.state + 1;
+    reward = 0.0f;
+  } else {
+    if (rl_u32_to_unit_f32(word) < 0.2f) action = 1 - action;  // Move::invert
+    if (action == 0) {  // Move::Left
+      s.state = 0;
+      reward = 2.0f;
+    } else if (s.state == c.chain_size - 1) {
+      reward = 10.0f;
+    } else {
+      s.state += 1;
+      reward = 0.0f;
+    }
+  }
+  if (c.limit_kind != RL_LIMIT_NONE) {
+    s.steps_remaining -= 1;
+    if (s.steps_remaining == 0) return RL_SUCC_INTERRUPT;
+  }
+  return RL_SUCC_CONTINUE;
+}
+
+// ---------------------------------------------------------------- the env side of a kernel, by env kind
+struct CartPoleOps {
+  using State = LaneState;
+  static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) { lane_load(st, i, s); }
+  static __device__ __forceinline__ void store(const EnvStateDev &st, uint32_t i, const State &s) { lane_store(st, i, s); }
+  template <int D>
+  static __device__ __forceinline__ void features(const CartPoleDev &c, const State &s, float (&f)[D]) {
+    cp_features<D>(c, s, f);
+  }
+  static __device__ __forceinline__ int step(const CartPoleDev &c, State &s, int a, uint64_t, uint64_t, float &reward) {
+    reward = 1.0f;  // Reward(1.0) as f32: CartPole::step (cartpole.rs:140)
+    return cp_step(c, s, a);
+  }
+  static __device__ __forceinline__ void reset(const CartPoleDev &c, State &s, uint64_t glane) { cp_reset(c, s, glane); }
+};
+
+// index envs of any state count (the standalone env kernels)
+struct IndexOps {
+  using State = ChainLane;
+  static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) { chain_load(st, i, s); }
+  static __device__ __forceinline__ void store(const EnvStateDev &st, uint32_t i, const State &s) { chain_store(st, i, s); }
+  template <int D>
+  static __device__ __forceinline__ void features(const CartPoleDev &c, const State &s, float (&f)[D]) {
+    index_features<D>(c, s, f);
+  }
+  // Environment::step; the slip draw of global step `word` is word `word` of the lane's env stream
+  static __device__ __forceinline__ int step(const CartPoleDev &c, State &s, int a, uint64_t glane, uint64_t word,
+                                             float &reward) {
+    return chain_step(c, s, a, stream_word(c.key_env, glane, word), reward);
+  }
+  static __device__ __forceinline__ void reset(const CartPoleDev &c, State &s, uint64_t glane) { chain_reset(c, s, glane); }
+};
+
+// ... of five states (the fused rollouts): the features alone differ
+struct ChainOps : IndexOps {
+  template <int D>
+  static __device__ __forceinline__ void features(const CartPoleDev &c, const State &s, float (&f)[D]) {
+    chain_features<D>(c, s, f);
+  }
+};
+
+// ---------------------------------------------------------------- one step of a lane, recorded
+// Environment::step, the step's record, the successor observation of a cut episode, the auto-reset: the rule every
+// stepping kernel follows, in this order.  `sink` is the kernel's part — where the record goes:
+//   record(action, reward, succ)   the step
+//   successor(f)                   the features of the state an Interrupt leaves behind, written BEFORE the reset
+// `f` is scratch: the feature registers of the kernel, which has no use for their content across the step; the caller
+// forms the features the next step starts from.  Returns `succ`.
+// (Three kernels write these lines out over the same `Env`: k_rollout_cartpole with TrajSink, and the two DQN collection
+// kernels, whose replay ring records a lane the horizon cuts as an Interrupt while the env carries its episode on and may
+// refuse a step — DESIGN.md §25 has the compiler's reasons.)
+template <class Env, int D, class Sink>
+__device__ __forceinline__ int lane_step(const CartPoleDev &c, typename Env::State &s, int action, uint64_t glane,
+                                         uint64_t word, Sink &sink, float (&f)[D]) {
+  float reward;
+  const int succ = Env::step(c, s, action, glane, word, reward);
+  sink.record(action, reward, succ);
+  if (succ == RL_SUCC_INTERRUPT) {
+    Env::template features<D>(c, s, f);
+    sink.successor(f);
+  }
+  if (succ != RL_SUCC_CONTINUE) Env::reset(c, s, glane);
+  return succ;
+}
+
+// slot `o` = t * n + lane of a trajectory's time-major planes; `on` false: a thread that follows a lane without storing
+// (a group's other threads, lanes past the end)
+struct TrajSink {
+  const TrajDev &tr;
+  size_t o;
+  bool on;
+  __device__ __forceinline__ void record(int action, float reward, int succ) const {
+    if (on) {
+      tr.action[o] = (uint8_t)action;
+      tr.reward[o] = reward;
+      tr.flag[o] = (uint8_t)succ;
+    }
+  }
+  template <int D>
+  __device__ __forceinline__ void successor(const float (&f)[D]) const {
+    if (on) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) tr.term_obs[(size_t)d * tr.T * tr.n + o] = f[d];
+    }
+  }
+};
+
+// the env's own step buffers ([n] per field): lane i.  The successor observation goes to its [D][n] buffer; the record is
+// held for the kernel, which writes it behind the next observation
+struct EnvBufSink {
+  float *__restrict__ term_obs;
+  uint32_t n, i;
+  float reward;
+  int succ;
+  __device__ __forceinline__ void record(int, float r, int sc) {
+    reward = r;
+    succ = sc;
+  }
+  template <int D>
+  __device__ __forceinline__ void successor(const float (&f)[D]) const {
+#pragma unroll
+    for (int d = 0; d < D; ++d) term_obs[(size_t)d * n + i] = f[d];
+  }
+};

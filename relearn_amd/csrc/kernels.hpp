@@ -8,10 +8,10 @@
 #include "engine.hpp"
 
 // kernels_rollout.hip
-void launch_env_reset(rl_env *env);
+void launch_env_reset(rl_env *env);  // the standalone env kernels: every env kind
 void launch_env_observe(rl_env *env, float *d_obs);
 void launch_env_step(rl_env *env);
-void launch_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj);
+void launch_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj);  // feed-forward policy on CartPole lanes
 void launch_values(rl_traj *traj, const rl_mlp *critic);
 void launch_gae(rl_traj *traj, const rl_mlp *critic, float gamma, float lambda);  // critic NULL: adv = rtg only
 // critic regression targets into traj->d.tgt: one-step TD from traj->d.values (critic != NULL) or reward-to-go (NULL)
@@ -137,10 +137,7 @@ void launch_dqn_build_minibatch(rl_engine *eng, const ReplayDev &rp, uint32_t n_
                                 float *d_obs, size_t out_plane, uint8_t *d_action, float *d_target, float gamma,
                                 int one_step_td, const rl_mlp *qnet);
 
-// kernels_seq.hip (recurrent configuration: Chain lanes, GRU -> ReLU -> MLP module; tiles of 32 lanes)
-void launch_chain_reset(rl_env *env);
-void launch_chain_observe(rl_env *env, float *d_obs);
-void launch_chain_step(rl_env *env);
+// kernels_seq.hip (recurrent configuration: GRU -> ReLU -> MLP module; tiles of 32 lanes)
 void launch_rollout_gru(rl_env *env, const rl_mlp *policy, rl_traj *traj);        // recurrent policy, either env kind
 void launch_rollout_chain_mlp(rl_env *env, const rl_mlp *policy, rl_traj *traj);  // feed-forward policy on Chain lanes
 // teacher-forced forward: d_out [A][T][n]; d_succ (may be NULL) [A][T][n]; d_act (may be NULL) activation record

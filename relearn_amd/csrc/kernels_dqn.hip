@@ -8,6 +8,7 @@
 
 #include "bf16_tile.hpp"
 #include "device_fns.hpp"
+#include "env_lanes.hpp"
 #include "kernels.hpp"
 #include "replay.hpp"
 
@@ -25,38 +26,39 @@ __device__ __forceinline__ void rec_store(ReplayRec *__restrict__ p, const Repla
   reinterpret_cast<uint4 *>(p)[1] = make_uint4(__float_as_uint(r.x[4]), __float_as_uint(r.reward), r.af, 0u);
 }
 
-// Sequential per-lane actor generator: ChaCha8(seed_actor), stream = global lane id, word position `pos` kept in
-// HBM between launches (it is the `rng_actor: Prng` of Steps, src/simulation/steps.rs:15-28).  The current
-// 16-word block is parked in a lane-private LDS column.
-template <int BLOCK>
-struct LaneActorRng {
-  uint32_t *col;  // &lds[threadIdx.x], stride BLOCK
-  const uint32_t *key;
-  uint64_t lane, pos, cur_block;
-  __device__ uint32_t next_u32() {
-    const uint64_t blk = pos >> 4;
-    if (blk != cur_block) {
-      uint32_t w[16];
-      rl_chacha_block(key, blk, lane, 4, w);
-#pragma unroll
-      for (int k = 0; k < 16; ++k) col[k * BLOCK] = w[k];
-      cur_block = blk;
-    }
-    const uint32_t v = col[(uint32_t)(pos & 15) * BLOCK];
-    pos += 1;
-    return v;
+// DqnActor::act (dqn.rs:360-379) from the lane's sequential actor stream:
+//   if rng.gen_bool(eps) { action_space.sample(rng) = gen_range(0..2) } else { argmax_a Q(obs)[a] }
+// The draws are here; the greedy branch is the kernel's (the first maximal index of its action values).
+template <class Rng>
+__device__ __forceinline__ bool dqn_explores(Rng &rng, uint64_t p_int, int always_explore) {
+  bool explore = always_explore != 0;
+  if (!explore) explore = rng.next_u64() < p_int;  // Bernoulli::sample: v < (p * 2^64) as u64
+  return explore;
+}
+template <class Rng>
+__device__ __forceinline__ int dqn_random_action(Rng &rng) {
+  // UniformInt::sample_single(0, 2): widening multiply by 2, zone = (2 << 62) - 1
+  for (;;) {
+    const uint64_t v = rng.next_u64();
+    const uint64_t lo = v << 1, hi = v >> 63;
+    if (lo <= 0x7fffffffffffffffull) return (int)hi;
   }
-  // BlockRng::next_u64: two consecutive words, low first
-  __device__ uint64_t next_u64() {
-    const uint64_t lo = next_u32();
-    const uint64_t hi = next_u32();
-    return (hi << 32) | lo;
+}
+
+// the lane's episode table; `writer` false: a thread that follows the lane (it reads the table, the lane's writer writes)
+struct LaneEpEnds {
+  uint32_t *base;
+  uint32_t N, lane;
+  bool writer;
+  __device__ uint32_t get(uint32_t k) const { return base[(size_t)k * N + lane]; }
+  __device__ void set(uint32_t k, uint32_t v) {
+    if (writer) base[(size_t)k * N + lane] = v;
   }
 };
 
-// T env-actor steps per lane with the DQN actor:
-//   if rng.gen_bool(eps) { action_space.sample(rng) = gen_range(0..2) } else { argmax_a Q(obs)[a] }
-// every step is appended to the lane's replay ring.
+// T env-actor steps per lane with the DQN actor (dqn_explores / dqn_random_action, else the greedy action); every step is
+// appended to the lane's replay ring.
+// The actor's generator (LaneActorRng, env_lanes.hpp) keeps its word position in HBM between launches.
 // G threads per lane (G consecutive lanes of a wave) share the greedy branch's Q-network forward, as in the fused TRPO
 // rollout (kernels_rollout.hip: a launch lasts T x the latency of one step, and most of a greedy step is the 128-unit
 // forward); everything else — draws, physics, ring bookkeeping — is repeated by every thread of the group, thread 0
@@ -67,11 +69,12 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, E
                                                                 uint64_t p_int, int always_explore,
                                                                 uint8_t *__restrict__ flags_out,
                                                                 uint32_t *__restrict__ range) {
+  using Env = CartPoleOps;
   __shared__ uint32_t words[16 * BLOCK];
   __shared__ __attribute__((aligned(16))) float pk[MLP_PK_FLOATS];  // the Q-network, one 8-float record per hidden unit
-  // the magnitude range of every observation that enters the store (steps and Interrupt successors), for the fused
-  // gradient kernel's range guard (bf16_tile.hpp): one fold per wave and launch into words that are never reset — the
-  // range of everything ever collected bounds every minibatch drawn from the store
+  // the collected observations' magnitude range, for the fused gradient kernel's range guard (bf16_tile.hpp): one fold
+  // per wave and launch into words that are never reset — the range of everything ever collected bounds every minibatch
+  // drawn from the store
   uint32_t r_lo = 0x7F7FFFFFu, r_hi = 0u;
   const uint32_t n = rp.N;
   mlp_pack_lds<D>(pk, qnet, H, threadIdx.x, BLOCK);
@@ -83,42 +86,27 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, E
   const uint32_t i = live ? i0 : n - 1;
   const bool writer = live && g == 0;
   const uint64_t lane = c.lane_offset + i;
-  LaneState s;
-  lane_load(st, i, s);
-  LaneRing ring{rp.head[i], rp.count[i], rp.ep_head[i], rp.ep_count[i], rp.total[i]};
-  struct GroupEpEnds {  // every thread of the group reads the lane's episode table, thread 0 writes it
-    uint32_t *base;
-    uint32_t N, lane;
-    bool writer;
-    __device__ uint32_t get(uint32_t k) const { return base[(size_t)k * N + lane]; }
-    __device__ void set(uint32_t k, uint32_t v) {
-      if (writer) base[(size_t)k * N + lane] = v;
-    }
-  } eps{rp.ep_end, n, i, writer};
+  Env::State s;
+  Env::load(st, i, s);
+  LaneRing ring = ring_load(rp, i);
+  LaneEpEnds eps{rp.ep_end, n, i, writer};
   LaneActorRng<BLOCK> rng{&words[threadIdx.x], c.key_actor, lane, rp.actor_pos[i], ~0ull};
   bool full = false;
   for (uint32_t t = 0; t < T; ++t) {
     float f[D];
-    cp_features<D>(c, s, f);
+    Env::features<D>(c, s, f);
     int a;
-    bool explore = always_explore != 0;
-    if (!explore) explore = rng.next_u64() < p_int;  // Bernoulli::sample: v < (p * 2^64) as u64
-    if (explore) {
-      // UniformInt::sample_single(0, 2): widening multiply by 2, zone = (2 << 62) - 1
-      for (;;) {
-        const uint64_t v = rng.next_u64();
-        const uint64_t lo = v << 1, hi = v >> 63;
-        if (lo <= 0x7fffffffffffffffull) {
-          a = (int)hi;
-          break;
-        }
-      }
+    if (dqn_explores(rng, p_int, always_explore)) {
+      a = dqn_random_action(rng);
     } else {
       float z[2];
       mlp_forward_group_lds<D, G>(pk, H, g, f, z);
       a = z[1] > z[0] ? 1 : 0;  // argmax: first maximal index
     }
-    int succ = cp_step(c, s, a);
+    // lane_step's rule (env_lanes.hpp) with the replay ring as its sink, written out: the ring may refuse the step, and
+    // closes a lane the horizon cuts in its own way (DESIGN.md §25 on why these lines are not a sink struct)
+    float reward;
+    const int succ = Env::step(c, s, a, lane, 0, reward);
     // the engine's horizon rule: a lane still mid-episode at the end of the launch closes its
     // episode as Interrupt(successor observation) and carries the env state on into the next collection
     const bool horizon_cut = succ == RL_SUCC_CONTINUE && t + 1 == T;
@@ -135,12 +123,12 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, E
       ReplayRec rec;
 #pragma unroll
       for (int d = 0; d < 5; ++d) rec.x[d] = d < D ? f[d < D ? d : 0] : 0.0f;
-      rec.reward = 1.0f;  // CartPole::step reward (cartpole.rs:140)
+      rec.reward = reward;
       rec.af = (uint32_t)a | (uint32_t)succ_rec << 8;
       rec_store(rp.rec + o, rec);
     }
     if (succ_rec == RL_SUCC_INTERRUPT) {
-      cp_features<D>(c, s, f);
+      Env::features<D>(c, s, f);
 #pragma unroll
       for (int d = 0; d < D; ++d) bt::range_accumulate(f[d], r_lo, r_hi);
       if (writer) {
@@ -149,64 +137,45 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, E
       }
     }
     if (writer) flags_out[(size_t)t * n + i] = (uint8_t)succ_rec;
-    if (succ != RL_SUCC_CONTINUE) cp_reset(c, s, lane);
+    if (succ != RL_SUCC_CONTINUE) Env::reset(c, s, lane);
   }
   if (range != nullptr) bt::range_fold_wave(range, blockIdx.x, r_lo, r_hi);  // (every thread of the wave is here)
   if (!writer) return;
   if (full) *rp.error = 1;
-  rp.head[i] = ring.head;
-  rp.count[i] = ring.count;
-  rp.ep_head[i] = ring.ep_head;
-  rp.ep_count[i] = ring.ep_count;
-  rp.total[i] = ring.total;
+  ring_store(rp, i, ring);
   rp.actor_pos[i] = rng.pos;
-  lane_store(st, i, s);
+  Env::store(st, i, s);
 }
 
 // ---------------------------------------------------------------- collection with an action-value module of any shape
 // DqnConfig<MB> is generic over the module (src/torch/agents/dqn.rs:26-39).  A module the fused collection kernel is not
 // built for (rl_mlp::general: several hidden layers, other activations, a wider layer) collects one launch sequence per
 // step — observe, the module's layer kernels over all lanes (kernels_general.hip), then this kernel: DqnActor::act
-// (dqn.rs:360-379) from the lane's actor stream with the greedy branch reading the module's outputs, the env step, the
-// ring write — with the fused kernel's stream discipline, ring bookkeeping and horizon rule (above), one thread per lane.
+// from the lane's actor stream with the greedy branch reading the module's outputs, the env step, the ring write — with
+// the fused kernel's stream discipline, ring bookkeeping and horizon rule (above), one thread per lane.
 template <int D, int BLOCK>
 __global__ void __launch_bounds__(BLOCK) k_dqn_lane_step(CartPoleDev c, EnvStateDev st, ReplayDev rp,
                                                          const float *__restrict__ q_values /* [2][n] */, uint64_t p_int,
                                                          int always_explore, int last_step,
                                                          uint8_t *__restrict__ flags_row) {
+  using Env = CartPoleOps;
   __shared__ uint32_t words[16 * BLOCK];
   const uint32_t n = rp.N;
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   const uint64_t lane = c.lane_offset + i;
-  LaneState s;
-  lane_load(st, i, s);
-  LaneRing ring{rp.head[i], rp.count[i], rp.ep_head[i], rp.ep_count[i], rp.total[i]};
-  struct EpEnds {
-    uint32_t *base;
-    uint32_t N, lane;
-    __device__ uint32_t get(uint32_t k) const { return base[(size_t)k * N + lane]; }
-    __device__ void set(uint32_t k, uint32_t v) { base[(size_t)k * N + lane] = v; }
-  } eps{rp.ep_end, n, i};
+  Env::State s;
+  Env::load(st, i, s);
+  LaneRing ring = ring_load(rp, i);
+  LaneEpEnds eps{rp.ep_end, n, i, true};
   LaneActorRng<BLOCK> rng{&words[threadIdx.x], c.key_actor, lane, rp.actor_pos[i], ~0ull};
   float f[D];
-  cp_features<D>(c, s, f);
+  Env::features<D>(c, s, f);
   int a;
-  bool explore = always_explore != 0;
-  if (!explore) explore = rng.next_u64() < p_int;  // Bernoulli::sample: v < (p * 2^64) as u64
-  if (explore) {
-    for (;;) {  // UniformInt::sample_single(0, 2)
-      const uint64_t v = rng.next_u64();
-      const uint64_t lo = v << 1, hi = v >> 63;
-      if (lo <= 0x7fffffffffffffffull) {
-        a = (int)hi;
-        break;
-      }
-    }
-  } else {
-    a = q_values[n + i] > q_values[i] ? 1 : 0;  // argmax: first maximal index
-  }
-  int succ = cp_step(c, s, a);
+  if (dqn_explores(rng, p_int, always_explore)) a = dqn_random_action(rng);
+  else a = q_values[n + i] > q_values[i] ? 1 : 0;  // argmax: first maximal index
+  float reward;  // (the step, its record and the horizon rule as in the fused kernel)
+  const int succ = Env::step(c, s, a, lane, 0, reward);
   const bool horizon_cut = succ == RL_SUCC_CONTINUE && last_step != 0;
   const int succ_rec = horizon_cut ? RL_SUCC_INTERRUPT : succ;
   const uint32_t slot_abs = ring_write_step(ring, rp.C, rp.E, eps, succ_rec != RL_SUCC_CONTINUE);
@@ -218,23 +187,19 @@ __global__ void __launch_bounds__(BLOCK) k_dqn_lane_step(CartPoleDev c, EnvState
   ReplayRec rec;
 #pragma unroll
   for (int d = 0; d < 5; ++d) rec.x[d] = d < D ? f[d < D ? d : 0] : 0.0f;
-  rec.reward = 1.0f;
+  rec.reward = reward;
   rec.af = (uint32_t)a | (uint32_t)succ_rec << 8;
   rec_store(rp.rec + o, rec);
   if (succ_rec == RL_SUCC_INTERRUPT) {
-    cp_features<D>(c, s, f);
+    Env::features<D>(c, s, f);
 #pragma unroll
     for (int d = 0; d < D; ++d) rp.next[o].x[d] = f[d];
   }
   flags_row[i] = (uint8_t)succ_rec;
-  if (succ != RL_SUCC_CONTINUE) cp_reset(c, s, lane);
-  rp.head[i] = ring.head;
-  rp.count[i] = ring.count;
-  rp.ep_head[i] = ring.ep_head;
-  rp.ep_count[i] = ring.ep_count;
-  rp.total[i] = ring.total;
+  if (succ != RL_SUCC_CONTINUE) Env::reset(c, s, lane);
+  ring_store(rp, i, ring);
   rp.actor_pos[i] = rng.pos;
-  lane_store(st, i, s);
+  Env::store(st, i, s);
 }
 
 // one-step TD targets from the module's outputs at the successor observations (the gather left rewards where the

@@ -22,6 +22,7 @@
 #include <set>
 
 #include "abi_internal.hpp"
+#include "env_lanes.hpp"
 #include "policy_terms.hpp"
 
 namespace {
@@ -341,13 +342,7 @@ __global__ void __launch_bounds__(256) k_gen_sample_actions(CartPoleDev c, const
                                                             uint64_t word, uint8_t *__restrict__ actions) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  uint32_t w[16];
-  rl_chacha_block(c.key_actor, word >> 4, c.lane_offset + i, 4, w);
-  uint32_t v = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k)
-    if (k == (int)(word & 15)) v = w[k];
-  const float u = rl_u32_to_unit_f32(v);
+  const float u = rl_u32_to_unit_f32(stream_word(c.key_actor, c.lane_offset + i, word));
   float zz[A], lp[A];
 #pragma unroll
   for (int a = 0; a < A; ++a) zz[a] = z[(size_t)a * n + i];
@@ -386,38 +381,25 @@ __global__ void __launch_bounds__(256) k_gen_step_cartpole(CartPoleDev c, EnvSta
                                                            float *__restrict__ obs_next) {
   const uint32_t n = tr.n, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  uint32_t w[16];
-  rl_chacha_block(c.key_actor, word >> 4, c.lane_offset + i, 4, w);
-  uint32_t v = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k)
-    if (k == (int)(word & 15)) v = w[k];
-  const float u = rl_u32_to_unit_f32(v);
+  const float u = rl_u32_to_unit_f32(stream_word(c.key_actor, c.lane_offset + i, word));
   const float zz[2] = {z[i], z[n + i]};
   float lp[2];
   log_softmax_lane<2>(zz, lp);
   const int a = categorical_sample_lane<2>(lp, u);
-  LaneState s;
-  lane_load(st, i, s);
-  const int succ = cp_step(c, s, a);
-  const size_t o = (size_t)t * n + i, plane = (size_t)(tr.T + 1) * n;
-  tr.action[o] = (uint8_t)a;
-  tr.reward[o] = 1.0f;  // Reward(1.0) as f32
-  tr.flag[o] = (uint8_t)succ;
+  using Env = CartPoleOps;
+  Env::State s;
+  Env::load(st, i, s);
+  const size_t plane = (size_t)(tr.T + 1) * n;
+  const TrajSink sink{tr, (size_t)t * n + i, true};
   float f[D];
-  if (succ == RL_SUCC_INTERRUPT) {
-    cp_features<D>(c, s, f);
-#pragma unroll
-    for (int d = 0; d < D; ++d) tr.term_obs[(size_t)d * tr.T * n + o] = f[d];
-  }
-  if (succ != RL_SUCC_CONTINUE) cp_reset(c, s, c.lane_offset + i);
-  cp_features<D>(c, s, f);
+  lane_step<Env>(c, s, a, c.lane_offset + i, word, sink, f);
+  Env::features<D>(c, s, f);
 #pragma unroll
   for (int d = 0; d < D; ++d) {
     obs_next[(size_t)d * n + i] = f[d];
     tr.obs[d * plane + (size_t)(t + 1) * n + i] = f[d];
   }
-  lane_store(st, i, s);
+  Env::store(st, i, s);
 }
 
 // d loss / d (pre-activation of the output layer) = d loss / d output * act'(output)   (output_activation != Identity)
@@ -521,7 +503,8 @@ constexpr int ROLL_WAVES = 16;
 template <int D>
 __global__ void __launch_bounds__(ROLL_WAVES * 64) k_gen_rollout_cartpole(CartPoleDev c, EnvStateDev st, TrajDev tr,
                                                                           ChainNet net, uint64_t t_global) {
-  extern __shared__ float chain_lds[];  // [2][wmax][GT], then the actor words [16][GT]
+  using Env = CartPoleOps;
+  extern __shared__ float chain_lds[];  // [2][wmax][GT], then the actor words [16][GT] (LaneActorRng's columns)
   const int s = threadIdx.x & (GT - 1);
   const int g = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const bool keeper = g == 0;
@@ -532,61 +515,42 @@ __global__ void __launch_bounds__(ROLL_WAVES * 64) k_gen_rollout_cartpole(CartPo
   const bool live = keeper && i < n;
   const uint32_t il = i < n ? i : n - 1;
   const uint64_t lane = c.lane_offset + il;
-  LaneState ls;
-  if (keeper) lane_load(st, il, ls);
+  Env::State ls;
+  if (keeper) Env::load(st, il, ls);
   const size_t plane = (size_t)(T + 1) * n;
-  uint64_t cur_block = ~0ull;
+  LaneActorRng<GT> rng{&actor_words[s], c.key_actor, lane, t_global, ~0ull};
   for (uint32_t t = 0; t < T; ++t) {
     float f[D];
     if (keeper) {
-      cp_features<D>(c, ls, f);
+      Env::features<D>(c, ls, f);
 #pragma unroll
       for (int d = 0; d < D; ++d) {
         if (live) tr.obs[d * plane + (size_t)t * n + il] = f[d];
         t0[d * GT + s] = f[d];
       }
-      const uint64_t blk = (t_global + t) >> 4;
-      if (blk != cur_block) {
-        uint32_t words[16];
-        rl_chacha_block(c.key_actor, blk, lane, 4, words);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) actor_words[k * GT + s] = words[k];
-        cur_block = blk;
-      }
+      rng.pos = t_global + t;
+      rng.fill();
     }
     __syncthreads();
     const float *z = chain_forward_tile(net, t0, t1, s, g, ROLL_WAVES);  // (ends with a barrier)
     if (keeper) {
-      const float u = rl_u32_to_unit_f32(actor_words[(uint32_t)((t_global + t) & 15) * GT + s]);
+      const float u = rl_u32_to_unit_f32(rng.take());
       const float zz[2] = {z[s], z[GT + s]};
       float lp[2];
       log_softmax_lane<2>(zz, lp);
       const int a = categorical_sample_lane<2>(lp, u);
-      const int succ = cp_step(c, ls, a);
-      const size_t o = (size_t)t * n + il;
-      if (live) {
-        tr.action[o] = (uint8_t)a;
-        tr.reward[o] = 1.0f;
-        tr.flag[o] = (uint8_t)succ;
-      }
-      if (succ == RL_SUCC_INTERRUPT) {
-        cp_features<D>(c, ls, f);
-        if (live) {
-#pragma unroll
-          for (int d = 0; d < D; ++d) tr.term_obs[(size_t)d * T * n + o] = f[d];
-        }
-      }
-      if (succ != RL_SUCC_CONTINUE) cp_reset(c, ls, lane);
+      const TrajSink sink{tr, (size_t)t * n + il, live};
+      lane_step<Env>(c, ls, a, lane, t_global + t, sink, f);
     }
     __syncthreads();  // the output tile is the next step's scratch
   }
   if (keeper) {
     float f[D];
-    cp_features<D>(c, ls, f);
+    Env::features<D>(c, ls, f);
     if (live) {
 #pragma unroll
       for (int d = 0; d < D; ++d) tr.obs[d * plane + (size_t)T * n + il] = f[d];
-      lane_store(st, il, ls);
+      Env::store(st, il, ls);
     }
   }
 }

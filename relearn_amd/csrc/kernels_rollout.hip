@@ -1,62 +1,63 @@
-// kernels_rollout.hip — env step, fused persistent rollout, value forward and GAE scan.
+// kernels_rollout.hip — the standalone env kernels of every env kind, the fused persistent rollout of a one-hidden-layer
+// feed-forward policy on CartPole lanes, value forward and GAE scan.  The lanes and the step rule: env_lanes.hpp.
 //
 // Layout: one env per lane, struct-of-arrays state in HBM, time-major trajectory planes so that every
 // global access of a wavefront is one contiguous 256-B (f32) / 64-B (u8) segment.
+#include <type_traits>
+
 #include "bf16_tile.hpp"
 #include "device_fns.hpp"
+#include "env_lanes.hpp"
 #include "kernels.hpp"
 
 // ---------------------------------------------------------------- reset / observe / standalone step
+// (the lane is loaded whole: an env's reset may read any of it — MemoryGame's stream position — and cp_reset, which reads
+// `reset_count` alone and overwrites every field, leaves the other loads dead)
+template <class Env>
 __global__ void k_env_reset(CartPoleDev c, EnvStateDev st, uint32_t n) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  LaneState s;
-  s.reset_count = st.reset_count[i];
-  cp_reset(c, s, c.lane_offset + i);
-  lane_store(st, i, s);
+  typename Env::State s;
+  Env::load(st, i, s);
+  Env::reset(c, s, c.lane_offset + i);
+  Env::store(st, i, s);
 }
 
-template <int D>
+template <class Env, int D>
 __global__ void k_env_observe(CartPoleDev c, EnvStateDev st, uint32_t n, float *__restrict__ obs) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  LaneState s;
-  lane_load(st, i, s);
+  typename Env::State s;
+  Env::load(st, i, s);
   float f[D];
-  cp_features<D>(c, s, f);
+  Env::template features<D>(c, s, f);
 #pragma unroll
   for (int d = 0; d < D; ++d) obs[(size_t)d * n + i] = f[d];
 }
 
-// Environment::step for every lane (reference src/envs/cartpole.rs:128-154 through the step-limit wrapper),
-// with auto-reset.  Algorithmic traffic per env-step: read state 32 B + sign 1 B + remaining 4 B
+// Environment::step for every lane (CartPole: reference src/envs/cartpole.rs:128-154 through the step-limit wrapper),
+// with auto-reset.  Algorithmic traffic per CartPole env-step: read state 32 B + sign 1 B + remaining 4 B
 // + action 1 B; write state 37 B + reward 4 B + flag 1 B + next-obs 4*D B  => 100 B at D = 5.
 // (FILLED: the same code under a second name for launches of >= 2^20 lanes, so that a kernel trace keeps the workload's
-// latency-bound launches and the chip-filling ones of bench.py's `roofline_env_step.filled` apart)
-template <int D, bool FILLED>
+// latency-bound launches and the chip-filling ones of bench.py's `roofline_env_step.filled` apart; CartPole only)
+template <class Env, int D, bool FILLED>
 __global__ void __launch_bounds__(256) k_env_step(CartPoleDev c, EnvStateDev st, uint32_t n,
                                                   const uint8_t *__restrict__ actions, float *__restrict__ reward,
                                                   uint8_t *__restrict__ flag, float *__restrict__ obs_next,
-                                                  float *__restrict__ term_obs) {
+                                                  float *__restrict__ term_obs, uint64_t t_global) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  LaneState s;
-  lane_load(st, i, s);
-  int a = actions[i];
-  int succ = cp_step(c, s, a);
+  typename Env::State s;
+  Env::load(st, i, s);
+  EnvBufSink sink{term_obs, n, i};
   float f[D];
-  if (succ == RL_SUCC_INTERRUPT) {
-    cp_features<D>(c, s, f);
-#pragma unroll
-    for (int d = 0; d < D; ++d) term_obs[(size_t)d * n + i] = f[d];
-  }
-  if (succ != RL_SUCC_CONTINUE) cp_reset(c, s, c.lane_offset + i);
-  cp_features<D>(c, s, f);
+  lane_step<Env>(c, s, actions[i], c.lane_offset + i, t_global, sink, f);
+  Env::template features<D>(c, s, f);
 #pragma unroll
   for (int d = 0; d < D; ++d) obs_next[(size_t)d * n + i] = f[d];
-  reward[i] = 1.0f;  // Reward(1.0) as f32
-  flag[i] = (uint8_t)succ;
-  lane_store(st, i, s);
+  reward[i] = sink.reward;
+  flag[i] = (uint8_t)sink.succ;
+  Env::store(st, i, s);
 }
 
 // ---------------------------------------------------------------- fused persistent rollout
@@ -64,8 +65,7 @@ __global__ void __launch_bounds__(256) k_env_step(CartPoleDev c, EnvStateDev st,
 // T env-actor steps per lane in one launch; lane state lives in registers for the whole horizon; the only
 // HBM traffic is the 26 B/step trajectory record (obs 20 + action 1 + reward 4 + flag 1) plus the sparse
 // interrupt successor observations.  The actor's uniform draw for global step t is word t of the lane's
-// ChaCha8 actor stream; a 16-word block is regenerated every 16 steps and parked in an LDS column that is
-// private to the thread (no bank conflicts: threads are consecutive in the fastest dimension).
+// ChaCha8 actor stream, through the cached generator (LaneActorRng, env_lanes.hpp).
 // A step is a chain of dependent work (features -> 128-unit MLP -> softmax -> sample -> f64 sincos + physics), so a
 // launch lasts T x the latency of one step whatever the lane count.  G threads per lane (G consecutive lanes of a wave)
 // share the MLP — each owns 16 / G of the output layer's sixteen partial chains (mlp_forward_group_lds) — and repeat the
@@ -75,6 +75,7 @@ template <int D, int BLOCK, int G>
 __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole(CartPoleDev c, EnvStateDev st, TrajDev tr,
                                                             const float *__restrict__ policy, int H,
                                                             uint64_t t_global) {
+  using Env = CartPoleOps;
   __shared__ uint32_t actor_words[16 * BLOCK];
   __shared__ __attribute__((aligned(16))) float pk[MLP_PK_FLOATS];  // the policy, one 8-float record per hidden unit
   const uint32_t n = tr.n, T = tr.T;
@@ -94,54 +95,41 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole(CartPoleDev c, EnvSt
   const uint32_t il = live ? i : n - 1;
   const bool writer = live && g == 0;
   const uint64_t lane = c.lane_offset + il;
-  LaneState s;
-  lane_load(st, il, s);
+  Env::State s;
+  Env::load(st, il, s);
   const size_t plane = (size_t)(T + 1) * n;
-  uint64_t cur_block = ~0ull;
+  LaneActorRng<BLOCK> rng{&actor_words[threadIdx.x], c.key_actor, lane, t_global, ~0ull};
   for (uint32_t t = 0; t < T; ++t) {
     float f[D];
-    cp_features<D>(c, s, f);
+    Env::features<D>(c, s, f);
     if (writer) {
 #pragma unroll
       for (int d = 0; d < D; ++d) tr.obs[d * plane + (size_t)t * n + il] = f[d];
     }
-    // actor draw
-    uint64_t w = t_global + t;
-    uint64_t blk = w >> 4;
-    if (blk != cur_block) {
-      uint32_t words[16];
-      rl_chacha_block(c.key_actor, blk, lane, 4, words);
-#pragma unroll
-      for (int k = 0; k < 16; ++k) actor_words[k * BLOCK + threadIdx.x] = words[k];
-      cur_block = blk;
-    }
-    float u = rl_u32_to_unit_f32(actor_words[(uint32_t)(w & 15) * BLOCK + threadIdx.x]);
+    rng.pos = t_global + t;  // actor draw
+    const float u = rl_u32_to_unit_f32(rng.next_u32());
     float z[2], lp[2];
     mlp_forward_group_lds<D, G>(pk, H, g, f, z);
     log_softmax_lane<2>(z, lp);
     int a = categorical_sample_lane<2>(lp, u);
-    int succ = cp_step(c, s, a);
-    size_t o = (size_t)t * n + il;
-    if (writer) {
-      tr.action[o] = (uint8_t)a;
-      tr.reward[o] = 1.0f;
-      tr.flag[o] = (uint8_t)succ;
-    }
+    const TrajSink sink{tr, (size_t)t * n + il, writer};
+    // lane_step's rule (env_lanes.hpp) written out: through the helper the compiler lays the successor code's branches out
+    // differently in this kernel
+    float reward;
+    const int succ = Env::step(c, s, a, lane, t_global + t, reward);
+    sink.record(a, reward, succ);
     if (succ == RL_SUCC_INTERRUPT) {
-      cp_features<D>(c, s, f);
-      if (writer) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) tr.term_obs[(size_t)d * T * n + o] = f[d];
-      }
+      Env::features<D>(c, s, f);
+      sink.successor(f);
     }
-    if (succ != RL_SUCC_CONTINUE) cp_reset(c, s, lane);
+    if (succ != RL_SUCC_CONTINUE) Env::reset(c, s, lane);
   }
   float f[D];
-  cp_features<D>(c, s, f);
+  Env::features<D>(c, s, f);
   if (writer) {
 #pragma unroll
     for (int d = 0; d < D; ++d) tr.obs[d * plane + (size_t)T * n + il] = f[d];
-    lane_store(st, il, s);
+    Env::store(st, il, s);
   }
 }
 
@@ -412,41 +400,64 @@ void launch_obs_range(rl_traj *traj) {
                      traj->d.range);
 }
 
+// The standalone env kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature
+// count as types.  CartPole lanes have 4 or 5 features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame:
+// num_actions + history_len [+ 1]) 4..8.
+template <int D>
+using FeatureCount = std::integral_constant<int, D>;
+template <class Go>
+static void env_dispatch(const rl_env *env, Go &&go) {
+  if (env->kind == RL_ENV_CARTPOLE) {
+    if (env->D == 5) go(CartPoleOps{}, FeatureCount<5>{});
+    else go(CartPoleOps{}, FeatureCount<4>{});
+    return;
+  }
+  switch (env->D) {
+    case 4: go(IndexOps{}, FeatureCount<4>{}); break;
+    case 5: go(IndexOps{}, FeatureCount<5>{}); break;
+    case 6: go(IndexOps{}, FeatureCount<6>{}); break;
+    case 7: go(IndexOps{}, FeatureCount<7>{}); break;
+    case 8: go(IndexOps{}, FeatureCount<8>{}); break;
+    default: throw RlError(RL_ERR_UNSUPPORTED, "index env lanes: 4..8 observation features");
+  }
+}
+
 void launch_env_reset(rl_env *env) {
-  if (env->kind != RL_ENV_CARTPOLE) return launch_chain_reset(env);
   ProfScope ps(env->eng, RL_K_SMALL);
   uint32_t n = (uint32_t)env->cfg.n_lanes;
-  hipLaunchKernelGGL(k_env_reset, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  if (env->kind == RL_ENV_CARTPOLE)
+    hipLaunchKernelGGL(k_env_reset<CartPoleOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  else
+    hipLaunchKernelGGL(k_env_reset<IndexOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
 }
 
 void launch_env_observe(rl_env *env, float *d_obs) {
-  if (env->kind != RL_ENV_CARTPOLE) return launch_chain_observe(env, d_obs);
   ProfScope ps(env->eng, RL_K_SMALL);
   uint32_t n = (uint32_t)env->cfg.n_lanes;
-  if (env->D == 5)
-    hipLaunchKernelGGL(k_env_observe<5>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n,
-                       d_obs);
-  else
-    hipLaunchKernelGGL(k_env_observe<4>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n,
-                       d_obs);
+  env_dispatch(env, [&](auto ops, auto d) {
+    hipLaunchKernelGGL((k_env_observe<decltype(ops), decltype(d)::value>), dim3(cdiv(n, 256)), dim3(256), 0,
+                       env->eng->stream, env->dev, env->st, n, d_obs);
+  });
 }
 
 void launch_env_step(rl_env *env) {
-  if (env->kind != RL_ENV_CARTPOLE) return launch_chain_step(env);
   ProfScope ps(env->eng, RL_K_ENV_STEP);
   uint32_t n = (uint32_t)env->cfg.n_lanes;
-#define ENV_STEP(DD, FF)                                                                                              \
-  hipLaunchKernelGGL((k_env_step<DD, FF>), dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n, \
-                     env->d_actions, env->d_reward, env->d_flag, env->d_obs, env->d_term_obs)
-  const bool filled = n >= (1u << 20);
-  if (env->D == 5) {
-    if (filled) ENV_STEP(5, true);
-    else ENV_STEP(5, false);
-  } else {
-    if (filled) ENV_STEP(4, true);
-    else ENV_STEP(4, false);
-  }
+  env_dispatch(env, [&](auto ops, auto d) {
+    using Env = decltype(ops);
+    constexpr int D = decltype(d)::value;
+#define ENV_STEP(FF)                                                                                                    \
+  hipLaunchKernelGGL((k_env_step<Env, D, FF>), dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n, \
+                     env->d_actions, env->d_reward, env->d_flag, env->d_obs, env->d_term_obs, env->t_global)
+    if constexpr (std::is_same_v<Env, CartPoleOps>) {
+      if (n >= (1u << 20)) {
+        ENV_STEP(true);
+        return;
+      }
+    }
+    ENV_STEP(false);
 #undef ENV_STEP
+  });
 }
 
 template <int D, int G>

@@ -1,9 +1,10 @@
-// kernels_seq.hip — the recurrent configuration (BASELINE.json configs[4]): vectorised Chain lanes and the
-// GRU -> ReLU -> MLP module (`GruMlpConfig`, src/torch/modules/mod.rs:14) as persistent, tile-resident MFMA kernels.
+// kernels_seq.hip — the recurrent configuration (BASELINE.json configs[4]): the GRU -> ReLU -> MLP module
+// (`GruMlpConfig`, src/torch/modules/mod.rs:14) as persistent, tile-resident MFMA kernels — the cells, the rollout over
+// either env kind (the lanes themselves: env_lanes.hpp), the teacher-forced forward, GAE with a recurrent critic — and
+// the feed-forward rollout over Chain lanes.
 //
 // Reference: Chain<Gru, Mlp> (src/torch/modules/chain.rs:127-186), GruImpl::cell_batch_step -> gru_cell
-// (src/torch/modules/seq/rnn/gru.rs:30-39), gru_data over packed episodes (gru.rs:76-98), Chain env
-// (src/envs/chain.rs:69-106), LatentStepLimit (src/envs/wrappers/step_limit.rs:57-89).
+// (src/torch/modules/seq/rnn/gru.rs:30-39), gru_data over packed episodes (gru.rs:76-98).
 //
 // One workgroup (4 waves) owns a TILE of 32 lanes for the whole horizon.  Wave w owns hidden units [32w, 32w+32)
 // of every gate and of the MLP layer: its slices of W_hh (3 x 64 MFMA B-operands) and W1 (64) stay in registers,
@@ -17,210 +18,8 @@
 //            (libtorch gru_cell operation order), rl_sigmoidf / rl_tanhf of include/rl_detmath.h;
 //   head   : u = relu(b1 + W1 relu(h')) by MFMA, out_a = b2_a + sum_j u_j W2[a][j] as a sequential chain on the
 //            VALU (one lane per (sample, output)).
+#include "env_lanes.hpp"
 #include "seq_common.hpp"
-
-// ---------------------------------------------------------------- lanes of the IndexSpace-observation envs
-// Chain (chain.rs) and MemoryGame (memory.rs) share the lane code: `c.mem_actions` == 0 selects Chain (a launch-uniform
-// branch).  MemoryGame keeps (current_state, initial_state) and the word position of the lane's env stream: its only
-// random draw is `rng.gen_range(0..num_actions)` in initial_state, taken SEQUENTIALLY from the lane's stream like one
-// worker's env Prng in the reference (a rejection loop, so the number of words per reset is not fixed).
-struct ChainLane {
-  uint32_t state, steps_remaining, reset_count;
-  uint32_t initial;   // MemoryGame: the state the episode started in
-  uint64_t env_pos;   // MemoryGame: next unread word of the lane's env stream (always even: u64 draws only)
-};
-
-__device__ __forceinline__ void chain_load(const EnvStateDev &st, uint32_t i, ChainLane &s) {
-  s.state = (uint32_t)st.x[i];
-  s.initial = (uint32_t)st.xdot[i];
-  s.env_pos = (uint64_t)st.th[i];
-  s.steps_remaining = st.steps_remaining[i];
-  s.reset_count = st.reset_count[i];
-}
-
-__device__ __forceinline__ void chain_store(const EnvStateDev &st, uint32_t i, const ChainLane &s) {
-  st.x[i] = (double)s.state;
-  st.xdot[i] = (double)s.initial;
-  st.th[i] = (double)s.env_pos;  // exact below 2^53 words
-  st.steps_remaining[i] = s.steps_remaining;
-  st.reset_count[i] = s.reset_count;
-}
-
-// features of StepLimit-wrapped IndexSpace observations: one-hot (spaces/index.rs:104-116) [+ remaining]
-template <int D>
-__device__ __forceinline__ void chain_features(const CartPoleDev &c, const ChainLane &s, float (&f)[D]) {
-#pragma unroll
-  for (int d = 0; d < D; ++d) f[d] = (uint32_t)d == s.state ? 1.0f : 0.0f;
-  if (D == 6) f[5] = (float)((double)s.steps_remaining / (double)c.max_steps);
-}
-
-// the same for any number of states (MemoryGame::new(num_actions, history_len): D = num_actions + history_len [+ 1]):
-// the remaining-steps feature follows the one-hot.  The standalone env kernels use it; the fused rollouts are built for
-// five states and keep chain_features.
-template <int D>
-__device__ __forceinline__ void index_features(const CartPoleDev &c, const ChainLane &s, float (&f)[D]) {
-#pragma unroll
-  for (int d = 0; d < D; ++d) f[d] = (uint32_t)d == s.state ? 1.0f : 0.0f;
-  if (c.limit_kind == RL_LIMIT_VISIBLE) f[D - 1] = (float)((double)s.steps_remaining / (double)c.max_steps);
-}
-
-// rand 0.8.5 `gen_range(0..range)` for u64/usize (UniformInt::sample_single): widening multiply, accept when the low
-// half is inside the zone `(range << leading_zeros(range)) - 1`; every attempt reads one u64 = stream words
-// (pos, pos + 1), low word first.  The loop ends with probability 1; 64 attempts bound it (each fails w.p. <= 1/2).
-__device__ __forceinline__ uint32_t lane_gen_range(const uint32_t *key, uint64_t glane, uint64_t &pos, uint64_t range) {
-  const uint64_t zone = (range << __clzll((long long)range)) - 1;
-  uint64_t hi = 0;
-  for (int attempt = 0; attempt < 64; ++attempt) {
-    uint32_t w[16];
-    rl_chacha_block(key, pos >> 4, glane, 4, w);
-    uint32_t lo32 = 0, hi32 = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k += 2)
-      if (k == (int)(pos & 15)) {
-        lo32 = w[k];
-        hi32 = w[k + 1];
-      }
-    pos += 2;
-    const uint64_t v = ((uint64_t)hi32 << 32) | lo32;
-    hi = __umul64hi(v, range);
-    if (v * range <= zone) break;
-  }
-  return (uint32_t)hi;
-}
-
-__device__ __forceinline__ void chain_reset(const CartPoleDev &c, ChainLane &s, uint64_t glane) {
-  if (c.mem_actions) {  // MemoryGame::initial_state (memory.rs:87-90)
-    s.state = lane_gen_range(c.key_env, glane, s.env_pos, c.mem_actions);
-    s.initial = s.state;
-  } else {
-    s.state = 0;  // Chain::initial_state (chain.rs:75-77), no random draw
-  }
-  s.steps_remaining = c.max_steps;
-  s.reset_count += 1;
-}
-
-// Chain::step (chain.rs:83-105) / MemoryGame::step (memory.rs:96-114) + the step-limit tail; `word` is the lane's
-// env-stream word for this global step (Chain's slip draw)
-__device__ __forceinline__ int chain_step(const CartPoleDev &c, ChainLane &s, int action, uint32_t word,
-                                          float &reward) {
-  if (c.bandit) {  // Bandit::step (bandits.rs:66-77): Deterministic::sample draws nothing
-    reward = c.bandit_r[action & 7];
-    return RL_SUCC_TERMINATE;
-  }
-  if (c.mem_actions) {
-    if (s.state == c.chain_size - 1) {  // the last of num_actions + history_len states: the answer step
-      reward = (uint32_t)action == s.initial ? 1.0f : -1.0f;
-      return RL_SUCC_TERMINATE;  // passes through the step limit untouched (step_limit.rs:216-222)
-    }
-    s.state = s.state < c.mem_actions ? c.mem_actions : s.state + 1;
-    reward = 0.0f;
-  } else {
-    if (rl_u32_to_unit_f32(word) < 0.2f) action = 1 - action;  // Move::invert
-    if (action == 0) {  // Move::Left
-      s.state = 0;
-      reward = 2.0f;
-    } else if (s.state == c.chain_size - 1) {
-      reward = 10.0f;
-    } else {
-      s.state += 1;
-      reward = 0.0f;
-    }
-  }
-  if (c.limit_kind != RL_LIMIT_NONE) {
-    s.steps_remaining -= 1;
-    if (s.steps_remaining == 0) return RL_SUCC_INTERRUPT;
-  }
-  return RL_SUCC_CONTINUE;
-}
-
-__device__ __forceinline__ uint32_t stream_word(const uint32_t *key, uint64_t stream, uint64_t word) {
-  uint32_t w[16];
-  rl_chacha_block(key, word >> 4, stream, 4, w);
-  uint32_t v = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k)
-    if (k == (int)(word & 15)) v = w[k];
-  return v;
-}
-
-// The env side of the fused rollouts, for both env kinds (the policy side is chosen by the kernel)
-struct ChainOps {
-  using State = ChainLane;
-  static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) { chain_load(st, i, s); }
-  static __device__ __forceinline__ void store(const EnvStateDev &st, uint32_t i, const State &s) { chain_store(st, i, s); }
-  template <int D>
-  static __device__ __forceinline__ void features(const CartPoleDev &c, const State &s, float (&f)[D]) {
-    chain_features<D>(c, s, f);
-  }
-  // Environment::step; the slip draw of global step `word` is word `word` of the lane's env stream
-  static __device__ __forceinline__ int step(const CartPoleDev &c, State &s, int a, uint64_t glane, uint64_t word,
-                                             float &reward) {
-    return chain_step(c, s, a, stream_word(c.key_env, glane, word), reward);
-  }
-  static __device__ __forceinline__ void reset(const CartPoleDev &c, State &s, uint64_t glane) { chain_reset(c, s, glane); }
-};
-
-struct CartPoleOps {
-  using State = LaneState;
-  static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) { lane_load(st, i, s); }
-  static __device__ __forceinline__ void store(const EnvStateDev &st, uint32_t i, const State &s) { lane_store(st, i, s); }
-  template <int D>
-  static __device__ __forceinline__ void features(const CartPoleDev &c, const State &s, float (&f)[D]) {
-    cp_features<D>(c, s, f);
-  }
-  static __device__ __forceinline__ int step(const CartPoleDev &c, State &s, int a, uint64_t, uint64_t, float &reward) {
-    reward = 1.0f;  // CartPole::step (cartpole.rs:140)
-    return cp_step(c, s, a);
-  }
-  static __device__ __forceinline__ void reset(const CartPoleDev &c, State &s, uint64_t glane) { cp_reset(c, s, glane); }
-};
-
-__global__ void k_chain_reset(CartPoleDev c, EnvStateDev st, uint32_t n) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  ChainLane s;
-  chain_load(st, i, s);
-  chain_reset(c, s, c.lane_offset + i);
-  chain_store(st, i, s);
-}
-
-template <int D>
-__global__ void k_chain_observe(CartPoleDev c, EnvStateDev st, uint32_t n, float *__restrict__ obs) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  ChainLane s;
-  chain_load(st, i, s);
-  float f[D];
-  index_features<D>(c, s, f);
-#pragma unroll
-  for (int d = 0; d < D; ++d) obs[(size_t)d * n + i] = f[d];
-}
-
-template <int D>
-__global__ void __launch_bounds__(256) k_chain_step(CartPoleDev c, EnvStateDev st, uint32_t n, uint64_t t_global,
-                                                    const uint8_t *__restrict__ actions, float *__restrict__ reward,
-                                                    uint8_t *__restrict__ flag, float *__restrict__ obs_next,
-                                                    float *__restrict__ term_obs) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  ChainLane s;
-  chain_load(st, i, s);
-  float r;
-  int succ = chain_step(c, s, actions[i], stream_word(c.key_env, c.lane_offset + i, t_global), r);
-  float f[D];
-  if (succ == RL_SUCC_INTERRUPT) {
-    index_features<D>(c, s, f);
-#pragma unroll
-    for (int d = 0; d < D; ++d) term_obs[(size_t)d * n + i] = f[d];
-  }
-  if (succ != RL_SUCC_CONTINUE) chain_reset(c, s, c.lane_offset + i);
-  index_features<D>(c, s, f);
-#pragma unroll
-  for (int d = 0; d < D; ++d) obs_next[(size_t)d * n + i] = f[d];
-  reward[i] = r;
-  flag[i] = (uint8_t)succ;
-  chain_store(st, i, s);
-}
 
 // LDS of the forward kernels
 constexpr int LSTM_KS_LDS = 15;  // k-steps (of GH / 4 = 32) of the LSTM's o gate whose W_hh operands wait in LDS
@@ -631,19 +430,9 @@ __global__ void __launch_bounds__(W16 * 64, 2) k_rollout_gru(CartPoleDev c, EnvS
       const uint64_t word = t_global + t;
       const float u = rl_u32_to_unit_f32(stream_word(c.key_actor, glane, word));
       const int a = categorical_sample_lane<2>(lp, u);
-      float rew;
-      const int succ = Env::step(c, s, a, glane, word, rew);
-      const size_t o = (size_t)t * N + i;
-      tr.action[o] = (uint8_t)a;
-      tr.reward[o] = rew;
-      tr.flag[o] = (uint8_t)succ;
+      const TrajSink sink{tr, (size_t)t * N + i, true};
       float f[D];
-      if (succ == RL_SUCC_INTERRUPT) {
-        Env::template features<D>(c, s, f);
-#pragma unroll
-        for (int d = 0; d < D; ++d) tr.term_obs[(size_t)d * T * N + o] = f[d];
-      }
-      if (succ != RL_SUCC_CONTINUE) Env::reset(c, s, glane);
+      const int succ = lane_step<Env>(c, s, a, glane, word, sink, f);
       Env::template features<D>(c, s, f);
 #pragma unroll
       for (int d = 0; d < D; ++d) {
@@ -668,12 +457,15 @@ __global__ void __launch_bounds__(W16 * 64, 2) k_rollout_gru(CartPoleDev c, EnvS
 }
 
 // ---------------------------------------------------------------- rollout (Chain lanes, feed-forward policy)
-// k_rollout_cartpole's lane-per-thread loop (kernels_rollout.hip) over Chain: features -> in-lane MLP -> log-softmax
-// -> inverse-CDF sample with the lane's actor word -> Chain::step with the lane's env word -> step limit -> reset.
+// k_rollout_cartpole's loop (kernels_rollout.hip) over Chain lanes: features -> in-lane MLP -> log-softmax -> inverse-CDF
+// sample with the lane's actor word -> Chain::step with the lane's env word -> step limit -> reset.  One thread per lane,
+// the actor word uncached.  (Its own kernel, not an instantiation of k_rollout_cartpole, and the one feed-forward kernel
+// of this unit: DESIGN.md §25 has the measurements behind both.)
 template <int D, int BLOCK>
 __global__ void __launch_bounds__(BLOCK) k_rollout_chain_mlp(CartPoleDev c, EnvStateDev st, TrajDev tr,
                                                              const float *__restrict__ policy, int H,
                                                              uint64_t t_global) {
+  using Env = ChainOps;
   __shared__ __attribute__((aligned(16))) float pk[MLP_PK_FLOATS];  // the policy, one 8-float record per hidden unit
   const uint32_t n = tr.n, T = tr.T;
   mlp_pack_lds<D>(pk, policy, H, threadIdx.x, BLOCK);
@@ -681,12 +473,12 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_chain_mlp(CartPoleDev c, EnvS
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   const uint64_t glane = c.lane_offset + i;
-  ChainLane s;
-  chain_load(st, i, s);
+  Env::State s;
+  Env::load(st, i, s);
   const size_t plane = (size_t)(T + 1) * n;
   for (uint32_t t = 0; t < T; ++t) {
     float f[D];
-    chain_features<D>(c, s, f);
+    Env::features<D>(c, s, f);
 #pragma unroll
     for (int d = 0; d < D; ++d) tr.obs[d * plane + (size_t)t * n + i] = f[d];
     const uint64_t word = t_global + t;
@@ -695,24 +487,14 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_chain_mlp(CartPoleDev c, EnvS
     mlp_forward_lane_lds<D>(pk, H, f, z);
     log_softmax_lane<2>(z, lp);
     const int a = categorical_sample_lane<2>(lp, u);
-    float rew;
-    const int succ = chain_step(c, s, a, stream_word(c.key_env, glane, word), rew);
-    const size_t o = (size_t)t * n + i;
-    tr.action[o] = (uint8_t)a;
-    tr.reward[o] = rew;
-    tr.flag[o] = (uint8_t)succ;
-    if (succ == RL_SUCC_INTERRUPT) {
-      chain_features<D>(c, s, f);
-#pragma unroll
-      for (int d = 0; d < D; ++d) tr.term_obs[(size_t)d * T * n + o] = f[d];
-    }
-    if (succ != RL_SUCC_CONTINUE) chain_reset(c, s, glane);
+    const TrajSink sink{tr, (size_t)t * n + i, true};
+    lane_step<Env>(c, s, a, glane, word, sink, f);
   }
   float f[D];
-  chain_features<D>(c, s, f);
+  Env::features<D>(c, s, f);
 #pragma unroll
   for (int d = 0; d < D; ++d) tr.obs[d * plane + (size_t)T * n + i] = f[d];
-  chain_store(st, i, s);
+  Env::store(st, i, s);
 }
 
 // ---------------------------------------------------------------- teacher-forced forward over a trajectory
@@ -973,50 +755,6 @@ void launch_seq_unpad(const rl_mlp *real, const float *exec_src, float *real_dst
   const uint32_t P = (uint32_t)real->P;
   hipLaunchKernelGGL(k_seq_pad<true>, dim3((P + 255) / 256), dim3(256), 0, real->eng->stream, exec_src, real_dst, P,
                      real->in_dim, real->gru_hidden, real->hidden, real->out_dim, (uint32_t)rl_module_gates(real->kind));
-}
-
-void launch_chain_reset(rl_env *env) {
-  ProfScope ps(env->eng, RL_K_SMALL);
-  uint32_t n = (uint32_t)env->cfg.n_lanes;
-  hipLaunchKernelGGL(k_chain_reset, dim3(cdiv_s(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
-}
-
-void launch_chain_observe(rl_env *env, float *d_obs) {
-  ProfScope ps(env->eng, RL_K_SMALL);
-  uint32_t n = (uint32_t)env->cfg.n_lanes;
-  switch (env->D) {  // Chain, bandit: 5 or 6; MemoryGame: num_actions + history_len [+ 1], 4..8
-#define OBSERVE(DD)                                                                                                     \
-  case DD:                                                                                                              \
-    hipLaunchKernelGGL(k_chain_observe<DD>, dim3(cdiv_s(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n, \
-                       d_obs);                                                                                          \
-    break
-    OBSERVE(4);
-    OBSERVE(5);
-    OBSERVE(6);
-    OBSERVE(7);
-    OBSERVE(8);
-#undef OBSERVE
-    default: throw RlError(RL_ERR_UNSUPPORTED, "index env lanes: 4..8 observation features");
-  }
-}
-
-void launch_chain_step(rl_env *env) {
-  ProfScope ps(env->eng, RL_K_ENV_STEP);
-  uint32_t n = (uint32_t)env->cfg.n_lanes;
-  switch (env->D) {
-#define STEP(DD)                                                                                                     \
-  case DD:                                                                                                           \
-    hipLaunchKernelGGL(k_chain_step<DD>, dim3(cdiv_s(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n, \
-                       env->t_global, env->d_actions, env->d_reward, env->d_flag, env->d_obs, env->d_term_obs);      \
-    break
-    STEP(4);
-    STEP(5);
-    STEP(6);
-    STEP(7);
-    STEP(8);
-#undef STEP
-    default: throw RlError(RL_ERR_UNSUPPORTED, "index env lanes: 4..8 observation features");
-  }
 }
 
 void launch_rollout_gru(rl_env *env, const rl_mlp *policy, rl_traj *traj) {

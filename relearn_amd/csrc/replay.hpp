@@ -23,6 +23,20 @@ struct LaneRing {
   uint32_t total;     // total_step_count (replay.rs:21-26)
 };
 
+// the lane's ring words in their per-field [N] tables (`Dev`: ReplayDev, engine.hpp)
+template <typename Dev>
+RL_RING_HD LaneRing ring_load(const Dev &rp, uint32_t i) {
+  return LaneRing{rp.head[i], rp.count[i], rp.ep_head[i], rp.ep_count[i], rp.total[i]};
+}
+template <typename Dev>
+RL_RING_HD void ring_store(const Dev &rp, uint32_t i, const LaneRing &r) {
+  rp.head[i] = r.head;
+  rp.count[i] = r.count;
+  rp.ep_head[i] = r.ep_head;
+  rp.ep_count[i] = r.ep_count;
+  rp.total[i] = r.total;
+}
+
 // One `write_step` (replay.rs:89-115).  `EpEnds` provides get(i)/set(i, v) over the lane's ring of E episode ends
 // (absolute one-past-the-end step indices).  Returns the ring slot (absolute index) the step goes to, or
 // 0xffffffff when the buffer is full of a single unfinished episode (WriteExperienceError::Full).

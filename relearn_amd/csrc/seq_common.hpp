@@ -1,4 +1,4 @@
-// seq_common.hpp — definitions shared by the recurrent-configuration kernels (kernels_seq.hip: lanes, cells, rollout,
+// seq_common.hpp — definitions shared by the recurrent-configuration kernels (kernels_seq.hip: cells, rollout,
 // teacher-forced forward; kernels_seq_bwd.hip: backward through time and weight gradients; kernels_seq_fvp.hip: forward-
 // mode tangents for Fisher-vector products): tile geometry, workspace array indices, the flat-parameter view.
 #pragma once
