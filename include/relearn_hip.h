@@ -640,7 +640,19 @@ typedef struct {
 int32_t rl_dqn_config_default(rl_dqn_config *cfg);
 /* `qnet` maps obs_dim -> n_actions; `opt` must have been created for `qnet`.  DqnConfig<MB> is generic over the module
  * (dqn.rs:26-39): any feed-forward module builds — the fused 5-128-2 shape on the fused kernels, other MlpConfigs on the
- * per-layer kernels; recurrent modules -> RL_ERR_BUILD_AGENT. */
+ * per-layer kernels; recurrent modules -> RL_ERR_BUILD_AGENT.
+ * What builds: every env kind with two actions, each stepped by its own lane code —
+ *   RL_ENV_CARTPOLE                           4 or 5 observation features
+ *   RL_ENV_CHAIN                              5, or 6 under a visible step limit
+ *   RL_ENV_BANDIT with two arms               5
+ *   RL_ENV_MEMORY, MemoryGame(2, h)           2 + h, + 1 under a visible step limit: 4..8
+ * with any feed-forward module of obs_dim inputs and 2 outputs.  A module of one Relu hidden layer of <= 128 units over 4
+ * or 5 features collects in the fused kernel (the whole horizon in one launch); every other module, and every env of 6..8
+ * features, collects step by step on the per-layer kernels.  Steps of 6..8 features keep features 5..7 in a second
+ * 16-byte record beside the 32-byte one (the replay fields read the same: RL_REPLAY_OBS is [obs_dim][C][N]).
+ * Refused: more than two actions (a bandit of >= 3 arms, MemoryGame(>= 3, h)) -> RL_ERR_UNSUPPORTED; a module that does
+ * not match the env's (obs_dim, n_actions) -> RL_ERR_INVALID_ARGUMENT; an env kind or feature count outside the table ->
+ * RL_ERR_UNSUPPORTED with a message that names it.  No env is ever collected by another env's lane code. */
 int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out);
 int32_t rl_dqn_destroy(rl_dqn *dqn);
 /* ExplorationRateSchedule::exploration_rate(global_steps, mode) (schedules.rs:35-45); training = 0 -> 0.0 */

@@ -41,6 +41,7 @@ static ReplayDev replay_alloc(rl_engine *e, DevMem &mem, uint32_t N, uint32_t C,
   size_t cn = (size_t)C * N;
   r.rec = mem.alloc<ReplayRec>(cn);
   r.next = mem.alloc<ReplayNext>(cn);
+  r.hi = D > 5 ? mem.alloc<float4>(cn) : nullptr;
   r.head = mem.alloc<uint32_t>(N);
   r.count = mem.alloc<uint32_t>(N);
   r.ep_head = mem.alloc<uint32_t>(N);
@@ -103,6 +104,17 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
     if (qnet->out_dim > 2) throw RlError(RL_ERR_UNSUPPORTED, "DQN kernels are built for 2 actions");
     RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A, "action-value module does not match the env");
     RL_REQUIRE(env->A == 2, "DQN kernels are built for 2-action envs");
+    // What builds (relearn_hip.h): the collection kernels step CartPole lanes and the index-env lanes (Chain, MemoryGame,
+    // the bandit) of 4..8 observation features.  Anything else is refused here, by name: no env is collected by another
+    // env's code.
+    const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
+    if (env->kind != RL_ENV_CARTPOLE && !index_env)
+      throw RlError(RL_ERR_UNSUPPORTED, "DQN collection is built for CartPole, Chain, MemoryGame and bandit lanes");
+    if (env->D < RL_ENV_MIN_OBS_DIM || env->D > (index_env ? RL_TRAJ_MAX_OBS_DIM : 5u))
+      throw RlError(RL_ERR_UNSUPPORTED, index_env ? "DQN on index-env lanes: 4..8 observation features"
+                                                  : "DQN on CartPole lanes: 4 or 5 observation features");
+    if (env->D > 5 && !qnet->general && !rl_module_is_recurrent(qnet->kind))
+      throw RlError(RL_ERR_UNSUPPORTED, "DQN over 6..8 observation features: the fused collection kernel takes 4 or 5");
     // DqnConfig<MB> is generic over the module (dqn.rs:26-39): feed-forward modules of any MlpConfig build (the fused
     // 5-128-2 shape on the fused kernels, others on the per-layer kernels); recurrent action-value modules do not
     if (rl_module_is_recurrent(qnet->kind))
@@ -116,7 +128,9 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
     if (cfg->exploration_kind == RL_SCHEDULE_LINEAR_ANNEALED)
       RL_REQUIRE(cfg->exploration_period > 0, "exploration_period must be positive");
     uint64_t N = env->cfg.n_lanes;
-    RL_REQUIRE(cfg->buffer_capacity * N * (sizeof(ReplayRec) + sizeof(ReplayNext)) < (200ull << 30), "replay store would not fit in HBM");
+    // (a step: its record, its successor observation, and features 5..7 of an observation wider than the record)
+    const uint64_t step_bytes = sizeof(ReplayRec) + sizeof(ReplayNext) + (env->D > 5 ? sizeof(float4) : 0);
+    RL_REQUIRE(cfg->buffer_capacity * N * step_bytes < (200ull << 30), "replay store would not fit in HBM");
     RL_HIP_CHECK(hipSetDevice(e->device));
     std::unique_ptr<rl_dqn> q(new rl_dqn());
     q->eng = e;
@@ -142,7 +156,7 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
     RL_HIP_CHECK(hipMemsetAsync(q->d_counts, 0, nb * sizeof(DqnCountsDev), e->stream));
     q->mb = traj_alloc(e, q->max_steps_mb, 1, env->D, true);
     {  // the fused step's range guard (bf16_tile.hpp): the words hold the magnitude range of every observation the
-       // collection kernel has put into the store so far (k_rollout_cartpole_dqn folds what it writes, one fold per wave
+       // collection kernel has put into the store so far (k_rollout_dqn folds what it writes, one fold per wave
        // and launch; never reset, so they bound every minibatch drawn from the store from outside).  Rounds 3-5 kept fixed bounds here, 2^-64 .. 2^16,
        // under which a Q-network with a zero bias could never pass the guard.
       std::vector<uint32_t> words(RL_RANGE_WORDS, 0u);  // every slot of the minima / the maxima (bf16_tile.hpp)

@@ -102,6 +102,10 @@ struct ReplayDev {
   uint64_t *actor_pos;  // [N] word position of the lane's actor stream
   int32_t *error;       // != 0: a lane hit WriteExperienceError::Full / an empty buffer was sampled
   uint32_t N, C, E, D;
+  // [N][C] features 5, 6 and 7 of an observation wider than the record's five floats (.w unused): a second 16-byte record
+  // per step, allocated when D > 5 (NULL otherwise; the step-wise collection writes it, the gathers read it).  Last, so
+  // that the fields above keep their kernel-argument offsets.
+  float4 *hi;
 };
 
 struct DqnCountsDev {

@@ -5,6 +5,7 @@
 // replay.rs:89-115), DqnAgent::batch_update_slice_refs sample_minibatch (dqn.rs:280-314), StepValueTarget
 // (src/torch/agents/critics/mod.rs:203-229).
 #include <memory>
+#include <type_traits>
 
 #include "bf16_tile.hpp"
 #include "device_fns.hpp"
@@ -24,6 +25,16 @@ __device__ __forceinline__ void rec_store(ReplayRec *__restrict__ p, const Repla
   reinterpret_cast<uint4 *>(p)[0] = make_uint4(__float_as_uint(r.x[0]), __float_as_uint(r.x[1]), __float_as_uint(r.x[2]),
                                                __float_as_uint(r.x[3]));
   reinterpret_cast<uint4 *>(p)[1] = make_uint4(__float_as_uint(r.x[4]), __float_as_uint(r.reward), r.af, 0u);
+}
+
+// features 5..D of the step at record index `o` (observations wider than the record: ReplayDev::hi), one 16-byte load
+template <int D>
+__device__ __forceinline__ void rec_load_hi(const ReplayDev &rp, size_t o, float (&x)[D]) {
+  static_assert(D > 5 && D <= 8, "the second record array holds features 5, 6 and 7");
+  const float4 h = rp.hi[o];
+  x[5] = h.x;
+  if (D > 6) x[D > 6 ? 6 : 0] = h.y;
+  if (D > 7) x[D > 7 ? 7 : 0] = h.z;
 }
 
 // DqnActor::act (dqn.rs:360-379) from the lane's sequential actor stream:
@@ -63,13 +74,14 @@ struct LaneEpEnds {
 // rollout (kernels_rollout.hip: a launch lasts T x the latency of one step, and most of a greedy step is the 128-unit
 // forward); everything else — draws, physics, ring bookkeeping — is repeated by every thread of the group, thread 0
 // stores.  The result does not depend on G (mlp_forward_group_lds).
-template <int D, int BLOCK, int G>
-__global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, EnvStateDev st, ReplayDev rp,
-                                                                const float *__restrict__ qnet, int H, uint32_t T,
-                                                                uint64_t p_int, int always_explore,
-                                                                uint8_t *__restrict__ flags_out,
-                                                                uint32_t *__restrict__ range) {
-  using Env = CartPoleOps;
+// `Env`: CartPoleOps, or IndexOps (Chain, MemoryGame, the bandit: env_lanes.hpp).  An index lane reads word t_global + t of
+// its env stream in step t (Chain's slip draw) and draws MemoryGame's initial states sequentially from ChainLane::env_pos:
+// every thread of a lane's group repeats both, like the physics.
+template <class Env, int D, int BLOCK, int G>
+__global__ void __launch_bounds__(BLOCK) k_rollout_dqn(CartPoleDev c, EnvStateDev st, ReplayDev rp,
+                                                       const float *__restrict__ qnet, int H, uint32_t T, uint64_t p_int,
+                                                       int always_explore, uint8_t *__restrict__ flags_out,
+                                                       uint32_t *__restrict__ range, uint64_t t_global) {
   __shared__ uint32_t words[16 * BLOCK];
   __shared__ __attribute__((aligned(16))) float pk[MLP_PK_FLOATS];  // the Q-network, one 8-float record per hidden unit
   // the collected observations' magnitude range, for the fused gradient kernel's range guard (bf16_tile.hpp): one fold
@@ -86,7 +98,7 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, E
   const uint32_t i = live ? i0 : n - 1;
   const bool writer = live && g == 0;
   const uint64_t lane = c.lane_offset + i;
-  Env::State s;
+  typename Env::State s;
   Env::load(st, i, s);
   LaneRing ring = ring_load(rp, i);
   LaneEpEnds eps{rp.ep_end, n, i, writer};
@@ -94,7 +106,7 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, E
   bool full = false;
   for (uint32_t t = 0; t < T; ++t) {
     float f[D];
-    Env::features<D>(c, s, f);
+    Env::template features<D>(c, s, f);
     int a;
     if (dqn_explores(rng, p_int, always_explore)) {
       a = dqn_random_action(rng);
@@ -106,7 +118,7 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, E
     // lane_step's rule (env_lanes.hpp) with the replay ring as its sink, written out: the ring may refuse the step, and
     // closes a lane the horizon cuts in its own way (DESIGN.md §25 on why these lines are not a sink struct)
     float reward;
-    const int succ = Env::step(c, s, a, lane, 0, reward);
+    const int succ = Env::step(c, s, a, lane, t_global + t, reward);
     // the engine's horizon rule: a lane still mid-episode at the end of the launch closes its
     // episode as Interrupt(successor observation) and carries the env state on into the next collection
     const bool horizon_cut = succ == RL_SUCC_CONTINUE && t + 1 == T;
@@ -128,7 +140,7 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, E
       rec_store(rp.rec + o, rec);
     }
     if (succ_rec == RL_SUCC_INTERRUPT) {
-      Env::features<D>(c, s, f);
+      Env::template features<D>(c, s, f);
 #pragma unroll
       for (int d = 0; d < D; ++d) bt::range_accumulate(f[d], r_lo, r_hi);
       if (writer) {
@@ -152,30 +164,31 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_cartpole_dqn(CartPoleDev c, E
 // built for (rl_mlp::general: several hidden layers, other activations, a wider layer) collects one launch sequence per
 // step — observe, the module's layer kernels over all lanes (kernels_general.hip), then this kernel: DqnActor::act
 // from the lane's actor stream with the greedy branch reading the module's outputs, the env step, the ring write — with
-// the fused kernel's stream discipline, ring bookkeeping and horizon rule (above), one thread per lane.
-template <int D, int BLOCK>
+// the fused kernel's stream discipline, ring bookkeeping and horizon rule (above), one thread per lane.  `word`: the
+// global step (t_global + t).  Features 5..7 of an observation wider than the 32-byte record go to the second record array
+// (ReplayDev::hi).
+template <class Env, int D, int BLOCK>
 __global__ void __launch_bounds__(BLOCK) k_dqn_lane_step(CartPoleDev c, EnvStateDev st, ReplayDev rp,
                                                          const float *__restrict__ q_values /* [2][n] */, uint64_t p_int,
                                                          int always_explore, int last_step,
-                                                         uint8_t *__restrict__ flags_row) {
-  using Env = CartPoleOps;
+                                                         uint8_t *__restrict__ flags_row, uint64_t word) {
   __shared__ uint32_t words[16 * BLOCK];
   const uint32_t n = rp.N;
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   const uint64_t lane = c.lane_offset + i;
-  Env::State s;
+  typename Env::State s;
   Env::load(st, i, s);
   LaneRing ring = ring_load(rp, i);
   LaneEpEnds eps{rp.ep_end, n, i, true};
   LaneActorRng<BLOCK> rng{&words[threadIdx.x], c.key_actor, lane, rp.actor_pos[i], ~0ull};
   float f[D];
-  Env::features<D>(c, s, f);
+  Env::template features<D>(c, s, f);
   int a;
   if (dqn_explores(rng, p_int, always_explore)) a = dqn_random_action(rng);
   else a = q_values[n + i] > q_values[i] ? 1 : 0;  // argmax: first maximal index
   float reward;  // (the step, its record and the horizon rule as in the fused kernel)
-  const int succ = Env::step(c, s, a, lane, 0, reward);
+  const int succ = Env::step(c, s, a, lane, word, reward);
   const bool horizon_cut = succ == RL_SUCC_CONTINUE && last_step != 0;
   const int succ_rec = horizon_cut ? RL_SUCC_INTERRUPT : succ;
   const uint32_t slot_abs = ring_write_step(ring, rp.C, rp.E, eps, succ_rec != RL_SUCC_CONTINUE);
@@ -190,8 +203,9 @@ __global__ void __launch_bounds__(BLOCK) k_dqn_lane_step(CartPoleDev c, EnvState
   rec.reward = reward;
   rec.af = (uint32_t)a | (uint32_t)succ_rec << 8;
   rec_store(rp.rec + o, rec);
+  if constexpr (D > 5) rp.hi[o] = make_float4(f[5], D > 6 ? f[D > 6 ? 6 : 0] : 0.0f, D > 7 ? f[D > 7 ? 7 : 0] : 0.0f, 0.0f);
   if (succ_rec == RL_SUCC_INTERRUPT) {
-    Env::features<D>(c, s, f);
+    Env::template features<D>(c, s, f);
 #pragma unroll
     for (int d = 0; d < D; ++d) rp.next[o].x[d] = f[d];
   }
@@ -231,6 +245,7 @@ __global__ void __launch_bounds__(64) k_dqn_build_minibatch(ReplayDev rp, const 
                                                             uint8_t *__restrict__ out_action,
                                                             float *__restrict__ out_target, float gamma,
                                                             int one_step_td, const float *__restrict__ qnet, int H) {
+  constexpr int DR = D < 5 ? D : 5;  // features in the 32-byte record
   __shared__ float rew[1024];
   __shared__ float carry;
   const uint32_t e = blockIdx.x;
@@ -240,8 +255,15 @@ __global__ void __launch_bounds__(64) k_dqn_build_minibatch(ReplayDev rp, const 
     const uint32_t slot = (start + i) % rp.C;
     const ReplayRec rec = rec_load(ring + slot);
 #pragma unroll
-    for (int d = 0; d < D; ++d) out_obs[d * out_plane + off + i] = rec.x[d];
+    for (int d = 0; d < DR; ++d) out_obs[d * out_plane + off + i] = rec.x[d];
+    if constexpr (D > 5) {
+      float x[D];
+      rec_load_hi<D>(rp, (size_t)lane * rp.C + slot, x);
+#pragma unroll
+      for (int d = 5; d < D; ++d) out_obs[d * out_plane + off + i] = x[d];
+    }
     out_action[off + i] = (uint8_t)(rec.af & 0xffu);
+    if constexpr (D <= 5)  // (the forward below is the fused module's: a wider module's TD targets are k_dqn_td_targets')
     if (one_step_td) {
       const uint32_t fl = rec.af >> 8;
       float vnext = 0.0f;
@@ -309,6 +331,7 @@ __global__ void __launch_bounds__(BUILD_ALL_WAVES * 64)
   // out_flag != NULL: one-step TD — the targets are left to the gradient kernel (they use the current network): the
   // reward goes where the target would, the successor code into out_flag, the successor observation (the next step's,
   // or the stored one after an Interrupt / at the episode's last step) into time slot 1 of the observation planes
+  constexpr int DR = D < 5 ? D : 5;  // features in the 32-byte record
   const bool td = out_flag != nullptr;
   const uint32_t b = blockIdx.y, lane = threadIdx.x & 63;
   const uint32_t e = blockIdx.x * BUILD_ALL_WAVES + (threadIdx.x >> 6);
@@ -343,7 +366,13 @@ __global__ void __launch_bounds__(BUILD_ALL_WAVES * 64)
     }
     if (mine) {
 #pragma unroll
-      for (int d = 0; d < D; ++d) obs_b[d * out_plane + off + i] = rec.x[d];
+      for (int d = 0; d < DR; ++d) obs_b[d * out_plane + off + i] = rec.x[d];
+      if constexpr (D > 5) {
+        float x[D];
+        rec_load_hi<D>(rp, (size_t)ln * rp.C + (start + i) % rp.C, x);
+#pragma unroll
+        for (int d = 5; d < D; ++d) obs_b[d * out_plane + off + i] = x[d];
+      }
       act_b[off + i] = (uint8_t)(rec.af & 0xffu);
       tgt_b[off + i] = td ? rew : out;
       if (td) {
@@ -357,7 +386,8 @@ __global__ void __launch_bounds__(BUILD_ALL_WAVES * 64)
         } else {
           const ReplayRec r1 = rec_load(ring + (start + i + 1) % rp.C);
 #pragma unroll
-          for (int d = 0; d < D; ++d) nx[d] = r1.x[d];
+          for (int d = 0; d < DR; ++d) nx[d] = r1.x[d];
+          if constexpr (D > 5) rec_load_hi<D>(rp, (size_t)ln * rp.C + (start + i + 1) % rp.C, nx);
         }
 #pragma unroll
         for (int d = 0; d < D; ++d) obs_b[d * out_plane + n_steps + off + i] = nx[d];
@@ -635,18 +665,39 @@ void launch_dqn_sample(rl_engine *eng, hipStream_t stream, const ReplayDev &rp, 
 
 static inline uint32_t cdiv_d(size_t a, size_t b) { return (uint32_t)((a + b - 1) / b); }
 
-template <int G>
-static void launch_rollout_dqn_g(rl_env *env, const rl_mlp *qnet, const ReplayDev &rp, uint32_t T, uint64_t p_int,
-                                 int always_explore, uint8_t *d_flags, uint32_t *d_range) {
-  constexpr int BLOCK = 64;
-  const uint32_t n = (uint32_t)env->cfg.n_lanes;
-  const dim3 grid(cdiv_d((size_t)n * G, BLOCK)), blk(BLOCK);
-  if (env->D == 5)
-    hipLaunchKernelGGL((k_rollout_cartpole_dqn<5, BLOCK, G>), grid, blk, 0, env->eng->stream, env->dev, env->st, rp,
-                       qnet->d_params, (int)qnet->hidden, T, p_int, always_explore, d_flags, d_range);
-  else
-    hipLaunchKernelGGL((k_rollout_cartpole_dqn<4, BLOCK, G>), grid, blk, 0, env->eng->stream, env->dev, env->st, rp,
-                       qnet->d_params, (int)qnet->hidden, T, p_int, always_explore, d_flags, d_range);
+// The collection kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature count
+// as types, as env_dispatch does for the standalone env kernels (kernels_rollout.hip).  CartPole lanes have 4 or 5
+// features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame(2, h): 2 + h [+ 1]) 4..`MAX_D`.
+template <int D>
+using FeatureCount = std::integral_constant<int, D>;
+template <int MAX_D, class Go>
+static void dqn_env_dispatch(const rl_env *env, const char *what, Go &&go) {
+  const bool cartpole = env->kind == RL_ENV_CARTPOLE;
+  if (env->D < 4 || env->D > (cartpole ? 5u : (uint32_t)MAX_D)) throw RlError(RL_ERR_UNSUPPORTED, what);
+  if (cartpole) {
+    if (env->D == 5) go(CartPoleOps{}, FeatureCount<5>{});
+    else go(CartPoleOps{}, FeatureCount<4>{});
+    return;
+  }
+  switch (env->D) {
+    case 4: go(IndexOps{}, FeatureCount<4>{}); break;
+    case 5: go(IndexOps{}, FeatureCount<5>{}); break;
+    case 6: if constexpr (MAX_D >= 6) go(IndexOps{}, FeatureCount<6>{}); break;
+    case 7: if constexpr (MAX_D >= 7) go(IndexOps{}, FeatureCount<7>{}); break;
+    default: if constexpr (MAX_D >= 8) go(IndexOps{}, FeatureCount<8>{}); break;
+  }
+}
+// ... and the kernels that read the store per feature count alone
+template <class Go>
+static void dqn_features_dispatch(uint32_t D, Go &&go) {
+  switch (D) {
+    case 4: go(FeatureCount<4>{}); break;
+    case 5: go(FeatureCount<5>{}); break;
+    case 6: go(FeatureCount<6>{}); break;
+    case 7: go(FeatureCount<7>{}); break;
+    case 8: go(FeatureCount<8>{}); break;
+    default: throw RlError(RL_ERR_UNSUPPORTED, "DQN replay store: 4..8 observation features");
+  }
 }
 
 void launch_rollout_dqn(rl_env *env, const rl_mlp *qnet, const ReplayDev &rp, uint32_t T, uint64_t p_int,
@@ -658,13 +709,22 @@ void launch_rollout_dqn(rl_env *env, const rl_mlp *qnet, const ReplayDev &rp, ui
   int G = 1;
   while (!always_explore && G < 16 && n * (uint64_t)(2 * G) <= simds * 64) G *= 2;
   if (env->eng->kernel_variant == 1) G = 1;
-  switch (G) {
-    case 16: launch_rollout_dqn_g<16>(env, qnet, rp, T, p_int, always_explore, d_flags, d_range); break;
-    case 8: launch_rollout_dqn_g<8>(env, qnet, rp, T, p_int, always_explore, d_flags, d_range); break;
-    case 4: launch_rollout_dqn_g<4>(env, qnet, rp, T, p_int, always_explore, d_flags, d_range); break;
-    case 2: launch_rollout_dqn_g<2>(env, qnet, rp, T, p_int, always_explore, d_flags, d_range); break;
-    default: launch_rollout_dqn_g<1>(env, qnet, rp, T, p_int, always_explore, d_flags, d_range); break;
-  }
+  dqn_env_dispatch<5>(env, "fused DQN collection: 4 or 5 observation features", [&](auto ops, auto d) {
+    using Env = decltype(ops);
+    constexpr int D = decltype(d)::value, BLOCK = 64;
+#define ROLLOUT_DQN(GG)                                                                                                 \
+  hipLaunchKernelGGL((k_rollout_dqn<Env, D, BLOCK, GG>), dim3(cdiv_d((size_t)n * GG, BLOCK)), dim3(BLOCK), 0,          \
+                     env->eng->stream, env->dev, env->st, rp, qnet->d_params, (int)qnet->hidden, T, p_int,             \
+                     always_explore, d_flags, d_range, env->t_global)
+    switch (G) {
+      case 16: ROLLOUT_DQN(16); break;
+      case 8: ROLLOUT_DQN(8); break;
+      case 4: ROLLOUT_DQN(4); break;
+      case 2: ROLLOUT_DQN(2); break;
+      default: ROLLOUT_DQN(1); break;
+    }
+#undef ROLLOUT_DQN
+  });
   RL_HIP_CHECK(hipGetLastError());
 }
 
@@ -678,12 +738,11 @@ void launch_rollout_dqn_general(rl_env *env, const rl_mlp *qnet, rl_traj *ws, fl
       launch_env_observe(env, env->d_obs);                          // [D][n]
       launch_gen_forward(ws, qnet, env->d_obs, (size_t)n, n, d_q);  // [2][n]
     }
-    if (env->D == 5)
-      hipLaunchKernelGGL((k_dqn_lane_step<5, BLOCK>), dim3(cdiv_d(n, BLOCK)), dim3(BLOCK), 0, env->eng->stream, env->dev,
-                         env->st, rp, d_q, p_int, always_explore, t + 1 == T ? 1 : 0, d_flags + (size_t)t * n);
-    else
-      hipLaunchKernelGGL((k_dqn_lane_step<4, BLOCK>), dim3(cdiv_d(n, BLOCK)), dim3(BLOCK), 0, env->eng->stream, env->dev,
-                         env->st, rp, d_q, p_int, always_explore, t + 1 == T ? 1 : 0, d_flags + (size_t)t * n);
+    dqn_env_dispatch<8>(env, "step-wise DQN collection: 4..8 observation features", [&](auto ops, auto d) {
+      hipLaunchKernelGGL((k_dqn_lane_step<decltype(ops), decltype(d)::value, BLOCK>), dim3(cdiv_d(n, BLOCK)), dim3(BLOCK),
+                         0, env->eng->stream, env->dev, env->st, rp, d_q, p_int, always_explore, t + 1 == T ? 1 : 0,
+                         d_flags + (size_t)t * n, env->t_global + t);
+    });
   }
   RL_HIP_CHECK(hipGetLastError());
 }
@@ -702,14 +761,13 @@ void launch_dqn_build_minibatch(rl_engine *eng, const ReplayDev &rp, uint32_t n_
                                 int one_step_td, const rl_mlp *qnet) {
   ProfScope ps(eng, RL_K_VALUES);
   if (n_eps == 0) return;
-  if (rp.D == 5)
-    hipLaunchKernelGGL(k_dqn_build_minibatch<5>, dim3(n_eps), dim3(64), 0, eng->stream, rp, d_lane, d_start, d_len,
-                       d_off, d_obs, out_plane, d_action, d_target, gamma, one_step_td, qnet->d_params,
+  if (one_step_td && rp.D > 5)  // (rl_dqn's general modules take launch_dqn_build_all + launch_dqn_td_targets)
+    throw RlError(RL_ERR_UNSUPPORTED, "in-kernel one-step TD targets: 4 or 5 observation features");
+  dqn_features_dispatch(rp.D, [&](auto d) {
+    hipLaunchKernelGGL(k_dqn_build_minibatch<decltype(d)::value>, dim3(n_eps), dim3(64), 0, eng->stream, rp, d_lane,
+                       d_start, d_len, d_off, d_obs, out_plane, d_action, d_target, gamma, one_step_td, qnet->d_params,
                        (int)qnet->hidden);
-  else
-    hipLaunchKernelGGL(k_dqn_build_minibatch<4>, dim3(n_eps), dim3(64), 0, eng->stream, rp, d_lane, d_start, d_len,
-                       d_off, d_obs, out_plane, d_action, d_target, gamma, one_step_td, qnet->d_params,
-                       (int)qnet->hidden);
+  });
 }
 
 void launch_dqn_build_all(rl_engine *eng, const ReplayDev &rp, uint32_t n_batches, uint32_t widest_eps, uint32_t max_eps,
@@ -719,12 +777,10 @@ void launch_dqn_build_all(rl_engine *eng, const ReplayDev &rp, uint32_t n_batche
   ProfScope ps(eng, RL_K_VALUES);
   if (n_batches == 0 || widest_eps == 0) return;
   const dim3 grid(cdiv_d(widest_eps, BUILD_ALL_WAVES), n_batches), block(BUILD_ALL_WAVES * 64);
-  if (rp.D == 5)
-    hipLaunchKernelGGL(k_dqn_build_all<5>, grid, block, 0, eng->stream, rp, d_lane, d_start, d_len, d_off, max_eps,
-                       d_counts, d_obs, obs_stride, d_action, d_target, step_stride, gamma, d_flag);
-  else
-    hipLaunchKernelGGL(k_dqn_build_all<4>, grid, block, 0, eng->stream, rp, d_lane, d_start, d_len, d_off, max_eps,
-                       d_counts, d_obs, obs_stride, d_action, d_target, step_stride, gamma, d_flag);
+  dqn_features_dispatch(rp.D, [&](auto d) {
+    hipLaunchKernelGGL(k_dqn_build_all<decltype(d)::value>, grid, block, 0, eng->stream, rp, d_lane, d_start, d_len,
+                       d_off, max_eps, d_counts, d_obs, obs_stride, d_action, d_target, step_stride, gamma, d_flag);
+  });
   RL_HIP_CHECK(hipGetLastError());
 }
 
@@ -968,7 +1024,11 @@ __global__ void __launch_bounds__(256) k_replay_planes(ReplayDev rp, int field, 
   const uint32_t lane = (uint32_t)(idx % rp.N), slot = (uint32_t)(idx / rp.N);
   const size_t o = (size_t)lane * rp.C + slot;
   if (field == RL_REPLAY_OBS) {
-    for (uint32_t d = 0; d < rp.D; ++d) static_cast<float *>(out)[d * cn + idx] = rp.rec[o].x[d];
+    for (uint32_t d = 0; d < rp.D && d < 5; ++d) static_cast<float *>(out)[d * cn + idx] = rp.rec[o].x[d];
+    if (rp.D > 5) {  // (the second record array exists)
+      const float4 h = rp.hi[o];
+      for (uint32_t d = 5; d < rp.D; ++d) static_cast<float *>(out)[d * cn + idx] = d == 5 ? h.x : d == 6 ? h.y : h.z;
+    }
   } else if (field == RL_REPLAY_NEXT_OBS) {
     for (uint32_t d = 0; d < rp.D; ++d) static_cast<float *>(out)[d * cn + idx] = rp.next[o].x[d];
   } else if (field == RL_REPLAY_ACTION) {
