@@ -51,21 +51,48 @@ struct GmArgs {
   uint32_t off[GM_MAX_HIDDEN + 1];  // parameter offset of layer l's weights [N][K]; its bias follows them
   uint32_t P;
 };
+// fan-in and fan-out of layer l (layer NL: the output layer)
+__device__ __forceinline__ int gm_K(const GmArgs &g, int l) { return l == 0 ? g.in_dim : g.width[l - 1]; }
+template <int NL>
+__device__ __forceinline__ int gm_N(const GmArgs &g, int l) { return l == NL ? g.out_dim : g.width[l]; }
 
 // fragment groups of the LDS weight image (three piece fragments each): forward layer 0 [ot], forward hidden layer l
 // [ot][ks], forward output [ks], backward hidden layer l [it][ks], backward output [it]
 // (GW = 32-unit tiles per hidden layer: 2 for up to three layers of at most 64 units, 4 for one layer of at most 128)
+// C, the COMPACT image of the pair kernel: the same groups without the output layer's forward fragments — of their 32
+// rows only the module's (at most two) outputs are non-zero, so they live apart, behind the groups, one 16-byte entry per
+// (k-step, piece, output, lane half) instead of 64: 1.5 KB instead of 12 KB (24 KB with the tangent's), which is what lets
+// four pairs of waves and the tangent image share a CU's LDS.
 constexpr int gm_fh(int GW, int l) { return GW + (l - 1) * 2 * GW * GW; }
 constexpr int gm_fo(int GW, int NL) { return GW + (NL - 1) * 2 * GW * GW; }
-constexpr int gm_bh(int GW, int NL, int l) { return gm_fo(GW, NL) + 2 * GW + (l - 1) * 2 * GW * GW; }
-constexpr int gm_bo(int GW, int NL) { return gm_bh(GW, NL, NL); }
-constexpr int gm_groups(int GW, int NL) { return gm_bo(GW, NL) + GW; }
+constexpr int gm_bh(bool C, int GW, int NL, int l) { return gm_fo(GW, NL) + (C ? 0 : 2 * GW) + (l - 1) * 2 * GW * GW; }
+constexpr int gm_bo(bool C, int GW, int NL) { return gm_bh(C, GW, NL, NL); }
+constexpr int gm_groups(bool C, int GW, int NL) { return gm_bo(C, GW, NL) + GW; }
 // PASS_JVP: the forward fragments of the tangent parameters follow, in the same order (layer 0, hidden, output)
-constexpr int gm_fwd_groups(int GW, int NL) { return gm_fo(GW, NL) + 2 * GW; }
-constexpr int gm_all_groups(int GW, int NL, bool jvp) { return gm_groups(GW, NL) + (jvp ? gm_fwd_groups(GW, NL) : 0); }
-constexpr size_t gm_lds_bytes(int GW, int NL, bool jvp) {
-  return (size_t)gm_all_groups(GW, NL, jvp) * 3 * 64 * 16 + (size_t)NL * 32 * GW * 4 * (jvp ? 2 : 1);
+constexpr int gm_fwd_groups(bool C, int GW, int NL) { return gm_fo(GW, NL) + (C ? 0 : 2 * GW); }
+constexpr int gm_all_groups(bool C, int GW, int NL, bool jvp) {
+  return gm_groups(C, GW, NL) + (jvp ? gm_fwd_groups(C, GW, NL) : 0);
 }
+constexpr int gm_outc_entries(int GW) { return 2 * GW * 3 * 4; }  // uint4 entries of one compact output-layer image
+// the image in bytes: the groups, (C) the compact output fragments, the bias table [NL][32 GW] of layers 1 .. NL
+constexpr size_t gm_image_bytes(bool C, int GW, int NL, bool jvp) {
+  return (size_t)gm_all_groups(C, GW, NL, jvp) * 3 * 64 * 16 + (C ? (size_t)(jvp ? 2 : 1) * gm_outc_entries(GW) * 16 : 0) +
+         (size_t)NL * 32 * GW * 4 * (jvp ? 2 : 1);
+}
+constexpr int GP_PAIRS = 4;
+// dynamic LDS of k_gen_mfma: the image; of k_gen_pair: the compact image, an exchange region [2][6][64] of 16 bytes and
+// the partial outputs [2][ZV][32] of every pair
+constexpr size_t gm_lds_bytes(int GW, int NL, bool jvp) { return gm_image_bytes(false, GW, NL, jvp); }
+constexpr size_t gp_lds_bytes(int NL, int pairs, bool jvp) {
+  return gm_image_bytes(true, 2, NL, jvp) + (size_t)pairs * 2 * 6 * 64 * 16 + (size_t)pairs * 2 * (jvp ? 4 : 2) * 32 * 4;
+}
+// (the byte counts of every instantiation, as they were with one family of index functions per kernel)
+static_assert(gm_lds_bytes(2, 1, false) == 24832 && gm_lds_bytes(2, 1, true) == 43520 && gm_lds_bytes(2, 2, false) == 74240 &&
+              gm_lds_bytes(2, 2, true) == 117760 && gm_lds_bytes(2, 3, false) == 123648 && gm_lds_bytes(2, 3, true) == 192000 &&
+              gm_lds_bytes(4, 1, false) == 49664 && gm_lds_bytes(4, 1, true) == 87040, "k_gen_mfma: LDS bytes");
+static_assert(gp_lds_bytes(1, GP_PAIRS, false) == 64512 && gp_lds_bytes(1, GP_PAIRS, true) == 73728 &&
+              gp_lds_bytes(2, GP_PAIRS, false) == 113920 && gp_lds_bytes(2, GP_PAIRS, true) == 147968 &&
+              gp_lds_bytes(3, GP_PAIRS, false) == 163328 && gp_lds_bytes(3, GP_PAIRS, true) == 222208, "k_gen_pair: LDS bytes");
 
 __device__ __forceinline__ constexpr int urow(int r, int kb) { return (r & 3) + 8 * (r >> 2) + 4 * kb; }
 
@@ -179,25 +206,13 @@ __device__ __forceinline__ f32x16 bias_tile(f32x16 acc, const Frag (&dt)[2][3], 
   return acc;
 }
 
-// The pair kernel's image: the same groups without the output layer's forward fragments — of their 32 rows only the
-// module's (at most two) outputs are non-zero, so they live apart, one 16-byte entry per (group, piece, output, lane half)
-// instead of 64: 1.5 KB instead of 12 KB (24 KB with the tangent's), which is what lets four pairs of waves and the
-// tangent image share a CU's LDS.
-constexpr int cp_bh(int GW, int NL, int l) { return GW + (NL - 1) * 2 * GW * GW + (l - 1) * 2 * GW * GW; }
-constexpr int cp_bo(int GW, int NL) { return cp_bh(GW, NL, NL); }
-constexpr int cp_groups(int GW, int NL) { return cp_bo(GW, NL) + GW; }
-constexpr int cp_tan_groups(int GW, int NL) { return GW + (NL - 1) * 2 * GW * GW; }
-
 // ---- the weight image: every fragment in the acc_row order of the tile it meets.  `src`: the parameters (forward and
 // backward fragments from group g0 = 0) or the tangent (forward fragments only, from group TG); every thread of the
 // workgroup (`nthreads`) calls it, the caller synchronises.
-// `outc` != NULL: the compact layout above (output-layer forward fragments into outc[(ks * 3 + piece) * 4 + 2 j + half]).
-template <int NL, int GW>
+// C: the compact layout (output-layer forward fragments into outc[(ks * 3 + piece) * 4 + 2 j + half]).
+template <bool C, int NL, int GW>
 __device__ __forceinline__ void gm_build_image(const GmArgs &g, const float *__restrict__ src, uint4 (*img)[64], int g0,
                                                bool with_backward, float *bias_out, int nthreads, uint4 *outc = nullptr) {
-  const bool compact = outc != nullptr;
-  auto Kof = [&](int l) { return l == 0 ? g.in_dim : g.width[l - 1]; };
-  auto Nof = [&](int l) { return l == NL ? g.out_dim : g.width[l]; };
   auto put_group = [&](int grp, int ln, const float (&v)[8]) {
     uint32_t p[3][8];
 #pragma unroll
@@ -210,7 +225,7 @@ __device__ __forceinline__ void gm_build_image(const GmArgs &g, const float *__r
   // forward, layer 0 [ot]: inputs 4 hh + e (e < 4), the bias as input `in_dim`
   for (int idx = threadIdx.x; idx < GW * 64; idx += nthreads) {
     const int ot = idx >> 6, ln = idx & 63, mm = ln & 31, hh = ln >> 5;
-    const int unit = ot * 32 + mm, N = Nof(0);
+    const int unit = ot * 32 + mm, N = gm_N<NL>(g, 0);
     const float *W = src + g.off[0];
     float v[8];
 #pragma unroll
@@ -223,7 +238,7 @@ __device__ __forceinline__ void gm_build_image(const GmArgs &g, const float *__r
   // forward [ot][ks] and backward [it][ks] through hidden layer l
 #pragma unroll
   for (int l = 1; l < NL; ++l) {
-    const int K = Kof(l), N = Nof(l);
+    const int K = gm_K(g, l), N = gm_N<NL>(g, l);
     const float *W = src + g.off[l];
     for (int idx = threadIdx.x; idx < (with_backward ? 2 : 1) * 2 * GW * GW * 64; idx += nthreads) {
       const int dir = idx / (2 * GW * GW * 64), r2 = (idx >> 6) % (2 * GW * GW), ln = idx & 63, mm = ln & 31, hh = ln >> 5;
@@ -236,11 +251,11 @@ __device__ __forceinline__ void gm_build_image(const GmArgs &g, const float *__r
         const int j = dir == 0 ? own : across, k = dir == 0 ? across : own;
         v[e] = (j < N && k < K) ? W[j * K + k] : 0.0f;
       }
-      put_group(g0 + (dir == 0 ? gm_fh(GW, l) : (compact ? cp_bh(GW, NL, l) : gm_bh(GW, NL, l))) + r2, ln, v);
+      put_group(g0 + (dir == 0 ? gm_fh(GW, l) : gm_bh(C, GW, NL, l)) + r2, ln, v);
     }
   }
   {  // output layer: forward [ks], backward [it]
-    const int K = Kof(NL);
+    const int K = gm_K(g, NL);
     const float *W = src + g.off[NL];
     for (int idx = threadIdx.x; idx < (with_backward ? 3 : 2) * GW * 64; idx += nthreads) {
       const int q = idx >> 6, ln = idx & 63, mm = ln & 31, hh = ln >> 5;
@@ -257,7 +272,7 @@ __device__ __forceinline__ void gm_build_image(const GmArgs &g, const float *__r
         }
         v[e] = (j < g.out_dim && k < K) ? W[j * K + k] : 0.0f;
       }
-      if (compact && q < 2 * GW) {
+      if (C && q < 2 * GW) {
         if (mm < 2) {
           uint32_t p[3][8];
 #pragma unroll
@@ -268,13 +283,13 @@ __device__ __forceinline__ void gm_build_image(const GmArgs &g, const float *__r
                                                              bt::pk(p[c][4], p[c][5]), bt::pk(p[c][6], p[c][7]));
         }
       } else {
-        put_group(g0 + (q < 2 * GW ? gm_fo(GW, NL) + q : (compact ? cp_bo(GW, NL) : gm_bo(GW, NL)) + (q - 2 * GW)), ln, v);
+        put_group(g0 + (q < 2 * GW ? gm_fo(GW, NL) + q : gm_bo(C, GW, NL) + (q - 2 * GW)), ln, v);
       }
     }
   }
 #pragma unroll
   for (int l = 1; l <= NL; ++l) {
-    const int N = Nof(l), K = Kof(l);
+    const int N = gm_N<NL>(g, l), K = gm_K(g, l);
     for (int u = threadIdx.x; u < 32 * GW; u += nthreads) bias_out[(l - 1) * 32 * GW + u] = u < N ? src[g.off[l] + N * K + u] : 0.0f;
   }
 }
@@ -372,6 +387,152 @@ __device__ __forceinline__ void gm_sample_terms(const GmArgs &g, float z0, float
   }
 }
 
+// ================================================================================================
+// What the two kernels below share around their chains.  Each keeps its accumulator set, its forward, backward
+// and weight-gradient chains and its assignment of tiles to waves.
+// ================================================================================================
+// a lane's place in the walk: its sample column and register half, the sample and tile counts
+struct GmLane {
+  int m, kb;
+  uint32_t B32, plane32;
+  size_t n_tiles;
+};
+
+// the operands of tile t (branch-free: padding lanes, and every lane of a tile past the last, read sample B - 1 and are
+// zeroed)
+template <int MODE>
+__device__ __forceinline__ TileIn gm_load_tile(const TrajDev &tr, const GmArgs &g, const float *lp0, const GmLane &w, size_t t) {
+  TileIn o;
+  const uint32_t sidx = (uint32_t)t * 32u + (uint32_t)w.m;
+  o.valid = t < w.n_tiles && sidx < w.B32;
+  const uint32_t sc = o.valid ? sidx : w.B32 - 1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int k = 4 * w.kb + e;
+    float v = 0.0f;
+    if (k < g.in_dim) v = tr.obs[(uint32_t)k * w.plane32 + sc];
+    else if (k == g.in_dim) v = 1.0f;
+    o.x[e] = o.valid ? v : 0.0f;
+  }
+  o.tgt = o.adv = o.l0 = o.l1 = 0.0f;
+  o.act = 0;
+  if (MODE == GM_CRITIC) {
+    const float tg = tr.tgt[sc];
+    o.tgt = o.valid ? tg : 0.0f;
+  } else if (MODE != PASS_JVP) {
+    const float adv = tr.adv[sc];
+    const int act = (int)tr.action[sc];
+    o.adv = o.valid ? adv : 0.0f;
+    o.act = o.valid ? act : 0;
+    if (MODE != PASS_INIT) {
+      const float l0 = lp0[sc], l1 = lp0[w.B32 + sc];
+      o.l0 = o.valid ? l0 : 0.0f;
+      o.l1 = o.valid ? l1 : 0.0f;
+    }
+  }
+  return o;
+}
+
+// the B operand pieces of the input tile: the lane's four inputs (bias input included), by truncation
+__device__ __forceinline__ void gm_input_pieces(const TileIn &op, Frag (&xb0)[1][3]) {
+  uint32_t p[3][4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) bt::split3t(op.x[e], p[0][e], p[1][e], p[2][e]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    xb0[0][c].u[0] = bt::pkh(p[c][0], p[c][1]);
+    xb0[0][c].u[1] = bt::pkh(p[c][2], p[c][3]);
+    xb0[0][c].u[2] = xb0[0][c].u[3] = 0u;
+  }
+}
+// ... and of the output layer's deltas (units 0 and 1 = elements 0 and 1 of half 0's k-step 0), by rounding
+__device__ __forceinline__ void gm_delta_pieces(float d0, float d1, int kb, Frag (&dob)[1][3]) {
+  uint32_t p0[3], p1[3];
+  bt::split3(d0, p0[0], p0[1], p0[2]);
+  bt::split3(d1, p1[0], p1[1], p1[2]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    dob[0][c].u[0] = kb == 0 ? bt::pk(p0[c], p1[c]) : 0u;
+    dob[0][c].u[1] = dob[0][c].u[2] = dob[0][c].u[3] = 0u;
+  }
+}
+
+// The slab row of a wave, or of a pair (its two waves fill disjoint entries): one f64 entry per parameter.
+struct GmRow {
+  double *p;
+  bool first;  // nothing flushed yet: an entry is stored, not added to
+  __device__ __forceinline__ void put(uint32_t at, float v) const {
+    if (first) p[at] = (double)v;
+    else p[at] = p[at] + (double)v;
+  }
+};
+// slab entry += tile entry for the valid (output j, input k) of weight tile (ot, it) of layer l (layer 0: and its bias,
+// the input behind the last); the tile is cleared
+template <int NL>
+__device__ __forceinline__ void gm_flush_w(const GmArgs &g, const GmRow &row, int m, int kb, f32x16 &t, int l, int ot, int it) {
+  // (the lane's column through a register the optimiser cannot see through: with a visible one, the ~100 slab addresses
+  // and bounds of a flush are loop-invariant, get computed ahead of the tile loop and live in scratch until the flush —
+  // ~1 KB per lane written and read back by every launch: 270 MB at 16,384 x 128 samples)
+  int mo = m, kbo = kb;
+  asm volatile("" : "+v"(mo), "+v"(kbo));
+  const int K = gm_K(g, l), N = gm_N<NL>(g, l), k = it * 32 + mo;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int j = ot * 32 + urow(r, kbo);
+    if (j < N) {
+      if (k < K) row.put(g.off[l] + (uint32_t)(j * K + k), t[r]);
+      else if (l == 0 && k == K) row.put(g.off[0] + (uint32_t)(N * K + j), t[r]);
+    }
+    t[r] = 0.0f;
+  }
+  // (the slab updates of one tile at a time: hoisting every load of the flush above the first store needs ~400 more
+  // registers than the kernel has)
+  __builtin_amdgcn_sched_barrier(0);
+}
+// f32 -> f64 fold of the scalar sums
+__device__ __forceinline__ void gm_fold(double (&sum64)[3], float (&sum32)[3]) {
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    sum64[q] += (double)sum32[q];
+    sum32[q] = 0.0f;
+  }
+}
+// the rest of a flush, behind the weight tiles: the biases of layers 1 .. NL — column c = (l - 1) GW + ot of the bias
+// tile, flushed by the wave that owns(l, ot) — and the scalar sums
+template <int NL, int GW, class Owns>
+__device__ __forceinline__ void gm_flush_rest(const GmArgs &g, GmRow &row, int m, int kb, f32x16 &dbt, double (&sum64)[3],
+                                              float (&sum32)[3], Owns owns) {
+#pragma unroll
+  for (int l = 1; l <= NL; ++l) {
+    int mo = m, kbo = kb;
+    asm volatile("" : "+v"(mo), "+v"(kbo));  // (as in gm_flush_w)
+    const int N = gm_N<NL>(g, l), K = gm_K(g, l), ot = mo - (l - 1) * GW;
+    if (owns(l, ot)) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int j = ot * 32 + urow(r, kbo);
+        if (j < N) row.put(g.off[l] + (uint32_t)(N * K + j), dbt[r]);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) dbt[r] = 0.0f;
+  gm_fold(sum64, sum32);
+  row.first = false;
+}
+// the scalar sums of a walk: over the wave's 32 owner lanes, into row `id` of slabB
+__device__ __forceinline__ void gm_store_sums(double (&sum64)[3], int kb, int lane, double *slabB, size_t id) {
+#pragma unroll
+  for (int q = 0; q < 3; ++q) sum64[q] = bt::owner_sum(sum64[q], kb);
+  if (lane == 0) {
+    double *sb = slabB + id * 4;
+    sb[0] = sum64[0];
+    sb[1] = sum64[1];
+    sb[2] = sum64[2];
+    sb[3] = 0.0;
+  }
+}
+
 template <int MODE, int NL, int GW>
 __global__ void __launch_bounds__(GWAVES * 64)
     k_gen_mfma(TrajDev tr, GmArgs g, float *__restrict__ lp0, double *__restrict__ slabA, double *__restrict__ slabB,
@@ -379,18 +540,16 @@ __global__ void __launch_bounds__(GWAVES * 64)
   extern __shared__ uint4 gm_lds[];
   uint4(*img)[64] = reinterpret_cast<uint4(*)[64]>(gm_lds);
   constexpr bool JVP = MODE == PASS_JVP;
-  constexpr int TG = gm_groups(GW, NL);  // first fragment group of the tangent parameters (JVP)
-  float *bias = reinterpret_cast<float *>(gm_lds + (size_t)gm_all_groups(GW, NL, JVP) * 3 * 64);  // [NL][32 GW]: layers 1 .. NL
+  constexpr int TG = gm_groups(false, GW, NL);  // first fragment group of the tangent parameters (JVP)
+  float *bias = reinterpret_cast<float *>(gm_lds + (size_t)gm_all_groups(false, GW, NL, JVP) * 3 * 64);  // [NL][32 GW]: layers 1 .. NL
   float *tbias = bias + NL * 32 * GW;                                                               // (JVP) of the tangent
   constexpr bool BWD = MODE != PASS_EVAL;
   if (skip != nullptr && *skip != 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m = lane & 31, kb = lane >> 5;
-  auto Kof = [&](int l) { return l == 0 ? g.in_dim : g.width[l - 1]; };
-  auto Nof = [&](int l) { return l == NL ? g.out_dim : g.width[l]; };
 
-  gm_build_image<NL, GW>(g, g.params, img, 0, true, bias, GWAVES * 64);
-  if (JVP) gm_build_image<NL, GW>(g, g.tangent, img, TG, false, tbias, GWAVES * 64);
+  gm_build_image<false, NL, GW>(g, g.params, img, 0, true, bias, GWAVES * 64);
+  if (JVP) gm_build_image<false, NL, GW>(g, g.tangent, img, TG, false, tbias, GWAVES * 64);
   __syncthreads();
 
   Frag idb[2];
@@ -416,34 +575,9 @@ __global__ void __launch_bounds__(GWAVES * 64)
   const size_t n_tiles = (B + 31) / 32;
   const size_t wave_id = (size_t)blockIdx.x * GWAVES + wave, n_waves = (size_t)gridDim.x * GWAVES;
   if (wave_id >= n_tiles) return;  // (no barrier below; the launcher counts slab rows for the waves that have tiles)
-  double *__restrict__ row = slabA + wave_id * g.P;
-  bool first_flush = true;
-
-  // slab entry += tile entry, for the valid (output j, input k) of a weight tile / the bias columns
-  auto put = [&](uint32_t at, float v) {
-    if (first_flush) row[at] = (double)v;
-    else row[at] = row[at] + (double)v;
-  };
-  auto flush_w = [&](f32x16 &t, int l, int ot, int it) {
-    // (the lane's column through a register the optimiser cannot see through: with a visible one, the ~100 slab addresses
-    // and bounds of a flush are loop-invariant, get computed ahead of the tile loop and live in scratch until the flush —
-    // ~1 KB per lane written and read back by every launch: 270 MB at 16,384 x 128 samples)
-    int mo = m, kbo = kb;
-    asm volatile("" : "+v"(mo), "+v"(kbo));
-    const int K = Kof(l), N = Nof(l), k = it * 32 + mo;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int j = ot * 32 + urow(r, kbo);
-      if (j < N) {
-        if (k < K) put(g.off[l] + (uint32_t)(j * K + k), t[r]);
-        else if (l == 0 && k == K) put(g.off[0] + (uint32_t)(N * K + j), t[r]);
-      }
-      t[r] = 0.0f;
-    }
-    // (the slab updates of one tile at a time: hoisting every load of the flush above the first store needs ~400 more
-    // registers than the kernel has)
-    __builtin_amdgcn_sched_barrier(0);
-  };
+  const GmLane w{m, kb, B32, plane32, n_tiles};
+  GmRow row{slabA + wave_id * g.P, true};
+  auto flush_w = [&](f32x16 &t, int l, int ot, int it) { gm_flush_w<NL>(g, row, m, kb, t, l, ot, it); };
   auto flush_all = [&]() {
 #pragma unroll
     for (int ot = 0; ot < GW; ++ot) flush_w(dW0[ot], 0, ot, 0);
@@ -455,61 +589,9 @@ __global__ void __launch_bounds__(GWAVES * 64)
         for (int it = 0; it < GW; ++it) flush_w(dWh[l - 1][ot][it], l, ot, it);
 #pragma unroll
     for (int it = 0; it < GW; ++it) flush_w(dWo[it], NL, 0, it);
-    // biases of layers 1 .. NL: column c = (l - 1) GW + ot of the bias tile
-#pragma unroll
-    for (int l = 1; l <= NL; ++l) {
-      int mo = m, kbo = kb;
-      asm volatile("" : "+v"(mo), "+v"(kbo));
-      const int N = Nof(l), K = Kof(l), ot = mo - (l - 1) * GW;
-      if (ot >= 0 && ot < (l < NL ? GW : 1)) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = ot * 32 + urow(r, kbo);
-          if (j < N) put(g.off[l] + (uint32_t)(N * K + j), dbt[r]);
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dbt[r] = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      sum64[q] += (double)sum32[q];
-      sum32[q] = 0.0f;
-    }
-    first_flush = false;
+    gm_flush_rest<NL, GW>(g, row, m, kb, dbt, sum64, sum32, [](int l, int ot) { return ot >= 0 && ot < (l < NL ? GW : 1); });
   };
-
-  auto load_tile = [&](size_t t) {  // (branch-free: padding lanes read sample B - 1 and are zeroed)
-    TileIn o;
-    const uint32_t sidx = (uint32_t)t * 32u + (uint32_t)m;
-    o.valid = t < n_tiles && sidx < B32;
-    const uint32_t sc = o.valid ? sidx : B32 - 1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int k = 4 * kb + e;
-      float v = 0.0f;
-      if (k < g.in_dim) v = tr.obs[(uint32_t)k * plane32 + sc];
-      else if (k == g.in_dim) v = 1.0f;
-      o.x[e] = o.valid ? v : 0.0f;
-    }
-    o.tgt = o.adv = o.l0 = o.l1 = 0.0f;
-    o.act = 0;
-    if (MODE == GM_CRITIC) {
-      const float tg = tr.tgt[sc];
-      o.tgt = o.valid ? tg : 0.0f;
-    } else if (!JVP) {
-      const float adv = tr.adv[sc];
-      const int act = (int)tr.action[sc];
-      o.adv = o.valid ? adv : 0.0f;
-      o.act = o.valid ? act : 0;
-      if (MODE != PASS_INIT) {
-        const float l0 = lp0[sc], l1 = lp0[B32 + sc];
-        o.l0 = o.valid ? l0 : 0.0f;
-        o.l1 = o.valid ? l1 : 0.0f;
-      }
-    }
-    return o;
-  };
+  auto load_tile = [&](size_t t) { return gm_load_tile<MODE>(tr, g, lp0, w, t); };
 
   int since_flush = 0;
   TileIn op = load_tile(wave_id);
@@ -517,17 +599,7 @@ __global__ void __launch_bounds__(GWAVES * 64)
     const TileIn next = load_tile(t + n_waves);
     // ---- forward
     Frag xb0[1][3];
-    {
-      uint32_t p[3][4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bt::split3t(op.x[e], p[0][e], p[1][e], p[2][e]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        xb0[0][c].u[0] = bt::pkh(p[c][0], p[c][1]);
-        xb0[0][c].u[1] = bt::pkh(p[c][2], p[c][3]);
-        xb0[0][c].u[2] = xb0[0][c].u[3] = 0u;
-      }
-    }
+    gm_input_pieces(op, xb0);
     // (JVP: the tangent of every layer rides along, ta_l = act'(.) (W_l ta_{l-1} + V_l a_{l-1} + vb_l), ta_{-1} = 0 —
     // forward-mode differentiation along the tangent parameters V, conjugate_gradient.rs:262-339)
     f32x16 a[NL][GW], ta[GW];
@@ -600,18 +672,9 @@ __global__ void __launch_bounds__(GWAVES * 64)
     gm_sample_terms<MODE>(g, zt[0], zt[1], tzt[0], tzt[1], op, kb == 0 && op.valid, true, inv_B, clip_lo, clip_hi, lp0,
                           (uint32_t)t * 32u + (uint32_t)m, B32, sum32, d0, d1);
     if (BWD) {
-      // ---- output layer: delta pieces (units 0 and 1 = elements 0 and 1 of half 0's k-step 0)
+      // ---- output layer
       Frag dob[1][3];
-      {
-        uint32_t p0[3], p1[3];
-        bt::split3(d0, p0[0], p0[1], p0[2]);
-        bt::split3(d1, p1[0], p1[1], p1[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          dob[0][c].u[0] = kb == 0 ? bt::pk(p0[c], p1[c]) : 0u;
-          dob[0][c].u[1] = dob[0][c].u[2] = dob[0][c].u[3] = 0u;
-        }
-      }
+      gm_delta_pieces(d0, d1, kb, dob);
       Frag dT[GW][2][3], aT[GW][2][3];  // transposed pieces: deltas of the layer in hand, activations below it
       transpose_pieces<1>(dob, idb, dT[0]);
       dbt = bias_tile(dbt, dT[0], (NL - 1) * GW, m);
@@ -623,7 +686,7 @@ __global__ void __launch_bounds__(GWAVES * 64)
         for (int q = 0; q < 2; ++q) pieces_trunc(a[NL - 1][it], q, ab[q]);
         transpose_pieces<2>(ab, idb, aT[it]);
         dWo[it] = wgrad_tile(dWo[it], dT[0], aT[it]);
-        f32x16 c = prod6_lds(zero16, img, gm_bo(GW, NL) + it, lane, dob[0]);
+        f32x16 c = prod6_lds(zero16, img, gm_bo(false, GW, NL) + it, lane, dob[0]);
         gm_slope_tile(g.act, c, a[NL - 1][it]);
         dl[it] = c;
       }
@@ -650,7 +713,7 @@ __global__ void __launch_bounds__(GWAVES * 64)
           f32x16 c = zero16;
 #pragma unroll
           for (int ks = 0; ks < 2 * GW; ++ks)
-            c = prod6_lds(c, img, gm_bh(GW, NL, l) + it * 2 * GW + ks, lane, db[ks >> 1][ks & 1]);
+            c = prod6_lds(c, img, gm_bh(false, GW, NL, l) + it * 2 * GW + ks, lane, db[ks >> 1][ks & 1]);
           gm_slope_tile(g.act, c, a[l - 1][it]);
           dn[it] = c;
         }
@@ -672,28 +735,12 @@ __global__ void __launch_bounds__(GWAVES * 64)
     // tiles and after the wave's last tile
     if (++since_flush == GM_FLUSH || t + n_waves >= n_tiles) {
       since_flush = 0;
-      if (BWD) {
-        flush_all();
-      } else {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          sum64[q] += (double)sum32[q];
-          sum32[q] = 0.0f;
-        }
-      }
+      if (BWD) flush_all();
+      else gm_fold(sum64, sum32);
     }
     op = next;
   }
-  // the wave's scalar sums: over its 32 owner lanes
-#pragma unroll
-  for (int q = 0; q < 3; ++q) sum64[q] = bt::owner_sum(sum64[q], kb);
-  if (lane == 0) {
-    double *sb = slabB + wave_id * 4;
-    sb[0] = sum64[0];
-    sb[1] = sum64[1];
-    sb[2] = sum64[2];
-    sb[3] = 0.0;
-  }
+  gm_store_sums(sum64, kb, lane, slabB, wave_id);
 }
 
 // ================================================================================================
@@ -711,32 +758,28 @@ __global__ void __launch_bounds__(GWAVES * 64)
 // One exchange region per wave: write, barrier, the partner reads; the next barrier in program order (there is always
 // one before the region's next write) guards the reuse.
 // ================================================================================================
-constexpr int GP_PAIRS = 4;
-
 template <int MODE, int NL, int PAIRS>
 __global__ void __launch_bounds__(PAIRS * 128)
     k_gen_pair(TrajDev tr, GmArgs g, float *__restrict__ lp0, double *__restrict__ slabA, double *__restrict__ slabB,
                float inv_B, const int32_t *__restrict__ skip, float clip_lo, float clip_hi) {
   constexpr int GW = 2;
   constexpr bool JVP = MODE == PASS_JVP, BWD = MODE != PASS_EVAL;
-  constexpr int TG = cp_groups(GW, NL);                                  // first fragment group of the tangent (JVP)
-  constexpr int NG = TG + (JVP ? cp_tan_groups(GW, NL) : 0);             // groups of the image
+  constexpr int TG = gm_groups(true, GW, NL);                             // first fragment group of the tangent (JVP)
+  constexpr int NG = gm_all_groups(true, GW, NL, JVP);                    // groups of the image
   constexpr int ZV = JVP ? 4 : 2;                                         // partial outputs a wave hands over per sample
   extern __shared__ uint4 gm_lds[];
   uint4(*img)[64] = reinterpret_cast<uint4(*)[64]>(gm_lds);
   uint4 *outc = gm_lds + (size_t)NG * 3 * 64;                             // compact output-layer forward fragments ...
-  uint4 *toutc = outc + 2 * GW * 3 * 4;                                   // ... and the tangent's
-  float *bias = reinterpret_cast<float *>(toutc + (JVP ? 2 * GW * 3 * 4 : 0));  // [NL][64]: layers 1 .. NL
+  uint4 *toutc = outc + gm_outc_entries(GW);                              // ... and the tangent's
+  float *bias = reinterpret_cast<float *>(toutc + (JVP ? gm_outc_entries(GW) : 0));  // [NL][64]: layers 1 .. NL
   float *tbias = bias + NL * 64;                                                 // (JVP) of the tangent
   uint4(*xch)[64] = reinterpret_cast<uint4(*)[64]>(bias + NL * 64 * (JVP ? 2 : 1));  // [PAIRS][2][6][64]
   float *zbuf = reinterpret_cast<float *>(xch + PAIRS * 2 * 6);                         // [PAIRS][2][ZV][32]
   if (skip != nullptr && *skip != 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m = lane & 31, kb = lane >> 5, pair = wave >> 1, h = wave & 1;
-  auto Kof = [&](int l) { return l == 0 ? g.in_dim : g.width[l - 1]; };
-  auto Nof = [&](int l) { return l == NL ? g.out_dim : g.width[l]; };
-  gm_build_image<NL, GW>(g, g.params, img, 0, true, bias, PAIRS * 128, outc);
-  if (JVP) gm_build_image<NL, GW>(g, g.tangent, img, TG, false, tbias, PAIRS * 128, toutc);
+  gm_build_image<true, NL, GW>(g, g.params, img, 0, true, bias, PAIRS * 128, outc);
+  if (JVP) gm_build_image<true, NL, GW>(g, g.tangent, img, TG, false, tbias, PAIRS * 128, toutc);
   __syncthreads();
 
   Frag idb[2];
@@ -757,25 +800,20 @@ __global__ void __launch_bounds__(PAIRS * 128)
   const size_t n_tiles = (B + 31) / 32;
   const size_t pair_id = (size_t)blockIdx.x * PAIRS + pair, n_pairs = (size_t)gridDim.x * PAIRS;
   const size_t iters = (n_tiles + n_pairs - 1) / n_pairs;
-  double *__restrict__ row = slabA + pair_id * g.P;  // the pair's row: the two waves fill disjoint entries
-  bool first_flush = true;
-  auto put = [&](uint32_t at, float v) {
-    if (first_flush) row[at] = (double)v;
-    else row[at] = row[at] + (double)v;
-  };
+  const GmLane w{m, kb, B32, plane32, n_tiles};
+  GmRow row{slabA + pair_id * g.P, true};  // the pair's row
+  // (gm_flush_w, written out: through the function the NL = 3 instantiations of this kernel get another register
+  // allocation — 4 bytes less scratch than they had)
   auto flush_w = [&](f32x16 &t, int l, int ot, int it) {
-    // (the lane's column through a register the optimiser cannot see through: with a visible one, the ~100 slab addresses
-    // and bounds of a flush are loop-invariant, get computed ahead of the tile loop and live in scratch until the flush —
-    // ~1 KB per lane written and read back by every launch: 270 MB at 16,384 x 128 samples)
     int mo = m, kbo = kb;
     asm volatile("" : "+v"(mo), "+v"(kbo));
-    const int K = Kof(l), N = Nof(l), k = it * 32 + mo;
+    const int K = gm_K(g, l), N = gm_N<NL>(g, l), k = it * 32 + mo;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int j = ot * 32 + urow(r, kbo);
       if (j < N) {
-        if (k < K) put(g.off[l] + (uint32_t)(j * K + k), t[r]);
-        else if (l == 0 && k == K) put(g.off[0] + (uint32_t)(N * K + j), t[r]);
+        if (k < K) row.put(g.off[l] + (uint32_t)(j * K + k), t[r]);
+        else if (l == 0 && k == K) row.put(g.off[0] + (uint32_t)(N * K + j), t[r]);
       }
       t[r] = 0.0f;
     }
@@ -789,59 +827,10 @@ __global__ void __launch_bounds__(PAIRS * 128)
       flush_w(dWoth[l - 1], l, h, 1 - h);
     }
     flush_w(dWo, NL, 0, h);
-#pragma unroll
-    for (int l = 1; l <= NL; ++l) {  // bias column (l - 1) GW + ot: this wave's tile of a hidden layer; wave 0: the outputs
-      int mo = m, kbo = kb;
-      asm volatile("" : "+v"(mo), "+v"(kbo));
-      const int N = Nof(l), K = Kof(l), ot = mo - (l - 1) * GW;
-      if (l < NL ? ot == h : (ot == 0 && h == 0)) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = ot * 32 + urow(r, kbo);
-          if (j < N) put(g.off[l] + (uint32_t)(N * K + j), dbt[r]);
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dbt[r] = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      sum64[q] += (double)sum32[q];
-      sum32[q] = 0.0f;
-    }
-    first_flush = false;
+    // (bias columns: this wave's tile of a hidden layer; wave 0: the outputs)
+    gm_flush_rest<NL, GW>(g, row, m, kb, dbt, sum64, sum32, [&](int l, int ot) { return l < NL ? ot == h : (ot == 0 && h == 0); });
   };
-  auto load_tile = [&](size_t t) {  // (branch-free: padding lanes read sample B - 1 and are zeroed)
-    TileIn o;
-    const uint32_t sidx = (uint32_t)t * 32u + (uint32_t)m;
-    o.valid = t < n_tiles && sidx < B32;
-    const uint32_t sc = o.valid ? sidx : B32 - 1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int k = 4 * kb + e;
-      float v = 0.0f;
-      if (k < g.in_dim) v = tr.obs[(uint32_t)k * plane32 + sc];
-      else if (k == g.in_dim) v = 1.0f;
-      o.x[e] = o.valid ? v : 0.0f;
-    }
-    o.tgt = o.adv = o.l0 = o.l1 = 0.0f;
-    o.act = 0;
-    if (MODE == GM_CRITIC) {
-      const float tg = tr.tgt[sc];
-      o.tgt = o.valid ? tg : 0.0f;
-    } else if (!JVP) {
-      const float adv = tr.adv[sc];
-      const int act = (int)tr.action[sc];
-      o.adv = o.valid ? adv : 0.0f;
-      o.act = o.valid ? act : 0;
-      if (MODE != PASS_INIT) {
-        const float l0 = lp0[sc], l1 = lp0[B32 + sc];
-        o.l0 = o.valid ? l0 : 0.0f;
-        o.l1 = o.valid ? l1 : 0.0f;
-      }
-    }
-    return o;
-  };
+  auto load_tile = [&](size_t t) { return gm_load_tile<MODE>(tr, g, lp0, w, t); };
   auto bias_rows = [&](const float *table, int l) {  // accumulator of this wave's tile initialised with its units' biases
     f32x16 c;
 #pragma unroll
@@ -877,17 +866,7 @@ __global__ void __launch_bounds__(PAIRS * 128)
     const TileIn next = load_tile(t + n_pairs);
     // ---- forward: this wave's unit tile of every layer
     Frag xb0[1][3];
-    {
-      uint32_t p[3][4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bt::split3t(op.x[e], p[0][e], p[1][e], p[2][e]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        xb0[0][c].u[0] = bt::pkh(p[c][0], p[c][1]);
-        xb0[0][c].u[1] = bt::pkh(p[c][2], p[c][3]);
-        xb0[0][c].u[2] = xb0[0][c].u[3] = 0u;
-      }
-    }
+    gm_input_pieces(op, xb0);
     // (JVP: the tangent rides along, ta_l = act'(.) (W_l ta_{l-1} + V_l a_{l-1} + vb_l), as in the one-wave kernel)
     f32x16 a[NL], ta = zero16;
     a[0] = prod6_lds(zero16, img, h, lane, xb0[0]);
@@ -978,16 +957,7 @@ __global__ void __launch_bounds__(PAIRS * 128)
                           (uint32_t)t * 32u + (uint32_t)m, B32, sum32, d0, d1);
     if (BWD) {
       Frag dob[1][3];
-      {
-        uint32_t p0[3], p1[3];
-        bt::split3(d0, p0[0], p0[1], p0[2]);
-        bt::split3(d1, p1[0], p1[1], p1[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          dob[0][c].u[0] = kb == 0 ? bt::pk(p0[c], p1[c]) : 0u;
-          dob[0][c].u[1] = dob[0][c].u[2] = dob[0][c].u[3] = 0u;
-        }
-      }
+      gm_delta_pieces(d0, d1, kb, dob);
       Frag dT[2][3], aT[2][3];  // transposed pieces: the deltas in hand, the activations below them
       transpose_pieces<1>(dob, idb, dT);
       if (h == 0) dbt = bias_tile(dbt, dT, (NL - 1) * GW, m);
@@ -998,7 +968,7 @@ __global__ void __launch_bounds__(PAIRS * 128)
         for (int q = 0; q < 2; ++q) pieces_trunc(a[NL - 1], q, ab[q]);
         transpose_pieces<2>(ab, idb, aT);
         dWo = wgrad_tile(dWo, dT, aT);
-        dl = prod6_lds(zero16, img, cp_bo(GW, NL) + h, lane, dob[0]);
+        dl = prod6_lds(zero16, img, gm_bo(true, GW, NL) + h, lane, dob[0]);
         gm_slope_tile(g.act, dl, a[NL - 1]);
       }
 #pragma unroll
@@ -1014,11 +984,11 @@ __global__ void __launch_bounds__(PAIRS * 128)
           transpose_pieces<2>(pc, idb, dT);
           dbt = bias_tile(dbt, dT, (l - 1) * GW + h, m);
 #pragma unroll
-          for (int q = 0; q < 2; ++q) c = prod6_lds(c, img, cp_bh(GW, NL, l) + h * 2 * GW + h * 2 + q, lane, pc[q]);
+          for (int q = 0; q < 2; ++q) c = prod6_lds(c, img, gm_bh(true, GW, NL, l) + h * 2 * GW + h * 2 + q, lane, pc[q]);
           __syncthreads();
           xget(pc);
 #pragma unroll
-          for (int q = 0; q < 2; ++q) c = prod6_lds(c, img, cp_bh(GW, NL, l) + h * 2 * GW + (1 - h) * 2 + q, lane, pc[q]);
+          for (int q = 0; q < 2; ++q) c = prod6_lds(c, img, gm_bh(true, GW, NL, l) + h * 2 * GW + (1 - h) * 2 + q, lane, pc[q]);
         }
         gm_slope_tile(g.act, c, a[l - 1]);
         // weight gradients of layer l: this wave's output units against its own input tile, then the partner's
@@ -1049,83 +1019,53 @@ __global__ void __launch_bounds__(PAIRS * 128)
     __syncthreads();  // the exchange regions are free for the next tile
     if (++since_flush == GM_FLUSH || it_ + 1 == iters) {
       since_flush = 0;
-      if (BWD) {
-        flush_all();
-      } else {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          sum64[q] += (double)sum32[q];
-          sum32[q] = 0.0f;
-        }
-      }
+      if (BWD) flush_all();
+      else gm_fold(sum64, sum32);
     }
     op = next;
   }
   if (h != 0) return;  // the scalar sums live on wave 0 of the pair
-#pragma unroll
-  for (int q = 0; q < 3; ++q) sum64[q] = bt::owner_sum(sum64[q], kb);
-  if (lane == 0) {
-    double *sb = slabB + pair_id * 4;
-    sb[0] = sum64[0];
-    sb[1] = sum64[1];
-    sb[2] = sum64[2];
-    sb[3] = 0.0;
-  }
+  gm_store_sums(sum64, kb, lane, slabB, pair_id);
 }
 
-constexpr size_t gp_lds_bytes(int NL, int pairs, bool jvp) {
-  return (size_t)(cp_groups(2, NL) + (jvp ? cp_tan_groups(2, NL) : 0)) * 3 * 64 * 16 + (size_t)(jvp ? 2 : 1) * 4 * 3 * 4 * 16 +
-         (size_t)NL * 64 * 4 * (jvp ? 2 : 1) + (size_t)pairs * 2 * 6 * 64 * 16 + (size_t)pairs * 2 * (jvp ? 4 : 2) * 32 * 4;
-}
-
-template <int MODE, int NL>
-void gp_launch(rl_traj *t, const GmArgs &g, uint32_t nwg, float inv_B, const int32_t *d_skip, float clip_lo, float clip_hi) {
-  const size_t lds = gp_lds_bytes(NL, GP_PAIRS, MODE == PASS_JVP);
-  {
-    static std::mutex mu;
-    static std::set<int> raised;
-    std::lock_guard<std::mutex> lock(mu);
-    if (raised.insert(t->eng->device).second)
-      RL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gen_pair<MODE, NL, GP_PAIRS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  hipLaunchKernelGGL((k_gen_pair<MODE, NL, GP_PAIRS>), dim3(nwg), dim3(GP_PAIRS * 128), lds, t->eng->stream, t->d, g, t->lp0,
-                     t->slabA, t->slabB, inv_B, d_skip, clip_lo, clip_hi);
-  RL_HIP_CHECK(hipGetLastError());
-}
-template <int MODE>
-void gp_launch_nl(rl_traj *t, const GmArgs &g, int NL, uint32_t nwg, float inv_B, const int32_t *d_skip, float clip_lo,
-                  float clip_hi) {
-  if (NL == 1) gp_launch<MODE, 1>(t, g, nwg, inv_B, d_skip, clip_lo, clip_hi);
-  else if (NL == 2) gp_launch<MODE, 2>(t, g, nwg, inv_B, d_skip, clip_lo, clip_hi);
-  else gp_launch<MODE, 3>(t, g, nwg, inv_B, d_skip, clip_lo, clip_hi);
-}
-
+// Both kernels take the same arguments.  The kernel of (mode, NL, gw) — gw = 4: one hidden layer of up to 128 units;
+// gw = 2: up to three of up to 64 — is the pair kernel where `pair` (gw = 2 and a gradient mode or the JVP), else the
+// one-wave kernel: the one mode -> template dispatch.
+using GmKernel = void (*)(TrajDev, GmArgs, float *, double *, double *, float, const int32_t *, float, float);
 template <int MODE, int NL, int GW>
-void gm_launch(rl_traj *t, const GmArgs &g, uint32_t nwg, float inv_B, const int32_t *d_skip, float clip_lo,
-               float clip_hi) {
-  const size_t lds = gm_lds_bytes(GW, NL, MODE == PASS_JVP);
-  {
-    static std::mutex mu;
-    static std::set<int> raised;
-    std::lock_guard<std::mutex> lock(mu);
-    if (raised.insert(t->eng->device).second)
-      RL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gen_mfma<MODE, NL, GW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  hipLaunchKernelGGL((k_gen_mfma<MODE, NL, GW>), dim3(nwg), dim3(GWAVES * 64), lds, t->eng->stream, t->d, g, t->lp0,
-                     t->slabA, t->slabB, inv_B, d_skip, clip_lo, clip_hi);
-  RL_HIP_CHECK(hipGetLastError());
+GmKernel gm_kernel(bool pair) {
+  if constexpr (GW == 2 && MODE != PASS_EVAL)
+    if (pair) return &k_gen_pair<MODE, NL, GP_PAIRS>;
+  return &k_gen_mfma<MODE, NL, GW>;
+}
+template <int MODE>
+GmKernel gm_kernel_nl(int NL, int gw, bool pair) {
+  if (gw == 4) return gm_kernel<MODE, 1, 4>(pair);
+  if (NL == 1) return gm_kernel<MODE, 1, 2>(pair);
+  if (NL == 2) return gm_kernel<MODE, 2, 2>(pair);
+  return gm_kernel<MODE, 3, 2>(pair);
+}
+GmKernel gm_kernel_of(int mode, int NL, int gw, bool pair) {
+  if (mode == RL_GEN_CRITIC) return gm_kernel_nl<GM_CRITIC>(NL, gw, pair);
+  if (mode == PASS_INIT) return gm_kernel_nl<PASS_INIT>(NL, gw, pair);
+  if (mode == PASS_PPO) return gm_kernel_nl<PASS_PPO>(NL, gw, pair);
+  if (mode == PASS_JVP) return gm_kernel_nl<PASS_JVP>(NL, gw, pair);
+  return gm_kernel_nl<PASS_EVAL>(NL, gw, pair);
 }
 
-// gw = 4: one hidden layer of up to 128 units; gw = 2: up to three of up to 64
-template <int MODE>
-void gm_launch_nl(rl_traj *t, const GmArgs &g, int NL, int gw, uint32_t nwg, float inv_B, const int32_t *d_skip,
-                  float clip_lo, float clip_hi) {
-  if (gw == 4) gm_launch<MODE, 1, 4>(t, g, nwg, inv_B, d_skip, clip_lo, clip_hi);
-  else if (NL == 1) gm_launch<MODE, 1, 2>(t, g, nwg, inv_B, d_skip, clip_lo, clip_hi);
-  else if (NL == 2) gm_launch<MODE, 2, 2>(t, g, nwg, inv_B, d_skip, clip_lo, clip_hi);
-  else gm_launch<MODE, 3, 2>(t, g, nwg, inv_B, d_skip, clip_lo, clip_hi);
+// one launch; the kernel's dynamic LDS limit is raised once per device and kernel
+void gm_launch(GmKernel kernel, rl_traj *t, const GmArgs &g, uint32_t nwg, uint32_t threads, size_t lds, float inv_B,
+               const int32_t *d_skip, float clip_lo, float clip_hi) {
+  {
+    static std::mutex mu;
+    static std::set<std::pair<GmKernel, int>> raised;
+    std::lock_guard<std::mutex> lock(mu);
+    if (raised.insert({kernel, t->eng->device}).second)
+      RL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  hipLaunchKernelGGL(kernel, dim3(nwg), dim3(threads), lds, t->eng->stream, t->d, g, t->lp0, t->slabA, t->slabB, inv_B, d_skip,
+                     clip_lo, clip_hi);
+  RL_HIP_CHECK(hipGetLastError());
 }
 
 // tiles per hidden layer of the instantiation that takes the module, 0 if none does
@@ -1174,28 +1114,18 @@ bool launch_gen_mfma(rl_traj *t, const rl_mlp *m, int mode, const float *d_tange
   const int NL = (int)m->n_hidden, gw = gm_width_tiles(m);
   const float inv_B = (mode == RL_GEN_CRITIC ? 2.0f : 1.0f) / (float)B_total;
   gen_ensure(t, m, 0, false, true);  // the P-sized vectors of the update workspace follow the module
-  if (gw == 2 && mode != PASS_EVAL && gp_lds_bytes(NL, GP_PAIRS, mode == PASS_JVP) <= 160 * 1024) {
-    // a tile per pair of waves, two waves per SIMD
-    uint64_t nwg = (n_tiles + GP_PAIRS - 1) / GP_PAIRS;
-    if (nwg > cus) nwg = cus;
-    t->last_rows = (uint32_t)(nwg * GP_PAIRS);  // one slab row per pair
-    traj_ensure_slabs(t, t->last_rows, m->P, t->last_rows);
-    if (mode == RL_GEN_CRITIC) gp_launch_nl<GM_CRITIC>(t, g, NL, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
-    else if (mode == PASS_INIT) gp_launch_nl<PASS_INIT>(t, g, NL, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
-    else if (mode == PASS_PPO) gp_launch_nl<PASS_PPO>(t, g, NL, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
-    else gp_launch_nl<PASS_JVP>(t, g, NL, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
-    return true;
-  }
+  const bool jvp = mode == PASS_JVP;
+  // a tile per pair of waves, two waves per SIMD, where that kernel is built and fits; else a tile per wave
+  const bool pair = gw == 2 && mode != PASS_EVAL && gp_lds_bytes(NL, GP_PAIRS, jvp) <= 160 * 1024;
   // (the one-wave kernel's image must fit the LDS: otherwise the caller takes the per-layer path)
-  if (gm_lds_bytes(gw, NL, mode == PASS_JVP) > 160 * 1024) return false;
-  uint64_t nwg = (n_tiles + GWAVES - 1) / GWAVES;
+  if (!pair && gm_lds_bytes(gw, NL, jvp) > 160 * 1024) return false;
+  const uint64_t walkers = pair ? GP_PAIRS : GWAVES;  // pairs or waves of a workgroup
+  uint64_t nwg = (n_tiles + walkers - 1) / walkers;
   if (nwg > cus) nwg = cus;
-  t->last_rows = (uint32_t)(nwg * GWAVES < n_tiles ? nwg * GWAVES : n_tiles);  // one slab row per wave that has tiles
+  // one slab row per pair, or per wave that has tiles
+  t->last_rows = (uint32_t)(pair || nwg * walkers < n_tiles ? nwg * walkers : n_tiles);
   traj_ensure_slabs(t, t->last_rows, m->P, t->last_rows);
-  if (mode == RL_GEN_CRITIC) gm_launch_nl<GM_CRITIC>(t, g, NL, gw, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
-  else if (mode == PASS_INIT) gm_launch_nl<PASS_INIT>(t, g, NL, gw, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
-  else if (mode == PASS_PPO) gm_launch_nl<PASS_PPO>(t, g, NL, gw, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
-  else if (mode == PASS_JVP) gm_launch_nl<PASS_JVP>(t, g, NL, gw, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
-  else gm_launch_nl<PASS_EVAL>(t, g, NL, gw, (uint32_t)nwg, inv_B, d_skip, clip_lo, clip_hi);
+  gm_launch(gm_kernel_of(mode, NL, gw, pair), t, g, (uint32_t)nwg, pair ? GP_PAIRS * 128 : GWAVES * 64,
+            pair ? gp_lds_bytes(NL, GP_PAIRS, jvp) : gm_lds_bytes(gw, NL, jvp), inv_B, d_skip, clip_lo, clip_hi);
   return true;
 }
