@@ -69,7 +69,10 @@ enum { RL_SUCC_CONTINUE = 0, RL_SUCC_TERMINATE = 1, RL_SUCC_INTERRUPT = 2 };
 enum { RL_OPT_OK = 0, RL_OPT_LOSS_NOT_IMPROVING = 1, RL_OPT_CONSTRAINT_VIOLATED = 2, RL_OPT_NAN_LOSS = 3,
        RL_OPT_NAN_CONSTRAINT = 4 };
 /* env kinds / step-limit wrappers (src/envs/cartpole.rs, chain.rs, wrappers/step_limit.rs:13,97) */
-enum { RL_ENV_CARTPOLE = 0, RL_ENV_CHAIN = 1, RL_ENV_MEMORY = 2, RL_ENV_BANDIT = 3 };
+enum { RL_ENV_CARTPOLE = 0, RL_ENV_CHAIN = 1, RL_ENV_MEMORY = 2, RL_ENV_BANDIT = 3,
+       RL_ENV_META_BANDIT = 4 /* rl_env_create_meta_bandit only (src/envs/meta.rs) */ };
+/* bandit distributions of a meta-bandit env (src/envs/bandits.rs:128-243, src/envs/testing.rs:108-160) */
+enum { RL_BANDITS_UNIFORM_BERNOULLI = 0, RL_BANDITS_ONE_HOT = 1, RL_BANDITS_ROUND_ROBIN = 2 };
 enum { RL_LIMIT_NONE = 0, RL_LIMIT_LATENT = 1, RL_LIMIT_VISIBLE = 2 };
 
 typedef struct rl_engine rl_engine;
@@ -217,6 +220,35 @@ int32_t rl_env_create(rl_engine *engine, const rl_env_config *cfg, rl_env **out)
  * else -> RL_ERR_BUILD_ENV. */
 int32_t rl_env_create_bandit(rl_engine *engine, const rl_env_config *cfg, const double *values, uint32_t n_arms,
                              rl_env **out);
+/* Meta-RL bandit lanes: `MetaEnv::new(D).wrap(TrialEpisodeLimit::new(episodes_per_trial))` (src/envs/meta.rs:128-203,
+ * 541-617) over Bandit<_> (src/envs/bandits.rs:58-78) — the env of relearn_experiments/src/bin/rl2-bandits.rs.  Every
+ * trial draws a new bandit from D; an inner episode is one arm pull (Bandit::step always terminates), the step after a
+ * pull ignores its action and starts the next inner episode (reward 0), and the pull that ends the trial's last inner
+ * episode is an Interrupt: a trial of E episodes is 2 E - 1 steps.  Observation (MetaObservationSpace, meta.rs:357-363),
+ * n_arms + 4 features: [inner observation is None] [prev_step is None] [one-hot(prev action)] [prev reward]
+ * [episode_done].  `distribution`:
+ *   RL_BANDITS_UNIFORM_BERNOULLI  UniformBernoulliBandits (bandits.rs:96-106, 170-181): n_arms means, each
+ *                                 Uniform::new_inclusive(0, 1); a pull is Bernoulli::new(mean).sample
+ *   RL_BANDITS_ONE_HOT            OneHotBandits (bandits.rs:229-243): reward 1 on the arm gen_range(0..n_arms), else 0
+ *   RL_BANDITS_ROUND_ROBIN        RoundRobinDeterministicBandits (src/envs/testing.rs:108-160): reward 1 on arm j mod
+ *                                 n_arms in a lane's j-th trial (every lane counts its own trials), no draw
+ * All draws are taken sequentially from the lane's env stream.  Discount factor 1 (bandits.rs:52-54). */
+typedef struct {
+  uint32_t n_arms;             /* 2..4: the observation has n_arms + 4 features, a trajectory at most 8 */
+  int32_t distribution;        /* RL_BANDITS_* */
+  uint64_t episodes_per_trial; /* TrialEpisodeLimit::new: > 0 (and < 2^32) */
+} rl_meta_bandit_config;
+/* UniformBernoulliBandits::default (bandits.rs:140-144) under TrialEpisodeLimit::default (meta.rs:557-564): 2 arms,
+ * RL_BANDITS_UNIFORM_BERNOULLI, 10 episodes per trial */
+int32_t rl_meta_bandit_config_default(rl_meta_bandit_config *meta);
+/* `cfg` supplies the lanes, the lane offset and the seeds, as in rl_env_create_bandit; its kind is not read.
+ * RL_ERR_BUILD_ENV: n_arms outside 2..4, episodes_per_trial == 0 (TrialEpisodeLimit::new asserts, meta.rs:548-553) or
+ * >= 2^32, an unknown distribution, a step limit in `cfg` (the trial limit is this env's limit).  rl_env_dims returns
+ * (n_arms + 4, n_arms).  Feed-forward policies of n_arms outputs roll out on it; recurrent chains on two arms (more ->
+ * RL_ERR_UNSUPPORTED from rl_rollout).  Not built, RL_ERR_UNSUPPORTED by name: rl_env_get_state / rl_env_set_state,
+ * rl_dqn_create, rl_actor_to_cbor.  An episode of rl_summary_push is a trial. */
+int32_t rl_env_create_meta_bandit(rl_engine *engine, const rl_env_config *cfg, const rl_meta_bandit_config *meta,
+                                  rl_env **out);
 int32_t rl_env_destroy(rl_env *env);
 /* number of observation features (CartPole 4, +1 `remaining` under VisibleStepLimit) and actions */
 int32_t rl_env_dims(const rl_env *env, uint32_t *obs_dim, uint32_t *n_actions);

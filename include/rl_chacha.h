@@ -101,4 +101,11 @@ RL_HDC double rl_uniform_f64_inclusive_scale(double low, double high) {
   return scale;
 }
 
+/* rand 0.8.5 `Bernoulli::new(p)` + `sample` (what `Rng::gen_bool(p)` runs): p_int = (p * 2^64) as u64 for p in [0, 1);
+ * a sample is one u64 `v` of the stream and is true when v < p_int.  p == 1.0 is ALWAYS_TRUE and draws NOTHING (the
+ * caller branches on rl_bernoulli_always(p) before it takes a u64); p == 0.0 still draws. */
+RL_HDC int rl_bernoulli_always(double p) { return p == 1.0; }
+RL_HDC uint64_t rl_bernoulli_p_int(double p) { return (uint64_t)(p * 18446744073709551616.0); }
+RL_HDC int rl_bernoulli_from_u64(uint64_t v, uint64_t p_int) { return v < p_int; }
+
 #endif /* RL_CHACHA_H */

@@ -25,7 +25,10 @@ ERR_INVALID_ARGUMENT, ERR_HIP, ERR_NO_DEVICE, ERR_BUILD_AGENT, ERR_BUILD_ENV = 1
 ERR_BUFFER_FULL, ERR_PACKING, ERR_COMM, ERR_OPT_NAN, ERR_UNSUPPORTED = 6, 7, 8, 9, 10
 SUCC_CONTINUE, SUCC_TERMINATE, SUCC_INTERRUPT = 0, 1, 2
 OPT_OK, OPT_LOSS_NOT_IMPROVING, OPT_CONSTRAINT_VIOLATED, OPT_NAN_LOSS, OPT_NAN_CONSTRAINT = range(5)
-ENV_CARTPOLE, ENV_CHAIN, ENV_MEMORY, ENV_BANDIT = 0, 1, 2, 3
+ENV_CARTPOLE, ENV_CHAIN, ENV_MEMORY, ENV_BANDIT, ENV_META_BANDIT = 0, 1, 2, 3, 4
+BANDITS_UNIFORM_BERNOULLI, BANDITS_ONE_HOT, BANDITS_ROUND_ROBIN = 0, 1, 2
+BANDIT_DISTRIBUTIONS = {"uniform_bernoulli": BANDITS_UNIFORM_BERNOULLI, "one_hot": BANDITS_ONE_HOT,
+                        "round_robin": BANDITS_ROUND_ROBIN}
 LIMIT_NONE, LIMIT_LATENT, LIMIT_VISIBLE = 0, 1, 2
 (TRAJ_OBS, TRAJ_ACTION, TRAJ_REWARD, TRAJ_FLAG, TRAJ_TERM_OBS, TRAJ_VALUES, TRAJ_ADVANTAGES,
  TRAJ_RETURNS, TRAJ_TARGETS) = range(9)
@@ -40,7 +43,7 @@ ABI_SYMBOLS = [
     "rl_last_error", "rl_engine_info", "rl_engine_set_kernel_variant", "rl_timer_begin", "rl_timer_end", "rl_profile_enable", "rl_profile_read",
     "rl_comm_available", "rl_comm_library_paths", "rl_comm_unique_id", "rl_comm_init", "rl_comm_destroy", "rl_comm_init_host",
     "rl_comm_ipc_handle", "rl_comm_init_ipc", "rl_comm_selftest",
-    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
+    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
@@ -84,6 +87,10 @@ class EnvConfig(C.Structure):
                 ("lane_offset", C.c_uint64), ("seed_env", C.c_uint64), ("seed_actor", C.c_uint64),
                 ("cartpole", CartPoleParams), ("chain_size", C.c_uint64), ("memory_num_actions", C.c_uint64),
                 ("memory_history_len", C.c_uint64), ("bandit_values", C.c_double * 2)]
+
+
+class MetaBanditConfig(C.Structure):
+    _fields_ = [("n_arms", C.c_uint32), ("distribution", C.c_int32), ("episodes_per_trial", C.c_uint64)]
 
 
 class TrpoConfig(C.Structure):
@@ -200,7 +207,7 @@ def _register(obj):
 @atexit.register
 def _close_all():
     objs = list(_live)
-    order = {"StepsSummary": -1, "Dqn": -1, "Adam": 0, "Optimizer": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "Mlp": 3, "GruMlp": 3,
+    order = {"StepsSummary": -1, "Dqn": -1, "Adam": 0, "Optimizer": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "MetaBanditEnv": 2, "Mlp": 3, "GruMlp": 3,
              "Engine": 4}
     for o in sorted(objs, key=lambda o: order.get(type(o).__name__, 2)):
         o.close()
@@ -508,6 +515,48 @@ class MemoryEnv(ChainEnv):
         """(current state, initial state, env-stream word position, steps_remaining, reset_count) per lane"""
         st, _, rem, rc = CartPoleEnv.get_state(self)
         return st[0].astype(np.uint64), st[1].astype(np.uint64), st[2].astype(np.uint64), rem, rc
+
+
+def meta_bandit_config_default():
+    m = MetaBanditConfig()
+    _check(lib().rl_meta_bandit_config_default(C.byref(m)))
+    return m
+
+
+class MetaBanditEnv(ChainEnv):
+    """N meta-RL bandit lanes (src/envs/meta.rs, bandits.rs) — `MetaEnv::new(D::new(n_arms)).wrap(TrialEpisodeLimit::
+    new(episodes_per_trial))`, D = "uniform_bernoulli" | "one_hot" | "round_robin" (or an RL_BANDITS_* integer).  Every trial
+    draws a new bandit; an inner episode is one arm pull, the step after it restarts the inner episode (action ignored,
+    reward 0), and the trial's last pull is an Interrupt: 2 * episodes_per_trial - 1 steps per trial.  Observations:
+    n_arms + 4 features [inner is None] [prev is None] [one-hot(prev action)] [prev reward] [episode_done]; 2..4 arms."""
+
+    def __init__(self, engine, n_lanes, n_arms=2, episodes_per_trial=10, distribution="uniform_bernoulli", lane_offset=0,
+                 seed_env=0, seed_actor=1, limit=LIMIT_NONE, max_steps=0):
+        self.eng = engine
+        cfg = EnvConfig()
+        cfg.kind = ENV_META_BANDIT
+        cfg.limit_kind = limit  # (a step limit is refused: the trial limit is this env's limit)
+        cfg.max_steps = max_steps
+        cfg.n_lanes = n_lanes
+        cfg.lane_offset = lane_offset
+        cfg.seed_env = seed_env
+        cfg.seed_actor = seed_actor
+        cfg.cartpole = cartpole_params_default()
+        meta = MetaBanditConfig()
+        meta.n_arms = n_arms
+        meta.distribution = BANDIT_DISTRIBUTIONS.get(distribution, distribution)
+        meta.episodes_per_trial = episodes_per_trial
+        self.cfg, self.meta = cfg, meta
+        self.h = C.c_void_p()
+        _check(lib().rl_env_create_meta_bandit(engine.h, C.byref(cfg), C.byref(meta), C.byref(self.h)), engine.h)
+        _register(self)
+        self.n = n_lanes
+        d, a = C.c_uint32(), C.c_uint32()
+        _check(lib().rl_env_dims(self.h, C.byref(d), C.byref(a)), engine.h)
+        self.D, self.A = d.value, a.value
+
+    get_state = CartPoleEnv.get_state  # (refused by the library: RL_ERR_UNSUPPORTED)
+    set_state = CartPoleEnv.set_state
 
 
 class GruMlp(_Handle):

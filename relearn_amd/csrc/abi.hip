@@ -666,13 +666,33 @@ int32_t rl_cartpole_params_default(rl_cartpole_params *p) {
 }
 
 // `arm_values` / `n_arms`: DeterministicBandit::from_values for rl_env_create_bandit (NULL: cfg->bandit_values, two arms)
-static int32_t env_create(rl_engine *e, const rl_env_config *cfg, const double *arm_values, uint32_t n_arms,
-                          rl_env **out) {
+// `meta`: rl_env_create_meta_bandit (the env kind is then RL_ENV_META_BANDIT whatever cfg->kind says)
+static int32_t env_create(rl_engine *e, const rl_env_config *cfg_in, const double *arm_values, uint32_t n_arms,
+                          const rl_meta_bandit_config *meta, rl_env **out) {
   return guarded(e, [&] {
-    RL_REQUIRE(e && cfg && out, "NULL argument");
+    RL_REQUIRE(e && cfg_in && out, "NULL argument");
     *out = nullptr;
+    rl_env_config cfg_v = *cfg_in;
+    rl_env_config *cfg = &cfg_v;
+    if (meta != nullptr) {
+      cfg->kind = RL_ENV_META_BANDIT;
+      if (meta->n_arms < 2 || meta->n_arms > RL_TRAJ_MAX_OBS_DIM - 4)
+        throw RlError(RL_ERR_BUILD_ENV, "meta-bandit lanes: 2..4 arms (the observation has n_arms + 4 features, a "
+                                        "trajectory at most 8)");
+      if (meta->episodes_per_trial == 0)  // TrialEpisodeLimit::new asserts (meta.rs:548-553)
+        throw RlError(RL_ERR_BUILD_ENV, "meta-bandit lanes: trials must contain at least 1 episode");
+      if (meta->episodes_per_trial >= (1ull << 32))
+        throw RlError(RL_ERR_BUILD_ENV, "meta-bandit lanes: episodes_per_trial must be < 2^32");
+      if (meta->distribution != RL_BANDITS_UNIFORM_BERNOULLI && meta->distribution != RL_BANDITS_ONE_HOT &&
+          meta->distribution != RL_BANDITS_ROUND_ROBIN)
+        throw RlError(RL_ERR_BUILD_ENV, "meta-bandit lanes: unknown bandit distribution");
+      if (cfg->limit_kind != RL_LIMIT_NONE)
+        throw RlError(RL_ERR_BUILD_ENV, "meta-bandit lanes take no step limit (the trial's episode limit is this env's limit)");
+    } else if (cfg->kind == RL_ENV_META_BANDIT) {
+      throw RlError(RL_ERR_BUILD_ENV, "RL_ENV_META_BANDIT lanes are created by rl_env_create_meta_bandit");
+    }
     if (cfg->kind != RL_ENV_CARTPOLE && cfg->kind != RL_ENV_CHAIN && cfg->kind != RL_ENV_MEMORY &&
-        cfg->kind != RL_ENV_BANDIT)
+        cfg->kind != RL_ENV_BANDIT && cfg->kind != RL_ENV_META_BANDIT)
       throw RlError(RL_ERR_BUILD_ENV, "unknown env kind");
     const uint64_t mem_actions = cfg->memory_num_actions ? cfg->memory_num_actions : 2;
     const uint64_t mem_history = cfg->memory_num_actions || cfg->memory_history_len ? cfg->memory_history_len : 3;
@@ -702,11 +722,14 @@ static int32_t env_create(rl_engine *e, const rl_env_config *cfg, const double *
     if (cfg->kind == RL_ENV_BANDIT && cfg->limit_kind != RL_LIMIT_NONE)
       throw RlError(RL_ERR_BUILD_ENV, "bandit lanes take no step limit (every step ends the episode)");
     const uint32_t n_states = cfg->kind == RL_ENV_MEMORY ? (uint32_t)mem_states : 5u;
-    if (cfg->kind == RL_ENV_CHAIN || cfg->kind == RL_ENV_MEMORY || cfg->kind == RL_ENV_BANDIT)
+    if (meta != nullptr)
+      env->D = meta->n_arms + 4;  // MetaObservationSpace (meta.rs:357-363)
+    else if (cfg->kind == RL_ENV_CHAIN || cfg->kind == RL_ENV_MEMORY || cfg->kind == RL_ENV_BANDIT)
       env->D = n_states + (cfg->limit_kind == RL_LIMIT_VISIBLE ? 1 : 0);  // one-hot(states) [+ remaining]
     else
       env->D = cfg->limit_kind == RL_LIMIT_VISIBLE ? 5 : 4;
     env->A = cfg->kind == RL_ENV_MEMORY ? (uint32_t)mem_actions : (arm_values != nullptr ? n_arms : 2u);
+    if (meta != nullptr) env->A = meta->n_arms;
     const rl_cartpole_params &p = cfg->cartpole;
     CartPoleDev &d = env->dev;
     d.gravity = p.gravity;
@@ -733,6 +756,16 @@ static int32_t env_create(rl_engine *e, const rl_env_config *cfg, const double *
     d.chain_size = n_states;
     d.mem_actions = cfg->kind == RL_ENV_MEMORY ? (uint32_t)mem_actions : 0u;
     d.bandit = cfg->kind == RL_ENV_BANDIT ? 1u : 0u;
+    d.meta_arms = meta != nullptr ? meta->n_arms : 0u;
+    d.meta_dist = meta != nullptr ? meta->distribution : 0;
+    if (meta != nullptr) {
+      // the means of UniformBernoulliBandits: Uniform::new_inclusive(0.0, 1.0) (bandits.rs:98-105); the trial's episode
+      // limit in the place of the step limit
+      d.init_low = 0.0;
+      d.init_scale = rl_uniform_f64_inclusive_scale(0.0, 1.0);
+      d.max_steps = (uint32_t)meta->episodes_per_trial;
+      d.chain_size = 0;  // (no one-hot state: nothing takes these lanes for an index env of five states)
+    }
     for (uint32_t a = 0; a < 8; ++a)  // Reward -> f32 feedback, as every env's reward record
       d.bandit_r[a] = arm_values != nullptr ? (a < n_arms ? (float)arm_values[a] : 0.0f)
                                             : (a < 2 ? (float)cfg->bandit_values[a] : 0.0f);
@@ -764,13 +797,30 @@ static int32_t env_create(rl_engine *e, const rl_env_config *cfg, const double *
 }
 
 int32_t rl_env_create(rl_engine *e, const rl_env_config *cfg, rl_env **out) {
-  return env_create(e, cfg, nullptr, 0, out);
+  return env_create(e, cfg, nullptr, 0, nullptr, out);
+}
+
+// UniformBernoulliBandits::default (bandits.rs:140-144), TrialEpisodeLimit::default (meta.rs:557-564)
+int32_t rl_meta_bandit_config_default(rl_meta_bandit_config *meta) {
+  return guarded(nullptr, [&] {
+    RL_REQUIRE(meta, "config is NULL");
+    meta->n_arms = 2;
+    meta->distribution = RL_BANDITS_UNIFORM_BERNOULLI;
+    meta->episodes_per_trial = 10;
+  });
+}
+
+// MetaEnv::new(distribution).wrap(TrialEpisodeLimit::new(episodes_per_trial)) (meta.rs:128-203, 541-617)
+int32_t rl_env_create_meta_bandit(rl_engine *e, const rl_env_config *cfg, const rl_meta_bandit_config *meta,
+                                  rl_env **out) {
+  if (meta == nullptr) return guarded(e, [&] { RL_REQUIRE(meta, "NULL argument"); });
+  return env_create(e, cfg, nullptr, 0, meta, out);
 }
 
 int32_t rl_env_create_bandit(rl_engine *e, const rl_env_config *cfg, const double *values, uint32_t n_arms,
                              rl_env **out) {
   if (values == nullptr) return guarded(e, [&] { RL_REQUIRE(values, "NULL argument"); });
-  return env_create(e, cfg, values, n_arms, out);
+  return env_create(e, cfg, values, n_arms, nullptr, out);
 }
 
 // Index::from_index of the env's action space: an index >= num_actions is no action
@@ -889,6 +939,8 @@ int32_t rl_env_get_state(rl_env *env, double *state4, int32_t *nv_pos, uint64_t 
                          uint64_t *reset_count) {
   return guarded(env ? env->eng : nullptr, [&] {
     RL_REQUIRE(env && state4 && nv_pos && steps_remaining && reset_count, "NULL argument");
+    if (env->kind == RL_ENV_META_BANDIT)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_env_get_state is not built for RL_ENV_META_BANDIT lanes");
     rl_engine *e = env->eng;
     size_t n = env->cfg.n_lanes;
     d2h(e, state4 + 0 * n, env->st.x, n * sizeof(double));
@@ -912,6 +964,8 @@ int32_t rl_env_set_state(rl_env *env, const double *state4, const int32_t *nv_po
                          const uint64_t *reset_count) {
   return guarded(env ? env->eng : nullptr, [&] {
     RL_REQUIRE(env && state4 && nv_pos && steps_remaining && reset_count, "NULL argument");
+    if (env->kind == RL_ENV_META_BANDIT)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_env_set_state is not built for RL_ENV_META_BANDIT lanes");
     rl_engine *e = env->eng;
     size_t n = env->cfg.n_lanes;
     std::vector<uint8_t> nv(n);
@@ -1641,7 +1695,8 @@ int32_t rl_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     }
     if (!fused_index_env && !policy->lane_kernels())
       throw RlError(RL_ERR_UNSUPPORTED, "the fused recurrent rollout is built for index envs of five states");
-    if (rl_module_is_recurrent(policy->kind) && policy->lane_kernels()) {  // a launch sequence per step
+    if (rl_module_is_recurrent(policy->kind) && policy->lane_kernels()) {  // a launch sequence per step (meta-bandit
+                                                                           // lanes: one launch, k_stack_rollout)
       seq_ensure(traj, policy, false);
       launch_stack_rollout(env, policy, traj);  // (advances t_global)
       return;

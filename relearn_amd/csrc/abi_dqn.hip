@@ -109,7 +109,9 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
     // env's code.
     const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
     if (env->kind != RL_ENV_CARTPOLE && !index_env)
-      throw RlError(RL_ERR_UNSUPPORTED, "DQN collection is built for CartPole, Chain, MemoryGame and bandit lanes");
+      throw RlError(RL_ERR_UNSUPPORTED, env->kind == RL_ENV_META_BANDIT
+                                            ? "rl_dqn_create is not built for RL_ENV_META_BANDIT lanes"
+                                            : "DQN collection is built for CartPole, Chain, MemoryGame and bandit lanes");
     if (env->D < RL_ENV_MIN_OBS_DIM || env->D > (index_env ? RL_TRAJ_MAX_OBS_DIM : 5u))
       throw RlError(RL_ERR_UNSUPPORTED, index_env ? "DQN on index-env lanes: 4..8 observation features"
                                                   : "DQN on CartPole lanes: 4 or 5 observation features");
@@ -218,8 +220,8 @@ int32_t rl_dqn_collect(rl_dqn *q, uint64_t horizon, rl_dqn_collect_stats *stats)
     // p == 1.0 always true without a draw
     double eps = dqn_exploration_rate(q, true);
     RL_REQUIRE(eps >= 0.0 && eps <= 1.0, "exploration rate outside [0, 1]");
-    int always = eps == 1.0 ? 1 : 0;
-    uint64_t p_int = always ? ~0ull : (uint64_t)(eps * 18446744073709551616.0);
+    int always = rl_bernoulli_always(eps);
+    uint64_t p_int = always ? ~0ull : rl_bernoulli_p_int(eps);
     if (q->qnet->general) {
       if (!q->d_q) q->d_q = q->mem.alloc<float>(2 * (size_t)q->rp.N);
       launch_rollout_dqn_general(q->env, q->qnet, q->mb, q->d_q, q->rp, (uint32_t)horizon, p_int, always, q->d_flags);

@@ -45,11 +45,20 @@ struct CartPoleDev {
   uint32_t mem_actions;  // RL_ENV_MEMORY: num_actions (0 selects Chain in the shared lane code)
   uint32_t bandit;       // RL_ENV_BANDIT: != 0; reward = bandit_r[action], every step terminates
   float bandit_r[8];     // DeterministicBandit::from_values, 2..8 arms
+  // RL_ENV_META_BANDIT (MetaOps, env_lanes.hpp): number of arms k (2..4) and the bandit distribution (RL_BANDITS_*);
+  // `max_steps` holds TrialEpisodeLimit::episodes_per_trial (the trial limit is this env's limit).  Last, so that the
+  // fields above keep their offsets in every kernel's arguments.
+  uint32_t meta_arms;
+  int32_t meta_dist;
 };
 
 struct EnvStateDev {
   double *x, *xdot, *th, *thdot;  // [n]; RL_ENV_CHAIN / RL_ENV_MEMORY keep their state index in x, MEMORY also its
                                   // initial state in xdot and its env-stream word position in th (exact in f64)
+  // RL_ENV_META_BANDIT: x = env-stream word position at which the trial's arms were drawn (UniformBernoulli: arm i's mean
+  // is the u64 at x + 2 i) or the good arm (OneHot, RoundRobin), xdot = next unread word of the env stream, th = the
+  // previous inner step's reward; nv_pos = bit 0 inner episode done, bit 1 prev_step_obs is Some, bits 2-3 its action;
+  // steps_remaining = inner episodes remaining in the trial
   uint8_t *nv_pos;                // [n] cached_normal_velocity_is_positive
   uint32_t *steps_remaining;      // [n]
   uint32_t *reset_count;          // [n]

@@ -342,6 +342,129 @@ struct ChainOps : IndexOps {
   }
 };
 
+// ---------------------------------------------------------------- meta-bandit lanes (RL_ENV_META_BANDIT)
+// Wrapped<MetaEnv<D>, TrialEpisodeLimit> (src/envs/meta.rs:128-203, 541-617) over Bandit<_> (src/envs/bandits.rs:58-78),
+// D = UniformBernoulliBandits (bandits.rs:96-106, 170-181), OneHotBandits (bandits.rs:229-243) or the reference's test
+// distribution RoundRobinDeterministicBandits (src/envs/testing.rs:108-160; the good arm of a lane's j-th trial is
+// j mod k).  An inner episode is one arm pull; a trial of E inner episodes is 2 E - 1 steps (pull, restart, pull, ...)
+// and ends in an Interrupt.  Every draw is one u64 taken SEQUENTIALLY from the lane's env stream (`env_pos`, always
+// even), low word first: at a trial's start k uniform means / one gen_range(0..k) / nothing, per pull of a Bernoulli arm
+// one u64 unless its mean is exactly 1.0 (rl_bernoulli_*, rl_chacha.h); deterministic arms and the restart step draw
+// nothing.  The k means are not kept: `arms` is the word position they were drawn at, and a pull recomputes the mean of
+// the pulled arm from the u64 at arms + 2 a (one ChaCha block; the same bits, hence the same mean).
+struct MetaLane {
+  uint64_t arms;     // UniformBernoulli: word position of arm 0's mean; OneHot / RoundRobin: the arm whose reward is 1
+  uint64_t env_pos;  // next unread word of the lane's env stream
+  float prev_reward;     // prev_step_obs: Some(InnerStepObs { action, feedback }) when prev_some
+  uint32_t prev_action;
+  uint32_t prev_some;
+  uint32_t inner_done;   // inner_successor is Terminate (a bandit's step always terminates)
+  uint32_t remaining;    // inner episodes left in the trial
+  uint32_t reset_count;
+};
+
+// the u64 at even word position `pos` of the lane's stream (both words lie in one block)
+__device__ __forceinline__ uint64_t lane_u64_at(const uint32_t *key, uint64_t glane, uint64_t pos) {
+  uint32_t w[16];
+  rl_chacha_block(key, pos >> 4, glane, 4, w);
+  uint32_t lo32 = 0, hi32 = 0;
+#pragma unroll
+  for (int k = 0; k < 16; k += 2)
+    if (k == (int)(pos & 15)) {
+      lo32 = w[k];
+      hi32 = w[k + 1];
+    }
+  return ((uint64_t)hi32 << 32) | lo32;
+}
+
+struct MetaOps {
+  using State = MetaLane;
+  static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) {
+    s.arms = (uint64_t)st.x[i];
+    s.env_pos = (uint64_t)st.xdot[i];
+    s.prev_reward = (float)st.th[i];
+    const uint32_t b = st.nv_pos[i];
+    s.inner_done = b & 1u;
+    s.prev_some = (b >> 1) & 1u;
+    s.prev_action = (b >> 2) & 3u;
+    s.remaining = st.steps_remaining[i];
+    s.reset_count = st.reset_count[i];
+  }
+  static __device__ __forceinline__ void store(const EnvStateDev &st, uint32_t i, const State &s) {
+    st.x[i] = (double)s.arms;  // exact below 2^53 words
+    st.xdot[i] = (double)s.env_pos;
+    st.th[i] = (double)s.prev_reward;
+    st.nv_pos[i] = (uint8_t)(s.inner_done | (s.prev_some << 1) | (s.prev_action << 2));
+    st.steps_remaining[i] = s.remaining;
+    st.reset_count[i] = s.reset_count;
+  }
+  // MetaObservationSpace features (meta.rs:357-363; OptionSpace: spaces/option.rs:87-114; field order of the derived
+  // ProductSpace: relearn_derive/src/space.rs:457-512), D = k + 4:
+  //   [inner is None] [prev is None] [one-hot(prev action), k] [prev reward] [episode_done]
+  // (the singleton inner observation has no feature of its own; the k + 1 entries behind a None marker are zero)
+  template <int D>
+  static __device__ __forceinline__ void features(const CartPoleDev &, const State &s, float (&f)[D]) {
+    f[0] = s.inner_done ? 1.0f : 0.0f;
+    f[1] = s.prev_some ? 0.0f : 1.0f;
+#pragma unroll
+    for (int a = 0; a < D - 4; ++a) f[2 + a] = s.prev_some && (uint32_t)a == s.prev_action ? 1.0f : 0.0f;
+    f[D - 2] = s.prev_some ? s.prev_reward : 0.0f;
+    f[D - 1] = s.inner_done ? 1.0f : 0.0f;
+  }
+  // MetaEnv::step (meta.rs:165-202), then the TrialEpisodeLimit tail (meta.rs:596-616).  `word` is unused: the draws
+  // are sequential.
+  static __device__ __forceinline__ int step(const CartPoleDev &c, State &s, int a, uint64_t glane, uint64_t,
+                                             float &reward) {
+    if (s.inner_done) {  // the action is ignored: a new inner episode (Bandit::initial_state draws nothing)
+      s.inner_done = 0;
+      s.prev_some = 0;
+      s.prev_action = 0;
+      s.prev_reward = 0.0f;
+      reward = 0.0f;  // neutral_outer
+      return RL_SUCC_CONTINUE;
+    }
+    float r;
+    if (c.meta_dist == RL_BANDITS_UNIFORM_BERNOULLI) {  // Bandit::step (bandits.rs:66-77) on a Bernoulli arm
+      const double p = rl_uniform_f64_from_u64(lane_u64_at(c.key_env, glane, s.arms + 2ull * (uint32_t)a), c.init_low,
+                                               c.init_scale);
+      if (rl_bernoulli_always(p)) {
+        r = 1.0f;
+      } else {
+        const uint64_t v = lane_u64_at(c.key_env, glane, s.env_pos);
+        s.env_pos += 2;
+        r = rl_bernoulli_from_u64(v, rl_bernoulli_p_int(p)) ? 1.0f : 0.0f;
+      }
+    } else {  // Deterministic::sample draws nothing
+      r = (uint64_t)(uint32_t)a == s.arms ? 1.0f : 0.0f;
+    }
+    s.prev_some = 1;
+    s.prev_action = (uint32_t)a;
+    s.prev_reward = r;
+    s.inner_done = 1;
+    reward = r;
+    s.remaining -= 1;
+    return s.remaining == 0 ? RL_SUCC_INTERRUPT : RL_SUCC_CONTINUE;
+  }
+  // TrialEpisodeLimit / MetaEnv::initial_state (meta.rs:580-589, 141-150): sample_environment, then the inner
+  // initial_state (no draw)
+  static __device__ __forceinline__ void reset(const CartPoleDev &c, State &s, uint64_t glane) {
+    if (c.meta_dist == RL_BANDITS_UNIFORM_BERNOULLI) {  // BernoulliBandit::uniform: k means, one u64 each
+      s.arms = s.env_pos;
+      s.env_pos += 2ull * c.meta_arms;
+    } else if (c.meta_dist == RL_BANDITS_ONE_HOT) {  // rng.gen_range(0..num_arms)
+      s.arms = lane_gen_range(c.key_env, glane, s.env_pos, c.meta_arms);
+    } else {  // RoundRobin: the lane's trial count mod k
+      s.arms = s.reset_count % c.meta_arms;
+    }
+    s.inner_done = 0;
+    s.prev_some = 0;
+    s.prev_action = 0;
+    s.prev_reward = 0.0f;
+    s.remaining = c.max_steps;
+    s.reset_count += 1;
+  }
+};
+
 // ---------------------------------------------------------------- one step of a lane, recorded
 // Environment::step, the step's record, the successor observation of a cut episode, the auto-reset: the rule every
 // stepping kernel follows, in this order.  `sink` is the kernel's part — where the record goes:

@@ -123,6 +123,12 @@ class EnvLanes {
     check(rl_env_create_bandit(eng.handle(), &cfg_, arm_values.data(), (uint32_t)arm_values.size(), &h_), eng.handle());
     check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
   }
+  // meta-bandit lanes (rl_env_create_meta_bandit)
+  EnvLanes(Engine &eng, const rl_env_config &cfg, const rl_meta_bandit_config &meta, double discount)
+      : eng_(eng), cfg_(cfg), discount_(discount) {
+    check(rl_env_create_meta_bandit(eng.handle(), &cfg_, &meta, &h_), eng.handle());
+    check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
+  }
   Engine &eng_;
   rl_env_config cfg_;
   rl_env *h_ = nullptr;
@@ -228,6 +234,32 @@ class DeterministicBanditLanes : public EnvLanes {
     check(rl_cartpole_params_default(&c.cartpole));
     c.bandit_values[0] = v0;
     c.bandit_values[1] = v1;
+    return c;
+  }
+};
+
+// `MetaEnv::new(D::new(n_arms)).wrap(TrialEpisodeLimit::new(episodes_per_trial))` x n_lanes (src/envs/meta.rs:128-203,
+// 541-617; D: src/envs/bandits.rs:128-243), 2..4 arms, n_arms + 4 observation features: the env of
+// relearn_experiments/src/bin/rl2-bandits.rs.  A trial is 2 * episodes_per_trial - 1 steps and ends in an Interrupt;
+// discount factor 1.0 (bandits.rs:165-167).  Defaults: UniformBernoulliBandits::default(), TrialEpisodeLimit::default().
+class MetaBanditLanes : public EnvLanes {
+ public:
+  MetaBanditLanes(Engine &eng, uint64_t n_lanes, uint32_t n_arms = 2, uint64_t episodes_per_trial = 10,
+                  int32_t distribution = RL_BANDITS_UNIFORM_BERNOULLI, uint64_t seed_env = 0, uint64_t seed_actor = 1,
+                  uint64_t lane_offset = 0)
+      : EnvLanes(eng, config(n_lanes, seed_env, seed_actor, lane_offset),
+                 rl_meta_bandit_config{n_arms, distribution, episodes_per_trial}, 1.0) {}
+
+ private:
+  static rl_env_config config(uint64_t n, uint64_t se, uint64_t sa, uint64_t off) {
+    rl_env_config c{};
+    c.kind = RL_ENV_META_BANDIT;
+    c.limit_kind = RL_LIMIT_NONE;
+    c.n_lanes = n;
+    c.lane_offset = off;
+    c.seed_env = se;
+    c.seed_actor = sa;
+    check(rl_cartpole_params_default(&c.cartpole));
     return c;
   }
 };

@@ -72,9 +72,8 @@ class Prng {
   }
   // Rng::gen_bool(p) = Bernoulli::new(p).sample: p == 1 draws nothing
   bool gen_bool(double p) {
-    if (p == 1.0) return true;
-    const uint64_t threshold = static_cast<uint64_t>(p * 18446744073709551616.0);
-    return next_u64() < threshold;
+    if (rl_bernoulli_always(p)) return true;
+    return rl_bernoulli_from_u64(next_u64(), rl_bernoulli_p_int(p)) != 0;
   }
   // Uniform::new_inclusive(low, high).sample for f64
   double uniform_inclusive(double low, double high) {

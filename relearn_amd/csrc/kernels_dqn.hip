@@ -43,7 +43,7 @@ __device__ __forceinline__ void rec_load_hi(const ReplayDev &rp, size_t o, float
 template <class Rng>
 __device__ __forceinline__ bool dqn_explores(Rng &rng, uint64_t p_int, int always_explore) {
   bool explore = always_explore != 0;
-  if (!explore) explore = rng.next_u64() < p_int;  // Bernoulli::sample: v < (p * 2^64) as u64
+  if (!explore) explore = rl_bernoulli_from_u64(rng.next_u64(), p_int) != 0;  // Bernoulli::sample (rl_chacha.h)
   return explore;
 }
 template <class Rng>

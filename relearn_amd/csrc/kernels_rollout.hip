@@ -402,7 +402,7 @@ void launch_obs_range(rl_traj *traj) {
 
 // The standalone env kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature
 // count as types.  CartPole lanes have 4 or 5 features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame:
-// num_actions + history_len [+ 1]) 4..8.
+// num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..8.
 template <int D>
 using FeatureCount = std::integral_constant<int, D>;
 template <class Go>
@@ -410,6 +410,15 @@ static void env_dispatch(const rl_env *env, Go &&go) {
   if (env->kind == RL_ENV_CARTPOLE) {
     if (env->D == 5) go(CartPoleOps{}, FeatureCount<5>{});
     else go(CartPoleOps{}, FeatureCount<4>{});
+    return;
+  }
+  if (env->kind == RL_ENV_META_BANDIT) {  // k + 4 features, k = 2..4 arms
+    switch (env->D) {
+      case 6: go(MetaOps{}, FeatureCount<6>{}); break;
+      case 7: go(MetaOps{}, FeatureCount<7>{}); break;
+      case 8: go(MetaOps{}, FeatureCount<8>{}); break;
+      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-bandit lanes: 6..8 observation features");
+    }
     return;
   }
   switch (env->D) {
@@ -427,6 +436,8 @@ void launch_env_reset(rl_env *env) {
   uint32_t n = (uint32_t)env->cfg.n_lanes;
   if (env->kind == RL_ENV_CARTPOLE)
     hipLaunchKernelGGL(k_env_reset<CartPoleOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  else if (env->kind == RL_ENV_META_BANDIT)
+    hipLaunchKernelGGL(k_env_reset<MetaOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else
     hipLaunchKernelGGL(k_env_reset<IndexOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
 }

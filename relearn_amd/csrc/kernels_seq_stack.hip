@@ -15,9 +15,12 @@
 // bit; backward and tangent passes are checked against an f64 restatement to f32 tolerance.
 //   k_stack_forward   teacher-forced forward over T steps (+ successor outputs of cut episodes, + the record)
 //   k_stack_step      one rollout step from the env's observation buffer (states persist between the launches)
+//   k_stack_rollout   all T rollout steps of an env's lanes in one launch (the env's ops struct is a template argument)
 //   k_stack_backward  reverse scan: d loss / d pre-activations of every layer and of the head into planes
 //   k_stack_tangent   forward-mode derivative along a parameter tangent through the recorded activations
 #include "abi_internal.hpp"
+#include "device_fns.hpp"
+#include "env_lanes.hpp"
 
 namespace {
 
@@ -38,6 +41,24 @@ struct StackNet {
   int D, H, H2, A, L;
   uint32_t off[RL_RNN_MAX_LAYERS + 1];  // W_ih of layer l; [L]: the head's W1
 };
+// How a kernel reads the module's parameters.  CW false: through the plain pointer (the compiler takes wave-uniform
+// scalar loads where it can prove that no store of the kernel reaches the load: k_stack_step).  CW true: through the
+// constant address space — the parameters are not written while a kernel of this unit runs, and a kernel that loops over
+// the steps with stores of its own in the loop keeps the scalar loads only when told so (k_stack_rollout: without it the
+// weights came through 120 per-lane vector loads instead of 87 scalar ones).
+template <bool CW>
+struct WeightPtr {
+  using type = const float *;
+};
+template <>
+struct WeightPtr<true> {
+  using type = const __attribute__((address_space(4))) float *;
+};
+template <bool CW>
+__device__ __forceinline__ typename WeightPtr<CW>::type weight_ptr(const float *p) {
+  return (typename WeightPtr<CW>::type)p;
+}
+
 // b_ih / b_hh of a layer whose W_hh starts at Whh
 template <int G>
 __device__ __forceinline__ const float *stack_bih(const StackNet &net, const float *Whh) {
@@ -82,9 +103,8 @@ __device__ __forceinline__ LaneCtx lane_ctx(uint32_t n) {
 // acc[r] = fma(x_k, W[row[r]][k], acc[r]) for k ascending: R rows of a [.][K] matrix against one input vector.  Four k
 // per trip: a row's four weights are contiguous (one wide wave-uniform load each), the four inputs are in flight
 // together; every sum stays the k-ascending fma chain of the arithmetic contract.
-template <int R, class XF>
-__device__ __forceinline__ void dot_rows(float (&acc)[R], const float *__restrict__ W, const int (&row)[R], int K,
-                                         XF x_at) {
+template <int R, class WP, class XF>
+__device__ __forceinline__ void dot_rows(float (&acc)[R], WP W, const int (&row)[R], int K, XF x_at) {
   int k = 0;
   for (; k + 4 <= K; k += 4) {
     float x[4], w[R][4];
@@ -141,7 +161,7 @@ __device__ __forceinline__ void tdot(float (&acc)[N], const float *__restrict__ 
 }
 
 // layer l of one step: in[k * in_stride + lane] (K inputs), states (h, c) -> (hn, cn); `fresh`: the lane's state is zero
-template <int CELL, bool REC>
+template <int CELL, bool REC, bool CW = false>
 __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &ws, int l, const float *__restrict__ in,
                                            size_t in_stride, const float *__restrict__ h, const float *__restrict__ c,
                                            bool fresh, float *__restrict__ hn, float *__restrict__ cn, const LaneCtx &lc,
@@ -149,8 +169,9 @@ __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &w
   constexpr int G = gates<CELL>();
   const int H = net.H, K = l == 0 ? net.D : net.H;
   const size_t n = ws.n;
-  const float *__restrict__ Wih = net.p + net.off[l], *__restrict__ Whh = Wih + (size_t)G * H * K;
-  const float *__restrict__ bih = stack_bih<G>(net, Whh), *__restrict__ bhh = stack_bhh<G>(net, Whh);
+  const float *__restrict__ Wih_p = net.p + net.off[l], *__restrict__ Whh_p = Wih_p + (size_t)G * H * K;
+  const auto Wih = weight_ptr<CW>(Wih_p), Whh = weight_ptr<CW>(Whh_p);
+  const auto bih = weight_ptr<CW>(stack_bih<G>(net, Whh_p)), bhh = weight_ptr<CW>(stack_bhh<G>(net, Whh_p));
   for (int j0 = UQ * lc.wave; j0 < H; j0 += UQ * SW) {
     float gif[G * UQ], ghf[G * UQ];  // [gate][unit of the quad]
     int row[G * UQ];
@@ -226,13 +247,14 @@ __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &w
 }
 
 // Chain's ReLU and the Mlp on the top layer's output `top` ([H][n]); out[q] in every thread.  One barrier inside.
-template <bool REC>
+template <bool REC, bool CW = false>
 __device__ __forceinline__ void stack_head(const StackNet &net, const StackWs &ws, const float *__restrict__ top,
                                            const LaneCtx &lc, size_t b, float (&out)[2]) {
   const int H = net.H, H2 = net.H2, A = net.A;
   const size_t n = ws.n;
-  const float *__restrict__ W1 = net.p + net.off[net.L], *__restrict__ b1 = W1 + (size_t)H2 * H;
-  const float *__restrict__ W2 = b1 + H2, *__restrict__ b2 = W2 + (size_t)A * H2;
+  const float *__restrict__ W1_p = net.p + net.off[net.L], *__restrict__ b1_p = W1_p + (size_t)H2 * H;
+  const float *__restrict__ W2_p = b1_p + H2, *__restrict__ b2_p = W2_p + (size_t)A * H2;
+  const auto W1 = weight_ptr<CW>(W1_p), b1 = weight_ptr<CW>(b1_p), W2 = weight_ptr<CW>(W2_p), b2 = weight_ptr<CW>(b2_p);
   for (int j0 = UQ * lc.wave; j0 < H2; j0 += UQ * SW) {
     float acc[UQ];
     int jj[UQ];
@@ -266,17 +288,18 @@ __device__ __forceinline__ void stack_head(const StackNet &net, const StackWs &w
 }
 
 // all layers + head of one step: states of set `cur` (zero where `fresh`) -> set `nxt`
-template <int CELL, bool REC>
+template <int CELL, bool REC, bool CW = false>
 __device__ __forceinline__ void stack_module_step(const StackNet &net, const StackWs &ws, const float *__restrict__ x,
                                                   size_t x_stride, int cur, int nxt, bool fresh, const LaneCtx &lc,
                                                   size_t b, float (&out)[2]) {
   for (int l = 0; l < net.L; ++l) {
     const float *in = l == 0 ? x : slot(ws, net, nxt, 0, l - 1);
-    stack_cell<CELL, REC>(net, ws, l, in, l == 0 ? x_stride : (size_t)ws.n, slot(ws, net, cur, 0, l),
-                          slot(ws, net, cur, 1, l), fresh, slot(ws, net, nxt, 0, l), slot(ws, net, nxt, 1, l), lc, b);
+    stack_cell<CELL, REC, CW>(net, ws, l, in, l == 0 ? x_stride : (size_t)ws.n, slot(ws, net, cur, 0, l),
+                              slot(ws, net, cur, 1, l), fresh, slot(ws, net, nxt, 0, l), slot(ws, net, nxt, 1, l), lc,
+                              b);
     __syncthreads();
   }
-  stack_head<REC>(net, ws, slot(ws, net, nxt, 0, net.L - 1), lc, b, out);
+  stack_head<REC, CW>(net, ws, slot(ws, net, nxt, 0, net.L - 1), lc, b, out);
 }
 
 // teacher-forced forward: out / succ [A][T][n] (succ may be NULL), the contract of launch_gru_seq_forward
@@ -326,6 +349,61 @@ __global__ void __launch_bounds__(SL *SW) k_stack_step(StackNet net, StackWs ws,
   stack_module_step<CELL, false>(net, ws, obs, (size_t)ws.n, parity, parity ^ 1, fresh, lc, 0, o);
   if (lc.live && lc.wave == 0)
     for (int q = 0; q < net.A; ++q) z[(size_t)q * ws.n + lc.ii] = o[q];
+}
+
+// All T steps of a rollout in one launch: what launch_rollout_stepwise's five launches per step (record the observation,
+// k_stack_step, PolicyActor::act, the env's step kernel, record the step) compute, value for value.  A workgroup keeps
+// its 64 lanes for the whole horizon and nothing crosses workgroups, so a step needs barriers only.  Per step: the
+// module reads the observation from the trajectory's planes (slot t, written by wave 0 one step earlier — plane stride
+// (T + 1) n as in k_stack_forward); the lane's wave-0 thread draws the action from word t_global + t of the lane's actor
+// stream with k_gen_sample_actions<2>'s code, steps the lane (lane_step, TrajSink) and writes the features of the next
+// observation into slot t + 1 (slot T after the last step); a barrier publishes them and the successor codes, from
+// which every thread of the lane learns whether the states restart (k_stack_step's flag_prev).  Lane state lives in wave
+// 0's registers from the first step to the last.
+template <int CELL, class Env, int D>
+__global__ void __launch_bounds__(SL *SW) k_stack_rollout(StackNet net, StackWs ws, CartPoleDev c, EnvStateDev st,
+                                                          TrajDev tr, uint64_t t_global) {
+  __shared__ uint8_t succ_of[SL];
+  const LaneCtx lc = lane_ctx(tr.n);
+  const size_t n = tr.n, T = tr.T, plane = (T + 1) * n;
+  const bool actor = lc.wave == 0, writer = lc.live && actor;
+  const uint64_t glane = c.lane_offset + lc.ii;
+  typename Env::State s{};
+  if (actor) {
+    Env::load(st, lc.ii, s);
+    float f[D];
+    Env::template features<D>(c, s, f);
+    if (writer) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) tr.obs[d * plane + lc.ii] = f[d];
+    }
+  }
+  __syncthreads();
+  bool fresh = true;
+  int cur = SET_A;
+  for (size_t t = 0; t < T; ++t) {
+    float o[2];
+    stack_module_step<CELL, false, true>(net, ws, tr.obs + t * n, plane, cur, cur ^ 1, fresh, lc, 0, o);
+    if (actor) {
+      const float u = rl_u32_to_unit_f32(stream_word(c.key_actor, glane, t_global + t));
+      float lp[2];
+      log_softmax_lane<2>(o, lp);
+      const int a = categorical_sample_lane<2>(lp, u);
+      TrajSink sink{tr, t * n + lc.ii, writer};
+      float f[D];
+      const int succ = lane_step<Env, D>(c, s, a, glane, t_global + t, sink, f);
+      Env::template features<D>(c, s, f);
+      if (writer) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) tr.obs[d * plane + (t + 1) * n + lc.ii] = f[d];
+      }
+      succ_of[threadIdx.x] = (uint8_t)succ;  // (wave 0: threadIdx.x < SL)
+    }
+    __syncthreads();
+    fresh = succ_of[threadIdx.x & (SL - 1)] != RL_SUCC_CONTINUE;
+    cur ^= 1;
+  }
+  if (writer) Env::store(st, lc.ii, s);
 }
 
 // Reverse scan over the record of the last training forward: dz [A][B] -> d loss / d pre-activation planes
@@ -650,6 +728,20 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
   float *z = traj->seq.stack.z;
   const bool lstm = policy->kind == RL_MODULE_LSTM_MLP;
+  if (env->kind == RL_ENV_META_BANDIT && env->eng->kernel_variant != 1) {
+    // meta-bandit lanes: all T steps in one launch (kernel variant 1 keeps the launch sequence per step, below).  Two
+    // arms: the recurrent chains are built for two actions (rl_rollout), so the observation has six features.
+    RL_REQUIRE(env->D == 6, "fused recurrent rollout on meta-bandit lanes: built for two arms (six features)");
+    if (lstm)
+      hipLaunchKernelGGL((k_stack_rollout<LSTM, MetaOps, 6>), grid, blk, 0, env->eng->stream, net, ws, env->dev, env->st,
+                         traj->d, env->t_global);
+    else
+      hipLaunchKernelGGL((k_stack_rollout<GRU, MetaOps, 6>), grid, blk, 0, env->eng->stream, net, ws, env->dev, env->st,
+                         traj->d, env->t_global);
+    RL_HIP_CHECK(hipGetLastError());
+    env->t_global += traj->d.T;
+    return;
+  }
   launch_rollout_stepwise(env, traj, z, [&](uint32_t step) {
     const int first = step == 0 ? 1 : 0, parity = (int)(step & 1);
     // (the step before has been recorded by now: its successor codes are in the trajectory)

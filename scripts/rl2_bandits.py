@@ -1,0 +1,55 @@
+"""The reference's RL^2 bandit experiment (relearn_experiments/src/bin/rl2-bandits.rs:379-425) on the meta-bandit lanes:
+`MetaEnv::new(UniformBernoulliBandits::new(arms)).wrap(TrialEpisodeLimit::new(episodes))`, policy and critic each a
+GRU(128) -> Relu -> linear head chain, TRPO at max KL 0.01, the critic fitted with 50 Adam steps per period, GAE with
+lambda 0.3, discount factor 0.99.  Recurrent chains are built for two actions, so `arms` is 2.  Every lane collects whole
+trials per period (horizon = trials_per_lane * (2 * episodes - 1)); the mean trial reward of a period comes from the
+device-side StepsSummary (an episode of the summary is a trial).  Prints one JSON line per period.
+
+    python scripts/rl2_bandits.py [lanes] [episodes] [periods] [trials_per_lane] [distribution] [hidden] [critic_steps]
+"""
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import relearn_amd as ra  # noqa: E402
+
+arg = lambda i, d: type(d)(sys.argv[i]) if len(sys.argv) > i else d
+N, E, periods, trials = arg(1, 1024), arg(2, 10), arg(3, 20), arg(4, 2)
+dist, H, critic_steps = arg(5, "uniform_bernoulli"), arg(6, 128), arg(7, 50)
+T = trials * (2 * E - 1)
+
+eng = ra.Engine(0)
+env = ra.MetaBanditEnv(eng, N, 2, E, dist, seed_env=0, seed_actor=1)
+pol, cri = ra.GruMlp(eng, env.D, 2, H, H), ra.GruMlp(eng, env.D, 1, H, H)
+pol.init(2)  # input weights Uniform(FanAvg), hidden weights Orthogonal, biases Zeros: the experiment's GruConfig
+cri.init(3)
+opt = ra.Adam(cri)
+trpo = ra.trpo_config_default()
+trpo.max_policy_step_kl = 0.01
+ccfg = ra.values_opt_config_default()
+ccfg.opt_steps_per_update = critic_steps
+ccfg.discount_factor = 0.99
+traj = ra.Trajectory(eng, N, T, env.D)
+summary = ra.StepsSummary(eng, N)
+
+for period in range(periods):
+    eng.sync()
+    t0 = time.perf_counter()
+    ra.rollout(env, pol, traj)
+    eng.sync()
+    t1 = time.perf_counter()
+    ra.gae(traj, cri, 0.99, 0.3)
+    pst, cst = ra.actor_critic_update(pol, cri, opt, traj, trpo, ccfg)
+    eng.sync()
+    t2 = time.perf_counter()
+    summary.clear()
+    summary.push(traj)
+    s = summary.read()
+    print(json.dumps({"period": period, "lanes": N, "episodes_per_trial": E, "horizon": T, "distribution": dist,
+                      "trials": s.episode_reward.count, "mean_trial_reward": s.episode_reward.mean,
+                      "trial_reward_stddev": s.episode_reward.stddev(), "mean_step_reward": s.step_reward.mean,
+                      "trpo_status": pst.status, "kl": pst.constraint_val_final, "entropy": pst.entropy,
+                      "critic_loss": [cst.loss_first, cst.loss_last],
+                      "rollout_ms": (t1 - t0) * 1e3, "update_ms": (t2 - t1) * 1e3}), flush=True)
