@@ -17,7 +17,8 @@
 //   cell   : r = sig(gh_r + gi_r), z = sig(gh_z + gi_z), n = tanh(gi_n + gh_n * r), h' = (h - n) * z + n
 //            (libtorch gru_cell operation order), rl_sigmoidf / rl_tanhf of include/rl_detmath.h;
 //   head   : u = relu(b1 + W1 relu(h')) by MFMA, out_a = b2_a + sum_j u_j W2[a][j] as a sequential chain on the
-//            VALU (one lane per (sample, output)).
+//            VALU (one lane per (sample, output)) — written once for both cells (seq_head16): a cell says where its W1
+//            operands come from, where u is parked and how far the k loop unrolls.
 #include "env_lanes.hpp"
 #include "seq_common.hpp"
 
@@ -78,10 +79,63 @@ __device__ __forceinline__ void seq_load_weights16(SeqFwdWeights16<D> &w, const 
   w.b1 = g.b1[j];
 }
 
+// The head both cells end with, entered after the barrier that publishes h' in sh.hT[nxt]: u = relu(b1 + W1 relu(h')) by
+// MFMA, parked [m][j] at uS (row stride MH + 1) and stored to the record, then out_a = b2_a + sum_j u_j W2[a][j] -> sh.outS.
+// w1_at(ks): the lane's B operand of k-step ks (W1[j][4 ks + g4]); UNROLL: the unroll of the k loop.
+template <int A, bool FINAL_BARRIER, int UNROLL, class Shared, class W1At>
+__device__ __forceinline__ void seq_head16(Shared &sh, int nxt, W1At w1_at, float *__restrict__ uS, float b1,
+                                           float b2_mine, float *__restrict__ store, int wave, int lane) {
+  const int n16 = lane & 15, g4 = lane >> 4, j = 16 * wave + n16;
+  f32x4 acc1[2];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) acc1[mt] = (f32x4){b1, b1, b1, b1};
+#pragma unroll UNROLL
+  for (int ks = 0; ks < GH / 4; ++ks) {
+    const float b = w1_at(ks);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      float a = sh.hT[nxt][4 * ks + g4][16 * mt + n16];
+      a = a > 0.0f ? a : 0.0f;  // Chain activation between the modules (chain.rs:165)
+      acc1[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc1[mt], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) {
+    f32x4 uv;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = acc16_row(mt, i, g4);
+      const float u = acc1[mt][i] > 0.0f ? acc1[mt][i] : 0.0f;
+      uS[m * (MH + 1) + j] = u;
+      uv[i] = u;
+    }
+    if (store != nullptr)
+      *reinterpret_cast<f32x4 *>(store + (size_t)ACT_U * GH * TL + rec_at(j, 16 * mt + 4 * g4)) = uv;
+  }
+  __syncthreads();
+  if (wave == 0 && (lane >> 5) < A) {
+    const int n = lane & 31, hf = lane >> 5;
+    float z = b2_mine;
+#pragma unroll 8
+    for (int q = 0; q < MH; ++q) z = __builtin_fmaf(uS[n * (MH + 1) + q], sh.w2S[hf][q], z);
+    sh.outS[hf][n] = z;
+  }
+  // the head's outputs are read by lanes of wave 0 only (the env / io lanes): a caller that syncs the workgroup later
+  // anyway needs just the in-wave ordering of these LDS writes
+  if (FINAL_BARRIER) {
+    __syncthreads();
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
+
 // One cell + head evaluation for the tile.  Reads the state from sh.hT[cur] and `hown`, writes the new state to
-// sh.hT[cur ^ 1] and `hnew`; the head outputs land in sh.outS (valid after the function returns: it ends with a
-// barrier).  `store` != nullptr: record the 7 activation arrays of this (t, tile) block ([half][unit][16] arrays, rec_at: a lane's
-// four samples of an M-tile are contiguous, one 16-byte store per array and M-tile).
+// sh.hT[cur ^ 1] and `hnew`; the head outputs land in sh.outS (valid after the function returns: seq_head16 ends with a
+// barrier or a wave fence).  `store` != nullptr: record the 7 activation arrays of this (t, tile) block
+// ([half][unit][16] arrays, rec_at: a lane's four samples of an M-tile are contiguous, one 16-byte store per array and
+// M-tile).
 template <int D, int A, bool FINAL_BARRIER = true>
 __device__ __forceinline__ void seq_cell16(SeqFwdShared &sh, const SeqFwdWeights16<D> &w, int cur,
                                            const float (&hown)[8], float (&hnew)[8], float b2_mine,
@@ -143,48 +197,8 @@ __device__ __forceinline__ void seq_cell16(SeqFwdShared &sh, const SeqFwdWeights
     }
   }
   __syncthreads();
-  f32x4 acc1[2];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt) acc1[mt] = (f32x4){w.b1, w.b1, w.b1, w.b1};
-#pragma unroll
-  for (int ks = 0; ks < GH / 4; ++ks) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      float a = sh.hT[nxt][4 * ks + g4][16 * mt + n16];
-      a = a > 0.0f ? a : 0.0f;  // Chain activation between the modules (chain.rs:165)
-      acc1[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w.w1[ks], acc1[mt], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
-    f32x4 uv;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = acc16_row(mt, i, g4);
-      const float u = acc1[mt][i] > 0.0f ? acc1[mt][i] : 0.0f;
-      sh.uS[m][j] = u;
-      uv[i] = u;
-    }
-    if (store != nullptr)
-      *reinterpret_cast<f32x4 *>(store + (size_t)ACT_U * GH * TL + rec_at(j, 16 * mt + 4 * g4)) = uv;
-  }
-  __syncthreads();
-  if (wave == 0 && (lane >> 5) < A) {
-    const int n = lane & 31, hf = lane >> 5;
-    float z = b2_mine;
-#pragma unroll 8
-    for (int q = 0; q < MH; ++q) z = __builtin_fmaf(sh.uS[n][q], sh.w2S[hf][q], z);
-    sh.outS[hf][n] = z;
-  }
-  // the head's outputs are read by lanes of wave 0 only (the env / io lanes): a caller that syncs the workgroup later
-  // anyway needs just the in-wave ordering of these LDS writes
-  if (FINAL_BARRIER) {
-    __syncthreads();
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
+  seq_head16<A, FINAL_BARRIER, GH / 4>(sh, nxt, [&](int ks) { return w.w1[ks]; }, &sh.uS[0][0], w.b1, b2_mine, store, wave,
+                                       lane);
 }
 
 // ---------------------------------------------------------------- LSTM cell (seq/rnn/lstm.rs:17-51), same ownership
@@ -301,49 +315,8 @@ __device__ __forceinline__ void lstm_cell16(LstmFwdShared &sh, const LstmFwdWeig
   // write h(t+2) there (after the workgroup barrier that ends this step)
   float *__restrict__ uS = &sh.hT[cur][0][0];
   static_assert(TL * (MH + 1) <= GH * TLS, "the head's activations fit the state buffer");
-  f32x4 acc1[2];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt) acc1[mt] = (f32x4){w.b1, w.b1, w.b1, w.b1};
-#pragma unroll 8
-  for (int ks = 0; ks < GH / 4; ++ks) {
-    const float b = sh.w1S[wave][ks][lane];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      float a = sh.hT[nxt][4 * ks + g4][16 * mt + n16];
-      a = a > 0.0f ? a : 0.0f;  // Chain activation between the modules (chain.rs:165)
-      acc1[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc1[mt], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
-    f32x4 uv;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = acc16_row(mt, i, g4);
-      const float u = acc1[mt][i] > 0.0f ? acc1[mt][i] : 0.0f;
-      uS[m * (MH + 1) + j] = u;
-      uv[i] = u;
-    }
-    if (store != nullptr)
-      *reinterpret_cast<f32x4 *>(store + (size_t)ACT_U * GH * TL + rec_at(j, 16 * mt + 4 * g4)) = uv;
-  }
-  __syncthreads();
-  if (wave == 0 && (lane >> 5) < A) {
-    const int n = lane & 31, hf = lane >> 5;
-    float z = b2_mine;
-#pragma unroll 8
-    for (int q = 0; q < MH; ++q) z = __builtin_fmaf(uS[n * (MH + 1) + q], sh.w2S[hf][q], z);
-    sh.outS[hf][n] = z;
-  }
-  // the head's outputs are read by lanes of wave 0 only (the env / io lanes): a caller that syncs the workgroup later
-  // anyway needs just the in-wave ordering of these LDS writes
-  if (FINAL_BARRIER) {
-    __syncthreads();
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
+  seq_head16<A, FINAL_BARRIER, 8>(sh, nxt, [&](int ks) { return sh.w1S[wave][ks][lane]; }, uS, w.b1, b2_mine, store, wave,
+                                  lane);
 }
 
 // The two cells behind one interface for the rollout / teacher-forced forward loops.  NS = per-lane state registers

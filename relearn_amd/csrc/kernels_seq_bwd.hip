@@ -1,6 +1,8 @@
 // kernels_seq_bwd.hip — training passes of the recurrent chains (GRU / LSTM -> ReLU -> MLP): per-sample output
 // gradients, backward through time, weight-gradient GEMMs, f64 row reduction.  Workspace layout and tile geometry:
-// seq_common.hpp; the forward that fills the activation record: kernels_seq.hip.
+// seq_common.hpp; the forward that fills the activation record: kernels_seq.hip.  The head's f32 backward (d u_pre, then
+// W1^T d u_pre) is written once (head_du16, head_w1t16): k_gru_bptt runs it inside its step, k_seq_head_backward over all
+// blocks ahead of k_lstm_bptt.
 #include "seq_common.hpp"
 
 // =====================================================================================================
@@ -98,6 +100,37 @@ __global__ void __launch_bounds__(256) k_seq_critic_dvalues(TrajDev tr, const fl
   }
 }
 
+// ---------------------------------------------------------------- the head's f32 backward (16-unit ownership)
+// For k_gru_bptt (inside its step) and k_seq_head_backward (over all blocks).  d u_pre = [u > 0] W2^T dz of the four samples
+// m0 .. m0 + 3 a lane owns of unit j in an M-tile: parked in bufU for the W1^T product, returned for the record
+template <int A>
+__device__ __forceinline__ f32x4 head_du16(const f32x4 &uv, const f32x4 (&dzv)[A], const float (&w2c)[A],
+                                           float (&bufU)[GH][TLS], int j, int m0) {
+  f32x4 duv;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float du = 0.0f;
+#pragma unroll
+    for (int a = 0; a < A; ++a) du = __builtin_fmaf(dzv[a][i], w2c[a], du);
+    du = uv[i] > 0.0f ? du : 0.0f;
+    bufU[j][m0 + i] = du;
+    duv[i] = du;
+  }
+  return duv;
+}
+// W1^T d u_pre (before the relu' mask of relu(h')): two half-chains per M-tile, acc1[mt][0] + acc1[mt][1] is the sum
+__device__ __forceinline__ void head_w1t16(const float (&bufU)[GH][TLS], const float (&w1T)[MH / 4], f32x4 (&acc1)[2][2],
+                                           int g4, int n16) {
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) acc1[mt][0] = acc1[mt][1] = (f32x4){0, 0, 0, 0};
+#pragma unroll
+  for (int ks = 0; ks < MH / 4; ++ks)
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+      acc1[mt][ks & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(bufU[4 * ks + g4][16 * mt + n16], w1T[ks],
+                                                              acc1[mt][ks & 1], 0, 0, 0);
+}
+
 // ---------------------------------------------------------------- backward through time
 // One workgroup (eight waves) per tile, t = T-1 .. 0.  Wave w owns units k in [16w, 16w+16) of every back-propagated
 // vector: its slices of W1^T (32 B-operands of 16x16x4 MFMAs) and W_hh^T (3 x 32) stay in registers; the vectors being
@@ -135,7 +168,7 @@ __global__ void __launch_bounds__(W16 * 64, 2) k_gru_bptt(TrajDev tr, const floa
   // one step's inputs: the lane's 2 x 4 samples of its unit in six record arrays + u, the logit gradients and the
   // episode-end flags of those samples
   struct StepIn {
-    f32x4 u[2], a1[2], r[2], z[2], n[2], ghn[2], hp[2], dzv[A][2];
+    f32x4 u[2], a1[2], r[2], z[2], n[2], ghn[2], hp[2], dzv[2][A];
     uint32_t end[2];  // four flag bytes
   };
   const size_t lo = rec_at(j, 4 * g4);  // + 16 mt: first of the lane's four contiguous samples
@@ -146,7 +179,7 @@ __global__ void __launch_bounds__(W16 * 64, 2) k_gru_bptt(TrajDev tr, const floa
       in.u[mt] = *reinterpret_cast<const f32x4 *>(ab + (size_t)ACT_U * GH * TL + lo + REC_HALF * mt);
 #pragma unroll
       for (int a = 0; a < A; ++a)
-        in.dzv[a][mt] = *reinterpret_cast<const f32x4 *>(dz + (size_t)a * B + (size_t)t * N + lane0 + 16 * mt + 4 * g4);
+        in.dzv[mt][a] = *reinterpret_cast<const f32x4 *>(dz + (size_t)a * B + (size_t)t * N + lane0 + 16 * mt + 4 * g4);
       in.end[mt] = *reinterpret_cast<const uint32_t *>(tr.flag + (size_t)t * N + lane0 + 16 * mt + 4 * g4);
     }
   };
@@ -172,32 +205,15 @@ __global__ void __launch_bounds__(W16 * 64, 2) k_gru_bptt(TrajDev tr, const floa
     float *__restrict__ db = dpre + ((size_t)t * tiles + tile) * DPRE_ARR * GH * TL;
     // head: d u_pre = [u > 0] W2^T dz
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      f32x4 duv;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float du = 0.0f;
-#pragma unroll
-        for (int a = 0; a < A; ++a) du = __builtin_fmaf(in.dzv[a][mt][i], w2c[a], du);
-        du = in.u[mt][i] > 0.0f ? du : 0.0f;
-        bufU[j][16 * mt + 4 * g4 + i] = du;
-        duv[i] = du;
-      }
-      *reinterpret_cast<f32x4 *>(db + (size_t)4 * GH * TL + lo + REC_HALF * mt) = duv;
-    }
+    for (int mt = 0; mt < 2; ++mt)
+      *reinterpret_cast<f32x4 *>(db + (size_t)DPRE_DU * GH * TL + lo + REC_HALF * mt) =
+          head_du16<A>(in.u[mt], in.dzv[mt], w2c, bufU, j, 16 * mt + 4 * g4);
     uint32_t endw[2] = {in.end[0], in.end[1]};
     if (t > 0) load_u(in, t - 1);  // consumed at the top of the next step
     __syncthreads();
     // d relu(h') = W1^T d u_pre: two half-chains per M-tile
     f32x4 acc1[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) acc1[mt][0] = acc1[mt][1] = (f32x4){0, 0, 0, 0};
-#pragma unroll
-    for (int ks = 0; ks < MH / 4; ++ks)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-        acc1[mt][ks & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(bufU[4 * ks + g4][16 * mt + n16], w1T[ks],
-                                                                acc1[mt][ks & 1], 0, 0, 0);
+    head_w1t16(bufU, w1T, acc1, g4, n16);
     // cell: h' = (h - n) z + n
     f32x4 dhdir[2];
 #pragma unroll
@@ -286,31 +302,16 @@ __global__ void __launch_bounds__(W16 * 64, 2) k_seq_head_backward(TrajDev tr, c
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
       const f32x4 uv = *reinterpret_cast<const f32x4 *>(ab + (size_t)ACT_U * GH * TL + lo + REC_HALF * mt);
-      f32x4 dzv[A], duv;
+      f32x4 dzv[A];
 #pragma unroll
       for (int a = 0; a < A; ++a)
         dzv[a] = *reinterpret_cast<const f32x4 *>(dz + (size_t)a * B + (size_t)t * N + lane0 + 16 * mt + 4 * g4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float du = 0.0f;
-#pragma unroll
-        for (int a = 0; a < A; ++a) du = __builtin_fmaf(dzv[a][i], w2c[a], du);
-        du = uv[i] > 0.0f ? du : 0.0f;
-        bufU[j][16 * mt + 4 * g4 + i] = du;
-        duv[i] = du;
-      }
-      *reinterpret_cast<f32x4 *>(db + (size_t)DPRE_DU * GH * TL + lo + REC_HALF * mt) = duv;
+      *reinterpret_cast<f32x4 *>(db + (size_t)DPRE_DU * GH * TL + lo + REC_HALF * mt) =
+          head_du16<A>(uv, dzv, w2c, bufU, j, 16 * mt + 4 * g4);
     }
     __syncthreads();
     f32x4 acc1[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) acc1[mt][0] = acc1[mt][1] = (f32x4){0, 0, 0, 0};
-#pragma unroll
-    for (int ks = 0; ks < MH / 4; ++ks)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-        acc1[mt][ks & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(bufU[4 * ks + g4][16 * mt + n16], w1T[ks],
-                                                                acc1[mt][ks & 1], 0, 0, 0);
+    head_w1t16(bufU, w1T, acc1, g4, n16);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
       const f32x4 a1 = *reinterpret_cast<const f32x4 *>(ab + (size_t)ACT_A1 * GH * TL + lo + REC_HALF * mt);

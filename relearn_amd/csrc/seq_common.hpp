@@ -1,6 +1,8 @@
 // seq_common.hpp — definitions shared by the recurrent-configuration kernels (kernels_seq.hip: cells, rollout,
-// teacher-forced forward; kernels_seq_bwd.hip: backward through time and weight gradients; kernels_seq_fvp.hip: forward-
-// mode tangents for Fisher-vector products): tile geometry, workspace array indices, the flat-parameter view.
+// teacher-forced forward; kernels_seq_train.hip: the training passes on the bf16 pipe; kernels_seq_bwd.hip: the f32 backward
+// through time and weight gradients; kernels_seq_fvp.hip: forward-mode tangents for Fisher-vector products): tile geometry,
+// workspace array indices, the record layout, the flat-parameter view and the accumulator-row maps of the two MFMA
+// shapes.  Weight slices live with the kernels that hold them (every kernel loads its own operands).
 #pragma once
 #include "device_fns.hpp"
 #include "kernels.hpp"
@@ -51,33 +53,6 @@ __host__ __device__ inline GruParams seq_params(const float *p, int D, int A, in
 __host__ __device__ inline GruParams gru_params(const float *p, int D, int A) { return seq_params(p, D, A, 3); }
 
 __device__ __forceinline__ int acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
-
-// Register-resident weight slices of one wave (unit j = 32 * wave + (lane & 31), k parity = lane >> 5)
-template <int D>
-struct SeqFwdWeights {
-  float whh[3][GH / 2];
-  float w1[GH / 2];
-  float wih[3][D];
-  float bih[3], bhh[3], b1;
-};
-
-template <int D>
-__device__ __forceinline__ void seq_load_weights(SeqFwdWeights<D> &w, const GruParams &g, int wave, int lane) {
-  const int n = lane & 31, hf = lane >> 5, j = 32 * wave + n;
-#pragma unroll
-  for (int gte = 0; gte < 3; ++gte) {
-    const int row = gte * GH + j;
-#pragma unroll
-    for (int ks = 0; ks < GH / 2; ++ks) w.whh[gte][ks] = g.Whh[(size_t)row * GH + 2 * ks + hf];
-#pragma unroll
-    for (int d = 0; d < D; ++d) w.wih[gte][d] = g.Wih[(size_t)row * D + d];
-    w.bih[gte] = g.bih[row];
-    w.bhh[gte] = g.bhh[row];
-  }
-#pragma unroll
-  for (int ks = 0; ks < GH / 2; ++ks) w.w1[ks] = g.W1[(size_t)j * GH + 2 * ks + hf];
-  w.b1 = g.b1[j];
-}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int W16 = 8;  // waves per tile

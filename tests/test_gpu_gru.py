@@ -324,6 +324,25 @@ def test_fisher_vector_product_through_time(engine):
     assert abs(kl_d - kl_o) <= 1e-4 * kl_o + 3e-8 and kl_o > 1e-5
 
 
+@pytest.mark.parametrize("n,T,max_steps", [(32, 1, 9), (32, 2, 1), (96, 7, 3), (160, 3, 2)],
+                         ids=["one-tile-one-step", "every-step-ends", "three-tiles", "five-tiles"])
+def test_fisher_vector_product_at_edge_shapes(engine, n, T, max_steps):
+    """the GRU chain's tangent kernels (kernels_seq_fvp.hip: static terms over all blocks, then the recurrence per tile) at
+    the edges of their loops — one block, a carried tangent that is zeroed at every step, episodes ending mid-walk, an odd
+    number of tiles — under the two bounds of test_fisher_vector_product_through_time.  (The oracle's own f32 evaluation is
+    0.7e-7 to 1.9e-7 from its f64 one at these shapes, so the second bound is 2.3e-6 to 2.8e-6.)"""
+    pol, cri, traj, want, _, _ = setup_update(engine, n=n, T=T, max_steps=max_steps)
+    p = pol.get_params()
+    v = np.random.default_rng(3).normal(size=len(p)).astype(np.float32)
+    reg = 1e-5
+    hv_d = ra.policy_fvp(pol, traj, v, reg)
+    hv64 = O.gru_policy_fvp(PS, p.astype(np.float64), v.astype(np.float64), want, reg, f64=True)
+    hv32 = O.gru_policy_fvp(PS, p, v, want, reg)
+    print("fvp edge shape", (n, T, max_steps), "device", rel_err(hv_d, hv64), "oracle f32", rel_err(hv32, hv64))
+    assert rel_err(hv_d, hv64) < 2e-5, (rel_err(hv_d, hv64), rel_err(hv32, hv64))
+    assert rel_err(hv_d, hv64) < 4 * rel_err(hv32, hv64) + 2e-6
+
+
 def oracle_trpo_loop(p0, want, f64, iterations=10, max_backtracks=15, ratio=0.8, reg=1e-5, max_kl=0.01):
     """trust_region_backward_step + backtracking_line_search (conjugate_gradient.rs:115-255) on the oracle's
     recurrent gradient / Fisher-vector / loss-KL pieces; arithmetic in f32 or f64"""
