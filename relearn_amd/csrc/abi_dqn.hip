@@ -364,13 +364,13 @@ static void dqn_gradient(rl_dqn *q, rl_adam *step_opt = nullptr, int loss_slot =
   // (the two fused launchers report their rows in nbV2)
   const SlabRows rows = fused ? SlabRows{mb->nbV2, mb->nbV2} : run_pass(q->qnet, mb, pass);
   if (step_opt && !q->eng->has_collective()) {
-    launch_reduce_adam(mb, step_opt, rows.A, rows.B, loss_slot, q->last_total_steps);
+    launch_reduce_opt(mb, step_opt, rows.A, rows.B, loss_slot, q->last_total_steps);
     return;
   }
   const uint32_t P = (uint32_t)q->qnet->P;
   launch_reduce(mb, P, true, true, rows.A, rows.B);
   rl_allreduce_sum_f32(q->eng, mb->vec, P + 4);
-  if (step_opt) launch_adam_step(mb, step_opt, loss_slot, q->last_total_steps);
+  if (step_opt) launch_opt_step(mb, step_opt, loss_slot, q->last_total_steps);
 }
 
 int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) {

@@ -414,7 +414,7 @@ int32_t rl_optimizer_step_host(rl_adam *o, const float *grad) {
     DevMem tmp;
     float *d_g = tmp.alloc<float>(o->mod->P);
     h2d(e, d_g, grad, o->mod->P * sizeof(float));
-    launch_adam_step_vec(o, d_g);
+    launch_opt_step_vec(o, d_g);
     sync(e);
   });
 }
@@ -455,10 +455,10 @@ static void critic_enqueue_steps(rl_mlp *critic, rl_adam *opt, rl_traj *traj, ui
   for (uint64_t k = first; k < opt_steps; ++k) {
     if (fused) {  // no all-reduce between the reduction and the (elementwise) optimiser step: one launch
       const SlabRows rows = run_pass(critic, traj, slabs_only);
-      launch_reduce_adam(traj, opt, rows.A, rows.B, (int)k, Bt);
+      launch_reduce_opt(traj, opt, rows.A, rows.B, (int)k, Bt);
     } else {
       run_pass(critic, traj, RUN_CRITIC);
-      launch_adam_step(traj, opt, (int)k, Bt);
+      launch_opt_step(traj, opt, (int)k, Bt);
     }
   }
 }
@@ -796,7 +796,7 @@ int32_t rl_ppo_update(rl_mlp *policy, rl_adam *opt, rl_traj *traj, const rl_ppo_
     for (uint64_t k = 0; k < K; ++k) {
       // gradient of the clipped surrogate against lp0 -> vec[0..P), sum of min(...) -> vec[P]
       run_pass(policy, traj, ppo);
-      launch_adam_step(traj, opt, (int)k, Bt);
+      launch_opt_step(traj, opt, (int)k, Bt);
     }
     std::vector<float> h(K ? K : 1, 0.0f);
     if (K) d2h(e, h.data(), traj->losses, K * sizeof(float));
@@ -823,7 +823,7 @@ int32_t rl_reinforce_update(rl_mlp *policy, rl_adam *opt, rl_traj *traj, rl_poli
     run_pass(policy, traj, RUN_INIT);
     float h0[4];
     d2h(e, h0, traj->vec + P, sizeof(h0));
-    launch_adam_step(traj, opt, -1, Bt);
+    launch_opt_step(traj, opt, -1, Bt);
     range_check(traj, 1u << RL_GUARD_POLICY);
     if (stats) {
       stats->entropy = (double)h0[1] / (double)Bt;

@@ -350,7 +350,7 @@ struct GenDev {
 };
 
 // What the optimiser kernels (kernels_update.hip) get by value.  OptStep: the constants of one step, each formed in f64 on
-// the host and rounded to f32 once (adam_next_step); a rule reads the ones it names.  OptState: the rule's state slots.
+// the host and rounded to f32 once (opt_next_step); a rule reads the ones it names.  OptState: the rule's state slots.
 enum : uint32_t {
   OPT_WEIGHT_DECAY = 1u,  // weight_decay != 0
   OPT_MOMENTUM = 2u,      // SGD: momentum != 0; RMSProp: momentum > 0
@@ -384,7 +384,7 @@ struct rl_adam {
   uint64_t *d_step = nullptr;
   uint64_t host_step = 0;  // == *d_step once the stream has drained (every optimiser launch increments both)
   // ... unless a launch was vetoed on the device (a failed exchange, the range guard): the entry point then returned an
-  // error, and the first step after an error on this engine re-reads the count (rl_engine::error_epoch, adam_next_step)
+  // error, and the first step after an error on this engine re-reads the count (rl_engine::error_epoch, opt_next_step)
   uint64_t error_epoch = 0;
 };
 

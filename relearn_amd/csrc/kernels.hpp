@@ -96,10 +96,10 @@ void launch_step_size(rl_traj *traj, rl_mlp *policy, float reg, double max_kl); 
 void launch_ls_set_params(rl_traj *traj, rl_mlp *policy, double ratio);
 void launch_ls_check(rl_traj *traj, uint32_t P, uint64_t B_total, int index, double ratio, double max_kl);
 void launch_ls_finalize(rl_traj *traj, rl_mlp *policy, double max_kl, int accept_violation);
-void launch_adam_step(rl_traj *traj, rl_adam *opt, int loss_slot, uint64_t B_total);     // after critic reduce
-void launch_adam_step_vec(rl_adam *opt, const float *d_grad);
-// reduce(A + B) and Adam in one launch (single-rank runs: no all-reduce between the two)
-void launch_reduce_adam(rl_traj *traj, rl_adam *opt, uint32_t rowsA, uint32_t rowsB, int loss_slot, uint64_t B_total);
+void launch_opt_step(rl_traj *traj, rl_adam *opt, int loss_slot, uint64_t B_total);      // after critic reduce
+void launch_opt_step_vec(rl_adam *opt, const float *d_grad);
+// reduce(A + B) and the optimiser's step in one launch (single-rank runs: no all-reduce between the two)
+void launch_reduce_opt(rl_traj *traj, rl_adam *opt, uint32_t rowsA, uint32_t rowsB, int loss_slot, uint64_t B_total);
 
 // kernels_critic.hip, kernels_mfma.hip ("v2"): the fused critic step and policy passes of a 5-128 module on the bf16
 // matrix pipe (bf16_tile.hpp); a module with several hidden layers goes on to launch_gen_mfma

@@ -246,91 +246,64 @@ __global__ void __launch_bounds__(128) k_mlp_backward(const float *__restrict__ 
 }
 
 // ---------------------------------------------------------------- (3) deterministic slab reduction
-// Workgroup = 16 waves for 64 consecutive vector entries: wave w sums slab rows w, w+16, ... in order, the
-// 16 partials are combined in wave order; f64 throughout, rounded to f32 once.  Rows are 512-B coalesced reads.
-// sum of the slab rows r = w, w + 16, w + 32, ... of one column: the loads of up to 16 rows are issued before the first
-// add (one memory round trip for <= 256 rows — the launch is latency-bound), the additions run in row order
-__device__ __forceinline__ double column_partial(const double *__restrict__ slab, uint32_t nb, uint32_t stride,
-                                                 uint32_t col, int w) {
+// Sum of one column over `nb` rows of f64 partials (`stride` doubles from row to row, `col` = the column's entry in row
+// 0) in a fixed order, by a workgroup of 1,024 threads that owns CW consecutive columns: thread x has column x % CW and
+// row group x / CW of RG = 16 x 64 / CW (the 64 / CW lane groups of a wave are on different rows).  A group sums rows rg,
+// rg + RG, ... in row order; the loads of a trip of U rows are issued before its first add (U loads in flight per lane:
+// one memory round trip for U x RG rows — these launches are latency-bound).  The partial is parked in part[RG][CW];
+// behind ONE barrier the first CW threads add the RG partials in group order and return the total (the other threads
+// return 0).  Every thread of the workgroup calls it; a thread without a column passes nb = 0.
+template <int CW, int U>
+__device__ __forceinline__ double column_sum(const double *__restrict__ col, uint32_t nb, uint32_t stride,
+                                             double (&part)[16 * (64 / CW)][CW]) {
+  static_assert(CW <= 64 && 64 % CW == 0, "a row group is a whole fraction of a wave");
+  constexpr int GPW = 64 / CW, RG = 16 * GPW;  // row groups per wave, per workgroup
+  const int c = threadIdx.x & (CW - 1), rg = threadIdx.x / CW;
   double acc = 0.0;
-  for (uint32_t r0 = w; r0 < nb; r0 += 16 * 16) {
-    double v[16];
+  for (uint32_t r0 = (uint32_t)rg; r0 < nb; r0 += RG * U) {
+    double v[U];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const uint32_t r = r0 + 16 * u;
-      v[u] = r < nb ? slab[(size_t)r * stride + col] : 0.0;
+    for (int u = 0; u < U; ++u) {
+      const uint32_t r = r0 + RG * u;
+      v[u] = r < nb ? col[(size_t)r * stride] : 0.0;
     }
 #pragma unroll
-    for (int u = 0; u < 16; ++u) acc = acc + v[u];
-  }
-  return acc;
-}
-
-__global__ void __launch_bounds__(1024) k_reduce(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
-                                                 const double *__restrict__ slabB, uint32_t nbB,
-                                                 float *__restrict__ vec, int useA, int useB) {
-  __shared__ double part[16][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint32_t p = blockIdx.x * 64 + lane;
-  double acc = 0.0;
-  if (p < P) {
-    if (useA) acc = column_partial(slabA, nbA, P, p, w);
-  } else if (p < P + 4) {
-    if (useB) acc = column_partial(slabB, nbB, 4, p - P, w);
-  }
-  part[w][lane] = acc;
-  __syncthreads();
-  if (w == 0 && p < P + 4) {
-    bool write = p < P ? useA != 0 : useB != 0;
-    if (write) {
-      double t = part[0][lane];
-#pragma unroll
-      for (int k = 1; k < 16; ++k) t = t + part[k][lane];
-      vec[p] = (float)t;
-    }
-  }
-}
-
-// k_reduce with narrower workgroups (round 6; k_reduce_opt_narrow below says why): CW columns per workgroup, the 64 / CW
-// lane groups of a wave on different rows
-template <int CW>
-__global__ void __launch_bounds__(1024) k_reduce_narrow(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
-                                                        const double *__restrict__ slabB, uint32_t nbB,
-                                                        float *__restrict__ vec, int useA, int useB) {
-  constexpr int GPW = 64 / CW, RG = 16 * GPW, U = 256 / RG;
-  __shared__ double part[RG][CW];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c = lane & (CW - 1), rg = w * GPW + lane / CW;
-  const uint32_t p = blockIdx.x * CW + (uint32_t)c;
-  auto partial = [&](const double *__restrict__ slab, uint32_t nb, uint32_t stride, uint32_t col) {
-    double acc = 0.0;
-    for (uint32_t r0 = (uint32_t)rg; r0 < nb; r0 += RG * U) {
-      double x[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const uint32_t r = r0 + RG * u;
-        x[u] = r < nb ? slab[(size_t)r * stride + col] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc = acc + x[u];
-    }
-    return acc;
-  };
-  double acc = 0.0;
-  if (p < P) {
-    if (useA) acc = partial(slabA, nbA, P, p);
-  } else if (p < P + 4) {
-    if (useB) acc = partial(slabB, nbB, 4, p - P);
+    for (int u = 0; u < U; ++u) acc = acc + v[u];
   }
   part[rg][c] = acc;
   __syncthreads();
-  if (threadIdx.x >= CW || p >= P + 4) return;
-  if (p < P ? useA != 0 : useB != 0) {
-    double t = part[0][c];
+  if (threadIdx.x >= CW) return 0.0;
+  double t = part[0][c];
 #pragma unroll
-    for (int k = 1; k < RG; ++k) t = t + part[k][c];
-    vec[p] = (float)t;
-  }
+  for (int k = 1; k < RG; ++k) t = t + part[k][c];
+  return t;
+}
+
+// A workgroup of 16 waves reduces CW consecutive entries of (gradient | four sums): entry p < P is column p of slab A
+// (nbA rows of P doubles), entry P + i column i of slab B (nbB rows of 4) — f64 throughout, rounded to f32 once by the
+// caller.  CW = 64: wave w sums rows w, w + 16, ... with 16 loads in flight, rows are 512-B coalesced reads.  CW = 16
+// (round 6; reduce_width below says when): 64 row groups, four times as many workgroups pull the slab, each a quarter of
+// the bytes, and a lane has 4 loads in flight instead of 16.  Either way one memory round trip covers <= 256 rows.  A
+// column's partial sums are per row group in row order, combined in group order: deterministic, and another order for
+// another CW.
+template <int CW>
+__device__ __forceinline__ double slab_column_sum(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
+                                                  const double *__restrict__ slabB, uint32_t nbB, uint32_t p,
+                                                  double (&part)[16 * (64 / CW)][CW]) {
+  constexpr int U = 256 / (16 * (64 / CW));  // loads in flight per lane
+  const bool a = p < P;
+  return column_sum<CW, U>(a ? slabA + p : slabB + (p - P), a ? nbA : p < P + 4 ? nbB : 0u, a ? P : 4u, part);
+}
+
+template <int CW>
+__global__ void __launch_bounds__(1024) k_reduce(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
+                                                 const double *__restrict__ slabB, uint32_t nbB,
+                                                 float *__restrict__ vec, int useA, int useB) {
+  __shared__ double part[16 * (64 / CW)][CW];
+  const uint32_t p = blockIdx.x * CW + (threadIdx.x & (CW - 1));
+  const double t = slab_column_sum<CW>(slabA, useA ? nbA : 0u, P, slabB, useB ? nbB : 0u, p, part);
+  if (threadIdx.x >= CW || p >= P + 4) return;
+  if (p < P ? useA != 0 : useB != 0) vec[p] = (float)t;
 }
 
 // ---------------------------------------------------------------- single-workgroup bookkeeping kernels
@@ -605,6 +578,31 @@ __device__ __forceinline__ float opt_apply(float p, float g, float &s0, float &s
   return rule_rmsprop(p, g, s0, s1, s2, k);
 }
 
+// One column of the optimiser's step, in two pieces so that a kernel may put work between them (k_reduce_opt requests the
+// column first and the slab rows behind it): load() reads the old parameter and the state words the rule has (none to
+// three), step() applies the rule to gradient entry g and stores the state words and the new parameter — and the
+// parameter's pieces in the module's weight image, which the lane that owns parameter i owns as well (bf16_tile.hpp; the
+// next fused launch reads the weights as piece fragments; NULL when this call has built no image).
+template <int RULE>
+struct OptColumn {
+  float p = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+  __device__ __forceinline__ void load(const float *__restrict__ params, const OptState &st, uint32_t i, uint32_t flags) {
+    p = params[i];
+    if (opt_has_slot<RULE>(0, flags)) s0 = st.s0[i];
+    if (opt_has_slot<RULE>(1, flags)) s1 = st.s1[i];
+    if (opt_has_slot<RULE>(2, flags)) s2 = st.s2[i];
+  }
+  __device__ __forceinline__ void step(float *__restrict__ params, const OptState &st, uint32_t i, float g, const OptStep &k,
+                                       uint32_t *__restrict__ wimg, int A) {
+    const float w = opt_apply<RULE>(p, g, s0, s1, s2, k);
+    if (opt_has_slot<RULE>(0, k.flags)) st.s0[i] = s0;
+    if (opt_has_slot<RULE>(1, k.flags)) st.s1[i] = s1;
+    if (opt_has_slot<RULE>(2, k.flags)) st.s2[i] = s2;
+    params[i] = w;
+    if (wimg) bt::wimg_store_param(wimg, i, w, A);
+  }
+};
+
 // The stand-alone step: behind an all-reduce, a recurrent or general module's reduction, or a host gradient.
 template <int RULE>
 __global__ void __launch_bounds__(SB) k_opt_step(float *__restrict__ params, const float *__restrict__ grad, OptState st,
@@ -613,33 +611,29 @@ __global__ void __launch_bounds__(SB) k_opt_step(float *__restrict__ params, con
                                                  float *__restrict__ loss_out, const int32_t *comm_err,
                                                  uint32_t *__restrict__ wimg, int A,
                                                  const uint32_t *__restrict__ veto) {
-  if (comm_failed(comm_err)) return;  // `grad` holds local sums: no step, no step count
-  if (veto != nullptr && *veto != 0u) return;  // the range guard refused the pass `grad` comes from: nothing is applied
+  // the range guard's veto word (set by a fused launch of the pass `grad` comes from, or an earlier one of the call: the
+  // sums are then not to be applied; bf16_tile.hpp range_guard)
+  const uint32_t vetoed = veto != nullptr ? *veto : 0u;
+  if (comm_failed(comm_err)) return;  // a failed exchange: `grad` holds local sums — no step, no step count
+  if (vetoed != 0u) return;  // parameters, optimiser state and step count stay as they are
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     *step_ptr = step;
     if (loss_out) *loss_out = (float)((double)(*loss_sum) * inv_B);
   }
   for (uint32_t i = blockIdx.x * SB + threadIdx.x; i < P; i += gridDim.x * SB) {  // (elementwise: any grid)
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-    if (opt_has_slot<RULE>(0, k.flags)) s0 = st.s0[i];
-    if (opt_has_slot<RULE>(1, k.flags)) s1 = st.s1[i];
-    if (opt_has_slot<RULE>(2, k.flags)) s2 = st.s2[i];
-    const float w = opt_apply<RULE>(params[i], grad[i], s0, s1, s2, k);
-    if (opt_has_slot<RULE>(0, k.flags)) st.s0[i] = s0;
-    if (opt_has_slot<RULE>(1, k.flags)) st.s1[i] = s1;
-    if (opt_has_slot<RULE>(2, k.flags)) st.s2[i] = s2;
-    params[i] = w;
-    if (wimg) bt::wimg_store_param(wimg, i, w, A);  // (the module's weight image stays current, bf16_tile.hpp)
+    OptColumn<RULE> col;
+    col.load(params, st, i, k.flags);
+    col.step(params, st, i, grad[i], k, wimg, A);
   }
 }
 
-// k_reduce followed by the optimiser step on the 64 entries each workgroup has just reduced (every rule is elementwise,
+// k_reduce followed by the optimiser step on the CW entries each workgroup has just reduced (every rule is elementwise,
 // so no second launch is needed when no all-reduce sits between the two: single-rank runs).  Same arithmetic as
 // k_reduce + k_opt_step; `step` is the 1-based step index, tracked by the host.
 // XCHG: with several ranks on the peer-mailbox transport, wave 0 exchanges the 64 reduced columns of the workgroup (one
 // chunk of the collective, comm_ipc.hpp) between the reduction and the optimiser step — the multi-rank critic loop stays
 // at two launches per step (built for Adam only; the other rules take reduce, exchange, k_opt_step)
-template <int RULE, bool XCHG>
+template <int RULE, int CW, bool XCHG>
 __global__ void __launch_bounds__(1024) k_reduce_opt(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
                                                      const double *__restrict__ slabB, uint32_t nbB,
                                                      float *__restrict__ vec, float *__restrict__ params, OptState st,
@@ -647,33 +641,22 @@ __global__ void __launch_bounds__(1024) k_reduce_opt(const double *__restrict__ 
                                                      float *__restrict__ loss_out, IpcPeers peers,
                                                      uint32_t *__restrict__ wimg, int A,
                                                      const uint32_t *__restrict__ veto) {
-  __shared__ double part[16][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint32_t p = blockIdx.x * 64 + lane;
-  // the optimiser state of this column (none to three words, by the rule) is requested first, so that it arrives under
-  // the slab loads — and the range guard's veto word with it (set by the fused launch this one reduces, or an earlier one
-  // of the call: the sums are then not to be applied; bf16_tile.hpp range_guard)
+  static_assert(!XCHG || CW == 64, "a chunk of the mailbox exchange is 64 columns");
+  __shared__ double part[16 * (64 / CW)][CW];
+  const uint32_t p = blockIdx.x * CW + (threadIdx.x & (CW - 1));
+  // the optimiser's column (the old parameter and none to three state words, by the rule) is requested first, so that it
+  // arrives under the slab loads — and with it the range guard's veto word (set by the fused launch this one reduces, or
+  // an earlier one of the call: the sums are then not to be applied; bf16_tile.hpp range_guard)
   const uint32_t vetoed = veto != nullptr ? *veto : 0u;
-  float p_old = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-  if (w == 0 && p < P) {
-    p_old = params[p];
-    if (opt_has_slot<RULE>(0, k.flags)) s0 = st.s0[p];
-    if (opt_has_slot<RULE>(1, k.flags)) s1 = st.s1[p];
-    if (opt_has_slot<RULE>(2, k.flags)) s2 = st.s2[p];
-  }
-  double acc = 0.0;
-  if (p < P) acc = column_partial(slabA, nbA, P, p, w);
-  else if (p < P + 4) acc = column_partial(slabB, nbB, 4, p - P, w);
-  part[w][lane] = acc;
-  __syncthreads();
-  if (w != 0) return;
-  double t = part[0][lane];
-#pragma unroll
-  for (int r = 1; r < 16; ++r) t = t + part[r][lane];
+  OptColumn<RULE> col;
+  if (threadIdx.x < CW && p < P) col.load(params, st, p, k.flags);
+  const double t = slab_column_sum<CW>(slabA, nbA, P, slabB, nbB, p, part);
+  if (threadIdx.x >= CW) return;
   float gsum = (float)t;
-  if (XCHG) {  // all 64 lanes; a failed exchange (sticky error word, comm_ipc.hpp) leaves vec, params and state alone
+  if (XCHG) {  // all 64 lanes of wave 0
     float total;
-    if (!ipc_exchange_chunk(peers, blockIdx.x, (uint32_t)lane, p < P + 4 ? gsum : 0.0f, total)) return;
+    // a failed exchange (sticky error word, comm_ipc.hpp): `gsum` is a local sum — vec stays too, no step, no step count
+    if (!ipc_exchange_chunk(peers, blockIdx.x, threadIdx.x, p < P + 4 ? gsum : 0.0f, total)) return;
     gsum = total;
   }
   if (p >= P + 4) return;
@@ -684,80 +667,7 @@ __global__ void __launch_bounds__(1024) k_reduce_opt(const double *__restrict__ 
   }
   if (vetoed != 0u) return;  // parameters, optimiser state and step count stay as they are
   if (p == 0) *step_ptr = step;
-  const float w_new = opt_apply<RULE>(p_old, gsum, s0, s1, s2, k);
-  if (opt_has_slot<RULE>(0, k.flags)) st.s0[p] = s0;
-  if (opt_has_slot<RULE>(1, k.flags)) st.s1[p] = s1;
-  if (opt_has_slot<RULE>(2, k.flags)) st.s2[p] = s2;
-  params[p] = w_new;
-  // the next fused launch reads the weights as piece fragments: this lane owns parameter p, it also owns p's pieces in
-  // the module's weight image (bf16_tile.hpp; NULL when this call has built none)
-  if (wimg) bt::wimg_store_param(wimg, p, w_new, A);
-}
-
-// The same launch with NARROWER workgroups (round 6): CW = 16 or 32 columns per workgroup instead of 64, the 64 / CW lane
-// groups of a wave taking different rows — four (two) times as many workgroups pull the slab, each a quarter (half) of
-// the bytes, and a lane has 4 (8) loads in flight instead of 16.  A column's partial sums are per row group r, r + RG, ...
-// (RG = 16 x 64 / CW groups) in row order, combined in group order: deterministic, another order than the wide form.
-// (No mailbox exchange here: its chunks are 64 columns.)
-template <int RULE, int CW>
-__global__ void __launch_bounds__(1024) k_reduce_opt_narrow(const double *__restrict__ slabA, uint32_t nbA, uint32_t P,
-                                                            const double *__restrict__ slabB, uint32_t nbB,
-                                                            float *__restrict__ vec, float *__restrict__ params,
-                                                            OptState st, uint64_t *step_ptr, uint64_t step, OptStep k,
-                                                            double inv_B, float *__restrict__ loss_out,
-                                                            uint32_t *__restrict__ wimg, int A,
-                                                            const uint32_t *__restrict__ veto) {
-  constexpr int GPW = 64 / CW, RG = 16 * GPW;  // row groups per wave, per workgroup
-  __shared__ double part[RG][CW];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c = lane & (CW - 1), rg = w * GPW + lane / CW;
-  const uint32_t p = blockIdx.x * CW + (uint32_t)c;
-  const uint32_t vetoed = veto != nullptr ? *veto : 0u;  // (the range guard's veto: k_reduce_opt)
-  float p_old = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-  if (threadIdx.x < CW && p < P) {  // the optimiser state of this column arrives under the slab loads
-    p_old = params[p];
-    if (opt_has_slot<RULE>(0, k.flags)) s0 = st.s0[p];
-    if (opt_has_slot<RULE>(1, k.flags)) s1 = st.s1[p];
-    if (opt_has_slot<RULE>(2, k.flags)) s2 = st.s2[p];
-  }
-  auto partial = [&](const double *__restrict__ slab, uint32_t nb, uint32_t stride, uint32_t col) {
-    constexpr int U = 256 / RG;  // loads in flight per lane: one memory round trip for <= 256 rows
-    double acc = 0.0;
-    for (uint32_t r0 = (uint32_t)rg; r0 < nb; r0 += RG * U) {
-      double x[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const uint32_t r = r0 + RG * u;
-        x[u] = r < nb ? slab[(size_t)r * stride + col] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc = acc + x[u];
-    }
-    return acc;
-  };
-  double acc = 0.0;
-  if (p < P) acc = partial(slabA, nbA, P, p);
-  else if (p < P + 4) acc = partial(slabB, nbB, 4, p - P);
-  part[rg][c] = acc;
-  __syncthreads();
-  if (threadIdx.x >= CW || p >= P + 4) return;
-  double t = part[0][c];
-#pragma unroll
-  for (int r = 1; r < RG; ++r) t = t + part[r][c];
-  const float gsum = (float)t;
-  vec[p] = gsum;
-  if (p >= P) {
-    if (p == P && loss_out) *loss_out = (float)((double)gsum * inv_B);
-    return;
-  }
-  if (vetoed != 0u) return;
-  if (p == 0) *step_ptr = step;
-  const float w_new = opt_apply<RULE>(p_old, gsum, s0, s1, s2, k);
-  if (opt_has_slot<RULE>(0, k.flags)) st.s0[p] = s0;
-  if (opt_has_slot<RULE>(1, k.flags)) st.s1[p] = s1;
-  if (opt_has_slot<RULE>(2, k.flags)) st.s2[p] = s2;
-  params[p] = w_new;
-  if (wimg) bt::wimg_store_param(wimg, p, w_new, A);
+  col.step(params, st, p, gsum, k, wimg, A);
 }
 
 // ---------------------------------------------------------------- launchers
@@ -840,15 +750,21 @@ void launch_mlp_backward(rl_traj *traj, const rl_mlp *mlp, const int32_t *d_skip
 // (vectors of more than 2,048 entries — the recurrent chains, wide general MLPs — are bandwidth-, not latency-bound and
 // keep the wide form)
 static int reduce_width(uint32_t P) { return P + 4 > 2048 ? 64 : 16; }
+// the instantiation of a width (never a branch inside a kernel)
+#define RL_WITH_WIDTH(WIDTH, CALL)         \
+  if ((WIDTH) == 64) {                     \
+    constexpr int CW = 64;                 \
+    CALL;                                  \
+  } else {                                 \
+    constexpr int CW = 16;                 \
+    CALL;                                  \
+  }
 
 void launch_reduce(rl_traj *traj, uint32_t P, bool useA, bool useB, uint32_t rowsA, uint32_t rowsB) {
   ProfScope ps(traj->eng, RL_K_REDUCE);
-  if (reduce_width(P) == 64)
-    hipLaunchKernelGGL(k_reduce, dim3(cdiv(P + 4, 64)), dim3(1024), 0, traj->eng->stream, traj->slabA, rowsA, P,
-                       traj->slabB, rowsB, traj->vec, useA ? 1 : 0, useB ? 1 : 0);
-  else
-    hipLaunchKernelGGL(k_reduce_narrow<16>, dim3(cdiv(P + 4, 16)), dim3(1024), 0, traj->eng->stream, traj->slabA, rowsA,
-                       P, traj->slabB, rowsB, traj->vec, useA ? 1 : 0, useB ? 1 : 0);
+  RL_WITH_WIDTH(reduce_width(P),
+                hipLaunchKernelGGL(k_reduce<CW>, dim3(cdiv(P + 4, CW)), dim3(1024), 0, traj->eng->stream, traj->slabA,
+                                   rowsA, P, traj->slabB, rowsB, traj->vec, useA ? 1 : 0, useB ? 1 : 0));
 }
 
 void launch_trpo_begin(rl_traj *traj, rl_mlp *policy, uint64_t B_total) {
@@ -914,7 +830,7 @@ void launch_ls_finalize(rl_traj *traj, rl_mlp *policy, double max_kl, int accept
 
 // The constants of the optimiser's NEXT step (advances the host's step count): every rule's scalars are formed in f64 here
 // and rounded to f32 once; Adam's and AdamW's bias corrections and SGD's first-step flag follow the step count.
-static OptStep adam_next_step(rl_adam *opt) {
+static OptStep opt_next_step(rl_adam *opt) {
   if (opt->error_epoch != opt->eng->error_epoch) {
     // an entry point failed on this engine since this optimiser last stepped: launches of it may have been vetoed on the
     // device (a failed exchange, the range guard) after the host had counted them — the device's count is the truth
@@ -967,42 +883,35 @@ static OptStep adam_next_step(rl_adam *opt) {
     default: throw RlError(RL_ERR_INVALID_ARGUMENT, "optimizer: unknown kind");       \
   }
 
-void launch_reduce_adam(rl_traj *traj, rl_adam *opt, uint32_t rowsA, uint32_t rowsB, int loss_slot,
-                        uint64_t B_total) {
+void launch_reduce_opt(rl_traj *traj, rl_adam *opt, uint32_t rowsA, uint32_t rowsB, int loss_slot, uint64_t B_total) {
   ProfScope ps(traj->eng, RL_K_REDUCE);
   uint32_t P = (uint32_t)opt->mod->P;
   rl_engine *e = traj->eng;
   RL_REQUIRE(!e->ipc_active || opt->cfg.kind == RL_OPTIMIZER_ADAM,
              "the exchange inside the reduction launch is built for Adam only");
-  const OptStep k = adam_next_step(opt);
+  const OptStep k = opt_next_step(opt);
   const OptState st{opt->d_state[0], opt->d_state[1], opt->d_state[2]};
   float *loss_out = loss_slot >= 0 ? traj->losses + loss_slot : (float *)nullptr;
+  // (RULE and CW are constants where this is expanded)
+#define REDUCE_OPT(XCHG, PEERS)                                                                                          \
+  hipLaunchKernelGGL((k_reduce_opt<RULE, CW, XCHG>), dim3(cdiv(P + 4, CW)), dim3(1024), 0, e->stream, traj->slabA, rowsA, \
+                     P, traj->slabB, rowsB, traj->vec, opt->mod->d_params, st, opt->d_step, opt->host_step, k,            \
+                     1.0 / (double)B_total, loss_out, PEERS, wimg_if_current(opt->mod), (int)opt->mod->out_dim,           \
+                     veto_word(traj, opt->mod))
   if (e->ipc_active) {
     ProfScope pa(e, RL_K_ALLREDUCE);  // counted as a collective as well: the exchange runs inside this launch
-    const IpcPeers peers = ipc_peers_next(e);
-    hipLaunchKernelGGL((k_reduce_opt<RL_OPTIMIZER_ADAM, true>), dim3(cdiv(P + 4, 64)), dim3(1024), 0, e->stream,
-                       traj->slabA, rowsA, P, traj->slabB, rowsB, traj->vec, opt->mod->d_params, st, opt->d_step,
-                       opt->host_step, k, 1.0 / (double)B_total, loss_out, peers, wimg_if_current(opt->mod),
-                       (int)opt->mod->out_dim, veto_word(traj, opt->mod));
-  } else if (reduce_width(P) != 64) {
-    RL_WITH_RULE(opt->cfg.kind,
-                 hipLaunchKernelGGL((k_reduce_opt_narrow<RULE, 16>), dim3(cdiv(P + 4, 16)), dim3(1024), 0, e->stream,
-                                    traj->slabA, rowsA, P, traj->slabB, rowsB, traj->vec, opt->mod->d_params, st,
-                                    opt->d_step, opt->host_step, k, 1.0 / (double)B_total, loss_out,
-                                    wimg_if_current(opt->mod), (int)opt->mod->out_dim, veto_word(traj, opt->mod)));
+    constexpr int RULE = RL_OPTIMIZER_ADAM, CW = 64;  // (a chunk of the exchange is 64 columns)
+    REDUCE_OPT(true, ipc_peers_next(e));
   } else {
-    RL_WITH_RULE(opt->cfg.kind,
-                 hipLaunchKernelGGL((k_reduce_opt<RULE, false>), dim3(cdiv(P + 4, 64)), dim3(1024), 0, e->stream,
-                                    traj->slabA, rowsA, P, traj->slabB, rowsB, traj->vec, opt->mod->d_params, st,
-                                    opt->d_step, opt->host_step, k, 1.0 / (double)B_total, loss_out, IpcPeers{},
-                                    wimg_if_current(opt->mod), (int)opt->mod->out_dim, veto_word(traj, opt->mod)));
+    RL_WITH_RULE(opt->cfg.kind, RL_WITH_WIDTH(reduce_width(P), REDUCE_OPT(false, IpcPeers{})));
   }
+#undef REDUCE_OPT
 }
 
-static void launch_opt_step(rl_adam *opt, hipStream_t stream, const float *d_grad, const float *loss_sum, double inv_B,
-                            float *loss_out, const int32_t *comm_err, const uint32_t *veto) {
+static void enqueue_opt_step(rl_adam *opt, hipStream_t stream, const float *d_grad, const float *loss_sum, double inv_B,
+                             float *loss_out, const int32_t *comm_err, const uint32_t *veto) {
   uint32_t P = (uint32_t)opt->mod->P;
-  const OptStep k = adam_next_step(opt);
+  const OptStep k = opt_next_step(opt);
   const OptState st{opt->d_state[0], opt->d_state[1], opt->d_state[2]};
   RL_WITH_RULE(opt->cfg.kind,
                hipLaunchKernelGGL(k_opt_step<RULE>, dim3((P + SB - 1) / SB), dim3(SB), 0, stream, opt->mod->d_params,
@@ -1010,16 +919,16 @@ static void launch_opt_step(rl_adam *opt, hipStream_t stream, const float *d_gra
                                   wimg_if_current(opt->mod), (int)opt->mod->out_dim, veto));
 }
 
-void launch_adam_step(rl_traj *traj, rl_adam *opt, int loss_slot, uint64_t B_total) {
+void launch_opt_step(rl_traj *traj, rl_adam *opt, int loss_slot, uint64_t B_total) {
   ProfScope ps(traj->eng, RL_K_SMALL);
   uint32_t P = (uint32_t)opt->mod->P;
-  launch_opt_step(opt, traj->eng->stream, traj->vec, traj->vec + P, 1.0 / (double)B_total,
-                  loss_slot >= 0 ? traj->losses + loss_slot : (float *)nullptr, comm_err_word(traj->eng),
-                  veto_word(traj, opt->mod));
+  enqueue_opt_step(opt, traj->eng->stream, traj->vec, traj->vec + P, 1.0 / (double)B_total,
+                   loss_slot >= 0 ? traj->losses + loss_slot : (float *)nullptr, comm_err_word(traj->eng),
+                   veto_word(traj, opt->mod));
 }
 
-void launch_adam_step_vec(rl_adam *opt, const float *d_grad) {
+void launch_opt_step_vec(rl_adam *opt, const float *d_grad) {
   ProfScope ps(opt->mod->eng, RL_K_SMALL);
-  launch_opt_step(opt, opt->mod->eng->stream, d_grad, (const float *)nullptr, 0.0, (float *)nullptr,
-                  (const int32_t *)nullptr, (const uint32_t *)nullptr);
+  enqueue_opt_step(opt, opt->mod->eng->stream, d_grad, (const float *)nullptr, 0.0, (float *)nullptr,
+                   (const int32_t *)nullptr, (const uint32_t *)nullptr);
 }

@@ -1,5 +1,5 @@
 """80 critic steps at 8,192 x 128 with each first-order rule (profiling target: the per-launch time of the reduce + step
-kernel per rule, one instantiation of k_reduce_opt_narrow each).
+kernel per rule, one instantiation of k_reduce_opt<RULE, 16, false> each).
 usage: rocprofv3 --kernel-trace --stats ... -- python3 scripts/optimizer_rules.py [lanes] [steps]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

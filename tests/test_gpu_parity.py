@@ -688,9 +688,9 @@ def test_rccl_call_path_single_rank():
 # ---------------------------------------------------------------- round 6: the weight image and the shared return plane
 def test_weight_image_kept_by_the_parameter_writers_equals_a_fresh_one(engine):
     """The fused kernels read their weight pieces from the module's weight image (relearn_amd/csrc/bf16_tile.hpp): built
-    by the first fused launch of a C-ABI call, then kept current by the kernels that write the parameters (k_reduce_adam
+    by the first fused launch of a C-ABI call, then kept current by the kernels that write the parameters (k_reduce_opt
     for the critic, k_ls_set_params for the line search's candidates).  A K-step critic update in ONE call (steps 2..K
-    read the image k_reduce_adam left) must equal K one-step calls (every call rebuilds the image from the flat vector)
+    read the image k_reduce_opt left) must equal K one-step calls (every call rebuilds the image from the flat vector)
     bit for bit; and the loss / KL the line search accepted (evaluated on an image k_ls_set_params wrote) must be the
     numbers rl_policy_loss_kl computes for the same two parameter vectors from images built from scratch."""
     n, T, K = 2048, 32, 6
