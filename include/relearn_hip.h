@@ -424,7 +424,10 @@ typedef enum {
   RL_TRAJ_REWARD = 2,    /* f32 [T][n] */
   RL_TRAJ_FLAG = 3,      /* u8  [T][n] successor code */
   RL_TRAJ_TERM_OBS = 4,  /* f32 [obs_dim][T][n], valid where flag == INTERRUPT */
-  RL_TRAJ_VALUES = 5,    /* f32 [T+1][n] critic values of OBS (after rl_gae) */
+  RL_TRAJ_VALUES = 5,    /* f32 [T+1][n] critic values of OBS (after rl_gae, or a OneStepTd rl_values_opt_update); slot T
+                          * is V(obs[T]) of every lane for a feed-forward critic, whatever ended step T-1.  A recurrent
+                          * critic has no fresh-state value of obs[T] behind an episode end: there slot T holds what step
+                          * T-1 bootstrapped from — 0 after Terminate, V(successor observation) otherwise */
   RL_TRAJ_ADVANTAGES = 6,/* f32 [T][n] */
   RL_TRAJ_RETURNS = 7,   /* f32 [T][n] discounted reward-to-go */
   RL_TRAJ_TARGETS = 8    /* f32 [T][n] value targets of the last rl_values_opt_update (StepValueTarget::targets) */

@@ -529,9 +529,11 @@ static void check_values_opt(const rl_mlp *critic, const rl_adam *opt, const rl_
 // read them — the helper says which of the two places, and with it which scan goes with them:
 //   VALUES_IN_PLANE   traj->d.values [T+1][n] (the fused 5-H-1 forward): launch_gae / launch_value_targets
 //   VALUES_IN_ARRAYS  traj->seq.out / seq.succ (the general and the recurrent forwards): launch_seq_gae /
-//                     launch_seq_value_targets, which read no observation and so need no SeqScope of their own
+//                     launch_seq_value_targets, which read no observation and so need no SeqScope of their own;
+//                     *v_last <- V(obs[T]) of every lane where the forward has it (the general one), else NULL
 enum ValueLayout { VALUES_IN_PLANE, VALUES_IN_ARRAYS };
-static ValueLayout value_forward(rl_traj *traj, const rl_mlp *critic) {
+static ValueLayout value_forward(rl_traj *traj, const rl_mlp *critic, const float **v_last) {
+  *v_last = nullptr;
   if (rl_module_is_recurrent(critic->kind)) {
     SeqScope sc(traj, critic);
     seq_ensure(traj, sc.x, false);
@@ -539,7 +541,7 @@ static ValueLayout value_forward(rl_traj *traj, const rl_mlp *critic) {
     return VALUES_IN_ARRAYS;
   }
   if (critic->general) {
-    launch_gen_values(traj, critic);
+    *v_last = launch_gen_values(traj, critic);
     return VALUES_IN_ARRAYS;
   }
   launch_values(traj, critic);
@@ -550,7 +552,8 @@ int32_t rl_gae(rl_traj *traj, const rl_mlp *critic, float gamma, float lambda) {
   return guarded(traj ? traj->eng : nullptr, [&] {
     RL_REQUIRE(traj && critic, "NULL argument");
     RL_REQUIRE(critic->in_dim == traj->d.D && critic->out_dim == 1, "critic shape does not match the trajectory");
-    if (value_forward(traj, critic) == VALUES_IN_ARRAYS) launch_seq_gae(traj, gamma, lambda);
+    const float *v_last;
+    if (value_forward(traj, critic, &v_last) == VALUES_IN_ARRAYS) launch_seq_gae(traj, gamma, lambda, v_last);
     else launch_gae(traj, critic, gamma, lambda);
   });
 }
@@ -562,14 +565,15 @@ static void values_opt_targets(rl_mlp *critic, rl_traj *traj, const rl_values_op
     traj->td = traj->mem.alloc<float>((size_t)traj->d.T * traj->d.n);
   }
   traj->d.tgt = traj->td;
+  const float *v_last;
   if (cfg->target == RL_VALUE_TARGET_REWARD_TO_GO && traj->rtg_scan_valid && traj->rtg_gamma == cfg->discount_factor) {
     // the advantage pass's lane scan has already left exactly these targets in the return plane (same recursion, same
     // operations: k_gae_scan / k_value_targets_rtg, kernels_rollout.hip) — no second scan over the rewards
     traj->d.tgt = traj->d.rtg;
   } else if (cfg->target == RL_VALUE_TARGET_REWARD_TO_GO) {
     launch_value_targets(traj, nullptr, cfg->discount_factor);
-  } else if (value_forward(traj, critic) == VALUES_IN_ARRAYS) {
-    launch_seq_value_targets(traj, cfg->discount_factor);
+  } else if (value_forward(traj, critic, &v_last) == VALUES_IN_ARRAYS) {
+    launch_seq_value_targets(traj, cfg->discount_factor, v_last);
   } else {
     launch_value_targets(traj, critic, cfg->discount_factor);
   }

@@ -157,7 +157,7 @@ constexpr int RL_GEN_CRITIC = 100;  // mode: mean((V - target)^2); else PASS_INI
 bool gen_mfma_fits(const rl_traj *t, const rl_mlp *m);
 bool launch_gen_mfma(rl_traj *t, const rl_mlp *m, int mode, const float *d_tangent, uint64_t B_total,
                      const int32_t *d_skip, float clip_lo, float clip_hi);
-void launch_gen_values(rl_traj *t, const rl_mlp *critic);  // -> seq.out / seq.succ (plane 0)
+const float *launch_gen_values(rl_traj *t, const rl_mlp *critic);  // -> seq.out / seq.succ (plane 0); returns V(obs[T]) [n]
 void launch_gen_rollout(rl_env *env, const rl_mlp *policy, rl_traj *t);
 void launch_rollout_stepwise(rl_env *env, rl_traj *t, const float *z, const std::function<void(uint32_t)> &forward);
 void launch_gen_wgrad_planes(rl_traj *t, const float *dY, size_t dys, int N, const float *X, size_t xs, int K, size_t S,
@@ -183,8 +183,10 @@ void launch_gru_train_head_backward(rl_traj *traj, const rl_mlp *mod, float *d_s
 void launch_gru_train_recur_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip);
 void launch_gru_train_wgrad(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip);
 constexpr uint32_t RL_SEQ_HEAD_ROWS = 512;  // rows of head-gradient partials behind the weight-gradient kernel's chunks
-void launch_seq_gae(rl_traj *traj, float gamma, float lambda);
-void launch_seq_value_targets(rl_traj *traj, float gamma);  // one-step TD targets from traj->seq.out / succ (plane 0) -> d.tgt
+// v_last: [n] V(obs[T]) of every lane for slot T of the value plane (a general critic's: launch_gen_values), or NULL
+void launch_seq_gae(rl_traj *traj, float gamma, float lambda, const float *v_last);
+// one-step TD targets from traj->seq.out / succ (plane 0) -> d.tgt
+void launch_seq_value_targets(rl_traj *traj, float gamma, const float *v_last);
 void launch_seq_policy_dlogits(rl_traj *traj, int mode, uint64_t B_total, float clip_lo, float clip_hi,
                                const int32_t *d_skip = nullptr);
 void launch_seq_critic_dvalues(rl_traj *traj, uint64_t B_total);

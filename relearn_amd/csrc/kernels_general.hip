@@ -809,8 +809,8 @@ void launch_gen_backward(rl_traj *t, const rl_mlp *m, const int32_t *d_skip) {
 
 // ---------------------------------------------------------------- values for GAE / TD targets
 // seq.out[0] <- V(obs[t]) for t < T, seq.succ[0] <- successor values of cut episodes (the layout launch_seq_gae and
-// launch_seq_value_targets read)
-void launch_gen_values(rl_traj *t, const rl_mlp *critic) {
+// launch_seq_value_targets read); returns V(obs[T]) of every lane, [n], for slot T of the trajectory's value plane
+const float *launch_gen_values(rl_traj *t, const rl_mlp *critic) {
   const uint64_t n = t->d.n, T = t->d.T, B = T * n;
   SeqDev &q = t->seq;
   seq_ensure_outputs(t);
@@ -831,6 +831,7 @@ void launch_gen_values(rl_traj *t, const rl_mlp *critic) {
   hipLaunchKernelGGL(k_gen_successor_values, dim3(cdiv_g(B, 256)), dim3(256), 0, t->eng->stream, t->d, g.z, g.z + B,
                      q.succ);
   fwd(t->d.obs, plane, B, q.out, nullptr);
+  return g.z + B;
 }
 
 // ---------------------------------------------------------------- rollout, one launch sequence per step

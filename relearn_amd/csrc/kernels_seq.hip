@@ -577,15 +577,25 @@ __global__ void __launch_bounds__(W16 * 64, 2) k_gru_seq_forward(TrajDev tr, con
 // ---------------------------------------------------------------- GAE with a recurrent critic
 // gae / temporal_differences / reward_to_go (critics/mod.rs:101-199) with the value of every observation and of
 // every cut episode's successor taken from the teacher-forced forward (values [T][n], succ [T][n]).  Same
-// arithmetic as k_gae_scan.  Also mirrors the values into the trajectory's [T+1][n] plane for inspection.
+// arithmetic as k_gae_scan.  Also mirrors the values into the trajectory's [T+1][n] plane for inspection: slot T is
+// V(obs[T]) where the caller has it for every lane (`v_last` [n]: a feed-forward critic), else (NULL: a recurrent
+// critic has no fresh-state value of obs[T] behind an episode end) what step T-1 bootstrapped from.
+__device__ __forceinline__ float seq_slot_T(const TrajDev &tr, const float *__restrict__ succ,
+                                            const float *__restrict__ v_last, uint32_t i) {
+  if (v_last != nullptr) return v_last[i];
+  const size_t o = (size_t)(tr.T - 1) * tr.n + i;
+  return tr.flag[o] == RL_SUCC_TERMINATE ? 0.0f : succ[o];
+}
+
 __global__ void __launch_bounds__(64) k_seq_gae(TrajDev tr, const float *__restrict__ values,
-                                                const float *__restrict__ succ, float gamma, float lambda) {
+                                                const float *__restrict__ succ, const float *__restrict__ v_last,
+                                                float gamma, float lambda) {
   const uint32_t n = tr.n, T = tr.T;
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float disc = lambda * gamma;
   float adv_next = 0.0f, rtg_next = 0.0f, v_next = 0.0f;
-  tr.values[(size_t)T * n + i] = succ[(size_t)(T - 1) * n + i];
+  tr.values[(size_t)T * n + i] = seq_slot_T(tr, succ, v_last, i);
   // the inputs of 16 steps are requested before the chain walks through them (k_gae_scan, kernels_rollout.hip: one
   // memory round trip per 16 steps instead of one per step)
   constexpr int AHEAD = 16;
@@ -650,7 +660,8 @@ __global__ void __launch_bounds__(64) k_seq_gae(TrajDev tr, const float *__restr
 // one_step_values (critics/mod.rs:139-150) with a recurrent critic: next values from the teacher-forced forward
 // (values [T][n]; succ [T][n] where an episode is cut), same selection rule as k_seq_gae; also mirrors the values
 __global__ void __launch_bounds__(256) k_seq_value_targets_td(TrajDev tr, const float *__restrict__ values,
-                                                              const float *__restrict__ succ, float gamma) {
+                                                              const float *__restrict__ succ,
+                                                              const float *__restrict__ v_last, float gamma) {
   const uint32_t n = tr.n, T = tr.T;
   const size_t B = (size_t)T * n;
   const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -664,22 +675,22 @@ __global__ void __launch_bounds__(256) k_seq_value_targets_td(TrajDev tr, const 
   const float dn = gamma * vn;
   tr.tgt[o] = tr.reward[o] + dn;
   tr.values[o] = values[o];
-  if (t == T - 1) tr.values[o + n] = succ[o];
+  if (t == T - 1) tr.values[o + n] = seq_slot_T(tr, succ, v_last, (uint32_t)(o - (size_t)t * n));
 }
 
-void launch_seq_value_targets(rl_traj *traj, float gamma) {
+void launch_seq_value_targets(rl_traj *traj, float gamma, const float *v_last) {
   ProfScope ps(traj->eng, RL_K_GAE);
   const size_t B = (size_t)traj->d.T * traj->d.n;
   hipLaunchKernelGGL(k_seq_value_targets_td, dim3(cdiv_s(B, 256)), dim3(256), 0, traj->eng->stream, traj->d,
-                     traj->seq.out, traj->seq.succ, gamma);
+                     traj->seq.out, traj->seq.succ, v_last, gamma);
 }
 
-void launch_seq_gae(rl_traj *traj, float gamma, float lambda) {
+void launch_seq_gae(rl_traj *traj, float gamma, float lambda, const float *v_last) {
   traj->rtg_scan_valid = false;  // (this scan writes the return plane too; only k_gae_scan's is vouched for, engine.hpp)
   ProfScope ps(traj->eng, RL_K_GAE);
   uint32_t n = traj->d.n;
   hipLaunchKernelGGL(k_seq_gae, dim3(cdiv_s(n, 64)), dim3(64), 0, traj->eng->stream, traj->d, traj->seq.out,
-                     traj->seq.succ, gamma, lambda);
+                     traj->seq.succ, v_last, gamma, lambda);
 }
 
 // ---------------------------------------------------------------- other widths embedded in the built shape

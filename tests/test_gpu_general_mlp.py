@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import advantage_cases as ac
 import oracle as O
 import relearn_amd as ra
 
@@ -74,6 +75,14 @@ def jvp64(net, tnet, x, act="Relu", out_act="Identity"):
         h, slope = act64(act if i + 1 < len(net) else out_act, h @ W.T + b)
         th = th * slope
     return h, th
+
+
+def check_scan_planes(traj, hist, cri, in_dim, hidden, act="Relu", out_act="Identity", bias=True):
+    """RL_TRAJ_VALUES / ADVANTAGES / RETURNS after rl_gae(traj, cri, 0.99, 0.95) against the oracle's forward and its
+    array-fed scan (tests/advantage_cases.py), bit for bit"""
+    e = ac.general_expectation((in_dim, hidden, act, bias), cri.get_params(), hist, 0.99, 0.95, out_act=out_act)
+    assert np.array_equal(traj.read(ra.TRAJ_VALUES), e["values"])
+    assert np.array_equal(traj.read(ra.TRAJ_ADVANTAGES), e["adv"]) and np.array_equal(traj.read(ra.TRAJ_RETURNS), e["rtg"])
 
 
 def make(engine, in_dim, hidden, out_dim, seed, act="Relu", out_act="Identity"):
@@ -197,6 +206,7 @@ def test_other_input_widths_on_host_made_histories(engine, in_dim, hidden, n, T)
     v = forward64(cnet, x)[0][:, 0]
     assert np.allclose(traj.read(ra.TRAJ_VALUES)[:T].reshape(-1), v, rtol=2e-5, atol=2e-6)
     adv, rtg = traj.read(ra.TRAJ_ADVANTAGES).reshape(-1), traj.read(ra.TRAJ_RETURNS).reshape(-1)
+    check_scan_planes(traj, want, cri, in_dim, hidden)
     z, acts = forward64(pnet, x)
     lp = z - np.log(np.exp(z - z.max(axis=1, keepdims=True)).sum(axis=1, keepdims=True)) - z.max(axis=1, keepdims=True)
     p = np.exp(lp)
@@ -303,6 +313,7 @@ def test_gradients_and_fisher_vector_products(engine, hidden, act, out_act):
     assert np.allclose(traj.read(ra.TRAJ_VALUES)[:T].reshape(-1), v, rtol=2e-5, atol=2e-6)
     adv, rtg = traj.read(ra.TRAJ_ADVANTAGES).reshape(-1), traj.read(ra.TRAJ_RETURNS).reshape(-1)
     assert np.isfinite(adv).all() and np.abs(adv).max() > 0
+    check_scan_planes(traj, tr, cri, 5, hidden, act, out_act)
     # ---- policy gradient: loss = -mean(A log pi(a)) at ratio 1 (Trpo / Reinforce closure)
     pnet = unflatten(pol.get_params(), 5, hidden, 2)
     z, acts = forward64(pnet, x, act, out_act)
@@ -419,8 +430,12 @@ def test_updates_run_and_improve(engine, hidden):
     assert losses[-1] < losses[0]
     vcfg = ra.values_opt_config_default()
     vcfg.opt_steps_per_update, vcfg.target, vcfg.discount_factor = 3, ra.VALUE_TARGET_ONE_STEP_TD, 0.99
+    c_before, hist = cri.get_params(), traj.read_all()
     vs, vl = ra.values_opt_update(cri, ra.Adam(cri), traj, vcfg, want_losses=True)
     assert np.isfinite(vl).all()
+    # the targets come from the critic as it stood before the first step: the oracle's forward and its array-fed targets
+    e = ac.general_expectation((5, hidden, "Relu", True), c_before, hist, td_gamma=0.99)
+    assert np.array_equal(traj.read(ra.TRAJ_TARGETS), e["td"]) and np.array_equal(traj.read(ra.TRAJ_VALUES), e["values"])
     ppo = ra.ppo_config_default()
     ppo.opt_steps_per_update = 3
     ps, pl = ra.ppo_update(pol, ra.Adam(pol), traj, ppo, want_losses=True)
@@ -605,6 +620,7 @@ def test_layers_without_bias_vectors(engine, hidden, act, out_act):
     B = n * T
     xs = tr["obs"][:, :T, :].reshape(5, B).T
     adv, rtg = traj.read(ra.TRAJ_ADVANTAGES).reshape(-1), traj.read(ra.TRAJ_RETURNS).reshape(-1)
+    check_scan_planes(traj, tr, cri, 5, hidden, act, out_act, bias=False)
     pnet = unflatten(with_zero_biases(p, 5, hidden, 2), 5, hidden, 2)
     cnet = unflatten(with_zero_biases(c, 5, hidden, 1), 5, hidden, 1)
     z, acts = forward64(pnet, xs, act, out_act)
