@@ -778,6 +778,69 @@ int32_t rl_summary_clear(rl_summary *s, int32_t forget_episodes_in_progress);
 int32_t rl_steps_summary_merge(const rl_steps_summary *a, const rl_steps_summary *b, rl_steps_summary *out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Bandit baselines on the meta-bandit lanes: the `eval` half of relearn_experiments/src/bin/rl2-bandits.rs (:166-261) —
+ * a classical bandit algorithm run over RL_ENV_META_BANDIT lanes, the figure a learned RL^2 policy is judged against.
+ * The actor is ResettingMetaAgent<TC> (src/agents/meta.rs:135-199) over SerialActorAgent (src/agents/serial.rs:43-95):
+ * a fresh inner agent per trial, the inner actor always in Training mode, min_update_size {1, 0} — every pull updates
+ * the inner agent at once.  TC by `kind`:
+ *   RL_BANDIT_AGENT_RANDOM     RandomAgentConfig (src/agents/random.rs:59-73): act = IndexSpace::sample =
+ *                              gen_range(0..k) (spaces/index.rs:65-67); no state
+ *   RL_BANDIT_AGENT_TABULAR_Q  TabularQLearningAgentConfig { exploration_rate, initial_action_count,
+ *                              initial_action_value } (src/agents/tabular.rs:21-51, 113-133, 159-180, 222-232): act
+ *                              draws one gen::<f64>() — always, also at rate 0 — and takes gen_range(0..k) when the draw
+ *                              is < exploration_rate, else the FIRST maximal value (ndarray-stats argmax); update, as
+ *                              separate operations: count += 1; w = 1 / count; v *= 1 - w; v += w * reward (a bandit
+ *                              step terminates: no successor value).  The experiment's EpsGreedy is (0.2, 2, 0.5), its
+ *                              Greedy (0.0, 2, 0.5)
+ *   RL_BANDIT_AGENT_UCB1       UCB1AgentConfig { exploration_rate } (src/agents/bandits/ucb.rs:106-160, 209-234): per
+ *                              trial mean[a] = 0.5, count[a] = 2, visit = 2 k; act computes ucb[a] = sqrt(L /
+ *                              (double)count[a]) * exploration_rate + mean[a] with L = 2.0 * ln((double)visit) and takes
+ *                              the LAST maximal index (utils/iter/cmp.rs:58; a trial's first pull is arm k - 1), no
+ *                              draw; update: visit += 1; count += 1; mean += (scaled - mean) / (double)count with
+ *                              scaled = (reward + (-0.0)) * 1.0 (rewards declared in [0, 1], bandits.rs:161-163, 220-222)
+ * All arithmetic is f64 in exactly these operations and this order, no contraction.  `ln` is taken of integers only
+ * and never on the device: at creation the host fills L[j] = 2.0 * log((double)(2 k + j)), j = 0 .. E - 1 (E episodes
+ * per trial), and the j-th pull of a trial reads L[j]; UCB1 with E > 1,048,576 -> RL_ERR_UNSUPPORTED.
+ * Per step of the meta env (meta.rs:159-198): an observation that shows a finished inner episode updates the inner
+ * agent with that pull, the action is some_element() = 0 and nothing is drawn (every restart step records action 0);
+ * otherwise the inner actor acts.  A lane gets a fresh inner agent whenever its env state is at the start of a trial
+ * (no inner episode done, no previous step, all E episodes left) — after an Interrupt's auto-reset, at the first step
+ * ever and after rl_env_reset alike; a horizon that cuts a trial leaves the agent's state in the handle and the next
+ * collection carries on.  Draws are sequential from the lane's ACTOR stream (ChaCha8 of seed_actor, stream = global
+ * lane id): a u64 is two words, low first; gen::<f64>() is rl_u64_to_unit_f64, gen_range is rand 0.8.5's
+ * UniformInt::sample_single.  The next unread word is per-lane state of the handle: 0 at creation, never rewound
+ * (the policy rollouts' word t_global + t does not apply: these actors draw a varying number of words per step). */
+typedef struct rl_bandit_agent rl_bandit_agent;
+enum { RL_BANDIT_AGENT_RANDOM = 0, RL_BANDIT_AGENT_TABULAR_Q = 1, RL_BANDIT_AGENT_UCB1 = 2 };
+typedef struct {
+  int32_t kind;                  /* RL_BANDIT_AGENT_* */
+  int32_t reserved;              /* 0 */
+  double exploration_rate;       /* TABULAR_Q: epsilon; UCB1: the confidence scale; RANDOM: unused */
+  uint64_t initial_action_count; /* TABULAR_Q */
+  double initial_action_value;   /* TABULAR_Q */
+} rl_bandit_agent_config;
+/* the reference's Default impls: TABULAR_Q (0.2, 0, 0.0) (tabular.rs:43-51), UCB1 0.2 (ucb.rs:36-42), RANDOM nothing;
+ * an unknown kind -> RL_ERR_INVALID_ARGUMENT */
+int32_t rl_bandit_agent_config_default(int32_t kind, rl_bandit_agent_config *cfg);
+/* The handle takes the env's lane count, arm count k and E, and owns its per-lane state and the ln table on the
+ * device.  `env` must be RL_ENV_META_BANDIT (else RL_ERR_UNSUPPORTED, naming this entry point).
+ * RL_ERR_INVALID_ARGUMENT, naming the field: a negative or non-finite exploration_rate / initial_action_value, a
+ * TABULAR_Q exploration_rate above 1, reserved != 0, an unknown kind. */
+int32_t rl_bandit_agent_create(rl_env *env, const rl_bandit_agent_config *cfg, rl_bandit_agent **out);
+int32_t rl_bandit_agent_destroy(rl_bandit_agent *agent);
+/* T = the trajectory's horizon steps of every lane in one launch.  Leaves in `traj` exactly what rl_rollout leaves:
+ * RL_TRAJ_OBS (slot T included), ACTION, REWARD, FLAG, TERM_OBS where a trial was cut by its Interrupt; the env's step
+ * counter advances by T.  `env` must have the lanes, arms and episodes per trial the agent was made on, the trajectory
+ * the env's shape (RL_ERR_INVALID_ARGUMENT). */
+int32_t rl_bandit_agent_rollout(rl_bandit_agent *agent, rl_env *env, rl_traj *traj);
+/* The agent's state AFTER the updates of all pulls recorded so far, lane-minor; a wrong byte count or a field the
+ * kind does not have (RANDOM: only ACTOR_POS; TABULAR_Q: no VISITS, no LN_TABLE) -> RL_ERR_INVALID_ARGUMENT. */
+enum { RL_BANDIT_STATE_ACTOR_POS = 0 /* u64 [n]: next unread word of the lane's actor stream */,
+       RL_BANDIT_STATE_COUNTS = 1 /* u64 [k][n] */, RL_BANDIT_STATE_VALUES = 2 /* f64 [k][n]: values / means */,
+       RL_BANDIT_STATE_VISITS = 3 /* u64 [n] */, RL_BANDIT_STATE_LN_TABLE = 4 /* f64 [E] */ };
+int32_t rl_bandit_agent_state_read(rl_bandit_agent *agent, int32_t field, void *host, uint64_t bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * Actor serialisation in the reference's on-disk format: the CBOR document that
  * `serde_cbor::to_writer(file, &agent.actor(ActorMode::Evaluation))` writes (examples/cartpole-trpo.rs:71-76,
  * examples/cartpole-dqn.rs) and `serde_cbor::from_reader` loads for evaluation (:82-93).

@@ -30,6 +30,10 @@ BANDITS_UNIFORM_BERNOULLI, BANDITS_ONE_HOT, BANDITS_ROUND_ROBIN = 0, 1, 2
 BANDIT_DISTRIBUTIONS = {"uniform_bernoulli": BANDITS_UNIFORM_BERNOULLI, "one_hot": BANDITS_ONE_HOT,
                         "round_robin": BANDITS_ROUND_ROBIN}
 LIMIT_NONE, LIMIT_LATENT, LIMIT_VISIBLE = 0, 1, 2
+BANDIT_AGENT_RANDOM, BANDIT_AGENT_TABULAR_Q, BANDIT_AGENT_UCB1 = 0, 1, 2
+BANDIT_AGENT_KINDS = {"random": BANDIT_AGENT_RANDOM, "tabular_q": BANDIT_AGENT_TABULAR_Q, "ucb1": BANDIT_AGENT_UCB1}
+(BANDIT_STATE_ACTOR_POS, BANDIT_STATE_COUNTS, BANDIT_STATE_VALUES, BANDIT_STATE_VISITS,
+ BANDIT_STATE_LN_TABLE) = range(5)
 (TRAJ_OBS, TRAJ_ACTION, TRAJ_REWARD, TRAJ_FLAG, TRAJ_TERM_OBS, TRAJ_VALUES, TRAJ_ADVANTAGES,
  TRAJ_RETURNS, TRAJ_TARGETS) = range(9)
 VALUE_TARGET_REWARD_TO_GO, VALUE_TARGET_ONE_STEP_TD = 0, 1
@@ -64,6 +68,8 @@ ABI_SYMBOLS = [
     "rl_chain_tabular_q_train", "rl_chain_tabular_q_eval",
     "rl_summary_create", "rl_summary_destroy", "rl_summary_push", "rl_summary_push_dqn", "rl_summary_read",
     "rl_summary_clear", "rl_steps_summary_merge",
+    "rl_bandit_agent_config_default", "rl_bandit_agent_create", "rl_bandit_agent_destroy", "rl_bandit_agent_rollout",
+    "rl_bandit_agent_state_read",
 ]
 
 
@@ -207,7 +213,7 @@ def _register(obj):
 @atexit.register
 def _close_all():
     objs = list(_live)
-    order = {"StepsSummary": -1, "Dqn": -1, "Adam": 0, "Optimizer": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "MetaBanditEnv": 2, "Mlp": 3, "GruMlp": 3,
+    order = {"StepsSummary": -1, "Dqn": -1, "BanditAgent": -1, "Adam": 0, "Optimizer": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "MetaBanditEnv": 2, "Mlp": 3, "GruMlp": 3,
              "Engine": 4}
     for o in sorted(objs, key=lambda o: order.get(type(o).__name__, 2)):
         o.close()
@@ -1095,6 +1101,67 @@ class StepsSummary(_Handle):
     def clear(self, forget=False):
         """a new period; forget=True also drops the episodes in progress (after an env reset)"""
         _check(lib().rl_summary_clear(self.h, C.c_int32(1 if forget else 0)), self.eng.h)
+
+
+class BanditAgentConfig(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("exploration_rate", C.c_double),
+                ("initial_action_count", C.c_uint64), ("initial_action_value", C.c_double)]
+
+
+def bandit_agent_config_default(kind):
+    """the reference's Default impls: TABULAR_Q (0.2, 0, 0.0), UCB1 0.2; `kind` a BANDIT_AGENT_* integer or its name"""
+    cfg = BanditAgentConfig()
+    _check(lib().rl_bandit_agent_config_default(C.c_int32(BANDIT_AGENT_KINDS.get(kind, kind)), C.byref(cfg)))
+    return cfg
+
+
+class BanditAgent(_Handle):
+    """A classical bandit algorithm on meta-bandit lanes (rl_bandit_agent_*): `ResettingMetaAgent` over RandomAgentConfig
+    ("random"), TabularQLearningAgentConfig ("tabular_q": eps-greedy; greedy at rate 0) or UCB1AgentConfig ("ucb1") — a
+    fresh inner agent per trial, every pull updates it.  Arguments left None keep the reference's defaults."""
+
+    def __init__(self, env, kind, exploration_rate=None, initial_action_count=None, initial_action_value=None):
+        self.eng, self.n, self.k = env.eng, env.n, env.A
+        self.E = int(env.meta.episodes_per_trial) if hasattr(env, "meta") else 0
+        cfg = bandit_agent_config_default(kind)
+        if exploration_rate is not None:
+            cfg.exploration_rate = exploration_rate
+        if initial_action_count is not None:
+            cfg.initial_action_count = initial_action_count
+        if initial_action_value is not None:
+            cfg.initial_action_value = initial_action_value
+        self.cfg, self.kind = cfg, cfg.kind
+        self.h = C.c_void_p()
+        _check(lib().rl_bandit_agent_create(env.h, C.byref(cfg), C.byref(self.h)), env.eng.h)
+        _register(self)
+
+    def close(self):
+        if self.h:
+            lib().rl_bandit_agent_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def rollout(self, env, traj):
+        """traj.T steps of every lane in one launch; leaves in `traj` what `rollout(env, policy, traj)` leaves"""
+        _check(lib().rl_bandit_agent_rollout(self.h, env.h, traj.h), self.eng.h)
+
+    def read(self, field):
+        shape, dtype = {BANDIT_STATE_ACTOR_POS: ((self.n,), np.uint64), BANDIT_STATE_COUNTS: ((self.k, self.n), np.uint64),
+                        BANDIT_STATE_VALUES: ((self.k, self.n), np.float64), BANDIT_STATE_VISITS: ((self.n,), np.uint64),
+                        BANDIT_STATE_LN_TABLE: ((self.E,), np.float64)}[field]
+        out = np.zeros(shape, dtype)
+        _check(lib().rl_bandit_agent_state_read(self.h, C.c_int32(field), out.ctypes.data_as(C.c_void_p),
+                                                C.c_uint64(out.nbytes)), self.eng.h)
+        return out
+
+    def state(self):
+        """the fields this kind has, AFTER the updates of all pulls recorded so far: "pos" u64 [n]; "counts" u64 [k][n],
+        "values" f64 [k][n] (tabular_q, ucb1); "visits" u64 [n], "ln_table" f64 [E] (ucb1)"""
+        st = {"pos": self.read(BANDIT_STATE_ACTOR_POS)}
+        if self.kind != BANDIT_AGENT_RANDOM:
+            st["counts"], st["values"] = self.read(BANDIT_STATE_COUNTS), self.read(BANDIT_STATE_VALUES)
+        if self.kind == BANDIT_AGENT_UCB1:
+            st["visits"], st["ln_table"] = self.read(BANDIT_STATE_VISITS), self.read(BANDIT_STATE_LN_TABLE)
+        return st
 
 
 def steps_summary_merge(a, b):

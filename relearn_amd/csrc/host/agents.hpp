@@ -1145,4 +1145,63 @@ inline void train_batched(ActorCriticAgent &agent, EnvLanes &env, DeviceHistory 
   }
 }
 
+// ---------------------------------------------------------------- bandit baselines (src/agents/meta.rs, bandits/)
+// The inner-agent configurations of relearn_experiments/src/bin/rl2-bandits.rs `eval` (:166-261) that the library runs on
+// the meta-bandit lanes, each with the reference's Default.  `raw()` is the C ABI's rl_bandit_agent_config.
+struct RandomAgentConfig {  // src/agents/random.rs:59-73: act = action_space.sample(rng)
+  rl_bandit_agent_config raw() const { return rl_bandit_agent_config{RL_BANDIT_AGENT_RANDOM, 0, 0.0, 0, 0.0}; }
+};
+struct TabularQLearningAgentConfig {  // src/agents/tabular.rs:21-51
+  double exploration_rate = 0.2;
+  uint64_t initial_action_count = 0;
+  double initial_action_value = 0.0;
+  rl_bandit_agent_config raw() const {
+    return rl_bandit_agent_config{RL_BANDIT_AGENT_TABULAR_Q, 0, exploration_rate, initial_action_count,
+                                  initial_action_value};
+  }
+};
+struct UCB1AgentConfig {  // src/agents/bandits/ucb.rs:18-42
+  double exploration_rate = 0.2;
+  rl_bandit_agent_config raw() const { return rl_bandit_agent_config{RL_BANDIT_AGENT_UCB1, 0, exploration_rate, 0, 0.0}; }
+};
+
+// ResettingMetaAgent<TC> (src/agents/meta.rs:21-199) over the lanes of a MetaBanditLanes: one inner agent per lane, built
+// fresh from `TC` wherever the lane's trial starts, acting in Training mode and updated after every pull
+// (SerialActorAgent, src/agents/serial.rs:43-95).  `collect` is the batched form of Actor::act driven by
+// Environment::run: all steps of a horizon in one launch.  No updates at the meta level (meta.rs:201-227).
+class ResettingMetaAgent {
+ public:
+  template <typename TC>
+  ResettingMetaAgent(MetaBanditLanes &env, const TC &inner_agent_config) : eng_(env.engine()), n_lanes_(env.num_lanes()) {
+    const rl_bandit_agent_config c = inner_agent_config.raw();
+    check(rl_bandit_agent_create(env.handle(), &c, &h_), eng_.handle());
+    n_arms_ = env.num_actions();
+  }
+  ~ResettingMetaAgent() { rl_bandit_agent_destroy(h_); }
+  ResettingMetaAgent(const ResettingMetaAgent &) = delete;
+  ResettingMetaAgent &operator=(const ResettingMetaAgent &) = delete;
+  rl_bandit_agent *handle() const { return h_; }
+  // history.horizon() steps of every lane of the env the agent was built on
+  void collect(MetaBanditLanes &env, DeviceHistory &history) {
+    check(rl_bandit_agent_rollout(h_, env.handle(), history.handle()), eng_.handle());
+  }
+  // the inner agents after the updates of all pulls so far: the next unread word of each lane's actor stream, the
+  // per-arm selection counts and values / mean rewards [n_arms][n_lanes] (not for RandomAgentConfig)
+  std::vector<uint64_t> actor_word_positions() const { return read<uint64_t>(RL_BANDIT_STATE_ACTOR_POS, n_lanes_); }
+  std::vector<uint64_t> action_counts() const { return read<uint64_t>(RL_BANDIT_STATE_COUNTS, n_arms_ * n_lanes_); }
+  std::vector<double> action_values() const { return read<double>(RL_BANDIT_STATE_VALUES, n_arms_ * n_lanes_); }
+
+ private:
+  template <typename T>
+  std::vector<T> read(int32_t field, uint64_t count) const {
+    std::vector<T> v(count);
+    check(rl_bandit_agent_state_read(h_, field, v.data(), count * sizeof(T)), eng_.handle());
+    return v;
+  }
+  Engine &eng_;
+  rl_bandit_agent *h_ = nullptr;
+  uint64_t n_lanes_;
+  uint32_t n_arms_ = 0;
+};
+
 }  // namespace relearn
