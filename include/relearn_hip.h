@@ -798,7 +798,19 @@ int32_t rl_steps_summary_merge(const rl_steps_summary *a, const rl_steps_summary
  *                              the LAST maximal index (utils/iter/cmp.rs:58; a trial's first pull is arm k - 1), no
  *                              draw; update: visit += 1; count += 1; mean += (scaled - mean) / (double)count with
  *                              scaled = (reward + (-0.0)) * 1.0 (rewards declared in [0, 1], bandits.rs:161-163, 220-222)
- * All arithmetic is f64 in exactly these operations and this order, no contraction.  `ln` is taken of integers only
+ *   RL_BANDIT_AGENT_THOMPSON   BetaThompsonSamplingAgentConfig { num_samples } (src/agents/bandits/thompson_sampling.rs:
+ *                              95-136, 186-205): per trial a low and a high reward count per arm, u64, both 1; act, for
+ *                              arms 0 .. k - 1 in order, builds Beta::new((double)high, (double)low), draws num_samples
+ *                              samples in sequence and sums them as 0.0 + x1 + x2 + ...; the LAST maximal sum wins
+ *                              (Iterator::max_by, utils/iter/cmp.rs:68-74); update: reward > 0.5 ? high += 1 : low += 1
+ *                              (the midpoint of the declared interval [0, 1], bandits.rs:161-163, 220-222).  The
+ *                              experiment's TS is num_samples 1, its OTS 10 (rl2-bandits.rs:213-216).  The Beta sampler
+ *                              is the engine's own statement, include/rl_beta.h: Cheng's BB / BC over rl_log / rl_exp of
+ *                              rl_detmath.h and rl_u64_to_open01_f64 of rl_chacha.h, at most 64 attempts per sample,
+ *                              4 words per attempt — build-defined as the Prng stream is; equality with rand_distr
+ *                              0.4.3 is conditional on a check against its source, and the reference, which calls the
+ *                              platform's ln / exp here, is not reproducible across libms either
+ * All arithmetic is f64 in exactly these operations and this order, no contraction.  UCB1 takes `ln` of integers only
  * and never on the device: at creation the host fills L[j] = 2.0 * log((double)(2 k + j)), j = 0 .. E - 1 (E episodes
  * per trial), and the j-th pull of a trial reads L[j]; UCB1 with E > 1,048,576 -> RL_ERR_UNSUPPORTED.
  * Per step of the meta env (meta.rs:159-198): an observation that shows a finished inner episode updates the inner
@@ -811,21 +823,25 @@ int32_t rl_steps_summary_merge(const rl_steps_summary *a, const rl_steps_summary
  * UniformInt::sample_single.  The next unread word is per-lane state of the handle: 0 at creation, never rewound
  * (the policy rollouts' word t_global + t does not apply: these actors draw a varying number of words per step). */
 typedef struct rl_bandit_agent rl_bandit_agent;
-enum { RL_BANDIT_AGENT_RANDOM = 0, RL_BANDIT_AGENT_TABULAR_Q = 1, RL_BANDIT_AGENT_UCB1 = 2 };
+enum { RL_BANDIT_AGENT_RANDOM = 0, RL_BANDIT_AGENT_TABULAR_Q = 1, RL_BANDIT_AGENT_UCB1 = 2, /* 3 is left unassigned */
+       RL_BANDIT_AGENT_THOMPSON = 4 };
 typedef struct {
   int32_t kind;                  /* RL_BANDIT_AGENT_* */
   int32_t reserved;              /* 0 */
   double exploration_rate;       /* TABULAR_Q: epsilon; UCB1: the confidence scale; RANDOM: unused */
-  uint64_t initial_action_count; /* TABULAR_Q */
+  uint64_t initial_action_count; /* TABULAR_Q; THOMPSON: num_samples, 1 .. 1024 */
   double initial_action_value;   /* TABULAR_Q */
 } rl_bandit_agent_config;
-/* the reference's Default impls: TABULAR_Q (0.2, 0, 0.0) (tabular.rs:43-51), UCB1 0.2 (ucb.rs:36-42), RANDOM nothing;
- * an unknown kind -> RL_ERR_INVALID_ARGUMENT */
+/* the reference's Default impls: TABULAR_Q (0.2, 0, 0.0) (tabular.rs:43-51), UCB1 0.2 (ucb.rs:36-42), THOMPSON
+ * num_samples 1 (thompson_sampling.rs, BetaThompsonSamplingAgentConfig::default), RANDOM nothing; an unknown kind ->
+ * RL_ERR_INVALID_ARGUMENT */
 int32_t rl_bandit_agent_config_default(int32_t kind, rl_bandit_agent_config *cfg);
 /* The handle takes the env's lane count, arm count k and E, and owns its per-lane state and the ln table on the
  * device.  `env` must be RL_ENV_META_BANDIT (else RL_ERR_UNSUPPORTED, naming this entry point).
  * RL_ERR_INVALID_ARGUMENT, naming the field: a negative or non-finite exploration_rate / initial_action_value, a
- * TABULAR_Q exploration_rate above 1, reserved != 0, an unknown kind. */
+ * TABULAR_Q exploration_rate above 1, reserved != 0, an unknown kind, a THOMPSON num_samples of 0.  A THOMPSON
+ * num_samples above 1,024 -> RL_ERR_UNSUPPORTED, naming num_samples: the bound keeps the one launch's length in hand
+ * on a shared device and is no limit of the reference's (the experiment uses 1 and 10). */
 int32_t rl_bandit_agent_create(rl_env *env, const rl_bandit_agent_config *cfg, rl_bandit_agent **out);
 int32_t rl_bandit_agent_destroy(rl_bandit_agent *agent);
 /* T = the trajectory's horizon steps of every lane in one launch.  Leaves in `traj` exactly what rl_rollout leaves:
@@ -834,10 +850,12 @@ int32_t rl_bandit_agent_destroy(rl_bandit_agent *agent);
  * the env's shape (RL_ERR_INVALID_ARGUMENT). */
 int32_t rl_bandit_agent_rollout(rl_bandit_agent *agent, rl_env *env, rl_traj *traj);
 /* The agent's state AFTER the updates of all pulls recorded so far, lane-minor; a wrong byte count or a field the
- * kind does not have (RANDOM: only ACTOR_POS; TABULAR_Q: no VISITS, no LN_TABLE) -> RL_ERR_INVALID_ARGUMENT. */
+ * kind does not have (RANDOM: only ACTOR_POS; TABULAR_Q: no VISITS, no LN_TABLE; THOMPSON: ACTOR_POS, LOW_COUNTS and
+ * HIGH_COUNTS, which no other kind has) -> RL_ERR_INVALID_ARGUMENT. */
 enum { RL_BANDIT_STATE_ACTOR_POS = 0 /* u64 [n]: next unread word of the lane's actor stream */,
        RL_BANDIT_STATE_COUNTS = 1 /* u64 [k][n] */, RL_BANDIT_STATE_VALUES = 2 /* f64 [k][n]: values / means */,
-       RL_BANDIT_STATE_VISITS = 3 /* u64 [n] */, RL_BANDIT_STATE_LN_TABLE = 4 /* f64 [E] */ };
+       RL_BANDIT_STATE_VISITS = 3 /* u64 [n] */, RL_BANDIT_STATE_LN_TABLE = 4 /* f64 [E] */,
+       RL_BANDIT_STATE_LOW_COUNTS = 5 /* u64 [k][n], THOMPSON */, RL_BANDIT_STATE_HIGH_COUNTS = 6 /* u64 [k][n], THOMPSON */ };
 int32_t rl_bandit_agent_state_read(rl_bandit_agent *agent, int32_t field, void *host, uint64_t bytes);
 
 /* ---------------------------------------------------------------------------------------------

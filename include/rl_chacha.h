@@ -78,6 +78,14 @@ RL_HDC float rl_u32_to_unit_f32(uint32_t w) { return (float)(w >> 8) * 5.9604644
 /* rand 0.8 `Standard` f64: 53 high bits scaled into [0, 1). */
 RL_HDC double rl_u64_to_unit_f64(uint64_t w) { return (double)(w >> 11) * 1.1102230246251565e-16; }
 
+/* rand 0.8.5 `Open01` f64: the [1,2) mantissa trick minus (1 - 2^-53): one u64 into [2^-53, 1 - 2^-53], both ends
+ * exact (the subtraction of two doubles in [1, 2) with a 2^-52 grid is exact). */
+RL_HDC double rl_u64_to_open01_f64(uint64_t w) {
+  union { uint64_t u; double d; } c;
+  c.u = (w >> 12) | 0x3ff0000000000000ULL;
+  return c.d - (1.0 - 1.1102230246251565e-16);
+}
+
 /* rand 0.8.5 `UniformFloat<f64>::sample`: [1,2) mantissa trick, then `v * scale + low`
  * (two roundings, not fused). `scale` comes from rl_uniform_f64_inclusive_scale. */
 RL_HDC double rl_uniform_f64_from_u64(uint64_t w, double low, double scale) {

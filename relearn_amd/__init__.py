@@ -31,9 +31,11 @@ BANDIT_DISTRIBUTIONS = {"uniform_bernoulli": BANDITS_UNIFORM_BERNOULLI, "one_hot
                         "round_robin": BANDITS_ROUND_ROBIN}
 LIMIT_NONE, LIMIT_LATENT, LIMIT_VISIBLE = 0, 1, 2
 BANDIT_AGENT_RANDOM, BANDIT_AGENT_TABULAR_Q, BANDIT_AGENT_UCB1 = 0, 1, 2
-BANDIT_AGENT_KINDS = {"random": BANDIT_AGENT_RANDOM, "tabular_q": BANDIT_AGENT_TABULAR_Q, "ucb1": BANDIT_AGENT_UCB1}
+BANDIT_AGENT_THOMPSON = 4  # (3 is unassigned)
+BANDIT_AGENT_KINDS = {"random": BANDIT_AGENT_RANDOM, "tabular_q": BANDIT_AGENT_TABULAR_Q, "ucb1": BANDIT_AGENT_UCB1,
+                      "thompson": BANDIT_AGENT_THOMPSON}
 (BANDIT_STATE_ACTOR_POS, BANDIT_STATE_COUNTS, BANDIT_STATE_VALUES, BANDIT_STATE_VISITS,
- BANDIT_STATE_LN_TABLE) = range(5)
+ BANDIT_STATE_LN_TABLE, BANDIT_STATE_LOW_COUNTS, BANDIT_STATE_HIGH_COUNTS) = range(7)
 (TRAJ_OBS, TRAJ_ACTION, TRAJ_REWARD, TRAJ_FLAG, TRAJ_TERM_OBS, TRAJ_VALUES, TRAJ_ADVANTAGES,
  TRAJ_RETURNS, TRAJ_TARGETS) = range(9)
 VALUE_TARGET_REWARD_TO_GO, VALUE_TARGET_ONE_STEP_TD = 0, 1
@@ -1109,7 +1111,8 @@ class BanditAgentConfig(C.Structure):
 
 
 def bandit_agent_config_default(kind):
-    """the reference's Default impls: TABULAR_Q (0.2, 0, 0.0), UCB1 0.2; `kind` a BANDIT_AGENT_* integer or its name"""
+    """the reference's Default impls: TABULAR_Q (0.2, 0, 0.0), UCB1 0.2, THOMPSON num_samples 1 (in
+    initial_action_count); `kind` a BANDIT_AGENT_* integer or its name"""
     cfg = BanditAgentConfig()
     _check(lib().rl_bandit_agent_config_default(C.c_int32(BANDIT_AGENT_KINDS.get(kind, kind)), C.byref(cfg)))
     return cfg
@@ -1117,10 +1120,12 @@ def bandit_agent_config_default(kind):
 
 class BanditAgent(_Handle):
     """A classical bandit algorithm on meta-bandit lanes (rl_bandit_agent_*): `ResettingMetaAgent` over RandomAgentConfig
-    ("random"), TabularQLearningAgentConfig ("tabular_q": eps-greedy; greedy at rate 0) or UCB1AgentConfig ("ucb1") — a
-    fresh inner agent per trial, every pull updates it.  Arguments left None keep the reference's defaults."""
+    ("random"), TabularQLearningAgentConfig ("tabular_q": eps-greedy; greedy at rate 0), UCB1AgentConfig ("ucb1") or
+    BetaThompsonSamplingAgentConfig ("thompson": `num_samples` 1 is the experiment's TS, 10 its OTS) — a fresh inner agent
+    per trial, every pull updates it.  Arguments left None keep the reference's defaults."""
 
-    def __init__(self, env, kind, exploration_rate=None, initial_action_count=None, initial_action_value=None):
+    def __init__(self, env, kind, exploration_rate=None, initial_action_count=None, initial_action_value=None,
+                 num_samples=None):
         self.eng, self.n, self.k = env.eng, env.n, env.A
         self.E = int(env.meta.episodes_per_trial) if hasattr(env, "meta") else 0
         cfg = bandit_agent_config_default(kind)
@@ -1130,6 +1135,10 @@ class BanditAgent(_Handle):
             cfg.initial_action_count = initial_action_count
         if initial_action_value is not None:
             cfg.initial_action_value = initial_action_value
+        if num_samples is not None:
+            if cfg.kind != BANDIT_AGENT_THOMPSON:
+                raise ValueError("num_samples belongs to a \"thompson\" agent")
+            cfg.initial_action_count = num_samples  # the field's second meaning (include/relearn_hip.h)
         self.cfg, self.kind = cfg, cfg.kind
         self.h = C.c_void_p()
         _check(lib().rl_bandit_agent_create(env.h, C.byref(cfg), C.byref(self.h)), env.eng.h)
@@ -1147,7 +1156,9 @@ class BanditAgent(_Handle):
     def read(self, field):
         shape, dtype = {BANDIT_STATE_ACTOR_POS: ((self.n,), np.uint64), BANDIT_STATE_COUNTS: ((self.k, self.n), np.uint64),
                         BANDIT_STATE_VALUES: ((self.k, self.n), np.float64), BANDIT_STATE_VISITS: ((self.n,), np.uint64),
-                        BANDIT_STATE_LN_TABLE: ((self.E,), np.float64)}[field]
+                        BANDIT_STATE_LN_TABLE: ((self.E,), np.float64),
+                        BANDIT_STATE_LOW_COUNTS: ((self.k, self.n), np.uint64),
+                        BANDIT_STATE_HIGH_COUNTS: ((self.k, self.n), np.uint64)}[field]
         out = np.zeros(shape, dtype)
         _check(lib().rl_bandit_agent_state_read(self.h, C.c_int32(field), out.ctypes.data_as(C.c_void_p),
                                                 C.c_uint64(out.nbytes)), self.eng.h)
@@ -1155,8 +1166,12 @@ class BanditAgent(_Handle):
 
     def state(self):
         """the fields this kind has, AFTER the updates of all pulls recorded so far: "pos" u64 [n]; "counts" u64 [k][n],
-        "values" f64 [k][n] (tabular_q, ucb1); "visits" u64 [n], "ln_table" f64 [E] (ucb1)"""
+        "values" f64 [k][n] (tabular_q, ucb1); "visits" u64 [n], "ln_table" f64 [E] (ucb1); "low", "high" u64 [k][n]
+        (thompson)"""
         st = {"pos": self.read(BANDIT_STATE_ACTOR_POS)}
+        if self.kind == BANDIT_AGENT_THOMPSON:
+            st["low"], st["high"] = self.read(BANDIT_STATE_LOW_COUNTS), self.read(BANDIT_STATE_HIGH_COUNTS)
+            return st
         if self.kind != BANDIT_AGENT_RANDOM:
             st["counts"], st["values"] = self.read(BANDIT_STATE_COUNTS), self.read(BANDIT_STATE_VALUES)
         if self.kind == BANDIT_AGENT_UCB1:

@@ -4,18 +4,25 @@
 #include "abi_internal.hpp"
 #include "bandit_agent.hpp"
 
+namespace {
+bool known_kind(int32_t kind) {  // (3 is unassigned)
+  return kind == RL_BANDIT_AGENT_RANDOM || kind == RL_BANDIT_AGENT_TABULAR_Q || kind == RL_BANDIT_AGENT_UCB1 ||
+         kind == RL_BANDIT_AGENT_THOMPSON;
+}
+}  // namespace
+
 extern "C" {
 
-// TabularQLearningAgentConfig::default (tabular.rs:43-51), UCB1AgentConfig::default (ucb.rs:36-42)
+// TabularQLearningAgentConfig::default (tabular.rs:43-51), UCB1AgentConfig::default (ucb.rs:36-42),
+// BetaThompsonSamplingAgentConfig::default (thompson_sampling.rs: num_samples 1, carried by initial_action_count)
 int32_t rl_bandit_agent_config_default(int32_t kind, rl_bandit_agent_config *cfg) {
   return guarded(nullptr, [&] {
     RL_REQUIRE(cfg, "config is NULL");
-    RL_REQUIRE(kind == RL_BANDIT_AGENT_RANDOM || kind == RL_BANDIT_AGENT_TABULAR_Q || kind == RL_BANDIT_AGENT_UCB1,
-               "rl_bandit_agent_config_default: unknown kind");
+    RL_REQUIRE(known_kind(kind), "rl_bandit_agent_config_default: unknown kind");
     cfg->kind = kind;
     cfg->reserved = 0;
-    cfg->exploration_rate = kind == RL_BANDIT_AGENT_RANDOM ? 0.0 : 0.2;
-    cfg->initial_action_count = 0;
+    cfg->exploration_rate = kind == RL_BANDIT_AGENT_TABULAR_Q || kind == RL_BANDIT_AGENT_UCB1 ? 0.2 : 0.0;
+    cfg->initial_action_count = kind == RL_BANDIT_AGENT_THOMPSON ? 1 : 0;
     cfg->initial_action_value = 0.0;
   });
 }
@@ -27,10 +34,18 @@ int32_t rl_bandit_agent_create(rl_env *env, const rl_bandit_agent_config *cfg, r
     if (env->kind != RL_ENV_META_BANDIT)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_bandit_agent_create is built for RL_ENV_META_BANDIT lanes");
     const int32_t kind = cfg->kind;
-    RL_REQUIRE(kind == RL_BANDIT_AGENT_RANDOM || kind == RL_BANDIT_AGENT_TABULAR_Q || kind == RL_BANDIT_AGENT_UCB1,
-               "rl_bandit_agent_create: unknown kind");
+    RL_REQUIRE(known_kind(kind), "rl_bandit_agent_create: unknown kind");
     RL_REQUIRE(cfg->reserved == 0, "rl_bandit_agent_create: reserved must be 0");
-    if (kind != RL_BANDIT_AGENT_RANDOM) {
+    const bool thompson = kind == RL_BANDIT_AGENT_THOMPSON;
+    if (thompson) {  // initial_action_count carries num_samples
+      RL_REQUIRE(cfg->initial_action_count != 0,
+                 "rl_bandit_agent_create: num_samples (initial_action_count of a THOMPSON agent) must not be 0");
+      if (cfg->initial_action_count > RL_BANDIT_NUM_SAMPLES_MAX)
+        throw RlError(RL_ERR_UNSUPPORTED, "rl_bandit_agent_create: num_samples (initial_action_count of a THOMPSON "
+                                          "agent) is at most 1024: every pull draws k * num_samples Beta samples "
+                                          "within the one launch");
+    }
+    if (kind == RL_BANDIT_AGENT_TABULAR_Q || kind == RL_BANDIT_AGENT_UCB1) {
       RL_REQUIRE(std::isfinite(cfg->exploration_rate) && cfg->exploration_rate >= 0.0,
                  "rl_bandit_agent_create: exploration_rate must be finite and not negative");
       RL_REQUIRE(kind != RL_BANDIT_AGENT_TABULAR_Q || cfg->exploration_rate <= 1.0,
@@ -59,7 +74,15 @@ int32_t rl_bandit_agent_create(rl_env *env, const rl_bandit_agent_config *cfg, r
     uint64_t *pos = a->mem.alloc<uint64_t>(n);
     d.pos = pos;
     RL_HIP_CHECK(hipMemsetAsync(pos, 0, n * sizeof(uint64_t), e->stream));
-    if (kind != RL_BANDIT_AGENT_RANDOM) {  // a fresh inner agent per lane (the kernel makes one again at every trial's start)
+    if (thompson) {  // BetaThompsonSamplingAgent::new: one low and one high reward per arm
+      d.num_samples = (uint32_t)cfg->initial_action_count;
+      uint64_t *low = a->mem.alloc<uint64_t>(k * n), *high = a->mem.alloc<uint64_t>(k * n);
+      d.low = low;
+      d.high = high;
+      const std::vector<uint64_t> ones(k * n, 1);
+      h2d(e, low, ones.data(), k * n * sizeof(uint64_t));
+      h2d(e, high, ones.data(), k * n * sizeof(uint64_t));
+    } else if (kind != RL_BANDIT_AGENT_RANDOM) {  // a fresh inner agent per lane (the kernel makes one again at every trial's start)
       const bool ucb = kind == RL_BANDIT_AGENT_UCB1;
       d.count = a->mem.alloc<uint64_t>(k * n);
       d.value = a->mem.alloc<double>(k * n);
@@ -125,6 +148,8 @@ int32_t rl_bandit_agent_state_read(rl_bandit_agent *agent, int32_t field, void *
       case RL_BANDIT_STATE_VALUES: src = d.value, want = agent->k * agent->n * sizeof(double); break;
       case RL_BANDIT_STATE_VISITS: src = d.visit, want = agent->n * sizeof(uint64_t); break;
       case RL_BANDIT_STATE_LN_TABLE: src = d.ln2, want = agent->E * sizeof(double); break;
+      case RL_BANDIT_STATE_LOW_COUNTS: src = d.low, want = agent->k * agent->n * sizeof(uint64_t); break;
+      case RL_BANDIT_STATE_HIGH_COUNTS: src = d.high, want = agent->k * agent->n * sizeof(uint64_t); break;
       default: throw RlError(RL_ERR_INVALID_ARGUMENT, "rl_bandit_agent_state_read: unknown field");
     }
     RL_REQUIRE(src != nullptr, "rl_bandit_agent_state_read: an agent of this kind has no such field");

@@ -7,6 +7,8 @@
 
 // UCB1: the table holds 2 ln(visit) for every pull of a trial, one f64 each (8 MiB at the bound)
 constexpr uint64_t RL_BANDIT_LN_TABLE_MAX = 1ull << 20;
+// THOMPSON: a pull draws k * num_samples Beta samples in the one launch; the bound keeps that launch's length in hand
+constexpr uint64_t RL_BANDIT_NUM_SAMPLES_MAX = 1024;
 
 // The inner agents' state, one per lane, lane-minor.  Views into rl_bandit_agent::mem.
 struct BanditAgentDev {
@@ -18,6 +20,9 @@ struct BanditAgentDev {
   double rate;        // exploration_rate
   double init_value;  // TABULAR_Q: initial_action_value
   uint64_t init_count;  // TABULAR_Q: initial_action_count
+  uint64_t *low;      // [k][n] THOMPSON: low_reward_count (NULL otherwise)
+  uint64_t *high;     // [k][n] THOMPSON: high_reward_count (NULL otherwise)
+  uint32_t num_samples;  // THOMPSON: samples summed per arm and pull
 };
 
 struct rl_bandit_agent {

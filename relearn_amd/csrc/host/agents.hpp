@@ -1164,6 +1164,14 @@ struct UCB1AgentConfig {  // src/agents/bandits/ucb.rs:18-42
   double exploration_rate = 0.2;
   rl_bandit_agent_config raw() const { return rl_bandit_agent_config{RL_BANDIT_AGENT_UCB1, 0, exploration_rate, 0, 0.0}; }
 };
+// src/agents/bandits/thompson_sampling.rs: the experiment's TS is num_samples 1, its OTS 10 (rl2-bandits.rs:213-216); the
+// C ABI carries num_samples in initial_action_count.  The Beta sampler is include/rl_beta.h
+struct BetaThompsonSamplingAgentConfig {
+  uint64_t num_samples = 1;
+  rl_bandit_agent_config raw() const {
+    return rl_bandit_agent_config{RL_BANDIT_AGENT_THOMPSON, 0, 0.0, num_samples, 0.0};
+  }
+};
 
 // ResettingMetaAgent<TC> (src/agents/meta.rs:21-199) over the lanes of a MetaBanditLanes: one inner agent per lane, built
 // fresh from `TC` wherever the lane's trial starts, acting in Training mode and updated after every pull
@@ -1186,10 +1194,13 @@ class ResettingMetaAgent {
     check(rl_bandit_agent_rollout(h_, env.handle(), history.handle()), eng_.handle());
   }
   // the inner agents after the updates of all pulls so far: the next unread word of each lane's actor stream, the
-  // per-arm selection counts and values / mean rewards [n_arms][n_lanes] (not for RandomAgentConfig)
+  // per-arm selection counts and values / mean rewards [n_arms][n_lanes] (TabularQLearningAgentConfig, UCB1AgentConfig)
   std::vector<uint64_t> actor_word_positions() const { return read<uint64_t>(RL_BANDIT_STATE_ACTOR_POS, n_lanes_); }
   std::vector<uint64_t> action_counts() const { return read<uint64_t>(RL_BANDIT_STATE_COUNTS, n_arms_ * n_lanes_); }
   std::vector<double> action_values() const { return read<double>(RL_BANDIT_STATE_VALUES, n_arms_ * n_lanes_); }
+  // BetaThompsonSamplingAgentConfig only: the per-arm counts of rewards at most / above 0.5, [n_arms][n_lanes]
+  std::vector<uint64_t> low_reward_counts() const { return read<uint64_t>(RL_BANDIT_STATE_LOW_COUNTS, n_arms_ * n_lanes_); }
+  std::vector<uint64_t> high_reward_counts() const { return read<uint64_t>(RL_BANDIT_STATE_HIGH_COUNTS, n_arms_ * n_lanes_); }
 
  private:
   template <typename T>

@@ -1,7 +1,8 @@
 // kernels_bandit_agent.hip — the bandit baselines on the meta-bandit lanes (rl_bandit_agent_rollout):
 // ResettingMetaAgent<TC> (src/agents/meta.rs:135-199) over SerialActorAgent (src/agents/serial.rs:43-95), TC =
 // RandomAgentConfig (src/agents/random.rs:59-73), TabularQLearningAgentConfig (src/agents/tabular.rs:113-133, 159-180,
-// 222-232) or UCB1AgentConfig (src/agents/bandits/ucb.rs:106-160, 209-234) — an actor that is not a network.
+// 222-232), UCB1AgentConfig (src/agents/bandits/ucb.rs:106-160, 209-234) or BetaThompsonSamplingAgentConfig
+// (src/agents/bandits/thompson_sampling.rs:95-136, 186-205) — an actor that is not a network.
 //
 //   k_meta_agent_rollout<KIND, D>   all T steps of the env's lanes in one launch, one thread per lane: the shape of
 //                                   k_stack_rollout (kernels_seq_stack.hip) without a module.  The lane's MetaOps::State
@@ -10,12 +11,13 @@
 //                                   stored once.  Nothing waits on another lane: no barrier, no LDS.
 //
 // Arithmetic: f64, the reference's operations in the reference's order; the unit is built with -ffp-contract=off and
-// writes no fma.  f64 divide and square root are IEEE-correct on the device; `ln` is never evaluated here — UCB1 reads
-// 2 ln(visit) from the table the host filled (BanditAgentDev::ln2).
+// writes no fma.  f64 divide and square root are IEEE-correct on the device; UCB1 never evaluates `ln` here — it reads
+// 2 ln(visit) from the table the host filled (BanditAgentDev::ln2); THOMPSON evaluates rl_log / rl_exp (rl_detmath.h).
 // The per-arm arrays are indexed by the action through selects over the unrolled k arms, never through a
 // lane-dependent index: that would put them into scratch memory (cp_reset, env_lanes.hpp, has the same reason).
 #include "bandit_agent.hpp"
 #include "env_lanes.hpp"
+#include "../../include/rl_beta.h"
 
 namespace {
 
@@ -136,6 +138,99 @@ struct InnerAgent {
   }
 };
 
+// BetaThompsonSamplingAgentConfig { num_samples } (src/agents/bandits/thompson_sampling.rs:95-136, 186-205; DESIGN.md
+// §33): per arm a low and a high reward count, both 1 in a fresh agent; act draws, arm by arm, num_samples samples of
+// Beta(high, low) (include/rl_beta.h) and takes the LAST maximal sum; update counts the reward on its side of 0.5.
+// Here ln and exp ARE evaluated on the device: rl_log / rl_exp of rl_detmath.h, the bits the host computes.
+// The draws are many — an OTS pull at four arms takes 80 u64s or more — so the lane keeps the ChaCha8 block it is
+// reading: 16 words in registers, computed again only where pos >> 4 changes (pos is even: a block serves 8 draws).
+template <int K>
+struct InnerAgent<RL_BANDIT_AGENT_THOMPSON, K> {
+  uint64_t low[K], high[K];
+  uint32_t blk[16];
+  uint64_t blk_at;  // the block index `blk` holds; ~0: none yet (word positions stay far below 2^68)
+
+  __device__ __forceinline__ void load(const BanditAgentDev &ag, uint32_t i, size_t n) {
+    blk_at = ~0ull;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) blk[w] = 0;
+#pragma unroll
+    for (int a = 0; a < K; ++a) {
+      low[a] = ag.low[(size_t)a * n + i];
+      high[a] = ag.high[(size_t)a * n + i];
+    }
+  }
+  __device__ __forceinline__ void store(const BanditAgentDev &ag, uint32_t i, size_t n) const {
+#pragma unroll
+    for (int a = 0; a < K; ++a) {
+      ag.low[(size_t)a * n + i] = low[a];
+      ag.high[(size_t)a * n + i] = high[a];
+    }
+  }
+  // BetaThompsonSamplingAgent::new (thompson_sampling.rs:95-110): one low and one high reward per arm
+  __device__ __forceinline__ void fresh(const BanditAgentDev &) {
+#pragma unroll
+    for (int a = 0; a < K; ++a) low[a] = high[a] = 1;
+  }
+  // the next u64 of the lane's actor stream, low word first
+  __device__ __forceinline__ uint64_t next_u64(const uint32_t *key, uint64_t glane, uint64_t &pos) {
+    if ((pos >> 4) != blk_at) {
+      blk_at = pos >> 4;
+      rl_chacha_block(key, blk_at, glane, 4, blk);
+    }
+    uint32_t lo32 = 0, hi32 = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k += 2)
+      if (k == (int)(pos & 15)) {
+        lo32 = blk[k];
+        hi32 = blk[k + 1];
+      }
+    pos += 2;
+    return ((uint64_t)hi32 << 32) | lo32;
+  }
+  __device__ __forceinline__ int act(const BanditAgentDev &ag, const uint32_t *key, uint64_t glane, uint64_t &pos,
+                                     uint32_t) {
+    int best = 0;  // the LAST maximal sum (Iterator::max_by, utils/iter/cmp.rs:68-74)
+    double best_v = 0.0;
+#pragma unroll 1
+    for (int arm = 0; arm < K; ++arm) {  // one copy of the sampler's code; the counts come through selects
+      uint64_t lo = 0, hi = 0;
+#pragma unroll
+      for (int a = 0; a < K; ++a)
+        if (a == arm) {
+          lo = low[a];
+          hi = high[a];
+        }
+      rl_beta beta;
+      rl_beta_new((double)hi, (double)lo, &beta);
+      double sum = 0.0;
+      for (uint32_t j = 0; j < ag.num_samples; ++j) {
+        double w = 0.0;
+        for (int attempt = 0; attempt < RL_BETA_MAX_ATTEMPTS; ++attempt) {
+          const double u1 = rl_u64_to_open01_f64(next_u64(key, glane, pos));
+          const double u2 = rl_u64_to_open01_f64(next_u64(key, glane, pos));
+          if (rl_beta_attempt(&beta, u1, u2, &w)) break;
+        }
+        sum += rl_beta_result(&beta, w);
+      }
+      if (arm == 0 || sum >= best_v) {
+        best = arm;
+        best_v = sum;
+      }
+    }
+    return best;
+  }
+  // thompson_sampling.rs:112-136: the reward against the midpoint of the declared interval [0, 1]
+  __device__ __forceinline__ void update(int action, double reward) {
+    const bool up = reward > 0.5;
+#pragma unroll
+    for (int a = 0; a < K; ++a) {
+      high[a] += (a == action && up) ? 1 : 0;
+      low[a] += (a == action && !up) ? 1 : 0;
+    }
+  }
+};
+
 template <int KIND, int D>
 __global__ void __launch_bounds__(BA_BLOCK) k_meta_agent_rollout(CartPoleDev c, EnvStateDev st, TrajDev tr,
                                                                 BanditAgentDev ag, uint64_t t_global) {
@@ -197,6 +292,7 @@ void launch_bandit_agent_rollout(rl_bandit_agent *agent, rl_env *env, rl_traj *t
   switch (agent->cfg.kind) {
     case RL_BANDIT_AGENT_RANDOM: launch_kind<RL_BANDIT_AGENT_RANDOM>(agent, env, traj); break;
     case RL_BANDIT_AGENT_TABULAR_Q: launch_kind<RL_BANDIT_AGENT_TABULAR_Q>(agent, env, traj); break;
+    case RL_BANDIT_AGENT_THOMPSON: launch_kind<RL_BANDIT_AGENT_THOMPSON>(agent, env, traj); break;
     default: launch_kind<RL_BANDIT_AGENT_UCB1>(agent, env, traj); break;
   }
   RL_HIP_CHECK(hipGetLastError());
