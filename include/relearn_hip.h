@@ -353,6 +353,7 @@ int32_t rl_mlp_init_with(rl_mlp *mlp, uint64_t seed, const rl_initializer *kerne
  * hidden_weights_init, b_ih and b_hh from bias_init — 1-D tensors: fan_in 1, fan_out = gate rows) and the chain's
  * MlpConfig::linear_config { kernel_init, bias_init } (fan_in = in + 1), layer after layer from the same stream.
  * rl_mlp_init(m, seed) on a recurrent chain = (Uniform(FanAvg), Orthogonal, Zeros; Uniform(FanAvg) x 2), the defaults.
+ * On a chain with a Linear tail (rl_rnn_linear_create) the last pair is that Linear's LinearConfig.
  * bias_init NULL <=> the module was built without recurrent bias vectors (rl_rnn_mlp_create_config, bias = 0:
  * RnnBaseConfig::bias_init = None); a mismatch -> RL_ERR_INVALID_ARGUMENT; mlp_bias_init NULL -> RL_ERR_UNSUPPORTED (the
  * chain's MLP is built with bias vectors); Orthogonal on a bias -> RL_ERR_INVALID_ARGUMENT (init_orthogonal asserts two
@@ -414,6 +415,24 @@ int32_t rl_rnn_mlp_create(rl_engine *engine, int32_t cell, uint32_t in_dim, uint
  * without the bias entries. */
 int32_t rl_rnn_mlp_create_config(rl_engine *engine, int32_t cell, uint32_t in_dim, uint32_t hidden_size,
                                  uint32_t num_layers, int32_t bias, uint32_t mlp_hidden, uint32_t out_dim, rl_mlp **out);
+/* ChainConfig<GruConfig | LstmConfig, LinearConfig> (modules/chain.rs:12-54, ff/linear.rs:13-68):
+ * in_dim -> num_layers x RNN(hidden_size) -> ReLU -> Linear(hidden_size, out_dim) — the model of the reference's
+ * rl2-bandits experiment (relearn_experiments/src/bin/rl2-bandits.rs:349,379-394: `type Model = Chain<Gru, Linear>`,
+ * hidden_dim 128, policy and critic alike).  in_dim 1..8, hidden_size 1..256, num_layers 1..4 (0 -> RL_ERR_BUILD_AGENT,
+ * > 4 -> RL_ERR_UNSUPPORTED), out_dim in {1, 2}, rnn_bias 0 | 1 (0: the layers of rl_rnn_mlp_create_config(...,
+ * bias = 0, ...)); anything else -> RL_ERR_BUILD_AGENT.  Flat order = trainable_variables(): per layer
+ * [W_ih, W_hh, b_ih, b_hh] (or [W_ih, W_hh]), then kernel [out_dim, hidden_size], then bias [out_dim]; a Linear
+ * without a bias vector is not built.  rl_mlp_init draws the layers and then the Linear (Linear::new, fan_in =
+ * hidden_size + 1) from the one stream with RnnBaseConfig::default's and LinearConfig::default's initializers; in
+ * rl_rnn_mlp_init_with the last two arguments are the Linear's pair.  The module runs the lane-per-thread kernels at
+ * every shape (5 -> 128 included: the fused tile kernels are built around the MLP tail's hidden layer), instantiated
+ * without the head's hidden layer; every entry
+ * point of the MLP-tail chains applies, rl_actor_critic_update with one module of each tail included.  Actor documents
+ * hold `second: Linear { kernel, bias }`; a document of the other tail than the module's is refused with
+ * RL_ERR_INVALID_ARGUMENT.  Outputs are bit-identical to the C restatement of the MLP-tail chain with mlp_hidden =
+ * hidden_size, W1 = I, b1 = 0 (tests/test_gpu_chain_linear.py). */
+int32_t rl_rnn_linear_create(rl_engine *engine, int32_t cell, uint32_t in_dim, uint32_t hidden_size,
+                             uint32_t num_layers, int32_t rnn_bias, uint32_t out_dim, rl_mlp **out);
 
 /* ---------------------------------------------------------------------------------------------
  * Trajectory store (replaces VecBuffer + LazyHistoryFeatures: src/agents/buffers/vec.rs:15-143,

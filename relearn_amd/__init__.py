@@ -53,7 +53,7 @@ ABI_SYMBOLS = [
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
-    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_mlp_init_with", "rl_seq_forward",
+    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_mlp_init_with", "rl_seq_forward",
     "rl_traj_create", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write",
     "rl_rollout", "rl_gae",
     "rl_trpo_config_default", "rl_trpo_update", "rl_policy_gradient", "rl_policy_fvp", "rl_policy_loss_kl",
@@ -614,6 +614,37 @@ class LstmMlp(GruMlp):
 
     def __init__(self, engine, in_dim, out_dim, lstm_hidden=128, mlp_hidden=128, num_layers=1, rnn_bias=True):
         GruMlp.__init__(self, engine, in_dim, out_dim, lstm_hidden, mlp_hidden, num_layers, rnn_bias)
+
+
+class GruLinear(GruMlp):
+    """`ChainConfig<GruConfig, LinearConfig>::build_module(in, out)`: num_layers x GRU(hidden) -> ReLU -> Linear(hidden,
+    out), the model of the reference's rl2-bandits experiment; flat order [layers .., kernel, bias]."""
+
+    def __init__(self, engine, in_dim, out_dim, hidden=128, num_layers=1, rnn_bias=True):
+        self.eng = engine
+        self.h = C.c_void_p()
+        _check(lib().rl_rnn_linear_create(engine.h, C.c_int32(self.CELL), C.c_uint32(in_dim), C.c_uint32(hidden),
+                                          C.c_uint32(num_layers), C.c_int32(1 if rnn_bias else 0), C.c_uint32(out_dim),
+                                          C.byref(self.h)), engine.h)
+        _register(self)
+        n = C.c_uint64()
+        _check(lib().rl_mlp_num_params(self.h, C.byref(n)), engine.h)
+        self.P = n.value
+        # (`hidden`: the width of an MLP tail's hidden layer — there is none)
+        self.in_dim, self.hidden, self.out_dim, self.gru_hidden = in_dim, 0, out_dim, hidden
+        self.num_layers = num_layers
+
+    def init_with(self, seed, input_weights=("Uniform", "FanAvg", 0.0), hidden_weights=("Orthogonal", "FanAvg", 0.0),
+                  bias=("Zeros", "FanAvg", 0.0), kernel=("Uniform", "FanAvg", 0.0),
+                  linear_bias=("Uniform", "FanAvg", 0.0)):
+        """RnnBaseConfig's initializers and the Linear's LinearConfig as (kind, scale, value) triples"""
+        GruMlp.init_with(self, seed, input_weights, hidden_weights, bias, kernel, linear_bias)
+
+
+class LstmLinear(GruLinear):
+    """`ChainConfig<LstmConfig, LinearConfig>::build_module(in, out)`: LSTM layers -> ReLU -> Linear."""
+
+    CELL = 1  # RL_CELL_LSTM
 
 
 ACTIVATIONS = ["Identity", "Relu", "Sigmoid", "Tanh"]  # rl_activation, in the reference enum's order

@@ -1067,18 +1067,23 @@ int32_t rl_mlp_create_config(rl_engine *e, uint32_t in_dim, const uint32_t *hidd
 // RnnBaseConfig { hidden_size, num_layers, .. } -> ReLU -> Mlp with one hidden layer.  The kernels are built for
 // 5 -> 128 -> 128 -> {1, 2}; narrower shapes (in_dim <= 5, widths <= 128) run on them embedded with zero padding
 // (rl_mlp::exec).  num_layers in 2..4 (stacked layers): the lane-per-thread kernels of kernels_seq_stack.hip at the
-// module's own widths.
+// module's own widths.  `linear_tail`: ChainConfig<_, LinearConfig> — the second module is one Linear(hidden_size,
+// out_dim) (mlp_hidden is 0 and marks it, rl_mlp::linear_tail); always the lane-per-thread kernels, never a twin.
 static void seq_module_create(rl_engine *e, int kind, uint32_t in_dim, uint32_t rnn_hidden, uint32_t num_layers,
-                              uint32_t mlp_hidden, uint32_t out_dim, rl_mlp **out, bool rnn_bias = true) {
+                              uint32_t mlp_hidden, uint32_t out_dim, rl_mlp **out, bool rnn_bias = true,
+                              bool linear_tail = false) {
   RL_REQUIRE(e && out, "NULL argument");
   *out = nullptr;
   if (num_layers == 0) throw RlError(RL_ERR_BUILD_AGENT, "RnnBaseConfig::num_layers must be at least 1");
   if (num_layers > RL_RNN_MAX_LAYERS)
     throw RlError(RL_ERR_UNSUPPORTED, "recurrent chains are built for RnnBaseConfig::num_layers <= 4");
-  if (in_dim < 1 || in_dim > RL_TRAJ_MAX_OBS_DIM || rnn_hidden < 1 || rnn_hidden > RL_MLP_MAX_WIDTH || mlp_hidden < 1 ||
-      mlp_hidden > RL_MLP_MAX_WIDTH || !(out_dim == 1 || out_dim == 2))
+  if (in_dim < 1 || in_dim > RL_TRAJ_MAX_OBS_DIM || rnn_hidden < 1 || rnn_hidden > RL_MLP_MAX_WIDTH ||
+      (linear_tail ? mlp_hidden != 0 : mlp_hidden < 1) || mlp_hidden > RL_MLP_MAX_WIDTH ||
+      !(out_dim == 1 || out_dim == 2))
     throw RlError(RL_ERR_BUILD_AGENT,
-                  "supported recurrent chain shapes: in_dim 1..8, recurrent hidden 1..256, mlp_hidden 1..256, out_dim in {1,2}");
+                  linear_tail
+                      ? "supported recurrent chain shapes: in_dim 1..8, recurrent hidden 1..256, out_dim in {1,2}"
+                      : "supported recurrent chain shapes: in_dim 1..8, recurrent hidden 1..256, mlp_hidden 1..256, out_dim in {1,2}");
   RL_HIP_CHECK(hipSetDevice(e->device));
   // (`mem`: who owns the parameters — the module itself, or the module a twin belongs to)
   auto make = [&](DevMem *mem, uint32_t D, uint32_t H, uint32_t H2, uint32_t layers, bool bias) {
@@ -1092,7 +1097,7 @@ static void seq_module_create(rl_engine *e, int kind, uint32_t in_dim, uint32_t 
     const uint64_t A = out_dim;
     m->rnn_layers = layers;
     m->has_bias = bias;  // of the recurrent weights (RnnBaseConfig::bias_init); the chain's MLP always has its own
-    m->P = m->rnn_layer_offset(m->rnn_layers) + (uint64_t)H2 * H + H2 + A * H2 + A;
+    m->P = m->rnn_layer_offset(m->rnn_layers) + (H2 == 0 ? A * H + A : (uint64_t)H2 * H + H2 + A * H2 + A);
     // (bias-less recurrent weights: the gate rows start from zeros kept behind the parameters)
     const size_t alloc = m->P + (m->has_bias ? 0 : 4 * RL_MLP_MAX_WIDTH);
     m->d_params = (mem ? mem : &m->mem)->alloc<float>(alloc);
@@ -1143,6 +1148,16 @@ int32_t rl_rnn_mlp_create_config(rl_engine *e, int32_t cell, uint32_t in_dim, ui
     if (cell != RL_CELL_GRU && cell != RL_CELL_LSTM) throw RlError(RL_ERR_BUILD_AGENT, "unknown recurrent cell");
     seq_module_create(e, cell == RL_CELL_GRU ? RL_MODULE_GRU_MLP : RL_MODULE_LSTM_MLP, in_dim, hidden_size, num_layers,
                       mlp_hidden, out_dim, out, bias != 0);
+  });
+}
+
+int32_t rl_rnn_linear_create(rl_engine *e, int32_t cell, uint32_t in_dim, uint32_t hidden_size, uint32_t num_layers,
+                             int32_t rnn_bias, uint32_t out_dim, rl_mlp **out) {
+  return guarded(e, [&] {
+    if (cell != RL_CELL_GRU && cell != RL_CELL_LSTM) throw RlError(RL_ERR_BUILD_AGENT, "unknown recurrent cell");
+    if (rnn_bias != 0 && rnn_bias != 1) throw RlError(RL_ERR_BUILD_AGENT, "rnn_bias is 0 or 1");
+    seq_module_create(e, cell == RL_CELL_GRU ? RL_MODULE_GRU_MLP : RL_MODULE_LSTM_MLP, in_dim, hidden_size, num_layers,
+                      0, out_dim, out, rnn_bias != 0, true);
   });
 }
 
@@ -1263,8 +1278,9 @@ static void rnn_mlp_init_host(const rl_mlp *m, uint64_t seed, const RnnInits &in
       k += R;
     }
   }
-  const uint64_t dims[2][2] = {{H, H2}, {H2, A}};
-  for (int l = 0; l < 2; ++l) {
+  // (a Linear tail, rl_mlp::linear_tail: the one Linear(H, A))
+  const uint64_t dims[2][2] = {{H, H2 == 0 ? A : H2}, {H2, A}};
+  for (int l = 0; l < (H2 == 0 ? 1 : 2); ++l) {
     const uint64_t fin = dims[l][0], fout = dims[l][1];
     st.fill(in.mlp_kernel, h.data() + k, fout, fin, (double)(fin + 1));
     k += fin * fout;

@@ -165,7 +165,16 @@ static void cbor_module(cbor::Writer &w, const rl_mlp *m, const std::vector<floa
   w.key("type_");
   w.null();  // PhantomData
   w.key("second");
-  cbor_mlp(w, q, H, m->hidden, m->out_dim);
+  if (m->linear_tail()) {  // Linear { kernel, bias } (ff/linear.rs:45-50)
+    const int64_t A = m->out_dim;
+    w.map(2);
+    w.key("kernel");
+    cbor_tensor(w, q, {A, H});
+    w.key("bias");
+    cbor_tensor(w, q + A * H, {A});
+  } else {
+    cbor_mlp(w, q, H, m->hidden, m->out_dim);
+  }
   w.key("activation");
   w.text("Relu");
 }
@@ -313,7 +322,21 @@ int32_t rl_module_from_cbor(rl_mlp *module, const uint8_t *buf, uint64_t len) {
           q += GHR;
         }
       }
-      end = cbor_read_mlp(mod.at("second"), H, module->hidden, module->out_dim, q);
+      const cbor::Value &second = mod.at("second");
+      // Chain<_, Linear> and Chain<_, Mlp> are different documents: Linear { kernel, bias } against Mlp { layers, .. }
+      RL_REQUIRE(second.has("kernel") == module->linear_tail() && second.has("layers") == !module->linear_tail(),
+                 "CBOR module: the document's second module is not the kind this module has (Linear against Mlp)");
+      if (module->linear_tail()) {
+        const int64_t A = module->out_dim;
+        cbor_read_tensor(second.at("kernel"), {A, H}, q);
+        q += A * H;
+        RL_REQUIRE(second.at("bias").kind == cbor::Value::MAP,
+                   "CBOR module: a Linear tail without a bias vector is not built");
+        cbor_read_tensor(second.at("bias"), {A}, q);
+        end = q + A;
+      } else {
+        end = cbor_read_mlp(second, H, module->hidden, module->out_dim, q);
+      }
     }
     RL_REQUIRE((uint64_t)(end - p.data()) == module->P, "CBOR module: parameter count mismatch");
     h2d(module->eng, module->d_params, p.data(), module->P * sizeof(float));

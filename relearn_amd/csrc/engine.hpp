@@ -252,7 +252,7 @@ constexpr uint32_t RL_RNN_MAX_LAYERS = 4;   // RnnBaseConfig::num_layers of a re
 struct rl_mlp {
   rl_engine *eng;
   mutable DevMem mem;  // (mutable: the weight image is made on first use by launchers that hold the module const)
-  uint32_t in_dim, hidden, out_dim;  // GRU_MLP: hidden = the MLP's hidden width
+  uint32_t in_dim, hidden, out_dim;  // GRU_MLP: hidden = the MLP's hidden width (0: a Linear tail, linear_tail())
   uint64_t P;
   float *d_params = nullptr;
   // the weight image of a 5 -> 128 -> A module for the fused update kernels (bf16_tile.hpp "the weight image"): allocated
@@ -269,7 +269,14 @@ struct rl_mlp {
   // kernels' five, or widths above their 128)
   // (or recurrent weights without bias vectors, RnnBaseConfig::bias_init = None: `has_bias` false — the gate rows then
   // start from 4 x 256 zeros kept behind the P parameters, like the bias-less MLP layers; the chain's MLP keeps its own)
-  bool lane_kernels() const { return rnn_layers > 1 || in_dim > 5 || gru_hidden > 128 || hidden > 128 || !has_bias; }
+  // (or a chain whose second module is one Linear, `linear_tail`: at every shape, 5 -> 128 included, and never a twin)
+  bool lane_kernels() const {
+    return rnn_layers > 1 || in_dim > 5 || gru_hidden > 128 || hidden > 128 || !has_bias || linear_tail();
+  }
+  // ChainConfig<GruConfig | LstmConfig, LinearConfig> (modules/chain.rs:12-54): the recurrent layers -> ReLU -> one
+  // Linear(gru_hidden, out_dim).  Marked by `hidden` == 0 on a recurrent kind (the MLP-tail chains have hidden >= 1);
+  // flat order [layers .., kernel [out_dim][gru_hidden], bias [out_dim]]: rnn_layer_offset(rnn_layers) is the kernel.
+  bool linear_tail() const { return rl_module_is_recurrent(kind) && hidden == 0; }
   uint64_t rnn_layer_offset(uint32_t l) const {  // W_ih of layer l; l == rnn_layers: the head's W1
     const uint64_t GH = rl_module_gates(kind) * (uint64_t)gru_hidden, nb = has_bias ? 2 * GH : 0;
     if (l == 0) return 0;

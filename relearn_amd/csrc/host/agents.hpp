@@ -284,6 +284,7 @@ class Module {
   friend struct MlpConfig;
   friend struct GruMlpConfig;
   friend struct ChainLstmMlpConfig;
+  friend struct GruLinearConfig;
   Engine &eng_;
   rl_mlp *h_;
   uint64_t n_ = 0;
@@ -381,6 +382,42 @@ struct ChainLstmMlpConfig {
                                lc.bias_init ? &lc.bias_init->raw : nullptr),
           eng.handle());
     return m;
+  }
+};
+
+// ChainConfig<GruConfig | LstmConfig, LinearConfig> (modules/chain.rs:12-54): the recurrent layers -> ReLU -> ONE
+// Linear(hidden_dim, out) — the model of the reference's rl2-bandits experiment (rl2-bandits.rs:349,379-394).  A Linear
+// without a bias vector (LinearConfig::bias_init = None) is not built.
+struct GruLinearConfig {
+  GruConfig first_config;
+  uint32_t hidden_dim = 128;
+  LinearConfig second_config;
+  std::unique_ptr<Module> build_module(Engine &eng, uint32_t in_dim, uint32_t out_dim, uint64_t seed) const {
+    return build(eng, RL_CELL_GRU, first_config, hidden_dim, second_config, in_dim, out_dim, seed);
+  }
+  // (both cells: ChainLstmLinearConfig builds through it)
+  static std::unique_ptr<Module> build(Engine &eng, int32_t cell, const RnnBaseConfig &first, uint32_t hidden_dim,
+                                       const LinearConfig &second, uint32_t in_dim, uint32_t out_dim, uint64_t seed) {
+    if (!second.bias_init)
+      throw BuildAgentError(RL_ERR_BUILD_AGENT, "a recurrent chain's Linear tail is built with a bias vector");
+    rl_mlp *h = nullptr;
+    check(rl_rnn_linear_create(eng.handle(), cell, in_dim, hidden_dim, first.num_layers, first.bias_init ? 1 : 0,
+                               out_dim, &h),
+          eng.handle());
+    std::unique_ptr<Module> m(new Module(eng, h));
+    check(rl_rnn_mlp_init_with(h, seed, &first.input_weights_init.raw, &first.hidden_weights_init.raw,
+                               first.bias_init ? &first.bias_init->raw : nullptr, &second.kernel_init.raw,
+                               &second.bias_init->raw),
+          eng.handle());
+    return m;
+  }
+};
+struct ChainLstmLinearConfig {
+  LstmConfig first_config;
+  uint32_t hidden_dim = 128;
+  LinearConfig second_config;
+  std::unique_ptr<Module> build_module(Engine &eng, uint32_t in_dim, uint32_t out_dim, uint64_t seed) const {
+    return GruLinearConfig::build(eng, RL_CELL_LSTM, first_config, hidden_dim, second_config, in_dim, out_dim, seed);
   }
 };
 

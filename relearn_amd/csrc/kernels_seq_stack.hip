@@ -2,7 +2,10 @@
 // 223-257): stacked GRU / LSTM layers -> ReLU -> Mlp([h]) (modules/chain.rs:127-186).  Flat order per layer
 // [W_ih (gates x layer input), W_hh (gates x hidden), b_ih, b_hh]; layer 0 reads the observation features, layer l > 0
 // the hidden output of layer l - 1 of the same step (Tensor::gru / ::lstm with num_layers, seq/rnn/gru.rs:41-66); no
-// dropout.  Every layer's state is zero at t = 0 and after a step whose flag ends the episode.
+// dropout.  Every layer's state is zero at t = 0 and after a step whose flag ends the episode.  The chain's second
+// module is a compile-time parameter of every kernel (LIN): the Mlp([h]) above, or one Linear(H, A) on relu(top)
+// (ChainConfig<_, LinearConfig>, modules/chain.rs:12-54; flat order [.., kernel [A][H], bias [A]]): no hidden units,
+// so no `u` / `ur` / `du` planes and one barrier less per step.
 //
 // The single-layer chains have fused tile kernels (kernels_seq*.hip, built for 5 -> 128 -> 128); this is the general
 // path for the stacked ones, at the module's own widths: ONE THREAD PER LANE, 64 lanes per workgroup, and the unit loop
@@ -39,7 +42,7 @@ struct StackNet {
   const float *p;  // flat parameters (or a tangent in the same layout)
   const float *z;  // >= 4 H zeros: what a layer WITHOUT bias vectors starts its gate rows from (NULL: the layers have them)
   int D, H, H2, A, L;
-  uint32_t off[RL_RNN_MAX_LAYERS + 1];  // W_ih of layer l; [L]: the head's W1
+  uint32_t off[RL_RNN_MAX_LAYERS + 1];  // W_ih of layer l; [L]: the head's W1 (linear tail: its kernel; H2 is 0)
 };
 // How a kernel reads the module's parameters.  CW false: through the plain pointer (the compiler takes wave-uniform
 // scalar loads where it can prove that no store of the kernel reaches the load: k_stack_step).  CW true: through the
@@ -247,11 +250,29 @@ __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &w
 }
 
 // Chain's ReLU and the Mlp on the top layer's output `top` ([H][n]); out[q] in every thread.  One barrier inside.
-template <bool REC, bool CW = false>
+// LIN: Chain's ReLU and one Linear — out[q] = bias[q] + sum_k relu(top[k]) kernel[q][k], no barrier.
+template <bool REC, bool CW = false, bool LIN = false>
 __device__ __forceinline__ void stack_head(const StackNet &net, const StackWs &ws, const float *__restrict__ top,
                                            const LaneCtx &lc, size_t b, float (&out)[2]) {
   const int H = net.H, H2 = net.H2, A = net.A;
   const size_t n = ws.n;
+  if (LIN) {
+    const float *__restrict__ Wk_p = net.p + net.off[net.L], *__restrict__ bk_p = Wk_p + (size_t)A * H;
+    const auto Wk = weight_ptr<CW>(Wk_p), bk = weight_ptr<CW>(bk_p);
+    if (REC && lc.live)
+      for (int k = lc.wave; k < H; k += SW) {
+        const float tv = top[(size_t)k * n + lc.ii];
+        ws.a1[(size_t)k * ws.B + b] = tv > 0.0f ? tv : 0.0f;
+      }
+    const int qq[2] = {0, A > 1 ? 1 : 0};
+    out[0] = bk[qq[0]];
+    out[1] = bk[qq[1]];
+    dot_rows(out, Wk, qq, H, [&](int k) {
+      const float tv = top[(size_t)k * n + lc.ii];
+      return tv > 0.0f ? tv : 0.0f;
+    });
+    return;
+  }
   const float *__restrict__ W1_p = net.p + net.off[net.L], *__restrict__ b1_p = W1_p + (size_t)H2 * H;
   const float *__restrict__ W2_p = b1_p + H2, *__restrict__ b2_p = W2_p + (size_t)A * H2;
   const auto W1 = weight_ptr<CW>(W1_p), b1 = weight_ptr<CW>(b1_p), W2 = weight_ptr<CW>(W2_p), b2 = weight_ptr<CW>(b2_p);
@@ -288,7 +309,7 @@ __device__ __forceinline__ void stack_head(const StackNet &net, const StackWs &w
 }
 
 // all layers + head of one step: states of set `cur` (zero where `fresh`) -> set `nxt`
-template <int CELL, bool REC, bool CW = false>
+template <int CELL, bool REC, bool CW = false, bool LIN = false>
 __device__ __forceinline__ void stack_module_step(const StackNet &net, const StackWs &ws, const float *__restrict__ x,
                                                   size_t x_stride, int cur, int nxt, bool fresh, const LaneCtx &lc,
                                                   size_t b, float (&out)[2]) {
@@ -299,11 +320,11 @@ __device__ __forceinline__ void stack_module_step(const StackNet &net, const Sta
                               b);
     __syncthreads();
   }
-  stack_head<REC, CW>(net, ws, slot(ws, net, nxt, 0, net.L - 1), lc, b, out);
+  stack_head<REC, CW, LIN>(net, ws, slot(ws, net, nxt, 0, net.L - 1), lc, b, out);
 }
 
 // teacher-forced forward: out / succ [A][T][n] (succ may be NULL), the contract of launch_gru_seq_forward
-template <int CELL, bool REC>
+template <int CELL, bool REC, bool LIN = false>
 __global__ void __launch_bounds__(SL *SW) k_stack_forward(StackNet net, StackWs ws, TrajDev tr, float *__restrict__ out,
                                                           float *__restrict__ succ, const int32_t *__restrict__ skip) {
   if (skip != nullptr && *skip != 0) return;
@@ -314,7 +335,7 @@ __global__ void __launch_bounds__(SL *SW) k_stack_forward(StackNet net, StackWs 
   for (size_t t = 0; t < T; ++t) {
     const size_t b = t * n + lc.ii;
     float o[2];
-    stack_module_step<CELL, REC>(net, ws, tr.obs + t * n, plane, cur, cur ^ 1, fresh, lc, b, o);
+    stack_module_step<CELL, REC, false, LIN>(net, ws, tr.obs + t * n, plane, cur, cur ^ 1, fresh, lc, b, o);
     const uint8_t f = tr.flag[b];
     if (lc.live && lc.wave == 0)
       for (int q = 0; q < net.A; ++q) out[(size_t)q * B + b] = o[q];
@@ -326,8 +347,8 @@ __global__ void __launch_bounds__(SL *SW) k_stack_forward(StackNet net, StackWs 
         // step t, which are not advanced: the results go to the third state set.  Per-lane plane stride: term_obs planes
         // are T * n apart, obs planes (T + 1) * n.
         const bool intr = f == RL_SUCC_INTERRUPT;
-        stack_module_step<CELL, false>(net, ws, intr ? tr.term_obs + t * n : tr.obs + T * n, intr ? B : plane, cur ^ 1,
-                                       SET_PEEK, false, lc, b, o2);
+        stack_module_step<CELL, false, false, LIN>(net, ws, intr ? tr.term_obs + t * n : tr.obs + T * n,
+                                                   intr ? B : plane, cur ^ 1, SET_PEEK, false, lc, b, o2);
       }
       if (lc.live && lc.wave == 0)
         for (int q = 0; q < net.A; ++q) succ[(size_t)q * B + b] = need ? o2[q] : 0.0f;
@@ -339,14 +360,14 @@ __global__ void __launch_bounds__(SL *SW) k_stack_forward(StackNet net, StackWs 
 
 // one rollout step: env observation buffer obs [D][n] -> logits z [A][n]; the lane's states restart where the step
 // before ended its episode (flag_prev: that step's successor codes) or at the first step of a collection
-template <int CELL>
+template <int CELL, bool LIN = false>
 __global__ void __launch_bounds__(SL *SW) k_stack_step(StackNet net, StackWs ws, const float *__restrict__ obs,
                                                        const uint8_t *__restrict__ flag_prev, int first, int parity,
                                                        float *__restrict__ z) {
   const LaneCtx lc = lane_ctx(ws.n);
   const bool fresh = first != 0 || flag_prev[lc.ii] != RL_SUCC_CONTINUE;
   float o[2];
-  stack_module_step<CELL, false>(net, ws, obs, (size_t)ws.n, parity, parity ^ 1, fresh, lc, 0, o);
+  stack_module_step<CELL, false, false, LIN>(net, ws, obs, (size_t)ws.n, parity, parity ^ 1, fresh, lc, 0, o);
   if (lc.live && lc.wave == 0)
     for (int q = 0; q < net.A; ++q) z[(size_t)q * ws.n + lc.ii] = o[q];
 }
@@ -360,7 +381,7 @@ __global__ void __launch_bounds__(SL *SW) k_stack_step(StackNet net, StackWs ws,
 // observation into slot t + 1 (slot T after the last step); a barrier publishes them and the successor codes, from
 // which every thread of the lane learns whether the states restart (k_stack_step's flag_prev).  Lane state lives in wave
 // 0's registers from the first step to the last.
-template <int CELL, class Env, int D>
+template <int CELL, class Env, int D, bool LIN = false>
 __global__ void __launch_bounds__(SL *SW) k_stack_rollout(StackNet net, StackWs ws, CartPoleDev c, EnvStateDev st,
                                                           TrajDev tr, uint64_t t_global) {
   __shared__ uint8_t succ_of[SL];
@@ -383,7 +404,7 @@ __global__ void __launch_bounds__(SL *SW) k_stack_rollout(StackNet net, StackWs 
   int cur = SET_A;
   for (size_t t = 0; t < T; ++t) {
     float o[2];
-    stack_module_step<CELL, false, true>(net, ws, tr.obs + t * n, plane, cur, cur ^ 1, fresh, lc, 0, o);
+    stack_module_step<CELL, false, true, LIN>(net, ws, tr.obs + t * n, plane, cur, cur ^ 1, fresh, lc, 0, o);
     if (actor) {
       const float u = rl_u32_to_unit_f32(stream_word(c.key_actor, glane, t_global + t));
       float lp[2];
@@ -412,8 +433,9 @@ __global__ void __launch_bounds__(SL *SW) k_stack_rollout(StackNet net, StackWs 
 // from which the weight-gradient kernel forms every dW / db.  Per step and layer: (A) this wave's units turn the gradient
 // into their output (carried from step t + 1, zero across an episode boundary, plus what the layer above — or the head —
 // sends down at this step) into gate deltas; (B) this wave's input indices k gather W_hh^T / W_ih^T times those deltas:
-// the gradient carried to step t - 1 and the one sent to the layer below.
-template <int CELL>
+// the gradient carried to step t - 1 and the one sent to the layer below.  LIN: no du plane, the head is one
+// transposed product, din[k] = [top[k] > 0] sum_q kernel[q][k] dz[q].
+template <int CELL, bool LIN = false>
 __global__ void __launch_bounds__(SL *SW) k_stack_backward(StackNet net, StackWs ws, TrajDev tr,
                                                            const float *__restrict__ dz,
                                                            const int32_t *__restrict__ skip) {
@@ -426,20 +448,24 @@ __global__ void __launch_bounds__(SL *SW) k_stack_backward(StackNet net, StackWs
   for (size_t t = T; t-- > 0;) {
     const size_t b = t * n + lc.ii;
     const bool ended = t == T - 1 || tr.flag[b] != RL_SUCC_CONTINUE;  // nothing flows in from step t + 1
-    for (int j0 = KB * lc.wave; j0 < H2; j0 += KB * SW) {
-      float acc[KB] = {};
-      tdot(acc, W2, H2, j0, H2, A, [&](int q) { return dz[(size_t)q * B + b]; });
+    if (!LIN) {
+      for (int j0 = KB * lc.wave; j0 < H2; j0 += KB * SW) {
+        float acc[KB] = {};
+        tdot(acc, W2, H2, j0, H2, A, [&](int q) { return dz[(size_t)q * B + b]; });
 #pragma unroll
-      for (int u = 0; u < KB; ++u)
-        if (j0 + u < H2 && lc.live)
-          ws.du[(size_t)(j0 + u) * B + b] = ws.ur[(size_t)(j0 + u) * B + b] > 0.0f ? acc[u] : 0.0f;
+        for (int u = 0; u < KB; ++u)
+          if (j0 + u < H2 && lc.live)
+            ws.du[(size_t)(j0 + u) * B + b] = ws.ur[(size_t)(j0 + u) * B + b] > 0.0f ? acc[u] : 0.0f;
+      }
+      __syncthreads();
     }
-    __syncthreads();
     {
+      // (LIN: W1 is the Linear's kernel [A][H], and dz is what comes down)
       const float *__restrict__ top = rec_plane(ws, net, L - 1, RP_HOUT);
       for (int k0 = KB * lc.wave; k0 < H; k0 += KB * SW) {
         float acc[KB] = {};
-        tdot(acc, W1, H, k0, H, H2, [&](int j) { return ws.du[(size_t)j * B + b]; });
+        tdot(acc, W1, H, k0, H, LIN ? A : H2,
+             [&](int j) { return LIN ? dz[(size_t)j * B + b] : ws.du[(size_t)j * B + b]; });
 #pragma unroll
         for (int u = 0; u < KB; ++u)
           if (k0 + u < H && lc.live)
@@ -516,7 +542,8 @@ __global__ void __launch_bounds__(SL *SW) k_stack_backward(StackNet net, StackWs
 
 // Forward-mode derivative along the tangent `tv` (same layout as the parameters) through the recorded activations:
 // out_dot [A][T][n].  With p = a gate's pre-activation: p_dot = V_ih x + v_bih + W_ih x_dot + V_hh h + v_bhh + W_hh h_dot.
-template <int CELL>
+// LIN: out_dot[q] = v_bias[q] + sum_k (v_kernel[q][k] a1[k] + kernel[q][k] [top[k] > 0] top_dot[k]).
+template <int CELL, bool LIN = false>
 __global__ void __launch_bounds__(SL *SW) k_stack_tangent(StackNet net, StackNet tv, StackWs ws, TrajDev tr,
                                                           float *__restrict__ out_dot,
                                                           const int32_t *__restrict__ skip) {
@@ -602,6 +629,23 @@ __global__ void __launch_bounds__(SL *SW) k_stack_tangent(StackNet net, StackNet
       }
       __syncthreads();
     }
+    if (LIN) {
+      if (lc.wave == 0) {
+        const float *__restrict__ top = rec_plane(ws, net, L - 1, RP_HOUT);
+        const float *__restrict__ topd = slot(ws, net, nxt, 0, L - 1);
+        const float *__restrict__ vbk = V1 + (size_t)A * H;  // (W1 / V1: the Linear's kernel [A][H] and its tangent)
+        const int qq[2] = {0, A > 1 ? 1 : 0};
+        float od[2] = {vbk[qq[0]], vbk[qq[1]]};
+        dot_rows(od, V1, qq, H, [&](int k) { return ws.a1[(size_t)k * B + b]; });
+        dot_rows(od, W1, qq, H,
+                 [&](int k) { return top[(size_t)k * B + b] > 0.0f ? topd[(size_t)k * n + lc.ii] : 0.0f; });
+        if (lc.live)
+          for (int q = 0; q < A; ++q) out_dot[(size_t)q * B + b] = od[q];
+      }
+      fresh = tr.flag[b] != RL_SUCC_CONTINUE;
+      cur = nxt;
+      continue;
+    }
     {
       const float *__restrict__ top = rec_plane(ws, net, L - 1, RP_HOUT);
       const float *__restrict__ topd = slot(ws, net, nxt, 0, L - 1);
@@ -678,17 +722,18 @@ void stack_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
   const uint64_t n = t->d.n, T = t->d.T, B = T * n, L = mod->rnn_layers, H = mod->gru_hidden, H2 = mod->hidden;
   DevMem &mem = t->mem;
   seq_ensure_outputs(t);
+  const bool lin = mod->linear_tail();  // no hidden units: no u / ur / du (a trajectory may serve both tails in turn)
   mem.ensure(k.st, 2 * N_SETS * L * H * n);
-  mem.ensure(k.u, H2 * n);
+  if (!lin) mem.ensure(k.u, H2 * n);
   if (k.z == nullptr) k.z = mem.alloc<float>(2 * n);
   if (!training) return;
   mem.ensure(k.din, H * n);
   mem.ensure(k.dst, 2 * L * H * n);
   mem.ensure(k.rec, L * RPN * H * B);
   mem.ensure(k.a1, H * B);
-  mem.ensure(k.ur, H2 * B);
+  if (!lin) mem.ensure(k.ur, H2 * B);
   mem.ensure(k.dg, L * 4 * H * B);
-  mem.ensure(k.du, H2 * B);
+  if (!lin) mem.ensure(k.du, H2 * B);
   // weight-gradient partials: at most 64 slab rows (the matrices are large: P doubles per row)
   uint64_t rows = t->nbA < 64 ? t->nbA : 64;
   uint64_t chunk = (B + rows - 1) / rows;
@@ -705,17 +750,23 @@ void launch_stack_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float 
   const StackNet net = stack_net(mod, mod->d_params);
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
-#define FWD(CELL, REC)                                                                                              \
-  hipLaunchKernelGGL((k_stack_forward<CELL, REC>), grid, blk, 0, traj->eng->stream, net, ws, traj->d, d_out, d_succ, \
-                     d_skip)
-  const bool lstm = mod->kind == RL_MODULE_LSTM_MLP;
+#define FWD(CELL, REC, LIN)                                                                                   \
+  hipLaunchKernelGGL((k_stack_forward<CELL, REC, LIN>), grid, blk, 0, traj->eng->stream, net, ws, traj->d, d_out, \
+                     d_succ, d_skip)
+#define FWD_TAIL(CELL, REC)        \
+  do {                             \
+    if (lin) FWD(CELL, REC, true); \
+    else FWD(CELL, REC, false);    \
+  } while (0)
+  const bool lstm = mod->kind == RL_MODULE_LSTM_MLP, lin = mod->linear_tail();
   if (record) {
-    if (lstm) FWD(LSTM, true);
-    else FWD(GRU, true);
+    if (lstm) FWD_TAIL(LSTM, true);
+    else FWD_TAIL(GRU, true);
   } else {
-    if (lstm) FWD(LSTM, false);
-    else FWD(GRU, false);
+    if (lstm) FWD_TAIL(LSTM, false);
+    else FWD_TAIL(GRU, false);
   }
+#undef FWD_TAIL
 #undef FWD
   RL_HIP_CHECK(hipGetLastError());
 }
@@ -727,17 +778,22 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
   float *z = traj->seq.stack.z;
-  const bool lstm = policy->kind == RL_MODULE_LSTM_MLP;
+  const bool lstm = policy->kind == RL_MODULE_LSTM_MLP, lin = policy->linear_tail();
   if (env->kind == RL_ENV_META_BANDIT && env->eng->kernel_variant != 1) {
     // meta-bandit lanes: all T steps in one launch (kernel variant 1 keeps the launch sequence per step, below).  Two
     // arms: the recurrent chains are built for two actions (rl_rollout), so the observation has six features.
     RL_REQUIRE(env->D == 6, "fused recurrent rollout on meta-bandit lanes: built for two arms (six features)");
-    if (lstm)
-      hipLaunchKernelGGL((k_stack_rollout<LSTM, MetaOps, 6>), grid, blk, 0, env->eng->stream, net, ws, env->dev, env->st,
-                         traj->d, env->t_global);
-    else
-      hipLaunchKernelGGL((k_stack_rollout<GRU, MetaOps, 6>), grid, blk, 0, env->eng->stream, net, ws, env->dev, env->st,
-                         traj->d, env->t_global);
+#define ROLL(CELL, LIN)                                                                                           \
+  hipLaunchKernelGGL((k_stack_rollout<CELL, MetaOps, 6, LIN>), grid, blk, 0, env->eng->stream, net, ws, env->dev, \
+                     env->st, traj->d, env->t_global)
+    if (lstm) {
+      if (lin) ROLL(LSTM, true);
+      else ROLL(LSTM, false);
+    } else {
+      if (lin) ROLL(GRU, true);
+      else ROLL(GRU, false);
+    }
+#undef ROLL
     RL_HIP_CHECK(hipGetLastError());
     env->t_global += traj->d.T;
     return;
@@ -746,12 +802,17 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     const int first = step == 0 ? 1 : 0, parity = (int)(step & 1);
     // (the step before has been recorded by now: its successor codes are in the trajectory)
     const uint8_t *flag_prev = traj->d.flag + (size_t)(step == 0 ? 0 : step - 1) * traj->d.n;
-    if (lstm)
-      hipLaunchKernelGGL(k_stack_step<LSTM>, grid, blk, 0, env->eng->stream, net, ws, env->d_obs, flag_prev, first,
-                         parity, z);
-    else
-      hipLaunchKernelGGL(k_stack_step<GRU>, grid, blk, 0, env->eng->stream, net, ws, env->d_obs, flag_prev, first,
-                         parity, z);
+#define STEP(CELL, LIN)                                                                                     \
+  hipLaunchKernelGGL((k_stack_step<CELL, LIN>), grid, blk, 0, env->eng->stream, net, ws, env->d_obs, flag_prev, \
+                     first, parity, z)
+    if (lstm) {
+      if (lin) STEP(LSTM, true);
+      else STEP(LSTM, false);
+    } else {
+      if (lin) STEP(GRU, true);
+      else STEP(GRU, false);
+    }
+#undef STEP
   });
 }
 
@@ -768,10 +829,16 @@ void launch_stack_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_sk
   {
     ProfScope ps(e, RL_K_POLICY_FUSED);
     const dim3 grid(cdiv_k(n, SL)), blk(SL * SW);
-    if (mod->kind == RL_MODULE_LSTM_MLP)
-      hipLaunchKernelGGL(k_stack_backward<LSTM>, grid, blk, 0, e->stream, net, ws, traj->d, traj->dz, d_skip);
-    else
-      hipLaunchKernelGGL(k_stack_backward<GRU>, grid, blk, 0, e->stream, net, ws, traj->d, traj->dz, d_skip);
+#define BWD(CELL, LIN) \
+  hipLaunchKernelGGL((k_stack_backward<CELL, LIN>), grid, blk, 0, e->stream, net, ws, traj->d, traj->dz, d_skip)
+    if (mod->kind == RL_MODULE_LSTM_MLP) {
+      if (mod->linear_tail()) BWD(LSTM, true);
+      else BWD(LSTM, false);
+    } else {
+      if (mod->linear_tail()) BWD(GRU, true);
+      else BWD(GRU, false);
+    }
+#undef BWD
   }
   {
     ProfScope ps(e, RL_K_BACKWARD);
@@ -798,9 +865,14 @@ void launch_stack_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_sk
               mod->has_bias ? obhh + (uint64_t)2 * H : 0xFFFFFFFFull);
       }
     }
-    const uint64_t oW1 = net.off[L], ob1 = oW1 + (uint64_t)H2 * H, oW2 = ob1 + H2, ob2 = oW2 + (uint64_t)A * H2;
-    wgrad(k.du, H2, k.a1, (size_t)B, H, oW1, ob1);
-    wgrad(traj->dz, A, k.ur, (size_t)B, H2, oW2, ob2);
+    if (mod->linear_tail()) {
+      const uint64_t oKernel = net.off[L], oBias = oKernel + (uint64_t)A * H;
+      wgrad(traj->dz, A, k.a1, (size_t)B, H, oKernel, oBias);
+    } else {
+      const uint64_t oW1 = net.off[L], ob1 = oW1 + (uint64_t)H2 * H, oW2 = ob1 + H2, ob2 = oW2 + (uint64_t)A * H2;
+      wgrad(k.du, H2, k.a1, (size_t)B, H, oW1, ob1);
+      wgrad(traj->dz, A, k.ur, (size_t)B, H2, oW2, ob2);
+    }
     RL_HIP_CHECK(hipGetLastError());
   }
   launch_reduce(traj, P, true, false, k.wg_rows, 0);
@@ -811,9 +883,16 @@ void launch_stack_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tange
   const StackNet net = stack_net(mod, mod->d_params), tv = stack_net(mod, d_tangent);
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
-  if (mod->kind == RL_MODULE_LSTM_MLP)
-    hipLaunchKernelGGL(k_stack_tangent<LSTM>, grid, blk, 0, traj->eng->stream, net, tv, ws, traj->d, traj->seq.out, d_skip);
-  else
-    hipLaunchKernelGGL(k_stack_tangent<GRU>, grid, blk, 0, traj->eng->stream, net, tv, ws, traj->d, traj->seq.out, d_skip);
+#define TAN(CELL, LIN)                                                                                  \
+  hipLaunchKernelGGL((k_stack_tangent<CELL, LIN>), grid, blk, 0, traj->eng->stream, net, tv, ws, traj->d, \
+                     traj->seq.out, d_skip)
+  if (mod->kind == RL_MODULE_LSTM_MLP) {
+    if (mod->linear_tail()) TAN(LSTM, true);
+    else TAN(LSTM, false);
+  } else {
+    if (mod->linear_tail()) TAN(GRU, true);
+    else TAN(GRU, false);
+  }
+#undef TAN
   RL_HIP_CHECK(hipGetLastError());
 }

@@ -1,11 +1,17 @@
 """The reference's RL^2 bandit experiment (relearn_experiments/src/bin/rl2-bandits.rs:379-425) on the meta-bandit lanes:
-`MetaEnv::new(UniformBernoulliBandits::new(arms)).wrap(TrialEpisodeLimit::new(episodes))`, policy and critic each a
-GRU(128) -> Relu -> linear head chain, TRPO at max KL 0.01, the critic fitted with 50 Adam steps per period, GAE with
-lambda 0.3, discount factor 0.99.  Recurrent chains are built for two actions, so `arms` is 2.  Every lane collects whole
+`MetaEnv::new(UniformBernoulliBandits::new(arms)).wrap(TrialEpisodeLimit::new(episodes))`, TRPO at max KL 0.01, the
+critic fitted with 50 Adam steps per period, GAE with lambda 0.3, discount factor 0.99.  Policy and critic are one
+recurrent chain each, chosen by `model`:
+    linear  the experiment's own `type Model = Chain<Gru, Linear>` (rl2-bandits.rs:349): GRU(128) -> Relu ->
+            Linear(128, out), ra.GruLinear
+    mlp     (the default) GRU(128) -> Relu -> Linear(128, 128) -> Relu -> Linear(128, out), ra.GruMlp: the chain with
+            an MLP tail, one hidden layer more than the experiment's model
+Recurrent chains are built for two actions, so `arms` is 2.  Every lane collects whole
 trials per period (horizon = trials_per_lane * (2 * episodes - 1)); the mean trial reward of a period comes from the
 device-side StepsSummary (an episode of the summary is a trial).  Prints one JSON line per period.
 
-    python scripts/rl2_bandits.py [lanes] [episodes] [periods] [trials_per_lane] [distribution] [hidden] [critic_steps]
+    python scripts/rl2_bandits.py [lanes] [episodes] [periods] [trials_per_lane] [distribution] [hidden] \\
+        [critic_steps] [model]
 """
 import json
 import os
@@ -18,13 +24,22 @@ import relearn_amd as ra  # noqa: E402
 arg = lambda i, d: type(d)(sys.argv[i]) if len(sys.argv) > i else d
 N, E, periods, trials = arg(1, 1024), arg(2, 10), arg(3, 20), arg(4, 2)
 dist, H, critic_steps = arg(5, "uniform_bernoulli"), arg(6, 128), arg(7, 50)
+model = arg(8, "mlp")
+assert model in ("mlp", "linear"), "model: mlp | linear"
 T = trials * (2 * E - 1)
 
 eng = ra.Engine(0)
 env = ra.MetaBanditEnv(eng, N, 2, E, dist, seed_env=0, seed_actor=1)
-pol, cri = ra.GruMlp(eng, env.D, 2, H, H), ra.GruMlp(eng, env.D, 1, H, H)
-pol.init(2)  # input weights Uniform(FanAvg), hidden weights Orthogonal, biases Zeros: the experiment's GruConfig
-cri.init(3)
+if model == "linear":
+    pol, cri = ra.GruLinear(eng, env.D, 2, H), ra.GruLinear(eng, env.D, 1, H)
+    glorot = ("Uniform", "FanAvg", 0.0)
+    gru_config = (glorot, ("Orthogonal", "FanAvg", 0.0), ("Zeros", "FanAvg", 0.0))
+    pol.init_with(2, *gru_config, glorot, glorot)  # the experiment's GruConfig, LinearConfig::default
+    cri.init_with(3, *gru_config, glorot, glorot)
+else:
+    pol, cri = ra.GruMlp(eng, env.D, 2, H, H), ra.GruMlp(eng, env.D, 1, H, H)
+    pol.init(2)  # input weights Uniform(FanAvg), hidden weights Orthogonal, biases Zeros: the experiment's GruConfig
+    cri.init(3)
 opt = ra.Adam(cri)
 trpo = ra.trpo_config_default()
 trpo.max_policy_step_kl = 0.01
@@ -47,7 +62,9 @@ for period in range(periods):
     summary.clear()
     summary.push(traj)
     s = summary.read()
-    print(json.dumps({"period": period, "lanes": N, "episodes_per_trial": E, "horizon": T, "distribution": dist,
+    # ("model" only for `linear`: the default's lines stay what they were before the argument existed, byte for byte)
+    print(json.dumps({**({"model": model} if model == "linear" else {}),
+                      "period": period, "lanes": N, "episodes_per_trial": E, "horizon": T, "distribution": dist,
                       "trials": s.episode_reward.count, "mean_trial_reward": s.episode_reward.mean,
                       "trial_reward_stddev": s.episode_reward.stddev(), "mean_step_reward": s.step_reward.mean,
                       "trpo_status": pst.status, "kl": pst.constraint_val_final, "entropy": pst.entropy,
