@@ -64,7 +64,13 @@ SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
       }
       launch_gru_tangent(traj, sc.x, tangent, Bt, req.skip);
     } else {
-      launch_gru_seq_forward(traj, sc.x, traj->seq.out, nullptr, grad ? seq_record(traj, sc.x) : nullptr, req.skip);
+      // The record is asked for wherever the pass kind has a backward, also when this request stops before it
+      // (forward_only): with a record the tile kernels run the bf16-pipe training forward, without one the f32 forward
+      // (launch_gru_seq_forward), and the two round differently.  rl_ppo_update's log pi_0 must come from the forward
+      // its steps recompute log pi with: then the first step's ratios are exactly 1, as the reference's are — off by
+      // an ulp they are clipped samples at clip_distance = 0.
+      launch_gru_seq_forward(traj, sc.x, traj->seq.out, nullptr, row.backward ? seq_record(traj, sc.x) : nullptr,
+                             req.skip);
       if (critic) launch_seq_critic_dvalues(traj, Bt);
       else launch_seq_policy_dlogits(traj, req.kind, Bt, req.clip_lo, req.clip_hi, req.skip);
     }
