@@ -496,6 +496,11 @@ typedef struct {
   int32_t cg_iterations;
 } rl_trpo_stats;
 
+/* Device memory: with the fused kernels (variant 0, a 5 -> 128 -> 2 policy) the first rl_trpo_update /
+ * rl_actor_critic_update / rl_policy_fvp on a trajectory allocates 20 bytes per sample of it (168 MB at 65,536 lanes x
+ * 128 steps) beside its update workspace: the gradient pass keeps its relu' masks (16 B per sample) and the Fisher weight
+ * p0 p1 (4 B) for the Fisher-vector products of the same call.  The memory is freed with the trajectory; what it holds is
+ * never read by a later call. */
 int32_t rl_trpo_update(rl_mlp *policy, rl_traj *traj, const rl_trpo_config *cfg, rl_trpo_stats *stats);
 /* pieces of the update exposed for parity tests (host vectors in flat parameter order) */
 int32_t rl_policy_gradient(rl_mlp *policy, rl_traj *traj, float *grad_out, float *loss_out, float *entropy_out);

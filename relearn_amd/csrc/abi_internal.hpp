@@ -127,6 +127,8 @@ struct PassRequest {
   bool reduce = true;         // false: stop at the slabs (a caller that fuses the reduction with its optimiser step;
                               // feed-forward modules)
   uint64_t B_total = 0;       // samples over all ranks; 0: the trajectory's (b_total)
+  bool keep = false;          // RUN_INIT with RUN_JVP passes behind it in the same call: keep the relu' masks and Fisher
+                              // weights for them (the fused 5-128-2 kernel; launch_policy_v2)
 };
 // (C++ linkage: shared between abi_update.hip and abi_dqn.hip without an unmangled name in the library's exports)
 SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req);

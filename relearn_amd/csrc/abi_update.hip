@@ -87,7 +87,7 @@ SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
   bool fused = false;
   if (traj->eng->kernel_variant == 0) {  // (1: the v1 reference kernels only)
     if (row.fused == FUSED_POLICY)
-      fused = launch_policy_v2(traj, mod, req.kind, req.tangent, Bt, req.skip, req.clip_lo, req.clip_hi);
+      fused = launch_policy_v2(traj, mod, req.kind, req.tangent, Bt, req.skip, req.clip_lo, req.clip_hi, req.keep);
     else if (row.fused == FUSED_CRITIC)
       fused = launch_critic_step_v2(traj, mod, Bt);
   }
@@ -154,8 +154,11 @@ static TrpoProgress trpo_update_head(rl_mlp *policy, rl_traj *traj, const rl_trp
   uint32_t P = (uint32_t)policy->P;
   uint64_t Bt = b_total(traj);
   float reg = (float)cfg->hpv_reg_coeff;
-  // loss gradient at theta0 and CG prologue
-  run_pass(policy, traj, RUN_INIT);
+  // loss gradient at theta0 (its relu' masks and Fisher weights kept for the products of the solve: the parameters do
+  // not move before the line search) and CG prologue
+  PassRequest init(RUN_INIT);
+  init.keep = true;
+  run_pass(policy, traj, init);
   launch_trpo_begin(traj, policy, Bt);
   // x = A^-1 g by `iterations` CG steps (early exit handled on the device)
   PassRequest fvp(RUN_JVP);
@@ -252,7 +255,9 @@ int32_t rl_policy_fvp(rl_mlp *policy, rl_traj *traj, const float *v, float reg, 
     check_policy(policy, traj);
     RL_REQUIRE(v && out, "NULL argument");
     uint32_t P = (uint32_t)policy->P;
-    run_pass(policy, traj, RUN_INIT);  // the product is taken at the current parameters: refresh log pi_0
+    PassRequest init(RUN_INIT);  // the product is taken at the current parameters: refresh log pi_0, keep the masks
+    init.keep = true;
+    run_pass(policy, traj, init);
     h2d(traj->eng, traj->cg_x, v, P * sizeof(float));  // (the recurrent pass above has grown the workspace)
     PassRequest fvp(RUN_JVP);
     fvp.tangent = traj->cg_x;

@@ -143,6 +143,14 @@ __device__ __forceinline__ float buf_f32(rsrc_t r, uint32_t lane_off, uint32_t t
 __device__ __forceinline__ uint32_t buf_u8(rsrc_t r, uint32_t lane_off, uint32_t tile_off) {
   return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)lane_off, (int)tile_off, 0);
 }
+// two words with one 8-byte load / store (a store past `bytes` is dropped)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x2 buf_u32x2(rsrc_t r, uint32_t lane_off, uint32_t tile_off) {
+  return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)lane_off, (int)tile_off, 0));
+}
+__device__ __forceinline__ void buf_store_u32x2(u32x2 v, rsrc_t r, uint32_t lane_off, uint32_t tile_off) {
+  __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)lane_off, (int)tile_off, 0);
+}
 
 union Frag {
   bf16x8 v;
@@ -617,30 +625,22 @@ __device__ __forceinline__ Dealing deal_tiles(int wave, uint32_t share_old, uint
 // selects — and the ragged last tile (tail = B % 32 samples) after them on the virtual wave whose turn it is, through the
 // same code with std::true_type.  Tile indices are wave-uniform.  load_tile(g) requests a tile's operands; the loads run
 // one tile ahead (past a virtual wave's last tile: that tile again), into two named buffers that take turns — no register
-// moves — or, for a kernel without the registers for a second buffer, into one with a move per operand.
-template <bool TWO_BUFFERS, typename L, typename T>
+// moves.  (The Fisher-vector pass walked with one buffer and a move per operand while it carried forward weight
+// fragments; with the kept masks it has the registers, and no kernel is left without: DESIGN 36.)
+template <typename L, typename T>
 __device__ __forceinline__ void walk_tiles(const Dealing &deal, uint32_t n_full, uint32_t tail, L &load_tile, T &tile) {
   const Dealing d = deal;  // (a copy: the compiler then allocates registers as for the same loops written in the kernel)
   for (uint32_t vw = 0; vw < d.share; ++vw) {
     const uint32_t wave_id = d.first + vw;
     if (wave_id < n_full) {
       auto op_a = load_tile(wave_id), op_b = op_a;
-      if (!TWO_BUFFERS) {
-        for (uint32_t g = wave_id; g < n_full; g += d.n_waves) {
-          const uint32_t g1 = g + d.n_waves;
-          op_b = load_tile(g1 < n_full ? g1 : g);
-          tile(std::false_type{}, op_a, g);
-          op_a = op_b;
-        }
-      } else {
-        for (uint32_t g = wave_id; g < n_full; g += 2 * d.n_waves) {
-          const uint32_t g1 = g + d.n_waves, g2 = g1 + d.n_waves;
-          op_b = load_tile(g1 < n_full ? g1 : g);
-          tile(std::false_type{}, op_a, g);
-          if (g1 >= n_full) break;
-          op_a = load_tile(g2 < n_full ? g2 : g1);
-          tile(std::false_type{}, op_b, g1);
-        }
+      for (uint32_t g = wave_id; g < n_full; g += 2 * d.n_waves) {
+        const uint32_t g1 = g + d.n_waves, g2 = g1 + d.n_waves;
+        op_b = load_tile(g1 < n_full ? g1 : g);
+        tile(std::false_type{}, op_a, g);
+        if (g1 >= n_full) break;
+        op_a = load_tile(g2 < n_full ? g2 : g1);
+        tile(std::false_type{}, op_b, g1);
       }
     }
     if (tail != 0 && n_full % d.n_waves == wave_id) tile(std::true_type{}, load_tile(n_full), n_full);

@@ -404,6 +404,15 @@ struct rl_traj {
   float *lp0 = nullptr;     // [act_planes][B]
   float *dz = nullptr;      // [act_planes][B]
   uint32_t act_planes = 2;  // one plane per action of the widest policy used so far (traj_ensure_action_planes)
+  // What a keeping gradient pass of the fused 5-128-2 kernel leaves for the Fisher-vector passes behind it (mask_plane.hpp,
+  // DESIGN 36): the relu' masks as bits, 8 bytes per (32-sample tile, lane), and the Fisher weight p0 p1 per sample —
+  // 20 bytes per sample, allocated on first use.  Valid for ONE C-ABI call, like a module's weight image: the keeping
+  // launch stamps the call's epoch, the policy and the sample count, launch_policy_v2 requires all three of a PASS_JVP
+  // launch and fails the call otherwise.  Nothing carries over between calls.
+  uint32_t *kept_mask = nullptr;
+  float *kept_w = nullptr;
+  uint64_t kept_epoch = 0, kept_samples = 0;  // rl_engine::call_epoch / rl_traj::B of the keeping launch
+  const rl_mlp *kept_policy = nullptr;
   // the action count of the env the last rollout recorded (0: the planes were written by the host, rl_traj_write), and
   // the largest action index a host-written action plane holds: what a policy's out_dim is checked against
   uint32_t n_actions = 0, max_action = 0;

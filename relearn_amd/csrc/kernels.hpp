@@ -105,8 +105,11 @@ void launch_reduce_opt(rl_traj *traj, rl_adam *opt, uint32_t rowsA, uint32_t row
 // matrix pipe (bf16_tile.hpp); a module with several hidden layers goes on to launch_gen_mfma
 // return false when the shape is not built (the caller has the v1 kernels)
 bool launch_critic_step_v2(rl_traj *traj, const rl_mlp *critic, uint64_t B_total);
+// `keep` (PASS_INIT of a 5-128-2 module): the gradient pass also leaves its relu' masks and Fisher weights in the
+// trajectory's kept planes for the PASS_JVP launches of the same call, which read them and refuse to run without
+// (rl_traj::kept_epoch); every other kernel family ignores it
 bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float *d_tangent, uint64_t B_total,
-                      const int32_t *d_skip_flag, float clip_lo = 0.0f, float clip_hi = 0.0f);
+                      const int32_t *d_skip_flag, float clip_lo = 0.0f, float clip_hi = 0.0f, bool keep = false);
 
 // kernels_dqn.hip
 // d_range (may be NULL): the collected observations' magnitude range is folded there (the fused gradient's range guard)

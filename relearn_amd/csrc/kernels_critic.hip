@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(CRITIC_WAVES * 64, 2)
   // (loading two tiles ahead — by register moves or by rotating three named buffers through a loop unrolled three
   // times — is SLOWER than the walk's one, 0.237 against 0.220 ms per step, although a timing build without the loads
   // runs in 0.197: what the loads cost is issue slots, not exposed latency)
-  bt::walk_tiles<true>(deal, n_full, tail, load_tile, tile);
+  bt::walk_tiles(deal, n_full, tail, load_tile, tile);
   if (since_flush != 0 || !flushed) {  // (a wave whose tile count is a multiple of the flush period has nothing left: at
                                        // the headline size every wave owns exactly 2 x C_FLUSH tiles, and this was a
                                        // third flush of zeros; a wave without tiles still defines its image)

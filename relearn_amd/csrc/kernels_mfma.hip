@@ -7,6 +7,7 @@
 #include "bf16_tile.hpp"
 #include "device_fns.hpp"
 #include "kernels.hpp"
+#include "mask_plane.hpp"
 #include "policy_fast.hpp"
 
 constexpr int V2_WAVES = 8;        // policy kernels: one workgroup of eight waves per CU (two per SIMD)
@@ -14,8 +15,10 @@ constexpr int V2_WAVES = 8;        // policy kernels: one workgroup of eight wav
 // ================================================================================================
 // Policy passes on the bf16 matrix pipe (tile machinery: bf16_tile.hpp; every product exact, f32 accumulation).
 //   PASS_INIT / PASS_PPO   gradient of the (clipped) surrogate: forward, per-sample math, masked-sum backward
-//   PASS_JVP               Fisher-vector product J^T (diag p - p p^T) J v: forward for the relu' masks, tangent forward,
-//                          per-sample metric, masked-sum backward
+//   PASS_JVP               Fisher-vector product J^T (diag p - p p^T) J v: tangent forward, per-sample metric, masked-sum
+//                          backward — on the relu' masks and the Fisher weights p0 p1 the gradient pass of the same call
+//                          KEPT for it (PASS_INIT with KEEP: mask_plane.hpp); the parameters do not move
+//                          during the conjugate-gradient solve, so the pass has no forward of its own
 //   PASS_EVAL              surrogate loss and KL of candidate parameters: forward only
 // Forward output layer (INIT / PPO / EVAL): relu through |x| as in the critic step — for each of the two logits
 //   z_a = b2_a + (v_a . x~ + sum_j w2_aj |pre_j|) / 2,  v_ak = sum_j w2_aj W~1[j][k].
@@ -34,12 +37,14 @@ constexpr int V2_WAVES = 8;        // policy kernels: one workgroup of eight wav
 constexpr int PB_FLUSH = 16;  // f32 -> f64 flush period in tiles (32 / 64: 2 % faster Fisher-vector products, measured; TRPO's
                               // CG wants the shorter f32 accumulation)
 
-template <int MODE, int WAVES, bool FW_LDS = false>
+template <int MODE, int WAVES, bool FW_LDS = false, bool KEEP = false>
 __global__ void __launch_bounds__(WAVES * 64)
     k_policy_bf16(TrajDev tr, const float *__restrict__ params, const uint32_t *__restrict__ wimg,
                   const float *__restrict__ tangent, float *__restrict__ lp0, double *__restrict__ slabA,
                   double *__restrict__ slabB, float inv_B, uint32_t P, const int32_t *__restrict__ skip, float clip_lo,
-                  float clip_hi, uint32_t share_old, uint32_t share_young) {
+                  float clip_hi, uint32_t share_old, uint32_t share_young, uint32_t *__restrict__ kept_mask,
+                  float *__restrict__ kept_w) {
+  static_assert(!KEEP || MODE == PASS_INIT, "only the gradient pass keeps");
   using bt::Frag;
   constexpr int D = 5, H = 128, NT = bt::NT, A = 2;
   constexpr bool BWD = MODE != PASS_EVAL;
@@ -69,21 +74,22 @@ __global__ void __launch_bounds__(WAVES * 64)
   float w2d[NT];
   float lvd[3] = {0.0f, 0.0f, 0.0f};  // the linear half of relu (bf16_tile.hpp) for the differenced logit
   float tb2d = 0.0f;
-  bt::load_weights<bt::GUARD_POLICY>(wimg, wave, lane, 2, tr.range, tr.range_err, fw, [&](int t, const bt::WRaw &r) {
+  // (the Fisher-vector pass reads no weights: its masks are the kept ones, and the range guard has run in the gradient
+  // pass of the same call)
+  auto fold_raw = [&](int t, const bt::WRaw &r) {
     if (FW_LDS && wave == t) {
 #pragma unroll
       for (int i = 0; i < 3; ++i) Fw[t * 3 + i][lane] = fw[t][i].x;
     }
     // the forward runs on weights scaled by 2^96 (relu' by conversion, bf16_tile.hpp); the |pre| chain of the gradient /
-    // evaluation passes takes the scale back out through w2d (both exact); the Fisher-vector pass only needs the masks
+    // evaluation passes takes the scale back out through w2d (both exact)
     const float wd = r.w2[0] - r.w2[1];
-    if (!JVP) {
-      lvd[0] = __builtin_fmaf(wd, r.wa, lvd[0]);
-      lvd[1] = __builtin_fmaf(wd, r.wb, lvd[1]);
-      lvd[2] = __builtin_fmaf(wd, r.wc, lvd[2]);
-    }
+    lvd[0] = __builtin_fmaf(wd, r.wa, lvd[0]);
+    lvd[1] = __builtin_fmaf(wd, r.wb, lvd[1]);
+    lvd[2] = __builtin_fmaf(wd, r.wc, lvd[2]);
     w2d[t] = bt::FWD_UNSCALE * wd;
-  });
+  };
+  if (!JVP) bt::load_weights<bt::GUARD_POLICY>(wimg, wave, lane, 2, tr.range, tr.range_err, fw, fold_raw);
   if (JVP) {
     // Z_jk = w2d_j V~1[j][k] + t2d_j W~1[j][k] (k = 5: the bias row): the tangent logit difference is
     // sum_j relu'(pre_j) (x~ . Z_j) + (vb2_0 - vb2_1) = sum_k x~_k q_k + ..., q = the masked sum of Z's rows
@@ -135,12 +141,20 @@ __global__ void __launch_bounds__(WAVES * 64)
   const bt::rsrc_t adv_r = bt::make_rsrc(tr.adv, B32 * 4u), act_r = bt::make_rsrc(tr.action, B32);
   const uint32_t off_a = ((uint32_t)(2 * hf) * plane32 + (uint32_t)n) * 4u, off_b = off_a + plane32 * 4u;
   const uint32_t off_c = (4u * plane32 + (uint32_t)n) * 4u, off_s = (uint32_t)n * 4u, off_s1 = off_s + B32 * 4u;
+  // the kept planes (KEEP writes, the Fisher-vector pass reads): 8 bytes of mask bits per (tile, lane), one Fisher weight
+  // per sample
+  const uint32_t n_tiles32 = (B32 + 31u) / 32u;
+  const bt::rsrc_t km_r = bt::make_rsrc(kept_mask, n_tiles32 * mp::TILE_BYTES), kw_r = bt::make_rsrc(kept_w, B32 * 4u);
+  const uint32_t off_m = mp::lane_offset(lane);
   int since_flush = 0;
   // per lane: features 2 hf, 2 hf + 1 and 4 of sample n, and the per-sample scalars the pass needs (log pi_0 of both
-  // actions; advantage and action) — all requested one tile ahead
+  // actions; advantage and action; the Fisher-vector pass: the lane's kept mask words and its sample's kept weight) — all
+  // requested one tile ahead
   struct TileOp {
     float xa, xb, xc, l0, l1, adv;
     int act;
+    uint32_t m[mp::WORDS];
+    float w;
   };
   auto load_tile = [&](uint32_t g) {  // g: wave-uniform tile index
     TileOp o;
@@ -148,9 +162,15 @@ __global__ void __launch_bounds__(WAVES * 64)
     o.xa = bt::buf_f32(obs_r, off_a, soff);
     o.xb = bt::buf_f32(obs_r, off_b, soff);
     o.xc = bt::buf_f32(obs_r, off_c, soff);
-    o.l0 = o.l1 = o.adv = 0.0f;
+    o.l0 = o.l1 = o.adv = o.w = 0.0f;
     o.act = 0;
-    if (MODE != PASS_INIT) {  // log pi_0 (written by PASS_INIT, read by the others)
+    o.m[0] = o.m[1] = 0u;
+    if (JVP) {
+      const bt::u32x2 mw = bt::buf_u32x2(km_r, off_m, mp::tile_offset(g));
+      o.m[0] = mw[0];
+      o.m[1] = mw[1];
+      o.w = bt::buf_f32(kw_r, off_s, soff);
+    } else if (MODE != PASS_INIT) {  // log pi_0 (written by PASS_INIT, read by the others)
       o.l0 = bt::buf_f32(lp0_r, off_s, soff);
       o.l1 = bt::buf_f32(lp0_r, off_s1, soff);
     }
@@ -176,9 +196,10 @@ __global__ void __launch_bounds__(WAVES * 64)
     op.l1 = op.valid ? op_in.l1 : 0.0f;
     op.adv = op.valid ? op_in.adv : 0.0f;
     op.act = op.valid ? op_in.act : 0;
+    const float kw_in = op.valid ? op_in.w : 0.0f;
     const size_t sidx = (size_t)g * 32 + n;
     Frag fa[3];
-    bt::input_frags(op.xa, op.xb, op.xc, op.valid, hf, fa);
+    if (!JVP) bt::input_frags(op.xa, op.xb, op.xc, op.valid, hf, fa);
     Frag ga[NT][2];
     float y0[16];
 #pragma unroll
@@ -193,18 +214,34 @@ __global__ void __launch_bounds__(WAVES * 64)
       }
       return bt::layer1(fa, fw[t]);
     };
-    bt::f32x16 c = fwd(0);
+    if (JVP) {
+      // the kept masks (a padding sample's bits are 0: the keeping pass saw pre = 0 there), decoded into the register
+      // contents bt::mask_tile would leave: two vector instructions per pair, one shift per eight
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      bt::f32x16 cn = c;
-      if (t + 1 < NT) cn = fwd(t + 1);
-      if (!JVP) {
+      for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) ga[t][s].u[i] = mp::decode_pair(op_in.m, mp::pair_index(t, s, i));
+        q = bt::masked_sum_tile(ga[t], idb, Fz, t, lane, q);
+      }
+    } else {
+      uint32_t grp[NT];  // KEEP: the tile's mask bits, a group word per hidden tile (mask_plane.hpp)
+      bt::f32x16 c = fwd(0);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        bt::f32x16 cn = c;
+        if (t + 1 < NT) cn = fwd(t + 1);
 #pragma unroll
         for (int r = 0; r < 16; ++r) y0[r] = __builtin_fmaf(__builtin_fabsf(c[r]), w2d[t], y0[r]);
+        if (BWD) bt::mask_tile(c, ga[t]);  // relu'(pre): one conversion per two values
+        if (KEEP) grp[t] = mp::encode_group([&](int k) { return ga[t][k >> 2].u[k & 3]; });
+        c = cn;
       }
-      if (BWD) bt::mask_tile(c, ga[t]);  // relu'(pre): one conversion per two values
-      if (JVP) q = bt::masked_sum_tile(ga[t], idb, Fz, t, lane, q);
-      c = cn;
+      if (KEEP) {
+        const bt::u32x2 mw = {mp::encode_word(grp[0], grp[1]), mp::encode_word(grp[2], grp[3])};
+        bt::buf_store_u32x2(mw, km_r, off_m, mp::tile_offset(g));
+      }
     }
     float s0;
     if (JVP) {
@@ -220,8 +257,7 @@ __global__ void __launch_bounds__(WAVES * 64)
     float dz0 = 0.0f, dz1 = 0.0f;
     if (JVP) {
       const float delta = s0 + tb2d;
-      const SoftPair old = soft_pair(op.l0 - op.l1);  // pi_0 from its stored log-probabilities
-      dz0 = op.valid ? (old.p[0] * old.p[1]) * delta * inv_B : 0.0f;
+      dz0 = op.valid ? kw_in * delta * inv_B : 0.0f;  // kw_in = p0 p1 of pi_0, kept by the gradient pass
       dz1 = -dz0;
     } else {
       const float adv = op.adv;
@@ -245,6 +281,10 @@ __global__ void __launch_bounds__(WAVES * 64)
         if (op.valid && hf == 0) {
           lp0[sidx] = lp[0];
           lp0[B + sidx] = lp[1];
+          if (KEEP) {  // the Fisher weight of the sample, from the values just stored
+            const SoftPair old = soft_pair(lp[0] - lp[1]);  // pi_0 from its stored log-probabilities
+            kept_w[sidx] = old.p[0] * old.p[1];
+          }
         }
         const float lpa = act == 0 ? lp[0] : lp[1];
         const float ratio = fast_expf(lpa - lpa);
@@ -296,8 +336,9 @@ __global__ void __launch_bounds__(WAVES * 64)
       fold();
     }
   };
-  // (the Fisher-vector pass has no registers for a second operand buffer)
-  bt::walk_tiles<!JVP>(deal, n_full, tail, load_tile, tile);
+  // (two operand buffers in every pass: without its forward weight fragments the Fisher-vector pass has the registers for
+  // the second one — 189 -> 178 us per launch at 8.4 M samples)
+  bt::walk_tiles(deal, n_full, tail, load_tile, tile);
   if (BWD && (since_flush != 0 || !flushed)) bt::flush(dm, acc64, IW, n, hf, !flushed);  // (nothing left when the last
                                                                 // tile ended a flush period; a wave without tiles
                                                                 // still defines its image)
@@ -345,12 +386,30 @@ __global__ void __launch_bounds__(WAVES * 64)
   }
 }
 
+// The kept planes of a trajectory (mask_plane.hpp; engine.hpp says who may trust them): room for the samples the
+// trajectory was allocated for, on first use
+static void traj_ensure_kept_planes(rl_traj *t) {
+  const uint64_t samples = (uint64_t)t->d.n * t->d.T;
+  t->mem.ensure(t->kept_mask, mp::plane_words(samples));
+  t->mem.ensure(t->kept_w, samples);
+}
+
 // gradient (PASS_INIT), Fisher-vector product (PASS_JVP) or loss/KL evaluation (PASS_EVAL) in one launch
 bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float *d_tangent, uint64_t B_total,
-                      const int32_t *d_skip, float clip_lo, float clip_hi) {
+                      const int32_t *d_skip, float clip_lo, float clip_hi, bool keep) {
   if (policy->general) return launch_gen_mfma(traj, policy, mode, d_tangent, B_total, d_skip, clip_lo, clip_hi);
   if (!fused_5_128_fits(traj, policy, 2)) return false;  // (only feed-forward modules are passed here)
   if (mode == PASS_DQN) return false;  // k_dqn_step_bf16 (kernels_dqn.hip)
+  keep = keep && mode == PASS_INIT;
+  if (keep) {
+    traj->kept_epoch = 0;  // (until the launch is enqueued: a failure on the way leaves nothing to trust)
+    traj_ensure_kept_planes(traj);
+  }
+  if (mode == PASS_JVP && !(traj->kept_epoch == traj->eng->call_epoch && traj->kept_policy == policy &&
+                            traj->kept_samples == traj->B && traj->kept_mask != nullptr && traj->kept_w != nullptr))
+    throw RlError(RL_ERR_UNSUPPORTED,
+                  "internal error: a Fisher-vector pass without a keeping gradient pass of the same policy and trajectory "
+                  "before it in the same call (its relu' masks would be stale)");
   traj_ensure_range(traj);
   const uint32_t *wimg = wimg_ensure(policy);
   ProfScope ps(traj->eng, mode == PASS_JVP ? RL_K_POLICY_FVP : RL_K_POLICY_FUSED);
@@ -363,9 +422,19 @@ bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float
   const TrajDev d = fused_traj_dev(traj, traj->guard_next_policy);
 #define BLAUNCH(MM)                                                                                                  \
   hipLaunchKernelGGL((k_policy_bf16<MM, V2_WAVES>), g, b, 0, s, d, policy->d_params, wimg, d_tangent, traj->lp0,       \
-                     traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo, clip_hi, bt::SHARE_OLD, bt::SHARE_YOUNG)
-  if (mode == PASS_INIT) BLAUNCH(PASS_INIT);
-  else if (mode == PASS_JVP) BLAUNCH(PASS_JVP);
+                     traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo, clip_hi, bt::SHARE_OLD, bt::SHARE_YOUNG,      \
+                     traj->kept_mask, traj->kept_w)
+  if (keep) {
+    hipLaunchKernelGGL((k_policy_bf16<PASS_INIT, V2_WAVES, false, true>), g, b, 0, s, d, policy->d_params, wimg,
+                       d_tangent, traj->lp0, traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo, clip_hi, bt::SHARE_OLD,
+                       bt::SHARE_YOUNG, traj->kept_mask, traj->kept_w);
+    traj->kept_epoch = traj->eng->call_epoch;
+    traj->kept_policy = policy;
+    traj->kept_samples = traj->B;
+  } else if (mode == PASS_INIT) {
+    traj->kept_epoch = 0;  // (log pi_0 is rewritten without the planes that go with it)
+    BLAUNCH(PASS_INIT);
+  } else if (mode == PASS_JVP) BLAUNCH(PASS_JVP);
   else if (mode == PASS_PPO) BLAUNCH(PASS_PPO);
   else {
     // the evaluation pass has no backward state: with the weight fragments in LDS it fits twelve waves per CU (152
@@ -373,7 +442,7 @@ bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float
     constexpr int EVAL_WAVES = 16;
     hipLaunchKernelGGL((k_policy_bf16<PASS_EVAL, EVAL_WAVES, true>), g, dim3(EVAL_WAVES * 64), 0, s, d,
                        policy->d_params, wimg, d_tangent, traj->lp0, traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo,
-                       clip_hi, 1u, 1u);
+                       clip_hi, 1u, 1u, nullptr, nullptr);
   }
 #undef BLAUNCH
   return true;
