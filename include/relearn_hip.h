@@ -433,6 +433,36 @@ int32_t rl_rnn_mlp_create_config(rl_engine *engine, int32_t cell, uint32_t in_di
  * hidden_size, W1 = I, b1 = 0 (tests/test_gpu_chain_linear.py). */
 int32_t rl_rnn_linear_create(rl_engine *engine, int32_t cell, uint32_t in_dim, uint32_t hidden_size,
                              uint32_t num_layers, int32_t rnn_bias, uint32_t out_dim, rl_mlp **out);
+/* ChainConfig<GruConfig | LstmConfig, MlpConfig | LinearConfig> in one statement (modules/chain.rs:12-56,
+ * seq/rnn/mod.rs:20-45,223-281) — and the one constructor of recurrent chains with MORE THAN TWO outputs: a categorical
+ * policy over IndexSpace::new(3..8), what MetaEnv<UniformBernoulliBandits(3 | 4)>, OneHotBandits::new(3)
+ * (src/agents/meta.rs:239) and MemoryGame::new(k >= 3, h) need.  The five constructors above remain the two-action
+ * shorthand (out_dim in {1, 2}); for out_dim <= 2 this one builds exactly what the matching one of them builds (same
+ * parameter count, same kernels, the fused 5 -> 128 -> 128 tile kernels and their padded twin included).
+ *   cell RL_CELL_GRU | RL_CELL_LSTM; in_dim 1..8; hidden 1..256; num_layers 1..4 (0 -> RL_ERR_BUILD_AGENT, > 4 ->
+ *   RL_ERR_UNSUPPORTED); rnn_bias 0 | 1; mlp_hidden 0..256, 0: the second module is one Linear(hidden, out_dim), else
+ *   Mlp([mlp_hidden]); out_dim 1..8 (0 or 9 -> RL_ERR_BUILD_AGENT).  A NULL `out` or `cfg`: RL_ERR_INVALID_ARGUMENT.
+ * out_dim >= 3 always runs the lane-per-thread kernels (kernels_seq_stack.hip) at the module's own widths, never a twin:
+ * the head's outputs are computed in passes of four rows, each the forward's contract chain (acc = bias[q]; acc =
+ * fma(x_k, w[q][k], acc), k ascending), so rl_seq_forward stays bit-identical to the C restatement.  Flat order, the
+ * initialisation stream (the head is drawn at its real out_dim) and the actor document (head tensors [out_dim, .]) are
+ * those of the two-action chains.  Every entry point of those chains applies: rl_rollout (out_dim must equal the env's
+ * action count; meta-bandit lanes of 2..4 arms in one launch, every other env one launch sequence per step),
+ * rl_seq_forward, rl_policy_gradient / _fvp / _loss_kl, rl_trpo_update, rl_ppo_update, rl_reinforce_update,
+ * rl_actor_critic_update and its begin / finish pair, rl_params_get / _set, rl_mlp_init, rl_rnn_mlp_init_with,
+ * rl_actor_to_cbor / rl_module_from_cbor.  Not an action-value module: rl_dqn_create refuses it. */
+typedef struct {
+  int32_t cell;        /* RL_CELL_GRU | RL_CELL_LSTM */
+  uint32_t in_dim;     /* observation features */
+  uint32_t hidden;     /* RnnBaseConfig::hidden_size */
+  uint32_t num_layers; /* RnnBaseConfig::num_layers */
+  int32_t rnn_bias;    /* RnnBaseConfig::bias_init is Some */
+  uint32_t mlp_hidden; /* MlpConfig::hidden_sizes = [mlp_hidden]; 0: a Linear tail */
+  uint32_t out_dim;    /* outputs: 1 (a critic) or the action count 2..8 */
+} rl_rnn_chain_config;
+/* RnnBaseConfig::default / ChainConfig::default over MlpConfig::default: 5 -> 128 -> [128] -> 2, one layer, bias vectors */
+int32_t rl_rnn_chain_config_default(int32_t cell, rl_rnn_chain_config *cfg);
+int32_t rl_rnn_chain_create(rl_engine *engine, const rl_rnn_chain_config *cfg, rl_mlp **out);
 
 /* ---------------------------------------------------------------------------------------------
  * Trajectory store (replaces VecBuffer + LazyHistoryFeatures: src/agents/buffers/vec.rs:15-143,

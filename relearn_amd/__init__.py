@@ -53,7 +53,7 @@ ABI_SYMBOLS = [
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
-    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_mlp_init_with", "rl_seq_forward",
+    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_chain_config_default", "rl_rnn_chain_create", "rl_rnn_mlp_init_with", "rl_seq_forward",
     "rl_traj_create", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write",
     "rl_rollout", "rl_gae",
     "rl_trpo_config_default", "rl_trpo_update", "rl_policy_gradient", "rl_policy_fvp", "rl_policy_loss_kl",
@@ -645,6 +645,42 @@ class LstmLinear(GruLinear):
     """`ChainConfig<LstmConfig, LinearConfig>::build_module(in, out)`: LSTM layers -> ReLU -> Linear."""
 
     CELL = 1  # RL_CELL_LSTM
+
+
+class RnnChainConfig(C.Structure):
+    """rl_rnn_chain_config"""
+    _fields_ = [("cell", C.c_int32), ("in_dim", C.c_uint32), ("hidden", C.c_uint32), ("num_layers", C.c_uint32),
+                ("rnn_bias", C.c_int32), ("mlp_hidden", C.c_uint32), ("out_dim", C.c_uint32)]
+
+
+CELLS = {"gru": 0, "lstm": 1}  # RL_CELL_GRU, RL_CELL_LSTM
+
+
+def rnn_chain_config_default(cell):
+    cfg = RnnChainConfig()
+    _check(lib().rl_rnn_chain_config_default(C.c_int32(CELLS.get(cell, cell)), C.byref(cfg)))
+    return cfg
+
+
+class RnnChain(GruMlp):
+    """`ChainConfig<GruConfig | LstmConfig, MlpConfig | LinearConfig>::build_module(in, out)` in one statement
+    (rl_rnn_chain_create): `cell` "gru" | "lstm" (or RL_CELL_*), `mlp_hidden` None: a Linear tail, else Mlp([mlp_hidden]);
+    out_dim 1..8 — the one constructor of recurrent chains over more than two actions.  GruMlp / LstmMlp / GruLinear /
+    LstmLinear stay the two-action shorthand; for out_dim <= 2 this builds what they build."""
+
+    def __init__(self, engine, cell, in_dim, hidden, out_dim, num_layers=1, bias=True, mlp_hidden=None):
+        self.eng = engine
+        self.h = C.c_void_p()
+        self.CELL = CELLS.get(cell, cell)
+        cfg = RnnChainConfig(self.CELL, in_dim, hidden, num_layers, 1 if bias else 0, mlp_hidden or 0, out_dim)
+        _check(lib().rl_rnn_chain_create(engine.h, C.byref(cfg), C.byref(self.h)), engine.h)
+        _register(self)
+        n = C.c_uint64()
+        _check(lib().rl_mlp_num_params(self.h, C.byref(n)), engine.h)
+        self.P = n.value
+        # (`hidden`: the width of an MLP tail's hidden layer, 0 for a Linear tail — the attribute names of GruMlp)
+        self.in_dim, self.hidden, self.out_dim, self.gru_hidden = in_dim, mlp_hidden or 0, out_dim, hidden
+        self.num_layers = num_layers
 
 
 ACTIVATIONS = ["Identity", "Relu", "Sigmoid", "Tanh"]  # rl_activation, in the reference enum's order

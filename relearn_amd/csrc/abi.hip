@@ -1071,7 +1071,7 @@ int32_t rl_mlp_create_config(rl_engine *e, uint32_t in_dim, const uint32_t *hidd
 // out_dim) (mlp_hidden is 0 and marks it, rl_mlp::linear_tail); always the lane-per-thread kernels, never a twin.
 static void seq_module_create(rl_engine *e, int kind, uint32_t in_dim, uint32_t rnn_hidden, uint32_t num_layers,
                               uint32_t mlp_hidden, uint32_t out_dim, rl_mlp **out, bool rnn_bias = true,
-                              bool linear_tail = false) {
+                              bool linear_tail = false, uint32_t max_out = 2) {
   RL_REQUIRE(e && out, "NULL argument");
   *out = nullptr;
   if (num_layers == 0) throw RlError(RL_ERR_BUILD_AGENT, "RnnBaseConfig::num_layers must be at least 1");
@@ -1079,9 +1079,11 @@ static void seq_module_create(rl_engine *e, int kind, uint32_t in_dim, uint32_t 
     throw RlError(RL_ERR_UNSUPPORTED, "recurrent chains are built for RnnBaseConfig::num_layers <= 4");
   if (in_dim < 1 || in_dim > RL_TRAJ_MAX_OBS_DIM || rnn_hidden < 1 || rnn_hidden > RL_MLP_MAX_WIDTH ||
       (linear_tail ? mlp_hidden != 0 : mlp_hidden < 1) || mlp_hidden > RL_MLP_MAX_WIDTH ||
-      !(out_dim == 1 || out_dim == 2))
+      out_dim < 1 || out_dim > max_out)
     throw RlError(RL_ERR_BUILD_AGENT,
-                  linear_tail
+                  max_out > 2
+                      ? "supported recurrent chain shapes: in_dim 1..8, recurrent hidden 1..256, mlp_hidden 0..256, out_dim 1..8"
+                  : linear_tail
                       ? "supported recurrent chain shapes: in_dim 1..8, recurrent hidden 1..256, out_dim in {1,2}"
                       : "supported recurrent chain shapes: in_dim 1..8, recurrent hidden 1..256, mlp_hidden 1..256, out_dim in {1,2}");
   RL_HIP_CHECK(hipSetDevice(e->device));
@@ -1158,6 +1160,38 @@ int32_t rl_rnn_linear_create(rl_engine *e, int32_t cell, uint32_t in_dim, uint32
     if (rnn_bias != 0 && rnn_bias != 1) throw RlError(RL_ERR_BUILD_AGENT, "rnn_bias is 0 or 1");
     seq_module_create(e, cell == RL_CELL_GRU ? RL_MODULE_GRU_MLP : RL_MODULE_LSTM_MLP, in_dim, hidden_size, num_layers,
                       0, out_dim, out, rnn_bias != 0, true);
+  });
+}
+
+// ChainConfig<GruConfig | LstmConfig, MlpConfig | LinearConfig>::build_module in one statement (modules/chain.rs:12-56,
+// seq/rnn/mod.rs:20-45,223-281): the constructors above are its two-action shorthand and build the same handle for
+// out_dim <= 2; out_dim 3..8 — a categorical policy over IndexSpace::new(3..8) — always runs the lane-per-thread kernels
+// (rl_mlp::lane_kernels), never a twin.
+int32_t rl_rnn_chain_config_default(int32_t cell, rl_rnn_chain_config *cfg) {
+  return guarded(nullptr, [&] {
+    RL_REQUIRE(cfg, "cfg is NULL");
+    if (cell != RL_CELL_GRU && cell != RL_CELL_LSTM) throw RlError(RL_ERR_BUILD_AGENT, "unknown recurrent cell");
+    // RnnBaseConfig::default (seq/rnn/mod.rs:28-45): hidden_size 128, num_layers 1, bias vectors; ChainConfig::default
+    // (modules/chain.rs:19-33) over MlpConfig::default (ff/mlp.rs:24-34): one hidden layer of 128
+    cfg->cell = cell;
+    cfg->in_dim = 5;
+    cfg->hidden = 128;
+    cfg->num_layers = 1;
+    cfg->rnn_bias = 1;
+    cfg->mlp_hidden = 128;
+    cfg->out_dim = 2;
+  });
+}
+
+int32_t rl_rnn_chain_create(rl_engine *e, const rl_rnn_chain_config *cfg, rl_mlp **out) {
+  return guarded(e, [&] {
+    RL_REQUIRE(e && cfg && out, "NULL argument");
+    *out = nullptr;
+    if (cfg->cell != RL_CELL_GRU && cfg->cell != RL_CELL_LSTM) throw RlError(RL_ERR_BUILD_AGENT, "unknown recurrent cell");
+    if (cfg->rnn_bias != 0 && cfg->rnn_bias != 1) throw RlError(RL_ERR_BUILD_AGENT, "rnn_bias is 0 or 1");
+    seq_module_create(e, cfg->cell == RL_CELL_GRU ? RL_MODULE_GRU_MLP : RL_MODULE_LSTM_MLP, cfg->in_dim, cfg->hidden,
+                      cfg->num_layers, cfg->mlp_hidden, cfg->out_dim, out, cfg->rnn_bias != 0, cfg->mlp_hidden == 0,
+                      RL_MLP_MAX_OUT);
   });
 }
 
@@ -1697,8 +1731,9 @@ int32_t rl_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     traj->range_valid = traj->range_reset = false;  // new observations: the range guard has them measured again
     traj->rtg_scan_valid = false;                   // new rewards: the return plane belongs to the old ones
     RL_REQUIRE(traj->d.n == env->cfg.n_lanes && traj->d.D == env->D, "trajectory shape does not match the env");
-    if (rl_module_is_recurrent(policy->kind) && env->A > 2)
-      throw RlError(RL_ERR_UNSUPPORTED, "recurrent chains are built for two actions: this env has more");
+    // (the two-action recurrent constructors' modules; a chain of rl_rnn_chain_create has one output per action)
+    if (rl_module_is_recurrent(policy->kind) && env->A > 2 && policy->out_dim <= 2)
+      throw RlError(RL_ERR_UNSUPPORTED, "this recurrent chain is built for two actions: the env has more");
     RL_REQUIRE(policy->in_dim == env->D && policy->out_dim == env->A, "policy shape does not match the env");
     traj->n_actions = env->A;
     // the fused index-env kernels are built for five states (Chain::default, MemoryGame::new(2, 3), the bandit's

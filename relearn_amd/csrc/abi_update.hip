@@ -72,7 +72,7 @@ SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
       launch_gru_seq_forward(traj, sc.x, traj->seq.out, nullptr, row.backward ? seq_record(traj, sc.x) : nullptr,
                              req.skip);
       if (critic) launch_seq_critic_dvalues(traj, Bt);
-      else launch_seq_policy_dlogits(traj, req.kind, Bt, req.clip_lo, req.clip_hi, req.skip);
+      else launch_seq_policy_dlogits(traj, req.kind, Bt, req.clip_lo, req.clip_hi, req.skip, sc.x->out_dim);
     }
     if (grad) {
       launch_gru_backward(traj, sc.x, req.skip);
@@ -129,8 +129,9 @@ static void check_policy(const rl_mlp *policy, const rl_traj *traj) {
   RL_REQUIRE(traj->n_actions == 0 || policy->out_dim == traj->n_actions,
              "policy outputs do not match the action count of the env this trajectory was collected on");
   RL_REQUIRE(policy->out_dim > traj->max_action, "the trajectory holds an action index the policy has no output for");
-  if (policy->out_dim > 2 && policy->kind != RL_MODULE_MLP)
-    throw RlError(RL_ERR_UNSUPPORTED, "recurrent chains are built for two actions");
+  // (a recurrent chain of more than two outputs runs the lane-per-thread kernels: rl_rnn_chain_create)
+  if (policy->out_dim > 2 && policy->kind != RL_MODULE_MLP && !policy->lane_kernels())
+    throw RlError(RL_ERR_UNSUPPORTED, "the recurrent tile kernels are built for two actions");
 }
 
 // Trpo::update (trpo.rs:97-164) on the engine's current stream, in two halves.  The head enqueues everything up to and

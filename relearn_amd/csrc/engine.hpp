@@ -270,8 +270,9 @@ struct rl_mlp {
   // (or recurrent weights without bias vectors, RnnBaseConfig::bias_init = None: `has_bias` false — the gate rows then
   // start from 4 x 256 zeros kept behind the P parameters, like the bias-less MLP layers; the chain's MLP keeps its own)
   // (or a chain whose second module is one Linear, `linear_tail`: at every shape, 5 -> 128 included, and never a twin)
+  // (or a chain of more than two outputs, rl_rnn_chain_create: the tile kernels and the twin stay two-action)
   bool lane_kernels() const {
-    return rnn_layers > 1 || in_dim > 5 || gru_hidden > 128 || hidden > 128 || !has_bias || linear_tail();
+    return rnn_layers > 1 || in_dim > 5 || gru_hidden > 128 || hidden > 128 || !has_bias || linear_tail() || out_dim > 2;
   }
   // ChainConfig<GruConfig | LstmConfig, LinearConfig> (modules/chain.rs:12-54): the recurrent layers -> ReLU -> one
   // Linear(gru_hidden, out_dim).  Marked by `hidden` == 0 on a recurrent kind (the MLP-tail chains have hidden >= 1);

@@ -340,14 +340,32 @@ struct RnnBaseConfig {
 using GruConfig = RnnBaseConfig;
 using LstmConfig = RnnBaseConfig;
 
+// More than two outputs (a categorical policy over IndexSpace::new(3..8)): the one constructor that builds them,
+// rl_rnn_chain_create — the two-action constructors below stay what they are for out_dim <= 2.  mlp_hidden 0: a Linear tail.
+inline int32_t rnn_chain_create_multi(Engine &eng, int32_t cell, const RnnBaseConfig &first, uint32_t hidden_dim,
+                                      uint32_t mlp_hidden, uint32_t in_dim, uint32_t out_dim, rl_mlp **h) {
+  rl_rnn_chain_config cfg;
+  cfg.cell = cell;
+  cfg.in_dim = in_dim;
+  cfg.hidden = hidden_dim;
+  cfg.num_layers = first.num_layers;
+  cfg.rnn_bias = first.bias_init ? 1 : 0;
+  cfg.mlp_hidden = mlp_hidden;
+  cfg.out_dim = out_dim;
+  return rl_rnn_chain_create(eng.handle(), &cfg, h);
+}
+
 struct GruMlpConfig {  // ChainConfig<GruConfig, MlpConfig>::default (modules/mod.rs:14, chain.rs:19-32)
   GruConfig first_config;
   uint32_t hidden_dim = 128;
   MlpConfig second_config;
   std::unique_ptr<Module> build_module(Engine &eng, uint32_t in_dim, uint32_t out_dim, uint64_t seed) const {
     rl_mlp *h = nullptr;
-    check(rl_rnn_mlp_create_config(eng.handle(), RL_CELL_GRU, in_dim, hidden_dim, first_config.num_layers,
-                                   first_config.bias_init ? 1 : 0, second_config.single_hidden_size(), out_dim, &h),
+    check(out_dim > 2 ? rnn_chain_create_multi(eng, RL_CELL_GRU, first_config, hidden_dim,
+                                               second_config.single_hidden_size(), in_dim, out_dim, &h)
+                      : rl_rnn_mlp_create_config(eng.handle(), RL_CELL_GRU, in_dim, hidden_dim, first_config.num_layers,
+                                                 first_config.bias_init ? 1 : 0, second_config.single_hidden_size(),
+                                                 out_dim, &h),
           eng.handle());
     std::unique_ptr<Module> m(new Module(eng, h));
     const LinearConfig &lc = second_config.linear_config;
@@ -372,8 +390,11 @@ struct ChainLstmMlpConfig {
   MlpConfig second_config;
   std::unique_ptr<Module> build_module(Engine &eng, uint32_t in_dim, uint32_t out_dim, uint64_t seed) const {
     rl_mlp *h = nullptr;
-    check(rl_rnn_mlp_create_config(eng.handle(), RL_CELL_LSTM, in_dim, hidden_dim, first_config.num_layers,
-                                   first_config.bias_init ? 1 : 0, second_config.single_hidden_size(), out_dim, &h),
+    check(out_dim > 2 ? rnn_chain_create_multi(eng, RL_CELL_LSTM, first_config, hidden_dim,
+                                               second_config.single_hidden_size(), in_dim, out_dim, &h)
+                      : rl_rnn_mlp_create_config(eng.handle(), RL_CELL_LSTM, in_dim, hidden_dim, first_config.num_layers,
+                                                 first_config.bias_init ? 1 : 0, second_config.single_hidden_size(),
+                                                 out_dim, &h),
           eng.handle());
     std::unique_ptr<Module> m(new Module(eng, h));
     const LinearConfig &lc = second_config.linear_config;
@@ -401,8 +422,9 @@ struct GruLinearConfig {
     if (!second.bias_init)
       throw BuildAgentError(RL_ERR_BUILD_AGENT, "a recurrent chain's Linear tail is built with a bias vector");
     rl_mlp *h = nullptr;
-    check(rl_rnn_linear_create(eng.handle(), cell, in_dim, hidden_dim, first.num_layers, first.bias_init ? 1 : 0,
-                               out_dim, &h),
+    check(out_dim > 2 ? rnn_chain_create_multi(eng, cell, first, hidden_dim, 0, in_dim, out_dim, &h)
+                      : rl_rnn_linear_create(eng.handle(), cell, in_dim, hidden_dim, first.num_layers,
+                                             first.bias_init ? 1 : 0, out_dim, &h),
           eng.handle());
     std::unique_ptr<Module> m(new Module(eng, h));
     check(rl_rnn_mlp_init_with(h, seed, &first.input_weights_init.raw, &first.hidden_weights_init.raw,

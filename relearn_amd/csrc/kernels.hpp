@@ -191,7 +191,7 @@ void launch_seq_gae(rl_traj *traj, float gamma, float lambda, const float *v_las
 // one-step TD targets from traj->seq.out / succ (plane 0) -> d.tgt
 void launch_seq_value_targets(rl_traj *traj, float gamma, const float *v_last);
 void launch_seq_policy_dlogits(rl_traj *traj, int mode, uint64_t B_total, float clip_lo, float clip_hi,
-                               const int32_t *d_skip = nullptr);
+                               const int32_t *d_skip = nullptr, uint32_t n_out = 2);  // n_out: logit planes (2..8)
 void launch_seq_critic_dvalues(rl_traj *traj, uint64_t B_total);
 void launch_gru_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip = nullptr);  // dz, seq.act -> vec[0..P)
 // Fisher-vector product pieces: static tangent terms (dpre, seq.succ) from the tangent parameters, then the recurrent

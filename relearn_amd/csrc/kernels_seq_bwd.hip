@@ -3,6 +3,7 @@
 // seq_common.hpp; the forward that fills the activation record: kernels_seq.hip.  The head's f32 backward (d u_pre, then
 // W1^T d u_pre) is written once (head_du16, head_w1t16): k_gru_bptt runs it inside its step, k_seq_head_backward over all
 // blocks ahead of k_lstm_bptt.
+#include "policy_terms.hpp"
 #include "seq_common.hpp"
 
 // =====================================================================================================
@@ -69,6 +70,36 @@ __global__ void __launch_bounds__(256) k_seq_policy_dlogits(TrajDev tr, const fl
     }
     dz[b] = c * ((act == 0 ? 1.0f : 0.0f) - pa0);
     dz[B + b] = c * ((act == 1 ? 1.0f : 0.0f) - pa1);
+  }
+  const double t0 = block_sum<256>(s0, red), t1 = block_sum<256>(s1, red), t2 = block_sum<256>(s2, red);
+  if (threadIdx.x == 0) {
+    slabB[blockIdx.x * 4 + 0] = t0;
+    slabB[blockIdx.x * 4 + 1] = t1;
+    slabB[blockIdx.x * 4 + 2] = t2;
+    slabB[blockIdx.x * 4 + 3] = 0.0;
+  }
+}
+
+// The same three passes over the A logit planes [A][T][n] of a chain of more than two outputs (rl_rnn_chain_create):
+// the per-sample rules are policy_terms.hpp's, the ones the feed-forward k-action path runs (log-softmax, entropy and KL
+// summed in ascending action order with the clamps above, the PPO sub-gradient rule, dz[q] = c ((act == q) - p_q)).
+template <int MODE, int A>
+__global__ void __launch_bounds__(256) k_seq_policy_dlogits_n(TrajDev tr, const float *__restrict__ logits,
+                                                              float *__restrict__ lp0, float *__restrict__ dz,
+                                                              double *__restrict__ slabB, float inv_B, float clip_lo,
+                                                              float clip_hi, const int32_t *__restrict__ skip) {
+  __shared__ double red[256];
+  if (skip != nullptr && *skip != 0) return;
+  const size_t B = (size_t)tr.T * tr.n;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (size_t b = (size_t)blockIdx.x * 256 + threadIdx.x; b < B; b += (size_t)gridDim.x * 256) {
+    float z[A], none[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+      z[q] = logits[(size_t)q * B + b];
+      none[q] = 0.0f;
+    }
+    policy_sample_terms<MODE>(z, none, (int)tr.action[b], tr.adv[b], b, B, lp0, dz, inv_B, clip_lo, clip_hi, s0, s1, s2);
   }
   const double t0 = block_sum<256>(s0, red), t1 = block_sum<256>(s1, red), t2 = block_sum<256>(s2, red);
   if (threadIdx.x == 0) {
@@ -665,10 +696,35 @@ __global__ void __launch_bounds__(1024) k_seq_reduce(SeqReduceSegs segs, uint32_
 }
 
 void launch_seq_policy_dlogits(rl_traj *traj, int mode, uint64_t B_total, float clip_lo, float clip_hi,
-                               const int32_t *d_skip) {
+                               const int32_t *d_skip, uint32_t n_out) {
   ProfScope ps(traj->eng, RL_K_POLICY_PASS);
   float inv_B = 1.0f / (float)B_total;
   dim3 g(traj->nbB), b(256);
+  if (n_out > 2) {  // (lp0 / dz hold n_out planes: stack_ensure)
+    RL_REQUIRE(traj->act_planes >= n_out, "the trajectory's action planes are narrower than the policy");
+#define DLN(MM, AA)                                                                                                  \
+  hipLaunchKernelGGL((k_seq_policy_dlogits_n<MM, AA>), g, b, 0, traj->eng->stream, traj->d, traj->seq.out, traj->lp0, \
+                     traj->dz, traj->slabB, inv_B, clip_lo, clip_hi, d_skip)
+#define DLN_A(AA)                                     \
+  case AA:                                            \
+    if (mode == PASS_INIT) DLN(PASS_INIT, AA);        \
+    else if (mode == PASS_EVAL) DLN(PASS_EVAL, AA);   \
+    else DLN(PASS_PPO, AA);                           \
+    break
+    switch (n_out) {
+      DLN_A(3);
+      DLN_A(4);
+      DLN_A(5);
+      DLN_A(6);
+      DLN_A(7);
+      DLN_A(8);
+      default: throw RlError(RL_ERR_UNSUPPORTED, "recurrent policy pass: categorical policies over 2..8 actions are built");
+    }
+#undef DLN_A
+#undef DLN
+    RL_HIP_CHECK(hipGetLastError());
+    return;
+  }
 #define DL(MM)                                                                                                     \
   hipLaunchKernelGGL(k_seq_policy_dlogits<MM>, g, b, 0, traj->eng->stream, traj->d, traj->seq.out, traj->lp0, traj->dz, \
                      traj->slabB, inv_B, clip_lo, clip_hi, d_skip)

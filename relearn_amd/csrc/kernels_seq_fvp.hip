@@ -273,6 +273,28 @@ __global__ void __launch_bounds__(256) k_seq_fvp_dlogits(TrajDev tr, const float
   }
 }
 
+// ... over the A planes of a chain of more than two outputs: dz[q] = p_q (d_q - sum_r p_r d_r) / B, the inner sum an
+// ascending fma chain from 0
+template <int A>
+__global__ void __launch_bounds__(256) k_seq_fvp_dlogits_n(TrajDev tr, const float *__restrict__ out_dot,
+                                                           const float *__restrict__ lp0, float *__restrict__ dz,
+                                                           float inv_B, const int32_t *__restrict__ skip) {
+  if (skip != nullptr && *skip != 0) return;
+  const size_t B = (size_t)tr.T * tr.n;
+  for (size_t b = (size_t)blockIdx.x * 256 + threadIdx.x; b < B; b += (size_t)gridDim.x * 256) {
+    float p[A], d[A];
+    float pdz = 0.0f;
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+      p[q] = rl_expf(lp0[(size_t)q * B + b]);
+      d[q] = out_dot[(size_t)q * B + b];
+      pdz = __builtin_fmaf(p[q], d[q], pdz);
+    }
+#pragma unroll
+    for (int q = 0; q < A; ++q) dz[(size_t)q * B + b] = p[q] * (d[q] - pdz) * inv_B;
+  }
+}
+
 // static terms over all blocks (-> seq.dpre, seq.succ), then the recurrence per tile (-> seq.out)
 template <class Cell>
 static void launch_seq_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent, const int32_t *d_skip) {
@@ -288,7 +310,9 @@ void launch_gru_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent
                         const int32_t *d_skip) {
   rl_engine *e = traj->eng;
   const SeqDev &q = traj->seq;
-  RL_REQUIRE(mod->out_dim == 2, "Fisher-vector products are for 2-action policies");
+  // (the tile kernels are two-action; a lane-kernel module may have up to eight outputs, rl_rnn_chain_create)
+  RL_REQUIRE(mod->out_dim == 2 || (mod->lane_kernels() && mod->out_dim > 2 && mod->out_dim <= RL_MLP_MAX_OUT),
+             "Fisher-vector products are for policies of two actions (lane-per-thread kernels: 2..8)");
   if (mod->lane_kernels()) launch_stack_tangent(traj, mod, d_tangent, d_skip);  // -> seq.out
   else {
     ProfScope ps(e, RL_K_POLICY_FUSED);
@@ -297,7 +321,24 @@ void launch_gru_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent
   }
   {
     ProfScope ps(e, RL_K_POLICY_PASS);
-    hipLaunchKernelGGL(k_seq_fvp_dlogits, dim3(traj->nbB), dim3(256), 0, e->stream, traj->d, q.out, traj->lp0,
-                       traj->dz, 1.0f / (float)B_total, d_skip);
+#define FVN(AA)                                                                                                     \
+  case AA:                                                                                                          \
+    hipLaunchKernelGGL(k_seq_fvp_dlogits_n<AA>, dim3(traj->nbB), dim3(256), 0, e->stream, traj->d, q.out, traj->lp0, \
+                       traj->dz, 1.0f / (float)B_total, d_skip);                                                    \
+    break
+    switch (mod->out_dim) {
+      case 2:
+        hipLaunchKernelGGL(k_seq_fvp_dlogits, dim3(traj->nbB), dim3(256), 0, e->stream, traj->d, q.out, traj->lp0,
+                           traj->dz, 1.0f / (float)B_total, d_skip);
+        break;
+      FVN(3);
+      FVN(4);
+      FVN(5);
+      FVN(6);
+      FVN(7);
+      FVN(8);
+      default: throw RlError(RL_ERR_UNSUPPORTED, "Fisher-vector products: 2..8 actions");
+    }
+#undef FVN
   }
 }

@@ -5,7 +5,9 @@
 // dropout.  Every layer's state is zero at t = 0 and after a step whose flag ends the episode.  The chain's second
 // module is a compile-time parameter of every kernel (LIN): the Mlp([h]) above, or one Linear(H, A) on relu(top)
 // (ChainConfig<_, LinearConfig>, modules/chain.rs:12-54; flat order [.., kernel [A][H], bias [A]]): no hidden units,
-// so no `u` / `ur` / `du` planes and one barrier less per step.
+// so no `u` / `ur` / `du` planes and one barrier less per step.  So is the head's output-count class (NQ): 2 for the
+// chains of one or two outputs, 4 or 8 for the chains of rl_rnn_chain_create over IndexSpace::new(3..8), whose outputs
+// are computed in passes of four rows (head_passes).
 //
 // The single-layer chains have fused tile kernels (kernels_seq*.hip, built for 5 -> 128 -> 128); this is the general
 // path for the stacked ones, at the module's own widths: ONE THREAD PER LANE, 64 lanes per workgroup, and the unit loop
@@ -163,6 +165,43 @@ __device__ __forceinline__ void tdot(float (&acc)[N], const float *__restrict__ 
   else tdot_n<N, false>(acc, W, ld, k0, K - 1, R, d_at);
 }
 
+// The head's outputs of a module with more than two of them (rl_rnn_chain_create, out_dim 3..8), NQ registers of a
+// thread (4 or 8): passes of UQ output rows, every output the contract's chain — acc = bias[q]; acc = fma(x_k, w[q][k],
+// acc), k ascending — from `bias_at(q)` through `dots(acc, rows)`, which runs one dot_rows per matrix of the sum.  Rows
+// past A repeat row A - 1 (never stored); a pass wholly past A is skipped (A is wave-uniform).
+template <int NQ, class BF, class DF>
+__device__ __forceinline__ void head_passes(float (&out)[NQ], int A, BF bias_at, DF dots) {
+  static_assert(NQ % UQ == 0, "whole passes");
+#pragma unroll
+  for (int q0 = 0; q0 < NQ; q0 += UQ) {
+    float acc[UQ] = {};
+    if (q0 < A) {
+      int qq[UQ];
+#pragma unroll
+      for (int u = 0; u < UQ; ++u) {
+        qq[u] = q0 + u < A ? q0 + u : A - 1;
+        acc[u] = bias_at(qq[u]);
+      }
+      dots(acc, qq);
+    }
+#pragma unroll
+    for (int u = 0; u < UQ; ++u) out[q0 + u] = acc[u];
+  }
+}
+// dst[q][b] = o[q] (or 0 where `take` is false) for the module's A outputs, planes `stride` apart.  NQ > 2: the
+// register array is indexed by the unrolled loop only (a run-time index would put it in scratch).
+template <int NQ>
+__device__ __forceinline__ void store_outputs(float *__restrict__ dst, size_t stride, size_t b, const float (&o)[NQ],
+                                              int A, bool take) {
+  if constexpr (NQ == 2) {
+    for (int q = 0; q < A; ++q) dst[(size_t)q * stride + b] = take ? o[q] : 0.0f;
+  } else {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+      if (q < A) dst[(size_t)q * stride + b] = take ? o[q] : 0.0f;
+  }
+}
+
 // layer l of one step: in[k * in_stride + lane] (K inputs), states (h, c) -> (hn, cn); `fresh`: the lane's state is zero
 template <int CELL, bool REC, bool CW = false>
 __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &ws, int l, const float *__restrict__ in,
@@ -251,9 +290,10 @@ __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &w
 
 // Chain's ReLU and the Mlp on the top layer's output `top` ([H][n]); out[q] in every thread.  One barrier inside.
 // LIN: Chain's ReLU and one Linear — out[q] = bias[q] + sum_k relu(top[k]) kernel[q][k], no barrier.
-template <bool REC, bool CW = false, bool LIN = false>
+// NQ: the output-count class — 2 for the chains of one or two outputs, 4 or 8 for more (head_passes).
+template <bool REC, bool CW = false, bool LIN = false, int NQ = 2>
 __device__ __forceinline__ void stack_head(const StackNet &net, const StackWs &ws, const float *__restrict__ top,
-                                           const LaneCtx &lc, size_t b, float (&out)[2]) {
+                                           const LaneCtx &lc, size_t b, float (&out)[NQ]) {
   const int H = net.H, H2 = net.H2, A = net.A;
   const size_t n = ws.n;
   if (LIN) {
@@ -264,13 +304,19 @@ __device__ __forceinline__ void stack_head(const StackNet &net, const StackWs &w
         const float tv = top[(size_t)k * n + lc.ii];
         ws.a1[(size_t)k * ws.B + b] = tv > 0.0f ? tv : 0.0f;
       }
-    const int qq[2] = {0, A > 1 ? 1 : 0};
-    out[0] = bk[qq[0]];
-    out[1] = bk[qq[1]];
-    dot_rows(out, Wk, qq, H, [&](int k) {
+    auto relu_top = [&](int k) {
       const float tv = top[(size_t)k * n + lc.ii];
       return tv > 0.0f ? tv : 0.0f;
-    });
+    };
+    if constexpr (NQ == 2) {
+      const int qq[2] = {0, A > 1 ? 1 : 0};
+      out[0] = bk[qq[0]];
+      out[1] = bk[qq[1]];
+      dot_rows(out, Wk, qq, H, relu_top);
+    } else {
+      head_passes(out, A, [&](int q) { return bk[q]; },
+                  [&](float (&acc)[UQ], const int (&qq)[UQ]) { dot_rows(acc, Wk, qq, H, relu_top); });
+    }
     return;
   }
   const float *__restrict__ W1_p = net.p + net.off[net.L], *__restrict__ b1_p = W1_p + (size_t)H2 * H;
@@ -302,17 +348,23 @@ __device__ __forceinline__ void stack_head(const StackNet &net, const StackWs &w
       ws.a1[(size_t)k * ws.B + b] = tv > 0.0f ? tv : 0.0f;
     }
   __syncthreads();
-  const int qq[2] = {0, A > 1 ? 1 : 0};
-  out[0] = b2[qq[0]];
-  out[1] = b2[qq[1]];
-  dot_rows(out, W2, qq, H2, [&](int j) { return ws.u[(size_t)j * n + lc.ii]; });
+  auto unit = [&](int j) { return ws.u[(size_t)j * n + lc.ii]; };
+  if constexpr (NQ == 2) {
+    const int qq[2] = {0, A > 1 ? 1 : 0};
+    out[0] = b2[qq[0]];
+    out[1] = b2[qq[1]];
+    dot_rows(out, W2, qq, H2, unit);
+  } else {
+    head_passes(out, A, [&](int q) { return b2[q]; },
+                [&](float (&acc)[UQ], const int (&qq)[UQ]) { dot_rows(acc, W2, qq, H2, unit); });
+  }
 }
 
 // all layers + head of one step: states of set `cur` (zero where `fresh`) -> set `nxt`
-template <int CELL, bool REC, bool CW = false, bool LIN = false>
+template <int CELL, bool REC, bool CW = false, bool LIN = false, int NQ = 2>
 __device__ __forceinline__ void stack_module_step(const StackNet &net, const StackWs &ws, const float *__restrict__ x,
                                                   size_t x_stride, int cur, int nxt, bool fresh, const LaneCtx &lc,
-                                                  size_t b, float (&out)[2]) {
+                                                  size_t b, float (&out)[NQ]) {
   for (int l = 0; l < net.L; ++l) {
     const float *in = l == 0 ? x : slot(ws, net, nxt, 0, l - 1);
     stack_cell<CELL, REC, CW>(net, ws, l, in, l == 0 ? x_stride : (size_t)ws.n, slot(ws, net, cur, 0, l),
@@ -320,11 +372,11 @@ __device__ __forceinline__ void stack_module_step(const StackNet &net, const Sta
                               b);
     __syncthreads();
   }
-  stack_head<REC, CW, LIN>(net, ws, slot(ws, net, nxt, 0, net.L - 1), lc, b, out);
+  stack_head<REC, CW, LIN, NQ>(net, ws, slot(ws, net, nxt, 0, net.L - 1), lc, b, out);
 }
 
 // teacher-forced forward: out / succ [A][T][n] (succ may be NULL), the contract of launch_gru_seq_forward
-template <int CELL, bool REC, bool LIN = false>
+template <int CELL, bool REC, bool LIN = false, int NQ = 2>
 __global__ void __launch_bounds__(SL *SW) k_stack_forward(StackNet net, StackWs ws, TrajDev tr, float *__restrict__ out,
                                                           float *__restrict__ succ, const int32_t *__restrict__ skip) {
   if (skip != nullptr && *skip != 0) return;
@@ -334,24 +386,22 @@ __global__ void __launch_bounds__(SL *SW) k_stack_forward(StackNet net, StackWs 
   int cur = SET_A;
   for (size_t t = 0; t < T; ++t) {
     const size_t b = t * n + lc.ii;
-    float o[2];
-    stack_module_step<CELL, REC, false, LIN>(net, ws, tr.obs + t * n, plane, cur, cur ^ 1, fresh, lc, b, o);
+    float o[NQ];
+    stack_module_step<CELL, REC, false, LIN, NQ>(net, ws, tr.obs + t * n, plane, cur, cur ^ 1, fresh, lc, b, o);
     const uint8_t f = tr.flag[b];
-    if (lc.live && lc.wave == 0)
-      for (int q = 0; q < net.A; ++q) out[(size_t)q * B + b] = o[q];
+    if (lc.live && lc.wave == 0) store_outputs(out, B, b, o, net.A, true);
     if (succ != nullptr) {
       const bool need = f == RL_SUCC_INTERRUPT || (f == RL_SUCC_CONTINUE && t == T - 1);
-      float o2[2] = {0.0f, 0.0f};
+      float o2[NQ] = {};
       if (__syncthreads_or(need && lc.live ? 1 : 0)) {
         // the successor observation (the interrupted step's, or obs[T] at the horizon) evaluated from the states after
         // step t, which are not advanced: the results go to the third state set.  Per-lane plane stride: term_obs planes
         // are T * n apart, obs planes (T + 1) * n.
         const bool intr = f == RL_SUCC_INTERRUPT;
-        stack_module_step<CELL, false, false, LIN>(net, ws, intr ? tr.term_obs + t * n : tr.obs + T * n,
-                                                   intr ? B : plane, cur ^ 1, SET_PEEK, false, lc, b, o2);
+        stack_module_step<CELL, false, false, LIN, NQ>(net, ws, intr ? tr.term_obs + t * n : tr.obs + T * n,
+                                                       intr ? B : plane, cur ^ 1, SET_PEEK, false, lc, b, o2);
       }
-      if (lc.live && lc.wave == 0)
-        for (int q = 0; q < net.A; ++q) succ[(size_t)q * B + b] = need ? o2[q] : 0.0f;
+      if (lc.live && lc.wave == 0) store_outputs(succ, B, b, o2, net.A, need);
     }
     fresh = f != RL_SUCC_CONTINUE;
     cur ^= 1;
@@ -360,16 +410,20 @@ __global__ void __launch_bounds__(SL *SW) k_stack_forward(StackNet net, StackWs 
 
 // one rollout step: env observation buffer obs [D][n] -> logits z [A][n]; the lane's states restart where the step
 // before ended its episode (flag_prev: that step's successor codes) or at the first step of a collection
-template <int CELL, bool LIN = false>
+template <int CELL, bool LIN = false, int NQ = 2>
 __global__ void __launch_bounds__(SL *SW) k_stack_step(StackNet net, StackWs ws, const float *__restrict__ obs,
                                                        const uint8_t *__restrict__ flag_prev, int first, int parity,
                                                        float *__restrict__ z) {
   const LaneCtx lc = lane_ctx(ws.n);
   const bool fresh = first != 0 || flag_prev[lc.ii] != RL_SUCC_CONTINUE;
-  float o[2];
-  stack_module_step<CELL, false, false, LIN>(net, ws, obs, (size_t)ws.n, parity, parity ^ 1, fresh, lc, 0, o);
-  if (lc.live && lc.wave == 0)
-    for (int q = 0; q < net.A; ++q) z[(size_t)q * ws.n + lc.ii] = o[q];
+  float o[NQ];
+  stack_module_step<CELL, false, false, LIN, NQ>(net, ws, obs, (size_t)ws.n, parity, parity ^ 1, fresh, lc, 0, o);
+  if constexpr (NQ == 2) {
+    if (lc.live && lc.wave == 0)
+      for (int q = 0; q < net.A; ++q) z[(size_t)q * ws.n + lc.ii] = o[q];
+  } else {
+    if (lc.live && lc.wave == 0) store_outputs(z, (size_t)ws.n, (size_t)lc.ii, o, net.A, true);
+  }
 }
 
 // All T steps of a rollout in one launch: what launch_rollout_stepwise's five launches per step (record the observation,
@@ -377,14 +431,15 @@ __global__ void __launch_bounds__(SL *SW) k_stack_step(StackNet net, StackWs ws,
 // its 64 lanes for the whole horizon and nothing crosses workgroups, so a step needs barriers only.  Per step: the
 // module reads the observation from the trajectory's planes (slot t, written by wave 0 one step earlier — plane stride
 // (T + 1) n as in k_stack_forward); the lane's wave-0 thread draws the action from word t_global + t of the lane's actor
-// stream with k_gen_sample_actions<2>'s code, steps the lane (lane_step, TrajSink) and writes the features of the next
+// stream with k_gen_sample_actions<NA>'s code (NA: the env's action count = the module's outputs), steps the lane (lane_step, TrajSink) and writes the features of the next
 // observation into slot t + 1 (slot T after the last step); a barrier publishes them and the successor codes, from
 // which every thread of the lane learns whether the states restart (k_stack_step's flag_prev).  Lane state lives in wave
 // 0's registers from the first step to the last.
-template <int CELL, class Env, int D, bool LIN = false>
+template <int CELL, class Env, int D, bool LIN = false, int NA = 2>
 __global__ void __launch_bounds__(SL *SW) k_stack_rollout(StackNet net, StackWs ws, CartPoleDev c, EnvStateDev st,
                                                           TrajDev tr, uint64_t t_global) {
   __shared__ uint8_t succ_of[SL];
+  constexpr int NQ = NA <= 2 ? 2 : ((NA + UQ - 1) / UQ) * UQ;
   const LaneCtx lc = lane_ctx(tr.n);
   const size_t n = tr.n, T = tr.T, plane = (T + 1) * n;
   const bool actor = lc.wave == 0, writer = lc.live && actor;
@@ -403,13 +458,20 @@ __global__ void __launch_bounds__(SL *SW) k_stack_rollout(StackNet net, StackWs 
   bool fresh = true;
   int cur = SET_A;
   for (size_t t = 0; t < T; ++t) {
-    float o[2];
-    stack_module_step<CELL, false, true, LIN>(net, ws, tr.obs + t * n, plane, cur, cur ^ 1, fresh, lc, 0, o);
+    float o[NQ];
+    stack_module_step<CELL, false, true, LIN, NQ>(net, ws, tr.obs + t * n, plane, cur, cur ^ 1, fresh, lc, 0, o);
     if (actor) {
       const float u = rl_u32_to_unit_f32(stream_word(c.key_actor, glane, t_global + t));
-      float lp[2];
-      log_softmax_lane<2>(o, lp);
-      const int a = categorical_sample_lane<2>(lp, u);
+      float lp[NA];
+      if constexpr (NA == 2) {
+        log_softmax_lane<2>(o, lp);
+      } else {
+        float zz[NA];
+#pragma unroll
+        for (int q = 0; q < NA; ++q) zz[q] = o[q];
+        log_softmax_lane<NA>(zz, lp);
+      }
+      const int a = categorical_sample_lane<NA>(lp, u);
       TrajSink sink{tr, t * n + lc.ii, writer};
       float f[D];
       const int succ = lane_step<Env, D>(c, s, a, glane, t_global + t, sink, f);
@@ -543,7 +605,7 @@ __global__ void __launch_bounds__(SL *SW) k_stack_backward(StackNet net, StackWs
 // Forward-mode derivative along the tangent `tv` (same layout as the parameters) through the recorded activations:
 // out_dot [A][T][n].  With p = a gate's pre-activation: p_dot = V_ih x + v_bih + W_ih x_dot + V_hh h + v_bhh + W_hh h_dot.
 // LIN: out_dot[q] = v_bias[q] + sum_k (v_kernel[q][k] a1[k] + kernel[q][k] [top[k] > 0] top_dot[k]).
-template <int CELL, bool LIN = false>
+template <int CELL, bool LIN = false, int NQ = 2>
 __global__ void __launch_bounds__(SL *SW) k_stack_tangent(StackNet net, StackNet tv, StackWs ws, TrajDev tr,
                                                           float *__restrict__ out_dot,
                                                           const int32_t *__restrict__ skip) {
@@ -634,13 +696,23 @@ __global__ void __launch_bounds__(SL *SW) k_stack_tangent(StackNet net, StackNet
         const float *__restrict__ top = rec_plane(ws, net, L - 1, RP_HOUT);
         const float *__restrict__ topd = slot(ws, net, nxt, 0, L - 1);
         const float *__restrict__ vbk = V1 + (size_t)A * H;  // (W1 / V1: the Linear's kernel [A][H] and its tangent)
-        const int qq[2] = {0, A > 1 ? 1 : 0};
-        float od[2] = {vbk[qq[0]], vbk[qq[1]]};
-        dot_rows(od, V1, qq, H, [&](int k) { return ws.a1[(size_t)k * B + b]; });
-        dot_rows(od, W1, qq, H,
-                 [&](int k) { return top[(size_t)k * B + b] > 0.0f ? topd[(size_t)k * n + lc.ii] : 0.0f; });
-        if (lc.live)
-          for (int q = 0; q < A; ++q) out_dot[(size_t)q * B + b] = od[q];
+        if constexpr (NQ == 2) {
+          const int qq[2] = {0, A > 1 ? 1 : 0};
+          float od[2] = {vbk[qq[0]], vbk[qq[1]]};
+          dot_rows(od, V1, qq, H, [&](int k) { return ws.a1[(size_t)k * B + b]; });
+          dot_rows(od, W1, qq, H,
+                   [&](int k) { return top[(size_t)k * B + b] > 0.0f ? topd[(size_t)k * n + lc.ii] : 0.0f; });
+          if (lc.live)
+            for (int q = 0; q < A; ++q) out_dot[(size_t)q * B + b] = od[q];
+        } else {
+          float od[NQ];
+          head_passes(od, A, [&](int q) { return vbk[q]; }, [&](float (&acc)[UQ], const int (&qq)[UQ]) {
+            dot_rows(acc, V1, qq, H, [&](int k) { return ws.a1[(size_t)k * B + b]; });
+            dot_rows(acc, W1, qq, H,
+                     [&](int k) { return top[(size_t)k * B + b] > 0.0f ? topd[(size_t)k * n + lc.ii] : 0.0f; });
+          });
+          if (lc.live) store_outputs(out_dot, B, b, od, A, true);
+        }
       }
       fresh = tr.flag[b] != RL_SUCC_CONTINUE;
       cur = nxt;
@@ -668,12 +740,21 @@ __global__ void __launch_bounds__(SL *SW) k_stack_tangent(StackNet net, StackNet
     }
     __syncthreads();
     if (lc.wave == 0) {
-      const int qq[2] = {0, A > 1 ? 1 : 0};
-      float od[2] = {vb2[qq[0]], vb2[qq[1]]};
-      dot_rows(od, V2, qq, H2, [&](int j) { return ws.ur[(size_t)j * B + b]; });
-      dot_rows(od, W2, qq, H2, [&](int j) { return ws.u[(size_t)j * n + lc.ii]; });
-      if (lc.live)
-        for (int q = 0; q < A; ++q) out_dot[(size_t)q * B + b] = od[q];
+      if constexpr (NQ == 2) {
+        const int qq[2] = {0, A > 1 ? 1 : 0};
+        float od[2] = {vb2[qq[0]], vb2[qq[1]]};
+        dot_rows(od, V2, qq, H2, [&](int j) { return ws.ur[(size_t)j * B + b]; });
+        dot_rows(od, W2, qq, H2, [&](int j) { return ws.u[(size_t)j * n + lc.ii]; });
+        if (lc.live)
+          for (int q = 0; q < A; ++q) out_dot[(size_t)q * B + b] = od[q];
+      } else {
+        float od[NQ];
+        head_passes(od, A, [&](int q) { return vb2[q]; }, [&](float (&acc)[UQ], const int (&qq)[UQ]) {
+          dot_rows(acc, V2, qq, H2, [&](int j) { return ws.ur[(size_t)j * B + b]; });
+          dot_rows(acc, W2, qq, H2, [&](int j) { return ws.u[(size_t)j * n + lc.ii]; });
+        });
+        if (lc.live) store_outputs(out_dot, B, b, od, A, true);
+      }
     }
     fresh = tr.flag[b] != RL_SUCC_CONTINUE;
     cur = nxt;
@@ -722,11 +803,18 @@ void stack_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
   const uint64_t n = t->d.n, T = t->d.T, B = T * n, L = mod->rnn_layers, H = mod->gru_hidden, H2 = mod->hidden;
   DevMem &mem = t->mem;
   seq_ensure_outputs(t);
+  // a module of more than two outputs (rl_rnn_chain_create): one plane per output, grown where such a module first
+  // meets the trajectory — the output planes, the rollout step's logits, and (training) lp0 / dz.  Grow-only: a
+  // two-output module that follows uses the first two planes' worth of the same arrays at its own stride.
+  const uint64_t A = mod->out_dim > 2 ? mod->out_dim : 2;
+  mem.ensure(q.out, A * B);
+  mem.ensure(q.succ, A * B);
   const bool lin = mod->linear_tail();  // no hidden units: no u / ur / du (a trajectory may serve both tails in turn)
   mem.ensure(k.st, 2 * N_SETS * L * H * n);
   if (!lin) mem.ensure(k.u, H2 * n);
-  if (k.z == nullptr) k.z = mem.alloc<float>(2 * n);
+  mem.ensure(k.z, A * n);
   if (!training) return;
+  traj_ensure_action_planes(t, (uint32_t)A);
   mem.ensure(k.din, H * n);
   mem.ensure(k.dst, 2 * L * H * n);
   mem.ensure(k.rec, L * RPN * H * B);
@@ -750,15 +838,19 @@ void launch_stack_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float 
   const StackNet net = stack_net(mod, mod->d_params);
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
-#define FWD(CELL, REC, LIN)                                                                                   \
-  hipLaunchKernelGGL((k_stack_forward<CELL, REC, LIN>), grid, blk, 0, traj->eng->stream, net, ws, traj->d, d_out, \
+#define FWD(CELL, REC, LIN, NQ)                                                                                       \
+  hipLaunchKernelGGL((k_stack_forward<CELL, REC, LIN, NQ>), grid, blk, 0, traj->eng->stream, net, ws, traj->d, d_out, \
                      d_succ, d_skip)
-#define FWD_TAIL(CELL, REC)        \
-  do {                             \
-    if (lin) FWD(CELL, REC, true); \
-    else FWD(CELL, REC, false);    \
+#define FWD_TAIL(CELL, REC)                   \
+  do {                                        \
+    if (wide) {                               \
+      if (lin) FWD(CELL, REC, true, 8);       \
+      else FWD(CELL, REC, false, 8);          \
+    } else if (lin) FWD(CELL, REC, true, 2);  \
+    else FWD(CELL, REC, false, 2);            \
   } while (0)
-  const bool lstm = mod->kind == RL_MODULE_LSTM_MLP, lin = mod->linear_tail();
+  // (`wide`: more than two outputs — the output-count class 8 of the head, stack_head)
+  const bool lstm = mod->kind == RL_MODULE_LSTM_MLP, lin = mod->linear_tail(), wide = mod->out_dim > 2;
   if (record) {
     if (lstm) FWD_TAIL(LSTM, true);
     else FWD_TAIL(GRU, true);
@@ -773,26 +865,34 @@ void launch_stack_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float 
 
 void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   ProfScope ps(env->eng, RL_K_ROLLOUT);
-  RL_REQUIRE(policy->out_dim == 2, "stacked recurrent rollouts: two-action policies");
+  RL_REQUIRE(policy->out_dim >= 2 && policy->out_dim == env->A, "recurrent rollouts: one output per action of the env");
   const StackNet net = stack_net(policy, policy->d_params);
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
   float *z = traj->seq.stack.z;
-  const bool lstm = policy->kind == RL_MODULE_LSTM_MLP, lin = policy->linear_tail();
+  const bool lstm = policy->kind == RL_MODULE_LSTM_MLP, lin = policy->linear_tail(), wide = policy->out_dim > 2;
   if (env->kind == RL_ENV_META_BANDIT && env->eng->kernel_variant != 1) {
-    // meta-bandit lanes: all T steps in one launch (kernel variant 1 keeps the launch sequence per step, below).  Two
-    // arms: the recurrent chains are built for two actions (rl_rollout), so the observation has six features.
-    RL_REQUIRE(env->D == 6, "fused recurrent rollout on meta-bandit lanes: built for two arms (six features)");
-#define ROLL(CELL, LIN)                                                                                           \
-  hipLaunchKernelGGL((k_stack_rollout<CELL, MetaOps, 6, LIN>), grid, blk, 0, env->eng->stream, net, ws, env->dev, \
+    // meta-bandit lanes: all T steps in one launch (kernel variant 1 keeps the launch sequence per step, below).  Two to
+    // four arms: k arms make k + 4 observation features (env_lanes.hpp, MetaOps).
+    RL_REQUIRE(env->A >= 2 && env->A <= 4 && env->D == env->A + 4,
+               "fused recurrent rollout on meta-bandit lanes: built for two to four arms (k + 4 features)");
+#define ROLL(CELL, LIN, DD, AA)                                                                                          \
+  hipLaunchKernelGGL((k_stack_rollout<CELL, MetaOps, DD, LIN, AA>), grid, blk, 0, env->eng->stream, net, ws, env->dev, \
                      env->st, traj->d, env->t_global)
+#define ROLL_ARMS(CELL, LIN)                     \
+  do {                                           \
+    if (env->A == 2) ROLL(CELL, LIN, 6, 2);      \
+    else if (env->A == 3) ROLL(CELL, LIN, 7, 3); \
+    else ROLL(CELL, LIN, 8, 4);                  \
+  } while (0)
     if (lstm) {
-      if (lin) ROLL(LSTM, true);
-      else ROLL(LSTM, false);
+      if (lin) ROLL_ARMS(LSTM, true);
+      else ROLL_ARMS(LSTM, false);
     } else {
-      if (lin) ROLL(GRU, true);
-      else ROLL(GRU, false);
+      if (lin) ROLL_ARMS(GRU, true);
+      else ROLL_ARMS(GRU, false);
     }
+#undef ROLL_ARMS
 #undef ROLL
     RL_HIP_CHECK(hipGetLastError());
     env->t_global += traj->d.T;
@@ -802,16 +902,22 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     const int first = step == 0 ? 1 : 0, parity = (int)(step & 1);
     // (the step before has been recorded by now: its successor codes are in the trajectory)
     const uint8_t *flag_prev = traj->d.flag + (size_t)(step == 0 ? 0 : step - 1) * traj->d.n;
-#define STEP(CELL, LIN)                                                                                     \
-  hipLaunchKernelGGL((k_stack_step<CELL, LIN>), grid, blk, 0, env->eng->stream, net, ws, env->d_obs, flag_prev, \
+#define STEP(CELL, LIN, NQ)                                                                                         \
+  hipLaunchKernelGGL((k_stack_step<CELL, LIN, NQ>), grid, blk, 0, env->eng->stream, net, ws, env->d_obs, flag_prev, \
                      first, parity, z)
+#define STEP_OUT(CELL, LIN)          \
+  do {                               \
+    if (wide) STEP(CELL, LIN, 8);    \
+    else STEP(CELL, LIN, 2);         \
+  } while (0)
     if (lstm) {
-      if (lin) STEP(LSTM, true);
-      else STEP(LSTM, false);
+      if (lin) STEP_OUT(LSTM, true);
+      else STEP_OUT(LSTM, false);
     } else {
-      if (lin) STEP(GRU, true);
-      else STEP(GRU, false);
+      if (lin) STEP_OUT(GRU, true);
+      else STEP_OUT(GRU, false);
     }
+#undef STEP_OUT
 #undef STEP
   });
 }
@@ -883,16 +989,22 @@ void launch_stack_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tange
   const StackNet net = stack_net(mod, mod->d_params), tv = stack_net(mod, d_tangent);
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
-#define TAN(CELL, LIN)                                                                                  \
-  hipLaunchKernelGGL((k_stack_tangent<CELL, LIN>), grid, blk, 0, traj->eng->stream, net, tv, ws, traj->d, \
+#define TAN(CELL, LIN, NQ)                                                                                  \
+  hipLaunchKernelGGL((k_stack_tangent<CELL, LIN, NQ>), grid, blk, 0, traj->eng->stream, net, tv, ws, traj->d, \
                      traj->seq.out, d_skip)
+#define TAN_OUT(CELL, LIN)                   \
+  do {                                       \
+    if (mod->out_dim > 2) TAN(CELL, LIN, 8); \
+    else TAN(CELL, LIN, 2);                  \
+  } while (0)
   if (mod->kind == RL_MODULE_LSTM_MLP) {
-    if (mod->linear_tail()) TAN(LSTM, true);
-    else TAN(LSTM, false);
+    if (mod->linear_tail()) TAN_OUT(LSTM, true);
+    else TAN_OUT(LSTM, false);
   } else {
-    if (mod->linear_tail()) TAN(GRU, true);
-    else TAN(GRU, false);
+    if (mod->linear_tail()) TAN_OUT(GRU, true);
+    else TAN_OUT(GRU, false);
   }
+#undef TAN_OUT
 #undef TAN
   RL_HIP_CHECK(hipGetLastError());
 }

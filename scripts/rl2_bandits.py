@@ -6,12 +6,13 @@ recurrent chain each, chosen by `model`:
             Linear(128, out), ra.GruLinear
     mlp     (the default) GRU(128) -> Relu -> Linear(128, 128) -> Relu -> Linear(128, out), ra.GruMlp: the chain with
             an MLP tail, one hidden layer more than the experiment's model
-Recurrent chains are built for two actions, so `arms` is 2.  Every lane collects whole
+`arms` is 2 (the default), 3 or 4: two arms build the two-action constructors' modules, three and four the same chains
+with one output per arm through ra.RnnChain (rl_rnn_chain_create).  Every lane collects whole
 trials per period (horizon = trials_per_lane * (2 * episodes - 1)); the mean trial reward of a period comes from the
 device-side StepsSummary (an episode of the summary is a trial).  Prints one JSON line per period.
 
     python scripts/rl2_bandits.py [lanes] [episodes] [periods] [trials_per_lane] [distribution] [hidden] \\
-        [critic_steps] [model]
+        [critic_steps] [model] [arms]
 """
 import json
 import os
@@ -25,19 +26,23 @@ arg = lambda i, d: type(d)(sys.argv[i]) if len(sys.argv) > i else d
 N, E, periods, trials = arg(1, 1024), arg(2, 10), arg(3, 20), arg(4, 2)
 dist, H, critic_steps = arg(5, "uniform_bernoulli"), arg(6, 128), arg(7, 50)
 model = arg(8, "mlp")
+arms = arg(9, 2)
 assert model in ("mlp", "linear"), "model: mlp | linear"
+assert arms in (2, 3, 4), "arms: 2 | 3 | 4"
 T = trials * (2 * E - 1)
 
 eng = ra.Engine(0)
-env = ra.MetaBanditEnv(eng, N, 2, E, dist, seed_env=0, seed_actor=1)
+env = ra.MetaBanditEnv(eng, N, arms, E, dist, seed_env=0, seed_actor=1)
 if model == "linear":
-    pol, cri = ra.GruLinear(eng, env.D, 2, H), ra.GruLinear(eng, env.D, 1, H)
+    pol = ra.GruLinear(eng, env.D, 2, H) if arms == 2 else ra.RnnChain(eng, "gru", env.D, H, arms)
+    cri = ra.GruLinear(eng, env.D, 1, H)
     glorot = ("Uniform", "FanAvg", 0.0)
     gru_config = (glorot, ("Orthogonal", "FanAvg", 0.0), ("Zeros", "FanAvg", 0.0))
     pol.init_with(2, *gru_config, glorot, glorot)  # the experiment's GruConfig, LinearConfig::default
     cri.init_with(3, *gru_config, glorot, glorot)
 else:
-    pol, cri = ra.GruMlp(eng, env.D, 2, H, H), ra.GruMlp(eng, env.D, 1, H, H)
+    pol = ra.GruMlp(eng, env.D, 2, H, H) if arms == 2 else ra.RnnChain(eng, "gru", env.D, H, arms, mlp_hidden=H)
+    cri = ra.GruMlp(eng, env.D, 1, H, H)
     pol.init(2)  # input weights Uniform(FanAvg), hidden weights Orthogonal, biases Zeros: the experiment's GruConfig
     cri.init(3)
 opt = ra.Adam(cri)
@@ -62,8 +67,9 @@ for period in range(periods):
     summary.clear()
     summary.push(traj)
     s = summary.read()
-    # ("model" only for `linear`: the default's lines stay what they were before the argument existed, byte for byte)
-    print(json.dumps({**({"model": model} if model == "linear" else {}),
+    # ("model" only for `linear`, "arms" only above two: the default's lines stay what they were before the arguments
+    # existed, byte for byte)
+    print(json.dumps({**({"model": model} if model == "linear" else {}), **({"arms": arms} if arms != 2 else {}),
                       "period": period, "lanes": N, "episodes_per_trial": E, "horizon": T, "distribution": dist,
                       "trials": s.episode_reward.count, "mean_trial_reward": s.episode_reward.mean,
                       "trial_reward_stddev": s.episode_reward.stddev(), "mean_step_reward": s.step_reward.mean,
