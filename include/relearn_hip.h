@@ -743,6 +743,29 @@ int32_t rl_dqn_config_default(rl_dqn_config *cfg);
  * not match the env's (obs_dim, n_actions) -> RL_ERR_INVALID_ARGUMENT; an env kind or feature count outside the table ->
  * RL_ERR_UNSUPPORTED with a message that names it.  No env is ever collected by another env's lane code. */
 int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out);
+/* DqnConfig<VB> over a sequence module (VB::Module: SeqPacked + SeqIterative, dqn.rs:75-86): `qnet` is a recurrent chain.
+ * The returned handle is an rl_dqn like rl_dqn_create's: every rl_dqn_* entry point and rl_summary_push_dqn take it.
+ *   actor    (dqn.rs:348-380) per lane and step: gen_bool(eps) first; an exploring step returns gen_range(0..2) BEFORE the
+ *            module's step() — the module does not see that observation and the lane's recurrent state (h, and c of an
+ *            LSTM, of every layer) stays exactly what it was; a greedy step advances the state and takes the first
+ *            maximal output.  The state is zero at an episode's first step (initial_state) and at the first step of every
+ *            rl_dqn_collect (the horizon rule records a cut episode as Interrupt: what follows is a new recorded episode).
+ *   update   (dqn.rs:263-337) seq_packed runs every sampled episode from the zero state over ALL its observations, the
+ *            explored ones included; loss = mse_loss(Q(s_t)[a_t], target_t, Mean) over the minibatch's sampled steps.
+ *            RL_DQN_TARGET_ONE_STEP_TD (critics/mod.rs:101-148): the module runs over the episode plus one slot — the
+ *            successor observation of an Interrupt, nothing (value 0) after a Terminate — and target_t = r_t + gamma *
+ *            amax(Q_ext[t + 1]), under no_grad with the parameters of that optimisation step.
+ * What builds: the env table of rl_dqn_create (CartPole 4 | 5 features, Chain 5 | 6, the two-armed bandit, MemoryGame(2, h)
+ * 4..8) with any recurrent chain of obs_dim inputs and 2 outputs — GRU or LSTM, Mlp or Linear tail, 1..4 layers, with or
+ * without recurrent bias vectors, from any of the recurrent constructors.  Collection is one launch per horizon on the
+ * lane-per-thread kernels at the module's own widths; RL_MB_TARGET holds the recurrent targets, rl_dqn_minibatch_gradient
+ * returns the gradient in the module's flat order.
+ * Refused, by this entry point's name: a feed-forward module -> RL_ERR_BUILD_AGENT (use rl_dqn_create); more than two
+ * actions -> RL_ERR_UNSUPPORTED; a module that does not match the env's (obs_dim, n_actions) -> RL_ERR_INVALID_ARGUMENT;
+ * RL_ENV_META_BANDIT lanes -> RL_ERR_UNSUPPORTED.  rl_dqn_update of such an agent on an engine with a communicator of
+ * more than one rank -> RL_ERR_UNSUPPORTED before anything is changed; rl_actor_to_cbor of a recurrent DqnActor ->
+ * RL_ERR_UNSUPPORTED. */
+int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out);
 int32_t rl_dqn_destroy(rl_dqn *dqn);
 /* ExplorationRateSchedule::exploration_rate(global_steps, mode) (schedules.rs:35-45); training = 0 -> 0.0 */
 int32_t rl_dqn_exploration_rate(const rl_dqn *dqn, int32_t training, double *rate_out);

@@ -64,7 +64,7 @@ ABI_SYMBOLS = [
     "rl_ppo_config_default", "rl_ppo_update", "rl_reinforce_update", "rl_reward_to_go",
     "rl_actor_to_cbor", "rl_module_from_cbor", "rl_tensor_def_to_cbor", "rl_tensor_def_from_cbor",
     "rl_indexed_type_space_to_cbor",
-    "rl_dqn_config_default", "rl_dqn_create", "rl_dqn_destroy", "rl_dqn_exploration_rate",
+    "rl_dqn_config_default", "rl_dqn_create", "rl_dqn_create_recurrent", "rl_dqn_destroy", "rl_dqn_exploration_rate",
     "rl_dqn_min_update_size", "rl_dqn_collect", "rl_dqn_update", "rl_dqn_replay_field_bytes", "rl_dqn_replay_read",
     "rl_dqn_minibatch_sample", "rl_dqn_minibatch_read", "rl_dqn_minibatch_gradient", "rl_dqn_agent_rng_pos",
     "rl_chain_tabular_q_train", "rl_chain_tabular_q_eval",
@@ -1030,10 +1030,12 @@ def dqn_config_default():
 class Dqn(_Handle):
     """`DqnConfig::build_agent` + the replay store of all lanes, resident in HBM (src/torch/agents/dqn.rs)."""
 
+    _create = "rl_dqn_create"  # the constructor entry point (RecurrentDqn: rl_dqn_create_recurrent)
+
     def __init__(self, env, qnet, opt, cfg):
         self.eng, self.env, self.qnet, self.opt, self.cfg = env.eng, env, qnet, opt, cfg
         self.h = C.c_void_p()
-        _check(lib().rl_dqn_create(env.h, qnet.h, opt.h, C.byref(cfg), C.byref(self.h)), env.eng.h)
+        _check(getattr(lib(), self._create)(env.h, qnet.h, opt.h, C.byref(cfg), C.byref(self.h)), env.eng.h)
         _register(self)
         self.n, self.D = env.n, env.D
         self.C = cfg.buffer_capacity
@@ -1112,6 +1114,13 @@ class Dqn(_Handle):
         p = C.c_uint64()
         _check(lib().rl_dqn_agent_rng_pos(self.h, C.byref(p)), self.eng.h)
         return p.value
+
+
+class RecurrentDqn(Dqn):
+    """`DqnConfig<VB>::build_agent` over a sequence module (dqn.rs:75-86): `qnet` is a recurrent chain (GruMlp, LstmMlp,
+    RnnMlp, RnnLinear, RnnChain of two outputs).  The interface of `Dqn`; an exploring step holds the lane's recurrent
+    state, the update runs whole sampled episodes from the zero state (include/relearn_hip.h, rl_dqn_create_recurrent)."""
+    _create = "rl_dqn_create_recurrent"
 
 
 class MeanVariance(C.Structure):

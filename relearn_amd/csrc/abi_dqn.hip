@@ -80,6 +80,8 @@ rl_dqn::~rl_dqn() {
   for (hipEvent_t ev : draw_events) (void)hipEventDestroy(ev);
   if (main_event) (void)hipEventDestroy(main_event);
   if (mb) rl_traj_destroy(mb);
+  if (roll) rl_traj_destroy(roll);
+  if (seq) rl_traj_destroy(seq);
 }
 
 // With several ranks a failure must be raised on ALL of them: a rank that throws before a collective leaves its peers
@@ -93,6 +95,8 @@ static bool dqn_any_rank_failed(rl_dqn *q, bool local_failure) {
   d2h(e, &flag, q->mb->vec, sizeof(flag));
   return flag > 0.0f;
 }
+
+static void dqn_build(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out, bool recurrent);
 
 int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out) {
   return guarded(env ? env->eng : nullptr, [&] {
@@ -121,59 +125,102 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
     // 5-128-2 shape on the fused kernels, others on the per-layer kernels); recurrent action-value modules do not
     if (rl_module_is_recurrent(qnet->kind))
       throw RlError(RL_ERR_BUILD_AGENT, "DQN is built for feed-forward action-value modules");
-    RL_REQUIRE(cfg->target == RL_DQN_TARGET_REWARD_TO_GO || cfg->target == RL_DQN_TARGET_ONE_STEP_TD, "bad target");
-    RL_REQUIRE(cfg->minibatch_steps > 0 && cfg->minibatch_steps < (1ull << 30), "bad minibatch_steps");
-    RL_REQUIRE(cfg->buffer_capacity > 0 && cfg->buffer_capacity < (1ull << 31), "bad buffer_capacity");
-    uint64_t E = cfg->episode_capacity ? cfg->episode_capacity : cfg->buffer_capacity;
-    RL_REQUIRE(E <= cfg->buffer_capacity, "episode_capacity exceeds buffer_capacity");
-    RL_REQUIRE(cfg->opt_steps_per_update <= 4096, "too many optimisation steps per update");
-    if (cfg->exploration_kind == RL_SCHEDULE_LINEAR_ANNEALED)
-      RL_REQUIRE(cfg->exploration_period > 0, "exploration_period must be positive");
-    uint64_t N = env->cfg.n_lanes;
-    // (a step: its record, its successor observation, and features 5..7 of an observation wider than the record)
-    const uint64_t step_bytes = sizeof(ReplayRec) + sizeof(ReplayNext) + (env->D > 5 ? sizeof(float4) : 0);
-    RL_REQUIRE(cfg->buffer_capacity * N * step_bytes < (200ull << 30), "replay store would not fit in HBM");
-    RL_HIP_CHECK(hipSetDevice(e->device));
-    std::unique_ptr<rl_dqn> q(new rl_dqn());
-    q->eng = e;
-    q->env = env;
-    q->qnet = qnet;
-    q->opt = opt;
-    q->cfg = *cfg;
-    q->cfg.episode_capacity = E;
-    DevMem &mem = q->mem;
-    q->rp = replay_alloc(e, mem, (uint32_t)N, (uint32_t)cfg->buffer_capacity, (uint32_t)E, env->D);
-    q->d_agent_pos = mem.alloc<uint64_t>(1);
-    RL_HIP_CHECK(hipMemsetAsync(q->d_agent_pos, 0, 8, e->stream));
-    // take_while accepts episodes while total < minibatch_steps and every episode has >= 1 step
-    q->max_eps = (uint32_t)cfg->minibatch_steps;
-    q->max_steps_mb = cfg->minibatch_steps - 1 + cfg->buffer_capacity;
-    // the episode lists of all opt_steps_per_update minibatches of an update are drawn in one launch
-    const size_t nb = cfg->opt_steps_per_update ? cfg->opt_steps_per_update : 1;
-    q->d_ep_lane = mem.alloc<uint32_t>(nb * q->max_eps);
-    q->d_ep_start = mem.alloc<uint32_t>(nb * q->max_eps);
-    q->d_ep_len = mem.alloc<uint32_t>(nb * q->max_eps);
-    q->d_ep_off = mem.alloc<uint32_t>(nb * q->max_eps);
-    q->d_counts = mem.alloc<DqnCountsDev>(nb);
-    RL_HIP_CHECK(hipMemsetAsync(q->d_counts, 0, nb * sizeof(DqnCountsDev), e->stream));
-    q->mb = traj_alloc(e, q->max_steps_mb, 1, env->D, true);
-    {  // the fused step's range guard (bf16_tile.hpp): the words hold the magnitude range of every observation the
-       // collection kernel has put into the store so far (k_rollout_dqn folds what it writes, one fold per wave
-       // and launch; never reset, so they bound every minibatch drawn from the store from outside).  Rounds 3-5 kept fixed bounds here, 2^-64 .. 2^16,
-       // under which a Q-network with a zero bias could never pass the guard.
-      std::vector<uint32_t> words(RL_RANGE_WORDS, 0u);  // every slot of the minima / the maxima (bf16_tile.hpp)
-      for (int s = 0; s < 64; ++s) words[(size_t)s * 32] = 0x7F7FFFFFu;  // "nothing seen": largest finite minimum, maximum 0
-      h2d(e, q->mb->d.range, words.data(), words.size() * sizeof(uint32_t));
-      q->mb->range_fixed = true;  // (maintained by the builders: no measuring pass over the workspace)
-    }
-    q->own_obs = q->mb->d.obs;
-    q->own_target = q->mb->d.adv;
-    q->own_action = q->mb->d.action;
-    q->own_flag = q->mb->d.flag;
-    sync(e);
-    e->live_handles += 1;
-    *out = q.release();
+    dqn_build(env, qnet, opt, cfg, out, /*recurrent=*/false);
   });
+}
+
+// DqnConfig<VB> over a sequence module (dqn.rs:75-86: VB::Module: SeqPacked + SeqIterative): the actor carries the
+// module's state through an episode (DqnActor::EpisodeState, dqn.rs:354-358) and the update runs seq_packed over whole
+// sampled episodes.  The env table of rl_dqn_create; every recurrent chain of two outputs.
+int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out) {
+  return guarded(env ? env->eng : nullptr, [&] {
+    RL_REQUIRE(env && qnet && opt && cfg && out, "rl_dqn_create_recurrent: NULL argument");
+    *out = nullptr;
+    rl_engine *e = env->eng;
+    RL_REQUIRE(qnet->eng == e && opt->eng == e, "rl_dqn_create_recurrent: handles belong to different engines");
+    RL_REQUIRE(opt->mod == qnet, "rl_dqn_create_recurrent: optimizer does not belong to the action-value module");
+    if (!rl_module_is_recurrent(qnet->kind))
+      throw RlError(RL_ERR_BUILD_AGENT,
+                    "rl_dqn_create_recurrent takes a recurrent action-value module; use rl_dqn_create for a feed-forward one");
+    if (env->kind == RL_ENV_META_BANDIT)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_recurrent is not built for RL_ENV_META_BANDIT lanes");
+    if (qnet->out_dim > 2 || env->A > 2)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_recurrent: the DQN kernels are built for 2 actions");
+    RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A,
+               "rl_dqn_create_recurrent: action-value module does not match the env");
+    const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
+    if (env->kind != RL_ENV_CARTPOLE && !index_env)
+      throw RlError(RL_ERR_UNSUPPORTED,
+                    "rl_dqn_create_recurrent: DQN collection is built for CartPole, Chain, MemoryGame and bandit lanes");
+    if (env->D < RL_ENV_MIN_OBS_DIM || env->D > (index_env ? RL_TRAJ_MAX_OBS_DIM : 5u))
+      throw RlError(RL_ERR_UNSUPPORTED, index_env ? "rl_dqn_create_recurrent on index-env lanes: 4..8 observation features"
+                                                  : "rl_dqn_create_recurrent on CartPole lanes: 4 or 5 observation features");
+    dqn_build(env, qnet, opt, cfg, out, /*recurrent=*/true);
+  });
+}
+
+// what the two constructors share: the configuration's checks, the replay store, the sampler's lists and the minibatch
+// workspace (+ the recurrent agent's two trajectory-shaped workspaces)
+static void dqn_build(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out, bool recurrent) {
+  rl_engine *e = env->eng;
+  RL_REQUIRE(cfg->target == RL_DQN_TARGET_REWARD_TO_GO || cfg->target == RL_DQN_TARGET_ONE_STEP_TD, "bad target");
+  RL_REQUIRE(cfg->minibatch_steps > 0 && cfg->minibatch_steps < (1ull << 30), "bad minibatch_steps");
+  RL_REQUIRE(cfg->buffer_capacity > 0 && cfg->buffer_capacity < (1ull << 31), "bad buffer_capacity");
+  uint64_t E = cfg->episode_capacity ? cfg->episode_capacity : cfg->buffer_capacity;
+  RL_REQUIRE(E <= cfg->buffer_capacity, "episode_capacity exceeds buffer_capacity");
+  RL_REQUIRE(cfg->opt_steps_per_update <= 4096, "too many optimisation steps per update");
+  if (cfg->exploration_kind == RL_SCHEDULE_LINEAR_ANNEALED)
+    RL_REQUIRE(cfg->exploration_period > 0, "exploration_period must be positive");
+  uint64_t N = env->cfg.n_lanes;
+  // (a step: its record, its successor observation, and features 5..7 of an observation wider than the record)
+  const uint64_t step_bytes = sizeof(ReplayRec) + sizeof(ReplayNext) + (env->D > 5 ? sizeof(float4) : 0);
+  RL_REQUIRE(cfg->buffer_capacity * N * step_bytes < (200ull << 30), "replay store would not fit in HBM");
+  RL_HIP_CHECK(hipSetDevice(e->device));
+  std::unique_ptr<rl_dqn> q(new rl_dqn());
+  q->eng = e;
+  q->env = env;
+  q->qnet = qnet;
+  q->opt = opt;
+  q->cfg = *cfg;
+  q->cfg.episode_capacity = E;
+  DevMem &mem = q->mem;
+  q->rp = replay_alloc(e, mem, (uint32_t)N, (uint32_t)cfg->buffer_capacity, (uint32_t)E, env->D);
+  q->d_agent_pos = mem.alloc<uint64_t>(1);
+  RL_HIP_CHECK(hipMemsetAsync(q->d_agent_pos, 0, 8, e->stream));
+  // take_while accepts episodes while total < minibatch_steps and every episode has >= 1 step
+  q->max_eps = (uint32_t)cfg->minibatch_steps;
+  q->max_steps_mb = cfg->minibatch_steps - 1 + cfg->buffer_capacity;
+  // the episode lists of all opt_steps_per_update minibatches of an update are drawn in one launch
+  const size_t nb = cfg->opt_steps_per_update ? cfg->opt_steps_per_update : 1;
+  q->d_ep_lane = mem.alloc<uint32_t>(nb * q->max_eps);
+  q->d_ep_start = mem.alloc<uint32_t>(nb * q->max_eps);
+  q->d_ep_len = mem.alloc<uint32_t>(nb * q->max_eps);
+  q->d_ep_off = mem.alloc<uint32_t>(nb * q->max_eps);
+  q->d_counts = mem.alloc<DqnCountsDev>(nb);
+  RL_HIP_CHECK(hipMemsetAsync(q->d_counts, 0, nb * sizeof(DqnCountsDev), e->stream));
+  q->mb = traj_alloc(e, q->max_steps_mb, 1, env->D, true);
+  {  // the fused step's range guard (bf16_tile.hpp): the words hold the magnitude range of every observation the
+     // collection kernel has put into the store so far (k_rollout_dqn folds what it writes, one fold per wave
+     // and launch; never reset, so they bound every minibatch drawn from the store from outside).  Rounds 3-5 kept fixed bounds here, 2^-64 .. 2^16,
+     // under which a Q-network with a zero bias could never pass the guard.
+    std::vector<uint32_t> words(RL_RANGE_WORDS, 0u);  // every slot of the minima / the maxima (bf16_tile.hpp)
+    for (int s = 0; s < 64; ++s) words[(size_t)s * 32] = 0x7F7FFFFFu;  // "nothing seen": largest finite minimum, maximum 0
+    h2d(e, q->mb->d.range, words.data(), words.size() * sizeof(uint32_t));
+    q->mb->range_fixed = true;  // (maintained by the builders: no measuring pass over the workspace)
+  }
+  q->own_obs = q->mb->d.obs;
+  q->own_target = q->mb->d.adv;
+  q->own_action = q->mb->d.action;
+  q->own_flag = q->mb->d.flag;
+  if (recurrent) {
+    q->recurrent = true;
+    q->roll = traj_alloc(e, N, 1, env->D, false);
+    stack_ensure(q->roll, qnet, false);
+    q->seq = traj_alloc(e, 1, 1, env->D, true);
+  }
+  sync(e);
+  e->live_handles += 1;
+  *out = q.release();
 }
 
 int32_t rl_dqn_destroy(rl_dqn *q) {
@@ -222,7 +269,9 @@ int32_t rl_dqn_collect(rl_dqn *q, uint64_t horizon, rl_dqn_collect_stats *stats)
     RL_REQUIRE(eps >= 0.0 && eps <= 1.0, "exploration rate outside [0, 1]");
     int always = rl_bernoulli_always(eps);
     uint64_t p_int = always ? ~0ull : rl_bernoulli_p_int(eps);
-    if (q->qnet->general) {
+    if (q->recurrent) {
+      launch_stack_collect_dqn(q->env, q->qnet, q->roll, q->rp, (uint32_t)horizon, p_int, always, q->d_flags);
+    } else if (q->qnet->general) {
       if (!q->d_q) q->d_q = q->mem.alloc<float>(2 * (size_t)q->rp.N);
       launch_rollout_dqn_general(q->env, q->qnet, q->mb, q->d_q, q->rp, (uint32_t)horizon, p_int, always, q->d_flags);
     } else {
@@ -283,6 +332,8 @@ static void dqn_draw_minibatches(rl_dqn *q, int sequential, uint32_t n_batches, 
   rl_engine *e = q->eng;
   launch_dqn_sample(e, e->stream, q->rp, dqn_key(q), q->d_agent_pos, (uint32_t)q->cfg.minibatch_steps, q->max_eps,
                     q->d_ep_lane, q->d_ep_start, q->d_ep_len, q->d_ep_off, q->d_counts, sequential, n_batches);
+  // (a recurrent agent lays a minibatch out by its longest episode: the length rides in the counts' spare word)
+  if (q->recurrent) launch_dqn_longest(e, q->d_ep_len, q->max_eps, q->d_counts, n_batches);
   counts.resize(n_batches);
   d2h(e, counts.data(), q->d_counts, n_batches * sizeof(DqnCountsDev));
   // local validation first, the verdict only after every rank has reported (a rank that throws here alone would leave
@@ -308,8 +359,84 @@ static void dqn_draw_minibatches(rl_dqn *q, int sequential, uint32_t n_batches, 
   }
 }
 
+// ---------------------------------------------------------------- a recurrent action-value module
+// (rl_dqn_create_recurrent; the workspace's layout and its kernels: kernels_dqn.hip, the forward / backward:
+// kernels_seq_stack.hip — every recurrent chain runs the lane-per-thread kernels here, at its own widths)
+static DqnSeqEps rdqn_eps(const rl_dqn *q, uint32_t k) {
+  const size_t o = (size_t)k * q->max_eps;
+  return DqnSeqEps{q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o, q->d_ep_off + o};
+}
+
+// seq_packed(observations) over the workspace (dqn.rs:316-318), with the activation record; `succ`: also the outputs at
+// the successor observations of Interrupts (the extended sequence of the one-step TD targets)
+static void rdqn_forward(rl_dqn *q, bool succ) {
+  rl_traj *s = q->seq;
+  launch_stack_forward(s, q->qnet, s->seq.out, succ ? s->seq.succ : (float *)nullptr, /*record=*/true, nullptr);
+  q->seq_fwd_epoch = q->eng->call_epoch;
+}
+
+// gather minibatch `k` of the last draw — episode after episode into `mb` (what rl_dqn_minibatch_read serves), one
+// episode per lane column into `seq` — and compute its targets (dqn.rs:293-314)
+static void rdqn_build_minibatch(rl_dqn *q, uint32_t k, const DqnCountsDev &c, uint64_t total) {
+  rl_engine *e = q->eng;
+  dqn_own_arrays(q);
+  q->last_n_eps = q->last_n_steps = 0;  // (until the workspace is whole)
+  rl_traj *mb = q->mb, *s = q->seq;
+  mb->d.n = c.n_steps;
+  mb->d.T = 1;
+  traj_plan(mb, c.n_steps);
+  const size_t o = (size_t)k * q->max_eps;
+  const bool td = q->cfg.target == RL_DQN_TARGET_ONE_STEP_TD;
+  launch_dqn_build_all(e, q->rp, 1, c.n_eps, q->max_eps, q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o,
+                       q->d_ep_off + o, q->d_counts + k, mb->d.obs, 0, mb->d.action, mb->d.adv, 0, q->cfg.discount_factor,
+                       td ? mb->d.flag : (uint8_t *)nullptr);
+  const uint64_t n = c.n_eps, T = c.pad, B = n * T, Dp = q->rp.D > 5 ? q->rp.D : 5;
+  RL_REQUIRE(T > 0 && T <= q->rp.C && B >= c.n_steps, "minibatch without its longest episode's length");
+  RL_REQUIRE(Dp * (T + 1) * n < (1ull << 31), "recurrent minibatch workspace: episodes x longest episode too large");
+  s->d.n = (uint32_t)n;
+  s->d.T = (uint32_t)T;
+  DevMem &mem = s->mem;
+  mem.ensure(s->d.obs, Dp * (T + 1) * n);
+  mem.ensure(s->d.term_obs, Dp * B);
+  mem.ensure(s->d.action, B);
+  mem.ensure(s->d.flag, B);
+  mem.ensure(s->d.reward, B);
+  mem.ensure(s->d.adv, B);
+  mem.ensure(s->dz, 2 * B);
+  traj_plan(s, B);
+  stack_ensure(s, q->qnet, true);
+  const DqnSeqEps eps = rdqn_eps(q, k);
+  launch_dqn_build_seq(s, q->rp, eps, td ? (const float *)nullptr : mb->d.adv);
+  q->seq_fwd_epoch = 0;
+  if (td) {  // under no_grad with the parameters of this optimisation step (dqn.rs:299-311): the forward the gradient reuses
+    rdqn_forward(q, true);
+    launch_dqn_seq_td_targets(s, eps, q->cfg.discount_factor, mb->d.adv);
+  }
+  q->last_n_eps = c.n_eps;
+  q->last_n_steps = c.n_steps;
+  q->last_total_steps = total;
+  q->last_batch_index = k;
+  q->last_longest = (uint32_t)T;
+}
+
+// gradient of mean((Q(s)[a] - target)^2) over the sampled steps of the current minibatch -> seq->vec[0..P), loss sum ->
+// seq->vec[P]; `step_opt`: also the optimiser's step, the loss into slot `loss_slot` of seq->losses
+static void rdqn_gradient(rl_dqn *q, rl_adam *step_opt, int loss_slot) {
+  rl_traj *s = q->seq;
+  const uint32_t P = (uint32_t)q->qnet->P;
+  if (q->seq_fwd_epoch != q->eng->call_epoch) rdqn_forward(q, false);
+  launch_dqn_seq_terms(s, rdqn_eps(q, q->last_batch_index), q->last_total_steps);
+  launch_stack_backward(s, q->qnet, nullptr);
+  launch_reduce(s, P, false, true, 0, s->nbB);
+  if (step_opt) {
+    launch_opt_step(s, step_opt, loss_slot, q->last_total_steps);
+    q->seq_fwd_epoch = 0;  // (the outputs are those of the parameters before the step)
+  }
+}
+
 // gather minibatch `k` of the last draw and compute its targets (dqn.rs:293-314)
 static void dqn_build_minibatch(rl_dqn *q, uint32_t k, const DqnCountsDev &c, uint64_t total) {
+  if (q->recurrent) return rdqn_build_minibatch(q, k, c, total);
   dqn_own_arrays(q);
   q->last_n_eps = c.n_eps;
   q->last_n_steps = c.n_steps;
@@ -348,6 +475,7 @@ static void dqn_sample_minibatch(rl_dqn *q, int sequential) {
 // `step_opt` != nullptr: also take the optimiser step, recording the loss in slot `loss_slot`; without an all-reduce
 // between them the reduction and the (elementwise) step are one launch
 static void dqn_gradient(rl_dqn *q, rl_adam *step_opt = nullptr, int loss_slot = -1) {
+  if (q->recurrent) return rdqn_gradient(q, step_opt, loss_slot);
   rl_traj *mb = q->mb;
   // targets given (reward-to-go, or one-step TD built beforehand): two critic-step channels per SIMD
   // (kernels_critic.hip, k_critic_step_mfma<2>); targets formed inside the launch (one-step TD on the current network):
@@ -373,9 +501,70 @@ static void dqn_gradient(rl_dqn *q, rl_adam *step_opt = nullptr, int loss_slot =
   if (step_opt) launch_opt_step(mb, step_opt, loss_slot, q->last_total_steps);
 }
 
+// rl_dqn_update of a recurrent agent.  The episode lists of all K minibatches come from one launch of the sampler and are
+// validated before the first step; their sizes and longest episodes are the update's one read-back.  Every minibatch is
+// then gathered, run forward (one-step TD: targets from the same forward), differentiated and stepped without another
+// host round trip.  All or nothing: parameters, optimiser state and step count are saved first and put back when a later
+// minibatch fails (RELEARN_DQN_FAIL_CHUNK=c fails at the start of chunk c of the 2, 4, 8, ... chunks the feed-forward
+// update trains in — the same test facility).
+static void rdqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) {
+  rl_engine *e = q->eng;
+  if (e->n_ranks > 1)
+    throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_update: an agent of rl_dqn_create_recurrent updates on one rank");
+  q->global_steps = q->steps_per_lane * (uint64_t)q->rp.N;
+  const uint64_t K = q->cfg.opt_steps_per_update;
+  std::vector<DqnCountsDev> counts;
+  std::vector<uint64_t> totals;
+  if (K) dqn_draw_minibatches(q, 0, (uint32_t)K, counts, totals);
+  const uint64_t Pq = q->qnet->P, host_step0 = q->opt->host_step;
+  if (!q->snap) q->snap = q->mem.alloc<float>(4 * Pq + 2);
+  RL_HIP_CHECK(hipMemcpyAsync(q->snap, q->qnet->d_params, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  for (int s = 0; s < 3; ++s)
+    if (q->opt->d_state[s])
+      RL_HIP_CHECK(hipMemcpyAsync(q->snap + (s + 1) * Pq, q->opt->d_state[s], Pq * sizeof(float), hipMemcpyDeviceToDevice,
+                                  e->stream));
+  RL_HIP_CHECK(hipMemcpyAsync(q->snap + 4 * Pq, q->opt->d_step, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
+  try {
+    size_t c = 0;
+    for (uint64_t first = 0, size = 2; first < K; first += size, size *= 2, ++c) {
+      if (const char *inj = std::getenv("RELEARN_DQN_FAIL_CHUNK"))
+        if ((size_t)std::atoi(inj) == c) throw RlError(RL_ERR_INVALID_ARGUMENT, "injected sampler failure");
+      for (uint64_t k = first; k < first + size && k < K; ++k) {
+        rdqn_build_minibatch(q, (uint32_t)k, counts[k], totals[k]);
+        rdqn_gradient(q, q->opt, (int)k);
+      }
+    }
+    sync(e);  // (a launch that failed surfaces here, inside the all-or-nothing scope)
+  } catch (...) {
+    (void)hipMemcpyAsync(q->qnet->d_params, q->snap, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
+    wimg_invalidate(q->qnet);
+    for (int s = 0; s < 3; ++s)
+      if (q->opt->d_state[s])
+        (void)hipMemcpyAsync(q->opt->d_state[s], q->snap + (s + 1) * Pq, Pq * sizeof(float), hipMemcpyDeviceToDevice,
+                             e->stream);
+    (void)hipMemcpyAsync(q->opt->d_step, q->snap + 4 * Pq, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream);
+    (void)hipStreamSynchronize(e->stream);
+    q->opt->host_step = host_step0;
+    q->last_n_eps = q->last_n_steps = 0;  // no minibatch to read after a failed update
+    throw;
+  }
+  std::vector<float> h(K ? K : 1, 0.0f);
+  if (K) d2h(e, h.data(), q->seq->losses, K * sizeof(float));
+  if (losses_out && K) std::memcpy(losses_out, h.data(), K * sizeof(float));
+  if (stats) {
+    stats->opt_steps = K;
+    stats->loss_first = K ? (double)h[0] : 0.0;
+    stats->loss_last = K ? (double)h[K - 1] : 0.0;
+    stats->global_steps = q->global_steps;
+    stats->last_minibatch_steps = q->last_n_steps;
+    stats->last_minibatch_episodes = q->last_n_eps;
+  }
+}
+
 int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) {
   return guarded(q ? q->eng : nullptr, [&] {
     RL_REQUIRE(q, "NULL argument");
+    if (q->recurrent) return rdqn_update(q, stats, losses_out);
     rl_engine *e = q->eng;
     // self.global_steps = sum of total_step_count over the buffers (dqn.rs:276); every lane of every rank has
     // taken the same number of steps and the horizon rule drops none
@@ -636,7 +825,7 @@ int32_t rl_dqn_minibatch_gradient(rl_dqn *q, float *grad_out, float *loss_out) {
     uint32_t P = (uint32_t)q->qnet->P;
     dqn_gradient(q);
     std::vector<float> h(P + 4);
-    d2h(q->eng, h.data(), q->mb->vec, (P + 4) * sizeof(float));
+    d2h(q->eng, h.data(), (q->recurrent ? q->seq : q->mb)->vec, (P + 4) * sizeof(float));
     range_check(q->mb, 1u << RL_GUARD_POLICY);
     std::memcpy(grad_out, h.data(), P * sizeof(float));
     if (loss_out) *loss_out = (float)((double)h[P] / (double)q->last_total_steps);

@@ -492,6 +492,16 @@ struct rl_dqn {
   uint64_t steps_per_lane = 0;       // collected so far
   uint32_t last_n_eps = 0, last_n_steps = 0, last_batch_index = 0;
   uint64_t last_total_steps = 0;     // minibatch size summed over ranks
+  // rl_dqn_create_recurrent: the action-value module is a recurrent chain.  `roll`: per-lane states and observation planes
+  // of the collection kernel (n = N lanes, T = 1).  `seq`: the current minibatch as a trajectory — one sampled episode per
+  // lane column, T = the longest one (`last_longest`), grown with the largest minibatch seen (kernels_dqn.hip has the
+  // layout); `mb` keeps the episode-after-episode arrays rl_dqn_minibatch_read serves.  `seq_fwd_epoch`: the C-ABI call
+  // (rl_engine::call_epoch) in which seq.out and the activation record were made for the current minibatch at the
+  // current parameters — the one-step TD targets' forward, which the gradient of the same call does not repeat.
+  bool recurrent = false;
+  rl_traj *roll = nullptr, *seq = nullptr;
+  uint32_t last_longest = 0;
+  uint64_t seq_fwd_epoch = 0;
 };
 
 // ---- profiling helper: wraps a launch with events when enabled ---------------------------------------

@@ -24,6 +24,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <optional>
 #include <vector>
@@ -442,6 +443,19 @@ struct ChainLstmLinearConfig {
     return GruLinearConfig::build(eng, RL_CELL_LSTM, first_config, hidden_dim, second_config, in_dim, out_dim, seed);
   }
 };
+
+// Is the module a configuration builds a sequence module with a state of its own (the recurrent chains)?  DqnConfig over
+// one builds its agent through rl_dqn_create_recurrent (dqn.rs:75-86: VB::Module: SeqPacked + SeqIterative).
+template <typename VB>
+struct builds_recurrent_module : std::false_type {};
+template <>
+struct builds_recurrent_module<GruMlpConfig> : std::true_type {};
+template <>
+struct builds_recurrent_module<ChainLstmMlpConfig> : std::true_type {};
+template <>
+struct builds_recurrent_module<GruLinearConfig> : std::true_type {};
+template <>
+struct builds_recurrent_module<ChainLstmLinearConfig> : std::true_type {};
 
 // ---------------------------------------------------------------- optimizers (src/torch/optimizers/mod.rs:25-92)
 // `Optimizer` (first-order: backward_step) and `TrustRegionOptimizer` (trust_region_backward_step) are the reference's
@@ -1056,6 +1070,7 @@ class DqnAgent {
  public:
   ~DqnAgent() { rl_dqn_destroy(dqn_); }  // before the optimizer and the module it refers to
   Module &action_value_fn() { return *q_; }
+  rl_dqn *handle() const { return dqn_; }
   struct Bound { uint64_t min_steps, slack_steps; };
   Bound min_update_size() const {  // dqn.rs:207-209
     Bound b{};
@@ -1133,7 +1148,11 @@ std::unique_ptr<DqnAgent> build_dqn_agent(const DqnConfig<VB, OC> &c, EnvLanes &
   d.update_rest = c.update_rest;
   d.discount_factor = (float)env.discount_factor();
   std::memcpy(d.agent_key, agent_key, sizeof(d.agent_key));
-  check(rl_dqn_create(env.handle(), a->q_->handle(), a->opt_->handle(), &d, &a->dqn_), eng.handle());
+  // a feed-forward module, or a recurrent chain: the actor then carries the module's state through an episode and the
+  // update runs whole sampled episodes (relearn_hip.h, rl_dqn_create_recurrent)
+  check((builds_recurrent_module<VB>::value ? rl_dqn_create_recurrent : rl_dqn_create)(
+            env.handle(), a->q_->handle(), a->opt_->handle(), &d, &a->dqn_),
+        eng.handle());
   return a;
 }
 

@@ -139,6 +139,23 @@ void launch_dqn_build_minibatch(rl_engine *eng, const ReplayDev &rp, uint32_t n_
                                 const uint32_t *d_start, const uint32_t *d_len, const uint32_t *d_off,
                                 float *d_obs, size_t out_plane, uint8_t *d_action, float *d_target, float gamma,
                                 int one_step_td, const rl_mlp *qnet);
+// recurrent action-value modules (rl_dqn_create_recurrent): the sampled episodes of one minibatch as the lane columns of
+// a trajectory-shaped workspace `seq` (n = episodes, T = the longest one; kernels_dqn.hip has the layout)
+struct DqnSeqEps {
+  const uint32_t *lane, *start, *len, *off;  // the minibatch's episode lists (k_dqn_sample)
+};
+// the longest episode of each minibatch of a draw -> d_counts[b].pad
+void launch_dqn_longest(rl_engine *eng, const uint32_t *d_len, uint32_t max_eps, DqnCountsDev *d_counts, uint32_t n_batches);
+// ring -> workspace planes; targets from `d_given` (episode-after-episode order), or NULL: the rewards
+void launch_dqn_build_seq(rl_traj *seq, const ReplayDev &rp, const DqnSeqEps &ep, const float *d_given);
+// one-step TD targets from seq.out / seq.succ -> the workspace's targets and `d_compact` (episode-after-episode order)
+void launch_dqn_seq_td_targets(rl_traj *seq, const DqnSeqEps &ep, float gamma, float *d_compact);
+// seq.out, targets -> dz (zero on padding) and the loss sum in slab B
+void launch_dqn_seq_terms(rl_traj *seq, const DqnSeqEps &ep, uint64_t B_total);
+// kernels_seq_stack.hip: all `T` collection steps of a recurrent action-value module in one launch; `roll` lends the
+// per-lane states and the observation planes ([D][2][N])
+void launch_stack_collect_dqn(rl_env *env, const rl_mlp *qnet, rl_traj *roll, const ReplayDev &rp, uint32_t T,
+                              uint64_t p_int, int always_explore, uint8_t *d_flags);
 
 // kernels_seq.hip (recurrent configuration: GRU -> ReLU -> MLP module; tiles of 32 lanes)
 void launch_rollout_gru(rl_env *env, const rl_mlp *policy, rl_traj *traj);        // recurrent policy, either env kind

@@ -9,63 +9,10 @@
 
 #include "bf16_tile.hpp"
 #include "device_fns.hpp"
+#include "dqn_lanes.hpp"
 #include "env_lanes.hpp"
 #include "kernels.hpp"
 #include "replay.hpp"
-
-// one step record: two 16-byte accesses
-__device__ __forceinline__ ReplayRec rec_load(const ReplayRec *__restrict__ p) {
-  const uint4 a = reinterpret_cast<const uint4 *>(p)[0], b = reinterpret_cast<const uint4 *>(p)[1];
-  ReplayRec r;
-  r.x[0] = __uint_as_float(a.x), r.x[1] = __uint_as_float(a.y), r.x[2] = __uint_as_float(a.z), r.x[3] = __uint_as_float(a.w);
-  r.x[4] = __uint_as_float(b.x), r.reward = __uint_as_float(b.y), r.af = b.z, r.pad = b.w;
-  return r;
-}
-__device__ __forceinline__ void rec_store(ReplayRec *__restrict__ p, const ReplayRec &r) {
-  reinterpret_cast<uint4 *>(p)[0] = make_uint4(__float_as_uint(r.x[0]), __float_as_uint(r.x[1]), __float_as_uint(r.x[2]),
-                                               __float_as_uint(r.x[3]));
-  reinterpret_cast<uint4 *>(p)[1] = make_uint4(__float_as_uint(r.x[4]), __float_as_uint(r.reward), r.af, 0u);
-}
-
-// features 5..D of the step at record index `o` (observations wider than the record: ReplayDev::hi), one 16-byte load
-template <int D>
-__device__ __forceinline__ void rec_load_hi(const ReplayDev &rp, size_t o, float (&x)[D]) {
-  static_assert(D > 5 && D <= 8, "the second record array holds features 5, 6 and 7");
-  const float4 h = rp.hi[o];
-  x[5] = h.x;
-  if (D > 6) x[D > 6 ? 6 : 0] = h.y;
-  if (D > 7) x[D > 7 ? 7 : 0] = h.z;
-}
-
-// DqnActor::act (dqn.rs:360-379) from the lane's sequential actor stream:
-//   if rng.gen_bool(eps) { action_space.sample(rng) = gen_range(0..2) } else { argmax_a Q(obs)[a] }
-// The draws are here; the greedy branch is the kernel's (the first maximal index of its action values).
-template <class Rng>
-__device__ __forceinline__ bool dqn_explores(Rng &rng, uint64_t p_int, int always_explore) {
-  bool explore = always_explore != 0;
-  if (!explore) explore = rl_bernoulli_from_u64(rng.next_u64(), p_int) != 0;  // Bernoulli::sample (rl_chacha.h)
-  return explore;
-}
-template <class Rng>
-__device__ __forceinline__ int dqn_random_action(Rng &rng) {
-  // UniformInt::sample_single(0, 2): widening multiply by 2, zone = (2 << 62) - 1
-  for (;;) {
-    const uint64_t v = rng.next_u64();
-    const uint64_t lo = v << 1, hi = v >> 63;
-    if (lo <= 0x7fffffffffffffffull) return (int)hi;
-  }
-}
-
-// the lane's episode table; `writer` false: a thread that follows the lane (it reads the table, the lane's writer writes)
-struct LaneEpEnds {
-  uint32_t *base;
-  uint32_t N, lane;
-  bool writer;
-  __device__ uint32_t get(uint32_t k) const { return base[(size_t)k * N + lane]; }
-  __device__ void set(uint32_t k, uint32_t v) {
-    if (writer) base[(size_t)k * N + lane] = v;
-  }
-};
 
 // T env-actor steps per lane with the DQN actor (dqn_explores / dqn_random_action, else the greedy action); every step is
 // appended to the lane's replay ring.
@@ -1043,5 +990,166 @@ __global__ void __launch_bounds__(256) k_replay_planes(ReplayDev rp, int field, 
 void launch_replay_planes(rl_engine *eng, const ReplayDev &rp, int field, void *d_out) {
   const size_t cn = (size_t)rp.C * rp.N;
   hipLaunchKernelGGL(k_replay_planes, dim3(cdiv_d(cn, 256)), dim3(256), 0, eng->stream, rp, field, d_out);
+  RL_HIP_CHECK(hipGetLastError());
+}
+
+// ================================================================================================
+// Recurrent action-value modules (rl_dqn_create_recurrent): the sampled episodes as a trajectory-shaped workspace.
+// seq_packed(observations) runs every sampled episode from the zero state over all of its steps (dqn.rs:293-326), so a
+// minibatch of n_eps episodes is laid out as n_eps lane columns of T = its longest episode: column e holds episode e in
+// slots 0 .. len_e - 1, the teacher-forced forward / backward of kernels_seq_stack.hip run on it as on any trajectory.
+// A padding slot (t >= len_e) holds a zero observation and the successor code Terminate: the state restarts behind it,
+// nothing flows back through it, and the terms below give it dz = 0 and no share in the loss or its divisor.
+// ================================================================================================
+
+// the longest episode of each minibatch of a draw -> counts[b].pad (read back with the counts)
+__global__ void __launch_bounds__(256) k_dqn_longest(const uint32_t *__restrict__ ep_len, uint32_t max_eps,
+                                                     DqnCountsDev *__restrict__ counts) {
+  __shared__ uint32_t red[256];
+  const uint32_t b = blockIdx.x, n_eps = counts[b].n_eps < max_eps ? counts[b].n_eps : max_eps;
+  uint32_t m = 0;
+  for (uint32_t e = threadIdx.x; e < n_eps; e += 256) {
+    const uint32_t l = ep_len[(size_t)b * max_eps + e];
+    m = l > m ? l : m;
+  }
+  red[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x + s] > red[threadIdx.x] ? red[threadIdx.x + s] : red[threadIdx.x];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) counts[b].pad = red[0];
+}
+
+// the gather: one thread per slot b = t * n + e of the workspace (`given`: the compact targets of the episode-after-episode
+// arrays — reward-to-go; NULL: the slot's reward, to which k_dqn_seq_td_targets adds the successor's value)
+template <int D>
+__global__ void __launch_bounds__(256) k_dqn_build_seq(ReplayDev rp, DqnSeqEps ep, TrajDev tr,
+                                                       const float *__restrict__ given) {
+  const uint32_t n = tr.n, T = tr.T;
+  const size_t B = (size_t)T * n, plane = (size_t)(T + 1) * n;
+  const size_t b = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const uint32_t e = (uint32_t)(b % n), t = (uint32_t)(b / n);
+  const uint32_t len = ep.len[e];
+  float x[D];
+#pragma unroll
+  for (int d = 0; d < D; ++d) x[d] = 0.0f;
+  uint32_t act = 0, fl = RL_SUCC_TERMINATE;
+  float rew = 0.0f, tgt = 0.0f;
+  if (t < len) {
+    const uint32_t lane = ep.lane[e], slot = (ep.start[e] + t) % rp.C;
+    const size_t o = (size_t)lane * rp.C + slot;
+    const ReplayRec rec = rec_load(rp.rec + o);
+#pragma unroll
+    for (int d = 0; d < (D < 5 ? D : 5); ++d) x[d] = rec.x[d];
+    if constexpr (D > 5) rec_load_hi<D>(rp, o, x);
+    act = rec.af & 0xffu;
+    fl = rec.af >> 8;
+    rew = rec.reward;
+    tgt = given != nullptr ? given[ep.off[e] + t] : rew;
+    if (fl == RL_SUCC_INTERRUPT) {
+      const ReplayNext *__restrict__ nx = rp.next + o;
+#pragma unroll
+      for (int d = 0; d < D; ++d) tr.term_obs[(size_t)d * B + b] = nx->x[d];
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    tr.obs[(size_t)d * plane + b] = x[d];
+    if (t + 1 == T) tr.obs[(size_t)d * plane + B + e] = 0.0f;  // (slot T: never read — no column ends on Continue)
+  }
+  tr.action[b] = (uint8_t)act;
+  tr.flag[b] = (uint8_t)fl;
+  tr.reward[b] = rew;
+  tr.adv[b] = tgt;
+}
+
+// one-step TD targets (critics/mod.rs:101-148) from the forward over the workspace: the module has run over the episode
+// plus one slot — the successor observation of an Interrupt (succ) — so V_ext[t + 1] = amax of the next slot's outputs,
+// of the successor outputs after an Interrupt, 0 after a Terminate; target = r + gamma * V_ext[t + 1] with
+// k_dqn_td_targets' arithmetic (`scalar * tensor`, then add).  Also into the episode-after-episode array (`compact`).
+__global__ void __launch_bounds__(256) k_dqn_seq_td_targets(TrajDev tr, DqnSeqEps ep, const float *__restrict__ out,
+                                                            const float *__restrict__ succ, float gamma,
+                                                            float *__restrict__ compact) {
+  const uint32_t n = tr.n;
+  const size_t B = (size_t)tr.T * n;
+  const size_t b = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const uint32_t e = (uint32_t)(b % n), t = (uint32_t)(b / n);
+  if (t >= ep.len[e]) return;
+  const uint8_t f = tr.flag[b];
+  float vnext = 0.0f;
+  // (a Continue slot has a successor slot in its own column: an episode's last step never continues — the second test
+  // only keeps a corrupt store from reading past the planes)
+  if (f != RL_SUCC_TERMINATE && (f == RL_SUCC_INTERRUPT || t + 1 < tr.T)) {
+    const float *__restrict__ src = f == RL_SUCC_INTERRUPT ? succ + b : out + b + n;
+    const float z0 = src[0], z1 = src[B];
+    vnext = z1 > z0 ? z1 : z0;
+  }
+  const float dn = gamma * vnext;
+  const float tgt = tr.reward[b] + dn;
+  tr.adv[b] = tgt;
+  compact[ep.off[e] + t] = tgt;
+}
+
+// the DQN terms over the output plane pair q [2][B] (PASS_DQN of policy_terms.hpp): dz[a] = [a == action] 2 (Q_a - target)
+// / n_steps, zero on padding, and the f64 sum of (Q_a - target)^2 through slab B
+__global__ void __launch_bounds__(256) k_dqn_seq_terms(TrajDev tr, DqnSeqEps ep, const float *__restrict__ q,
+                                                       float *__restrict__ dz, double *__restrict__ slabB,
+                                                       float two_over_B) {
+  __shared__ double red[256];
+  const uint32_t n = tr.n;
+  const size_t B = (size_t)tr.T * n;
+  double s0 = 0.0;
+  for (size_t b = (size_t)blockIdx.x * 256 + threadIdx.x; b < B; b += (size_t)gridDim.x * 256) {
+    const uint32_t e = (uint32_t)(b % n), t = (uint32_t)(b / n);
+    const bool valid = t < ep.len[e];
+    const int act = tr.action[b];
+    const float dq = (act == 0 ? q[b] : q[B + b]) - tr.adv[b];
+    const float g = dq * two_over_B;
+    dz[b] = valid && act == 0 ? g : 0.0f;
+    dz[B + b] = valid && act == 1 ? g : 0.0f;
+    if (valid) s0 += (double)(dq * dq);
+  }
+  const double t0 = block_sum<256>(s0, red);
+  if (threadIdx.x == 0) {
+    slabB[blockIdx.x * 4 + 0] = t0;
+    slabB[blockIdx.x * 4 + 1] = 0.0;
+    slabB[blockIdx.x * 4 + 2] = 0.0;
+    slabB[blockIdx.x * 4 + 3] = 0.0;
+  }
+}
+
+void launch_dqn_longest(rl_engine *eng, const uint32_t *d_len, uint32_t max_eps, DqnCountsDev *d_counts,
+                        uint32_t n_batches) {
+  ProfScope ps(eng, RL_K_SMALL);
+  if (n_batches == 0) return;
+  hipLaunchKernelGGL(k_dqn_longest, dim3(n_batches), dim3(256), 0, eng->stream, d_len, max_eps, d_counts);
+  RL_HIP_CHECK(hipGetLastError());
+}
+
+void launch_dqn_build_seq(rl_traj *seq, const ReplayDev &rp, const DqnSeqEps &ep, const float *d_given) {
+  ProfScope ps(seq->eng, RL_K_VALUES);
+  const size_t B = (size_t)seq->d.T * seq->d.n;
+  dqn_features_dispatch(rp.D, [&](auto d) {
+    hipLaunchKernelGGL(k_dqn_build_seq<decltype(d)::value>, dim3(cdiv_d(B, 256)), dim3(256), 0, seq->eng->stream, rp, ep,
+                       seq->d, d_given);
+  });
+  RL_HIP_CHECK(hipGetLastError());
+}
+
+void launch_dqn_seq_td_targets(rl_traj *seq, const DqnSeqEps &ep, float gamma, float *d_compact) {
+  ProfScope ps(seq->eng, RL_K_VALUES);
+  const size_t B = (size_t)seq->d.T * seq->d.n;
+  hipLaunchKernelGGL(k_dqn_seq_td_targets, dim3(cdiv_d(B, 256)), dim3(256), 0, seq->eng->stream, seq->d, ep, seq->seq.out,
+                     seq->seq.succ, gamma, d_compact);
+  RL_HIP_CHECK(hipGetLastError());
+}
+
+void launch_dqn_seq_terms(rl_traj *seq, const DqnSeqEps &ep, uint64_t B_total) {
+  ProfScope ps(seq->eng, RL_K_POLICY_PASS);
+  hipLaunchKernelGGL(k_dqn_seq_terms, dim3(seq->nbB), dim3(256), 0, seq->eng->stream, seq->d, ep, seq->seq.out, seq->dz,
+                     seq->slabB, 2.0f / (float)B_total);
   RL_HIP_CHECK(hipGetLastError());
 }

@@ -25,6 +25,7 @@
 //   k_stack_tangent   forward-mode derivative along a parameter tangent through the recorded activations
 #include "abi_internal.hpp"
 #include "device_fns.hpp"
+#include "dqn_lanes.hpp"
 #include "env_lanes.hpp"
 
 namespace {
@@ -203,11 +204,13 @@ __device__ __forceinline__ void store_outputs(float *__restrict__ dst, size_t st
 }
 
 // layer l of one step: in[k * in_stride + lane] (K inputs), states (h, c) -> (hn, cn); `fresh`: the lane's state is zero
-template <int CELL, bool REC, bool CW = false>
+// HOLD (the DQN collection, k_stack_collect_dqn): a lane with `hold` set passes its state through, bit for bit — (hn, cn)
+// = (h, c), zero where `fresh` — whatever the step computed for it
+template <int CELL, bool REC, bool CW = false, bool HOLD = false>
 __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &ws, int l, const float *__restrict__ in,
                                            size_t in_stride, const float *__restrict__ h, const float *__restrict__ c,
                                            bool fresh, float *__restrict__ hn, float *__restrict__ cn, const LaneCtx &lc,
-                                           size_t b) {
+                                           size_t b, bool hold = false) {
   constexpr int G = gates<CELL>();
   const int H = net.H, K = l == 0 ? net.D : net.H;
   const size_t n = ws.n;
@@ -252,7 +255,7 @@ __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &w
         const float tc = rl_tanhf(cc);
         hnew = og * tc;
         if (lc.live) {
-          cn[(size_t)j * n + lc.ii] = cc;
+          cn[(size_t)j * n + lc.ii] = HOLD && hold ? cp : cc;
           if (REC) {
             rec_plane(ws, net, l, RP_G0)[(size_t)j * ws.B + b] = ig;
             rec_plane(ws, net, l, RP_G1)[(size_t)j * ws.B + b] = fg;
@@ -277,6 +280,7 @@ __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &w
           rec_plane(ws, net, l, RP_G3)[(size_t)j * ws.B + b] = gh[2][u];
         }
       }
+      if (HOLD && hold) hnew = hp;
       if (lc.live) {
         hn[(size_t)j * n + lc.ii] = hnew;
         if (REC) {
@@ -361,15 +365,16 @@ __device__ __forceinline__ void stack_head(const StackNet &net, const StackWs &w
 }
 
 // all layers + head of one step: states of set `cur` (zero where `fresh`) -> set `nxt`
-template <int CELL, bool REC, bool CW = false, bool LIN = false, int NQ = 2>
+// (HOLD / hold: stack_cell's; the outputs of a held lane are not its action values and are not to be used)
+template <int CELL, bool REC, bool CW = false, bool LIN = false, int NQ = 2, bool HOLD = false>
 __device__ __forceinline__ void stack_module_step(const StackNet &net, const StackWs &ws, const float *__restrict__ x,
                                                   size_t x_stride, int cur, int nxt, bool fresh, const LaneCtx &lc,
-                                                  size_t b, float (&out)[NQ]) {
+                                                  size_t b, float (&out)[NQ], bool hold = false) {
   for (int l = 0; l < net.L; ++l) {
     const float *in = l == 0 ? x : slot(ws, net, nxt, 0, l - 1);
-    stack_cell<CELL, REC, CW>(net, ws, l, in, l == 0 ? x_stride : (size_t)ws.n, slot(ws, net, cur, 0, l),
-                              slot(ws, net, cur, 1, l), fresh, slot(ws, net, nxt, 0, l), slot(ws, net, nxt, 1, l), lc,
-                              b);
+    stack_cell<CELL, REC, CW, HOLD>(net, ws, l, in, l == 0 ? x_stride : (size_t)ws.n, slot(ws, net, cur, 0, l),
+                                    slot(ws, net, cur, 1, l), fresh, slot(ws, net, nxt, 0, l), slot(ws, net, nxt, 1, l),
+                                    lc, b, hold);
     __syncthreads();
   }
   stack_head<REC, CW, LIN, NQ>(net, ws, slot(ws, net, nxt, 0, net.L - 1), lc, b, out);
@@ -487,6 +492,117 @@ __global__ void __launch_bounds__(SL *SW) k_stack_rollout(StackNet net, StackWs 
     cur ^= 1;
   }
   if (writer) Env::store(st, lc.ii, s);
+}
+
+// All T collection steps of a DQN agent with a recurrent action-value module in one launch (rl_dqn_create_recurrent):
+// k_stack_rollout's module step joined with k_rollout_dqn's actor and replay ring (kernels_dqn.hip, dqn_lanes.hpp).
+// DqnActor::act (dqn.rs:360-379) draws gen_bool(eps) first and, when the step explores, returns gen_range(0..2) BEFORE
+// the module's step(): the module never sees that observation and the lane's recurrent state is what it was.  Per step:
+//   wave 0   the lane's observation features -> the observation planes `xobs` ([D][.][n], plane stride `xstride`); the
+//            exploration draw and, for an exploring lane, the random action; the decision -> LDS
+//   barrier  (also the vote: a workgroup whose lanes all explore skips the module step — nothing is advanced, and the
+//            state sets are not swapped)
+//   all      the module step, exploring lanes held (stack_cell HOLD: their states pass through bit for bit)
+//   wave 0   the greedy action (first maximal index), Env::step, the ring record (+ `hi` for D > 5, the successor
+//            observation of an Interrupt, flags_out), the horizon rule and the auto-reset of k_rollout_dqn; the successor
+//            code -> LDS
+//   barrier  every thread of the lane learns whether its state is zero at the next step: after an episode's end, or
+//            still — a lane that has only explored since
+// The lane's env state, ring words and LaneActorRng live in wave 0's registers from the first step to the last; the
+// state is zero at the first step of every launch (the ring closes a lane the horizon cuts as Interrupt: what follows is
+// a new recorded episode).  A lane whose ring refuses a step (WriteExperienceError::Full) stops acting and follows the
+// barriers; the host raises the error.
+template <int CELL, class Env, int D, bool LIN>
+__global__ void __launch_bounds__(SL *SW) k_stack_collect_dqn(StackNet net, StackWs ws, CartPoleDev c, EnvStateDev st,
+                                                              ReplayDev rp, float *__restrict__ xobs, size_t xstride,
+                                                              uint32_t T, uint64_t p_int, int always_explore,
+                                                              uint8_t *__restrict__ flags_out, uint64_t t_global) {
+  __shared__ uint32_t words[16 * SL];  // LaneActorRng's block columns (wave 0)
+  __shared__ uint8_t succ_of[SL], hold_of[SL];
+  const uint32_t n = rp.N;
+  const LaneCtx lc = lane_ctx(n);
+  const bool actor = lc.wave == 0, writer = lc.live && actor;
+  const uint32_t col = threadIdx.x & (SL - 1);
+  const uint64_t glane = c.lane_offset + lc.ii;
+  typename Env::State s{};
+  LaneRing ring{};
+  LaneEpEnds eps{rp.ep_end, n, lc.ii, writer};
+  LaneActorRng<SL> rng{&words[col], c.key_actor, glane, 0, ~0ull};
+  if (actor) {
+    Env::load(st, lc.ii, s);
+    ring = ring_load(rp, lc.ii);
+    rng.pos = rp.actor_pos[lc.ii];
+  }
+  bool fresh = true, full = false;
+  int cur = SET_A;
+  for (uint32_t t = 0; t < T; ++t) {
+    float f[D];
+    bool explore = true;
+    int a = 0;
+    if (actor) {
+      Env::template features<D>(c, s, f);
+      if (!full) {
+        explore = dqn_explores(rng, p_int, always_explore);
+        if (explore) a = dqn_random_action(rng);
+      }
+      if (writer && !explore) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) xobs[(size_t)d * xstride + lc.ii] = f[d];
+      }
+      hold_of[col] = explore ? 1 : 0;
+    }
+    const int any_greedy = __syncthreads_or(writer && !explore ? 1 : 0);
+    const bool hold = hold_of[col] != 0;
+    float o[2] = {0.0f, 0.0f};
+    if (any_greedy) {
+      stack_module_step<CELL, false, true, LIN, 2, true>(net, ws, xobs, xstride, cur, cur ^ 1, fresh, lc, 0, o, hold);
+      cur ^= 1;
+    }
+    if (actor) {
+      int succ = RL_SUCC_CONTINUE;
+      if (!full) {
+        if (!explore) a = o[1] > o[0] ? 1 : 0;  // argmax: first maximal index
+        float reward;
+        succ = Env::step(c, s, a, glane, t_global + t, reward);
+        const bool horizon_cut = succ == RL_SUCC_CONTINUE && t + 1 == T;
+        const int succ_rec = horizon_cut ? RL_SUCC_INTERRUPT : succ;
+        const uint32_t slot_abs = ring_write_step(ring, rp.C, rp.E, eps, succ_rec != RL_SUCC_CONTINUE);
+        if (slot_abs == 0xffffffffu) {
+          full = true;  // WriteExperienceError::Full: a single episode longer than the lane's capacity
+          succ = RL_SUCC_CONTINUE;
+        } else {
+          const size_t o_rec = (size_t)lc.ii * rp.C + slot_abs % rp.C;
+          if (writer) {
+            ReplayRec rec;
+#pragma unroll
+            for (int d = 0; d < 5; ++d) rec.x[d] = d < D ? f[d < D ? d : 0] : 0.0f;
+            rec.reward = reward;
+            rec.af = (uint32_t)a | (uint32_t)succ_rec << 8;
+            rec_store(rp.rec + o_rec, rec);
+            if constexpr (D > 5)
+              rp.hi[o_rec] = make_float4(f[5], D > 6 ? f[D > 6 ? 6 : 0] : 0.0f, D > 7 ? f[D > 7 ? 7 : 0] : 0.0f, 0.0f);
+          }
+          if (succ_rec == RL_SUCC_INTERRUPT) {
+            Env::template features<D>(c, s, f);
+            if (writer) {
+#pragma unroll
+              for (int d = 0; d < D; ++d) rp.next[o_rec].x[d] = f[d];
+            }
+          }
+          if (writer) flags_out[(size_t)t * n + lc.ii] = (uint8_t)succ_rec;
+          if (succ != RL_SUCC_CONTINUE) Env::reset(c, s, glane);
+        }
+      }
+      succ_of[col] = (uint8_t)succ;
+    }
+    __syncthreads();
+    fresh = succ_of[col] != RL_SUCC_CONTINUE || (hold && fresh);
+  }
+  if (!writer) return;
+  if (full) *rp.error = 1;
+  ring_store(rp, lc.ii, ring);
+  rp.actor_pos[lc.ii] = rng.pos;
+  Env::store(st, lc.ii, s);
 }
 
 // Reverse scan over the record of the last training forward: dz [A][B] -> d loss / d pre-activation planes
@@ -796,7 +912,9 @@ inline uint32_t cdiv_k(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) /
 }  // namespace
 
 void stack_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
-  RL_REQUIRE(rl_module_is_recurrent(mod->kind) && mod->lane_kernels(), "not a module of the lane-per-thread kernels");
+  // (any recurrent chain: the modules of rl_mlp::lane_kernels always come here, and a recurrent DQN agent brings every
+  // chain — a single-layer chain's flat order [W_ih, W_hh, b_ih, b_hh, head] IS the stacked order at L = 1, stack_net)
+  RL_REQUIRE(rl_module_is_recurrent(mod->kind), "not a recurrent module");
   RL_REQUIRE(mod->in_dim == t->d.D, "module input width does not match the trajectory");
   SeqDev &q = t->seq;
   SeqDev::Stack &k = q.stack;
@@ -920,6 +1038,50 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
 #undef STEP_OUT
 #undef STEP
   });
+}
+
+void launch_stack_collect_dqn(rl_env *env, const rl_mlp *qnet, rl_traj *roll, const ReplayDev &rp, uint32_t T,
+                              uint64_t p_int, int always_explore, uint8_t *d_flags) {
+  ProfScope ps(env->eng, RL_K_ROLLOUT);
+  RL_REQUIRE(rl_module_is_recurrent(qnet->kind) && qnet->out_dim == 2 && env->A == 2 && qnet->in_dim == env->D,
+             "recurrent DQN collection: a two-output recurrent chain over the env's features");
+  RL_REQUIRE(roll->d.n == rp.N && roll->d.D == env->D, "recurrent DQN collection: workspace of another shape");
+  const StackNet net = stack_net(qnet, qnet->d_params);
+  const StackWs ws = stack_ws(roll);
+  const dim3 grid(cdiv_k(rp.N, SL)), blk(SL * SW);
+  const size_t xstride = (size_t)(roll->d.T + 1) * roll->d.n;
+  const bool lstm = qnet->kind == RL_MODULE_LSTM_MLP, lin = qnet->linear_tail(), cartpole = env->kind == RL_ENV_CARTPOLE;
+  const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
+  if (!(cartpole ? env->D == 4 || env->D == 5 : index_env && env->D >= 4 && env->D <= 8))
+    throw RlError(RL_ERR_UNSUPPORTED, "recurrent DQN collection: CartPole lanes of 4 or 5 features, index-env lanes of 4..8");
+#define COLLECT(CELL, LIN, ENV, DD)                                                                                      \
+  hipLaunchKernelGGL((k_stack_collect_dqn<CELL, ENV, DD, LIN>), grid, blk, 0, env->eng->stream, net, ws, env->dev,      \
+                     env->st, rp, roll->d.obs, xstride, T, p_int, always_explore, d_flags, env->t_global)
+#define COLLECT_ENV(CELL, LIN)                            \
+  do {                                                    \
+    if (cartpole) {                                       \
+      if (env->D == 5) COLLECT(CELL, LIN, CartPoleOps, 5); \
+      else COLLECT(CELL, LIN, CartPoleOps, 4);            \
+    } else {                                              \
+      switch (env->D) {                                   \
+        case 4: COLLECT(CELL, LIN, IndexOps, 4); break;   \
+        case 5: COLLECT(CELL, LIN, IndexOps, 5); break;   \
+        case 6: COLLECT(CELL, LIN, IndexOps, 6); break;   \
+        case 7: COLLECT(CELL, LIN, IndexOps, 7); break;   \
+        default: COLLECT(CELL, LIN, IndexOps, 8); break;  \
+      }                                                   \
+    }                                                     \
+  } while (0)
+  if (lstm) {
+    if (lin) COLLECT_ENV(LSTM, true);
+    else COLLECT_ENV(LSTM, false);
+  } else {
+    if (lin) COLLECT_ENV(GRU, true);
+    else COLLECT_ENV(GRU, false);
+  }
+#undef COLLECT_ENV
+#undef COLLECT
+  RL_HIP_CHECK(hipGetLastError());
 }
 
 // dz [A][B] and the record of the last training forward -> vec[0..P): the reverse scan, then one weight-gradient
