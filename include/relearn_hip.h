@@ -739,7 +739,8 @@ int32_t rl_dqn_config_default(rl_dqn_config *cfg);
  * or 5 features collects in the fused kernel (the whole horizon in one launch); every other module, and every env of 6..8
  * features, collects step by step on the per-layer kernels.  Steps of 6..8 features keep features 5..7 in a second
  * 16-byte record beside the 32-byte one (the replay fields read the same: RL_REPLAY_OBS is [obs_dim][C][N]).
- * Refused: more than two actions (a bandit of >= 3 arms, MemoryGame(>= 3, h)) -> RL_ERR_UNSUPPORTED; a module that does
+ * Refused: more than two actions (a bandit of >= 3 arms, MemoryGame(>= 3, h)) -> RL_ERR_UNSUPPORTED (rl_dqn_create_finite
+ * builds them); a module that does
  * not match the env's (obs_dim, n_actions) -> RL_ERR_INVALID_ARGUMENT; an env kind or feature count outside the table ->
  * RL_ERR_UNSUPPORTED with a message that names it.  No env is ever collected by another env's lane code. */
 int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out);
@@ -766,6 +767,27 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
  * more than one rank -> RL_ERR_UNSUPPORTED before anything is changed; rl_actor_to_cbor of a recurrent DqnActor ->
  * RL_ERR_UNSUPPORTED. */
 int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out);
+/* DqnConfig over any finite action space (dqn.rs:75-86, AS: FiniteSpace): 2..8 actions, a feed-forward or a recurrent
+ * action-value module.  The returned handle is an rl_dqn: every rl_dqn_* entry point and rl_summary_push_dqn take it.
+ *   actor    (dqn.rs:360-379) gen_bool(eps); an exploring step returns action_space.sample(rng) = gen_range(0..n_actions)
+ *            from the lane's sequential actor stream (rand 0.8.5 UniformInt::sample_single: widening multiply, retry on
+ *            rejection), a greedy step argmax — the first maximal of the n_actions outputs.  A recurrent module's state is
+ *            held over an exploring step, as in rl_dqn_create_recurrent.
+ *   targets  RL_DQN_TARGET_ONE_STEP_TD takes amax(-1) over the n_actions outputs (dqn.rs:300-309), `gamma * vnext`, then the
+ *            add; the loss is mse_loss on the taken action's value (dqn.rs:316-326).
+ * What builds:
+ *   two actions                               what rl_dqn_create builds for a feed-forward module and rl_dqn_create_recurrent
+ *                                             for a recurrent one, through them: same kernels, same bytes, same refusals
+ *   RL_ENV_BANDIT of 3..8 arms                5 observation features
+ *   RL_ENV_MEMORY, MemoryGame(k >= 3, h)      k + h, + 1 under a visible step limit: 4..8 (6..8: the second record array)
+ * with any feed-forward module of obs_dim inputs and n_actions outputs (rl_mlp_create_layers: always the per-layer
+ * kernels, collection step by step), or any recurrent chain of n_actions outputs from rl_rnn_chain_create (GRU or LSTM, Mlp
+ * or Linear tail, 1..4 layers: collection is one launch per horizon).
+ * Refused, by this entry point's name: RL_ENV_META_BANDIT lanes -> RL_ERR_UNSUPPORTED; a module that does not match the
+ * env's (obs_dim, n_actions) -> RL_ERR_INVALID_ARGUMENT (more than eight actions cannot be constructed upstream).
+ * rl_dqn_update of a recurrent agent on more than one rank -> RL_ERR_UNSUPPORTED before anything is changed;
+ * rl_actor_to_cbor of a recurrent DqnActor -> RL_ERR_UNSUPPORTED. */
+int32_t rl_dqn_create_finite(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out);
 int32_t rl_dqn_destroy(rl_dqn *dqn);
 /* ExplorationRateSchedule::exploration_rate(global_steps, mode) (schedules.rs:35-45); training = 0 -> 0.0 */
 int32_t rl_dqn_exploration_rate(const rl_dqn *dqn, int32_t training, double *rate_out);

@@ -64,7 +64,7 @@ ABI_SYMBOLS = [
     "rl_ppo_config_default", "rl_ppo_update", "rl_reinforce_update", "rl_reward_to_go",
     "rl_actor_to_cbor", "rl_module_from_cbor", "rl_tensor_def_to_cbor", "rl_tensor_def_from_cbor",
     "rl_indexed_type_space_to_cbor",
-    "rl_dqn_config_default", "rl_dqn_create", "rl_dqn_create_recurrent", "rl_dqn_destroy", "rl_dqn_exploration_rate",
+    "rl_dqn_config_default", "rl_dqn_create", "rl_dqn_create_recurrent", "rl_dqn_create_finite", "rl_dqn_destroy", "rl_dqn_exploration_rate",
     "rl_dqn_min_update_size", "rl_dqn_collect", "rl_dqn_update", "rl_dqn_replay_field_bytes", "rl_dqn_replay_read",
     "rl_dqn_minibatch_sample", "rl_dqn_minibatch_read", "rl_dqn_minibatch_gradient", "rl_dqn_agent_rng_pos",
     "rl_chain_tabular_q_train", "rl_chain_tabular_q_eval",
@@ -1121,6 +1121,15 @@ class RecurrentDqn(Dqn):
     RnnMlp, RnnLinear, RnnChain of two outputs).  The interface of `Dqn`; an exploring step holds the lane's recurrent
     state, the update runs whole sampled episodes from the zero state (include/relearn_hip.h, rl_dqn_create_recurrent)."""
     _create = "rl_dqn_create_recurrent"
+
+
+class FiniteDqn(Dqn):
+    """`DqnConfig::build_agent` over any finite action space (dqn.rs:75-86, AS: FiniteSpace): 2..8 actions, `qnet` a
+    feed-forward module of (obs_dim -> n_actions) or a recurrent chain of n_actions outputs (RnnChain).  Two actions: what
+    `Dqn` / `RecurrentDqn` build.  More: bandit lanes of 3..8 arms and MemoryGame(k >= 3, h) lanes; an exploring step
+    draws gen_range(0..n_actions), a greedy step takes the first maximal output (include/relearn_hip.h,
+    rl_dqn_create_finite)."""
+    _create = "rl_dqn_create_finite"
 
 
 class MeanVariance(C.Structure):

@@ -159,7 +159,46 @@ int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const r
   });
 }
 
-// what the two constructors share: the configuration's checks, the replay store, the sampler's lists and the minibatch
+// DqnConfig over any finite action space (dqn.rs:75-86, AS: FiniteSpace; the actor's action_space.sample(rng) and argmax,
+// dqn.rs:360-379; the one-step TD target's amax(-1), dqn.rs:300-309).  Two actions: what the two constructors above build,
+// through them.  3..8 actions: the index-env lanes that have them — the bandit of 3..8 arms, MemoryGame(k >= 3, h) — with
+// a feed-forward module (always on the per-layer kernels: step-wise collection) or a recurrent chain of one output per
+// action (rl_rnn_chain_create: k_stack_collect_dqn<.., NA>).
+int32_t rl_dqn_create_finite(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out) {
+  if (env && qnet && env->A <= 2 && qnet->out_dim <= 2 && env->kind != RL_ENV_META_BANDIT)
+    return rl_module_is_recurrent(qnet->kind) ? rl_dqn_create_recurrent(env, qnet, opt, cfg, out)
+                                              : rl_dqn_create(env, qnet, opt, cfg, out);
+  return guarded(env ? env->eng : nullptr, [&] {
+    RL_REQUIRE(env && qnet && opt && cfg && out, "rl_dqn_create_finite: NULL argument");
+    *out = nullptr;
+    rl_engine *e = env->eng;
+    RL_REQUIRE(qnet->eng == e && opt->eng == e, "rl_dqn_create_finite: handles belong to different engines");
+    RL_REQUIRE(opt->mod == qnet, "rl_dqn_create_finite: optimizer does not belong to the action-value module");
+    if (env->kind == RL_ENV_META_BANDIT)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite is not built for RL_ENV_META_BANDIT lanes");
+    RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A,
+               "rl_dqn_create_finite: action-value module does not match the env's (obs_dim, n_actions)");
+    // (env->A > 2 from here on: the two-action envs went to the older constructors)
+    if (env->kind != RL_ENV_MEMORY && env->kind != RL_ENV_BANDIT)
+      throw RlError(RL_ERR_UNSUPPORTED,
+                    "rl_dqn_create_finite over more than two actions: MemoryGame and bandit lanes");
+    if (env->A > 8) throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite: 2..8 actions");
+    if (env->D < RL_ENV_MIN_OBS_DIM || env->D > RL_TRAJ_MAX_OBS_DIM)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite on index-env lanes: 4..8 observation features");
+    const bool recurrent = rl_module_is_recurrent(qnet->kind);
+    if (recurrent) {
+      if (!qnet->lane_kernels())
+        throw RlError(RL_ERR_UNSUPPORTED,
+                      "rl_dqn_create_finite: a recurrent module of more than two outputs comes from rl_rnn_chain_create");
+    } else if (qnet->kind != RL_MODULE_MLP || !qnet->general) {
+      throw RlError(RL_ERR_UNSUPPORTED,
+                    "rl_dqn_create_finite: a feed-forward module of more than two outputs runs the per-layer kernels");
+    }
+    dqn_build(env, qnet, opt, cfg, out, recurrent);
+  });
+}
+
+// what the constructors share: the configuration's checks, the replay store, the sampler's lists and the minibatch
 // workspace (+ the recurrent agent's two trajectory-shaped workspaces)
 static void dqn_build(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out, bool recurrent) {
   rl_engine *e = env->eng;
@@ -183,6 +222,7 @@ static void dqn_build(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
   q->opt = opt;
   q->cfg = *cfg;
   q->cfg.episode_capacity = E;
+  q->A = env->A;
   DevMem &mem = q->mem;
   q->rp = replay_alloc(e, mem, (uint32_t)N, (uint32_t)cfg->buffer_capacity, (uint32_t)E, env->D);
   q->d_agent_pos = mem.alloc<uint64_t>(1);
@@ -199,6 +239,8 @@ static void dqn_build(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
   q->d_counts = mem.alloc<DqnCountsDev>(nb);
   RL_HIP_CHECK(hipMemsetAsync(q->d_counts, 0, nb * sizeof(DqnCountsDev), e->stream));
   q->mb = traj_alloc(e, q->max_steps_mb, 1, env->D, true);
+  // (dz: one plane per action, sized while the workspace still has its allocation's sample count)
+  traj_ensure_action_planes(q->mb, q->A);
   {  // the fused step's range guard (bf16_tile.hpp): the words hold the magnitude range of every observation the
      // collection kernel has put into the store so far (k_rollout_dqn folds what it writes, one fold per wave
      // and launch; never reset, so they bound every minibatch drawn from the store from outside).  Rounds 3-5 kept fixed bounds here, 2^-64 .. 2^16,
@@ -272,7 +314,7 @@ int32_t rl_dqn_collect(rl_dqn *q, uint64_t horizon, rl_dqn_collect_stats *stats)
     if (q->recurrent) {
       launch_stack_collect_dqn(q->env, q->qnet, q->roll, q->rp, (uint32_t)horizon, p_int, always, q->d_flags);
     } else if (q->qnet->general) {
-      if (!q->d_q) q->d_q = q->mem.alloc<float>(2 * (size_t)q->rp.N);
+      if (!q->d_q) q->d_q = q->mem.alloc<float>((size_t)q->A * q->rp.N);
       launch_rollout_dqn_general(q->env, q->qnet, q->mb, q->d_q, q->rp, (uint32_t)horizon, p_int, always, q->d_flags);
     } else {
       launch_rollout_dqn(q->env, q->qnet, q->rp, (uint32_t)horizon, p_int, always, q->d_flags, q->mb->d.range);
@@ -402,7 +444,7 @@ static void rdqn_build_minibatch(rl_dqn *q, uint32_t k, const DqnCountsDev &c, u
   mem.ensure(s->d.flag, B);
   mem.ensure(s->d.reward, B);
   mem.ensure(s->d.adv, B);
-  mem.ensure(s->dz, 2 * B);
+  mem.ensure(s->dz, (uint64_t)q->A * B);
   traj_plan(s, B);
   stack_ensure(s, q->qnet, true);
   const DqnSeqEps eps = rdqn_eps(q, k);
@@ -410,7 +452,7 @@ static void rdqn_build_minibatch(rl_dqn *q, uint32_t k, const DqnCountsDev &c, u
   q->seq_fwd_epoch = 0;
   if (td) {  // under no_grad with the parameters of this optimisation step (dqn.rs:299-311): the forward the gradient reuses
     rdqn_forward(q, true);
-    launch_dqn_seq_td_targets(s, eps, q->cfg.discount_factor, mb->d.adv);
+    launch_dqn_seq_td_targets(s, eps, q->A, q->cfg.discount_factor, mb->d.adv);
   }
   q->last_n_eps = c.n_eps;
   q->last_n_steps = c.n_steps;
@@ -425,7 +467,7 @@ static void rdqn_gradient(rl_dqn *q, rl_adam *step_opt, int loss_slot) {
   rl_traj *s = q->seq;
   const uint32_t P = (uint32_t)q->qnet->P;
   if (q->seq_fwd_epoch != q->eng->call_epoch) rdqn_forward(q, false);
-  launch_dqn_seq_terms(s, rdqn_eps(q, q->last_batch_index), q->last_total_steps);
+  launch_dqn_seq_terms(s, rdqn_eps(q, q->last_batch_index), q->A, q->last_total_steps);
   launch_stack_backward(s, q->qnet, nullptr);
   launch_reduce(s, P, false, true, 0, s->nbB);
   if (step_opt) {
@@ -454,9 +496,9 @@ static void dqn_build_minibatch(rl_dqn *q, uint32_t k, const DqnCountsDev &c, ui
     launch_dqn_build_all(q->eng, q->rp, 1, c.n_eps, q->max_eps, q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o,
                          q->d_ep_off + o, q->d_counts + k, mb->d.obs, 0, mb->d.action, mb->d.adv, 0,
                          q->cfg.discount_factor, mb->d.flag);
-    q->mem.ensure(q->d_q_next, 2ull * q->max_steps_mb);  // (c.n_steps <= max_steps_mb: allocated once)
+    q->mem.ensure(q->d_q_next, (uint64_t)q->A * q->max_steps_mb);  // (c.n_steps <= max_steps_mb: allocated once)
     launch_gen_forward(mb, q->qnet, mb->d.obs + c.n_steps, (size_t)2 * c.n_steps, c.n_steps, q->d_q_next);
-    launch_dqn_td_targets(q->eng, mb->d.adv, mb->d.flag, q->d_q_next, c.n_steps, q->cfg.discount_factor);
+    launch_dqn_td_targets(q->eng, mb->d.adv, mb->d.flag, q->d_q_next, c.n_steps, q->A, q->cfg.discount_factor);
     return;
   }
   launch_dqn_build_minibatch(q->eng, q->rp, c.n_eps, q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o,

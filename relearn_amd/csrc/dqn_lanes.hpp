@@ -31,22 +31,54 @@ __device__ __forceinline__ void rec_load_hi(const ReplayDev &rp, size_t o, float
 }
 
 // DqnActor::act (dqn.rs:360-379) from the lane's sequential actor stream:
-//   if rng.gen_bool(eps) { action_space.sample(rng) = gen_range(0..2) } else { argmax_a Q(obs)[a] }
-// The draws are here; the greedy branch is the kernel's (the first maximal index of its action values).
+//   if rng.gen_bool(eps) { action_space.sample(rng) = gen_range(0..A) } else { argmax_a Q(obs)[a] }
+// The draws are here, and the rule of the greedy branch (first_max_index); the action values are the kernel's.
 template <class Rng>
 __device__ __forceinline__ bool dqn_explores(Rng &rng, uint64_t p_int, int always_explore) {
   bool explore = always_explore != 0;
   if (!explore) explore = rl_bernoulli_from_u64(rng.next_u64(), p_int) != 0;  // Bernoulli::sample (rl_chacha.h)
   return explore;
 }
-template <class Rng>
+template <int A, class Rng>
 __device__ __forceinline__ int dqn_random_action(Rng &rng) {
-  // UniformInt::sample_single(0, 2): widening multiply by 2, zone = (2 << 62) - 1
+  // FiniteSpace::sample = gen_range(0..A): UniformInt::sample_single(0, A) of rand 0.8.5 for u64 — a widening multiply
+  // by A, accepted when the low half is within zone = (A << A.leading_zeros()) - 1, else the next word (lane_gen_range,
+  // env_lanes.hpp, is this rule on the env stream).  A = 2: lo = v << 1, hi = v >> 63, zone = (2 << 62) - 1.
+  static_assert(A >= 2 && A <= 8, "finite action spaces of 2..8 actions");
+  constexpr uint64_t range = (uint64_t)A;
+  constexpr uint64_t zone = (range << __builtin_clzll(range)) - 1;
   for (;;) {
     const uint64_t v = rng.next_u64();
-    const uint64_t lo = v << 1, hi = v >> 63;
-    if (lo <= 0x7fffffffffffffffull) return (int)hi;
+    uint64_t lo, hi;
+    if constexpr ((range & (range - 1)) == 0) {  // a power of two: the product's halves are shifts (A = 2: the code as it was)
+      constexpr int sh = __builtin_ctzll(range);
+      lo = v << sh, hi = v >> (64 - sh);
+    } else {
+      lo = v * range, hi = __umul64hi(v, range);
+    }
+    if (lo <= zone) return (int)hi;
   }
+}
+
+// argmax(-1) of A action values: the first maximal index (a later value replaces the choice only when strictly larger),
+// and amax(-1) with it.  An unrolled compare-select chain: nothing is indexed dynamically.  A = 2: `z[1] > z[0] ? 1 : 0`
+// and `z[1] > z[0] ? z[1] : z[0]`.
+template <int A>
+__device__ __forceinline__ int first_max_index(const float (&z)[A], float &zmax) {
+  int best = 0;
+  zmax = z[0];
+#pragma unroll
+  for (int a = 1; a < A; ++a) {
+    const bool up = z[a] > zmax;
+    best = up ? a : best;
+    zmax = up ? z[a] : zmax;
+  }
+  return best;
+}
+template <int A>
+__device__ __forceinline__ int first_max_index(const float (&z)[A]) {
+  float zmax;
+  return first_max_index<A>(z, zmax);
 }
 
 // the lane's episode table; `writer` false: a thread that follows the lane (it reads the table, the lane's writer writes)

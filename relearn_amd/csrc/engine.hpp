@@ -482,7 +482,8 @@ struct rl_dqn {
   std::vector<hipEvent_t> draw_events;
   hipEvent_t main_event = nullptr;
   DqnCountsDev *h_counts = nullptr;  // pinned, [K]
-  float *d_q = nullptr, *d_q_next = nullptr;  // module outputs of a collection step [2][N] / at a minibatch's successor
+  uint32_t A = 2;                    // the env's action count = the module's outputs (rl_dqn_create_finite: 2..8)
+  float *d_q = nullptr, *d_q_next = nullptr;  // module outputs of a collection step [A][N] / at a minibatch's successor
                                               // observations (action-value modules on the per-layer kernels)
   float *snap = nullptr;             // parameters + optimiser state slots + step count as of the start of a pipelined update
   // ... `mb` then points into them (the last minibatch stays readable); its own arrays, for the one-at-a-time builder:

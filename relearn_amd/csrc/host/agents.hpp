@@ -1149,10 +1149,11 @@ std::unique_ptr<DqnAgent> build_dqn_agent(const DqnConfig<VB, OC> &c, EnvLanes &
   d.discount_factor = (float)env.discount_factor();
   std::memcpy(d.agent_key, agent_key, sizeof(d.agent_key));
   // a feed-forward module, or a recurrent chain: the actor then carries the module's state through an episode and the
-  // update runs whole sampled episodes (relearn_hip.h, rl_dqn_create_recurrent)
-  check((builds_recurrent_module<VB>::value ? rl_dqn_create_recurrent : rl_dqn_create)(
-            env.handle(), a->q_->handle(), a->opt_->handle(), &d, &a->dqn_),
-        eng.handle());
+  // update runs whole sampled episodes (relearn_hip.h, rl_dqn_create_recurrent); an env of more than two actions (AS:
+  // FiniteSpace, dqn.rs:75-86) builds through rl_dqn_create_finite, either kind of module
+  auto *create = env.num_actions() > 2 ? rl_dqn_create_finite
+                                       : (builds_recurrent_module<VB>::value ? rl_dqn_create_recurrent : rl_dqn_create);
+  check(create(env.handle(), a->q_->handle(), a->opt_->handle(), &d, &a->dqn_), eng.handle());
   return a;
 }
 

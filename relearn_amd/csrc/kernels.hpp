@@ -116,11 +116,12 @@ bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float
 void launch_rollout_dqn(rl_env *env, const rl_mlp *qnet, const ReplayDev &rp, uint32_t T, uint64_t p_int,
                         int always_explore, uint8_t *d_flags, uint32_t *d_range = nullptr);
 // an action-value module of any shape (rl_mlp::general): one launch sequence per step; `ws` lends the layer kernels their
-// workspace, d_q [2][n] receives the module's outputs of every step
+// workspace, d_q [n_actions][n] receives the module's outputs of every step (n_actions: the env's, 2..8)
 void launch_rollout_dqn_general(rl_env *env, const rl_mlp *qnet, rl_traj *ws, float *d_q, const ReplayDev &rp, uint32_t T,
                                 uint64_t p_int, int always_explore, uint8_t *d_flags);
+// d_target += gamma * amax over the n_actions planes of d_q_next [n_actions][n], 0 beyond a Terminate
 void launch_dqn_td_targets(rl_engine *eng, float *d_target, const uint8_t *d_flag, const float *d_q_next, uint32_t n,
-                           float gamma);
+                           uint32_t n_actions, float gamma);
 struct AgentKey { uint32_t w[8]; };
 void launch_dqn_sample(rl_engine *eng, hipStream_t stream, const ReplayDev &rp, const AgentKey &key, uint64_t *d_agent_pos,
                        uint32_t minibatch_steps, uint32_t max_eps, uint32_t *d_lane, uint32_t *d_start,
@@ -149,9 +150,9 @@ void launch_dqn_longest(rl_engine *eng, const uint32_t *d_len, uint32_t max_eps,
 // ring -> workspace planes; targets from `d_given` (episode-after-episode order), or NULL: the rewards
 void launch_dqn_build_seq(rl_traj *seq, const ReplayDev &rp, const DqnSeqEps &ep, const float *d_given);
 // one-step TD targets from seq.out / seq.succ -> the workspace's targets and `d_compact` (episode-after-episode order)
-void launch_dqn_seq_td_targets(rl_traj *seq, const DqnSeqEps &ep, float gamma, float *d_compact);
+void launch_dqn_seq_td_targets(rl_traj *seq, const DqnSeqEps &ep, uint32_t n_actions, float gamma, float *d_compact);
 // seq.out, targets -> dz (zero on padding) and the loss sum in slab B
-void launch_dqn_seq_terms(rl_traj *seq, const DqnSeqEps &ep, uint64_t B_total);
+void launch_dqn_seq_terms(rl_traj *seq, const DqnSeqEps &ep, uint32_t n_actions, uint64_t B_total);
 // kernels_seq_stack.hip: all `T` collection steps of a recurrent action-value module in one launch; `roll` lends the
 // per-lane states and the observation planes ([D][2][N])
 void launch_stack_collect_dqn(rl_env *env, const rl_mlp *qnet, rl_traj *roll, const ReplayDev &rp, uint32_t T,

@@ -12,6 +12,7 @@
 #include "dqn_lanes.hpp"
 #include "env_lanes.hpp"
 #include "kernels.hpp"
+#include "policy_terms.hpp"
 #include "replay.hpp"
 
 // T env-actor steps per lane with the DQN actor (dqn_explores / dqn_random_action, else the greedy action); every step is
@@ -56,7 +57,7 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_dqn(CartPoleDev c, EnvStateDe
     Env::template features<D>(c, s, f);
     int a;
     if (dqn_explores(rng, p_int, always_explore)) {
-      a = dqn_random_action(rng);
+      a = dqn_random_action<2>(rng);
     } else {
       float z[2];
       mlp_forward_group_lds<D, G>(pk, H, g, f, z);
@@ -114,9 +115,9 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_dqn(CartPoleDev c, EnvStateDe
 // the fused kernel's stream discipline, ring bookkeeping and horizon rule (above), one thread per lane.  `word`: the
 // global step (t_global + t).  Features 5..7 of an observation wider than the 32-byte record go to the second record array
 // (ReplayDev::hi).
-template <class Env, int D, int BLOCK>
+template <class Env, int D, int BLOCK, int A>
 __global__ void __launch_bounds__(BLOCK) k_dqn_lane_step(CartPoleDev c, EnvStateDev st, ReplayDev rp,
-                                                         const float *__restrict__ q_values /* [2][n] */, uint64_t p_int,
+                                                         const float *__restrict__ q_values /* [A][n] */, uint64_t p_int,
                                                          int always_explore, int last_step,
                                                          uint8_t *__restrict__ flags_row, uint64_t word) {
   __shared__ uint32_t words[16 * BLOCK];
@@ -132,8 +133,14 @@ __global__ void __launch_bounds__(BLOCK) k_dqn_lane_step(CartPoleDev c, EnvState
   float f[D];
   Env::template features<D>(c, s, f);
   int a;
-  if (dqn_explores(rng, p_int, always_explore)) a = dqn_random_action(rng);
-  else a = q_values[n + i] > q_values[i] ? 1 : 0;  // argmax: first maximal index
+  if (dqn_explores(rng, p_int, always_explore)) {
+    a = dqn_random_action<A>(rng);
+  } else {
+    float z[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) z[q] = q_values[(size_t)q * n + i];
+    a = first_max_index<A>(z);  // argmax: first maximal index
+  }
   float reward;  // (the step, its record and the horizon rule as in the fused kernel)
   const int succ = Env::step(c, s, a, lane, word, reward);
   const bool horizon_cut = succ == RL_SUCC_CONTINUE && last_step != 0;
@@ -166,14 +173,17 @@ __global__ void __launch_bounds__(BLOCK) k_dqn_lane_step(CartPoleDev c, EnvState
 // one-step TD targets from the module's outputs at the successor observations (the gather left rewards where the
 // targets go and the successor codes in `flag`): r + gamma * max_a Q(s'), 0 beyond a Terminate — the arithmetic of
 // k_dqn_build_minibatch (amax, `scalar * tensor`, then `tensor + tensor`)
+template <int A>
 __global__ void k_dqn_td_targets(float *__restrict__ tgt, const uint8_t *__restrict__ flag,
-                                 const float *__restrict__ q_next /* [2][n] */, uint32_t n, float gamma) {
+                                 const float *__restrict__ q_next /* [A][n] */, uint32_t n, float gamma) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float vnext = 0.0f;
   if (flag[i] != RL_SUCC_TERMINATE) {
-    const float z0 = q_next[i], z1 = q_next[n + i];
-    vnext = z1 > z0 ? z1 : z0;
+    float z[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) z[q] = q_next[(size_t)q * n + i];
+    first_max_index<A>(z, vnext);
   }
   const float dn = gamma * vnext;
   tgt[i] = tgt[i] + dn;
@@ -647,6 +657,21 @@ static void dqn_features_dispatch(uint32_t D, Go &&go) {
   }
 }
 
+// ... and the kernels built per action count (FiniteSpace of 2..8 actions: rl_dqn_create_finite)
+template <class Go>
+static void dqn_actions_dispatch(uint32_t A, Go &&go) {
+  switch (A) {
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    case 3: go(std::integral_constant<int, 3>{}); break;
+    case 4: go(std::integral_constant<int, 4>{}); break;
+    case 5: go(std::integral_constant<int, 5>{}); break;
+    case 6: go(std::integral_constant<int, 6>{}); break;
+    case 7: go(std::integral_constant<int, 7>{}); break;
+    case 8: go(std::integral_constant<int, 8>{}); break;
+    default: throw RlError(RL_ERR_UNSUPPORTED, "DQN kernels: 2..8 actions");
+  }
+}
+
 void launch_rollout_dqn(rl_env *env, const rl_mlp *qnet, const ReplayDev &rp, uint32_t T, uint64_t p_int,
                         int always_explore, uint8_t *d_flags, uint32_t *d_range) {
   ProfScope ps(env->eng, RL_K_ROLLOUT);
@@ -683,23 +708,40 @@ void launch_rollout_dqn_general(rl_env *env, const rl_mlp *qnet, rl_traj *ws, fl
   for (uint32_t t = 0; t < T; ++t) {
     if (!always_explore) {  // (a collection that always explores never reads the module)
       launch_env_observe(env, env->d_obs);                          // [D][n]
-      launch_gen_forward(ws, qnet, env->d_obs, (size_t)n, n, d_q);  // [2][n]
+      launch_gen_forward(ws, qnet, env->d_obs, (size_t)n, n, d_q);  // [A][n]
     }
     dqn_env_dispatch<8>(env, "step-wise DQN collection: 4..8 observation features", [&](auto ops, auto d) {
-      hipLaunchKernelGGL((k_dqn_lane_step<decltype(ops), decltype(d)::value, BLOCK>), dim3(cdiv_d(n, BLOCK)), dim3(BLOCK),
-                         0, env->eng->stream, env->dev, env->st, rp, d_q, p_int, always_explore, t + 1 == T ? 1 : 0,
-                         d_flags + (size_t)t * n, env->t_global + t);
+      using Env = decltype(ops);
+      constexpr int D = decltype(d)::value;
+      // more than two actions: the index-env lanes alone (MemoryGame(k >= 3, h), the bandit of 3..8 arms)
+      if constexpr (std::is_same<Env, IndexOps>::value) {
+        if (env->A > 2) {
+          dqn_actions_dispatch(env->A, [&](auto na) {
+            constexpr int A = decltype(na)::value;
+            if constexpr (A > 2)
+              hipLaunchKernelGGL((k_dqn_lane_step<Env, D, BLOCK, A>), dim3(cdiv_d(n, BLOCK)), dim3(BLOCK), 0,
+                                 env->eng->stream, env->dev, env->st, rp, d_q, p_int, always_explore, t + 1 == T ? 1 : 0,
+                                 d_flags + (size_t)t * n, env->t_global + t);
+          });
+          return;
+        }
+      }
+      hipLaunchKernelGGL((k_dqn_lane_step<Env, D, BLOCK, 2>), dim3(cdiv_d(n, BLOCK)), dim3(BLOCK), 0, env->eng->stream,
+                         env->dev, env->st, rp, d_q, p_int, always_explore, t + 1 == T ? 1 : 0, d_flags + (size_t)t * n,
+                         env->t_global + t);
     });
   }
   RL_HIP_CHECK(hipGetLastError());
 }
 
 void launch_dqn_td_targets(rl_engine *eng, float *d_target, const uint8_t *d_flag, const float *d_q_next, uint32_t n,
-                           float gamma) {
+                           uint32_t n_actions, float gamma) {
   ProfScope ps(eng, RL_K_VALUES);
   if (n == 0) return;
-  hipLaunchKernelGGL(k_dqn_td_targets, dim3(cdiv_d(n, 256)), dim3(256), 0, eng->stream, d_target, d_flag, d_q_next, n,
-                     gamma);
+  dqn_actions_dispatch(n_actions, [&](auto na) {
+    hipLaunchKernelGGL(k_dqn_td_targets<decltype(na)::value>, dim3(cdiv_d(n, 256)), dim3(256), 0, eng->stream, d_target,
+                       d_flag, d_q_next, n, gamma);
+  });
 }
 
 void launch_dqn_build_minibatch(rl_engine *eng, const ReplayDev &rp, uint32_t n_eps, const uint32_t *d_lane,
@@ -1069,6 +1111,7 @@ __global__ void __launch_bounds__(256) k_dqn_build_seq(ReplayDev rp, DqnSeqEps e
 // plus one slot — the successor observation of an Interrupt (succ) — so V_ext[t + 1] = amax of the next slot's outputs,
 // of the successor outputs after an Interrupt, 0 after a Terminate; target = r + gamma * V_ext[t + 1] with
 // k_dqn_td_targets' arithmetic (`scalar * tensor`, then add).  Also into the episode-after-episode array (`compact`).
+template <int A>
 __global__ void __launch_bounds__(256) k_dqn_seq_td_targets(TrajDev tr, DqnSeqEps ep, const float *__restrict__ out,
                                                             const float *__restrict__ succ, float gamma,
                                                             float *__restrict__ compact) {
@@ -1084,8 +1127,10 @@ __global__ void __launch_bounds__(256) k_dqn_seq_td_targets(TrajDev tr, DqnSeqEp
   // only keeps a corrupt store from reading past the planes)
   if (f != RL_SUCC_TERMINATE && (f == RL_SUCC_INTERRUPT || t + 1 < tr.T)) {
     const float *__restrict__ src = f == RL_SUCC_INTERRUPT ? succ + b : out + b + n;
-    const float z0 = src[0], z1 = src[B];
-    vnext = z1 > z0 ? z1 : z0;
+    float z[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) z[q] = src[(size_t)q * B];
+    first_max_index<A>(z, vnext);
   }
   const float dn = gamma * vnext;
   const float tgt = tr.reward[b] + dn;
@@ -1093,8 +1138,9 @@ __global__ void __launch_bounds__(256) k_dqn_seq_td_targets(TrajDev tr, DqnSeqEp
   compact[ep.off[e] + t] = tgt;
 }
 
-// the DQN terms over the output plane pair q [2][B] (PASS_DQN of policy_terms.hpp): dz[a] = [a == action] 2 (Q_a - target)
+// the DQN terms over the output planes q [A][B] (PASS_DQN of policy_terms.hpp): dz[a] = [a == action] 2 (Q_a - target)
 // / n_steps, zero on padding, and the f64 sum of (Q_a - target)^2 through slab B
+template <int A>
 __global__ void __launch_bounds__(256) k_dqn_seq_terms(TrajDev tr, DqnSeqEps ep, const float *__restrict__ q,
                                                        float *__restrict__ dz, double *__restrict__ slabB,
                                                        float two_over_B) {
@@ -1106,10 +1152,13 @@ __global__ void __launch_bounds__(256) k_dqn_seq_terms(TrajDev tr, DqnSeqEps ep,
     const uint32_t e = (uint32_t)(b % n), t = (uint32_t)(b / n);
     const bool valid = t < ep.len[e];
     const int act = tr.action[b];
-    const float dq = (act == 0 ? q[b] : q[B + b]) - tr.adv[b];
+    float z[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) z[a] = q[(size_t)a * B + b];
+    const float dq = select_action<A>(z, act) - tr.adv[b];
     const float g = dq * two_over_B;
-    dz[b] = valid && act == 0 ? g : 0.0f;
-    dz[B + b] = valid && act == 1 ? g : 0.0f;
+#pragma unroll
+    for (int a = 0; a < A; ++a) dz[(size_t)a * B + b] = valid && act == a ? g : 0.0f;
     if (valid) s0 += (double)(dq * dq);
   }
   const double t0 = block_sum<256>(s0, red);
@@ -1139,17 +1188,21 @@ void launch_dqn_build_seq(rl_traj *seq, const ReplayDev &rp, const DqnSeqEps &ep
   RL_HIP_CHECK(hipGetLastError());
 }
 
-void launch_dqn_seq_td_targets(rl_traj *seq, const DqnSeqEps &ep, float gamma, float *d_compact) {
+void launch_dqn_seq_td_targets(rl_traj *seq, const DqnSeqEps &ep, uint32_t n_actions, float gamma, float *d_compact) {
   ProfScope ps(seq->eng, RL_K_VALUES);
   const size_t B = (size_t)seq->d.T * seq->d.n;
-  hipLaunchKernelGGL(k_dqn_seq_td_targets, dim3(cdiv_d(B, 256)), dim3(256), 0, seq->eng->stream, seq->d, ep, seq->seq.out,
-                     seq->seq.succ, gamma, d_compact);
+  dqn_actions_dispatch(n_actions, [&](auto na) {
+    hipLaunchKernelGGL(k_dqn_seq_td_targets<decltype(na)::value>, dim3(cdiv_d(B, 256)), dim3(256), 0, seq->eng->stream,
+                       seq->d, ep, seq->seq.out, seq->seq.succ, gamma, d_compact);
+  });
   RL_HIP_CHECK(hipGetLastError());
 }
 
-void launch_dqn_seq_terms(rl_traj *seq, const DqnSeqEps &ep, uint64_t B_total) {
+void launch_dqn_seq_terms(rl_traj *seq, const DqnSeqEps &ep, uint32_t n_actions, uint64_t B_total) {
   ProfScope ps(seq->eng, RL_K_POLICY_PASS);
-  hipLaunchKernelGGL(k_dqn_seq_terms, dim3(seq->nbB), dim3(256), 0, seq->eng->stream, seq->d, ep, seq->seq.out, seq->dz,
-                     seq->slabB, 2.0f / (float)B_total);
+  dqn_actions_dispatch(n_actions, [&](auto na) {
+    hipLaunchKernelGGL(k_dqn_seq_terms<decltype(na)::value>, dim3(seq->nbB), dim3(256), 0, seq->eng->stream, seq->d, ep,
+                       seq->seq.out, seq->dz, seq->slabB, 2.0f / (float)B_total);
+  });
   RL_HIP_CHECK(hipGetLastError());
 }

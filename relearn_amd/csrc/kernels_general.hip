@@ -726,22 +726,18 @@ void launch_gen_policy_pass(rl_traj *t, const rl_mlp *m, int mode, const float *
     if (mode == PASS_INIT) TERMS(PASS_INIT, AA);     \
     else if (mode == PASS_EVAL) TERMS(PASS_EVAL, AA); \
     else if (mode == PASS_PPO) TERMS(PASS_PPO, AA);  \
+    else if (mode == PASS_DQN) TERMS(PASS_DQN, AA);  \
     else TERMS(PASS_JVP, AA);                        \
     break
-  if (mode == PASS_DQN) {
-    RL_REQUIRE(m->out_dim == 2, "the DQN terms are built for two actions");
-    TERMS(PASS_DQN, 2);
-  } else {
-    switch (m->out_dim) {
-      TERMS_A(2);
-      TERMS_A(3);
-      TERMS_A(4);
-      TERMS_A(5);
-      TERMS_A(6);
-      TERMS_A(7);
-      TERMS_A(8);
-      default: throw RlError(RL_ERR_UNSUPPORTED, "policy pass: categorical policies over 2..8 actions are built");
-    }
+  switch (m->out_dim) {
+    TERMS_A(2);
+    TERMS_A(3);
+    TERMS_A(4);
+    TERMS_A(5);
+    TERMS_A(6);
+    TERMS_A(7);
+    TERMS_A(8);
+    default: throw RlError(RL_ERR_UNSUPPORTED, "policy pass: policies and action values over 2..8 actions are built");
   }
 #undef TERMS_A
 #undef TERMS

@@ -496,7 +496,7 @@ __global__ void __launch_bounds__(SL *SW) k_stack_rollout(StackNet net, StackWs 
 
 // All T collection steps of a DQN agent with a recurrent action-value module in one launch (rl_dqn_create_recurrent):
 // k_stack_rollout's module step joined with k_rollout_dqn's actor and replay ring (kernels_dqn.hip, dqn_lanes.hpp).
-// DqnActor::act (dqn.rs:360-379) draws gen_bool(eps) first and, when the step explores, returns gen_range(0..2) BEFORE
+// DqnActor::act (dqn.rs:360-379) draws gen_bool(eps) first and, when the step explores, returns gen_range(0..NA) BEFORE
 // the module's step(): the module never sees that observation and the lane's recurrent state is what it was.  Per step:
 //   wave 0   the lane's observation features -> the observation planes `xobs` ([D][.][n], plane stride `xstride`); the
 //            exploration draw and, for an exploring lane, the random action; the decision -> LDS
@@ -512,13 +512,16 @@ __global__ void __launch_bounds__(SL *SW) k_stack_rollout(StackNet net, StackWs 
 // state is zero at the first step of every launch (the ring closes a lane the horizon cuts as Interrupt: what follows is
 // a new recorded episode).  A lane whose ring refuses a step (WriteExperienceError::Full) stops acting and follows the
 // barriers; the host raises the error.
-template <int CELL, class Env, int D, bool LIN>
+// NA: the env's action count = the module's outputs (rl_dqn_create_finite: 3..8), taken as in k_stack_rollout — the head
+// computes NQ outputs in passes of four rows, the greedy action is the first maximal of the first NA.
+template <int CELL, class Env, int D, bool LIN, int NA = 2>
 __global__ void __launch_bounds__(SL *SW) k_stack_collect_dqn(StackNet net, StackWs ws, CartPoleDev c, EnvStateDev st,
                                                               ReplayDev rp, float *__restrict__ xobs, size_t xstride,
                                                               uint32_t T, uint64_t p_int, int always_explore,
                                                               uint8_t *__restrict__ flags_out, uint64_t t_global) {
   __shared__ uint32_t words[16 * SL];  // LaneActorRng's block columns (wave 0)
   __shared__ uint8_t succ_of[SL], hold_of[SL];
+  constexpr int NQ = NA <= 2 ? 2 : ((NA + UQ - 1) / UQ) * UQ;
   const uint32_t n = rp.N;
   const LaneCtx lc = lane_ctx(n);
   const bool actor = lc.wave == 0, writer = lc.live && actor;
@@ -543,7 +546,7 @@ __global__ void __launch_bounds__(SL *SW) k_stack_collect_dqn(StackNet net, Stac
       Env::template features<D>(c, s, f);
       if (!full) {
         explore = dqn_explores(rng, p_int, always_explore);
-        if (explore) a = dqn_random_action(rng);
+        if (explore) a = dqn_random_action<NA>(rng);
       }
       if (writer && !explore) {
 #pragma unroll
@@ -553,15 +556,24 @@ __global__ void __launch_bounds__(SL *SW) k_stack_collect_dqn(StackNet net, Stac
     }
     const int any_greedy = __syncthreads_or(writer && !explore ? 1 : 0);
     const bool hold = hold_of[col] != 0;
-    float o[2] = {0.0f, 0.0f};
+    float o[NQ] = {};
     if (any_greedy) {
-      stack_module_step<CELL, false, true, LIN, 2, true>(net, ws, xobs, xstride, cur, cur ^ 1, fresh, lc, 0, o, hold);
+      stack_module_step<CELL, false, true, LIN, NQ, true>(net, ws, xobs, xstride, cur, cur ^ 1, fresh, lc, 0, o, hold);
       cur ^= 1;
     }
     if (actor) {
       int succ = RL_SUCC_CONTINUE;
       if (!full) {
-        if (!explore) a = o[1] > o[0] ? 1 : 0;  // argmax: first maximal index
+        if (!explore) {  // argmax: first maximal index
+          if constexpr (NA == 2) {
+            a = o[1] > o[0] ? 1 : 0;
+          } else {
+            float zz[NA];
+#pragma unroll
+            for (int q = 0; q < NA; ++q) zz[q] = o[q];
+            a = first_max_index<NA>(zz);
+          }
+        }
         float reward;
         succ = Env::step(c, s, a, glane, t_global + t, reward);
         const bool horizon_cut = succ == RL_SUCC_CONTINUE && t + 1 == T;
@@ -1040,11 +1052,37 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   });
 }
 
+namespace {
+// k_stack_collect_dqn over more than two actions (rl_dqn_create_finite): index-env lanes alone.  The bandit of NA arms has
+// 5 features and MemoryGame(NA, h) has NA + h [+ 1]: the (NA, D) pairs no env has are not built.
+template <int CELL, bool LIN, int NA>
+void collect_dqn_actions(uint32_t D, dim3 grid, dim3 blk, hipStream_t stream, const StackNet &net, const StackWs &ws,
+                         const rl_env *env, const ReplayDev &rp, float *xobs, size_t xstride, uint32_t T, uint64_t p_int,
+                         int always_explore, uint8_t *d_flags) {
+  auto go = [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    if constexpr (DD == 5 || DD > NA)
+      hipLaunchKernelGGL((k_stack_collect_dqn<CELL, IndexOps, DD, LIN, NA>), grid, blk, 0, stream, net, ws, env->dev,
+                         env->st, rp, xobs, xstride, T, p_int, always_explore, d_flags, env->t_global);
+    else
+      throw RlError(RL_ERR_UNSUPPORTED, "recurrent DQN collection: no index env has this (actions, features) pair");
+  };
+  switch (D) {
+    case 4: go(std::integral_constant<int, 4>{}); break;
+    case 5: go(std::integral_constant<int, 5>{}); break;
+    case 6: go(std::integral_constant<int, 6>{}); break;
+    case 7: go(std::integral_constant<int, 7>{}); break;
+    default: go(std::integral_constant<int, 8>{}); break;
+  }
+}
+}  // namespace
+
 void launch_stack_collect_dqn(rl_env *env, const rl_mlp *qnet, rl_traj *roll, const ReplayDev &rp, uint32_t T,
                               uint64_t p_int, int always_explore, uint8_t *d_flags) {
   ProfScope ps(env->eng, RL_K_ROLLOUT);
-  RL_REQUIRE(rl_module_is_recurrent(qnet->kind) && qnet->out_dim == 2 && env->A == 2 && qnet->in_dim == env->D,
-             "recurrent DQN collection: a two-output recurrent chain over the env's features");
+  RL_REQUIRE(rl_module_is_recurrent(qnet->kind) && qnet->out_dim == env->A && env->A >= 2 && env->A <= 8 &&
+                 qnet->in_dim == env->D,
+             "recurrent DQN collection: a recurrent chain of one output per action (2..8) over the env's features");
   RL_REQUIRE(roll->d.n == rp.N && roll->d.D == env->D, "recurrent DQN collection: workspace of another shape");
   const StackNet net = stack_net(qnet, qnet->d_params);
   const StackWs ws = stack_ws(roll);
@@ -1054,6 +1092,37 @@ void launch_stack_collect_dqn(rl_env *env, const rl_mlp *qnet, rl_traj *roll, co
   const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
   if (!(cartpole ? env->D == 4 || env->D == 5 : index_env && env->D >= 4 && env->D <= 8))
     throw RlError(RL_ERR_UNSUPPORTED, "recurrent DQN collection: CartPole lanes of 4 or 5 features, index-env lanes of 4..8");
+  if (env->A > 2) {
+    RL_REQUIRE(index_env, "recurrent DQN collection over more than two actions: index-env lanes");
+#define COLLECT_NA(CELL, LIN, NA)                                                                                     \
+  case NA:                                                                                                            \
+    collect_dqn_actions<CELL, LIN, NA>(env->D, grid, blk, env->eng->stream, net, ws, env, rp, roll->d.obs, xstride, T, \
+                                       p_int, always_explore, d_flags);                                              \
+    break
+#define COLLECT_ACTIONS(CELL, LIN) \
+  do {                             \
+    switch (env->A) {              \
+      COLLECT_NA(CELL, LIN, 3);    \
+      COLLECT_NA(CELL, LIN, 4);    \
+      COLLECT_NA(CELL, LIN, 5);    \
+      COLLECT_NA(CELL, LIN, 6);    \
+      COLLECT_NA(CELL, LIN, 7);    \
+      default:                     \
+        COLLECT_NA(CELL, LIN, 8);  \
+    }                              \
+  } while (0)
+    if (lstm) {
+      if (lin) COLLECT_ACTIONS(LSTM, true);
+      else COLLECT_ACTIONS(LSTM, false);
+    } else {
+      if (lin) COLLECT_ACTIONS(GRU, true);
+      else COLLECT_ACTIONS(GRU, false);
+    }
+#undef COLLECT_ACTIONS
+#undef COLLECT_NA
+    RL_HIP_CHECK(hipGetLastError());
+    return;
+  }
 #define COLLECT(CELL, LIN, ENV, DD)                                                                                      \
   hipLaunchKernelGGL((k_stack_collect_dqn<CELL, ENV, DD, LIN>), grid, blk, 0, env->eng->stream, net, ws, env->dev,      \
                      env->st, rp, roll->d.obs, xstride, T, p_int, always_explore, d_flags, env->t_global)

@@ -22,14 +22,13 @@ __device__ __forceinline__ float select_action(const float (&v)[A], int act) {
 // z: logits; dzt: tangent logits (PASS_JVP); act: the action taken; adv: advantage (DQN: the target).
 // Writes dz[a * B + b] (and lp0 in PASS_INIT); adds to the f64 sums s0, s1, s2 of the pass.
 // A: the number of actions (IndexSpace::new(A)), 2..8, deduced from the logits; the fused single-layer kernels call it
-// at A = 2.  PASS_DQN is built for two actions.
+// at A = 2.
 template <int MODE, int A>
 __device__ __forceinline__ void policy_sample_terms(const float (&z)[A], const float (&dzt)[A], int act, float adv,
                                                 size_t b, size_t B, float *__restrict__ lp0, float *__restrict__ dz,
                                                 float inv_B, float clip_lo, float clip_hi, double &s0, double &s1,
                                                 double &s2) {
   static_assert(A >= 2 && A <= 8, "categorical policies over 2..8 actions");
-  static_assert(MODE != PASS_DQN || A == 2, "the DQN terms are built for two actions");
   if (MODE == PASS_JVP) {
   float lp[A], p[A];
   log_softmax_lane<A>(z, lp);
@@ -46,10 +45,10 @@ __device__ __forceinline__ void policy_sample_terms(const float (&z)[A], const f
   float lp[A];
   if (MODE == PASS_DQN) {
     // action_values.gather(-1, actions).mse_loss(targets, Mean) + backward (dqn.rs:316-326); inv_B = 2 / B
-    float dq = (act == 0 ? z[0] : z[1]) - adv;
+    float dq = select_action<A>(z, act) - adv;
     float g = dq * inv_B;
-    dz[b] = act == 0 ? g : 0.0f;
-    dz[B + b] = act == 1 ? g : 0.0f;
+#pragma unroll
+    for (int a = 0; a < A; ++a) dz[(size_t)a * B + b] = act == a ? g : 0.0f;
     s0 += (double)(dq * dq);
     return;
   }
