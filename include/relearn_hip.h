@@ -249,6 +249,15 @@ int32_t rl_meta_bandit_config_default(rl_meta_bandit_config *meta);
  * rl_dqn_create, rl_actor_to_cbor.  An episode of rl_summary_push is a trial. */
 int32_t rl_env_create_meta_bandit(rl_engine *engine, const rl_env_config *cfg, const rl_meta_bandit_config *meta,
                                   rl_env **out);
+/* The same lanes at n_arms 2..12 (6..16 observation features): the range of the reference's rl2-bandits experiment, whose
+ * default is ten arms.  n_arms 2..4: rl_env_create_meta_bandit, the same handle.  RL_ERR_BUILD_ENV: n_arms outside 2..12
+ * and everything rl_env_create_meta_bandit refuses.  Above four arms the lanes serve rl_env_reset / _observe / _step,
+ * rl_rollout under a recurrent chain of rl_rnn_chain_create_wide (in one launch; kernel variant 1: a launch sequence per
+ * step) with every update on what it collected, rl_bandit_agent_* and rl_summary_push; trajectories take up to 16
+ * observation features.  Feed-forward modules have at most eight inputs and do not build for them; rl_dqn_create*,
+ * rl_env_get_state / rl_env_set_state and rl_actor_to_cbor refuse every meta lane by name. */
+int32_t rl_env_create_meta_bandit_wide(rl_engine *engine, const rl_env_config *cfg, const rl_meta_bandit_config *meta,
+                                       rl_env **out);
 int32_t rl_env_destroy(rl_env *env);
 /* number of observation features (CartPole 4, +1 `remaining` under VisibleStepLimit) and actions */
 int32_t rl_env_dims(const rl_env *env, uint32_t *obs_dim, uint32_t *n_actions);
@@ -463,6 +472,12 @@ typedef struct {
 /* RnnBaseConfig::default / ChainConfig::default over MlpConfig::default: 5 -> 128 -> [128] -> 2, one layer, bias vectors */
 int32_t rl_rnn_chain_config_default(int32_t cell, rl_rnn_chain_config *cfg);
 int32_t rl_rnn_chain_create(rl_engine *engine, const rl_rnn_chain_config *cfg, rl_mlp **out);
+/* The same chain at in_dim 1..16 and out_dim 1..12: policy (k + 4 -> k) and critic (k + 4 -> 1) of the rl2-bandits
+ * experiment on up to 12 arms.  in_dim <= 8 and out_dim <= 8: rl_rnn_chain_create, the same handle.  Beyond, the module
+ * always runs the lane-per-thread kernels (the head's outputs in up to three passes of four rows), never a twin.  out_dim
+ * 0 or 13, in_dim 0 or 17 -> RL_ERR_BUILD_AGENT; everything else as rl_rnn_chain_create.  Not an action-value module, and
+ * no actor document on the lanes wide enough to need it. */
+int32_t rl_rnn_chain_create_wide(rl_engine *engine, const rl_rnn_chain_config *cfg, rl_mlp **out);
 
 /* ---------------------------------------------------------------------------------------------
  * Trajectory store (replaces VecBuffer + LazyHistoryFeatures: src/agents/buffers/vec.rs:15-143,

@@ -49,11 +49,11 @@ ABI_SYMBOLS = [
     "rl_last_error", "rl_engine_info", "rl_engine_set_kernel_variant", "rl_timer_begin", "rl_timer_end", "rl_profile_enable", "rl_profile_read",
     "rl_comm_available", "rl_comm_library_paths", "rl_comm_unique_id", "rl_comm_init", "rl_comm_destroy", "rl_comm_init_host",
     "rl_comm_ipc_handle", "rl_comm_init_ipc", "rl_comm_selftest",
-    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
+    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
-    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_chain_config_default", "rl_rnn_chain_create", "rl_rnn_mlp_init_with", "rl_seq_forward",
+    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_chain_config_default", "rl_rnn_chain_create", "rl_rnn_chain_create_wide", "rl_rnn_mlp_init_with", "rl_seq_forward",
     "rl_traj_create", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write",
     "rl_rollout", "rl_gae",
     "rl_trpo_config_default", "rl_trpo_update", "rl_policy_gradient", "rl_policy_fvp", "rl_policy_loss_kl",
@@ -215,7 +215,7 @@ def _register(obj):
 @atexit.register
 def _close_all():
     objs = list(_live)
-    order = {"StepsSummary": -1, "Dqn": -1, "BanditAgent": -1, "Adam": 0, "Optimizer": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "MetaBanditEnv": 2, "Mlp": 3, "GruMlp": 3,
+    order = {"StepsSummary": -1, "Dqn": -1, "BanditAgent": -1, "Adam": 0, "Optimizer": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "MetaBanditEnv": 2, "MetaBanditEnvWide": 2, "Mlp": 3, "GruMlp": 3,
              "Engine": 4}
     for o in sorted(objs, key=lambda o: order.get(type(o).__name__, 2)):
         o.close()
@@ -538,6 +538,8 @@ class MetaBanditEnv(ChainEnv):
     reward 0), and the trial's last pull is an Interrupt: 2 * episodes_per_trial - 1 steps per trial.  Observations:
     n_arms + 4 features [inner is None] [prev is None] [one-hot(prev action)] [prev reward] [episode_done]; 2..4 arms."""
 
+    CREATE = "rl_env_create_meta_bandit"
+
     def __init__(self, engine, n_lanes, n_arms=2, episodes_per_trial=10, distribution="uniform_bernoulli", lane_offset=0,
                  seed_env=0, seed_actor=1, limit=LIMIT_NONE, max_steps=0):
         self.eng = engine
@@ -556,7 +558,7 @@ class MetaBanditEnv(ChainEnv):
         meta.episodes_per_trial = episodes_per_trial
         self.cfg, self.meta = cfg, meta
         self.h = C.c_void_p()
-        _check(lib().rl_env_create_meta_bandit(engine.h, C.byref(cfg), C.byref(meta), C.byref(self.h)), engine.h)
+        _check(getattr(lib(), self.CREATE)(engine.h, C.byref(cfg), C.byref(meta), C.byref(self.h)), engine.h)
         _register(self)
         self.n = n_lanes
         d, a = C.c_uint32(), C.c_uint32()
@@ -565,6 +567,13 @@ class MetaBanditEnv(ChainEnv):
 
     get_state = CartPoleEnv.get_state  # (refused by the library: RL_ERR_UNSUPPORTED)
     set_state = CartPoleEnv.set_state
+
+
+class MetaBanditEnvWide(MetaBanditEnv):
+    """The same lanes at 2..12 arms, 6..16 observation features (rl_env_create_meta_bandit_wide; two to four arms build
+    what MetaBanditEnv builds).  Above four arms: recurrent chains of RnnChainWide and BanditAgent."""
+
+    CREATE = "rl_env_create_meta_bandit_wide"
 
 
 class GruMlp(_Handle):
@@ -668,12 +677,14 @@ class RnnChain(GruMlp):
     out_dim 1..8 — the one constructor of recurrent chains over more than two actions.  GruMlp / LstmMlp / GruLinear /
     LstmLinear stay the two-action shorthand; for out_dim <= 2 this builds what they build."""
 
+    CREATE = "rl_rnn_chain_create"
+
     def __init__(self, engine, cell, in_dim, hidden, out_dim, num_layers=1, bias=True, mlp_hidden=None):
         self.eng = engine
         self.h = C.c_void_p()
         self.CELL = CELLS.get(cell, cell)
         cfg = RnnChainConfig(self.CELL, in_dim, hidden, num_layers, 1 if bias else 0, mlp_hidden or 0, out_dim)
-        _check(lib().rl_rnn_chain_create(engine.h, C.byref(cfg), C.byref(self.h)), engine.h)
+        _check(getattr(lib(), self.CREATE)(engine.h, C.byref(cfg), C.byref(self.h)), engine.h)
         _register(self)
         n = C.c_uint64()
         _check(lib().rl_mlp_num_params(self.h, C.byref(n)), engine.h)
@@ -681,6 +692,13 @@ class RnnChain(GruMlp):
         # (`hidden`: the width of an MLP tail's hidden layer, 0 for a Linear tail — the attribute names of GruMlp)
         self.in_dim, self.hidden, self.out_dim, self.gru_hidden = in_dim, mlp_hidden or 0, out_dim, hidden
         self.num_layers = num_layers
+
+
+class RnnChainWide(RnnChain):
+    """The same chain at in_dim 1..16 and out_dim 1..12 (rl_rnn_chain_create_wide; within in_dim <= 8 and out_dim <= 8 it
+    builds what RnnChain builds): policy and critic of the RL2 experiment on up to 12 arms."""
+
+    CREATE = "rl_rnn_chain_create_wide"
 
 
 ACTIVATIONS = ["Identity", "Relu", "Sigmoid", "Tanh"]  # rl_activation, in the reference enum's order

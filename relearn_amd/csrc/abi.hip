@@ -667,8 +667,9 @@ int32_t rl_cartpole_params_default(rl_cartpole_params *p) {
 
 // `arm_values` / `n_arms`: DeterministicBandit::from_values for rl_env_create_bandit (NULL: cfg->bandit_values, two arms)
 // `meta`: rl_env_create_meta_bandit (the env kind is then RL_ENV_META_BANDIT whatever cfg->kind says)
+// `wide`: rl_env_create_meta_bandit_wide — up to RL_WIDE_MAX_OBS_DIM - 4 = 12 arms
 static int32_t env_create(rl_engine *e, const rl_env_config *cfg_in, const double *arm_values, uint32_t n_arms,
-                          const rl_meta_bandit_config *meta, rl_env **out) {
+                          const rl_meta_bandit_config *meta, rl_env **out, bool wide = false) {
   return guarded(e, [&] {
     RL_REQUIRE(e && cfg_in && out, "NULL argument");
     *out = nullptr;
@@ -676,7 +677,10 @@ static int32_t env_create(rl_engine *e, const rl_env_config *cfg_in, const doubl
     rl_env_config *cfg = &cfg_v;
     if (meta != nullptr) {
       cfg->kind = RL_ENV_META_BANDIT;
-      if (meta->n_arms < 2 || meta->n_arms > RL_TRAJ_MAX_OBS_DIM - 4)
+      if (wide && (meta->n_arms < 2 || meta->n_arms > RL_WIDE_MAX_OBS_DIM - 4))
+        throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_bandit_wide: 2..12 arms (the observation has n_arms + 4 "
+                                        "features, a trajectory of wide lanes at most 16)");
+      if (!wide && (meta->n_arms < 2 || meta->n_arms > RL_TRAJ_MAX_OBS_DIM - 4))
         throw RlError(RL_ERR_BUILD_ENV, "meta-bandit lanes: 2..4 arms (the observation has n_arms + 4 features, a "
                                         "trajectory at most 8)");
       if (meta->episodes_per_trial == 0)  // TrialEpisodeLimit::new asserts (meta.rs:548-553)
@@ -815,6 +819,17 @@ int32_t rl_env_create_meta_bandit(rl_engine *e, const rl_env_config *cfg, const 
                                   rl_env **out) {
   if (meta == nullptr) return guarded(e, [&] { RL_REQUIRE(meta, "NULL argument"); });
   return env_create(e, cfg, nullptr, 0, meta, out);
+}
+
+// The same lanes at 2..12 arms (6..16 observation features).  Two to four arms: the older constructor, the same handle.
+// Above four, the lanes serve what takes their width: the standalone env calls, recurrent chains of
+// rl_rnn_chain_create_wide (rl_rollout and every update on what it collected) and rl_bandit_agent_*; feed-forward
+// modules of more than eight inputs do not build, and DQN, rl_env_get_state / rl_env_set_state and actor documents
+// refuse every meta lane by name.
+int32_t rl_env_create_meta_bandit_wide(rl_engine *e, const rl_env_config *cfg, const rl_meta_bandit_config *meta,
+                                       rl_env **out) {
+  if (meta == nullptr || meta->n_arms <= RL_TRAJ_MAX_OBS_DIM - 4) return rl_env_create_meta_bandit(e, cfg, meta, out);
+  return env_create(e, cfg, nullptr, 0, meta, out, true);
 }
 
 int32_t rl_env_create_bandit(rl_engine *e, const rl_env_config *cfg, const double *values, uint32_t n_arms,
@@ -1071,17 +1086,19 @@ int32_t rl_mlp_create_config(rl_engine *e, uint32_t in_dim, const uint32_t *hidd
 // out_dim) (mlp_hidden is 0 and marks it, rl_mlp::linear_tail); always the lane-per-thread kernels, never a twin.
 static void seq_module_create(rl_engine *e, int kind, uint32_t in_dim, uint32_t rnn_hidden, uint32_t num_layers,
                               uint32_t mlp_hidden, uint32_t out_dim, rl_mlp **out, bool rnn_bias = true,
-                              bool linear_tail = false, uint32_t max_out = 2) {
+                              bool linear_tail = false, uint32_t max_out = 2, uint32_t max_in = RL_TRAJ_MAX_OBS_DIM) {
   RL_REQUIRE(e && out, "NULL argument");
   *out = nullptr;
   if (num_layers == 0) throw RlError(RL_ERR_BUILD_AGENT, "RnnBaseConfig::num_layers must be at least 1");
   if (num_layers > RL_RNN_MAX_LAYERS)
     throw RlError(RL_ERR_UNSUPPORTED, "recurrent chains are built for RnnBaseConfig::num_layers <= 4");
-  if (in_dim < 1 || in_dim > RL_TRAJ_MAX_OBS_DIM || rnn_hidden < 1 || rnn_hidden > RL_MLP_MAX_WIDTH ||
+  if (in_dim < 1 || in_dim > max_in || rnn_hidden < 1 || rnn_hidden > RL_MLP_MAX_WIDTH ||
       (linear_tail ? mlp_hidden != 0 : mlp_hidden < 1) || mlp_hidden > RL_MLP_MAX_WIDTH ||
       out_dim < 1 || out_dim > max_out)
     throw RlError(RL_ERR_BUILD_AGENT,
-                  max_out > 2
+                  max_out > RL_MLP_MAX_OUT
+                      ? "rl_rnn_chain_create_wide: in_dim 1..16, recurrent hidden 1..256, mlp_hidden 0..256, out_dim 1..12"
+                  : max_out > 2
                       ? "supported recurrent chain shapes: in_dim 1..8, recurrent hidden 1..256, mlp_hidden 0..256, out_dim 1..8"
                   : linear_tail
                       ? "supported recurrent chain shapes: in_dim 1..8, recurrent hidden 1..256, out_dim in {1,2}"
@@ -1192,6 +1209,23 @@ int32_t rl_rnn_chain_create(rl_engine *e, const rl_rnn_chain_config *cfg, rl_mlp
     seq_module_create(e, cfg->cell == RL_CELL_GRU ? RL_MODULE_GRU_MLP : RL_MODULE_LSTM_MLP, cfg->in_dim, cfg->hidden,
                       cfg->num_layers, cfg->mlp_hidden, cfg->out_dim, out, cfg->rnn_bias != 0, cfg->mlp_hidden == 0,
                       RL_MLP_MAX_OUT);
+  });
+}
+
+// The same chain at in_dim 1..16 and out_dim 1..12 (the RL2 experiment's model on up to 12 arms: k + 4 inputs, k outputs
+// for the policy, one for the critic).  Within in_dim <= 8 and out_dim <= 8: rl_rnn_chain_create, the same handle.
+// Beyond, always the lane-per-thread kernels (rl_mlp::lane_kernels: in_dim > 5 or out_dim > 2), never a twin.
+int32_t rl_rnn_chain_create_wide(rl_engine *e, const rl_rnn_chain_config *cfg, rl_mlp **out) {
+  if (cfg == nullptr || (cfg->in_dim <= RL_TRAJ_MAX_OBS_DIM && cfg->out_dim <= RL_MLP_MAX_OUT))
+    return rl_rnn_chain_create(e, cfg, out);
+  return guarded(e, [&] {
+    RL_REQUIRE(e && out, "NULL argument");
+    *out = nullptr;
+    if (cfg->cell != RL_CELL_GRU && cfg->cell != RL_CELL_LSTM) throw RlError(RL_ERR_BUILD_AGENT, "unknown recurrent cell");
+    if (cfg->rnn_bias != 0 && cfg->rnn_bias != 1) throw RlError(RL_ERR_BUILD_AGENT, "rnn_bias is 0 or 1");
+    seq_module_create(e, cfg->cell == RL_CELL_GRU ? RL_MODULE_GRU_MLP : RL_MODULE_LSTM_MLP, cfg->in_dim, cfg->hidden,
+                      cfg->num_layers, cfg->mlp_hidden, cfg->out_dim, out, cfg->rnn_bias != 0, cfg->mlp_hidden == 0,
+                      RL_WIDE_MAX_OUT, RL_WIDE_MAX_OBS_DIM);
   });
 }
 
@@ -1533,7 +1567,8 @@ void traj_plan(rl_traj *t, uint64_t B) {
 rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, bool resizable) {
   RL_REQUIRE(n_lanes > 0 && n_lanes < (1ull << 31), "bad n_lanes");
   RL_REQUIRE(horizon > 0 && horizon < (1ull << 20), "bad horizon");
-  RL_REQUIRE(obs_dim >= 1 && obs_dim <= RL_TRAJ_MAX_OBS_DIM, "obs_dim must be in 1..8");
+  // (up to 16 planes: the wide meta-bandit lanes; what reads a trajectory checks its own width against the planes')
+  RL_REQUIRE(obs_dim >= 1 && obs_dim <= RL_WIDE_MAX_OBS_DIM, "obs_dim must be in 1..16");
   RL_REQUIRE(n_lanes * horizon < (1ull << 32), "T * n must fit 32 bits");
   RL_HIP_CHECK(hipSetDevice(e->device));
   std::unique_ptr<rl_traj> t(new rl_traj());

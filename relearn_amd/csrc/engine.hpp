@@ -45,8 +45,8 @@ struct CartPoleDev {
   uint32_t mem_actions;  // RL_ENV_MEMORY: num_actions (0 selects Chain in the shared lane code)
   uint32_t bandit;       // RL_ENV_BANDIT: != 0; reward = bandit_r[action], every step terminates
   float bandit_r[8];     // DeterministicBandit::from_values, 2..8 arms
-  // RL_ENV_META_BANDIT (MetaOps, env_lanes.hpp): number of arms k (2..4) and the bandit distribution (RL_BANDITS_*);
-  // `max_steps` holds TrialEpisodeLimit::episodes_per_trial (the trial limit is this env's limit).  Last, so that the
+  // RL_ENV_META_BANDIT (MetaOps, env_lanes.hpp): number of arms k (2..12; above four: rl_env_create_meta_bandit_wide)
+  // and the bandit distribution (RL_BANDITS_*); `max_steps` holds TrialEpisodeLimit::episodes_per_trial (the trial limit is this env's limit).  Last, so that the
   // fields above keep their offsets in every kernel's arguments.
   uint32_t meta_arms;
   int32_t meta_dist;
@@ -57,7 +57,7 @@ struct EnvStateDev {
                                   // initial state in xdot and its env-stream word position in th (exact in f64)
   // RL_ENV_META_BANDIT: x = env-stream word position at which the trial's arms were drawn (UniformBernoulli: arm i's mean
   // is the u64 at x + 2 i) or the good arm (OneHot, RoundRobin), xdot = next unread word of the env stream, th = the
-  // previous inner step's reward; nv_pos = bit 0 inner episode done, bit 1 prev_step_obs is Some, bits 2-3 its action;
+  // previous inner step's reward; nv_pos = bit 0 inner episode done, bit 1 prev_step_obs is Some, bits 2-5 its action;
   // steps_remaining = inner episodes remaining in the trial
   uint8_t *nv_pos;                // [n] cached_normal_velocity_is_positive
   uint32_t *steps_remaining;      // [n]
@@ -247,6 +247,11 @@ constexpr uint32_t RL_MLP_MAX_WIDTH = 256;  // widest hidden layer
 constexpr uint32_t RL_MLP_MAX_OUT = 8;      // outputs of a general MLP: a categorical policy over IndexSpace::new(2..8)
 constexpr uint32_t RL_TRAJ_MAX_OBS_DIM = 8;  // observation features of a trajectory (the envs here have 4 to 8)
 constexpr uint32_t RL_ENV_MIN_OBS_DIM = 4;   // narrowest observation the env kernels are built for
+// the wide entry points (rl_env_create_meta_bandit_wide, rl_rnn_chain_create_wide): meta-bandit lanes of up to 12 arms
+// (k + 4 = 16 features) and recurrent chains of up to 16 inputs and 12 outputs on the lane-per-thread kernels.  The two
+// constants above keep guarding what they guard: feed-forward modules, MemoryGame, DQN, the older constructors.
+constexpr uint32_t RL_WIDE_MAX_OBS_DIM = 16;
+constexpr uint32_t RL_WIDE_MAX_OUT = 12;
 constexpr uint32_t RL_RNN_MAX_LAYERS = 4;   // RnnBaseConfig::num_layers of a recurrent chain
 
 struct rl_mlp {

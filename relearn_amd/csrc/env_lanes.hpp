@@ -363,7 +363,10 @@ struct MetaLane {
   uint32_t reset_count;
 };
 
-// the u64 at even word position `pos` of the lane's stream (both words lie in one block)
+// the u64 at even word position `pos` of the lane's stream: the block is pos >> 4, and because `pos` is even both words
+// lie in it.  Every position a meta lane asks for is even: env_pos starts at 0 and moves by 2 per u64 (a trial's k means
+// move it by 2 k — at k >= 8 a whole block or more, so arm a's mean at arms + 2 a may lie a block or two behind arm 0's:
+// the block is taken from the position asked for, never from `arms`).
 __device__ __forceinline__ uint64_t lane_u64_at(const uint32_t *key, uint64_t glane, uint64_t pos) {
   uint32_t w[16];
   rl_chacha_block(key, pos >> 4, glane, 4, w);
@@ -386,7 +389,7 @@ struct MetaOps {
     const uint32_t b = st.nv_pos[i];
     s.inner_done = b & 1u;
     s.prev_some = (b >> 1) & 1u;
-    s.prev_action = (b >> 2) & 3u;
+    s.prev_action = (b >> 2) & 15u;  // bits 2-5: up to 12 arms (at 2..4 arms the byte is the one two bits gave)
     s.remaining = st.steps_remaining[i];
     s.reset_count = st.reset_count[i];
   }

@@ -124,10 +124,12 @@ class EnvLanes {
     check(rl_env_create_bandit(eng.handle(), &cfg_, arm_values.data(), (uint32_t)arm_values.size(), &h_), eng.handle());
     check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
   }
-  // meta-bandit lanes (rl_env_create_meta_bandit)
+  // meta-bandit lanes (rl_env_create_meta_bandit; above four arms rl_env_create_meta_bandit_wide)
   EnvLanes(Engine &eng, const rl_env_config &cfg, const rl_meta_bandit_config &meta, double discount)
       : eng_(eng), cfg_(cfg), discount_(discount) {
-    check(rl_env_create_meta_bandit(eng.handle(), &cfg_, &meta, &h_), eng.handle());
+    check(meta.n_arms > 4 ? rl_env_create_meta_bandit_wide(eng.handle(), &cfg_, &meta, &h_)
+                          : rl_env_create_meta_bandit(eng.handle(), &cfg_, &meta, &h_),
+          eng.handle());
     check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
   }
   Engine &eng_;
@@ -240,7 +242,7 @@ class DeterministicBanditLanes : public EnvLanes {
 };
 
 // `MetaEnv::new(D::new(n_arms)).wrap(TrialEpisodeLimit::new(episodes_per_trial))` x n_lanes (src/envs/meta.rs:128-203,
-// 541-617; D: src/envs/bandits.rs:128-243), 2..4 arms, n_arms + 4 observation features: the env of
+// 541-617; D: src/envs/bandits.rs:128-243), 2..12 arms, n_arms + 4 observation features: the env of
 // relearn_experiments/src/bin/rl2-bandits.rs.  A trial is 2 * episodes_per_trial - 1 steps and ends in an Interrupt;
 // discount factor 1.0 (bandits.rs:165-167).  Defaults: UniformBernoulliBandits::default(), TrialEpisodeLimit::default().
 class MetaBanditLanes : public EnvLanes {
@@ -353,8 +355,12 @@ inline int32_t rnn_chain_create_multi(Engine &eng, int32_t cell, const RnnBaseCo
   cfg.rnn_bias = first.bias_init ? 1 : 0;
   cfg.mlp_hidden = mlp_hidden;
   cfg.out_dim = out_dim;
-  return rl_rnn_chain_create(eng.handle(), &cfg, h);
+  // (more than eight inputs or outputs — the rl2-bandits experiment above four arms: the wide constructor)
+  return in_dim > 8 || out_dim > 8 ? rl_rnn_chain_create_wide(eng.handle(), &cfg, h)
+                                   : rl_rnn_chain_create(eng.handle(), &cfg, h);
 }
+// the shapes the two-action constructors do not take: more than two outputs, or more than eight inputs
+inline bool chain_by_config(uint32_t in_dim, uint32_t out_dim) { return out_dim > 2 || in_dim > 8; }
 
 struct GruMlpConfig {  // ChainConfig<GruConfig, MlpConfig>::default (modules/mod.rs:14, chain.rs:19-32)
   GruConfig first_config;
@@ -362,7 +368,7 @@ struct GruMlpConfig {  // ChainConfig<GruConfig, MlpConfig>::default (modules/mo
   MlpConfig second_config;
   std::unique_ptr<Module> build_module(Engine &eng, uint32_t in_dim, uint32_t out_dim, uint64_t seed) const {
     rl_mlp *h = nullptr;
-    check(out_dim > 2 ? rnn_chain_create_multi(eng, RL_CELL_GRU, first_config, hidden_dim,
+    check(chain_by_config(in_dim, out_dim) ? rnn_chain_create_multi(eng, RL_CELL_GRU, first_config, hidden_dim,
                                                second_config.single_hidden_size(), in_dim, out_dim, &h)
                       : rl_rnn_mlp_create_config(eng.handle(), RL_CELL_GRU, in_dim, hidden_dim, first_config.num_layers,
                                                  first_config.bias_init ? 1 : 0, second_config.single_hidden_size(),
@@ -391,7 +397,7 @@ struct ChainLstmMlpConfig {
   MlpConfig second_config;
   std::unique_ptr<Module> build_module(Engine &eng, uint32_t in_dim, uint32_t out_dim, uint64_t seed) const {
     rl_mlp *h = nullptr;
-    check(out_dim > 2 ? rnn_chain_create_multi(eng, RL_CELL_LSTM, first_config, hidden_dim,
+    check(chain_by_config(in_dim, out_dim) ? rnn_chain_create_multi(eng, RL_CELL_LSTM, first_config, hidden_dim,
                                                second_config.single_hidden_size(), in_dim, out_dim, &h)
                       : rl_rnn_mlp_create_config(eng.handle(), RL_CELL_LSTM, in_dim, hidden_dim, first_config.num_layers,
                                                  first_config.bias_init ? 1 : 0, second_config.single_hidden_size(),
@@ -423,7 +429,7 @@ struct GruLinearConfig {
     if (!second.bias_init)
       throw BuildAgentError(RL_ERR_BUILD_AGENT, "a recurrent chain's Linear tail is built with a bias vector");
     rl_mlp *h = nullptr;
-    check(out_dim > 2 ? rnn_chain_create_multi(eng, cell, first, hidden_dim, 0, in_dim, out_dim, &h)
+    check(chain_by_config(in_dim, out_dim) ? rnn_chain_create_multi(eng, cell, first, hidden_dim, 0, in_dim, out_dim, &h)
                       : rl_rnn_linear_create(eng.handle(), cell, in_dim, hidden_dim, first.num_layers,
                                              first.bias_init ? 1 : 0, out_dim, &h),
           eng.handle());

@@ -280,7 +280,15 @@ void launch_kind(rl_bandit_agent *agent, rl_env *env, rl_traj *traj) {
     case 6: ROLLOUT(6); break;
     case 7: ROLLOUT(7); break;
     case 8: ROLLOUT(8); break;
-    default: throw RlError(RL_ERR_UNSUPPORTED, "rl_bandit_agent_rollout: built for 2..4 arms (6..8 features)");
+    case 9: ROLLOUT(9); break;  // 5..12 arms: rl_env_create_meta_bandit_wide
+    case 10: ROLLOUT(10); break;
+    case 11: ROLLOUT(11); break;
+    case 12: ROLLOUT(12); break;
+    case 13: ROLLOUT(13); break;
+    case 14: ROLLOUT(14); break;
+    case 15: ROLLOUT(15); break;
+    case 16: ROLLOUT(16); break;
+    default: throw RlError(RL_ERR_UNSUPPORTED, "rl_bandit_agent_rollout: built for 2..12 arms (6..16 features)");
   }
 #undef ROLLOUT
 }

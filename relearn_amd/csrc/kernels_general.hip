@@ -897,8 +897,12 @@ void launch_rollout_stepwise(rl_env *env, rl_traj *t, const float *z, const std:
       SAMPLE(6);
       SAMPLE(7);
       SAMPLE(8);
+      SAMPLE(9);  // 9..12: the wide meta-bandit lanes (rl_env_create_meta_bandit_wide) under a recurrent chain
+      SAMPLE(10);
+      SAMPLE(11);
+      SAMPLE(12);
 #undef SAMPLE
-      default: throw RlError(RL_ERR_UNSUPPORTED, "rollout: envs of 2..8 actions are built");
+      default: throw RlError(RL_ERR_UNSUPPORTED, "rollout: envs of 2..12 actions are built");
     }
     launch_env_step(env);  // leaves reward, flag, the next observation and the interrupted successor in the env's buffers
     env->t_global += 1;

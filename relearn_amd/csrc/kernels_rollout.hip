@@ -402,7 +402,7 @@ void launch_obs_range(rl_traj *traj) {
 
 // The standalone env kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature
 // count as types.  CartPole lanes have 4 or 5 features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame:
-// num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..8.
+// num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..16.
 template <int D>
 using FeatureCount = std::integral_constant<int, D>;
 template <class Go>
@@ -412,12 +412,20 @@ static void env_dispatch(const rl_env *env, Go &&go) {
     else go(CartPoleOps{}, FeatureCount<4>{});
     return;
   }
-  if (env->kind == RL_ENV_META_BANDIT) {  // k + 4 features, k = 2..4 arms
+  if (env->kind == RL_ENV_META_BANDIT) {  // k + 4 features, k = 2..12 arms (above four: rl_env_create_meta_bandit_wide)
     switch (env->D) {
       case 6: go(MetaOps{}, FeatureCount<6>{}); break;
       case 7: go(MetaOps{}, FeatureCount<7>{}); break;
       case 8: go(MetaOps{}, FeatureCount<8>{}); break;
-      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-bandit lanes: 6..8 observation features");
+      case 9: go(MetaOps{}, FeatureCount<9>{}); break;
+      case 10: go(MetaOps{}, FeatureCount<10>{}); break;
+      case 11: go(MetaOps{}, FeatureCount<11>{}); break;
+      case 12: go(MetaOps{}, FeatureCount<12>{}); break;
+      case 13: go(MetaOps{}, FeatureCount<13>{}); break;
+      case 14: go(MetaOps{}, FeatureCount<14>{}); break;
+      case 15: go(MetaOps{}, FeatureCount<15>{}); break;
+      case 16: go(MetaOps{}, FeatureCount<16>{}); break;
+      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-bandit lanes: 6..16 observation features");
     }
     return;
   }

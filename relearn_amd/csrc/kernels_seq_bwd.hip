@@ -718,7 +718,11 @@ void launch_seq_policy_dlogits(rl_traj *traj, int mode, uint64_t B_total, float 
       DLN_A(6);
       DLN_A(7);
       DLN_A(8);
-      default: throw RlError(RL_ERR_UNSUPPORTED, "recurrent policy pass: categorical policies over 2..8 actions are built");
+      DLN_A(9);  // 9..12: rl_rnn_chain_create_wide
+      DLN_A(10);
+      DLN_A(11);
+      DLN_A(12);
+      default: throw RlError(RL_ERR_UNSUPPORTED, "recurrent policy pass: categorical policies over 2..12 actions are built");
     }
 #undef DLN_A
 #undef DLN

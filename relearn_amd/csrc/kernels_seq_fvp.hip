@@ -310,9 +310,10 @@ void launch_gru_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent
                         const int32_t *d_skip) {
   rl_engine *e = traj->eng;
   const SeqDev &q = traj->seq;
-  // (the tile kernels are two-action; a lane-kernel module may have up to eight outputs, rl_rnn_chain_create)
-  RL_REQUIRE(mod->out_dim == 2 || (mod->lane_kernels() && mod->out_dim > 2 && mod->out_dim <= RL_MLP_MAX_OUT),
-             "Fisher-vector products are for policies of two actions (lane-per-thread kernels: 2..8)");
+  // (the tile kernels are two-action; a lane-kernel module may have up to eight outputs, rl_rnn_chain_create, or twelve,
+  // rl_rnn_chain_create_wide)
+  RL_REQUIRE(mod->out_dim == 2 || (mod->lane_kernels() && mod->out_dim > 2 && mod->out_dim <= RL_WIDE_MAX_OUT),
+             "Fisher-vector products are for policies of two actions (lane-per-thread kernels: 2..12)");
   if (mod->lane_kernels()) launch_stack_tangent(traj, mod, d_tangent, d_skip);  // -> seq.out
   else {
     ProfScope ps(e, RL_K_POLICY_FUSED);
@@ -337,7 +338,11 @@ void launch_gru_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent
       FVN(6);
       FVN(7);
       FVN(8);
-      default: throw RlError(RL_ERR_UNSUPPORTED, "Fisher-vector products: 2..8 actions");
+      FVN(9);  // 9..12: rl_rnn_chain_create_wide
+      FVN(10);
+      FVN(11);
+      FVN(12);
+      default: throw RlError(RL_ERR_UNSUPPORTED, "Fisher-vector products: 2..12 actions");
     }
 #undef FVN
   }

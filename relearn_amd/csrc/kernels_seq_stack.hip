@@ -6,8 +6,8 @@
 // module is a compile-time parameter of every kernel (LIN): the Mlp([h]) above, or one Linear(H, A) on relu(top)
 // (ChainConfig<_, LinearConfig>, modules/chain.rs:12-54; flat order [.., kernel [A][H], bias [A]]): no hidden units,
 // so no `u` / `ur` / `du` planes and one barrier less per step.  So is the head's output-count class (NQ): 2 for the
-// chains of one or two outputs, 4 or 8 for the chains of rl_rnn_chain_create over IndexSpace::new(3..8), whose outputs
-// are computed in passes of four rows (head_passes).
+// chains of one or two outputs, 4 or 8 for the chains of rl_rnn_chain_create over IndexSpace::new(3..8), 12 for those of
+// rl_rnn_chain_create_wide over 9..12, whose outputs are computed in passes of four rows (head_passes).
 //
 // The single-layer chains have fused tile kernels (kernels_seq*.hip, built for 5 -> 128 -> 128); this is the general
 // path for the stacked ones, at the module's own widths: ONE THREAD PER LANE, 64 lanes per workgroup, and the unit loop
@@ -166,9 +166,9 @@ __device__ __forceinline__ void tdot(float (&acc)[N], const float *__restrict__ 
   else tdot_n<N, false>(acc, W, ld, k0, K - 1, R, d_at);
 }
 
-// The head's outputs of a module with more than two of them (rl_rnn_chain_create, out_dim 3..8), NQ registers of a
-// thread (4 or 8): passes of UQ output rows, every output the contract's chain — acc = bias[q]; acc = fma(x_k, w[q][k],
-// acc), k ascending — from `bias_at(q)` through `dots(acc, rows)`, which runs one dot_rows per matrix of the sum.  Rows
+// The head's outputs of a module with more than two of them (rl_rnn_chain_create, out_dim 3..8;
+// rl_rnn_chain_create_wide, 9..12), NQ registers of a thread (4, 8 or 12): passes of UQ output rows, every output the
+// contract's chain — acc = bias[q]; acc = fma(x_k, w[q][k], acc), k ascending — from `bias_at(q)` through `dots(acc, rows)`, which runs one dot_rows per matrix of the sum.  Rows
 // past A repeat row A - 1 (never stored); a pass wholly past A is skipped (A is wave-uniform).
 template <int NQ, class BF, class DF>
 __device__ __forceinline__ void head_passes(float (&out)[NQ], int A, BF bias_at, DF dots) {
@@ -294,7 +294,7 @@ __device__ __forceinline__ void stack_cell(const StackNet &net, const StackWs &w
 
 // Chain's ReLU and the Mlp on the top layer's output `top` ([H][n]); out[q] in every thread.  One barrier inside.
 // LIN: Chain's ReLU and one Linear — out[q] = bias[q] + sum_k relu(top[k]) kernel[q][k], no barrier.
-// NQ: the output-count class — 2 for the chains of one or two outputs, 4 or 8 for more (head_passes).
+// NQ: the output-count class — 2 for the chains of one or two outputs, 4, 8 or 12 for more (head_passes).
 template <bool REC, bool CW = false, bool LIN = false, int NQ = 2>
 __device__ __forceinline__ void stack_head(const StackNet &net, const StackWs &ws, const float *__restrict__ top,
                                            const LaneCtx &lc, size_t b, float (&out)[NQ]) {
@@ -921,6 +921,13 @@ StackWs stack_ws(const rl_traj *t) {
 
 inline uint32_t cdiv_k(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
+// the head's output-count class of a module (k_stack_forward / _step / _tangent are built at 2, 8 and 12): 2 for one or
+// two outputs, 8 up to eight, 12 beyond (rl_rnn_chain_create_wide: at most RL_WIDE_MAX_OUT)
+inline int out_class(const rl_mlp *m) {
+  RL_REQUIRE(m->out_dim >= 1 && m->out_dim <= RL_WIDE_MAX_OUT, "recurrent chains: 1..12 outputs");
+  return m->out_dim <= 2 ? 2 : (m->out_dim <= 8 ? 8 : 12);
+}
+
 }  // namespace
 
 void stack_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
@@ -973,14 +980,18 @@ void launch_stack_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float 
                      d_succ, d_skip)
 #define FWD_TAIL(CELL, REC)                   \
   do {                                        \
-    if (wide) {                               \
+    if (nq == 12) {                           \
+      if (lin) FWD(CELL, REC, true, 12);      \
+      else FWD(CELL, REC, false, 12);         \
+    } else if (nq == 8) {                     \
       if (lin) FWD(CELL, REC, true, 8);       \
       else FWD(CELL, REC, false, 8);          \
     } else if (lin) FWD(CELL, REC, true, 2);  \
     else FWD(CELL, REC, false, 2);            \
   } while (0)
-  // (`wide`: more than two outputs — the output-count class 8 of the head, stack_head)
-  const bool lstm = mod->kind == RL_MODULE_LSTM_MLP, lin = mod->linear_tail(), wide = mod->out_dim > 2;
+  // (`nq`: the output-count class of the head, stack_head)
+  const bool lstm = mod->kind == RL_MODULE_LSTM_MLP, lin = mod->linear_tail();
+  const int nq = out_class(mod);
   if (record) {
     if (lstm) FWD_TAIL(LSTM, true);
     else FWD_TAIL(GRU, true);
@@ -1000,20 +1011,31 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
   float *z = traj->seq.stack.z;
-  const bool lstm = policy->kind == RL_MODULE_LSTM_MLP, lin = policy->linear_tail(), wide = policy->out_dim > 2;
+  const bool lstm = policy->kind == RL_MODULE_LSTM_MLP, lin = policy->linear_tail();
+  const int nq = out_class(policy);
   if (env->kind == RL_ENV_META_BANDIT && env->eng->kernel_variant != 1) {
     // meta-bandit lanes: all T steps in one launch (kernel variant 1 keeps the launch sequence per step, below).  Two to
-    // four arms: k arms make k + 4 observation features (env_lanes.hpp, MetaOps).
-    RL_REQUIRE(env->A >= 2 && env->A <= 4 && env->D == env->A + 4,
-               "fused recurrent rollout on meta-bandit lanes: built for two to four arms (k + 4 features)");
+    // twelve arms: k arms make k + 4 observation features (env_lanes.hpp, MetaOps).
+    RL_REQUIRE(env->A >= 2 && env->A <= RL_WIDE_MAX_OUT && env->D == env->A + 4,
+               "fused recurrent rollout on meta-bandit lanes: built for two to twelve arms (k + 4 features)");
 #define ROLL(CELL, LIN, DD, AA)                                                                                          \
   hipLaunchKernelGGL((k_stack_rollout<CELL, MetaOps, DD, LIN, AA>), grid, blk, 0, env->eng->stream, net, ws, env->dev, \
                      env->st, traj->d, env->t_global)
-#define ROLL_ARMS(CELL, LIN)                     \
-  do {                                           \
-    if (env->A == 2) ROLL(CELL, LIN, 6, 2);      \
-    else if (env->A == 3) ROLL(CELL, LIN, 7, 3); \
-    else ROLL(CELL, LIN, 8, 4);                  \
+#define ROLL_ARMS(CELL, LIN)                        \
+  do {                                              \
+    switch (env->A) {                               \
+      case 2: ROLL(CELL, LIN, 6, 2); break;         \
+      case 3: ROLL(CELL, LIN, 7, 3); break;         \
+      case 4: ROLL(CELL, LIN, 8, 4); break;         \
+      case 5: ROLL(CELL, LIN, 9, 5); break;         \
+      case 6: ROLL(CELL, LIN, 10, 6); break;        \
+      case 7: ROLL(CELL, LIN, 11, 7); break;        \
+      case 8: ROLL(CELL, LIN, 12, 8); break;        \
+      case 9: ROLL(CELL, LIN, 13, 9); break;        \
+      case 10: ROLL(CELL, LIN, 14, 10); break;      \
+      case 11: ROLL(CELL, LIN, 15, 11); break;      \
+      default: ROLL(CELL, LIN, 16, 12); break;      \
+    }                                               \
   } while (0)
     if (lstm) {
       if (lin) ROLL_ARMS(LSTM, true);
@@ -1035,10 +1057,11 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
 #define STEP(CELL, LIN, NQ)                                                                                         \
   hipLaunchKernelGGL((k_stack_step<CELL, LIN, NQ>), grid, blk, 0, env->eng->stream, net, ws, env->d_obs, flag_prev, \
                      first, parity, z)
-#define STEP_OUT(CELL, LIN)          \
-  do {                               \
-    if (wide) STEP(CELL, LIN, 8);    \
-    else STEP(CELL, LIN, 2);         \
+#define STEP_OUT(CELL, LIN)              \
+  do {                                   \
+    if (nq == 12) STEP(CELL, LIN, 12);   \
+    else if (nq == 8) STEP(CELL, LIN, 8); \
+    else STEP(CELL, LIN, 2);             \
   } while (0)
     if (lstm) {
       if (lin) STEP_OUT(LSTM, true);
@@ -1223,11 +1246,13 @@ void launch_stack_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tange
 #define TAN(CELL, LIN, NQ)                                                                                  \
   hipLaunchKernelGGL((k_stack_tangent<CELL, LIN, NQ>), grid, blk, 0, traj->eng->stream, net, tv, ws, traj->d, \
                      traj->seq.out, d_skip)
-#define TAN_OUT(CELL, LIN)                   \
-  do {                                       \
-    if (mod->out_dim > 2) TAN(CELL, LIN, 8); \
-    else TAN(CELL, LIN, 2);                  \
+#define TAN_OUT(CELL, LIN)                \
+  do {                                    \
+    if (nq == 12) TAN(CELL, LIN, 12);     \
+    else if (nq == 8) TAN(CELL, LIN, 8);  \
+    else TAN(CELL, LIN, 2);               \
   } while (0)
+  const int nq = out_class(mod);
   if (mod->kind == RL_MODULE_LSTM_MLP) {
     if (mod->linear_tail()) TAN_OUT(LSTM, true);
     else TAN_OUT(LSTM, false);

@@ -11,9 +11,24 @@
 
 // v[act] of a register array without dynamic indexing (which would put the array in scratch): a compare-select chain
 // over the unrolled index.  A = 2: `act == 0 ? v[0] : v[1]`.
+// Above eight actions (rl_rnn_chain_create_wide) every element is read into a value BEFORE its compare: with the read
+// inside the conditional arm the compiler merges the arms' loads into one load through a selected ADDRESS — a run-time
+// index after all — and keeps the array in memory: LDS up to eight actions (what those kernels have always had, and
+// keep: their resource figures are pinned in DESIGN.md), scratch from ten on.
 template <int A>
 __device__ __forceinline__ float select_action(const float (&v)[A], int act) {
   float r = v[A - 1];
+  if constexpr (A > 8) {
+    float e[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) e[a] = v[a];
+#pragma unroll
+    for (int a = A - 2; a >= 0; --a) {
+      const float va = e[a];
+      r = act == a ? va : r;
+    }
+    return r;
+  }
 #pragma unroll
   for (int a = A - 2; a >= 0; --a) r = act == a ? v[a] : r;
   return r;
@@ -21,14 +36,14 @@ __device__ __forceinline__ float select_action(const float (&v)[A], int act) {
 
 // z: logits; dzt: tangent logits (PASS_JVP); act: the action taken; adv: advantage (DQN: the target).
 // Writes dz[a * B + b] (and lp0 in PASS_INIT); adds to the f64 sums s0, s1, s2 of the pass.
-// A: the number of actions (IndexSpace::new(A)), 2..8, deduced from the logits; the fused single-layer kernels call it
-// at A = 2.
+// A: the number of actions (IndexSpace::new(A)), 2..12, deduced from the logits; the fused single-layer kernels call it
+// at A = 2, the feed-forward modules at up to 8, the recurrent chains of rl_rnn_chain_create_wide at up to 12.
 template <int MODE, int A>
 __device__ __forceinline__ void policy_sample_terms(const float (&z)[A], const float (&dzt)[A], int act, float adv,
                                                 size_t b, size_t B, float *__restrict__ lp0, float *__restrict__ dz,
                                                 float inv_B, float clip_lo, float clip_hi, double &s0, double &s1,
                                                 double &s2) {
-  static_assert(A >= 2 && A <= 8, "categorical policies over 2..8 actions");
+  static_assert(A >= 2 && A <= 12, "categorical policies over 2..12 actions");
   if (MODE == PASS_JVP) {
   float lp[A], p[A];
   log_softmax_lane<A>(z, lp);

@@ -6,8 +6,9 @@ recurrent chain each, chosen by `model`:
             Linear(128, out), ra.GruLinear
     mlp     (the default) GRU(128) -> Relu -> Linear(128, 128) -> Relu -> Linear(128, out), ra.GruMlp: the chain with
             an MLP tail, one hidden layer more than the experiment's model
-`arms` is 2 (the default), 3 or 4: two arms build the two-action constructors' modules, three and four the same chains
-with one output per arm through ra.RnnChain (rl_rnn_chain_create).  Every lane collects whole
+`arms` is 2 (the default) .. 12 (the experiment's own default is 10): two arms build the two-action constructors'
+modules, three and more the same chains with one output per arm through ra.RnnChainWide (rl_rnn_chain_create_wide; up to
+four arms and eight features that is rl_rnn_chain_create), on ra.MetaBanditEnvWide lanes.  Every lane collects whole
 trials per period (horizon = trials_per_lane * (2 * episodes - 1)); the mean trial reward of a period comes from the
 device-side StepsSummary (an episode of the summary is a trial).  Prints one JSON line per period.
 
@@ -28,21 +29,21 @@ dist, H, critic_steps = arg(5, "uniform_bernoulli"), arg(6, 128), arg(7, 50)
 model = arg(8, "mlp")
 arms = arg(9, 2)
 assert model in ("mlp", "linear"), "model: mlp | linear"
-assert arms in (2, 3, 4), "arms: 2 | 3 | 4"
+assert 2 <= arms <= 12, "arms: 2..12"
 T = trials * (2 * E - 1)
 
 eng = ra.Engine(0)
-env = ra.MetaBanditEnv(eng, N, arms, E, dist, seed_env=0, seed_actor=1)
+env = ra.MetaBanditEnvWide(eng, N, arms, E, dist, seed_env=0, seed_actor=1)
 if model == "linear":
-    pol = ra.GruLinear(eng, env.D, 2, H) if arms == 2 else ra.RnnChain(eng, "gru", env.D, H, arms)
-    cri = ra.GruLinear(eng, env.D, 1, H)
+    pol = ra.GruLinear(eng, env.D, 2, H) if arms == 2 else ra.RnnChainWide(eng, "gru", env.D, H, arms)
+    cri = ra.GruLinear(eng, env.D, 1, H) if env.D <= 8 else ra.RnnChainWide(eng, "gru", env.D, H, 1)
     glorot = ("Uniform", "FanAvg", 0.0)
     gru_config = (glorot, ("Orthogonal", "FanAvg", 0.0), ("Zeros", "FanAvg", 0.0))
     pol.init_with(2, *gru_config, glorot, glorot)  # the experiment's GruConfig, LinearConfig::default
     cri.init_with(3, *gru_config, glorot, glorot)
 else:
-    pol = ra.GruMlp(eng, env.D, 2, H, H) if arms == 2 else ra.RnnChain(eng, "gru", env.D, H, arms, mlp_hidden=H)
-    cri = ra.GruMlp(eng, env.D, 1, H, H)
+    pol = ra.GruMlp(eng, env.D, 2, H, H) if arms == 2 else ra.RnnChainWide(eng, "gru", env.D, H, arms, mlp_hidden=H)
+    cri = ra.GruMlp(eng, env.D, 1, H, H) if env.D <= 8 else ra.RnnChainWide(eng, "gru", env.D, H, 1, mlp_hidden=H)
     pol.init(2)  # input weights Uniform(FanAvg), hidden weights Orthogonal, biases Zeros: the experiment's GruConfig
     cri.init(3)
 opt = ra.Adam(cri)

@@ -3,8 +3,8 @@ meta-bandit lanes: a classical bandit algorithm, wrapped in a ResettingMetaAgent
 trial, over `MetaEnv::new(D::new(arms)).wrap(TrialEpisodeLimit::new(episodes))` for `trials` trials — one lane per trial,
 one collection of 2 * episodes - 1 steps.  `agent` is one of the experiment's AgentType values the library builds:
 random, eps_greedy (tabular Q-learning 0.2, 2, 0.5), greedy (0.0, 2, 0.5), ucb1 (0.2), ts (Beta Thompson sampling,
-num_samples 1), ots (num_samples 10) — all six of the experiment's; 2..4 arms (the reference's default
-of ten does not fit the lanes' eight observation features).  The summary is the device-side StepsSummary, of which an
+num_samples 1), ots (num_samples 10) — all six of the experiment's; 2..12 arms (the reference's default is ten;
+ra.MetaBanditEnvWide).  The summary is the device-side StepsSummary, of which an
 episode is a trial.  Prints one JSON line with the reference's EvalResults: trial_reward_mean, trial_reward_stddev.
 
     python scripts/rl2_bandits_eval.py [agent] [arms] [episodes] [trials] [distribution]
@@ -31,7 +31,7 @@ kind, params = AGENTS[name]
 T = 2 * E - 1
 
 eng = ra.Engine(0)
-env = ra.MetaBanditEnv(eng, trials, arms, E, dist, seed_env=0, seed_actor=1)
+env = ra.MetaBanditEnvWide(eng, trials, arms, E, dist, seed_env=0, seed_actor=1)
 agent = ra.BanditAgent(env, kind, **params)
 traj = ra.Trajectory(eng, trials, T, env.D)
 summary = ra.StepsSummary(eng, trials)
