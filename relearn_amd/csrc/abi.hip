@@ -3,6 +3,7 @@
 #include <dlfcn.h>
 
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <map>
 #include <mutex>
@@ -143,6 +144,8 @@ void rccl_check(int rc, const char *what) {
 // (`bad_rank` >= 0: a test of the tests — that rank's vector enters the sum multiplied by `bad_weight`, what a rank that
 // weighs its samples by a wrong B_local / B_total contributes; every rank still receives the same sums, so the job runs
 // to its end and must FAIL the sharded parity bars: tests/test_gpu_multirank.py, RELEARN_LOOPBACK_TEST_WEIGHT)
+// (RELEARN_LOOPBACK_TIMEOUT_MS, read like the weight when the group is made: the deadline of one barrier wait, 120 s by
+// default: tests/test_gpu_sharded_modules.py)
 __global__ void k_loopback_sum(float *const *bufs, int n_ranks, size_t count, int bad_rank, float bad_weight) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
@@ -160,15 +163,26 @@ struct LoopbackGroup {
   float **d_bufs = nullptr;
   int bad_rank = -1;        // RELEARN_LOOPBACK_TEST_WEIGHT="rank:weight" when the group was made (k_loopback_sum)
   float bad_weight = 1.0f;  // ... applied to the gradient-sized vectors only (the set-up's rank count stays a count)
+  // A rank that never arrives (it raised, or returned early) must not strand its peers' host threads: a wait ends after
+  // `deadline` (RELEARN_LOOPBACK_TIMEOUT_MS when the group was made), the group is then failed for good, and every rank
+  // that is in a barrier or enters one later gets RL_ERR_COMM.  (Host side only: a waiting rank has synchronised its
+  // stream before it waits, no kernel is in flight.)
+  std::chrono::milliseconds deadline{120000};
+  bool failed = false;
   void barrier(std::unique_lock<std::mutex> &lk) {
+    if (failed) throw RlError(RL_ERR_COMM, "loopback collective: a peer did not arrive");
     const uint64_t gen = generation;
     if (++arrived == n_ranks) {
       arrived = 0;
       generation += 1;
       cv.notify_all();
-    } else {
-      cv.wait(lk, [&] { return generation != gen; });
+      return;
     }
+    if (!cv.wait_for(lk, deadline, [&] { return generation != gen || failed; })) {
+      failed = true;
+      cv.notify_all();
+    }
+    if (generation == gen) throw RlError(RL_ERR_COMM, "loopback collective: a peer did not arrive");
   }
 };
 static std::mutex g_loopback_mu;
@@ -476,6 +490,10 @@ int32_t rl_comm_init(rl_engine *e, int32_t rank, int32_t n_ranks, const uint8_t 
           int r = -1;
           float w = 1.0f;
           if (std::sscanf(tw, "%d:%f", &r, &w) == 2 && r >= 0 && r < n_ranks) grp->bad_rank = r, grp->bad_weight = w;
+        }
+        if (const char *tm = std::getenv("RELEARN_LOOPBACK_TIMEOUT_MS")) {
+          long long ms = 0;
+          if (std::sscanf(tm, "%lld", &ms) == 1 && ms > 0) grp->deadline = std::chrono::milliseconds(ms);
         }
       }
       RL_REQUIRE(grp->n_ranks == n_ranks, "loopback group: inconsistent n_ranks");
