@@ -70,7 +70,8 @@ enum { RL_OPT_OK = 0, RL_OPT_LOSS_NOT_IMPROVING = 1, RL_OPT_CONSTRAINT_VIOLATED 
        RL_OPT_NAN_CONSTRAINT = 4 };
 /* env kinds / step-limit wrappers (src/envs/cartpole.rs, chain.rs, wrappers/step_limit.rs:13,97) */
 enum { RL_ENV_CARTPOLE = 0, RL_ENV_CHAIN = 1, RL_ENV_MEMORY = 2, RL_ENV_BANDIT = 3,
-       RL_ENV_META_BANDIT = 4 /* rl_env_create_meta_bandit only (src/envs/meta.rs) */ };
+       RL_ENV_META_BANDIT = 4 /* rl_env_create_meta_bandit only (src/envs/meta.rs) */,
+       RL_ENV_TABULAR_MDP = 5 /* rl_env_create_tabular_mdp only (src/envs/mdps.rs) */ };
 /* bandit distributions of a meta-bandit env (src/envs/bandits.rs:128-243, src/envs/testing.rs:108-160) */
 enum { RL_BANDITS_UNIFORM_BERNOULLI = 0, RL_BANDITS_ONE_HOT = 1, RL_BANDITS_ROUND_ROBIN = 2 };
 enum { RL_LIMIT_NONE = 0, RL_LIMIT_LATENT = 1, RL_LIMIT_VISIBLE = 2 };
@@ -258,6 +259,60 @@ int32_t rl_env_create_meta_bandit(rl_engine *engine, const rl_env_config *cfg, c
  * rl_env_get_state / rl_env_set_state and rl_actor_to_cbor refuse every meta lane by name. */
 int32_t rl_env_create_meta_bandit_wide(rl_engine *engine, const rl_env_config *cfg, const rl_meta_bandit_config *meta,
                                        rl_env **out);
+/* Tabular MDP lanes: `TabularMdp<_, Normal<f64>>` (src/envs/mdps.rs:12-85), any finite MDP of 2..8 states and 2..8
+ * actions given as tables; ONE MDP shared by all lanes.  `cfg` supplies the lanes, the lane offset, the seeds and the step
+ * limit, as in rl_env_create_bandit; its kind is not read.  The handle's kind is RL_ENV_TABULAR_MDP.
+ *   transitions   [S][A][S] f32, transitions[s][a][j] = P(s' = j | s, a); every row sums to 1
+ *   reward_mean   [S][A] f64;  reward_stddev [S][A] f64, NULL: 1.0 everywhere (DirichletRandomMdps, mdps.rs:163)
+ * Semantics.  initial_state is state 0 and draws nothing; the observation is the one-hot of the state, then `remaining`
+ * under a VisibleStepLimit: n_states [+ 1] features, at most 8 — the lanes end at 8, so the reference's default
+ * 10 x 5 does not build.  rl_env_dims returns (n_states [+ 1], n_actions).  A step in state s with action a takes its
+ * draws sequentially from the lane's env stream at the even word position env_pos (as MemoryGame and meta lanes do):
+ *   1. successor: one u64 at env_pos (env_pos += 2; always drawn), u = the low word as rl_u32_to_unit_f32 makes it,
+ *      s' = #{ j < S - 1 : cum[s][a][j] <= u } with cum the f32 running sum of the row in index order, formed once on the
+ *      host (from the row's last successor of positive probability on, the entries are exactly 1: no draw reaches 1, so
+ *      the rounding of a running sum opens no bucket behind it); u == cum[j] goes to the bucket after j, a
+ *      zero-probability successor is never reached
+ *   2. reward: stddev[s][a] == 0: the mean, no draw; otherwise the polar normal z of include/rl_normal.h from env_pos
+ *      (4 words per attempt); reward = (float)(mean + stddev * z), formed in f64
+ *   3. always Successor::Continue, then the step-limit tail of the index lanes: an Interrupt at 0 remaining steps, the
+ *      successor observation is written, then a reset.  RL_LIMIT_NONE: episodes never end, as on Chain lanes.
+ * Lane state, in the columns MemoryGame uses: rl_env_get_state / rl_env_set_state work, state4[0] the state index,
+ * state4[2] env_pos, plus steps_remaining and reset_count.
+ * RL_ERR_BUILD_ENV: n_states or n_actions outside 2..8; n_states + 1 > 8 under a VisibleStepLimit; a probability that is
+ * negative or not finite; a row whose f32 running sum differs from 1 by more than 1e-5; a mean that is not finite; a
+ * stddev that is negative or not finite; what every env refuses of `cfg` (lanes, step limit).  A NULL pointer other than
+ * reward_stddev: RL_ERR_INVALID_ARGUMENT.
+ * Agents: rl_rollout with feed-forward modules of (obs_dim -> n_actions) and recurrent chains of rl_rnn_chain_create, a
+ * launch sequence per step (a two-output module of the five older constructors on more than two actions ->
+ * RL_ERR_UNSUPPORTED, as on every env of another width than its own); every update on what
+ * it collected; rl_summary_*; the sharding over ranks (streams are keyed by global lane).  DQN: rl_dqn_create_finite with
+ * a feed-forward action-value module on the per-layer kernels, at every n_actions 2..8 (step-wise collection); a module of
+ * the fused shape (4 or 5 inputs, one ReLU layer of at most 128 units, two outputs, biases), a recurrent module,
+ * rl_dqn_create and rl_dqn_create_recurrent -> RL_ERR_UNSUPPORTED by name.  rl_actor_to_cbor writes the form MemoryGame
+ * lanes use: IndexSpace observation of n_states and action of n_actions, with the step-limit wrapper as there. */
+typedef struct {
+  uint32_t n_states, n_actions;
+  double discount_factor;
+} rl_tabular_mdp_config;
+int32_t rl_env_create_tabular_mdp(rl_engine *engine, const rl_env_config *cfg, const rl_tabular_mdp_config *mdp,
+                                  const float *transitions, const double *reward_mean, const double *reward_stddev,
+                                  rl_env **out);
+/* `DirichletRandomMdps` (mdps.rs:87-171), the distribution of the second task of the RL^2 paper, and its
+ * sample_environment on the host: no engine, no device.  num_states, num_actions 1..64; alpha > 0; stddev >= 0; every
+ * field finite; anything else -> RL_ERR_INVALID_ARGUMENT.  Consumes ONE stream, ChaCha8Rng::seed_from_u64(seed) with
+ * set_stream(stream), sequentially, in the reference's order, row-major over (s, a): the S Gamma(alpha, 1) draws of the
+ * row's Dirichlet sample (include/rl_normal.h), normalised in f64 and each cast to f32 -> transitions[s][a][.]; then the
+ * row's reward mean, reward_prior_mean + reward_prior_stddev * z -> reward_mean[s][a].  The reward stddev of the sampled
+ * MDP is 1 everywhere (mdps.rs:163). */
+typedef struct {
+  uint64_t num_states, num_actions;
+  double transition_prior_dirichlet_alpha, reward_prior_mean, reward_prior_stddev, discount_factor;
+} rl_random_mdps_config;
+/* DirichletRandomMdps::default (mdps.rs:111-122): 10, 5, 1, 1, 1, 1 */
+int32_t rl_random_mdps_config_default(rl_random_mdps_config *cfg);
+int32_t rl_random_mdps_sample(const rl_random_mdps_config *cfg, uint64_t seed, uint64_t stream, float *transitions,
+                              double *reward_mean);
 int32_t rl_env_destroy(rl_env *env);
 /* number of observation features (CartPole 4, +1 `remaining` under VisibleStepLimit) and actions */
 int32_t rl_env_dims(const rl_env *env, uint32_t *obs_dim, uint32_t *n_actions);
@@ -795,6 +850,9 @@ int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const r
  *                                             for a recurrent one, through them: same kernels, same bytes, same refusals
  *   RL_ENV_BANDIT of 3..8 arms                5 observation features
  *   RL_ENV_MEMORY, MemoryGame(k >= 3, h)      k + h, + 1 under a visible step limit: 4..8 (6..8: the second record array)
+ *   RL_ENV_TABULAR_MDP, 2..8 actions          n_states, + 1 under a visible step limit: 2..8; two actions too build HERE,
+ *                                             with a feed-forward module on the per-layer kernels alone (a module of
+ *                                             the fused shape or a recurrent one -> RL_ERR_UNSUPPORTED)
  * with any feed-forward module of obs_dim inputs and n_actions outputs (rl_mlp_create_layers: always the per-layer
  * kernels, collection step by step), or any recurrent chain of n_actions outputs from rl_rnn_chain_create (GRU or LSTM, Mlp
  * or Linear tail, 1..4 layers: collection is one launch per horizon).

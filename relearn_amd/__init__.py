@@ -25,7 +25,7 @@ ERR_INVALID_ARGUMENT, ERR_HIP, ERR_NO_DEVICE, ERR_BUILD_AGENT, ERR_BUILD_ENV = 1
 ERR_BUFFER_FULL, ERR_PACKING, ERR_COMM, ERR_OPT_NAN, ERR_UNSUPPORTED = 6, 7, 8, 9, 10
 SUCC_CONTINUE, SUCC_TERMINATE, SUCC_INTERRUPT = 0, 1, 2
 OPT_OK, OPT_LOSS_NOT_IMPROVING, OPT_CONSTRAINT_VIOLATED, OPT_NAN_LOSS, OPT_NAN_CONSTRAINT = range(5)
-ENV_CARTPOLE, ENV_CHAIN, ENV_MEMORY, ENV_BANDIT, ENV_META_BANDIT = 0, 1, 2, 3, 4
+ENV_CARTPOLE, ENV_CHAIN, ENV_MEMORY, ENV_BANDIT, ENV_META_BANDIT, ENV_TABULAR_MDP = 0, 1, 2, 3, 4, 5
 BANDITS_UNIFORM_BERNOULLI, BANDITS_ONE_HOT, BANDITS_ROUND_ROBIN = 0, 1, 2
 BANDIT_DISTRIBUTIONS = {"uniform_bernoulli": BANDITS_UNIFORM_BERNOULLI, "one_hot": BANDITS_ONE_HOT,
                         "round_robin": BANDITS_ROUND_ROBIN}
@@ -49,7 +49,7 @@ ABI_SYMBOLS = [
     "rl_last_error", "rl_engine_info", "rl_engine_set_kernel_variant", "rl_timer_begin", "rl_timer_end", "rl_profile_enable", "rl_profile_read",
     "rl_comm_available", "rl_comm_library_paths", "rl_comm_unique_id", "rl_comm_init", "rl_comm_destroy", "rl_comm_init_host",
     "rl_comm_ipc_handle", "rl_comm_init_ipc", "rl_comm_selftest",
-    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
+    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_create_tabular_mdp", "rl_random_mdps_config_default", "rl_random_mdps_sample", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
@@ -99,6 +99,17 @@ class EnvConfig(C.Structure):
 
 class MetaBanditConfig(C.Structure):
     _fields_ = [("n_arms", C.c_uint32), ("distribution", C.c_int32), ("episodes_per_trial", C.c_uint64)]
+
+
+class TabularMdpConfig(C.Structure):
+    _fields_ = [("n_states", C.c_uint32), ("n_actions", C.c_uint32), ("discount_factor", C.c_double)]
+
+
+class RandomMdpsConfig(C.Structure):
+    """DirichletRandomMdps (src/envs/mdps.rs:87-122)"""
+    _fields_ = [("num_states", C.c_uint64), ("num_actions", C.c_uint64),
+                ("transition_prior_dirichlet_alpha", C.c_double), ("reward_prior_mean", C.c_double),
+                ("reward_prior_stddev", C.c_double), ("discount_factor", C.c_double)]
 
 
 class TrpoConfig(C.Structure):
@@ -215,7 +226,7 @@ def _register(obj):
 @atexit.register
 def _close_all():
     objs = list(_live)
-    order = {"StepsSummary": -1, "Dqn": -1, "BanditAgent": -1, "Adam": 0, "Optimizer": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "MetaBanditEnv": 2, "MetaBanditEnvWide": 2, "Mlp": 3, "GruMlp": 3,
+    order = {"StepsSummary": -1, "Dqn": -1, "BanditAgent": -1, "Adam": 0, "Optimizer": 0, "Trajectory": 1, "CartPoleEnv": 2, "ChainEnv": 2, "MetaBanditEnv": 2, "MetaBanditEnvWide": 2, "TabularMdpEnv": 2, "Mlp": 3, "GruMlp": 3,
              "Engine": 4}
     for o in sorted(objs, key=lambda o: order.get(type(o).__name__, 2)):
         o.close()
@@ -574,6 +585,73 @@ class MetaBanditEnvWide(MetaBanditEnv):
     what MetaBanditEnv builds).  Above four arms: recurrent chains of RnnChainWide and BanditAgent."""
 
     CREATE = "rl_env_create_meta_bandit_wide"
+
+
+def random_mdps_config_default():
+    """DirichletRandomMdps::default(): 10 states, 5 actions, alpha 1, reward prior N(1, 1), discount factor 1"""
+    c = RandomMdpsConfig()
+    _check(lib().rl_random_mdps_config_default(C.byref(c)))
+    return c
+
+
+def sample_random_mdp(cfg=None, seed=0, stream=0):
+    """DirichletRandomMdps::sample_environment on the host (no engine, no device) from ChaCha8Rng::seed_from_u64(seed)
+    with set_stream(stream) -> (transitions [S][A][S] f32, reward_mean [S][A] f64); the reward stddev is 1 everywhere"""
+    cfg = cfg if cfg is not None else random_mdps_config_default()
+    S, A = max(int(cfg.num_states), 0), max(int(cfg.num_actions), 0)
+    ok = 1 <= S <= 64 and 1 <= A <= 64  # (the library refuses the rest before it writes; the buffers only need to exist)
+    tr = np.zeros((S, A, S) if ok else (1,), dtype=np.float32)
+    mean = np.zeros((S, A) if ok else (1,), dtype=np.float64)
+    _check(lib().rl_random_mdps_sample(C.byref(cfg), C.c_uint64(seed), C.c_uint64(stream),
+                                       tr.ctypes.data_as(C.c_void_p), mean.ctypes.data_as(C.c_void_p)))
+    return tr, mean
+
+
+class TabularMdpEnv(ChainEnv):
+    """N lanes of one tabular MDP (src/envs/mdps.rs:12-85) — `TabularMdp { transitions, discount_factor }`, optionally
+    wrapped in a step limit: `transitions` [S][A][S] (rows sum to 1), `reward_mean` [S][A], `reward_stddev` [S][A] or None
+    (1 everywhere).  2..8 states and actions; observations one-hot(S) [+ remaining under a visible limit], at most 8."""
+
+    def __init__(self, engine, transitions, reward_mean, reward_stddev=None, n_lanes=1, max_steps=0, limit=LIMIT_NONE,
+                 lane_offset=0, seed_env=0, seed_actor=1, discount_factor=1.0):
+        self.eng = engine
+        cfg = EnvConfig()
+        cfg.kind = ENV_TABULAR_MDP
+        cfg.limit_kind = limit
+        cfg.max_steps = max_steps
+        cfg.n_lanes = n_lanes
+        cfg.lane_offset = lane_offset
+        cfg.seed_env = seed_env
+        cfg.seed_actor = seed_actor
+        cfg.cartpole = cartpole_params_default()
+        tr = np.ascontiguousarray(transitions, dtype=np.float32)
+        mean = np.ascontiguousarray(reward_mean, dtype=np.float64)
+        assert tr.ndim == 3 and tr.shape[0] == tr.shape[2] and mean.shape == tr.shape[:2], "tables: [S][A][S] and [S][A]"
+        sd = None if reward_stddev is None else np.ascontiguousarray(reward_stddev, dtype=np.float64)
+        assert sd is None or sd.shape == mean.shape, "reward_stddev: [S][A]"
+        mdp = TabularMdpConfig()
+        mdp.n_states, mdp.n_actions, mdp.discount_factor = tr.shape[0], tr.shape[1], discount_factor
+        self.cfg, self.mdp = cfg, mdp
+        self.h = C.c_void_p()
+        _check(lib().rl_env_create_tabular_mdp(engine.h, C.byref(cfg), C.byref(mdp), tr.ctypes.data_as(C.c_void_p),
+                                               mean.ctypes.data_as(C.c_void_p),
+                                               sd.ctypes.data_as(C.c_void_p) if sd is not None else None,
+                                               C.byref(self.h)), engine.h)
+        _register(self)
+        self.n = n_lanes
+        d, a = C.c_uint32(), C.c_uint32()
+        _check(lib().rl_env_dims(self.h, C.byref(d), C.byref(a)), engine.h)
+        self.D, self.A = d.value, a.value
+
+    def get_state(self):
+        """(state, env-stream word position, steps_remaining, reset_count) per lane"""
+        st, _, rem, rc = CartPoleEnv.get_state(self)
+        return st[0].astype(np.uint64), st[2].astype(np.uint64), rem, rc
+
+    def set_state(self, state, env_pos, rem, rc):
+        st = np.zeros((4, self.n), dtype=np.float64)
+        st[0], st[2] = state, env_pos
+        CartPoleEnv.set_state(self, st, np.zeros(self.n, dtype=np.int32), rem, rc)
 
 
 class GruMlp(_Handle):

@@ -10,6 +10,7 @@
 
 #include "abi_internal.hpp"
 #include "env_lanes.hpp"
+#include "host/envs.hpp"
 
 thread_local std::string g_last_error_no_engine;
 
@@ -683,11 +684,63 @@ int32_t rl_cartpole_params_default(rl_cartpole_params *p) {
   });
 }
 
+// The tables of rl_env_create_tabular_mdp as the lanes read them (env_lanes.hpp, MdpOps), checked: `cum` [S][A][S] the f32
+// running sums of the successor rows in index order (relearn::TabularMdp::cumulative, host/envs.hpp: from a row's last
+// successor of positive probability on, the entries are exactly 1 — no draw reaches 1, so the rounding of a running sum,
+// which may end at 1 - 1e-5, opens no bucket behind it), `mean` / `stddev` [S][A].
+struct MdpTables {
+  uint32_t S = 0, A = 0;
+  std::vector<float> cum;
+  std::vector<double> mean, stddev;
+};
+
+static MdpTables mdp_tables(const rl_env_config *cfg, const rl_tabular_mdp_config *mdp, const float *transitions,
+                            const double *reward_mean, const double *reward_stddev) {
+  MdpTables t;
+  const uint32_t S = mdp->n_states, A = mdp->n_actions;
+  if (S < 2 || S > RL_TRAJ_MAX_OBS_DIM || A < 2 || A > RL_MLP_MAX_OUT)
+    throw RlError(RL_ERR_BUILD_ENV, "tabular-MDP lanes: n_states 2..8 and n_actions 2..8 (the lanes end at 8)");
+  if (S + (cfg->limit_kind == RL_LIMIT_VISIBLE ? 1u : 0u) > RL_TRAJ_MAX_OBS_DIM)
+    throw RlError(RL_ERR_BUILD_ENV, "tabular-MDP lanes: n_states + 1 observation features under a VisibleStepLimit, at "
+                                    "most 8 in total");
+  if (!std::isfinite(mdp->discount_factor))
+    throw RlError(RL_ERR_BUILD_ENV, "tabular-MDP lanes: discount_factor is not finite");
+  t.S = S;
+  t.A = A;
+  t.cum.resize((size_t)S * A * S);
+  t.mean.resize((size_t)S * A);
+  t.stddev.resize((size_t)S * A);
+  for (uint32_t row = 0; row < S * A; ++row) {
+    const std::string where = " (state " + std::to_string(row / A) + ", action " + std::to_string(row % A) + ")";
+    const float *p = transitions + (size_t)row * S;
+    float acc = 0.0f;
+    for (uint32_t j = 0; j < S; ++j) {
+      if (!std::isfinite(p[j]) || p[j] < 0.0f)
+        throw RlError(RL_ERR_BUILD_ENV, "tabular-MDP lanes: a transition probability is negative or not finite" + where);
+      acc = acc + p[j];
+    }
+    if (!(std::fabs((double)acc - 1.0) <= 1e-5))
+      throw RlError(RL_ERR_BUILD_ENV, "tabular-MDP lanes: a transition row does not sum to 1 within 1e-5" + where);
+    if (!std::isfinite(reward_mean[row]))
+      throw RlError(RL_ERR_BUILD_ENV, "tabular-MDP lanes: a reward mean is not finite" + where);
+    const double sd = reward_stddev != nullptr ? reward_stddev[row] : 1.0;  // mdps.rs:163
+    if (!std::isfinite(sd) || sd < 0.0)
+      throw RlError(RL_ERR_BUILD_ENV, "tabular-MDP lanes: a reward stddev is negative or not finite" + where);
+    t.mean[row] = reward_mean[row];
+    t.stddev[row] = sd;
+  }
+  // the running sums: the scalar mirror's (host/envs.hpp), one statement for both
+  t.cum = relearn::TabularMdp(S, A, std::vector<float>(transitions, transitions + t.cum.size()), t.mean, t.stddev).cumulative;
+  return t;
+}
+
 // `arm_values` / `n_arms`: DeterministicBandit::from_values for rl_env_create_bandit (NULL: cfg->bandit_values, two arms)
 // `meta`: rl_env_create_meta_bandit (the env kind is then RL_ENV_META_BANDIT whatever cfg->kind says)
 // `wide`: rl_env_create_meta_bandit_wide — up to RL_WIDE_MAX_OBS_DIM - 4 = 12 arms
+// `mdp`: rl_env_create_tabular_mdp (the env kind is then RL_ENV_TABULAR_MDP whatever cfg->kind says)
 static int32_t env_create(rl_engine *e, const rl_env_config *cfg_in, const double *arm_values, uint32_t n_arms,
-                          const rl_meta_bandit_config *meta, rl_env **out, bool wide = false) {
+                          const rl_meta_bandit_config *meta, rl_env **out, bool wide = false,
+                          const MdpTables *mdp = nullptr) {
   return guarded(e, [&] {
     RL_REQUIRE(e && cfg_in && out, "NULL argument");
     *out = nullptr;
@@ -710,11 +763,15 @@ static int32_t env_create(rl_engine *e, const rl_env_config *cfg_in, const doubl
         throw RlError(RL_ERR_BUILD_ENV, "meta-bandit lanes: unknown bandit distribution");
       if (cfg->limit_kind != RL_LIMIT_NONE)
         throw RlError(RL_ERR_BUILD_ENV, "meta-bandit lanes take no step limit (the trial's episode limit is this env's limit)");
+    } else if (mdp != nullptr) {
+      cfg->kind = RL_ENV_TABULAR_MDP;
     } else if (cfg->kind == RL_ENV_META_BANDIT) {
       throw RlError(RL_ERR_BUILD_ENV, "RL_ENV_META_BANDIT lanes are created by rl_env_create_meta_bandit");
+    } else if (cfg->kind == RL_ENV_TABULAR_MDP) {
+      throw RlError(RL_ERR_BUILD_ENV, "RL_ENV_TABULAR_MDP lanes are created by rl_env_create_tabular_mdp");
     }
     if (cfg->kind != RL_ENV_CARTPOLE && cfg->kind != RL_ENV_CHAIN && cfg->kind != RL_ENV_MEMORY &&
-        cfg->kind != RL_ENV_BANDIT && cfg->kind != RL_ENV_META_BANDIT)
+        cfg->kind != RL_ENV_BANDIT && cfg->kind != RL_ENV_META_BANDIT && cfg->kind != RL_ENV_TABULAR_MDP)
       throw RlError(RL_ERR_BUILD_ENV, "unknown env kind");
     const uint64_t mem_actions = cfg->memory_num_actions ? cfg->memory_num_actions : 2;
     const uint64_t mem_history = cfg->memory_num_actions || cfg->memory_history_len ? cfg->memory_history_len : 3;
@@ -752,6 +809,10 @@ static int32_t env_create(rl_engine *e, const rl_env_config *cfg_in, const doubl
       env->D = cfg->limit_kind == RL_LIMIT_VISIBLE ? 5 : 4;
     env->A = cfg->kind == RL_ENV_MEMORY ? (uint32_t)mem_actions : (arm_values != nullptr ? n_arms : 2u);
     if (meta != nullptr) env->A = meta->n_arms;
+    if (mdp != nullptr) {  // one-hot(states) [+ remaining]: index_features
+      env->D = mdp->S + (cfg->limit_kind == RL_LIMIT_VISIBLE ? 1 : 0);
+      env->A = mdp->A;
+    }
     const rl_cartpole_params &p = cfg->cartpole;
     CartPoleDev &d = env->dev;
     d.gravity = p.gravity;
@@ -805,6 +866,22 @@ static int32_t env_create(rl_engine *e, const rl_env_config *cfg_in, const doubl
     env->d_reward = mem.alloc<float>(n);
     env->d_obs = mem.alloc<float>(n * env->D);
     env->d_term_obs = mem.alloc<float>(n * env->D);
+    if (mdp != nullptr) {
+      // the tables: one allocation of the handle, the f64 tables first so that both are aligned
+      const size_t rows = (size_t)mdp->S * mdp->A, bytes = rows * 16 + rows * mdp->S * sizeof(float);
+      uint8_t *tab = mem.alloc<uint8_t>(bytes);
+      std::vector<uint8_t> img(bytes);
+      std::memcpy(img.data(), mdp->mean.data(), rows * 8);
+      std::memcpy(img.data() + rows * 8, mdp->stddev.data(), rows * 8);
+      std::memcpy(img.data() + rows * 16, mdp->cum.data(), rows * mdp->S * sizeof(float));
+      h2d(e, tab, img.data(), bytes);
+      d.chain_size = 0;  // (as on meta lanes: nothing takes these for an index env of five states)
+      d.mdp.mean = reinterpret_cast<const double *>(tab);  // (over bandit_r, which these lanes do not have)
+      d.mdp.stddev = reinterpret_cast<const double *>(tab + rows * 8);
+      d.mdp.cum = reinterpret_cast<const float *>(tab + rows * 16);
+      d.mdp.states = mdp->S;
+      d.mdp.actions = mdp->A;
+    }
     RL_HIP_CHECK(hipMemsetAsync(env->st.reset_count, 0, n * sizeof(uint32_t), e->stream));
     for (double *p : {env->st.x, env->st.xdot, env->st.th, env->st.thdot})
       RL_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(double), e->stream));
@@ -854,6 +931,51 @@ int32_t rl_env_create_bandit(rl_engine *e, const rl_env_config *cfg, const doubl
                              rl_env **out) {
   if (values == nullptr) return guarded(e, [&] { RL_REQUIRE(values, "NULL argument"); });
   return env_create(e, cfg, values, n_arms, nullptr, out);
+}
+
+// TabularMdp<_, Normal<f64>> (src/envs/mdps.rs:12-85) under the index lanes' step limit
+int32_t rl_env_create_tabular_mdp(rl_engine *e, const rl_env_config *cfg, const rl_tabular_mdp_config *mdp,
+                                  const float *transitions, const double *reward_mean, const double *reward_stddev,
+                                  rl_env **out) {
+  MdpTables tables;
+  const int32_t rc = guarded(e, [&] {
+    RL_REQUIRE(e && cfg && mdp && transitions && reward_mean && out, "rl_env_create_tabular_mdp: NULL argument");
+    *out = nullptr;
+    tables = mdp_tables(cfg, mdp, transitions, reward_mean, reward_stddev);
+  });
+  if (rc != RL_OK) return rc;
+  return env_create(e, cfg, nullptr, 0, nullptr, out, false, &tables);
+}
+
+// DirichletRandomMdps::default (mdps.rs:111-122)
+int32_t rl_random_mdps_config_default(rl_random_mdps_config *cfg) {
+  return guarded(nullptr, [&] {
+    RL_REQUIRE(cfg, "config is NULL");
+    cfg->num_states = 10;
+    cfg->num_actions = 5;
+    cfg->transition_prior_dirichlet_alpha = 1.0;
+    cfg->reward_prior_mean = 1.0;
+    cfg->reward_prior_stddev = 1.0;
+    cfg->discount_factor = 1.0;
+  });
+}
+
+// DirichletRandomMdps::sample_environment (mdps.rs:151-170) on the host: one stream, consumed in the reference's order
+int32_t rl_random_mdps_sample(const rl_random_mdps_config *cfg, uint64_t seed, uint64_t stream, float *transitions,
+                              double *reward_mean) {
+  return guarded(nullptr, [&] {
+    RL_REQUIRE(cfg && transitions && reward_mean, "rl_random_mdps_sample: NULL argument");
+    // (the sampler is the host mirror's, host/envs.hpp: it needs no engine and no device; what it refuses is an
+    // std::invalid_argument naming the field -> RL_ERR_INVALID_ARGUMENT)
+    relearn::DirichletRandomMdps d;
+    d.num_states = cfg->num_states;
+    d.num_actions = cfg->num_actions;
+    d.transition_prior_dirichlet_alpha = cfg->transition_prior_dirichlet_alpha;
+    d.reward_prior_mean = cfg->reward_prior_mean;
+    d.reward_prior_stddev = cfg->reward_prior_stddev;
+    d.discount_factor = cfg->discount_factor;
+    d.sample_tables(seed, stream, transitions, reward_mean);
+  });
 }
 
 // Index::from_index of the env's action space: an index >= num_actions is no action
@@ -1001,6 +1123,14 @@ int32_t rl_env_set_state(rl_env *env, const double *state4, const int32_t *nv_po
       throw RlError(RL_ERR_UNSUPPORTED, "rl_env_set_state is not built for RL_ENV_META_BANDIT lanes");
     rl_engine *e = env->eng;
     size_t n = env->cfg.n_lanes;
+    if (env->kind == RL_ENV_TABULAR_MDP)  // the lane's state indexes the tables; its stream position is an even word
+      for (size_t i = 0; i < n; ++i) {
+        const double st = state4[i], pos = state4[2 * n + i];
+        RL_REQUIRE(st >= 0.0 && st < (double)env->dev.mdp.states && st == std::floor(st),
+                   "rl_env_set_state: tabular-MDP lanes: state index outside 0 .. n_states - 1");
+        RL_REQUIRE(pos >= 0.0 && pos < 9007199254740992.0 && pos == 2.0 * std::floor(pos / 2.0),
+                   "rl_env_set_state: tabular-MDP lanes: env-stream position must be an even word below 2^53");
+      }
     std::vector<uint8_t> nv(n);
     std::vector<uint32_t> a(n), b(n);
     for (size_t i = 0; i < n; ++i) {
@@ -1795,6 +1925,14 @@ int32_t rl_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     if (policy->general || (policy->kind == RL_MODULE_MLP && !fused_index_env)) {
       // any hidden_sizes: one launch sequence per step, either env family (advances t_global)
       launch_gen_rollout(env, policy, traj);
+      return;
+    }
+    if (env->kind == RL_ENV_TABULAR_MDP && rl_module_is_recurrent(policy->kind)) {
+      // tabular-MDP lanes: every recurrent chain, the two-output ones of the tile kernels' shapes included, steps through
+      // the lane-per-thread kernels, a launch sequence per step (a single-layer chain's flat order is the stacked order
+      // at one layer: stack_ensure)
+      stack_ensure(traj, policy, false);
+      launch_stack_rollout(env, policy, traj);  // (advances t_global)
       return;
     }
     if (!fused_index_env && !policy->lane_kernels())

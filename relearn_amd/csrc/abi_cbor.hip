@@ -189,7 +189,7 @@ static void cbor_observation_space(cbor::Writer &w, const rl_env *env) {
     if (env->kind != RL_ENV_CARTPOLE) {
       w.map(1);  // IndexSpace { size } (spaces/index.rs:19-22)
       w.key("size");
-      w.uint(env->dev.chain_size);
+      w.uint(env->kind == RL_ENV_TABULAR_MDP ? env->dev.mdp.states : env->dev.chain_size);  // (mdps.rs:37-39)
       return;
     }
     // CartPolePhysicalStateSpace (envs/cartpole.rs:73-82, 273-284); default intervals = [f64::MIN, f64::MAX]
@@ -233,8 +233,8 @@ int32_t rl_actor_to_cbor(rl_env *env, rl_mlp *module, int32_t actor_kind, double
     w.key("observation_space");
     cbor_observation_space(w, env);
     w.key("action_space");
-    if (env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT) {
-      w.map(1);  // IndexSpace { size } (memory.rs:66-68, bandits.rs:45-47; spaces/index.rs:19-22)
+    if (env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT || env->kind == RL_ENV_TABULAR_MDP) {
+      w.map(1);  // IndexSpace { size } (memory.rs:66-68, bandits.rs:45-47, mdps.rs:41-43; spaces/index.rs:19-22)
       w.key("size");
       w.uint(env->A);
     } else {

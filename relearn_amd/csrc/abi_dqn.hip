@@ -112,6 +112,8 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
     // the bandit) of 4..8 observation features.  Anything else is refused here, by name: no env is collected by another
     // env's code.
     const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
+    if (env->kind == RL_ENV_TABULAR_MDP)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create is not built for RL_ENV_TABULAR_MDP lanes (rl_dqn_create_finite is)");
     if (env->kind != RL_ENV_CARTPOLE && !index_env)
       throw RlError(RL_ERR_UNSUPPORTED, env->kind == RL_ENV_META_BANDIT
                                             ? "rl_dqn_create is not built for RL_ENV_META_BANDIT lanes"
@@ -144,6 +146,8 @@ int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const r
                     "rl_dqn_create_recurrent takes a recurrent action-value module; use rl_dqn_create for a feed-forward one");
     if (env->kind == RL_ENV_META_BANDIT)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_recurrent is not built for RL_ENV_META_BANDIT lanes");
+    if (env->kind == RL_ENV_TABULAR_MDP)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_recurrent is not built for RL_ENV_TABULAR_MDP lanes");
     if (qnet->out_dim > 2 || env->A > 2)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_recurrent: the DQN kernels are built for 2 actions");
     RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A,
@@ -165,7 +169,8 @@ int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const r
 // a feed-forward module (always on the per-layer kernels: step-wise collection) or a recurrent chain of one output per
 // action (rl_rnn_chain_create: k_stack_collect_dqn<.., NA>).
 int32_t rl_dqn_create_finite(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out) {
-  if (env && qnet && env->A <= 2 && qnet->out_dim <= 2 && env->kind != RL_ENV_META_BANDIT)
+  if (env && qnet && env->A <= 2 && qnet->out_dim <= 2 && env->kind != RL_ENV_META_BANDIT &&
+      env->kind != RL_ENV_TABULAR_MDP)
     return rl_module_is_recurrent(qnet->kind) ? rl_dqn_create_recurrent(env, qnet, opt, cfg, out)
                                               : rl_dqn_create(env, qnet, opt, cfg, out);
   return guarded(env ? env->eng : nullptr, [&] {
@@ -178,6 +183,20 @@ int32_t rl_dqn_create_finite(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_d
       throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite is not built for RL_ENV_META_BANDIT lanes");
     RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A,
                "rl_dqn_create_finite: action-value module does not match the env's (obs_dim, n_actions)");
+    if (env->kind == RL_ENV_TABULAR_MDP) {
+      // tabular-MDP lanes: every action count 2..8 and every width 2..8 through the step-wise collection
+      // (k_dqn_lane_step<MdpOps, D, A>), which reads the outputs of a module on the per-layer kernels
+      if (rl_module_is_recurrent(qnet->kind))
+        throw RlError(RL_ERR_UNSUPPORTED,
+                      "rl_dqn_create_finite: recurrent DQN is not built for RL_ENV_TABULAR_MDP lanes");
+      if (qnet->kind != RL_MODULE_MLP || !qnet->general)
+        throw RlError(RL_ERR_UNSUPPORTED,
+                      "rl_dqn_create_finite on RL_ENV_TABULAR_MDP lanes: the action-value module runs the per-layer "
+                      "kernels; a module of the fused shape (4 or 5 inputs, one ReLU layer of at most 128 units, two "
+                      "outputs, with biases) is not collected on these lanes");
+      dqn_build(env, qnet, opt, cfg, out, false);
+      return;
+    }
     // (env->A > 2 from here on: the two-action envs went to the older constructors)
     if (env->kind != RL_ENV_MEMORY && env->kind != RL_ENV_BANDIT)
       throw RlError(RL_ERR_UNSUPPORTED,

@@ -31,6 +31,16 @@ struct RlError : std::runtime_error {
   } while (0)
 
 // ---- device-side plain structs passed by value to kernels ---------------------------------------
+// RL_ENV_TABULAR_MDP (MdpOps, env_lanes.hpp): the tables of the one MDP all lanes share, in one device allocation of the
+// env handle — cum f32 [S][A][S] (running sums of the successor rows), mean and stddev f64 [S][A] — and their sizes
+// (launch-uniform).  32 bytes: it lies over the bandit's eight arm values in CartPoleDev, which these lanes do not have, so
+// that the struct — an argument of every env kernel — keeps its size and every field its offset.
+struct MdpTablesDev {
+  const float *cum;
+  const double *mean, *stddev;
+  uint32_t states, actions;
+};
+
 struct CartPoleDev {
   double gravity, mass_pole, length_half_pole, friction_cart, friction_pole, time_step;
   double action_force, max_pos, max_angle;
@@ -44,13 +54,19 @@ struct CartPoleDev {
                          // history_len)
   uint32_t mem_actions;  // RL_ENV_MEMORY: num_actions (0 selects Chain in the shared lane code)
   uint32_t bandit;       // RL_ENV_BANDIT: != 0; reward = bandit_r[action], every step terminates
-  float bandit_r[8];     // DeterministicBandit::from_values, 2..8 arms
+  union {
+    float bandit_r[8];   // DeterministicBandit::from_values, 2..8 arms
+    MdpTablesDev mdp;    // RL_ENV_TABULAR_MDP
+  };
   // RL_ENV_META_BANDIT (MetaOps, env_lanes.hpp): number of arms k (2..12; above four: rl_env_create_meta_bandit_wide)
   // and the bandit distribution (RL_BANDITS_*); `max_steps` holds TrialEpisodeLimit::episodes_per_trial (the trial limit is this env's limit).  Last, so that the
   // fields above keep their offsets in every kernel's arguments.
   uint32_t meta_arms;
   int32_t meta_dist;
 };
+
+static_assert(sizeof(MdpTablesDev) == 8 * sizeof(float) && sizeof(CartPoleDev) == 248,
+              "the tables lie over the eight arm values: the struct keeps its size");
 
 struct EnvStateDev {
   double *x, *xdot, *th, *thdot;  // [n]; RL_ENV_CHAIN / RL_ENV_MEMORY keep their state index in x, MEMORY also its
@@ -59,6 +75,7 @@ struct EnvStateDev {
   // is the u64 at x + 2 i) or the good arm (OneHot, RoundRobin), xdot = next unread word of the env stream, th = the
   // previous inner step's reward; nv_pos = bit 0 inner episode done, bit 1 prev_step_obs is Some, bits 2-5 its action;
   // steps_remaining = inner episodes remaining in the trial
+  // RL_ENV_TABULAR_MDP: x = state index, th = next unread word of the env stream (MemoryGame's columns; xdot unused)
   uint8_t *nv_pos;                // [n] cached_normal_velocity_is_positive
   uint32_t *steps_remaining;      // [n]
   uint32_t *reset_count;          // [n]

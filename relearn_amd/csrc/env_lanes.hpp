@@ -16,6 +16,7 @@
 
 #include "../../include/rl_chacha.h"
 #include "../../include/rl_detmath.h"
+#include "../../include/rl_normal.h"
 #include "engine.hpp"
 
 // ---------------------------------------------------------------- word `w` of a lane's ChaCha stream
@@ -464,6 +465,69 @@ struct MetaOps {
     s.prev_action = 0;
     s.prev_reward = 0.0f;
     s.remaining = c.max_steps;
+    s.reset_count += 1;
+  }
+};
+
+// ---------------------------------------------------------------- tabular-MDP lanes (RL_ENV_TABULAR_MDP)
+// TabularMdp<_, Normal<f64>> (src/envs/mdps.rs:12-85) under the index lanes' step limit: one MDP of S states and A actions
+// shared by all lanes, given as tables (CartPoleDev::mdp: cum f32 [S][A][S], the running sums of the successor rows;
+// mean and stddev f64 [S][A]).  The lane is MemoryGame's — state index, env-stream word position, step limit — and so
+// are its columns and its one-hot features.  A step draws SEQUENTIALLY from the lane's env stream at `env_pos` (always
+// even): one u64 for the successor, always; then, unless the row's stddev is 0, the polar normal of include/rl_normal.h,
+// 4 words per attempt.  The table index depends on the lane's state: these are vector loads through the CU's vector
+// cache (the tables are at most 3 KiB), nothing is staged.
+struct MdpOps {
+  using State = ChainLane;
+  static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) { chain_load(st, i, s); }
+  static __device__ __forceinline__ void store(const EnvStateDev &st, uint32_t i, const State &s) { chain_store(st, i, s); }
+  template <int D>
+  static __device__ __forceinline__ void features(const CartPoleDev &c, const State &s, float (&f)[D]) {
+    index_features<D>(c, s, f);
+  }
+  // TabularMdp::step (mdps.rs:73-84), then the step-limit tail.  `word` is unused: the draws are sequential.
+  static __device__ __forceinline__ int step(const CartPoleDev &c, State &s, int a, uint64_t glane, uint64_t,
+                                             float &reward) {
+    const uint32_t S = c.mdp.states;
+    // (a state or an action outside the tables cannot come from a step or a checked action; rl_env_set_state checks too:
+    // the clamps keep the loads inside the tables whatever the columns hold)
+    const uint32_t st = s.state < S ? s.state : S - 1;
+    const uint32_t ac = (uint32_t)a < c.mdp.actions ? (uint32_t)a : c.mdp.actions - 1;
+    const uint32_t row = st * c.mdp.actions + ac;
+    const float u = rl_u32_to_unit_f32((uint32_t)lane_u64_at(c.key_env, glane, s.env_pos));
+    s.env_pos += 2;
+    // s' = #{ j < S - 1 : cum[j] <= u }: a compare-add per entry under the launch-uniform bound, no register indexing; the
+    // count cannot leave 0 .. S - 1, and u == cum[j] goes to the bucket after j
+    const float *__restrict__ cum = c.mdp.cum + (size_t)row * S;
+    uint32_t next = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 7; ++j)
+      if (j + 1 < S) next += cum[j] <= u ? 1u : 0u;
+    const double mean = c.mdp.mean[row], stddev = c.mdp.stddev[row];
+    double r = mean;
+    if (stddev != 0.0) {  // rl_normal_sample over the lane's block select: 4 words per attempt, at most 64 attempts
+      double z = 0.0;
+      for (int attempt = 0; attempt < RL_NORMAL_MAX_ATTEMPTS; ++attempt) {
+        const uint64_t w1 = lane_u64_at(c.key_env, glane, s.env_pos);
+        const uint64_t w2 = lane_u64_at(c.key_env, glane, s.env_pos + 2);
+        s.env_pos += 4;
+        if (rl_normal_attempt(w1, w2, &z)) break;
+      }
+      r = mean + stddev * z;
+    }
+    reward = (float)r;
+    s.state = next;
+    if (c.limit_kind != RL_LIMIT_NONE) {
+      s.steps_remaining -= 1;
+      if (s.steps_remaining == 0) return RL_SUCC_INTERRUPT;
+    }
+    return RL_SUCC_CONTINUE;
+  }
+  // TabularMdp::initial_state (mdps.rs:65-67): state 0, no draw
+  static __device__ __forceinline__ void reset(const CartPoleDev &c, State &s, uint64_t) {
+    s.state = 0;
+    s.initial = 0;
+    s.steps_remaining = c.max_steps;
     s.reset_count += 1;
   }
 };

@@ -32,6 +32,7 @@
 #include "../../../include/relearn_hip.h"
 #include "../../../include/rl_detmath.h"
 #include "logging.hpp"
+#include "envs.hpp"
 #include "prng.hpp"
 
 namespace relearn {
@@ -90,6 +91,8 @@ class EnvLanes {
   uint32_t num_observation_features() const { return obs_dim_; }
   uint32_t num_actions() const { return n_actions_; }
   double discount_factor() const { return discount_; }
+  // lanes of rl_env_create_tabular_mdp: DQN builds through rl_dqn_create_finite at every action count, two included
+  bool tabular_mdp() const { return tabular_mdp_; }
   // Environment::{initial_state, observe, step} for every lane (src/envs/mod.rs:76-127)
   void initial_state() { check(rl_env_reset(h_), eng_.handle()); }
   std::vector<float> observe() {
@@ -132,11 +135,23 @@ class EnvLanes {
           eng.handle());
     check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
   }
+  // tabular-MDP lanes (rl_env_create_tabular_mdp); `stddev` empty: 1.0 everywhere
+  EnvLanes(Engine &eng, const rl_env_config &cfg, const rl_tabular_mdp_config &mdp, const std::vector<float> &transitions,
+           const std::vector<double> &mean, const std::vector<double> &stddev)
+      : eng_(eng), cfg_(cfg), discount_(mdp.discount_factor), tabular_mdp_(true) {
+    const size_t rows = (size_t)mdp.n_states * mdp.n_actions;
+    if (transitions.size() != rows * mdp.n_states || mean.size() != rows || (!stddev.empty() && stddev.size() != rows))
+      throw BuildEnvError(RL_ERR_BUILD_ENV, "TabularMdpLanes: tables of [S][A][S] and [S][A]");
+    check(rl_env_create_tabular_mdp(eng.handle(), &cfg_, &mdp, transitions.data(), mean.data(),
+                                    stddev.empty() ? nullptr : stddev.data(), &h_), eng.handle());
+    check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
+  }
   Engine &eng_;
   rl_env_config cfg_;
   rl_env *h_ = nullptr;
   uint32_t obs_dim_ = 0, n_actions_ = 0;
   double discount_;
+  bool tabular_mdp_ = false;
 };
 
 // `CartPole::default().wrap(VisibleStepLimit::new(max_steps))` x n_lanes (src/envs/cartpole.rs, wrappers/step_limit.rs)
@@ -258,6 +273,33 @@ class MetaBanditLanes : public EnvLanes {
     rl_env_config c{};
     c.kind = RL_ENV_META_BANDIT;
     c.limit_kind = RL_LIMIT_NONE;
+    c.n_lanes = n;
+    c.lane_offset = off;
+    c.seed_env = se;
+    c.seed_actor = sa;
+    check(rl_cartpole_params_default(&c.cartpole));
+    return c;
+  }
+};
+
+// `TabularMdp { transitions, discount_factor }` x n_lanes, optionally under a step limit (src/envs/mdps.rs:12-85): ONE MDP
+// of 2..8 states and 2..8 actions for all lanes, from the scalar mirror's tables (host/envs.hpp: TabularMdp, or
+// DirichletRandomMdps::sample_environment(seed, stream)); n_states (+ 1 under a visible limit) <= 8 observation features.
+class TabularMdpLanes : public EnvLanes {
+ public:
+  TabularMdpLanes(Engine &eng, uint64_t n_lanes, const TabularMdp &mdp, uint64_t max_steps = 0,
+                  StepLimit limit = StepLimit::None, uint64_t seed_env = 0, uint64_t seed_actor = 1,
+                  uint64_t lane_offset = 0)
+      : EnvLanes(eng, config(n_lanes, max_steps, limit, seed_env, seed_actor, lane_offset),
+                 rl_tabular_mdp_config{(uint32_t)mdp.num_states, (uint32_t)mdp.num_actions(), mdp.discount_factor},
+                 mdp.transitions, mdp.reward_mean, mdp.reward_stddev) {}
+
+ private:
+  static rl_env_config config(uint64_t n, uint64_t max_steps, StepLimit limit, uint64_t se, uint64_t sa, uint64_t off) {
+    rl_env_config c{};
+    c.kind = RL_ENV_TABULAR_MDP;
+    c.limit_kind = (int32_t)limit;
+    c.max_steps = max_steps;
     c.n_lanes = n;
     c.lane_offset = off;
     c.seed_env = se;
@@ -1157,7 +1199,8 @@ std::unique_ptr<DqnAgent> build_dqn_agent(const DqnConfig<VB, OC> &c, EnvLanes &
   // a feed-forward module, or a recurrent chain: the actor then carries the module's state through an episode and the
   // update runs whole sampled episodes (relearn_hip.h, rl_dqn_create_recurrent); an env of more than two actions (AS:
   // FiniteSpace, dqn.rs:75-86) builds through rl_dqn_create_finite, either kind of module
-  auto *create = env.num_actions() > 2 ? rl_dqn_create_finite
+  // (tabular-MDP lanes: rl_dqn_create_finite at every action count, step-wise collection)
+  auto *create = env.num_actions() > 2 || env.tabular_mdp() ? rl_dqn_create_finite
                                        : (builds_recurrent_module<VB>::value ? rl_dqn_create_recurrent : rl_dqn_create);
   check(create(env.handle(), a->q_->handle(), a->opt_->handle(), &d, &a->dqn_), eng.handle());
   return a;

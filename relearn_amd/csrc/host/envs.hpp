@@ -2,10 +2,14 @@
 // 257-269): `initial_state(rng)`, `observe(state, rng)`, `step(state, action, rng) -> (Successor<State>, reward)`.
 // Used by the CPU-only plumbing configuration (Chain + tabular Q) and as the scalar view of what the lanes do.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <optional>
+#include <stdexcept>
 #include <utility>
+#include <vector>
 
+#include "../../../include/rl_normal.h"
 #include "prng.hpp"
 
 namespace relearn {
@@ -80,6 +84,116 @@ struct MemoryGame {
     if (s.first == num_actions_ + history_len - 1) return {Successor<State>::Terminate(), a == s.second ? 1.0 : -1.0};
     const uint64_t next = s.first < num_actions_ ? num_actions_ : s.first + 1;
     return {Successor<State>::Continue({next, s.second}), 0.0};
+  }
+};
+
+// TabularMdp<_, Normal<f64>> (src/envs/mdps.rs:12-85) as the lanes state it (include/relearn_hip.h,
+// rl_env_create_tabular_mdp): starts in state 0; a step draws one u64 for the successor — always — and counts the entries
+// of the row's f32 running sum at or below the low word's unit float, then draws the reward's polar normal
+// (include/rl_normal.h) unless the row's stddev is 0.  No terminal states.
+struct TabularMdp {
+  using State = uint64_t;
+  using Observation = uint64_t;
+  using Action = uint64_t;
+  uint64_t num_states = 0, num_actions_ = 0;
+  std::vector<float> transitions;            // [S][A][S]
+  std::vector<float> cumulative;             // [S][A][S], formed by the constructor
+  std::vector<double> reward_mean, reward_stddev;  // [S][A]
+  double discount_factor = 1.0;
+
+  TabularMdp() = default;
+  // `stddev` empty: 1.0 everywhere (DirichletRandomMdps, mdps.rs:163)
+  TabularMdp(uint64_t S, uint64_t A, std::vector<float> tr, std::vector<double> mean, std::vector<double> stddev = {},
+             double discount = 1.0)
+      : num_states(S), num_actions_(A), transitions(std::move(tr)), reward_mean(std::move(mean)),
+        reward_stddev(std::move(stddev)), discount_factor(discount) {
+    if (S == 0 || A == 0 || transitions.size() != S * A * S || reward_mean.size() != S * A)
+      throw std::invalid_argument("TabularMdp: tables of [S][A][S] and [S][A]");
+    if (reward_stddev.empty()) reward_stddev.assign(S * A, 1.0);
+    if (reward_stddev.size() != S * A) throw std::invalid_argument("TabularMdp: reward_stddev of [S][A]");
+    cumulative.resize(transitions.size());
+    for (uint64_t row = 0; row < S * A; ++row) {
+      float acc = 0.0f;
+      uint64_t last = 0;
+      for (uint64_t j = 0; j < S; ++j) {
+        acc = acc + transitions[row * S + j];
+        cumulative[row * S + j] = acc;
+        if (transitions[row * S + j] > 0.0f) last = j;
+      }
+      // no draw reaches 1: the rounding of the running sum opens no bucket behind the last possible successor
+      for (uint64_t j = last; j < S; ++j) cumulative[row * S + j] = 1.0f;
+    }
+  }
+  uint64_t num_observations() const { return num_states; }
+  uint64_t num_actions() const { return num_actions_; }
+  State initial_state(Prng &) const { return 0; }
+  Observation observe(const State &s, Prng &) const { return s; }
+  // the polar normal from a sequential generator: two u64 per attempt, at most RL_NORMAL_MAX_ATTEMPTS attempts
+  static double normal(Prng &rng) {
+    double z = 0.0;
+    for (int attempt = 0; attempt < RL_NORMAL_MAX_ATTEMPTS; ++attempt) {
+      const uint64_t w1 = rng.next_u64(), w2 = rng.next_u64();
+      if (rl_normal_attempt(w1, w2, &z)) break;
+    }
+    return z;
+  }
+  std::pair<Successor<State>, double> step(State s, Action a, Prng &rng) const {
+    const uint64_t row = s * num_actions_ + a;
+    const float u = rl_u32_to_unit_f32((uint32_t)rng.next_u64());
+    State next = 0;
+    for (uint64_t j = 0; j + 1 < num_states; ++j) next += cumulative[row * num_states + j] <= u ? 1 : 0;
+    double reward = reward_mean[row];
+    if (reward_stddev[row] != 0.0) reward = reward_mean[row] + reward_stddev[row] * normal(rng);
+    return {Successor<State>::Continue(next), reward};
+  }
+};
+
+// DirichletRandomMdps (src/envs/mdps.rs:87-171): the distribution over MDPs of the second task of the RL^2 paper.
+// sample_environment consumes ONE stream — ChaCha8Rng::seed_from_u64(seed), set_stream(stream) — sequentially, row-major
+// over (s, a): the S Gamma(alpha, 1) draws of the row's Dirichlet sample (include/rl_normal.h), normalised in f64 and each
+// cast to f32, then the row's reward mean.  rl_random_mdps_sample is this function.
+struct DirichletRandomMdps {
+  uint64_t num_states = 10, num_actions = 5;
+  double transition_prior_dirichlet_alpha = 1.0, reward_prior_mean = 1.0, reward_prior_stddev = 1.0;
+  double discount_factor = 1.0;  // (assumes a step limit on the episodes)
+
+  // throws std::invalid_argument naming the field
+  void validate() const {
+    if (num_states < 1 || num_states > 64 || num_actions < 1 || num_actions > 64)
+      throw std::invalid_argument("DirichletRandomMdps: num_states and num_actions in 1..64");
+    if (!std::isfinite(transition_prior_dirichlet_alpha) || !(transition_prior_dirichlet_alpha > 0.0))
+      throw std::invalid_argument("DirichletRandomMdps: transition_prior_dirichlet_alpha must be positive and finite");
+    if (!std::isfinite(reward_prior_mean))
+      throw std::invalid_argument("DirichletRandomMdps: reward_prior_mean must be finite");
+    if (!std::isfinite(reward_prior_stddev) || reward_prior_stddev < 0.0)
+      throw std::invalid_argument("DirichletRandomMdps: reward_prior_stddev must be non-negative and finite");
+    if (!std::isfinite(discount_factor)) throw std::invalid_argument("DirichletRandomMdps: discount_factor must be finite");
+  }
+  // transitions [S][A][S], reward_mean [S][A]
+  void sample_tables(uint64_t seed, uint64_t stream, float *transitions, double *reward_mean) const {
+    validate();
+    uint32_t key[8];
+    rl_seed_from_u64(seed, key);
+    uint64_t pos = 0;
+    const uint64_t S = num_states, A = num_actions;
+    double g[64];
+    for (uint64_t row = 0; row < S * A; ++row) {
+      double sum = 0.0;  // Dirichlet::sample: S Gamma(alpha, 1) draws, normalised
+      for (uint64_t j = 0; j < S; ++j) {
+        g[j] = rl_gamma_sample(transition_prior_dirichlet_alpha, key, stream, &pos);
+        sum = sum + g[j];
+      }
+      for (uint64_t j = 0; j < S; ++j) transitions[row * S + j] = (float)(g[j] / sum);
+      // Normal::new(reward_prior_mean, reward_prior_stddev).sample
+      reward_mean[row] = reward_prior_mean + reward_prior_stddev * rl_normal_sample(key, stream, &pos);
+    }
+  }
+  TabularMdp sample_environment(uint64_t seed, uint64_t stream = 0) const {
+    validate();
+    std::vector<float> tr(num_states * num_actions * num_states);
+    std::vector<double> mean(num_states * num_actions);
+    sample_tables(seed, stream, tr.data(), mean.data());
+    return TabularMdp(num_states, num_actions, std::move(tr), std::move(mean), {}, discount_factor);
   }
 };
 

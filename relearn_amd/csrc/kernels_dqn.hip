@@ -629,6 +629,20 @@ template <int D>
 using FeatureCount = std::integral_constant<int, D>;
 template <int MAX_D, class Go>
 static void dqn_env_dispatch(const rl_env *env, const char *what, Go &&go) {
+  if (env->kind == RL_ENV_TABULAR_MDP) {  // states [+ 1] = 2..8 features; the step-wise collection alone
+    if constexpr (MAX_D >= 8) {
+      switch (env->D) {
+        case 2: go(MdpOps{}, FeatureCount<2>{}); return;
+        case 3: go(MdpOps{}, FeatureCount<3>{}); return;
+        case 4: go(MdpOps{}, FeatureCount<4>{}); return;
+        case 5: go(MdpOps{}, FeatureCount<5>{}); return;
+        case 6: go(MdpOps{}, FeatureCount<6>{}); return;
+        case 7: go(MdpOps{}, FeatureCount<7>{}); return;
+        case 8: go(MdpOps{}, FeatureCount<8>{}); return;
+      }
+    }
+    throw RlError(RL_ERR_UNSUPPORTED, what);
+  }
   const bool cartpole = env->kind == RL_ENV_CARTPOLE;
   if (env->D < 4 || env->D > (cartpole ? 5u : (uint32_t)MAX_D)) throw RlError(RL_ERR_UNSUPPORTED, what);
   if (cartpole) {
@@ -648,12 +662,14 @@ static void dqn_env_dispatch(const rl_env *env, const char *what, Go &&go) {
 template <class Go>
 static void dqn_features_dispatch(uint32_t D, Go &&go) {
   switch (D) {
+    case 2: go(FeatureCount<2>{}); break;  // (2 and 3: tabular-MDP lanes of two or three features)
+    case 3: go(FeatureCount<3>{}); break;
     case 4: go(FeatureCount<4>{}); break;
     case 5: go(FeatureCount<5>{}); break;
     case 6: go(FeatureCount<6>{}); break;
     case 7: go(FeatureCount<7>{}); break;
     case 8: go(FeatureCount<8>{}); break;
-    default: throw RlError(RL_ERR_UNSUPPORTED, "DQN replay store: 4..8 observation features");
+    default: throw RlError(RL_ERR_UNSUPPORTED, "DQN replay store: 2..8 observation features");
   }
 }
 
@@ -713,8 +729,8 @@ void launch_rollout_dqn_general(rl_env *env, const rl_mlp *qnet, rl_traj *ws, fl
     dqn_env_dispatch<8>(env, "step-wise DQN collection: 4..8 observation features", [&](auto ops, auto d) {
       using Env = decltype(ops);
       constexpr int D = decltype(d)::value;
-      // more than two actions: the index-env lanes alone (MemoryGame(k >= 3, h), the bandit of 3..8 arms)
-      if constexpr (std::is_same<Env, IndexOps>::value) {
+      // more than two actions: the index-env lanes (MemoryGame(k >= 3, h), the bandit of 3..8 arms) and tabular MDPs
+      if constexpr (std::is_same<Env, IndexOps>::value || std::is_same<Env, MdpOps>::value) {
         if (env->A > 2) {
           dqn_actions_dispatch(env->A, [&](auto na) {
             constexpr int A = decltype(na)::value;

@@ -402,7 +402,7 @@ void launch_obs_range(rl_traj *traj) {
 
 // The standalone env kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature
 // count as types.  CartPole lanes have 4 or 5 features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame:
-// num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..16.
+// num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..16; tabular-MDP lanes states [+ 1] = 2..8.
 template <int D>
 using FeatureCount = std::integral_constant<int, D>;
 template <class Go>
@@ -429,6 +429,19 @@ static void env_dispatch(const rl_env *env, Go &&go) {
     }
     return;
   }
+  if (env->kind == RL_ENV_TABULAR_MDP) {  // n_states [+ 1] features, 2..8 states
+    switch (env->D) {
+      case 2: go(MdpOps{}, FeatureCount<2>{}); break;
+      case 3: go(MdpOps{}, FeatureCount<3>{}); break;
+      case 4: go(MdpOps{}, FeatureCount<4>{}); break;
+      case 5: go(MdpOps{}, FeatureCount<5>{}); break;
+      case 6: go(MdpOps{}, FeatureCount<6>{}); break;
+      case 7: go(MdpOps{}, FeatureCount<7>{}); break;
+      case 8: go(MdpOps{}, FeatureCount<8>{}); break;
+      default: throw RlError(RL_ERR_UNSUPPORTED, "tabular-MDP lanes: 2..8 observation features");
+    }
+    return;
+  }
   switch (env->D) {
     case 4: go(IndexOps{}, FeatureCount<4>{}); break;
     case 5: go(IndexOps{}, FeatureCount<5>{}); break;
@@ -446,6 +459,8 @@ void launch_env_reset(rl_env *env) {
     hipLaunchKernelGGL(k_env_reset<CartPoleOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else if (env->kind == RL_ENV_META_BANDIT)
     hipLaunchKernelGGL(k_env_reset<MetaOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  else if (env->kind == RL_ENV_TABULAR_MDP)
+    hipLaunchKernelGGL(k_env_reset<MdpOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else
     hipLaunchKernelGGL(k_env_reset<IndexOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
 }
