@@ -106,13 +106,20 @@ int32_t rl_engine_set_kernel_variant(rl_engine *engine, int32_t variant);
  * src/torch/modules/ff/mlp.rs:139-151) and has no bound beyond f32's own.  The fused kernels compute every product of
  * layer 1 exactly on the bf16 matrix pipe with the weights scaled by 2^96 and read relu' off the scaled accumulator, which
  * is exact — bit-for-bit the mask of the f32 pre-activation's sign — when, for every hidden unit j,
- *     sum_k |W1[j][k]| * max|obs| + |b1[j]|  <  2^31      (the scaled accumulator stays finite), and
+ *     sum_k |W1[j][k]| * max|obs| + |b1[j]|  <  2^31      (the scaled accumulator stays finite),
+ *     sum_k |W1[j][k]|  <  2^31                           (the scaled weights themselves stay finite), and
  *     max(max_k |W1[j][k]| * min{|obs| : obs != 0}, |b1[j]|)  >=  2^-46   unless the unit's weights and bias are all zero
  *                                                         (a non-zero pre-activation cannot fall below 2^-96),
  * and every observation is finite.  With Glorot-initialised 5-128 layers (|w| <= 0.22) that is |obs| < 1.9e9 whatever the
  * small end when the biases are non-zero, and |obs| >= 7e-14 when they are zero.  Observation pieces below 2^-126 (bf16
  * subnormals: |obs| < 2^-110) may be flushed by the matrix pipe; inside the range above their contribution is below the
- * f32 rounding of the terms that carry the pre-activation.
+ * f32 rounding of the terms that carry the pre-activation.  "The f32 pre-activation" is an f32 evaluation of it: where the
+ * exact value is below 2^-46 of its terms (f64 sees a sign, f32 sees 0) the mask is 0, never a fraction.
+ * The mask is exact; the OUTPUTS are not the plain-f32 ones.  relu(x) is formed as (x + |x|) / 2 with the two halves summed
+ * over the hidden units separately in f32, so a value or a logit carries roundings of 2^-24 of sum_j |W2[.][j] pre_j| over
+ * ALL hidden units, those that are off included, where a plain f32 forward carries them of the active units' sum only:
+ * measured 0.30 x 2^-24 of that sum with b1 = -1000 on 96 of 128 units (1.9e-4 absolute on values of order 0.1, where kernel
+ * variant 1 is within 1e-7); with biases of the weights' own size the two sums are of one size.
  * The library checks the condition in the first fused launch of each module of every call (the later launches of the
  * same call start from parameters that call produced itself, in steps bounded by the learning rate or the KL constraint),
  * from the weights the launch has just loaded and the magnitude range of the trajectory's observation planes (measured
@@ -123,7 +130,8 @@ int32_t rl_engine_set_kernel_variant(rl_engine *engine, int32_t variant);
  * Adam moments and step count are what they were at entry (rl_dqn_update: put back from a snapshot).  The policy chain
  * and the critic chain have a word each: under rl_actor_critic_update[_begin] a violation of one chain refuses that
  * chain, the error names it, and the other chain's step stands (like the NaN policy step above).
- * Kernel variant 1 is plain f32 and takes any magnitudes.  tests/test_gpu_numeric_range.py. */
+ * Kernel variant 1 is plain f32 and takes any magnitudes.  tests/test_gpu_numeric_range.py; at the bounds themselves,
+ * at relu'(0) = 0 and for the forward bound: tests/test_gpu_relu_edges.py. */
 /* HIP-event timing of everything enqueued between begin and end on the engine stream (milliseconds) */
 int32_t rl_timer_begin(rl_engine *engine);
 int32_t rl_timer_end(rl_engine *engine, float *elapsed_ms);

@@ -289,7 +289,10 @@ __device__ __forceinline__ f32x16 layer1(const Frag (&fa)[3], const Frag (&fw)[3
 // 2 hf, 2 hf + 1, input 4 and its bias) and the magnitude range of the trajectory's observations (xmin = the smallest
 // non-zero |x|, xmax = the largest |x|, from the range words: range_bounds; a NaN / Inf observation shows up as a
 // non-finite xmax):
-//   overflow   2^96 pre must stay finite with room for the partial sums:  sum_k |W1[j][k]| max|x| + |b1[j]| < 2^31;
+//   overflow   2^96 pre must stay finite with room for the partial sums:  sum_k |W1[j][k]| max|x| + |b1[j]| < 2^31,
+//              and so must the scaled weights themselves, whatever the observations:  sum_k |W1[j][k]| < 2^31
+//              (under observations of 2^-46 a weight of 2^40 met the first bound, its image 2^136 is Inf and the pass
+//              returned NaN: tests/test_gpu_relu_edges.py);
 //   relu'      a non-zero pre must reach 2^-96, or the clamped conversion returns a FRACTIONAL mask.  pre is a sum of
 //              exact products whose f32 accumulation can cancel down to 2^-48 of its largest term, so the largest term of
 //              a unit that is not identically zero must be able to reach 2^-46: max(max_k |W1[j][k]| min_nz|x|, |b1[j]|).
@@ -358,7 +361,7 @@ __device__ __forceinline__ void range_guard(float wa, float wb, float w4, float 
   both_halves(nz, nz0, nz1);
   const float upper = hi0 + hi1 + bias, largest = __builtin_fmaxf(__builtin_fmaxf(lo0, lo1), bias);
   const bool zero_unit = nz0 + nz1 + bias == 0.0f;
-  const bool bad = !(upper < 0x1p31f) || (!zero_unit && !(largest >= 0x1p-46f));
+  const bool bad = !(upper < 0x1p31f) || !(nz0 + nz1 < 0x1p31f) || (!zero_unit && !(largest >= 0x1p-46f));
   if (bad) {
     __hip_atomic_store(veto, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
