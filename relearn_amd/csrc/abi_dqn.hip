@@ -58,18 +58,6 @@ static ReplayDev replay_alloc(rl_engine *e, DevMem &mem, uint32_t N, uint32_t C,
   return r;
 }
 
-// point the minibatch workspace back at its own sample arrays (an all-at-once update leaves it looking at its last
-// minibatch inside the big arrays).  For the builders and readers only: the workspace's pointers are views, and
-// destroying it while they look into the big arrays frees nothing it does not own (DevMem)
-static void dqn_own_arrays(rl_dqn *q) {
-  if (!q->mb || !q->own_obs) return;
-  q->mb->d.obs = q->own_obs;
-  q->mb->d.adv = q->own_target;
-  q->mb->d.action = q->own_action;
-  q->mb->d.flag = q->own_flag;
-  q->td_in_kernel = false;
-}
-
 // what a DQN handle holds besides memory (also the clean-up of a failed rl_dqn_create): the draw stream, the events and
 // the minibatch workspace; the device and pinned memory goes with `mem` after this body
 rl_dqn::~rl_dqn() {
@@ -98,29 +86,42 @@ static bool dqn_any_rank_failed(rl_dqn *q, bool local_failure) {
 
 static void dqn_build(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out, bool recurrent);
 
+// what every constructor checks first.  `who`: the messages' prefix — the entry point's name and a colon, or nothing
+// (rl_dqn_create's messages carry none)
+static void dqn_check_handles(const std::string &who, rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg,
+                              rl_dqn **out) {
+  RL_REQUIRE(env && qnet && opt && cfg && out, who + "NULL argument");
+  *out = nullptr;
+  RL_REQUIRE(qnet->eng == env->eng && opt->eng == env->eng, who + "handles belong to different engines");
+  RL_REQUIRE(opt->mod == qnet, who + "optimizer does not belong to the action-value module");
+}
+
+// The env table of the two-action constructors (relearn_hip.h): the collection kernels step CartPole lanes of 4 or 5
+// observation features and the index-env lanes (Chain, MemoryGame, the bandit) of 4..8.  Anything else is refused here,
+// by name: no env is collected by another env's code.  rl_dqn_create_recurrent's messages begin with its name.
+static void dqn_check_env(const rl_env *env, bool recurrent) {
+  const std::string name = recurrent ? "rl_dqn_create_recurrent" : "rl_dqn_create";
+  if (env->kind == RL_ENV_TABULAR_MDP)
+    throw RlError(RL_ERR_UNSUPPORTED,
+                  name + " is not built for RL_ENV_TABULAR_MDP lanes" + (recurrent ? "" : " (rl_dqn_create_finite is)"));
+  if (env->kind == RL_ENV_META_BANDIT)
+    throw RlError(RL_ERR_UNSUPPORTED, name + " is not built for RL_ENV_META_BANDIT lanes");
+  const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
+  if (env->kind != RL_ENV_CARTPOLE && !index_env)
+    throw RlError(RL_ERR_UNSUPPORTED, (recurrent ? name + ": " : "") +
+                                          "DQN collection is built for CartPole, Chain, MemoryGame and bandit lanes");
+  if (env->D < RL_ENV_MIN_OBS_DIM || env->D > (index_env ? RL_TRAJ_MAX_OBS_DIM : 5u))
+    throw RlError(RL_ERR_UNSUPPORTED, (recurrent ? name : "DQN") + (index_env ? " on index-env lanes: 4..8 observation features"
+                                                                              : " on CartPole lanes: 4 or 5 observation features"));
+}
+
 int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out) {
   return guarded(env ? env->eng : nullptr, [&] {
-    RL_REQUIRE(env && qnet && opt && cfg && out, "NULL argument");
-    *out = nullptr;
-    rl_engine *e = env->eng;
-    RL_REQUIRE(qnet->eng == e && opt->eng == e, "handles belong to different engines");
-    RL_REQUIRE(opt->mod == qnet, "optimizer does not belong to the action-value module");
+    dqn_check_handles("", env, qnet, opt, cfg, out);
     if (qnet->out_dim > 2) throw RlError(RL_ERR_UNSUPPORTED, "DQN kernels are built for 2 actions");
     RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A, "action-value module does not match the env");
     RL_REQUIRE(env->A == 2, "DQN kernels are built for 2-action envs");
-    // What builds (relearn_hip.h): the collection kernels step CartPole lanes and the index-env lanes (Chain, MemoryGame,
-    // the bandit) of 4..8 observation features.  Anything else is refused here, by name: no env is collected by another
-    // env's code.
-    const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
-    if (env->kind == RL_ENV_TABULAR_MDP)
-      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create is not built for RL_ENV_TABULAR_MDP lanes (rl_dqn_create_finite is)");
-    if (env->kind != RL_ENV_CARTPOLE && !index_env)
-      throw RlError(RL_ERR_UNSUPPORTED, env->kind == RL_ENV_META_BANDIT
-                                            ? "rl_dqn_create is not built for RL_ENV_META_BANDIT lanes"
-                                            : "DQN collection is built for CartPole, Chain, MemoryGame and bandit lanes");
-    if (env->D < RL_ENV_MIN_OBS_DIM || env->D > (index_env ? RL_TRAJ_MAX_OBS_DIM : 5u))
-      throw RlError(RL_ERR_UNSUPPORTED, index_env ? "DQN on index-env lanes: 4..8 observation features"
-                                                  : "DQN on CartPole lanes: 4 or 5 observation features");
+    dqn_check_env(env, /*recurrent=*/false);
     if (env->D > 5 && !qnet->general && !rl_module_is_recurrent(qnet->kind))
       throw RlError(RL_ERR_UNSUPPORTED, "DQN over 6..8 observation features: the fused collection kernel takes 4 or 5");
     // DqnConfig<MB> is generic over the module (dqn.rs:26-39): feed-forward modules of any MlpConfig build (the fused
@@ -136,29 +137,15 @@ int32_t rl_dqn_create(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
 // sampled episodes.  The env table of rl_dqn_create; every recurrent chain of two outputs.
 int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out) {
   return guarded(env ? env->eng : nullptr, [&] {
-    RL_REQUIRE(env && qnet && opt && cfg && out, "rl_dqn_create_recurrent: NULL argument");
-    *out = nullptr;
-    rl_engine *e = env->eng;
-    RL_REQUIRE(qnet->eng == e && opt->eng == e, "rl_dqn_create_recurrent: handles belong to different engines");
-    RL_REQUIRE(opt->mod == qnet, "rl_dqn_create_recurrent: optimizer does not belong to the action-value module");
+    dqn_check_handles("rl_dqn_create_recurrent: ", env, qnet, opt, cfg, out);
     if (!rl_module_is_recurrent(qnet->kind))
       throw RlError(RL_ERR_BUILD_AGENT,
                     "rl_dqn_create_recurrent takes a recurrent action-value module; use rl_dqn_create for a feed-forward one");
-    if (env->kind == RL_ENV_META_BANDIT)
-      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_recurrent is not built for RL_ENV_META_BANDIT lanes");
-    if (env->kind == RL_ENV_TABULAR_MDP)
-      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_recurrent is not built for RL_ENV_TABULAR_MDP lanes");
+    dqn_check_env(env, /*recurrent=*/true);
     if (qnet->out_dim > 2 || env->A > 2)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_recurrent: the DQN kernels are built for 2 actions");
     RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A,
                "rl_dqn_create_recurrent: action-value module does not match the env");
-    const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
-    if (env->kind != RL_ENV_CARTPOLE && !index_env)
-      throw RlError(RL_ERR_UNSUPPORTED,
-                    "rl_dqn_create_recurrent: DQN collection is built for CartPole, Chain, MemoryGame and bandit lanes");
-    if (env->D < RL_ENV_MIN_OBS_DIM || env->D > (index_env ? RL_TRAJ_MAX_OBS_DIM : 5u))
-      throw RlError(RL_ERR_UNSUPPORTED, index_env ? "rl_dqn_create_recurrent on index-env lanes: 4..8 observation features"
-                                                  : "rl_dqn_create_recurrent on CartPole lanes: 4 or 5 observation features");
     dqn_build(env, qnet, opt, cfg, out, /*recurrent=*/true);
   });
 }
@@ -174,11 +161,7 @@ int32_t rl_dqn_create_finite(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_d
     return rl_module_is_recurrent(qnet->kind) ? rl_dqn_create_recurrent(env, qnet, opt, cfg, out)
                                               : rl_dqn_create(env, qnet, opt, cfg, out);
   return guarded(env ? env->eng : nullptr, [&] {
-    RL_REQUIRE(env && qnet && opt && cfg && out, "rl_dqn_create_finite: NULL argument");
-    *out = nullptr;
-    rl_engine *e = env->eng;
-    RL_REQUIRE(qnet->eng == e && opt->eng == e, "rl_dqn_create_finite: handles belong to different engines");
-    RL_REQUIRE(opt->mod == qnet, "rl_dqn_create_finite: optimizer does not belong to the action-value module");
+    dqn_check_handles("rl_dqn_create_finite: ", env, qnet, opt, cfg, out);
     if (env->kind == RL_ENV_META_BANDIT)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite is not built for RL_ENV_META_BANDIT lanes");
     RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A,
@@ -217,6 +200,7 @@ int32_t rl_dqn_create_finite(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_d
   });
 }
 
+
 // what the constructors share: the configuration's checks, the replay store, the sampler's lists and the minibatch
 // workspace (+ the recurrent agent's two trajectory-shaped workspaces)
 static void dqn_build(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out, bool recurrent) {
@@ -251,10 +235,8 @@ static void dqn_build(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
   q->max_steps_mb = cfg->minibatch_steps - 1 + cfg->buffer_capacity;
   // the episode lists of all opt_steps_per_update minibatches of an update are drawn in one launch
   const size_t nb = cfg->opt_steps_per_update ? cfg->opt_steps_per_update : 1;
-  q->d_ep_lane = mem.alloc<uint32_t>(nb * q->max_eps);
-  q->d_ep_start = mem.alloc<uint32_t>(nb * q->max_eps);
-  q->d_ep_len = mem.alloc<uint32_t>(nb * q->max_eps);
-  q->d_ep_off = mem.alloc<uint32_t>(nb * q->max_eps);
+  for (uint32_t **list : {&q->eps.lane, &q->eps.start, &q->eps.len, &q->eps.off})
+    *list = mem.alloc<uint32_t>(nb * q->max_eps);
   q->d_counts = mem.alloc<DqnCountsDev>(nb);
   RL_HIP_CHECK(hipMemsetAsync(q->d_counts, 0, nb * sizeof(DqnCountsDev), e->stream));
   q->mb = traj_alloc(e, q->max_steps_mb, 1, env->D, true);
@@ -385,16 +367,21 @@ static int32_t dqn_check_counts(const rl_dqn *q, const DqnCountsDev *counts, siz
   return RL_OK;
 }
 
-// one sample_minibatch (dqn.rs:279-314): draw episodes, gather them, compute targets
+// the episode lists of minibatch `k` of the last draw
+static EpisodeLists dqn_lists(const rl_dqn *q, uint64_t k) {
+  const size_t o = (size_t)k * q->max_eps;
+  return EpisodeLists{q->eps.lane + o, q->eps.start + o, q->eps.len + o, q->eps.off + o};
+}
+
 // draw the episode lists of `n_batches` consecutive minibatches (dqn.rs:280-291) in one launch and read back their
 // sizes: the draws do not depend on the network, so the whole update needs this one host round trip
 static void dqn_draw_minibatches(rl_dqn *q, int sequential, uint32_t n_batches, std::vector<DqnCountsDev> &counts,
                                  std::vector<uint64_t> &totals) {
   rl_engine *e = q->eng;
   launch_dqn_sample(e, e->stream, q->rp, dqn_key(q), q->d_agent_pos, (uint32_t)q->cfg.minibatch_steps, q->max_eps,
-                    q->d_ep_lane, q->d_ep_start, q->d_ep_len, q->d_ep_off, q->d_counts, sequential, n_batches);
+                    dqn_lists(q, 0), q->d_counts, sequential, n_batches);
   // (a recurrent agent lays a minibatch out by its longest episode: the length rides in the counts' spare word)
-  if (q->recurrent) launch_dqn_longest(e, q->d_ep_len, q->max_eps, q->d_counts, n_batches);
+  if (q->recurrent) launch_dqn_longest(e, dqn_lists(q, 0), q->max_eps, q->d_counts, n_batches);
   counts.resize(n_batches);
   d2h(e, counts.data(), q->d_counts, n_batches * sizeof(DqnCountsDev));
   // local validation first, the verdict only after every rank has reported (a rank that throws here alone would leave
@@ -420,13 +407,42 @@ static void dqn_draw_minibatches(rl_dqn *q, int sequential, uint32_t n_batches, 
   }
 }
 
+// ---------------------------------------------------------------- the current minibatch
+// Which minibatch the workspace holds, for rl_dqn_minibatch_read / _gradient and the update's statistics.  Set: minibatch
+// `k` of the last draw — c.n_steps steps here, `total` over all ranks — with `mb` planned to its size.  Cleared: none;
+// the readers refuse, and `mb` points back at its own sample arrays (an all-at-once update leaves it looking at its last
+// minibatch inside the big arrays; the pointers are views: destroying `mb` frees nothing it does not own, DevMem).
+static void dqn_set_current(rl_dqn *q, uint64_t k, const DqnCountsDev &c, uint64_t total) {
+  q->last_n_eps = c.n_eps;
+  q->last_n_steps = c.n_steps;
+  q->last_total_steps = total;
+  q->last_batch_index = (uint32_t)k;
+  q->last_longest = c.pad;  // (a recurrent agent's draw: launch_dqn_longest)
+  q->mb->d.n = c.n_steps;
+  q->mb->d.T = 1;
+  traj_plan(q->mb, c.n_steps);
+}
+static void dqn_clear_current(rl_dqn *q) {
+  q->mb->d.obs = q->own_obs;
+  q->mb->d.adv = q->own_target;
+  q->mb->d.action = q->own_action;
+  q->mb->d.flag = q->own_flag;
+  q->td_in_kernel = false;
+  q->last_n_eps = q->last_n_steps = 0;
+}
+
+// gather minibatch `k` of the last draw into the workspace's own arrays, as the only minibatch of the all-at-once
+// builder: with its reward-to-go targets, or (`td`) with rewards, successor codes and successor observations (time slot
+// 1) for one-step TD targets formed behind it
+static void dqn_gather_one(rl_dqn *q, uint32_t k, const DqnCountsDev &c, bool td) {
+  rl_traj *mb = q->mb;
+  launch_dqn_build_all(q->eng, q->rp, 1, c.n_eps, q->max_eps, dqn_lists(q, k), q->d_counts + k, mb->d.obs, 0,
+                       mb->d.action, mb->d.adv, 0, q->cfg.discount_factor, td ? mb->d.flag : (uint8_t *)nullptr);
+}
+
 // ---------------------------------------------------------------- a recurrent action-value module
 // (rl_dqn_create_recurrent; the workspace's layout and its kernels: kernels_dqn.hip, the forward / backward:
 // kernels_seq_stack.hip — every recurrent chain runs the lane-per-thread kernels here, at its own widths)
-static DqnSeqEps rdqn_eps(const rl_dqn *q, uint32_t k) {
-  const size_t o = (size_t)k * q->max_eps;
-  return DqnSeqEps{q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o, q->d_ep_off + o};
-}
 
 // seq_packed(observations) over the workspace (dqn.rs:316-318), with the activation record; `succ`: also the outputs at
 // the successor observations of Interrupts (the extended sequence of the one-step TD targets)
@@ -437,20 +453,12 @@ static void rdqn_forward(rl_dqn *q, bool succ) {
 }
 
 // gather minibatch `k` of the last draw — episode after episode into `mb` (what rl_dqn_minibatch_read serves), one
-// episode per lane column into `seq` — and compute its targets (dqn.rs:293-314)
+// episode per lane column into `seq` — and compute its targets (dqn.rs:293-314).  No minibatch is current until the
+// workspace is whole.
 static void rdqn_build_minibatch(rl_dqn *q, uint32_t k, const DqnCountsDev &c, uint64_t total) {
-  rl_engine *e = q->eng;
-  dqn_own_arrays(q);
-  q->last_n_eps = q->last_n_steps = 0;  // (until the workspace is whole)
   rl_traj *mb = q->mb, *s = q->seq;
-  mb->d.n = c.n_steps;
-  mb->d.T = 1;
-  traj_plan(mb, c.n_steps);
-  const size_t o = (size_t)k * q->max_eps;
   const bool td = q->cfg.target == RL_DQN_TARGET_ONE_STEP_TD;
-  launch_dqn_build_all(e, q->rp, 1, c.n_eps, q->max_eps, q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o,
-                       q->d_ep_off + o, q->d_counts + k, mb->d.obs, 0, mb->d.action, mb->d.adv, 0, q->cfg.discount_factor,
-                       td ? mb->d.flag : (uint8_t *)nullptr);
+  dqn_gather_one(q, k, c, td);
   const uint64_t n = c.n_eps, T = c.pad, B = n * T, Dp = q->rp.D > 5 ? q->rp.D : 5;
   RL_REQUIRE(T > 0 && T <= q->rp.C && B >= c.n_steps, "minibatch without its longest episode's length");
   RL_REQUIRE(Dp * (T + 1) * n < (1ull << 31), "recurrent minibatch workspace: episodes x longest episode too large");
@@ -466,18 +474,14 @@ static void rdqn_build_minibatch(rl_dqn *q, uint32_t k, const DqnCountsDev &c, u
   mem.ensure(s->dz, (uint64_t)q->A * B);
   traj_plan(s, B);
   stack_ensure(s, q->qnet, true);
-  const DqnSeqEps eps = rdqn_eps(q, k);
+  const EpisodeLists eps = dqn_lists(q, k);
   launch_dqn_build_seq(s, q->rp, eps, td ? (const float *)nullptr : mb->d.adv);
   q->seq_fwd_epoch = 0;
   if (td) {  // under no_grad with the parameters of this optimisation step (dqn.rs:299-311): the forward the gradient reuses
     rdqn_forward(q, true);
     launch_dqn_seq_td_targets(s, eps, q->A, q->cfg.discount_factor, mb->d.adv);
   }
-  q->last_n_eps = c.n_eps;
-  q->last_n_steps = c.n_steps;
-  q->last_total_steps = total;
-  q->last_batch_index = k;
-  q->last_longest = (uint32_t)T;
+  dqn_set_current(q, k, c, total);
 }
 
 // gradient of mean((Q(s)[a] - target)^2) over the sampled steps of the current minibatch -> seq->vec[0..P), loss sum ->
@@ -486,7 +490,7 @@ static void rdqn_gradient(rl_dqn *q, rl_adam *step_opt, int loss_slot) {
   rl_traj *s = q->seq;
   const uint32_t P = (uint32_t)q->qnet->P;
   if (q->seq_fwd_epoch != q->eng->call_epoch) rdqn_forward(q, false);
-  launch_dqn_seq_terms(s, rdqn_eps(q, q->last_batch_index), q->A, q->last_total_steps);
+  launch_dqn_seq_terms(s, dqn_lists(q, q->last_batch_index), q->A, q->last_total_steps);
   launch_stack_backward(s, q->qnet, nullptr);
   launch_reduce(s, P, false, true, 0, s->nbB);
   if (step_opt) {
@@ -497,40 +501,24 @@ static void rdqn_gradient(rl_dqn *q, rl_adam *step_opt, int loss_slot) {
 
 // gather minibatch `k` of the last draw and compute its targets (dqn.rs:293-314)
 static void dqn_build_minibatch(rl_dqn *q, uint32_t k, const DqnCountsDev &c, uint64_t total) {
+  dqn_clear_current(q);
   if (q->recurrent) return rdqn_build_minibatch(q, k, c, total);
-  dqn_own_arrays(q);
-  q->last_n_eps = c.n_eps;
-  q->last_n_steps = c.n_steps;
-  q->last_total_steps = total;
-  q->last_batch_index = k;
+  dqn_set_current(q, k, c, total);
   rl_traj *mb = q->mb;
-  mb->d.n = c.n_steps;
-  mb->d.T = 1;
-  traj_plan(mb, c.n_steps);
-  const size_t o = (size_t)k * q->max_eps;
   const bool td = q->cfg.target == RL_DQN_TARGET_ONE_STEP_TD;
   if (td && q->qnet->general) {
     // the builder's in-kernel forward is the fused module's; any other module: gather with rewards, successor codes and
-    // successor observations (time slot 1), the module's layer kernels over the successor observations, then the targets
-    launch_dqn_build_all(q->eng, q->rp, 1, c.n_eps, q->max_eps, q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o,
-                         q->d_ep_off + o, q->d_counts + k, mb->d.obs, 0, mb->d.action, mb->d.adv, 0,
-                         q->cfg.discount_factor, mb->d.flag);
+    // successor observations, the module's layer kernels over the successor observations, then the targets
+    dqn_gather_one(q, k, c, true);
     q->mem.ensure(q->d_q_next, (uint64_t)q->A * q->max_steps_mb);  // (c.n_steps <= max_steps_mb: allocated once)
     launch_gen_forward(mb, q->qnet, mb->d.obs + c.n_steps, (size_t)2 * c.n_steps, c.n_steps, q->d_q_next);
     launch_dqn_td_targets(q->eng, mb->d.adv, mb->d.flag, q->d_q_next, c.n_steps, q->A, q->cfg.discount_factor);
     return;
   }
-  launch_dqn_build_minibatch(q->eng, q->rp, c.n_eps, q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o,
-                             q->d_ep_off + o, mb->d.obs, (size_t)2 * c.n_steps, mb->d.action, mb->d.adv,
-                             q->cfg.discount_factor, td ? 1 : 0, q->qnet);
+  launch_dqn_build_minibatch(q->eng, q->rp, c.n_eps, dqn_lists(q, k), mb->d.obs, (size_t)2 * c.n_steps, mb->d.action,
+                             mb->d.adv, q->cfg.discount_factor, td ? 1 : 0, q->qnet);
 }
 
-static void dqn_sample_minibatch(rl_dqn *q, int sequential) {
-  std::vector<DqnCountsDev> counts;
-  std::vector<uint64_t> totals;
-  dqn_draw_minibatches(q, sequential, 1, counts, totals);
-  dqn_build_minibatch(q, 0, counts[0], totals[0]);
-}
 
 // gradient of mean((Q(s)[a] - target)^2) over the current minibatch -> mb->vec[0..P), loss sum -> mb->vec[P]
 // `step_opt` != nullptr: also take the optimiser step, recording the loss in slot `loss_slot`; without an all-reduce
@@ -562,106 +550,91 @@ static void dqn_gradient(rl_dqn *q, rl_adam *step_opt = nullptr, int loss_slot =
   if (step_opt) launch_opt_step(mb, step_opt, loss_slot, q->last_total_steps);
 }
 
-// rl_dqn_update of a recurrent agent.  The episode lists of all K minibatches come from one launch of the sampler and are
-// validated before the first step; their sizes and longest episodes are the update's one read-back.  Every minibatch is
-// then gathered, run forward (one-step TD: targets from the same forward), differentiated and stepped without another
-// host round trip.  All or nothing: parameters, optimiser state and step count are saved first and put back when a later
-// minibatch fails (RELEARN_DQN_FAIL_CHUNK=c fails at the start of chunk c of the 2, 4, 8, ... chunks the feed-forward
-// update trains in — the same test facility).
-static void rdqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) {
-  rl_engine *e = q->eng;
-  if (e->n_ranks > 1)
-    throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_update: an agent of rl_dqn_create_recurrent updates on one rank");
-  q->global_steps = q->steps_per_lane * (uint64_t)q->rp.N;
-  const uint64_t K = q->cfg.opt_steps_per_update;
-  std::vector<DqnCountsDev> counts;
-  std::vector<uint64_t> totals;
-  if (K) dqn_draw_minibatches(q, 0, (uint32_t)K, counts, totals);
-  const uint64_t Pq = q->qnet->P, host_step0 = q->opt->host_step;
-  if (!q->snap) q->snap = q->mem.alloc<float>(4 * Pq + 2);
-  RL_HIP_CHECK(hipMemcpyAsync(q->snap, q->qnet->d_params, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-  for (int s = 0; s < 3; ++s)
-    if (q->opt->d_state[s])
-      RL_HIP_CHECK(hipMemcpyAsync(q->snap + (s + 1) * Pq, q->opt->d_state[s], Pq * sizeof(float), hipMemcpyDeviceToDevice,
-                                  e->stream));
-  RL_HIP_CHECK(hipMemcpyAsync(q->snap + 4 * Pq, q->opt->d_step, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
-  try {
-    size_t c = 0;
-    for (uint64_t first = 0, size = 2; first < K; first += size, size *= 2, ++c) {
-      if (const char *inj = std::getenv("RELEARN_DQN_FAIL_CHUNK"))
-        if ((size_t)std::atoi(inj) == c) throw RlError(RL_ERR_INVALID_ARGUMENT, "injected sampler failure");
-      for (uint64_t k = first; k < first + size && k < K; ++k) {
-        rdqn_build_minibatch(q, (uint32_t)k, counts[k], totals[k]);
-        rdqn_gradient(q, q->opt, (int)k);
-      }
+// What an all-or-nothing update puts back when it fails: the parameters, every state slot the optimiser's rule has (none
+// for plain SGD, three for centered RMSProp with momentum) and the step count, on the device and on the host, as of
+// save().  Held by the update, which restores in its `catch` — not from a destructor: nothing here runs while another
+// exception unwinds.  (A few device copies of <= 4 KB each, in q->snap.)
+struct DqnSnapshot {
+  bool saved = false;
+  uint64_t host_step = 0;
+  // the copies of either direction on the engine's stream; the first failure
+  static hipError_t copy(rl_dqn *q, bool restore) {
+    const uint64_t P = q->qnet->P;
+    hipError_t err = hipSuccess;
+    auto cp = [&](void *live, float *kept, size_t bytes) {
+      const hipError_t r = hipMemcpyAsync(restore ? live : (void *)kept, restore ? (const void *)kept : live, bytes,
+                                          hipMemcpyDeviceToDevice, q->eng->stream);
+      if (err == hipSuccess) err = r;
+    };
+    cp(q->qnet->d_params, q->snap, P * sizeof(float));
+    size_t slot = 1;  // (of P floats in q->snap: the parameters, one per state slot, then the step count)
+    for (float *state : q->opt->d_state) {
+      if (state) cp(state, q->snap + slot * P, P * sizeof(float));
+      ++slot;
     }
-    sync(e);  // (a launch that failed surfaces here, inside the all-or-nothing scope)
-  } catch (...) {
-    (void)hipMemcpyAsync(q->qnet->d_params, q->snap, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
+    cp(q->opt->d_step, q->snap + slot * P, sizeof(uint64_t));
+    return err;
+  }
+  void save(rl_dqn *q) {
+    if (!q->snap) q->snap = q->mem.alloc<float>((std::size(q->opt->d_state) + 1) * q->qnet->P + 2);
+    RL_HIP_CHECK(copy(q, false));
+    host_step = q->opt->host_step;
+    saved = true;
+  }
+  void restore(rl_dqn *q) {
+    if (!saved) return;
+    (void)copy(q, true);
     wimg_invalidate(q->qnet);
-    for (int s = 0; s < 3; ++s)
-      if (q->opt->d_state[s])
-        (void)hipMemcpyAsync(q->opt->d_state[s], q->snap + (s + 1) * Pq, Pq * sizeof(float), hipMemcpyDeviceToDevice,
-                             e->stream);
-    (void)hipMemcpyAsync(q->opt->d_step, q->snap + 4 * Pq, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream);
-    (void)hipStreamSynchronize(e->stream);
-    q->opt->host_step = host_step0;
-    q->last_n_eps = q->last_n_steps = 0;  // no minibatch to read after a failed update
-    throw;
+    (void)hipStreamSynchronize(q->eng->stream);
+    q->opt->host_step = host_step;
   }
-  std::vector<float> h(K ? K : 1, 0.0f);
-  if (K) d2h(e, h.data(), q->seq->losses, K * sizeof(float));
-  if (losses_out && K) std::memcpy(losses_out, h.data(), K * sizeof(float));
-  if (stats) {
-    stats->opt_steps = K;
-    stats->loss_first = K ? (double)h[0] : 0.0;
-    stats->loss_last = K ? (double)h[K - 1] : 0.0;
-    stats->global_steps = q->global_steps;
-    stats->last_minibatch_steps = q->last_n_steps;
-    stats->last_minibatch_episodes = q->last_n_eps;
-  }
-}
+};
 
+// DqnAgent::batch_update (dqn.rs:270-340): opt_steps_per_update x {sample_minibatch; gradient; optimiser step}, all or
+// nothing.  The draws do not depend on the network, so the episode lists come from the sampler ahead of the steps and
+// their sizes are the update's only read-backs.  What differs between the agents is decided once, at the top:
+//   all_at_once  feed-forward, reward-to-go targets (or one-step TD targets the fused 5-128-2 gradient kernel forms itself
+//                from the successor observations in time slot 1): a chunk's minibatches are gathered in one launch
+//   pipelined    ... on one rank, not profiling: the draws — one sequential chain through the agent's Prng, 12 us per
+//                minibatch on one CU — run on a second stream in chunks of 2, 4, 8, ... minibatches while the main stream
+//                trains on the chunks already drawn (the draw is the faster: only the first chunk is waited for)
+//   otherwise    one draw launch, which validates every minibatch before the first step; minibatches are built one at a
+//                time with the parameters of their step.  A recurrent agent (one rank) walks the 2, 4, 8, ... chunks too.
+// RELEARN_DQN_FAIL_CHUNK=c (test facility, tests/test_gpu_dqn.py) fails chunk c of a chunked update as a sampler error would.
 int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) {
   return guarded(q ? q->eng : nullptr, [&] {
     RL_REQUIRE(q, "NULL argument");
-    if (q->recurrent) return rdqn_update(q, stats, losses_out);
     rl_engine *e = q->eng;
+    const bool rec = q->recurrent;
+    if (rec && e->n_ranks > 1)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_update: an agent of rl_dqn_create_recurrent updates on one rank");
     // self.global_steps = sum of total_step_count over the buffers (dqn.rs:276); every lane of every rank has
     // taken the same number of steps and the horizon rule drops none
     q->global_steps = q->steps_per_lane * (uint64_t)q->rp.N * (uint64_t)e->n_ranks;
-    uint64_t K = q->cfg.opt_steps_per_update;
-    // Reward-to-go targets do not depend on the network: whole chunks of minibatches are gathered, targets included, in
-    // one launch each, and an optimisation step is a gradient launch and a reduction + Adam launch.  (One-step TD targets
-    // use the current network: those minibatches are still built one step at a time.)
-    const uint64_t D = q->rp.D, cap = q->max_steps_mb;
-    // One-step TD targets use the current network: on the matrix-pipe kernel they are formed inside the gradient launch
-    // (a second forward over the successor observations, which the gather leaves in time slot 1 of the workspace); the
-    // other kernels still build those minibatches one step at a time.
+    const uint64_t K = q->cfg.opt_steps_per_update, D = q->rp.D, cap = q->max_steps_mb;
     const bool td = q->cfg.target == RL_DQN_TARGET_ONE_STEP_TD;
     // Do the fused 5-128-2 kernels take this handle's minibatches?  Asked once per update, before the minibatch sizes
     // are known: without the element-offset term, which the launchers test per minibatch.  (Two outputs and a
     // feed-forward module are rl_dqn_create's conditions; the workspace has the store's D features.)
     const bool fused_shape = e->kernel_variant == 0 && fused_5_128_fits(q->mb, q->qnet, 2, /*offsets=*/false);
-    const bool td_fused = td && fused_shape;
-    const bool all_at_once = K > 1 && (!td || td_fused) && K * cap * (8 * D + 6) <= (8ull << 30);
+    const bool all_at_once = !rec && K > 1 && (!td || fused_shape) && K * cap * (8 * D + 6) <= (8ull << 30);
+    const bool pipelined = all_at_once && e->n_ranks == 1 && !e->profiling;
+    const bool chunked = pipelined || rec;
     if (all_at_once) {  // (allocated by the first such update: K and cap are the handle's constants)
       q->mem.ensure(q->all_obs, K * D * 2 * cap);
       q->mem.ensure(q->all_target, K * cap);
       q->mem.ensure(q->all_action, K * cap);
       if (td) q->mem.ensure(q->all_flag, K * cap);
     }
-    // The draws do not depend on the network either, but they are one sequential chain through the agent's Prng (12 us
-    // per minibatch on one CU).  One rank: the chain runs on a second stream in chunks of 2, 4, 8, ... minibatches
-    // while the main stream trains on the chunks already drawn — the draw is faster than the training, so only the first
-    // chunk is waited for.  (Several ranks agree on the counts through a collective first; per-kernel profiling keeps
-    // everything on the profiled stream.)
-    const bool pipelined = all_at_once && e->n_ranks == 1 && !e->profiling;
     std::vector<DqnCountsDev> counts;
     std::vector<uint64_t> totals;
     std::vector<uint32_t> chunk_end;  // minibatches [chunk_end[c - 1], chunk_end[c]) form chunk c
+    if (chunked)
+      for (uint64_t first = 0, size = 2; first < K; first += size, size *= 2)
+        chunk_end.push_back((uint32_t)(first + size < K ? first + size : K));
+    else
+      chunk_end.push_back((uint32_t)K);
     if (pipelined) {
-      for (uint64_t first = 0, size = 2; first < K; first += size, size *= 2) chunk_end.push_back((uint32_t)(first + size < K ? first + size : K));
       if (!q->draw_stream) RL_HIP_CHECK(hipStreamCreateWithFlags(&q->draw_stream, hipStreamNonBlocking));
       if (!q->main_event) RL_HIP_CHECK(hipEventCreateWithFlags(&q->main_event, hipEventDisableTiming));
       if (!q->h_counts) q->h_counts = q->mem.alloc_host<DqnCountsDev>(K, /*mapped=*/false);
@@ -675,38 +648,22 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
       RL_HIP_CHECK(hipStreamWaitEvent(q->draw_stream, q->main_event, 0));
       for (size_t c = 0; c < chunk_end.size(); ++c) {
         const uint32_t first = c ? chunk_end[c - 1] : 0, size = chunk_end[c] - first;
-        const size_t o = (size_t)first * q->max_eps;
         launch_dqn_sample(e, q->draw_stream, q->rp, dqn_key(q), q->d_agent_pos, (uint32_t)q->cfg.minibatch_steps,
-                          q->max_eps, q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o, q->d_ep_off + o,
-                          q->d_counts + first, 0, size);
+                          q->max_eps, dqn_lists(q, first), q->d_counts + first, 0, size);
         RL_HIP_CHECK(hipMemcpyAsync(q->h_counts + first, q->d_counts + first, size * sizeof(DqnCountsDev),
                                     hipMemcpyDeviceToHost, q->draw_stream));
         RL_HIP_CHECK(hipEventRecord(q->draw_events[c], q->draw_stream));
       }
       counts.resize(K);
       totals.resize(K);
-    } else {
-      if (K) dqn_draw_minibatches(q, 0, (uint32_t)K, counts, totals);
-      chunk_end.push_back((uint32_t)K);
+    } else if (K) {  // (the one-launch draw validates every minibatch before the first step)
+      dqn_draw_minibatches(q, 0, (uint32_t)K, counts, totals);
     }
-    rl_traj *mb = q->mb;
-    // With pipelined draws a sampler error can surface in a LATER chunk, after the earlier chunks' optimisation steps
-    // have run: the update is all or nothing, so the network and the optimiser state are saved first and put back then
-    // (a few device copies of <= 4 KB; the one-launch draw validates every minibatch before the first step).
-    const uint64_t Pq = q->qnet->P, host_step0 = q->opt->host_step;
-    // (the fused gradient kernel's range guard reports after the steps it could not vouch for have run: the same
-    // all-or-nothing rule — saved, and put back when the guard fires)
-    const bool snapshot = pipelined || fused_shape;
-    if (snapshot) {
-      // (every state slot the optimiser's rule has: none for plain SGD, three for centered RMSProp with momentum)
-      if (!q->snap) q->snap = q->mem.alloc<float>(4 * Pq + 2);
-      RL_HIP_CHECK(hipMemcpyAsync(q->snap, q->qnet->d_params, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-      for (int s = 0; s < 3; ++s)
-        if (q->opt->d_state[s])
-          RL_HIP_CHECK(hipMemcpyAsync(q->snap + (s + 1) * Pq, q->opt->d_state[s], Pq * sizeof(float),
-                                      hipMemcpyDeviceToDevice, e->stream));
-      RL_HIP_CHECK(hipMemcpyAsync(q->snap + 4 * Pq, q->opt->d_step, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
-    }
+    // All or nothing.  With pipelined draws a sampler error can surface in a LATER chunk, after the earlier chunks'
+    // optimisation steps have run; the fused gradient kernel's range guard reports after the steps it could not vouch
+    // for have run; a recurrent update's launches fail where the stream is drained.
+    DqnSnapshot snapshot;
+    if (chunked || fused_shape) snapshot.save(q);
     try {
       for (size_t c = 0; c < chunk_end.size(); ++c) {
         const uint32_t first = c ? chunk_end[c - 1] : 0, size = chunk_end[c] - first;
@@ -715,32 +672,27 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
           const char *what = "";
           const int32_t code = dqn_check_counts(q, q->h_counts + first, size, &what);
           if (code != RL_OK) throw RlError(code, what);
-          // (test facility: RELEARN_DQN_FAIL_CHUNK=c fails chunk c as a sampler error would, tests/test_gpu_dqn.py)
+        }
+        if (chunked)
           if (const char *inj = std::getenv("RELEARN_DQN_FAIL_CHUNK"))
             if ((size_t)std::atoi(inj) == c) throw RlError(RL_ERR_INVALID_ARGUMENT, "injected sampler failure");
+        if (pipelined)
           for (uint32_t k = first; k < first + size; ++k) {
             counts[k] = q->h_counts[k];
             totals[k] = counts[k].n_steps;
           }
-        }
         if (all_at_once && size) {
           uint32_t widest = 0;
           for (uint32_t k = first; k < first + size; ++k) widest = counts[k].n_eps > widest ? counts[k].n_eps : widest;
-          const size_t o = (size_t)first * q->max_eps;
-          launch_dqn_build_all(e, q->rp, size, widest, q->max_eps, q->d_ep_lane + o, q->d_ep_start + o, q->d_ep_len + o,
-                               q->d_ep_off + o, q->d_counts + first, q->all_obs + first * D * 2 * cap,
-                               (size_t)(D * 2 * cap), q->all_action + first * cap, q->all_target + first * cap,
-                               (size_t)cap, q->cfg.discount_factor, td ? q->all_flag + first * cap : (uint8_t *)nullptr);
+          launch_dqn_build_all(e, q->rp, size, widest, q->max_eps, dqn_lists(q, first), q->d_counts + first,
+                               q->all_obs + first * D * 2 * cap, (size_t)(D * 2 * cap), q->all_action + first * cap,
+                               q->all_target + first * cap, (size_t)cap, q->cfg.discount_factor,
+                               td ? q->all_flag + first * cap : (uint8_t *)nullptr);
         }
         for (uint64_t k = first; k < first + size; ++k) {
           if (all_at_once) {
-            q->last_n_eps = counts[k].n_eps;
-            q->last_n_steps = counts[k].n_steps;
-            q->last_total_steps = totals[k];
-            q->last_batch_index = (uint32_t)k;
-            mb->d.n = counts[k].n_steps;
-            mb->d.T = 1;
-            traj_plan(mb, counts[k].n_steps);
+            rl_traj *mb = q->mb;
+            dqn_set_current(q, k, counts[k], totals[k]);
             mb->d.obs = q->all_obs + k * D * 2 * cap;
             mb->d.action = q->all_action + k * cap;
             mb->d.adv = q->all_target + k * cap;
@@ -752,27 +704,14 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
           dqn_gradient(q, q->opt, (int)k);
         }
       }
-      // the range guard's word is read here, inside the all-or-nothing scope (the stream is drained first: the word is
-      // host memory the kernels write across the bus)
-      if (fused_shape && K) {
-        sync(e);
-        range_check(q->mb, 1u << RL_GUARD_POLICY);
-      }
+      // a launch that failed surfaces here, inside the all-or-nothing scope; so does the range guard's word (the stream
+      // is drained first: the word is host memory the kernels write across the bus)
+      if (rec || (fused_shape && K)) sync(e);
+      if (fused_shape && K) range_check(q->mb, 1u << RL_GUARD_POLICY);
     } catch (...) {
-      if (snapshot) {
-        if (pipelined) (void)hipStreamSynchronize(q->draw_stream);  // the later chunks' draws still advance the agent's Prng
-        (void)hipMemcpyAsync(q->qnet->d_params, q->snap, Pq * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
-        wimg_invalidate(q->qnet);
-        for (int s = 0; s < 3; ++s)
-          if (q->opt->d_state[s])
-            (void)hipMemcpyAsync(q->opt->d_state[s], q->snap + (s + 1) * Pq, Pq * sizeof(float), hipMemcpyDeviceToDevice,
-                                 e->stream);
-        (void)hipMemcpyAsync(q->opt->d_step, q->snap + 4 * Pq, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream);
-        (void)hipStreamSynchronize(e->stream);
-        q->opt->host_step = host_step0;
-      }
-      dqn_own_arrays(q);
-      q->last_n_eps = q->last_n_steps = 0;  // no minibatch to read after a failed update
+      if (pipelined) (void)hipStreamSynchronize(q->draw_stream);  // the later chunks' draws still advance the agent's Prng
+      snapshot.restore(q);
+      dqn_clear_current(q);  // no minibatch to read after a failed update
       throw;
     }
     // (after an all-at-once update `mb` keeps looking at the last minibatch: rl_dqn_minibatch_read / _gradient work;
@@ -780,8 +719,8 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
     // one-at-a-time builder, with the targets of the parameters the update ends on)
     if (all_at_once && td && K) dqn_build_minibatch(q, (uint32_t)(K - 1), counts[K - 1], totals[K - 1]);
     std::vector<float> h(K ? K : 1, 0.0f);
-    if (K) d2h(e, h.data(), q->mb->losses, K * sizeof(float));
-    range_check(q->mb, 1u << RL_GUARD_POLICY);
+    if (K) d2h(e, h.data(), (rec ? q->seq : q->mb)->losses, K * sizeof(float));
+    if (!rec) range_check(q->mb, 1u << RL_GUARD_POLICY);
     if (losses_out && K) std::memcpy(losses_out, h.data(), K * sizeof(float));
     if (stats) {
       stats->opt_steps = K;
@@ -793,6 +732,7 @@ int32_t rl_dqn_update(rl_dqn *q, rl_dqn_update_stats *stats, float *losses_out) 
     }
   });
 }
+
 
 static void replay_field(const rl_dqn *q, int32_t field, void **ptr, uint64_t *bytes) {
   const ReplayDev &r = q->rp;
@@ -848,7 +788,10 @@ int32_t rl_dqn_replay_read(rl_dqn *q, int32_t field, void *host, uint64_t bytes)
 int32_t rl_dqn_minibatch_sample(rl_dqn *q, int32_t sequential, uint64_t *n_episodes_out, uint64_t *n_steps_out) {
   return guarded(q ? q->eng : nullptr, [&] {
     RL_REQUIRE(q, "NULL argument");
-    dqn_sample_minibatch(q, sequential);
+    std::vector<DqnCountsDev> counts;
+    std::vector<uint64_t> totals;
+    dqn_draw_minibatches(q, sequential, 1, counts, totals);
+    dqn_build_minibatch(q, 0, counts[0], totals[0]);
     if (n_episodes_out) *n_episodes_out = q->last_n_eps;
     if (n_steps_out) *n_steps_out = q->last_n_steps;
   });
@@ -861,10 +804,16 @@ int32_t rl_dqn_minibatch_read(rl_dqn *q, int32_t field, void *host, uint64_t byt
     RL_REQUIRE(ns > 0, "no minibatch has been sampled");
     rl_engine *e = q->eng;
     switch (field) {
-      case RL_MB_EP_LANE: RL_REQUIRE(bytes == ne * 4, "byte count mismatch"); d2h(e, host, q->d_ep_lane + (size_t)q->last_batch_index * q->max_eps, bytes); break;
-      case RL_MB_EP_START: RL_REQUIRE(bytes == ne * 4, "byte count mismatch"); d2h(e, host, q->d_ep_start + (size_t)q->last_batch_index * q->max_eps, bytes); break;
-      case RL_MB_EP_LEN: RL_REQUIRE(bytes == ne * 4, "byte count mismatch"); d2h(e, host, q->d_ep_len + (size_t)q->last_batch_index * q->max_eps, bytes); break;
-      case RL_MB_EP_OFFSET: RL_REQUIRE(bytes == ne * 4, "byte count mismatch"); d2h(e, host, q->d_ep_off + (size_t)q->last_batch_index * q->max_eps, bytes); break;
+      case RL_MB_EP_LANE:
+      case RL_MB_EP_START:
+      case RL_MB_EP_LEN:
+      case RL_MB_EP_OFFSET: {
+        const EpisodeLists ep = dqn_lists(q, q->last_batch_index);
+        RL_REQUIRE(bytes == ne * 4, "byte count mismatch");
+        d2h(e, host, field == RL_MB_EP_LANE ? ep.lane : field == RL_MB_EP_START ? ep.start : field == RL_MB_EP_LEN ? ep.len : ep.off,
+            bytes);
+        break;
+      }
       case RL_MB_OBS: {
         RL_REQUIRE(bytes == D * ns * 4, "byte count mismatch");
         // feature planes are 2 * n_steps apart in the workspace (T = 1 trajectory layout)

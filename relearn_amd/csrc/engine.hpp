@@ -139,6 +139,11 @@ struct DqnCountsDev {
   int32_t error;
   uint32_t pad;
 };
+// the episode lists of one minibatch as k_dqn_sample writes them: per sampled episode its lane, its first ring step, its
+// length and its offset among the minibatch's steps.  Kernels take it by value.
+struct EpisodeLists {
+  uint32_t *lane, *start, *len, *off;
+};
 
 // scalar state of one TRPO update, lives in HBM so that the whole update needs no host round trip
 struct TrpoStateDev {
@@ -487,7 +492,7 @@ struct rl_dqn {
   rl_dqn_config cfg;
   ReplayDev rp;
   uint64_t *d_agent_pos = nullptr;   // word position of the agent's Prng (stream 0 of cfg.agent_key)
-  uint32_t *d_ep_lane = nullptr, *d_ep_start = nullptr, *d_ep_len = nullptr, *d_ep_off = nullptr;  // [max_eps]
+  EpisodeLists eps{};                // [opt_steps_per_update][max_eps]: minibatch k of a draw at k * max_eps (dqn_lists)
   DqnCountsDev *d_counts = nullptr;
   uint8_t *d_flags = nullptr;        // [T_cap][N] successor codes of the last collection
   uint64_t last_horizon = 0;
@@ -507,7 +512,7 @@ struct rl_dqn {
   uint32_t A = 2;                    // the env's action count = the module's outputs (rl_dqn_create_finite: 2..8)
   float *d_q = nullptr, *d_q_next = nullptr;  // module outputs of a collection step [A][N] / at a minibatch's successor
                                               // observations (action-value modules on the per-layer kernels)
-  float *snap = nullptr;             // parameters + optimiser state slots + step count as of the start of a pipelined update
+  float *snap = nullptr;             // parameters + optimiser state slots + step count as of the start of an update (DqnSnapshot)
   // ... `mb` then points into them (the last minibatch stays readable); its own arrays, for the one-at-a-time builder:
   float *own_obs = nullptr, *own_target = nullptr;
   uint8_t *own_action = nullptr, *own_flag = nullptr;

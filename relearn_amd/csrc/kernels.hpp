@@ -123,36 +123,35 @@ void launch_rollout_dqn_general(rl_env *env, const rl_mlp *qnet, rl_traj *ws, fl
 void launch_dqn_td_targets(rl_engine *eng, float *d_target, const uint8_t *d_flag, const float *d_q_next, uint32_t n,
                            uint32_t n_actions, float gamma);
 struct AgentKey { uint32_t w[8]; };
+// `ep` (EpisodeLists, engine.hpp): the episode lists of one minibatch; the two launchers that take `n_batches` of them
+// take the first one's and find minibatch b at b * max_eps
 void launch_dqn_sample(rl_engine *eng, hipStream_t stream, const ReplayDev &rp, const AgentKey &key, uint64_t *d_agent_pos,
-                       uint32_t minibatch_steps, uint32_t max_eps, uint32_t *d_lane, uint32_t *d_start,
-                       uint32_t *d_len, uint32_t *d_off, DqnCountsDev *d_counts, int sequential,
-                       uint32_t n_batches = 1);
+                       uint32_t minibatch_steps, uint32_t max_eps, const EpisodeLists &ep, DqnCountsDev *d_counts,
+                       int sequential, uint32_t n_batches = 1);
+// gather + reward-to-go targets of `n_batches` minibatches; d_flag != NULL: rewards, successor codes and successor
+// observations (time slot 1) instead, for one-step TD targets formed later
 void launch_dqn_build_all(rl_engine *eng, const ReplayDev &rp, uint32_t n_batches, uint32_t widest_eps, uint32_t max_eps,
-                          const uint32_t *d_lane, const uint32_t *d_start, const uint32_t *d_len, const uint32_t *d_off,
-                          const DqnCountsDev *d_counts, float *d_obs, size_t obs_stride, uint8_t *d_action,
-                          float *d_target, size_t step_stride, float gamma, uint8_t *d_flag);
+                          const EpisodeLists &ep, const DqnCountsDev *d_counts, float *d_obs, size_t obs_stride,
+                          uint8_t *d_action, float *d_target, size_t step_stride, float gamma, uint8_t *d_flag);
 void launch_replay_planes(rl_engine *eng, const ReplayDev &rp, int field, void *d_out);
 // the DQN gradient with the one-step TD targets formed in the launch (the workspace holds rewards)
 bool launch_dqn_step_bf16(rl_traj *mb, const rl_mlp *qnet, uint64_t B_total, float gamma);
 // kernels_critic.hip: the same gradient with the targets given, as two critic-step channels per SIMD
 bool launch_dqn_step_pair(rl_traj *mb, const rl_mlp *qnet, uint64_t B_total);
-void launch_dqn_build_minibatch(rl_engine *eng, const ReplayDev &rp, uint32_t n_eps, const uint32_t *d_lane,
-                                const uint32_t *d_start, const uint32_t *d_len, const uint32_t *d_off,
-                                float *d_obs, size_t out_plane, uint8_t *d_action, float *d_target, float gamma,
-                                int one_step_td, const rl_mlp *qnet);
+// one minibatch's gather and targets: reward-to-go, or one-step TD from the fused module's forward inside the launch
+void launch_dqn_build_minibatch(rl_engine *eng, const ReplayDev &rp, uint32_t n_eps, const EpisodeLists &ep, float *d_obs,
+                                size_t out_plane, uint8_t *d_action, float *d_target, float gamma, int one_step_td,
+                                const rl_mlp *qnet);
 // recurrent action-value modules (rl_dqn_create_recurrent): the sampled episodes of one minibatch as the lane columns of
 // a trajectory-shaped workspace `seq` (n = episodes, T = the longest one; kernels_dqn.hip has the layout)
-struct DqnSeqEps {
-  const uint32_t *lane, *start, *len, *off;  // the minibatch's episode lists (k_dqn_sample)
-};
 // the longest episode of each minibatch of a draw -> d_counts[b].pad
-void launch_dqn_longest(rl_engine *eng, const uint32_t *d_len, uint32_t max_eps, DqnCountsDev *d_counts, uint32_t n_batches);
+void launch_dqn_longest(rl_engine *eng, const EpisodeLists &ep, uint32_t max_eps, DqnCountsDev *d_counts, uint32_t n_batches);
 // ring -> workspace planes; targets from `d_given` (episode-after-episode order), or NULL: the rewards
-void launch_dqn_build_seq(rl_traj *seq, const ReplayDev &rp, const DqnSeqEps &ep, const float *d_given);
+void launch_dqn_build_seq(rl_traj *seq, const ReplayDev &rp, const EpisodeLists &ep, const float *d_given);
 // one-step TD targets from seq.out / seq.succ -> the workspace's targets and `d_compact` (episode-after-episode order)
-void launch_dqn_seq_td_targets(rl_traj *seq, const DqnSeqEps &ep, uint32_t n_actions, float gamma, float *d_compact);
+void launch_dqn_seq_td_targets(rl_traj *seq, const EpisodeLists &ep, uint32_t n_actions, float gamma, float *d_compact);
 // seq.out, targets -> dz (zero on padding) and the loss sum in slab B
-void launch_dqn_seq_terms(rl_traj *seq, const DqnSeqEps &ep, uint32_t n_actions, uint64_t B_total);
+void launch_dqn_seq_terms(rl_traj *seq, const EpisodeLists &ep, uint32_t n_actions, uint64_t B_total);
 // kernels_seq_stack.hip: all `T` collection steps of a recurrent action-value module in one launch; `roll` lends the
 // per-lane states and the observation planes ([D][2][N])
 void launch_stack_collect_dqn(rl_env *env, const rl_mlp *qnet, rl_traj *roll, const ReplayDev &rp, uint32_t T,

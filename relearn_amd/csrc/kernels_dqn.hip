@@ -189,61 +189,86 @@ __global__ void k_dqn_td_targets(float *__restrict__ tgt, const uint8_t *__restr
   tgt[i] = tgt[i] + dn;
 }
 
-// Minibatch builder: one workgroup per sampled episode.  Gathers the episode's steps from the ring into the compact
-// sample arrays (obs plane stride `out_plane`) and computes the value targets:
-//   RewardToGo: G_t = r_t + gamma * G_{t+1} (f32 multiply, then add — packed.rs:312-342 arithmetic)
-//   OneStepTd : r_t + gamma * max_a Q(s_{t+1}); 0 beyond a Terminate, Q(interrupt successor) after an Interrupt
+// ---------------------------------------------------------------- the gather, for every minibatch builder
+// one stored step: its observation (the record's features, 5..7 from the second record array when D > 5), action,
+// successor code and reward
 template <int D>
-__global__ void __launch_bounds__(64) k_dqn_build_minibatch(ReplayDev rp, const uint32_t *__restrict__ ep_lane,
-                                                            const uint32_t *__restrict__ ep_start,
-                                                            const uint32_t *__restrict__ ep_len,
-                                                            const uint32_t *__restrict__ ep_offset,
-                                                            float *__restrict__ out_obs, size_t out_plane,
-                                                            uint8_t *__restrict__ out_action,
+struct StoredStep {
+  float x[D];
+  uint32_t action, succ;
+  float reward;
+};
+template <int D>
+__device__ __forceinline__ StoredStep<D> step_load(const ReplayDev &rp, uint32_t lane, uint32_t slot) {
+  const size_t o = (size_t)lane * rp.C + slot;
+  const ReplayRec rec = rec_load(rp.rec + o);
+  StoredStep<D> s;
+#pragma unroll
+  for (int d = 0; d < (D < 5 ? D : 5); ++d) s.x[d] = rec.x[d];
+  if constexpr (D > 5) rec_load_hi<D>(rp, o, s.x);
+  s.action = rec.af & 0xffu;
+  s.succ = rec.af >> 8;
+  s.reward = rec.reward;
+  return s;
+}
+// the successor observation stored with the step in `slot` (meaningful after an Interrupt and at an episode's last step)
+template <int D>
+__device__ __forceinline__ void next_load(const ReplayDev &rp, uint32_t lane, uint32_t slot, float (&x)[D]) {
+  const ReplayNext *__restrict__ nx = rp.next + (size_t)lane * rp.C + slot;
+#pragma unroll
+  for (int d = 0; d < D; ++d) x[d] = nx->x[d];
+}
+// the successor observation of step i (successor code `succ`) of the episode of `len` steps from ring step `start`: the
+// stored one after an Interrupt or at the episode's last step, else the observation of the following step
+template <int D>
+__device__ __forceinline__ void successor_load(const ReplayDev &rp, uint32_t lane, uint32_t start, uint32_t len,
+                                               uint32_t i, uint32_t succ, float (&x)[D]) {
+  if (succ == RL_SUCC_INTERRUPT || i + 1 == len) {
+    next_load<D>(rp, lane, (start + i) % rp.C, x);
+  } else {
+    const StoredStep<D> s1 = step_load<D>(rp, lane, (start + i + 1) % rp.C);
+#pragma unroll
+    for (int d = 0; d < D; ++d) x[d] = s1.x[d];
+  }
+}
+
+// One minibatch, one workgroup per sampled episode: the episode's steps into the compact sample arrays (obs plane stride
+// `out_plane`) and the value targets:
+//   RewardToGo: G_t = r_t + gamma * G_{t+1} (f32 multiply, then add — packed.rs:312-342 arithmetic)
+//   OneStepTd : r_t + gamma * max_a Q(s_{t+1}) from the fused module's forward; 0 beyond a Terminate
+// (k_dqn_build_all with one minibatch computes the same reward-to-go targets; at config 3's shape, 4,337 episodes of 23
+// steps on average, it takes 13 us against this kernel's 10 — profiles/dqn_one_path_parent_vs_this.jsonl — so the
+// one-at-a-time builder keeps this scan.)
+template <int D>
+__global__ void __launch_bounds__(64) k_dqn_build_minibatch(ReplayDev rp, EpisodeLists ep, float *__restrict__ out_obs,
+                                                            size_t out_plane, uint8_t *__restrict__ out_action,
                                                             float *__restrict__ out_target, float gamma,
                                                             int one_step_td, const float *__restrict__ qnet, int H) {
-  constexpr int DR = D < 5 ? D : 5;  // features in the 32-byte record
   __shared__ float rew[1024];
   __shared__ float carry;
   const uint32_t e = blockIdx.x;
-  const uint32_t lane = ep_lane[e], start = ep_start[e], len = ep_len[e], off = ep_offset[e];
-  const ReplayRec *__restrict__ ring = rp.rec + (size_t)lane * rp.C;
+  const uint32_t lane = ep.lane[e], start = ep.start[e], len = ep.len[e], off = ep.off[e];
   for (uint32_t i = threadIdx.x; i < len; i += 64) {
-    const uint32_t slot = (start + i) % rp.C;
-    const ReplayRec rec = rec_load(ring + slot);
+    const StoredStep<D> s = step_load<D>(rp, lane, (start + i) % rp.C);
 #pragma unroll
-    for (int d = 0; d < DR; ++d) out_obs[d * out_plane + off + i] = rec.x[d];
-    if constexpr (D > 5) {
-      float x[D];
-      rec_load_hi<D>(rp, (size_t)lane * rp.C + slot, x);
-#pragma unroll
-      for (int d = 5; d < D; ++d) out_obs[d * out_plane + off + i] = x[d];
-    }
-    out_action[off + i] = (uint8_t)(rec.af & 0xffu);
+    for (int d = 0; d < D; ++d) out_obs[d * out_plane + off + i] = s.x[d];
+    out_action[off + i] = (uint8_t)s.action;
     if constexpr (D <= 5)  // (the forward below is the fused module's: a wider module's TD targets are k_dqn_td_targets')
     if (one_step_td) {
-      const uint32_t fl = rec.af >> 8;
       float vnext = 0.0f;
-      if (fl != RL_SUCC_TERMINATE) {
+      if (s.succ != RL_SUCC_TERMINATE) {
         float x[D], z[2];
-        if (fl == RL_SUCC_INTERRUPT || i + 1 == len) {
-          const ReplayNext *__restrict__ nx = rp.next + (size_t)lane * rp.C + slot;
-#pragma unroll
-          for (int d = 0; d < D; ++d) x[d] = nx->x[d];
-        } else {
-          const ReplayRec r1 = rec_load(ring + (start + i + 1) % rp.C);
-#pragma unroll
-          for (int d = 0; d < D; ++d) x[d] = r1.x[d];
-        }
+        successor_load<D>(rp, lane, start, len, i, s.succ, x);
         mlp_forward_lane<D, 2>(qnet, H, x, z);
         vnext = z[1] > z[0] ? z[1] : z[0];  // amax(-1)
       }
       const float dn = gamma * vnext;
-      out_target[off + i] = rec.reward + dn;
+      out_target[off + i] = s.reward + dn;
     }
   }
   if (one_step_td) return;
   // reward-to-go: backwards in chunks of 1024 steps staged through LDS, scanned by one lane
+  const ReplayRec *__restrict__ ring = rp.rec + (size_t)lane * rp.C;
   if (threadIdx.x == 0) carry = 0.0f;
   __syncthreads();
   for (uint32_t hi = len; hi > 0;) {
@@ -272,32 +297,29 @@ __global__ void __launch_bounds__(64) k_dqn_build_minibatch(ReplayDev rp, const 
   }
 }
 
-// All minibatches of an update in ONE launch (reward-to-go targets do not depend on the network, so nothing in an update
-// has to wait for them): one wave per sampled episode, blockIdx.y = minibatch.  Same arithmetic as the builder above
-// (G_t = r_t + gamma * G_{t+1}: multiply, then add), the scan runs on broadcast values of one 64-step chunk at a time,
-// last chunk first.  Minibatch b lands at obs + b * obs_stride (plane stride 2 * its step count: the T = 1 trajectory
-// layout the gradient kernels read), action / target + b * step_stride.
+// The minibatches of an update in ONE launch (reward-to-go targets do not depend on the network, so nothing in an update
+// has to wait for them), or one of them (a recurrent agent's, and the gather behind which another module's one-step TD
+// targets are formed): one wave per sampled episode, blockIdx.y = minibatch.  RewardToGo: G_t = r_t + gamma * G_{t+1} (f32 multiply, then add — packed.rs:312-342 arithmetic); the scan
+// runs on broadcast values of one 64-step chunk at a time, last chunk first.  Minibatch b reads its lists at b * max_eps
+// and lands at obs + b * obs_stride (plane stride 2 * its step count: the T = 1 trajectory layout the gradient kernels
+// read), action / target + b * step_stride.
 constexpr int BUILD_ALL_WAVES = 4;
 template <int D>
 __global__ void __launch_bounds__(BUILD_ALL_WAVES * 64)
-    k_dqn_build_all(ReplayDev rp, const uint32_t *__restrict__ ep_lane, const uint32_t *__restrict__ ep_start,
-                    const uint32_t *__restrict__ ep_len, const uint32_t *__restrict__ ep_offset, uint32_t max_eps,
-                    const DqnCountsDev *__restrict__ counts, float *__restrict__ out_obs, size_t obs_stride,
-                    uint8_t *__restrict__ out_action, float *__restrict__ out_target, size_t step_stride, float gamma,
-                    uint8_t *__restrict__ out_flag) {
-  // out_flag != NULL: one-step TD — the targets are left to the gradient kernel (they use the current network): the
-  // reward goes where the target would, the successor code into out_flag, the successor observation (the next step's,
-  // or the stored one after an Interrupt / at the episode's last step) into time slot 1 of the observation planes
-  constexpr int DR = D < 5 ? D : 5;  // features in the 32-byte record
+    k_dqn_build_all(ReplayDev rp, EpisodeLists ep, uint32_t max_eps, const DqnCountsDev *__restrict__ counts,
+                    float *__restrict__ out_obs, size_t obs_stride, uint8_t *__restrict__ out_action,
+                    float *__restrict__ out_target, size_t step_stride, float gamma, uint8_t *__restrict__ out_flag) {
+  // out_flag != NULL: one-step TD — the targets are formed later (they use the current network): the reward goes where
+  // the target would, the successor code into out_flag, the successor observation into time slot 1 of the observation
+  // planes
   const bool td = out_flag != nullptr;
   const uint32_t b = blockIdx.y, lane = threadIdx.x & 63;
   const uint32_t e = blockIdx.x * BUILD_ALL_WAVES + (threadIdx.x >> 6);
   const uint32_t n_eps = counts[b].n_eps, n_steps = counts[b].n_steps;
   if (e >= n_eps) return;
   const size_t eo = (size_t)b * max_eps + e;
-  const uint32_t ln = ep_lane[eo], start = ep_start[eo], len = ep_len[eo], off = ep_offset[eo];
+  const uint32_t ln = ep.lane[eo], start = ep.start[eo], len = ep.len[eo], off = ep.off[eo];
   const size_t out_plane = (size_t)2 * n_steps;
-  const ReplayRec *__restrict__ ring = rp.rec + (size_t)ln * rp.C;
   float *__restrict__ obs_b = out_obs + (size_t)b * obs_stride;
   uint8_t *__restrict__ act_b = out_action + (size_t)b * step_stride;
   float *__restrict__ tgt_b = out_target + (size_t)b * step_stride;
@@ -307,11 +329,10 @@ __global__ void __launch_bounds__(BUILD_ALL_WAVES * 64)
     const uint32_t lo = hi > 64 ? hi - 64 : 0, cnt = hi - lo;
     const bool mine = lane < cnt;
     const uint32_t i = lo + (mine ? lane : 0);
-    const ReplayRec rec = rec_load(ring + (start + i) % rp.C);
-    const float rew = rec.reward;
+    const StoredStep<D> s = step_load<D>(rp, ln, (start + i) % rp.C);
     float out = 0.0f;
     for (uint32_t k = cnt; k-- > 0;) {  // (uniform trip count; every lane carries the same g)
-      const float r = __shfl(rew, (int)k, 64);
+      const float r = __shfl(s.reward, (int)k, 64);
       if (first) {
         g = r;
         first = false;
@@ -323,29 +344,13 @@ __global__ void __launch_bounds__(BUILD_ALL_WAVES * 64)
     }
     if (mine) {
 #pragma unroll
-      for (int d = 0; d < DR; ++d) obs_b[d * out_plane + off + i] = rec.x[d];
-      if constexpr (D > 5) {
-        float x[D];
-        rec_load_hi<D>(rp, (size_t)ln * rp.C + (start + i) % rp.C, x);
-#pragma unroll
-        for (int d = 5; d < D; ++d) obs_b[d * out_plane + off + i] = x[d];
-      }
-      act_b[off + i] = (uint8_t)(rec.af & 0xffu);
-      tgt_b[off + i] = td ? rew : out;
+      for (int d = 0; d < D; ++d) obs_b[d * out_plane + off + i] = s.x[d];
+      act_b[off + i] = (uint8_t)s.action;
+      tgt_b[off + i] = td ? s.reward : out;
       if (td) {
-        const uint32_t fl = rec.af >> 8;
-        out_flag[(size_t)b * step_stride + off + i] = (uint8_t)fl;
+        out_flag[(size_t)b * step_stride + off + i] = (uint8_t)s.succ;
         float nx[D];
-        if (fl == RL_SUCC_INTERRUPT || i + 1 == len) {
-          const ReplayNext *__restrict__ nrec = rp.next + (size_t)ln * rp.C + (start + i) % rp.C;
-#pragma unroll
-          for (int d = 0; d < D; ++d) nx[d] = nrec->x[d];
-        } else {
-          const ReplayRec r1 = rec_load(ring + (start + i + 1) % rp.C);
-#pragma unroll
-          for (int d = 0; d < DR; ++d) nx[d] = r1.x[d];
-          if constexpr (D > 5) rec_load_hi<D>(rp, (size_t)ln * rp.C + (start + i + 1) % rp.C, nx);
-        }
+        successor_load<D>(rp, ln, start, len, i, s.succ, nx);
 #pragma unroll
         for (int d = 0; d < D; ++d) obs_b[d * out_plane + n_steps + off + i] = nx[d];
       }
@@ -606,17 +611,13 @@ __global__ void __launch_bounds__(SAMPLE_BLOCK) k_dqn_sample(ReplayDev rp, Agent
 
 // `stream`: the engine's stream, or the side stream an update draws its later minibatches on (not profiled there)
 void launch_dqn_sample(rl_engine *eng, hipStream_t stream, const ReplayDev &rp, const AgentKey &key,
-                       uint64_t *d_agent_pos, uint32_t minibatch_steps, uint32_t max_eps, uint32_t *d_lane,
-                       uint32_t *d_start, uint32_t *d_len, uint32_t *d_off, DqnCountsDev *d_counts, int sequential,
-                       uint32_t n_batches) {
+                       uint64_t *d_agent_pos, uint32_t minibatch_steps, uint32_t max_eps, const EpisodeLists &ep,
+                       DqnCountsDev *d_counts, int sequential, uint32_t n_batches) {
   std::unique_ptr<ProfScope> ps;
   if (stream == eng->stream) ps.reset(new ProfScope(eng, RL_K_SMALL));
-  if (rp.N <= (uint32_t)SAMPLE_META_LANES)
-    hipLaunchKernelGGL(k_dqn_sample<true>, dim3(1), dim3(SAMPLE_BLOCK), 0, stream, rp, key, d_agent_pos,
-                       minibatch_steps, max_eps, d_lane, d_start, d_len, d_off, d_counts, sequential, n_batches);
-  else
-    hipLaunchKernelGGL(k_dqn_sample<false>, dim3(1), dim3(SAMPLE_BLOCK), 0, stream, rp, key, d_agent_pos,
-                       minibatch_steps, max_eps, d_lane, d_start, d_len, d_off, d_counts, sequential, n_batches);
+  const auto kernel = rp.N <= (uint32_t)SAMPLE_META_LANES ? k_dqn_sample<true> : k_dqn_sample<false>;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(SAMPLE_BLOCK), 0, stream, rp, key, d_agent_pos, minibatch_steps, max_eps,
+                     ep.lane, ep.start, ep.len, ep.off, d_counts, sequential, n_batches);
   RL_HIP_CHECK(hipGetLastError());
 }
 
@@ -760,31 +761,28 @@ void launch_dqn_td_targets(rl_engine *eng, float *d_target, const uint8_t *d_fla
   });
 }
 
-void launch_dqn_build_minibatch(rl_engine *eng, const ReplayDev &rp, uint32_t n_eps, const uint32_t *d_lane,
-                                const uint32_t *d_start, const uint32_t *d_len, const uint32_t *d_off,
-                                float *d_obs, size_t out_plane, uint8_t *d_action, float *d_target, float gamma,
-                                int one_step_td, const rl_mlp *qnet) {
+void launch_dqn_build_minibatch(rl_engine *eng, const ReplayDev &rp, uint32_t n_eps, const EpisodeLists &ep, float *d_obs,
+                                size_t out_plane, uint8_t *d_action, float *d_target, float gamma, int one_step_td,
+                                const rl_mlp *qnet) {
   ProfScope ps(eng, RL_K_VALUES);
   if (n_eps == 0) return;
   if (one_step_td && rp.D > 5)  // (rl_dqn's general modules take launch_dqn_build_all + launch_dqn_td_targets)
     throw RlError(RL_ERR_UNSUPPORTED, "in-kernel one-step TD targets: 4 or 5 observation features");
   dqn_features_dispatch(rp.D, [&](auto d) {
-    hipLaunchKernelGGL(k_dqn_build_minibatch<decltype(d)::value>, dim3(n_eps), dim3(64), 0, eng->stream, rp, d_lane,
-                       d_start, d_len, d_off, d_obs, out_plane, d_action, d_target, gamma, one_step_td, qnet->d_params,
-                       (int)qnet->hidden);
+    hipLaunchKernelGGL(k_dqn_build_minibatch<decltype(d)::value>, dim3(n_eps), dim3(64), 0, eng->stream, rp, ep, d_obs,
+                       out_plane, d_action, d_target, gamma, one_step_td, qnet->d_params, (int)qnet->hidden);
   });
 }
 
 void launch_dqn_build_all(rl_engine *eng, const ReplayDev &rp, uint32_t n_batches, uint32_t widest_eps, uint32_t max_eps,
-                          const uint32_t *d_lane, const uint32_t *d_start, const uint32_t *d_len, const uint32_t *d_off,
-                          const DqnCountsDev *d_counts, float *d_obs, size_t obs_stride, uint8_t *d_action,
-                          float *d_target, size_t step_stride, float gamma, uint8_t *d_flag) {
+                          const EpisodeLists &ep, const DqnCountsDev *d_counts, float *d_obs, size_t obs_stride,
+                          uint8_t *d_action, float *d_target, size_t step_stride, float gamma, uint8_t *d_flag) {
   ProfScope ps(eng, RL_K_VALUES);
   if (n_batches == 0 || widest_eps == 0) return;
   const dim3 grid(cdiv_d(widest_eps, BUILD_ALL_WAVES), n_batches), block(BUILD_ALL_WAVES * 64);
   dqn_features_dispatch(rp.D, [&](auto d) {
-    hipLaunchKernelGGL(k_dqn_build_all<decltype(d)::value>, grid, block, 0, eng->stream, rp, d_lane, d_start, d_len,
-                       d_off, max_eps, d_counts, d_obs, obs_stride, d_action, d_target, step_stride, gamma, d_flag);
+    hipLaunchKernelGGL(k_dqn_build_all<decltype(d)::value>, grid, block, 0, eng->stream, rp, ep, max_eps, d_counts, d_obs,
+                       obs_stride, d_action, d_target, step_stride, gamma, d_flag);
   });
   RL_HIP_CHECK(hipGetLastError());
 }
@@ -1061,13 +1059,13 @@ void launch_replay_planes(rl_engine *eng, const ReplayDev &rp, int field, void *
 // ================================================================================================
 
 // the longest episode of each minibatch of a draw -> counts[b].pad (read back with the counts)
-__global__ void __launch_bounds__(256) k_dqn_longest(const uint32_t *__restrict__ ep_len, uint32_t max_eps,
+__global__ void __launch_bounds__(256) k_dqn_longest(EpisodeLists ep, uint32_t max_eps,
                                                      DqnCountsDev *__restrict__ counts) {
   __shared__ uint32_t red[256];
   const uint32_t b = blockIdx.x, n_eps = counts[b].n_eps < max_eps ? counts[b].n_eps : max_eps;
   uint32_t m = 0;
   for (uint32_t e = threadIdx.x; e < n_eps; e += 256) {
-    const uint32_t l = ep_len[(size_t)b * max_eps + e];
+    const uint32_t l = ep.len[(size_t)b * max_eps + e];
     m = l > m ? l : m;
   }
   red[threadIdx.x] = m;
@@ -1082,44 +1080,35 @@ __global__ void __launch_bounds__(256) k_dqn_longest(const uint32_t *__restrict_
 // the gather: one thread per slot b = t * n + e of the workspace (`given`: the compact targets of the episode-after-episode
 // arrays — reward-to-go; NULL: the slot's reward, to which k_dqn_seq_td_targets adds the successor's value)
 template <int D>
-__global__ void __launch_bounds__(256) k_dqn_build_seq(ReplayDev rp, DqnSeqEps ep, TrajDev tr,
+__global__ void __launch_bounds__(256) k_dqn_build_seq(ReplayDev rp, EpisodeLists ep, TrajDev tr,
                                                        const float *__restrict__ given) {
   const uint32_t n = tr.n, T = tr.T;
   const size_t B = (size_t)T * n, plane = (size_t)(T + 1) * n;
   const size_t b = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   const uint32_t e = (uint32_t)(b % n), t = (uint32_t)(b / n);
-  const uint32_t len = ep.len[e];
-  float x[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) x[d] = 0.0f;
-  uint32_t act = 0, fl = RL_SUCC_TERMINATE;
-  float rew = 0.0f, tgt = 0.0f;
-  if (t < len) {
+  StoredStep<D> s{};  // (a padding slot: a zero observation, action 0, no reward ...
+  s.succ = RL_SUCC_TERMINATE;  // ... and the state restarts behind it)
+  float tgt = 0.0f;
+  if (t < ep.len[e]) {
     const uint32_t lane = ep.lane[e], slot = (ep.start[e] + t) % rp.C;
-    const size_t o = (size_t)lane * rp.C + slot;
-    const ReplayRec rec = rec_load(rp.rec + o);
+    s = step_load<D>(rp, lane, slot);
+    tgt = given != nullptr ? given[ep.off[e] + t] : s.reward;
+    if (s.succ == RL_SUCC_INTERRUPT) {
+      float nx[D];
+      next_load<D>(rp, lane, slot, nx);
 #pragma unroll
-    for (int d = 0; d < (D < 5 ? D : 5); ++d) x[d] = rec.x[d];
-    if constexpr (D > 5) rec_load_hi<D>(rp, o, x);
-    act = rec.af & 0xffu;
-    fl = rec.af >> 8;
-    rew = rec.reward;
-    tgt = given != nullptr ? given[ep.off[e] + t] : rew;
-    if (fl == RL_SUCC_INTERRUPT) {
-      const ReplayNext *__restrict__ nx = rp.next + o;
-#pragma unroll
-      for (int d = 0; d < D; ++d) tr.term_obs[(size_t)d * B + b] = nx->x[d];
+      for (int d = 0; d < D; ++d) tr.term_obs[(size_t)d * B + b] = nx[d];
     }
   }
 #pragma unroll
   for (int d = 0; d < D; ++d) {
-    tr.obs[(size_t)d * plane + b] = x[d];
+    tr.obs[(size_t)d * plane + b] = s.x[d];
     if (t + 1 == T) tr.obs[(size_t)d * plane + B + e] = 0.0f;  // (slot T: never read — no column ends on Continue)
   }
-  tr.action[b] = (uint8_t)act;
-  tr.flag[b] = (uint8_t)fl;
-  tr.reward[b] = rew;
+  tr.action[b] = (uint8_t)s.action;
+  tr.flag[b] = (uint8_t)s.succ;
+  tr.reward[b] = s.reward;
   tr.adv[b] = tgt;
 }
 
@@ -1128,7 +1117,7 @@ __global__ void __launch_bounds__(256) k_dqn_build_seq(ReplayDev rp, DqnSeqEps e
 // of the successor outputs after an Interrupt, 0 after a Terminate; target = r + gamma * V_ext[t + 1] with
 // k_dqn_td_targets' arithmetic (`scalar * tensor`, then add).  Also into the episode-after-episode array (`compact`).
 template <int A>
-__global__ void __launch_bounds__(256) k_dqn_seq_td_targets(TrajDev tr, DqnSeqEps ep, const float *__restrict__ out,
+__global__ void __launch_bounds__(256) k_dqn_seq_td_targets(TrajDev tr, EpisodeLists ep, const float *__restrict__ out,
                                                             const float *__restrict__ succ, float gamma,
                                                             float *__restrict__ compact) {
   const uint32_t n = tr.n;
@@ -1157,7 +1146,7 @@ __global__ void __launch_bounds__(256) k_dqn_seq_td_targets(TrajDev tr, DqnSeqEp
 // the DQN terms over the output planes q [A][B] (PASS_DQN of policy_terms.hpp): dz[a] = [a == action] 2 (Q_a - target)
 // / n_steps, zero on padding, and the f64 sum of (Q_a - target)^2 through slab B
 template <int A>
-__global__ void __launch_bounds__(256) k_dqn_seq_terms(TrajDev tr, DqnSeqEps ep, const float *__restrict__ q,
+__global__ void __launch_bounds__(256) k_dqn_seq_terms(TrajDev tr, EpisodeLists ep, const float *__restrict__ q,
                                                        float *__restrict__ dz, double *__restrict__ slabB,
                                                        float two_over_B) {
   __shared__ double red[256];
@@ -1186,15 +1175,15 @@ __global__ void __launch_bounds__(256) k_dqn_seq_terms(TrajDev tr, DqnSeqEps ep,
   }
 }
 
-void launch_dqn_longest(rl_engine *eng, const uint32_t *d_len, uint32_t max_eps, DqnCountsDev *d_counts,
+void launch_dqn_longest(rl_engine *eng, const EpisodeLists &ep, uint32_t max_eps, DqnCountsDev *d_counts,
                         uint32_t n_batches) {
   ProfScope ps(eng, RL_K_SMALL);
   if (n_batches == 0) return;
-  hipLaunchKernelGGL(k_dqn_longest, dim3(n_batches), dim3(256), 0, eng->stream, d_len, max_eps, d_counts);
+  hipLaunchKernelGGL(k_dqn_longest, dim3(n_batches), dim3(256), 0, eng->stream, ep, max_eps, d_counts);
   RL_HIP_CHECK(hipGetLastError());
 }
 
-void launch_dqn_build_seq(rl_traj *seq, const ReplayDev &rp, const DqnSeqEps &ep, const float *d_given) {
+void launch_dqn_build_seq(rl_traj *seq, const ReplayDev &rp, const EpisodeLists &ep, const float *d_given) {
   ProfScope ps(seq->eng, RL_K_VALUES);
   const size_t B = (size_t)seq->d.T * seq->d.n;
   dqn_features_dispatch(rp.D, [&](auto d) {
@@ -1204,7 +1193,7 @@ void launch_dqn_build_seq(rl_traj *seq, const ReplayDev &rp, const DqnSeqEps &ep
   RL_HIP_CHECK(hipGetLastError());
 }
 
-void launch_dqn_seq_td_targets(rl_traj *seq, const DqnSeqEps &ep, uint32_t n_actions, float gamma, float *d_compact) {
+void launch_dqn_seq_td_targets(rl_traj *seq, const EpisodeLists &ep, uint32_t n_actions, float gamma, float *d_compact) {
   ProfScope ps(seq->eng, RL_K_VALUES);
   const size_t B = (size_t)seq->d.T * seq->d.n;
   dqn_actions_dispatch(n_actions, [&](auto na) {
@@ -1214,7 +1203,7 @@ void launch_dqn_seq_td_targets(rl_traj *seq, const DqnSeqEps &ep, uint32_t n_act
   RL_HIP_CHECK(hipGetLastError());
 }
 
-void launch_dqn_seq_terms(rl_traj *seq, const DqnSeqEps &ep, uint32_t n_actions, uint64_t B_total) {
+void launch_dqn_seq_terms(rl_traj *seq, const EpisodeLists &ep, uint32_t n_actions, uint64_t B_total) {
   ProfScope ps(seq->eng, RL_K_POLICY_PASS);
   dqn_actions_dispatch(n_actions, [&](auto na) {
     hipLaunchKernelGGL(k_dqn_seq_terms<decltype(na)::value>, dim3(seq->nbB), dim3(256), 0, seq->eng->stream, seq->d, ep,

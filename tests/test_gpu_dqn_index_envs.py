@@ -404,6 +404,54 @@ def minibatch_case(engine, name, hidden, act, variant, td):
     dqn.close()
 
 
+@pytest.mark.parametrize("limit,visible", [(64, False), (65, True), (130, False)],
+                         ids=["64-steps", "65-steps-6-features", "130-steps"])
+def test_reward_to_go_of_one_minibatch_across_scan_chunks(engine, limit, visible):
+    """rl_dqn_minibatch_sample with reward-to-go targets, the one-at-a-time builder: its scan walks an episode in chunks of
+    64 steps from the end.  Chain lanes end an episode at the step limit alone, so every episode is exactly one chunk (64
+    steps), one chunk and one step (65; six features: the second record array is read) or two chunks and two steps (130).
+    Collections of one step limit each keep every episode whole; a capacity of three episodes and seven steps makes the
+    fourth one wrap in the ring.  The discount factor 0.9 has inexact powers in f32: a scan that associated differently
+    would round differently.  Three episodes per minibatch.  Observations and actions against the restated store, the
+    targets against the oracle's discounted_cumsum_from_end on the stored rewards — all bit for bit."""
+    L, n, capacity, gamma = O.lib(), 6, 3 * limit + 7, np.float32(0.9)
+    kind, D = (ra.LIMIT_VISIBLE, 6) if visible else (ra.LIMIT_LATENT, 5)
+    env = ra.ChainEnv(engine, n, max_steps=limit, limit=kind, **SEEDS)
+    sim = O.ChainLaneSim(n, max_steps=limit, limit=O.LIMIT_VISIBLE if visible else O.LIMIT_LATENT, **SEEDS)
+    assert (env.D, sim.D) == (D, D)
+    q = ra.Mlp(engine, D, [16, 16] if visible else 128, 2, "Tanh" if visible else "Relu", "Identity")
+    q.init(77)
+    dqn = ra.Dqn(env, q, ra.Adam(q), dqn_cfg(capacity, 0.5, minibatch=2 * limit + 1, opt_steps=1, gamma=float(gamma)))
+    store = RingStore(n, capacity, D)
+    for _ in range(4):
+        dqn.collect(limit)
+        store.write_collection(*oracle_planes(sim, last_collection(dqn, limit)["action"]))
+    store.check_device(dqn, ra)
+    wrapped = False
+    for _ in range(8):
+        ne, ns = dqn.minibatch_sample()
+        obs, a, tgt = dqn.minibatch_read(ra.MB_OBS), dqn.minibatch_read(ra.MB_ACTION), dqn.minibatch_read(ra.MB_TARGET)
+        lanes, starts, lens = (dqn.minibatch_read(f) for f in (ra.MB_EP_LANE, ra.MB_EP_START, ra.MB_EP_LEN))
+        assert (ne, ns) == (3, 3 * limit) and np.all(lens == limit)
+        assert np.array_equal(dqn.minibatch_read(ra.MB_EP_OFFSET), np.cumsum(lens) - lens)
+        k = 0
+        for ln, st in zip(lanes, starts):
+            ring = store.rings[ln]
+            assert (int(st), limit) in [ring.episode(e) for e in range(ring.num_episodes())], (ln, st)
+            wrapped |= int(st) % capacity + limit > capacity
+            steps = [store.step_data(ln, int(st) + j) for j in range(limit)]
+            assert np.array_equal(obs[:, k:k + limit], np.array([s[0] for s in steps]).T)
+            assert np.array_equal(a[k:k + limit], np.array([s[1] for s in steps], dtype=np.uint8))
+            want = np.array([s[2] for s in steps], dtype=np.float32)
+            assert np.unique(want).size > 1  # (rewards of 0 and 2: the returns are sums of many powers of 0.9)
+            ones = np.ones(limit, dtype=np.uint64)
+            L.oracle_discounted_cumsum_from_end_f32(O.f32p(want), limit, float(gamma), O.u64p(ones), limit)
+            assert np.array_equal(tgt[k:k + limit], want), (ln, st)
+            k += limit
+    assert wrapped  # an episode that lies across the ring's end was among the sampled ones
+    dqn.close()
+
+
 @pytest.mark.parametrize("td", [False, True], ids=["reward-to-go", "one-step-td"])
 def test_a_failed_draw_leaves_the_bandit_agent_as_it_was(engine, td):
     """the all-or-nothing update (tests/test_gpu_dqn.py) on bandit lanes: a sampler failure injected into a later chunk
