@@ -108,15 +108,7 @@ int32_t rl_bandit_agent_create(rl_env *env, const rl_bandit_agent_config *cfg, r
   });
 }
 
-int32_t rl_bandit_agent_destroy(rl_bandit_agent *agent) {
-  if (!agent) return RL_OK;
-  (void)hipSetDevice(agent->eng->device);
-  (void)hipStreamSynchronize(agent->eng->main_stream);
-  rl_engine *eng = agent->eng;
-  delete agent;
-  engine_release_child(eng);
-  return RL_OK;
-}
+int32_t rl_bandit_agent_destroy(rl_bandit_agent *agent) { return destroy_child(agent); }
 
 // `settle` false, as rl_rollout: a critic chain in flight reads its own trajectory
 int32_t rl_bandit_agent_rollout(rl_bandit_agent *agent, rl_env *env, rl_traj *traj) {

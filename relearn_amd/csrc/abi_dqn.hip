@@ -266,16 +266,7 @@ static void dqn_build(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_conf
   *out = q.release();
 }
 
-int32_t rl_dqn_destroy(rl_dqn *q) {
-  if (!q) return RL_OK;
-  (void)hipSetDevice(q->eng->device);
-  (void)hipStreamSynchronize(q->eng->stream);
-  (void)hipStreamSynchronize(q->eng->aux_stream);
-  rl_engine *eng = q->eng;
-  delete q;
-  engine_release_child(eng);
-  return RL_OK;
-}
+int32_t rl_dqn_destroy(rl_dqn *q) { return destroy_child(q); }
 
 int32_t rl_dqn_exploration_rate(const rl_dqn *q, int32_t training, double *rate_out) {
   return guarded(q ? q->eng : nullptr, [&] {

@@ -138,11 +138,27 @@ SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req);
 extern "C" {
 // abi.hip
 void engine_release_child(rl_engine *e);
+// abi_traj.hip
 void traj_plan(rl_traj *t, uint64_t B);
 rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, bool resizable);
 void seq_ensure(rl_traj *t, const rl_mlp *mod, bool training);
 void traj_ensure_pvec(rl_traj *t, uint64_t P);
+// abi_module.hip
 rl_mlp *seq_exec(const rl_mlp *m);
+}
+
+// The body of every rl_*_destroy of a child handle: nothing the engine has in flight on either of its streams may still
+// read the handle's memory when it goes (a critic chain left on the auxiliary stream by rl_actor_critic_update_begin).
+template <typename Handle>
+static inline int32_t destroy_child(Handle *h) {
+  if (!h) return RL_OK;
+  rl_engine *eng = h->eng;
+  (void)hipSetDevice(eng->device);
+  (void)hipStreamSynchronize(eng->main_stream);
+  (void)hipStreamSynchronize(eng->aux_stream);
+  delete h;  // (its device memory goes with its `mem`; the twin of a narrow recurrent chain with ~rl_mlp)
+  engine_release_child(eng);
+  return RL_OK;
 }
 
 // Running the recurrent kernels for module `m` on trajectory `t`: `x` is the module they run (m itself, or its zero-padded

@@ -30,15 +30,7 @@ int32_t rl_summary_create(rl_engine *e, uint64_t n_lanes, rl_summary **out) {
   });
 }
 
-int32_t rl_summary_destroy(rl_summary *s) {
-  if (!s) return RL_OK;
-  (void)hipSetDevice(s->eng->device);
-  (void)hipStreamSynchronize(s->eng->main_stream);
-  rl_engine *eng = s->eng;
-  delete s;
-  engine_release_child(eng);
-  return RL_OK;
-}
+int32_t rl_summary_destroy(rl_summary *s) { return destroy_child(s); }
 
 // OnlineStepsSummary::push (summary.rs:198-214) over the trajectory's steps.  `settle` false: the two planes it reads
 // are written by rollouts (main stream) and rl_traj_write only, never by an update chain, so it need not wait for a

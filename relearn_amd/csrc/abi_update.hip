@@ -408,16 +408,7 @@ int32_t rl_optimizer_create(rl_mlp *module, const rl_optimizer_config *cfg, rl_a
   });
 }
 
-int32_t rl_adam_destroy(rl_adam *o) {
-  if (!o) return RL_OK;
-  (void)hipSetDevice(o->eng->device);
-  (void)hipStreamSynchronize(o->eng->stream);
-  (void)hipStreamSynchronize(o->eng->aux_stream);  // (a critic chain left in flight by rl_actor_critic_update_begin)
-  rl_engine *eng = o->eng;
-  delete o;
-  engine_release_child(eng);
-  return RL_OK;
-}
+int32_t rl_adam_destroy(rl_adam *o) { return destroy_child(o); }
 
 int32_t rl_optimizer_step_host(rl_adam *o, const float *grad) {
   return guarded(o ? o->mod->eng : nullptr, [&] {

@@ -11,11 +11,7 @@
 
 #include "../../include/relearn_hip.h"
 #include "dev_mem.hpp"
-
-struct RlError : std::runtime_error {
-  int32_t code;
-  RlError(int32_t c, const std::string &m) : std::runtime_error(m), code(c) {}
-};
+#include "handle_spec.hpp"  // RlError, RL_REQUIRE, the limits, CartPoleDev, ModuleShape: what needs no device
 
 #define RL_HIP_CHECK(expr)                                                                          \
   do {                                                                                              \
@@ -25,49 +21,7 @@ struct RlError : std::runtime_error {
                                     std::to_string(__LINE__) + ")");                                \
   } while (0)
 
-#define RL_REQUIRE(cond, msg)                                        \
-  do {                                                               \
-    if (!(cond)) throw RlError(RL_ERR_INVALID_ARGUMENT, (msg));      \
-  } while (0)
-
-// ---- device-side plain structs passed by value to kernels ---------------------------------------
-// RL_ENV_TABULAR_MDP (MdpOps, env_lanes.hpp): the tables of the one MDP all lanes share, in one device allocation of the
-// env handle — cum f32 [S][A][S] (running sums of the successor rows), mean and stddev f64 [S][A] — and their sizes
-// (launch-uniform).  32 bytes: it lies over the bandit's eight arm values in CartPoleDev, which these lanes do not have, so
-// that the struct — an argument of every env kernel — keeps its size and every field its offset.
-struct MdpTablesDev {
-  const float *cum;
-  const double *mean, *stddev;
-  uint32_t states, actions;
-};
-
-struct CartPoleDev {
-  double gravity, mass_pole, length_half_pole, friction_cart, friction_pole, time_step;
-  double action_force, max_pos, max_angle;
-  double total_weight, inv_total_mass, mass_length_pole;
-  double init_low, init_scale;  // Uniform::new_inclusive(-0.05, 0.05)
-  uint32_t key_env[8], key_actor[8];
-  uint64_t lane_offset;
-  uint32_t max_steps;
-  int32_t limit_kind;
-  uint32_t chain_size;   // RL_ENV_CHAIN / RL_ENV_MEMORY: number of states = one-hot width (MemoryGame: num_actions +
-                         // history_len)
-  uint32_t mem_actions;  // RL_ENV_MEMORY: num_actions (0 selects Chain in the shared lane code)
-  uint32_t bandit;       // RL_ENV_BANDIT: != 0; reward = bandit_r[action], every step terminates
-  union {
-    float bandit_r[8];   // DeterministicBandit::from_values, 2..8 arms
-    MdpTablesDev mdp;    // RL_ENV_TABULAR_MDP
-  };
-  // RL_ENV_META_BANDIT (MetaOps, env_lanes.hpp): number of arms k (2..12; above four: rl_env_create_meta_bandit_wide)
-  // and the bandit distribution (RL_BANDITS_*); `max_steps` holds TrialEpisodeLimit::episodes_per_trial (the trial limit is this env's limit).  Last, so that the
-  // fields above keep their offsets in every kernel's arguments.
-  uint32_t meta_arms;
-  int32_t meta_dist;
-};
-
-static_assert(sizeof(MdpTablesDev) == 8 * sizeof(float) && sizeof(CartPoleDev) == 248,
-              "the tables lie over the eight arm values: the struct keeps its size");
-
+// ---- device-side plain structs passed by value to kernels (CartPoleDev: handle_spec.hpp) ---------------
 struct EnvStateDev {
   double *x, *xdot, *th, *thdot;  // [n]; RL_ENV_CHAIN / RL_ENV_MEMORY keep their state index in x, MEMORY also its
                                   // initial state in xdot and its env-stream word position in th (exact in f64)
@@ -259,96 +213,27 @@ struct rl_env {
   float *d_reward = nullptr, *d_obs = nullptr, *d_term_obs = nullptr;
 };
 
-enum { RL_MODULE_MLP = 0, RL_MODULE_GRU_MLP = 1, RL_MODULE_LSTM_MLP = 2 };
-// a recurrent chain module (Chain<Gru | Lstm, Mlp>)?
-inline bool rl_module_is_recurrent(int kind) { return kind == RL_MODULE_GRU_MLP || kind == RL_MODULE_LSTM_MLP; }
-inline uint64_t rl_module_gates(int kind) { return kind == RL_MODULE_LSTM_MLP ? 4 : 3; }  // RnnImpl::GATES_MULTIPLE
-
-constexpr uint32_t RL_MLP_MAX_HIDDEN = 4;   // hidden layers of a general MlpConfig
-constexpr uint32_t RL_MLP_MAX_WIDTH = 256;  // widest hidden layer
-constexpr uint32_t RL_MLP_MAX_OUT = 8;      // outputs of a general MLP: a categorical policy over IndexSpace::new(2..8)
-constexpr uint32_t RL_TRAJ_MAX_OBS_DIM = 8;  // observation features of a trajectory (the envs here have 4 to 8)
-constexpr uint32_t RL_ENV_MIN_OBS_DIM = 4;   // narrowest observation the env kernels are built for
-// the wide entry points (rl_env_create_meta_bandit_wide, rl_rnn_chain_create_wide): meta-bandit lanes of up to 12 arms
-// (k + 4 = 16 features) and recurrent chains of up to 16 inputs and 12 outputs on the lane-per-thread kernels.  The two
-// constants above keep guarding what they guard: feed-forward modules, MemoryGame, DQN, the older constructors.
-constexpr uint32_t RL_WIDE_MAX_OBS_DIM = 16;
-constexpr uint32_t RL_WIDE_MAX_OUT = 12;
-constexpr uint32_t RL_RNN_MAX_LAYERS = 4;   // RnnBaseConfig::num_layers of a recurrent chain
-
-struct rl_mlp {
+// A module handle: its shape (ModuleShape, handle_spec.hpp: what it computes and how its flat vector is laid out) and what
+// lives on the device.
+struct rl_mlp : ModuleShape {
+  rl_mlp(rl_engine *e, const ModuleShape &shape) : ModuleShape(shape), eng(e) {}
   rl_engine *eng;
   mutable DevMem mem;  // (mutable: the weight image is made on first use by launchers that hold the module const)
-  uint32_t in_dim, hidden, out_dim;  // GRU_MLP: hidden = the MLP's hidden width (0: a Linear tail, linear_tail())
-  uint64_t P;
-  float *d_params = nullptr;
+  float *d_params = nullptr;  // [alloc_floats()]
   // the weight image of a 5 -> 128 -> A module for the fused update kernels (bf16_tile.hpp "the weight image"): allocated
   // on first use, current while wimg_epoch == eng->call_epoch (wimg_ensure / wimg_if_current / wimg_invalidate, kernels.hpp)
   mutable uint32_t *d_wimg = nullptr;
   mutable uint64_t wimg_epoch = 0;
-  int kind = RL_MODULE_MLP;
-  uint32_t gru_hidden = 0;
-  // RnnBaseConfig::num_layers (seq/rnn/mod.rs:20-45,223-257).  > 1: stacked layers — flat order [W_ih, W_hh, b_ih, b_hh]
-  // per layer (layer l > 0 reads the hidden output of layer l - 1), then the head; such a module runs the lane-per-thread
-  // kernels of kernels_seq_stack.hip at its own widths (no twin).
-  uint32_t rnn_layers = 1;
-  // the lane-per-thread kernels run this recurrent module (stacked layers, more input features than the fused tile
-  // kernels' five, or widths above their 128)
-  // (or recurrent weights without bias vectors, RnnBaseConfig::bias_init = None: `has_bias` false — the gate rows then
-  // start from 4 x 256 zeros kept behind the P parameters, like the bias-less MLP layers; the chain's MLP keeps its own)
-  // (or a chain whose second module is one Linear, `linear_tail`: at every shape, 5 -> 128 included, and never a twin)
-  // (or a chain of more than two outputs, rl_rnn_chain_create: the tile kernels and the twin stay two-action)
-  bool lane_kernels() const {
-    return rnn_layers > 1 || in_dim > 5 || gru_hidden > 128 || hidden > 128 || !has_bias || linear_tail() || out_dim > 2;
-  }
-  // ChainConfig<GruConfig | LstmConfig, LinearConfig> (modules/chain.rs:12-54): the recurrent layers -> ReLU -> one
-  // Linear(gru_hidden, out_dim).  Marked by `hidden` == 0 on a recurrent kind (the MLP-tail chains have hidden >= 1);
-  // flat order [layers .., kernel [out_dim][gru_hidden], bias [out_dim]]: rnn_layer_offset(rnn_layers) is the kernel.
-  bool linear_tail() const { return rl_module_is_recurrent(kind) && hidden == 0; }
-  uint64_t rnn_layer_offset(uint32_t l) const {  // W_ih of layer l; l == rnn_layers: the head's W1
-    const uint64_t GH = rl_module_gates(kind) * (uint64_t)gru_hidden, nb = has_bias ? 2 * GH : 0;
-    if (l == 0) return 0;
-    return GH * (in_dim + gru_hidden) + nb + (uint64_t)(l - 1) * (GH * 2 * gru_hidden + nb);
-  }
-  // MlpConfig::hidden_sizes (ff/mlp.rs:13-34).  `general`: a shape the fused single-hidden-layer kernels do not cover
-  // (no hidden layer, several, or one wider than 128) — it runs the per-layer kernels of kernels_general.hip; then
-  // `hidden` is 0, which keeps every fused launcher away.
-  uint32_t n_hidden = 1;
-  uint32_t widths[RL_MLP_MAX_HIDDEN] = {0, 0, 0, 0};
-  bool general = false;
-  // MlpConfig::activation / output_activation (rl_activation); the fused kernels are built for Relu / Identity
-  int act = 1, out_act = 0;
-  // Recurrent chains of other widths than the kernels' 5 -> 128 -> 128 (RnnBaseConfig::hidden_size, ChainConfig::
-  // hidden_dim, MlpConfig::hidden_sizes = [h]; in_dim <= 5, widths <= 128): `exec` is the module the kernels run — the
+  // Recurrent chains of other widths than the kernels' 5 -> 128 -> 128 (ModuleShape::needs_twin: RnnBaseConfig::hidden_size,
+  // ChainConfig::hidden_dim, MlpConfig::hidden_sizes = [h]; in_dim <= 5, widths <= 128): `exec` is the module the kernels run — the
   // same network embedded in the built shape, every padding weight and bias zero, so padded units stay exactly 0 (GRU:
   // h' = h / 2 from h = 0; LSTM: c' = c / 2, h' = tanh(0) / 2) and every real dot product only gains terms fma(0, 0, acc).
-  // Its parameter image is refreshed from this module's flat vector before a pass (seq_exec, abi.hip); gradients and
+  // Its parameter image is refreshed from this module's flat vector before a pass (seq_exec, abi_module.hip); gradients and
   // tangents are gathered / scattered between the two layouts (launch_seq_pad / _unpad).  NULL: the module is the built
   // shape itself.
   rl_mlp *exec = nullptr;  // (a host struct of its own; its parameter image lives in THIS module's `mem`)
   ~rl_mlp() { delete exec; }
   float *x_tmp = nullptr, *x_tan = nullptr;  // [exec->P]: gather scratch, padded tangent (zero outside the real entries)
-  // layer l (0 .. n_hidden; the last one is the output layer): fan-in, fan-out, offset of its kernel in the flat
-  // parameter vector ([W, b] per layer, the reference's order)
-  uint32_t n_layers() const { return n_hidden + 1; }
-  uint32_t fan_in(uint32_t l) const { return l == 0 ? in_dim : widths[l - 1]; }
-  uint32_t fan_out(uint32_t l) const { return l == n_hidden ? out_dim : widths[l]; }
-  uint64_t layer_offset(uint32_t l) const {
-    uint64_t o = 0;
-    for (uint32_t i = 0; i < l; ++i) o += (uint64_t)fan_in(i) * fan_out(i) + (has_bias ? fan_out(i) : 0);
-    return o;
-  }
-  // LinearConfig::bias_init = None (ff/linear.rs:13-33): layers without a bias vector — the flat vector holds the
-  // kernels only.  Every layer kernel starts its dot products from `bias`; such a module's layers read it from
-  // RL_MLP_MAX_WIDTH zeros kept BEHIND the P parameters in the same allocation (never written), and its gradient passes
-  // skip the bias columns.  Always on the per-layer path (`general`).
-  bool has_bias = true;
-  uint64_t bias_offset(uint32_t l) const { return has_bias ? layer_offset(l) + (uint64_t)fan_in(l) * fan_out(l) : P; }
-  uint32_t hidden_units() const {
-    uint32_t s = 0;
-    for (uint32_t i = 0; i < n_hidden; ++i) s += widths[i];
-    return s;
-  }
 };
 
 // workspace of the recurrent path, attached to a trajectory on first use (tiles of 32 lanes)
@@ -458,7 +343,7 @@ struct rl_traj {
   double *aux_slabA = nullptr, *aux_slabB = nullptr;
   float *aux_vec = nullptr;
   uint32_t aux_last_rows = 0;
-  // d.range[0..1] describe the current observation planes (false after anything rewrote them: traj_ensure_range, abi.hip);
+  // d.range[0..1] describe the current observation planes (false after anything rewrote them: traj_ensure_range, kernels.hpp);
   // `range_fixed`: the words are constants of the producer (the DQN minibatch workspace: CartPole-generated observations)
   bool range_valid = false, range_fixed = false;
   // the rollout that wrote the planes has reset d.range[0..1]: the value forward that follows (launch_values) measures
@@ -532,7 +417,7 @@ struct rl_dqn {
   uint64_t seq_fwd_epoch = 0;
 };
 
-// ---- profiling helper: wraps a launch with events when enabled ---------------------------------------
+// ---- profiling helper: wraps a launch with events when enabled (abi.hip) ------------------------------
 struct ProfScope {
   rl_engine *e;
   int cls;
@@ -541,7 +426,7 @@ struct ProfScope {
   ~ProfScope();
 };
 
-// abi.hip
+// abi.hip (the allocator behind dev_mem.hpp, the engine, the collectives)
 void rl_allreduce_sum_f32(rl_engine *e, float *d_buf, size_t count);
 void comm_agree(rl_engine *e);  // settings all ranks must share, agreed through the collective just installed
 // comm_ipc.hip

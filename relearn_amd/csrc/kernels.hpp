@@ -36,6 +36,10 @@ inline bool fused_5_128_fits(const rl_traj *t, const rl_mlp *m, uint32_t out_dim
   return m->kind == RL_MODULE_MLP && !m->general && t->d.D == 5 && m->hidden == 128 && m->out_dim == out_dim &&
          (!offsets || (uint64_t)(t->d.T + 1) * t->d.n * 5 < (1ull << 30));
 }
+// rl_rollout's path for this env and policy, or the refusal of the pair (handle_spec.hpp has the table)
+inline RolloutPath rollout_path(const rl_env *env, const rl_mlp *policy) {
+  return rollout_path(env->kind, env->D, env->A, env->dev.chain_size, *policy);
+}
 // The persistent grid of a fused 5-128 launch over the planes of `t`: one workgroup per `walkers` 32-sample tiles (its
 // tile-walking waves), at most one per CU — fewer, fatter workgroups are fewer slab rows for the reduction that follows
 // every launch.

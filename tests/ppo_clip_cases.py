@@ -45,7 +45,7 @@ Row = collections.namedtuple("Row", "name kind spec n T lr seed gain statement b
 # p1 is the reference's only to f32 rounding), no ratio exceeded the wide clip's upper bound 5, and 5 % of the ratios lay
 # within 0.1 of 1.
 # A Relu module of one hidden layer of at most 128 units over 4 or 5 inputs is rl_mlp_create's, never the general one
-# (mlp_create_config, abi.hip): the general single-layer rows have six inputs.  In launch_gen_mfma every module of widths
+# (mlp_shape, handle_spec.hpp): the general single-layer rows have six inputs.  In launch_gen_mfma every module of widths
 # <= 64 takes k_gen_pair in a gradient mode (gw = 2, and gp_lds_bytes fits at one to three layers); one hidden layer of
 # 65..128 units (gw = 4) takes the one-wave k_gen_mfma: 6-[100].
 ROWS = [
