@@ -71,7 +71,8 @@ enum { RL_OPT_OK = 0, RL_OPT_LOSS_NOT_IMPROVING = 1, RL_OPT_CONSTRAINT_VIOLATED 
 /* env kinds / step-limit wrappers (src/envs/cartpole.rs, chain.rs, wrappers/step_limit.rs:13,97) */
 enum { RL_ENV_CARTPOLE = 0, RL_ENV_CHAIN = 1, RL_ENV_MEMORY = 2, RL_ENV_BANDIT = 3,
        RL_ENV_META_BANDIT = 4 /* rl_env_create_meta_bandit only (src/envs/meta.rs) */,
-       RL_ENV_TABULAR_MDP = 5 /* rl_env_create_tabular_mdp only (src/envs/mdps.rs) */ };
+       RL_ENV_TABULAR_MDP = 5 /* rl_env_create_tabular_mdp only (src/envs/mdps.rs) */,
+       RL_ENV_META_MDP = 6 /* rl_env_create_meta_mdp only (src/envs/meta.rs over src/envs/mdps.rs) */ };
 /* bandit distributions of a meta-bandit env (src/envs/bandits.rs:128-243, src/envs/testing.rs:108-160) */
 enum { RL_BANDITS_UNIFORM_BERNOULLI = 0, RL_BANDITS_ONE_HOT = 1, RL_BANDITS_ROUND_ROBIN = 2 };
 enum { RL_LIMIT_NONE = 0, RL_LIMIT_LATENT = 1, RL_LIMIT_VISIBLE = 2 };
@@ -321,6 +322,55 @@ typedef struct {
 int32_t rl_random_mdps_config_default(rl_random_mdps_config *cfg);
 int32_t rl_random_mdps_sample(const rl_random_mdps_config *cfg, uint64_t seed, uint64_t stream, float *transitions,
                               double *reward_mean);
+/* Meta-RL random-MDP lanes, the second task of the RL^2 paper:
+ * `MetaEnv::new(DirichletRandomMdps{..}.wrap(LatentStepLimit::new(L))).wrap(TrialEpisodeLimit::new(E))`
+ * (src/envs/meta.rs:128-203, 541-617; src/envs/mdps.rs:12-171; src/envs/wrappers/mod.rs:104-123,
+ * wrappers/step_limit.rs:13-89).  Every lane draws ITS OWN MDP of S = n_states and A = n_actions on the device at each
+ * trial's start and keeps its tables in device memory.  S and A 2..8 with S + A + 4 <= 16; L = max_inner_steps and
+ * E = episodes_per_trial positive and < 2^32.  The handle's kind is RL_ENV_META_MDP; rl_env_dims returns (S + A + 4, A).
+ * Observation, S + A + 4 features in the derived product space's field order (MetaObservationSpace, meta.rs:357-363):
+ *   [inner is None] [one-hot(inner state), S] [prev is None] [one-hot(prev action), A] [prev reward] [episode_done]
+ * TabularMdp never terminates: an inner episode ends only by the limit's Interrupt(state), whose state is kept, so
+ * feature 0 is always 0, and on the step after an inner episode's last step the state's one-hot is still there and
+ * episode_done is 1.  The A + 1 entries behind a prev-None marker are zero; prev reward is the step's f32 reward.
+ * Step, inner episode done: the action is ignored; inner state <- 0, inner steps remaining <- L, prev <- None; reward 0,
+ *   Continue, nothing drawn.
+ * Step, inner episode live: TabularMdp::step on the lane's own tables as rl_env_create_tabular_mdp states it — one u64
+ *   for the successor, always; then the polar normal of include/rl_normal.h unless reward_stddev is 0;
+ *   reward = (float)(mean + reward_stddev z).  prev <- Some(action, reward).  The inner steps remaining drop by 1; at 0
+ *   the inner episode is done and the trial has one episode less; when none is left the step is an Interrupt, the
+ *   successor observation is written, then the lane is reset.  A trial is E (L + 1) - 1 steps.
+ * Reset (trial start): sample_environment from the lane's env stream at the lane's word position env_pos, in
+ *   rl_random_mdps_sample's order, row-major over (s, a): the row's S Gamma(alpha, 1) variates, normalised in f64 and each
+ *   cast to f32 (rl_dirichlet_row_normalise), the f32 running sums (rl_mdp_row_cumulative: from the last successor of
+ *   positive probability on exactly 1), then the row's mean, reward_prior_mean + reward_prior_stddev z (always drawn).
+ *   The inner initial_state (state 0) draws nothing.  Lanes are keyed by seed_from_u64(seed_env) and stream = global lane,
+ *   so at env_pos 0 lane g's first trial is rl_random_mdps_sample(.., seed_env, stream = g) bit for bit.
+ * reward_stddev is one launch-uniform value, the stddev of every sampled MDP's rewards (mdps.rs:163: 1.0); 0 draws nothing
+ * per step. */
+typedef struct {
+  uint32_t n_states, n_actions;
+  double alpha;               /* transition_prior_dirichlet_alpha: positive and finite */
+  double reward_prior_mean, reward_prior_stddev;
+  double reward_stddev;       /* of the sampled MDP's rewards: >= 0 */
+  double discount_factor;
+  uint64_t max_inner_steps;   /* LatentStepLimit::new(L) of an inner episode */
+  uint64_t episodes_per_trial; /* TrialEpisodeLimit::new(E) */
+} rl_meta_mdp_config;
+/* 5 states, 5 actions, alpha 1, prior N(1, 1), reward stddev 1, discount 1, L = 10, E = 10.  Five states and not
+ * DirichletRandomMdps::default's ten: 10 x 5 has 19 observation features and the widest lanes 16. */
+int32_t rl_meta_mdp_config_default(rl_meta_mdp_config *meta);
+/* `cfg` supplies the lanes, the lane offset and the seeds, as in rl_env_create_meta_bandit; its kind is not read.
+ * RL_ERR_BUILD_ENV: sizes outside the ranges above, L or E zero or >= 2^32, alpha not positive and finite, a stddev
+ * negative or not finite, a mean or discount not finite, a step limit in `cfg`.  The lanes serve rl_env_reset / _observe /
+ * _step, rl_rollout under a recurrent chain of rl_rnn_chain_create_wide (one launch at (S, A) in (2,2), (3,2), (4,3),
+ * (5,5), (8,4), (4,8) unless the kernel variant is 1; a launch sequence per step otherwise) or, at 2 x 2, a feed-forward
+ * module of eight inputs, every update on what was collected, and rl_summary_push (an episode is a trial).  Not built,
+ * RL_ERR_UNSUPPORTED by name: rl_env_get_state / rl_env_set_state, rl_dqn_create*, rl_actor_to_cbor, rl_bandit_agent_*. */
+int32_t rl_env_create_meta_mdp(rl_engine *engine, const rl_env_config *cfg, const rl_meta_mdp_config *meta, rl_env **out);
+/* The current trial's tables of lanes first_lane .. first_lane + n - 1 (local lanes) as the lanes read them; read-only.
+ * cum_out [n][S*A][S] f32 running sums, mean_out [n][S*A] f64; either may be NULL. */
+int32_t rl_env_meta_mdp_read_tables(rl_env *env, uint64_t first_lane, uint64_t n, float *cum_out, double *mean_out);
 int32_t rl_env_destroy(rl_env *env);
 /* number of observation features (CartPole 4, +1 `remaining` under VisibleStepLimit) and actions */
 int32_t rl_env_dims(const rl_env *env, uint32_t *obs_dim, uint32_t *n_actions);

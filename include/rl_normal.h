@@ -108,4 +108,31 @@ RL_HD double rl_gamma_sample(double alpha, const uint32_t key[8], uint64_t strea
   return rl_gamma_sample_ge1(alpha, key, stream, pos);
 }
 
+/* A Dirichlet row from its S Gamma draws and their f64 sum (DirichletRandomMdps::sample_environment, mdps.rs:151-170):
+ * p[j] = (float)(g[j] / sum).  `cap` >= S bounds the loop: a kernel gives a constant, so that the loop unrolls and the
+ * arrays stay in registers; a host caller gives S.  Entries at and behind S are not touched. */
+RL_HD void rl_dirichlet_row_normalise(const double *g, double sum, uint32_t S, uint32_t cap, float *p) {
+  for (uint32_t j = 0; j < cap; ++j)
+    if (j < S) p[j] = (float)(g[j] / sum);
+}
+
+/* The f32 running sums of a successor row as the tabular-MDP lanes read them (relearn::TabularMdp, rl_env_create_tabular_mdp
+ * and the lanes of rl_env_create_meta_mdp): cum[j] = p[0] + .. + p[j] in index order, and from the row's last successor of
+ * positive probability on (a row without one: from 0 on) the entries are exactly 1 — no draw reaches 1, so the rounding of
+ * the running sum opens no bucket behind that successor.  `cap` as above. */
+RL_HD void rl_mdp_row_cumulative(const float *p, uint32_t S, uint32_t cap, float *cum) {
+  float acc = 0.0f;
+  for (uint32_t j = 0; j < cap; ++j)
+    if (j < S) {
+      acc = acc + p[j];
+      cum[j] = acc;
+    }
+  int tail = 1; /* no successor of positive probability behind this one */
+  for (uint32_t j = cap; j-- > 0;)
+    if (j < S) {
+      if (tail) cum[j] = 1.0f;
+      if (p[j] > 0.0f) tail = 0;
+    }
+}
+
 #endif /* RL_NORMAL_H */

@@ -26,6 +26,7 @@ ERR_BUFFER_FULL, ERR_PACKING, ERR_COMM, ERR_OPT_NAN, ERR_UNSUPPORTED = 6, 7, 8, 
 SUCC_CONTINUE, SUCC_TERMINATE, SUCC_INTERRUPT = 0, 1, 2
 OPT_OK, OPT_LOSS_NOT_IMPROVING, OPT_CONSTRAINT_VIOLATED, OPT_NAN_LOSS, OPT_NAN_CONSTRAINT = range(5)
 ENV_CARTPOLE, ENV_CHAIN, ENV_MEMORY, ENV_BANDIT, ENV_META_BANDIT, ENV_TABULAR_MDP = 0, 1, 2, 3, 4, 5
+ENV_META_MDP = 6
 BANDITS_UNIFORM_BERNOULLI, BANDITS_ONE_HOT, BANDITS_ROUND_ROBIN = 0, 1, 2
 BANDIT_DISTRIBUTIONS = {"uniform_bernoulli": BANDITS_UNIFORM_BERNOULLI, "one_hot": BANDITS_ONE_HOT,
                         "round_robin": BANDITS_ROUND_ROBIN}
@@ -49,7 +50,7 @@ ABI_SYMBOLS = [
     "rl_last_error", "rl_engine_info", "rl_engine_set_kernel_variant", "rl_timer_begin", "rl_timer_end", "rl_profile_enable", "rl_profile_read",
     "rl_comm_available", "rl_comm_library_paths", "rl_comm_unique_id", "rl_comm_init", "rl_comm_destroy", "rl_comm_init_host",
     "rl_comm_ipc_handle", "rl_comm_init_ipc", "rl_comm_selftest",
-    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_create_tabular_mdp", "rl_random_mdps_config_default", "rl_random_mdps_sample", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
+    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_create_tabular_mdp", "rl_random_mdps_config_default", "rl_random_mdps_sample", "rl_meta_mdp_config_default", "rl_env_create_meta_mdp", "rl_env_meta_mdp_read_tables", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
@@ -103,6 +104,13 @@ class MetaBanditConfig(C.Structure):
 
 class TabularMdpConfig(C.Structure):
     _fields_ = [("n_states", C.c_uint32), ("n_actions", C.c_uint32), ("discount_factor", C.c_double)]
+
+
+class MetaMdpConfig(C.Structure):
+    """MetaEnv<DirichletRandomMdps under a LatentStepLimit> under a TrialEpisodeLimit (rl_meta_mdp_config)"""
+    _fields_ = [("n_states", C.c_uint32), ("n_actions", C.c_uint32), ("alpha", C.c_double),
+                ("reward_prior_mean", C.c_double), ("reward_prior_stddev", C.c_double), ("reward_stddev", C.c_double),
+                ("discount_factor", C.c_double), ("max_inner_steps", C.c_uint64), ("episodes_per_trial", C.c_uint64)]
 
 
 class RandomMdpsConfig(C.Structure):
@@ -652,6 +660,65 @@ class TabularMdpEnv(ChainEnv):
         st = np.zeros((4, self.n), dtype=np.float64)
         st[0], st[2] = state, env_pos
         CartPoleEnv.set_state(self, st, np.zeros(self.n, dtype=np.int32), rem, rc)
+
+
+def meta_mdp_config_default():
+    """5 states, 5 actions, alpha 1, reward prior N(1, 1), reward stddev 1, discount 1, 10 inner steps, 10 episodes"""
+    m = MetaMdpConfig()
+    _check(lib().rl_meta_mdp_config_default(C.byref(m)))
+    return m
+
+
+class MetaMdpEnv(ChainEnv):
+    """N meta-RL random-MDP lanes (src/envs/meta.rs over mdps.rs) — `MetaEnv::new(DirichletRandomMdps{..}.wrap(
+    LatentStepLimit::new(max_inner_steps))).wrap(TrialEpisodeLimit::new(episodes_per_trial))`.  Every lane draws its own
+    MDP at each trial's start; an inner episode is max_inner_steps steps, the step after it restarts the inner episode
+    (action ignored, reward 0), and the trial's last step is an Interrupt: E (L + 1) - 1 steps per trial.  Observations:
+    S + A + 4 features [inner is None] [one-hot(state)] [prev is None] [one-hot(prev action)] [prev reward]
+    [episode_done]; S and A 2..8 with S + A + 4 <= 16.  `meta`: a MetaMdpConfig instead of the keyword fields."""
+
+    def __init__(self, engine, n_lanes, n_states=5, n_actions=5, max_inner_steps=10, episodes_per_trial=10, alpha=1.0,
+                 reward_prior_mean=1.0, reward_prior_stddev=1.0, reward_stddev=1.0, discount_factor=1.0, lane_offset=0,
+                 seed_env=0, seed_actor=1, limit=LIMIT_NONE, max_steps=0, meta=None):
+        self.eng = engine
+        cfg = EnvConfig()
+        cfg.kind = ENV_META_MDP
+        cfg.limit_kind = limit  # (a step limit is refused: the inner and the trial limit are this env's limits)
+        cfg.max_steps = max_steps
+        cfg.n_lanes = n_lanes
+        cfg.lane_offset = lane_offset
+        cfg.seed_env = seed_env
+        cfg.seed_actor = seed_actor
+        cfg.cartpole = cartpole_params_default()
+        if meta is None:
+            meta = MetaMdpConfig()
+            meta.n_states, meta.n_actions = n_states, n_actions
+            meta.alpha, meta.reward_prior_mean, meta.reward_prior_stddev = alpha, reward_prior_mean, reward_prior_stddev
+            meta.reward_stddev, meta.discount_factor = reward_stddev, discount_factor
+            meta.max_inner_steps, meta.episodes_per_trial = max_inner_steps, episodes_per_trial
+        self.cfg, self.meta = cfg, meta
+        self.h = C.c_void_p()
+        _check(lib().rl_env_create_meta_mdp(engine.h, C.byref(cfg), C.byref(meta), C.byref(self.h)), engine.h)
+        _register(self)
+        self.n = n_lanes
+        self.S, self.n_actions = int(meta.n_states), int(meta.n_actions)
+        self.trial_steps = int(meta.episodes_per_trial) * (int(meta.max_inner_steps) + 1) - 1
+        d, a = C.c_uint32(), C.c_uint32()
+        _check(lib().rl_env_dims(self.h, C.byref(d), C.byref(a)), engine.h)
+        self.D, self.A = d.value, a.value
+
+    def read_tables(self, first_lane=0, n=None):
+        """the current trial's tables as the lanes read them: (cum [n][S][A][S] f32 running sums, mean [n][S][A] f64)"""
+        n = self.n - first_lane if n is None else n
+        cum = np.zeros((max(n, 1), self.S, self.n_actions, self.S), dtype=np.float32)
+        mean = np.zeros((max(n, 1), self.S, self.n_actions), dtype=np.float64)
+        _check(lib().rl_env_meta_mdp_read_tables(self.h, C.c_uint64(first_lane), C.c_uint64(n),
+                                                 cum.ctypes.data_as(C.c_void_p), mean.ctypes.data_as(C.c_void_p)),
+               self.eng.h)
+        return cum, mean
+
+    get_state = CartPoleEnv.get_state  # (refused by the library: RL_ERR_UNSUPPORTED)
+    set_state = CartPoleEnv.set_state
 
 
 class GruMlp(_Handle):

@@ -106,6 +106,8 @@ static void dqn_check_env(const rl_env *env, bool recurrent) {
                   name + " is not built for RL_ENV_TABULAR_MDP lanes" + (recurrent ? "" : " (rl_dqn_create_finite is)"));
   if (env->kind == RL_ENV_META_BANDIT)
     throw RlError(RL_ERR_UNSUPPORTED, name + " is not built for RL_ENV_META_BANDIT lanes");
+  if (env->kind == RL_ENV_META_MDP)
+    throw RlError(RL_ERR_UNSUPPORTED, name + " is not built for RL_ENV_META_MDP lanes");
   const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
   if (env->kind != RL_ENV_CARTPOLE && !index_env)
     throw RlError(RL_ERR_UNSUPPORTED, (recurrent ? name + ": " : "") +
@@ -157,13 +159,15 @@ int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const r
 // action (rl_rnn_chain_create: k_stack_collect_dqn<.., NA>).
 int32_t rl_dqn_create_finite(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out) {
   if (env && qnet && env->A <= 2 && qnet->out_dim <= 2 && env->kind != RL_ENV_META_BANDIT &&
-      env->kind != RL_ENV_TABULAR_MDP)
+      env->kind != RL_ENV_TABULAR_MDP && env->kind != RL_ENV_META_MDP)
     return rl_module_is_recurrent(qnet->kind) ? rl_dqn_create_recurrent(env, qnet, opt, cfg, out)
                                               : rl_dqn_create(env, qnet, opt, cfg, out);
   return guarded(env ? env->eng : nullptr, [&] {
     dqn_check_handles("rl_dqn_create_finite: ", env, qnet, opt, cfg, out);
     if (env->kind == RL_ENV_META_BANDIT)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite is not built for RL_ENV_META_BANDIT lanes");
+    if (env->kind == RL_ENV_META_MDP)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite is not built for RL_ENV_META_MDP lanes");
     RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A,
                "rl_dqn_create_finite: action-value module does not match the env's (obs_dim, n_actions)");
     if (env->kind == RL_ENV_TABULAR_MDP) {

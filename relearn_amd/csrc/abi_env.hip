@@ -63,6 +63,15 @@ static void env_build(rl_engine *e, const EnvSpec &spec, rl_env **out) {
     env->dev.mdp.stddev = reinterpret_cast<const double *>(tab + rows * 8);
     env->dev.mdp.cum = reinterpret_cast<const float *>(tab + rows * 16);
   }
+  if (spec.meta_mdp_rows != 0) {
+    // every lane's own tables, written by the lanes' reset below: one allocation of the handle, the rows
+    // of running sums first — 32 bytes each from an aligned base, so both 16-byte halves of a row are aligned — then the
+    // f64 means
+    const size_t rows = n * spec.meta_mdp_rows;
+    uint8_t *tab = mem.alloc<uint8_t>(rows * 8 * sizeof(float) + rows * sizeof(double));
+    env->dev.mm.cum = reinterpret_cast<float *>(tab);
+    env->dev.mm.mean = reinterpret_cast<double *>(tab + rows * 8 * sizeof(float));
+  }
   RL_HIP_CHECK(hipMemsetAsync(env->st.reset_count, 0, n * sizeof(uint32_t), e->stream));
   for (double *p : {env->st.x, env->st.xdot, env->st.th, env->st.thdot})
     RL_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(double), e->stream));
@@ -135,6 +144,51 @@ int32_t rl_env_create_tabular_mdp(rl_engine *e, const rl_env_config *cfg, const 
     RL_REQUIRE(e && cfg && mdp && transitions && reward_mean && out, "rl_env_create_tabular_mdp: NULL argument");
     *out = nullptr;
     env_build(e, env_spec_mdp(*cfg, *mdp, transitions, reward_mean, reward_stddev), out);
+  });
+}
+
+// DirichletRandomMdps::default (mdps.rs:111-122) but for the sizes — 10 x 5 has 19 observation features, the widest lanes
+// 16 — under a LatentStepLimit of 10 steps and TrialEpisodeLimit::default (meta.rs:557-564); reward stddev mdps.rs:163
+int32_t rl_meta_mdp_config_default(rl_meta_mdp_config *meta) {
+  return guarded(nullptr, [&] {
+    RL_REQUIRE(meta, "config is NULL");
+    meta->n_states = 5;
+    meta->n_actions = 5;
+    meta->alpha = 1.0;
+    meta->reward_prior_mean = 1.0;
+    meta->reward_prior_stddev = 1.0;
+    meta->reward_stddev = 1.0;
+    meta->discount_factor = 1.0;
+    meta->max_inner_steps = 10;
+    meta->episodes_per_trial = 10;
+  });
+}
+
+// MetaEnv::new(DirichletRandomMdps{..}.wrap(LatentStepLimit::new(L))).wrap(TrialEpisodeLimit::new(E))
+int32_t rl_env_create_meta_mdp(rl_engine *e, const rl_env_config *cfg, const rl_meta_mdp_config *meta, rl_env **out) {
+  return guarded(e, [&] {
+    RL_REQUIRE(e && cfg && meta && out, "rl_env_create_meta_mdp: NULL argument");
+    *out = nullptr;
+    env_build(e, env_spec_meta_mdp(*cfg, *meta), out);
+  });
+}
+
+// the current trial's tables as the lanes read them: the padding of the rows' eight floats is dropped
+int32_t rl_env_meta_mdp_read_tables(rl_env *env, uint64_t first_lane, uint64_t n, float *cum_out, double *mean_out) {
+  return guarded(env ? env->eng : nullptr, [&] {
+    RL_REQUIRE(env, "env is NULL");
+    if (env->kind != RL_ENV_META_MDP)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_env_meta_mdp_read_tables is built for RL_ENV_META_MDP lanes");
+    RL_REQUIRE(n >= 1 && first_lane < env->cfg.n_lanes && n <= env->cfg.n_lanes - first_lane,
+               "rl_env_meta_mdp_read_tables: lanes outside the env");
+    const size_t S = env->dev.mm.states, rows = S * env->dev.mm.actions;
+    if (mean_out) d2h(env->eng, mean_out, env->dev.mm.mean + first_lane * rows, n * rows * sizeof(double));
+    if (cum_out) {
+      std::vector<float> padded(n * rows * 8);
+      d2h(env->eng, padded.data(), env->dev.mm.cum + first_lane * rows * 8, padded.size() * sizeof(float));
+      for (size_t r = 0; r < n * rows; ++r)
+        for (size_t j = 0; j < S; ++j) cum_out[r * S + j] = padded[r * 8 + j];
+    }
   });
 }
 
@@ -270,6 +324,8 @@ int32_t rl_env_get_state(rl_env *env, double *state4, int32_t *nv_pos, uint64_t 
     RL_REQUIRE(env && state4 && nv_pos && steps_remaining && reset_count, "NULL argument");
     if (env->kind == RL_ENV_META_BANDIT)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_env_get_state is not built for RL_ENV_META_BANDIT lanes");
+    if (env->kind == RL_ENV_META_MDP)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_env_get_state is not built for RL_ENV_META_MDP lanes");
     rl_engine *e = env->eng;
     size_t n = env->cfg.n_lanes;
     d2h(e, state4 + 0 * n, env->st.x, n * sizeof(double));
@@ -295,6 +351,8 @@ int32_t rl_env_set_state(rl_env *env, const double *state4, const int32_t *nv_po
     RL_REQUIRE(env && state4 && nv_pos && steps_remaining && reset_count, "NULL argument");
     if (env->kind == RL_ENV_META_BANDIT)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_env_set_state is not built for RL_ENV_META_BANDIT lanes");
+    if (env->kind == RL_ENV_META_MDP)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_env_set_state is not built for RL_ENV_META_MDP lanes");
     rl_engine *e = env->eng;
     size_t n = env->cfg.n_lanes;
     if (env->kind == RL_ENV_TABULAR_MDP)  // the lane's state indexes the tables; its stream position is an even word

@@ -30,6 +30,8 @@ struct EnvStateDev {
   // previous inner step's reward; nv_pos = bit 0 inner episode done, bit 1 prev_step_obs is Some, bits 2-5 its action;
   // steps_remaining = inner episodes remaining in the trial
   // RL_ENV_TABULAR_MDP: x = state index, th = next unread word of the env stream (MemoryGame's columns; xdot unused)
+  // RL_ENV_META_MDP: x = inner state index, thdot = inner steps remaining, xdot = next unread word of the env stream,
+  // th = the previous inner step's reward; nv_pos and steps_remaining as on RL_ENV_META_BANDIT
   uint8_t *nv_pos;                // [n] cached_normal_velocity_is_positive
   uint32_t *steps_remaining;      // [n]
   uint32_t *reset_count;          // [n]

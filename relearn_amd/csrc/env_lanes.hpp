@@ -477,6 +477,35 @@ struct MetaOps {
 // even): one u64 for the successor, always; then, unless the row's stddev is 0, the polar normal of include/rl_normal.h,
 // 4 words per attempt.  The table index depends on the lane's state: these are vector loads through the CU's vector
 // cache (the tables are at most 3 KiB), nothing is staged.
+// TabularMdp::step's two draws, stated once for the lanes of one shared MDP (MdpOps) and the lanes that each have their own
+// (MetaMdpOps).
+// s' = #{ j < bound - 1 : cum[j] <= u }: a compare-add per entry under the launch-uniform bound, no register indexing; the
+// count cannot leave 0 .. bound - 1, and u == cum[j] goes to the bucket after j.  `cum_at(j)` is entry j of the row.
+template <class CumAt>
+__device__ __forceinline__ uint32_t mdp_successor_count(CumAt cum_at, uint32_t bound, float u) {
+  uint32_t next = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 7; ++j)
+    if (j + 1 < bound) next += cum_at(j) <= u ? 1u : 0u;
+  return next;
+}
+// mean + stddev z, formed in f64, with z the polar normal of rl_normal_sample drawn at `pos` over the lane's block select:
+// 4 words per attempt, at most 64 attempts.  Always drawn, whatever the stddev.  The one statement of the lanes' normal:
+// a reward is this value (where its stddev is not 0), a sampled MDP's mean is, and the standard normal itself is it at
+// (0, 1) — 0 + 1 z is z.  (Kept in one function body: with the loop a call further in, k_env_step<MdpOps, ..> takes a
+// register more.)
+__device__ __forceinline__ double lane_normal_affine(const uint32_t *key, uint64_t glane, uint64_t &pos, double mean,
+                                                     double stddev) {
+  double z = 0.0;
+  for (int attempt = 0; attempt < RL_NORMAL_MAX_ATTEMPTS; ++attempt) {
+    const uint64_t w1 = lane_u64_at(key, glane, pos);
+    const uint64_t w2 = lane_u64_at(key, glane, pos + 2);
+    pos += 4;
+    if (rl_normal_attempt(w1, w2, &z)) break;
+  }
+  return mean + stddev * z;
+}
+
 struct MdpOps {
   using State = ChainLane;
   static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) { chain_load(st, i, s); }
@@ -496,25 +525,11 @@ struct MdpOps {
     const uint32_t row = st * c.mdp.actions + ac;
     const float u = rl_u32_to_unit_f32((uint32_t)lane_u64_at(c.key_env, glane, s.env_pos));
     s.env_pos += 2;
-    // s' = #{ j < S - 1 : cum[j] <= u }: a compare-add per entry under the launch-uniform bound, no register indexing; the
-    // count cannot leave 0 .. S - 1, and u == cum[j] goes to the bucket after j
     const float *__restrict__ cum = c.mdp.cum + (size_t)row * S;
-    uint32_t next = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 7; ++j)
-      if (j + 1 < S) next += cum[j] <= u ? 1u : 0u;
+    const uint32_t next = mdp_successor_count([&](uint32_t j) { return cum[j]; }, S, u);
     const double mean = c.mdp.mean[row], stddev = c.mdp.stddev[row];
-    double r = mean;
-    if (stddev != 0.0) {  // rl_normal_sample over the lane's block select: 4 words per attempt, at most 64 attempts
-      double z = 0.0;
-      for (int attempt = 0; attempt < RL_NORMAL_MAX_ATTEMPTS; ++attempt) {
-        const uint64_t w1 = lane_u64_at(c.key_env, glane, s.env_pos);
-        const uint64_t w2 = lane_u64_at(c.key_env, glane, s.env_pos + 2);
-        s.env_pos += 4;
-        if (rl_normal_attempt(w1, w2, &z)) break;
-      }
-      r = mean + stddev * z;
-    }
+    double r = mean;  // a stddev of 0 draws nothing
+    if (stddev != 0.0) r = lane_normal_affine(c.key_env, glane, s.env_pos, mean, stddev);
     reward = (float)r;
     s.state = next;
     if (c.limit_kind != RL_LIMIT_NONE) {
@@ -528,6 +543,185 @@ struct MdpOps {
     s.state = 0;
     s.initial = 0;
     s.steps_remaining = c.max_steps;
+    s.reset_count += 1;
+  }
+};
+
+// ---------------------------------------------------------------- meta-MDP lanes (RL_ENV_META_MDP)
+// Wrapped<MetaEnv<Wrapped<DirichletRandomMdps, LatentStepLimit>>, TrialEpisodeLimit> (src/envs/meta.rs:128-203, 541-617;
+// mdps.rs:87-171; wrappers/step_limit.rs:13-89): every lane draws its own TabularMdp at a trial's start and keeps its
+// tables in device memory (CartPoleDev::mm: cum f32 [n][S*A][8], rows padded with 1.0f; mean f64 [n][S*A]; indexed by the
+// LOCAL lane, the streams by the global one).  An inner episode is L steps of TabularMdp::step and ends in the limit's
+// Interrupt(state), which keeps the state; the step after it ignores its action and starts the next inner episode; a
+// trial of E inner episodes is E (L + 1) - 1 steps and ends in an Interrupt.  Every draw is taken SEQUENTIALLY from the
+// lane's env stream at `env_pos` (always even).
+struct MetaMdpLane {
+  uint64_t env_pos;      // next unread word of the lane's env stream
+  uint32_t state;        // the inner state
+  uint32_t inner_left;   // inner steps remaining (LatentStepLimit)
+  float prev_reward;     // prev_step_obs: Some(InnerStepObs { action, feedback }) when prev_some
+  uint32_t prev_action;
+  uint32_t prev_some;
+  uint32_t inner_done;   // inner_successor is Interrupt(state)
+  uint32_t remaining;    // inner episodes left in the trial
+  uint32_t reset_count;
+};
+
+// Gamma(alpha, 1) = rl_gamma_sample (include/rl_normal.h) over the lane's block select, draw for draw
+__device__ __forceinline__ double lane_gamma_sample_ge1(double alpha, const uint32_t *key, uint64_t glane, uint64_t &pos) {
+  if (alpha == 1.0) {
+    const double u = rl_u64_to_open01_f64(lane_u64_at(key, glane, pos));
+    pos += 2;
+    return -rl_log(u);
+  }
+  const double d = alpha - 1.0 / 3.0;
+  const double cc = 1.0 / __builtin_sqrt(9.0 * d);
+  double g = 0.0;
+  for (int attempt = 0; attempt < RL_NORMAL_MAX_ATTEMPTS; ++attempt) {
+    const double x = lane_normal_affine(key, glane, pos, 0.0, 1.0);
+    const double u = rl_u64_to_open01_f64(lane_u64_at(key, glane, pos));
+    pos += 2;
+    if (rl_gamma_attempt(d, cc, x, u, &g)) break;
+  }
+  return g;
+}
+__device__ __forceinline__ double lane_gamma_sample(double alpha, const uint32_t *key, uint64_t glane, uint64_t &pos) {
+  if (alpha < 1.0) {  // (launch-uniform)
+    const double g = lane_gamma_sample_ge1(alpha + 1.0, key, glane, pos);
+    const double u = rl_u64_to_open01_f64(lane_u64_at(key, glane, pos));
+    pos += 2;
+    return g * rl_exp(rl_log(u) / alpha);
+  }
+  return lane_gamma_sample_ge1(alpha, key, glane, pos);
+}
+
+// DirichletRandomMdps::sample_environment (mdps.rs:151-170) into the lane's tables, in rl_random_mdps_sample's order; moves
+// `pos` behind the last word read: S A (S + 1) variates, once per trial.  The row's S gammas stay in registers: every draw is selected into its place
+// (v_cndmask per entry), the loops over a row's entries are unrolled under the launch-uniform S.
+__device__ __forceinline__ void meta_mdp_sample_tables(const CartPoleDev &c, uint64_t glane, uint64_t &pos) {
+  const uint32_t S = c.mm.states, rows = S * c.mm.actions;
+  const size_t local = (size_t)(glane - c.lane_offset);
+  float *cum = c.mm.cum + local * rows * 8;
+  double *mean = c.mm.mean + local * rows;
+  const double alpha = c.mm_prior.alpha;
+  for (uint32_t row = 0; row < rows; ++row) {
+    double g[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double sum = 0.0;
+    for (uint32_t j = 0; j < S; ++j) {
+      const double gj = lane_gamma_sample(alpha, c.key_env, glane, pos);
+      sum = sum + gj;
+#pragma unroll
+      for (uint32_t k = 0; k < 8; ++k) g[k] = k == j ? gj : g[k];
+    }
+    float p[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float cs[8] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};  // behind S: the padding no draw reaches
+    rl_dirichlet_row_normalise(g, sum, S, 8, p);
+    rl_mdp_row_cumulative(p, S, 8, cs);
+    float4 *out = reinterpret_cast<float4 *>(cum + (size_t)row * 8);  // (hipMalloc'd and 32-byte rows: aligned)
+    out[0] = make_float4(cs[0], cs[1], cs[2], cs[3]);
+    out[1] = make_float4(cs[4], cs[5], cs[6], cs[7]);
+    // Normal::new(reward_prior_mean, reward_prior_stddev).sample: always drawn, as the host sampler does
+    mean[row] = lane_normal_affine(c.key_env, glane, pos, c.mm_prior.reward_prior_mean, c.mm_prior.reward_prior_stddev);
+  }
+}
+
+struct MetaMdpOps {
+  using State = MetaMdpLane;
+  // columns: x the inner state, thdot the inner steps remaining, xdot env_pos, th the prev reward; the byte as on MetaOps
+  static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) {
+    s.state = (uint32_t)st.x[i];
+    s.env_pos = (uint64_t)st.xdot[i];
+    s.prev_reward = (float)st.th[i];
+    s.inner_left = (uint32_t)st.thdot[i];
+    const uint32_t b = st.nv_pos[i];
+    s.inner_done = b & 1u;
+    s.prev_some = (b >> 1) & 1u;
+    s.prev_action = (b >> 2) & 15u;
+    s.remaining = st.steps_remaining[i];
+    s.reset_count = st.reset_count[i];
+  }
+  static __device__ __forceinline__ void store(const EnvStateDev &st, uint32_t i, const State &s) {
+    st.x[i] = (double)s.state;
+    st.xdot[i] = (double)s.env_pos;  // exact below 2^53 words
+    st.th[i] = (double)s.prev_reward;
+    st.thdot[i] = (double)s.inner_left;
+    st.nv_pos[i] = (uint8_t)(s.inner_done | (s.prev_some << 1) | (s.prev_action << 2));
+    st.steps_remaining[i] = s.remaining;
+    st.reset_count[i] = s.reset_count;
+  }
+  // MetaObservationSpace features (meta.rs:357-363) with the inner observation's one-hot, D = S + A + 4:
+  //   [inner is None] [one-hot(inner state), S] [prev is None] [one-hot(prev action), A] [prev reward] [episode_done]
+  // (the inner observation is never None: an inner episode ends in Interrupt(state), whose state stays observable; the
+  // A + 1 entries behind a prev-None marker are zero).  S is launch-uniform: the position tests are scalar.
+  template <int D>
+  static __device__ __forceinline__ void features(const CartPoleDev &c, const State &s, float (&f)[D]) {
+    const uint32_t S = c.mm.states;
+    f[0] = 0.0f;
+#pragma unroll
+    for (uint32_t d = 1; d < (uint32_t)D - 2; ++d) {
+      float v;
+      if (d <= S) v = d - 1 == s.state ? 1.0f : 0.0f;
+      else if (d == S + 1) v = s.prev_some ? 0.0f : 1.0f;
+      else v = s.prev_some && d - S - 2 == s.prev_action ? 1.0f : 0.0f;
+      f[d] = v;
+    }
+    f[D - 2] = s.prev_some ? s.prev_reward : 0.0f;
+    f[D - 1] = s.inner_done ? 1.0f : 0.0f;
+  }
+  // MetaEnv::step (meta.rs:165-202) over Wrapped<TabularMdp, LatentStepLimit>::step, then the TrialEpisodeLimit tail
+  // (meta.rs:596-616).  `word` is unused: the draws are sequential.
+  static __device__ __forceinline__ int step(const CartPoleDev &c, State &s, int a, uint64_t glane, uint64_t,
+                                             float &reward) {
+    if (s.inner_done) {  // the action is ignored: a new inner episode (TabularMdp::initial_state draws nothing)
+      s.state = 0;
+      s.inner_left = c.mm.inner_steps;
+      s.inner_done = 0;
+      s.prev_some = 0;
+      s.prev_action = 0;
+      s.prev_reward = 0.0f;
+      reward = 0.0f;  // neutral_outer
+      return RL_SUCC_CONTINUE;
+    }
+    const uint32_t S = c.mm.states, A = c.mm.actions;
+    // (the clamps keep the loads inside the lane's tables whatever the columns hold, as on MdpOps)
+    const uint32_t st = s.state < S ? s.state : S - 1;
+    const uint32_t ac = (uint32_t)a < A ? (uint32_t)a : A - 1;
+    const size_t row = (size_t)(glane - c.lane_offset) * (S * A) + st * A + ac;
+    const float u = rl_u32_to_unit_f32((uint32_t)lane_u64_at(c.key_env, glane, s.env_pos));
+    s.env_pos += 2;
+    // the row is one 32-byte sector, padded with 1.0f: two 16-byte loads and no bound that depends on S
+    const float4 *rowp = reinterpret_cast<const float4 *>(c.mm.cum + row * 8);
+    const float4 lo = rowp[0], hi = rowp[1];
+    const float cs[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t next = mdp_successor_count([&](uint32_t j) { return cs[j]; }, 8u, u);
+    const double mean = c.mm.mean[row], stddev = c.mm_prior.reward_stddev;
+    double rd = mean;  // a stddev of 0 draws nothing
+    if (stddev != 0.0) rd = lane_normal_affine(c.key_env, glane, s.env_pos, mean, stddev);
+    const float r = (float)rd;
+    s.state = next;
+    s.prev_some = 1;
+    s.prev_action = ac;
+    s.prev_reward = r;
+    reward = r;
+    s.inner_left -= 1;
+    if (s.inner_left == 0) {  // the inner limit's Interrupt(state)
+      s.inner_done = 1;
+      s.remaining -= 1;
+      if (s.remaining == 0) return RL_SUCC_INTERRUPT;
+    }
+    return RL_SUCC_CONTINUE;
+  }
+  // TrialEpisodeLimit / MetaEnv::initial_state (meta.rs:580-589, 141-150): sample_environment, then the inner
+  // initial_state (state 0, no draw)
+  static __device__ __forceinline__ void reset(const CartPoleDev &c, State &s, uint64_t glane) {
+    meta_mdp_sample_tables(c, glane, s.env_pos);
+    s.state = 0;
+    s.inner_left = c.mm.inner_steps;
+    s.inner_done = 0;
+    s.prev_some = 0;
+    s.prev_action = 0;
+    s.prev_reward = 0.0f;
+    s.remaining = c.max_steps;
     s.reset_count += 1;
   }
 };

@@ -51,8 +51,31 @@ struct MdpTablesDev {
   uint32_t states, actions;
 };
 
+// RL_ENV_META_MDP (MetaMdpOps, env_lanes.hpp): every lane's own tables of the current trial, in one device allocation of
+// the env handle — cum f32 [n][S*A][8] (a row's running sums padded to eight floats with 1.0f: one 32-byte sector), mean f64
+// [n][S*A], both indexed by the LOCAL lane — with the sizes and the inner step limit (launch-uniform).  The lanes write the
+// tables in their reset and read them in their steps: plain pointers, never const __restrict__.  32 bytes, over the
+// bandit's arm values like MdpTablesDev.
+struct MetaMdpDev {
+  float *cum;
+  double *mean;
+  uint32_t states, actions;
+  uint32_t inner_steps;  // LatentStepLimit::new(L) of the inner episodes
+  uint32_t pad_;
+};
+// ... and the distribution's four f64 parameters, over the first four cart-pole constants, which these lanes do not read
+struct MetaMdpPriorDev {
+  double alpha, reward_prior_mean, reward_prior_stddev, reward_stddev;
+};
+
 struct CartPoleDev {
-  double gravity, mass_pole, length_half_pole, friction_cart, friction_pole, time_step;
+  union {
+    struct {
+      double gravity, mass_pole, length_half_pole, friction_cart;
+    };
+    MetaMdpPriorDev mm_prior;  // RL_ENV_META_MDP
+  };
+  double friction_pole, time_step;
   double action_force, max_pos, max_angle;
   double total_weight, inv_total_mass, mass_length_pole;
   double init_low, init_scale;  // Uniform::new_inclusive(-0.05, 0.05)
@@ -67,6 +90,7 @@ struct CartPoleDev {
   union {
     float bandit_r[8];   // DeterministicBandit::from_values, 2..8 arms
     MdpTablesDev mdp;    // RL_ENV_TABULAR_MDP
+    MetaMdpDev mm;       // RL_ENV_META_MDP
   };
   // RL_ENV_META_BANDIT (MetaOps, env_lanes.hpp): number of arms k (2..12; above four: rl_env_create_meta_bandit_wide)
   // and the bandit distribution (RL_BANDITS_*); `max_steps` holds TrialEpisodeLimit::episodes_per_trial (the trial limit is
@@ -75,7 +99,8 @@ struct CartPoleDev {
   int32_t meta_dist;
 };
 
-static_assert(sizeof(MdpTablesDev) == 8 * sizeof(float) && sizeof(CartPoleDev) == 248,
+static_assert(sizeof(MdpTablesDev) == 8 * sizeof(float) && sizeof(MetaMdpDev) == 8 * sizeof(float) &&
+                  sizeof(MetaMdpPriorDev) == 4 * sizeof(double) && sizeof(CartPoleDev) == 248,
               "the tables lie over the eight arm values: the struct keeps its size");
 
 // The tables of rl_env_create_tabular_mdp as the lanes read them (env_lanes.hpp, MdpOps), checked: `cum` [S][A][S] the f32
@@ -134,6 +159,7 @@ struct EnvSpec {
   uint32_t D, A;
   CartPoleDev dev;
   MdpTables mdp;
+  uint32_t meta_mdp_rows = 0;  // RL_ENV_META_MDP: S * A rows of tables per lane (0: the env has none)
 };
 
 // the kinds rl_env_create and rl_env_create_bandit build (the other two have constructors that name them)
@@ -142,6 +168,8 @@ inline void env_check_kind(const rl_env_config &cfg) {
     throw RlError(RL_ERR_BUILD_ENV, "RL_ENV_META_BANDIT lanes are created by rl_env_create_meta_bandit");
   if (cfg.kind == RL_ENV_TABULAR_MDP)
     throw RlError(RL_ERR_BUILD_ENV, "RL_ENV_TABULAR_MDP lanes are created by rl_env_create_tabular_mdp");
+  if (cfg.kind == RL_ENV_META_MDP)
+    throw RlError(RL_ERR_BUILD_ENV, "RL_ENV_META_MDP lanes are created by rl_env_create_meta_mdp");
   if (cfg.kind != RL_ENV_CARTPOLE && cfg.kind != RL_ENV_CHAIN && cfg.kind != RL_ENV_MEMORY && cfg.kind != RL_ENV_BANDIT)
     throw RlError(RL_ERR_BUILD_ENV, "unknown env kind");
 }
@@ -310,6 +338,64 @@ inline EnvSpec env_spec_mdp(const rl_env_config &cfg_in, const rl_tabular_mdp_co
   d.mdp.actions = tables.A;
   s.mdp = std::move(tables);
   return s;
+}
+
+// MetaEnv::new(DirichletRandomMdps{..}.wrap(LatentStepLimit::new(L))).wrap(TrialEpisodeLimit::new(E)) (meta.rs:128-203,
+// 541-617; mdps.rs:87-171; wrappers/step_limit.rs:13-89), whatever cfg.kind says.  Observations: MetaObservationSpace
+// with the inner state's one-hot, S + A + 4 features — the widest lanes have 16, so 10 x 5 (19) does not build.
+constexpr uint32_t RL_META_MDP_MAX = 8;  // states, and actions
+inline EnvSpec env_spec_meta_mdp(const rl_env_config &cfg_in, const rl_meta_mdp_config &meta) {
+  const rl_env_config cfg = env_config_of_kind(cfg_in, RL_ENV_META_MDP);
+  const uint64_t S = meta.n_states, A = meta.n_actions;
+  if (S < 2 || S > RL_META_MDP_MAX || A < 2 || A > RL_META_MDP_MAX || S + A + 4 > RL_WIDE_MAX_OBS_DIM)
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: n_states 2..8 and n_actions 2..8 with n_states + n_actions "
+                                    "+ 4 observation features, at most 16");
+  if (meta.max_inner_steps == 0 || meta.max_inner_steps >= (1ull << 32))  // StepLimit::new asserts > 0
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: max_inner_steps must be positive and < 2^32");
+  if (meta.episodes_per_trial == 0 || meta.episodes_per_trial >= (1ull << 32))  // TrialEpisodeLimit::new (meta.rs:548-553)
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: episodes_per_trial must be positive and < 2^32");
+  if (!std::isfinite(meta.alpha) || !(meta.alpha > 0.0))
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: alpha must be positive and finite");
+  if (!std::isfinite(meta.reward_prior_mean))
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: reward_prior_mean is not finite");
+  if (!std::isfinite(meta.reward_prior_stddev) || meta.reward_prior_stddev < 0.0)
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: reward_prior_stddev is negative or not finite");
+  if (!std::isfinite(meta.reward_stddev) || meta.reward_stddev < 0.0)
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: reward_stddev is negative or not finite");
+  if (!std::isfinite(meta.discount_factor))
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: discount_factor is not finite");
+  if (cfg.limit_kind != RL_LIMIT_NONE)
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: the lanes take no step limit (the inner limit and the trial's "
+                                    "episode limit are this env's limits)");
+  env_check_limit_and_lanes(cfg);
+  EnvSpec s = env_spec_begin(cfg, (uint32_t)(S + A + 4), (uint32_t)A);
+  CartPoleDev &d = s.dev;
+  d.init_low = -0.05;  // (read by nothing on these lanes)
+  d.init_scale = rl_uniform_f64_inclusive_scale(-0.05, 0.05);
+  d.max_steps = (uint32_t)meta.episodes_per_trial;  // the trial's episode limit in the place of the step limit
+  d.chain_size = 0;  // (as on meta-bandit lanes: nothing takes these for an index env of five states)
+  d.mm.cum = nullptr;  // (env_build points them into the handle's memory)
+  d.mm.mean = nullptr;
+  d.mm.states = (uint32_t)S;
+  d.mm.actions = (uint32_t)A;
+  d.mm.inner_steps = (uint32_t)meta.max_inner_steps;
+  d.mm.pad_ = 0;
+  d.mm_prior = MetaMdpPriorDev{meta.alpha, meta.reward_prior_mean, meta.reward_prior_stddev, meta.reward_stddev};
+  s.meta_mdp_rows = (uint32_t)(S * A);
+  return s;
+}
+
+// The (S, A) shapes of RL_ENV_META_MDP lanes whose recurrent rollout is one launch (k_stack_rollout<.., MetaMdpOps, ..>,
+// kernels_seq_stack.hip): the smallest, the odd widths, the default, the most features with the widest row, and the most
+// actions with two head passes.  Every other shape in range runs the launch sequence per step.
+struct MetaMdpShape {
+  uint32_t S, A;
+};
+constexpr MetaMdpShape META_MDP_FUSED_SHAPES[] = {{2, 2}, {3, 2}, {4, 3}, {5, 5}, {8, 4}, {4, 8}};
+inline bool meta_mdp_fused_shape(uint32_t S, uint32_t A) {
+  for (const MetaMdpShape &m : META_MDP_FUSED_SHAPES)
+    if (m.S == S && m.A == A) return true;
+  return false;
 }
 
 // ---------------------------------------------------------------- modules
@@ -725,6 +811,9 @@ inline RolloutPath rollout_path(int env_kind, uint32_t D, uint32_t A, uint32_t c
   // tabular-MDP lanes: every recurrent chain, the two-output ones of the tile kernels' shapes included, steps through the
   // lane-per-thread kernels (a single-layer chain's flat order is the stacked order at one layer: stack_ensure)
   if (env_kind == RL_ENV_TABULAR_MDP && recurrent) return ROLL_STACK;
+  // meta-MDP lanes likewise (one launch at the shapes of META_MDP_FUSED_SHAPES).  A feed-forward module has at most eight
+  // inputs: it matches 2 x 2 alone, and went to ROLL_GENERAL above (chain_size is 0 on these lanes)
+  if (env_kind == RL_ENV_META_MDP) return ROLL_STACK;
   if (!fused_index_env && !m.lane_kernels())
     throw RlError(RL_ERR_UNSUPPORTED, "the fused recurrent rollout is built for index envs of five states");
   if (recurrent && m.lane_kernels()) return ROLL_STACK;

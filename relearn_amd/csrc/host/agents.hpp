@@ -146,6 +146,12 @@ class EnvLanes {
                                     stddev.empty() ? nullptr : stddev.data(), &h_), eng.handle());
     check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
   }
+  // meta-MDP lanes (rl_env_create_meta_mdp)
+  EnvLanes(Engine &eng, const rl_env_config &cfg, const rl_meta_mdp_config &meta)
+      : eng_(eng), cfg_(cfg), discount_(meta.discount_factor) {
+    check(rl_env_create_meta_mdp(eng.handle(), &cfg_, &meta, &h_), eng.handle());
+    check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
+  }
   Engine &eng_;
   rl_env_config cfg_;
   rl_env *h_ = nullptr;
@@ -300,6 +306,51 @@ class TabularMdpLanes : public EnvLanes {
     c.kind = RL_ENV_TABULAR_MDP;
     c.limit_kind = (int32_t)limit;
     c.max_steps = max_steps;
+    c.n_lanes = n;
+    c.lane_offset = off;
+    c.seed_env = se;
+    c.seed_actor = sa;
+    check(rl_cartpole_params_default(&c.cartpole));
+    return c;
+  }
+};
+
+// `MetaEnv::new(DirichletRandomMdps{..}.wrap(LatentStepLimit::new(L))).wrap(TrialEpisodeLimit::new(E))` x n_lanes
+// (src/envs/meta.rs:128-203, 541-617 over mdps.rs:87-171): the second task of the RL^2 paper.  Every lane draws its own MDP
+// at each trial's start; S + A + 4 observation features, at most 16; a trial is E (L + 1) - 1 steps and ends in an
+// Interrupt.  `dist`: the scalar mirror's distribution (host/envs.hpp), whose sample_environment(seed_env, g) is lane g's
+// first trial.  Policies: the recurrent chains of rl_rnn_chain_create_wide.
+class MetaMdpLanes : public EnvLanes {
+ public:
+  MetaMdpLanes(Engine &eng, uint64_t n_lanes, const DirichletRandomMdps &dist, uint64_t max_inner_steps = 10,
+               uint64_t episodes_per_trial = 10, double reward_stddev = 1.0, uint64_t seed_env = 0, uint64_t seed_actor = 1,
+               uint64_t lane_offset = 0)
+      : EnvLanes(eng, config(n_lanes, seed_env, seed_actor, lane_offset),
+                 rl_meta_mdp_config{(uint32_t)dist.num_states, (uint32_t)dist.num_actions,
+                                    dist.transition_prior_dirichlet_alpha, dist.reward_prior_mean, dist.reward_prior_stddev,
+                                    reward_stddev, dist.discount_factor, max_inner_steps, episodes_per_trial}),
+        states_(dist.num_states), trial_steps_(episodes_per_trial * (max_inner_steps + 1) - 1) {}
+  uint64_t trial_steps() const { return trial_steps_; }
+  // the current trial's tables of lanes [first, first + n) as the lanes read them: running sums [n][S*A][S], means [n][S*A]
+  struct Tables {
+    std::vector<float> cumulative;
+    std::vector<double> reward_mean;
+  };
+  Tables read_tables(uint64_t first, uint64_t n) {
+    Tables t;
+    const size_t rows = (size_t)n * states_ * n_actions_;
+    t.cumulative.resize(rows * states_);
+    t.reward_mean.resize(rows);
+    check(rl_env_meta_mdp_read_tables(h_, first, n, t.cumulative.data(), t.reward_mean.data()), eng_.handle());
+    return t;
+  }
+
+ private:
+  uint64_t states_, trial_steps_;
+  static rl_env_config config(uint64_t n, uint64_t se, uint64_t sa, uint64_t off) {
+    rl_env_config c{};
+    c.kind = RL_ENV_META_MDP;
+    c.limit_kind = RL_LIMIT_NONE;
     c.n_lanes = n;
     c.lane_offset = off;
     c.seed_env = se;

@@ -112,17 +112,9 @@ struct TabularMdp {
     if (reward_stddev.empty()) reward_stddev.assign(S * A, 1.0);
     if (reward_stddev.size() != S * A) throw std::invalid_argument("TabularMdp: reward_stddev of [S][A]");
     cumulative.resize(transitions.size());
-    for (uint64_t row = 0; row < S * A; ++row) {
-      float acc = 0.0f;
-      uint64_t last = 0;
-      for (uint64_t j = 0; j < S; ++j) {
-        acc = acc + transitions[row * S + j];
-        cumulative[row * S + j] = acc;
-        if (transitions[row * S + j] > 0.0f) last = j;
-      }
-      // no draw reaches 1: the rounding of the running sum opens no bucket behind the last possible successor
-      for (uint64_t j = last; j < S; ++j) cumulative[row * S + j] = 1.0f;
-    }
+    // the running sums, from the row's last possible successor on exactly 1: the one statement the lanes share
+    for (uint64_t row = 0; row < S * A; ++row)
+      rl_mdp_row_cumulative(transitions.data() + row * S, (uint32_t)S, (uint32_t)S, cumulative.data() + row * S);
   }
   uint64_t num_observations() const { return num_states; }
   uint64_t num_actions() const { return num_actions_; }
@@ -171,10 +163,22 @@ struct DirichletRandomMdps {
   }
   // transitions [S][A][S], reward_mean [S][A]
   void sample_tables(uint64_t seed, uint64_t stream, float *transitions, double *reward_mean) const {
-    validate();
     uint32_t key[8];
     rl_seed_from_u64(seed, key);
     uint64_t pos = 0;
+    sample_tables_at(key, stream, &pos, transitions, reward_mean);
+  }
+  // the same draws from a sequential generator where it stands, which moves behind them: a meta env's trial start
+  void sample_tables_from(Prng &rng, float *transitions, double *reward_mean) const {
+    uint64_t pos = rng.word_pos();
+    sample_tables_at(rng.key(), rng.stream(), &pos, transitions, reward_mean);
+    rng.set_word_pos(pos);
+  }
+  // ... from word `*pos` (even) of the stream (key, stream); `*pos` moves behind the last word read
+  void sample_tables_at(const uint32_t key[8], uint64_t stream, uint64_t *pos_io, float *transitions,
+                        double *reward_mean) const {
+    validate();
+    uint64_t pos = *pos_io;
     const uint64_t S = num_states, A = num_actions;
     double g[64];
     for (uint64_t row = 0; row < S * A; ++row) {
@@ -183,10 +187,11 @@ struct DirichletRandomMdps {
         g[j] = rl_gamma_sample(transition_prior_dirichlet_alpha, key, stream, &pos);
         sum = sum + g[j];
       }
-      for (uint64_t j = 0; j < S; ++j) transitions[row * S + j] = (float)(g[j] / sum);
+      rl_dirichlet_row_normalise(g, sum, (uint32_t)S, (uint32_t)S, transitions + row * S);
       // Normal::new(reward_prior_mean, reward_prior_stddev).sample
       reward_mean[row] = reward_prior_mean + reward_prior_stddev * rl_normal_sample(key, stream, &pos);
     }
+    *pos_io = pos;
   }
   TabularMdp sample_environment(uint64_t seed, uint64_t stream = 0) const {
     validate();
@@ -218,6 +223,92 @@ struct WithLatentStepLimit {
     const uint64_t left = s.steps_remaining - 1;
     auto wrapped = std::move(succ).template map<State>([&](typename E::State in) { return State{std::move(in), left}; });
     return {std::move(wrapped).then_interrupt_if([](const State &n) { return n.steps_remaining == 0; }), reward};
+  }
+};
+
+// Wrapped<MetaEnv<Wrapped<DirichletRandomMdps, LatentStepLimit>>, TrialEpisodeLimit> (src/envs/meta.rs:128-203, 541-617
+// over mdps.rs:87-171 and wrappers/step_limit.rs:13-89), the second task of the RL^2 paper, as the lanes of
+// rl_env_create_meta_mdp state it (include/relearn_hip.h): a trial starts with sample_environment from the env generator
+// where it stands; an inner episode is max_inner_steps steps of TabularMdp::step and ends in the limit's Interrupt(state);
+// the step after it ignores its action, draws nothing and starts the next inner episode; the step that ends the trial's
+// last inner episode is an Interrupt.  The scalar env takes any size the sampler takes; the lanes end at 8 x 8 and 16
+// features.  One generator, seed_from_u64(seed_env) on stream g, gives lane g's trials.
+struct MetaRandomMdps {
+  using Action = uint64_t;
+  using Observation = std::vector<float>;
+  struct State {
+    TabularMdp mdp;  // the trial's MDP
+    uint64_t inner_state = 0, inner_left = 0, episodes_left = 0;
+    bool inner_done = false;  // inner_successor is Interrupt(inner_state)
+    bool prev_some = false;   // prev_step_obs: Some(InnerStepObs { action, feedback })
+    uint64_t prev_action = 0;
+    float prev_reward = 0.0f;
+  };
+  DirichletRandomMdps dist;
+  uint64_t max_inner_steps = 10, episodes_per_trial = 10;
+  double reward_stddev = 1.0;  // of every sampled MDP's rewards (mdps.rs:163)
+
+  void validate() const {
+    dist.validate();
+    if (max_inner_steps == 0) throw std::invalid_argument("MetaRandomMdps: max_inner_steps must be positive");
+    if (episodes_per_trial == 0) throw std::invalid_argument("MetaRandomMdps: trials must contain at least 1 episode");
+    if (!std::isfinite(reward_stddev) || reward_stddev < 0.0)
+      throw std::invalid_argument("MetaRandomMdps: reward_stddev must be non-negative and finite");
+  }
+  uint64_t num_observation_features() const { return dist.num_states + dist.num_actions + 4; }
+  uint64_t num_actions() const { return dist.num_actions; }
+  uint64_t trial_steps() const { return episodes_per_trial * (max_inner_steps + 1) - 1; }
+  // TrialEpisodeLimit / MetaEnv::initial_state: sample_environment, then the inner initial_state (state 0, no draw)
+  State initial_state(Prng &rng) const {
+    validate();
+    const uint64_t S = dist.num_states, A = dist.num_actions;
+    std::vector<float> tr(S * A * S);
+    std::vector<double> mean(S * A);
+    dist.sample_tables_from(rng, tr.data(), mean.data());
+    State s;
+    s.mdp = TabularMdp(S, A, std::move(tr), std::move(mean), std::vector<double>(S * A, reward_stddev), dist.discount_factor);
+    s.inner_left = max_inner_steps;
+    s.episodes_left = episodes_per_trial;
+    return s;
+  }
+  // [inner is None] [one-hot(inner state), S] [prev is None] [one-hot(prev action), A] [prev reward] [episode_done]
+  Observation observe(const State &s, Prng &) const {
+    const uint64_t S = dist.num_states, A = dist.num_actions;
+    Observation f(S + A + 4, 0.0f);
+    f[1 + s.inner_state] = 1.0f;
+    if (s.prev_some) {
+      f[2 + S + s.prev_action] = 1.0f;
+      f[2 + S + A] = s.prev_reward;
+    } else {
+      f[1 + S] = 1.0f;
+    }
+    f[S + A + 3] = s.inner_done ? 1.0f : 0.0f;
+    return f;
+  }
+  // (an action outside 0 .. num_actions - 1 is the caller's error, as on TabularMdp)
+  std::pair<Successor<State>, double> step(State s, Action a, Prng &rng) const {
+    if (s.inner_done) {  // the action is ignored, nothing is drawn
+      s.inner_state = 0;
+      s.inner_left = max_inner_steps;
+      s.inner_done = false;
+      s.prev_some = false;
+      s.prev_action = 0;
+      s.prev_reward = 0.0f;
+      return {Successor<State>::Continue(std::move(s)), 0.0};
+    }
+    auto [succ, reward] = s.mdp.step(s.inner_state, a, rng);
+    s.inner_state = *succ.state;
+    s.prev_some = true;
+    s.prev_action = a;
+    s.prev_reward = (float)reward;
+    const double outer = (double)s.prev_reward;
+    s.inner_left -= 1;
+    if (s.inner_left == 0) {
+      s.inner_done = true;
+      s.episodes_left -= 1;
+      if (s.episodes_left == 0) return {Successor<State>::Interrupt(std::move(s)), outer};
+    }
+    return {Successor<State>::Continue(std::move(s)), outer};
   }
 };
 

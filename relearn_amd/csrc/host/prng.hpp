@@ -34,6 +34,12 @@ class Prng {
     index_ = static_cast<uint32_t>(word_pos % 16);
   }
 
+  // where the generator stands: its key, its stream and the next unread word (what get_word_pos gives) — for code that
+  // draws by position (include/rl_normal.h) and moves the generator behind its draws with set_word_pos
+  const uint32_t *key() const { return key_.data(); }
+  uint64_t stream() const { return stream_; }
+  uint64_t word_pos() const { return (next_block_ - 4) * 16 + index_; }  // (unread buffer: index_ == kBuf, the next block)
+
   uint32_t next_u32() {
     if (index_ >= kBuf) {
       refill();

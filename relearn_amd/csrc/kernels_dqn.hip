@@ -645,6 +645,9 @@ static void dqn_env_dispatch(const rl_env *env, const char *what, Go &&go) {
     throw RlError(RL_ERR_UNSUPPORTED, what);
   }
   const bool cartpole = env->kind == RL_ENV_CARTPOLE;
+  // (meta lanes and any kind this function does not know are never collected by the index lanes' code)
+  if (!cartpole && env->kind != RL_ENV_CHAIN && env->kind != RL_ENV_MEMORY && env->kind != RL_ENV_BANDIT)
+    throw RlError(RL_ERR_UNSUPPORTED, what);
   if (env->D < 4 || env->D > (cartpole ? 5u : (uint32_t)MAX_D)) throw RlError(RL_ERR_UNSUPPORTED, what);
   if (cartpole) {
     if (env->D == 5) go(CartPoleOps{}, FeatureCount<5>{});

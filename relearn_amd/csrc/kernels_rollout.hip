@@ -402,7 +402,8 @@ void launch_obs_range(rl_traj *traj) {
 
 // The standalone env kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature
 // count as types.  CartPole lanes have 4 or 5 features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame:
-// num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..16; tabular-MDP lanes states [+ 1] = 2..8.
+// num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..16; tabular-MDP lanes states [+ 1] = 2..8;
+// meta-MDP lanes states + actions + 4 = 8..16.
 template <int D>
 using FeatureCount = std::integral_constant<int, D>;
 template <class Go>
@@ -429,6 +430,21 @@ static void env_dispatch(const rl_env *env, Go &&go) {
     }
     return;
   }
+  if (env->kind == RL_ENV_META_MDP) {  // S + A + 4 features, S and A 2..8 with at most 16 in all
+    switch (env->D) {
+      case 8: go(MetaMdpOps{}, FeatureCount<8>{}); break;
+      case 9: go(MetaMdpOps{}, FeatureCount<9>{}); break;
+      case 10: go(MetaMdpOps{}, FeatureCount<10>{}); break;
+      case 11: go(MetaMdpOps{}, FeatureCount<11>{}); break;
+      case 12: go(MetaMdpOps{}, FeatureCount<12>{}); break;
+      case 13: go(MetaMdpOps{}, FeatureCount<13>{}); break;
+      case 14: go(MetaMdpOps{}, FeatureCount<14>{}); break;
+      case 15: go(MetaMdpOps{}, FeatureCount<15>{}); break;
+      case 16: go(MetaMdpOps{}, FeatureCount<16>{}); break;
+      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-MDP lanes: 8..16 observation features");
+    }
+    return;
+  }
   if (env->kind == RL_ENV_TABULAR_MDP) {  // n_states [+ 1] features, 2..8 states
     switch (env->D) {
       case 2: go(MdpOps{}, FeatureCount<2>{}); break;
@@ -442,6 +458,9 @@ static void env_dispatch(const rl_env *env, Go &&go) {
     }
     return;
   }
+  // (a kind this function does not know never steps through the index lanes' code)
+  if (env->kind != RL_ENV_CHAIN && env->kind != RL_ENV_MEMORY && env->kind != RL_ENV_BANDIT)
+    throw RlError(RL_ERR_UNSUPPORTED, "env kernels: unknown env kind");
   switch (env->D) {
     case 4: go(IndexOps{}, FeatureCount<4>{}); break;
     case 5: go(IndexOps{}, FeatureCount<5>{}); break;
@@ -461,6 +480,10 @@ void launch_env_reset(rl_env *env) {
     hipLaunchKernelGGL(k_env_reset<MetaOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else if (env->kind == RL_ENV_TABULAR_MDP)
     hipLaunchKernelGGL(k_env_reset<MdpOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  else if (env->kind == RL_ENV_META_MDP)
+    hipLaunchKernelGGL(k_env_reset<MetaMdpOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  else if (env->kind != RL_ENV_CHAIN && env->kind != RL_ENV_MEMORY && env->kind != RL_ENV_BANDIT)
+    throw RlError(RL_ERR_UNSUPPORTED, "env kernels: unknown env kind");
   else
     hipLaunchKernelGGL(k_env_reset<IndexOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
 }

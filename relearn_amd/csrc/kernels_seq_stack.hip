@@ -1050,6 +1050,38 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     env->t_global += traj->d.T;
     return;
   }
+  if (env->kind == RL_ENV_META_MDP && env->eng->kernel_variant != 1 &&
+      meta_mdp_fused_shape(env->dev.mm.states, env->dev.mm.actions)) {
+    // meta-MDP lanes at the shapes of META_MDP_FUSED_SHAPES (handle_spec.hpp): all T steps in one launch; every other
+    // shape in range, and kernel variant 1, keep the launch sequence per step, below.  Trials have one length, so all
+    // lanes of a run draw their tables at the same step: a serial section of wave 0, once per trial (MetaMdpOps::reset).
+    const uint32_t S = env->dev.mm.states, A = env->dev.mm.actions;
+    RL_REQUIRE(env->D == S + A + 4 && env->A == A, "fused recurrent rollout on meta-MDP lanes: S + A + 4 features");
+#define ROLL(CELL, LIN, SS, AA)                                                                                       \
+  hipLaunchKernelGGL((k_stack_rollout<CELL, MetaMdpOps, SS + AA + 4, LIN, AA>), grid, blk, 0, env->eng->stream, net, \
+                     ws, env->dev, env->st, traj->d, env->t_global)
+#define ROLL_SHAPES(CELL, LIN)                                  \
+  do {                                                          \
+    if (S == 2 && A == 2) ROLL(CELL, LIN, 2, 2);                \
+    else if (S == 3 && A == 2) ROLL(CELL, LIN, 3, 2);           \
+    else if (S == 4 && A == 3) ROLL(CELL, LIN, 4, 3);           \
+    else if (S == 5 && A == 5) ROLL(CELL, LIN, 5, 5);           \
+    else if (S == 8 && A == 4) ROLL(CELL, LIN, 8, 4);           \
+    else ROLL(CELL, LIN, 4, 8);                                 \
+  } while (0)
+    if (lstm) {
+      if (lin) ROLL_SHAPES(LSTM, true);
+      else ROLL_SHAPES(LSTM, false);
+    } else {
+      if (lin) ROLL_SHAPES(GRU, true);
+      else ROLL_SHAPES(GRU, false);
+    }
+#undef ROLL_SHAPES
+#undef ROLL
+    RL_HIP_CHECK(hipGetLastError());
+    env->t_global += traj->d.T;
+    return;
+  }
   launch_rollout_stepwise(env, traj, z, [&](uint32_t step) {
     const int first = step == 0 ? 1 : 0, parity = (int)(step & 1);
     // (the step before has been recorded by now: its successor codes are in the trajectory)
