@@ -358,7 +358,8 @@ typedef struct {
   uint64_t episodes_per_trial; /* TrialEpisodeLimit::new(E) */
 } rl_meta_mdp_config;
 /* 5 states, 5 actions, alpha 1, prior N(1, 1), reward stddev 1, discount 1, L = 10, E = 10.  Five states and not
- * DirichletRandomMdps::default's ten: 10 x 5 has 19 observation features and the widest lanes 16. */
+ * DirichletRandomMdps::default's ten: 10 x 5 has 19 observation features and rl_env_create_meta_mdp ends at 16
+ * (rl_env_create_meta_mdp_wide takes it). */
 int32_t rl_meta_mdp_config_default(rl_meta_mdp_config *meta);
 /* `cfg` supplies the lanes, the lane offset and the seeds, as in rl_env_create_meta_bandit; its kind is not read.
  * RL_ERR_BUILD_ENV: sizes outside the ranges above, L or E zero or >= 2^32, alpha not positive and finite, a stddev
@@ -368,6 +369,18 @@ int32_t rl_meta_mdp_config_default(rl_meta_mdp_config *meta);
  * module of eight inputs, every update on what was collected, and rl_summary_push (an episode is a trial).  Not built,
  * RL_ERR_UNSUPPORTED by name: rl_env_get_state / rl_env_set_state, rl_dqn_create*, rl_actor_to_cbor, rl_bandit_agent_*. */
 int32_t rl_env_create_meta_mdp(rl_engine *engine, const rl_env_config *cfg, const rl_meta_mdp_config *meta, rl_env **out);
+/* The same lanes at n_states 2..10 and n_actions 2..8 with n_states + n_actions + 4 <= 20 observation features: the size
+ * of DirichletRandomMdps::default and of the RL^2 paper's tabular-MDP task, 10 x 5 (19 features), is in this range.
+ * Wherever rl_env_create_meta_mdp builds, this is that constructor and that handle.  RL_ERR_BUILD_ENV, in this entry
+ * point's name: sizes outside these ranges (tested first), then everything rl_env_create_meta_mdp refuses.  At nine and
+ * ten states a lane's row of running sums is sixteen floats in device memory; rl_env_meta_mdp_read_tables returns `cum`
+ * at the logical width S whatever the padded row is.  Above 16 features the lanes serve rl_env_reset / _observe / _step,
+ * rl_rollout under a recurrent chain of rl_rnn_chain_create_wide20 into a trajectory of rl_traj_create_wide (one launch
+ * at 10 x 5 unless the kernel variant is 1; a launch sequence per step otherwise), every update on what was collected,
+ * and rl_summary_push.  Feed-forward modules (at most eight inputs) do not build for them; rl_dqn_create*,
+ * rl_env_get_state / rl_env_set_state, rl_actor_to_cbor and rl_bandit_agent_* refuse every meta-MDP lane by name. */
+int32_t rl_env_create_meta_mdp_wide(rl_engine *engine, const rl_env_config *cfg, const rl_meta_mdp_config *meta,
+                                    rl_env **out);
 /* The current trial's tables of lanes first_lane .. first_lane + n - 1 (local lanes) as the lanes read them; read-only.
  * cum_out [n][S*A][S] f32 running sums, mean_out [n][S*A] f64; either may be NULL. */
 int32_t rl_env_meta_mdp_read_tables(rl_env *env, uint64_t first_lane, uint64_t n, float *cum_out, double *mean_out);
@@ -591,6 +604,11 @@ int32_t rl_rnn_chain_create(rl_engine *engine, const rl_rnn_chain_config *cfg, r
  * 0 or 13, in_dim 0 or 17 -> RL_ERR_BUILD_AGENT; everything else as rl_rnn_chain_create.  Not an action-value module, and
  * no actor document on the lanes wide enough to need it. */
 int32_t rl_rnn_chain_create_wide(rl_engine *engine, const rl_rnn_chain_config *cfg, rl_mlp **out);
+/* The same chain at in_dim 1..20 and out_dim 1..12: the model of the RL^2 MDP experiment on 10 x 5 lanes (19 inputs; five
+ * outputs for the policy, one for the critic).  "wide20" names the bound: rl_rnn_chain_create_wide keeps ending at 16.
+ * in_dim <= 16: rl_rnn_chain_create_wide, the same handle and the same refusals.  in_dim 0 or 21, out_dim 0 or 13 ->
+ * RL_ERR_BUILD_AGENT; everything else as rl_rnn_chain_create.  Serves trajectories of rl_traj_create_wide. */
+int32_t rl_rnn_chain_create_wide20(rl_engine *engine, const rl_rnn_chain_config *cfg, rl_mlp **out);
 
 /* ---------------------------------------------------------------------------------------------
  * Trajectory store (replaces VecBuffer + LazyHistoryFeatures: src/agents/buffers/vec.rs:15-143,
@@ -613,6 +631,9 @@ typedef enum {
 /* obs_dim in 1..8 (feed-forward modules take 4 or 5; the others serve recurrent chains of that in_dim, written through
  * rl_traj_write: the envs of this library have 4 or 5 features) */
 int32_t rl_traj_create(rl_engine *engine, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, rl_traj **out);
+/* The same store with up to 20 observation planes (the lanes of rl_env_create_meta_mdp_wide).  Up to the width
+ * rl_traj_create takes it is rl_traj_create.  Whatever reads a trajectory checks its own width against the planes'. */
+int32_t rl_traj_create_wide(rl_engine *engine, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, rl_traj **out);
 int32_t rl_traj_destroy(rl_traj *traj);
 int32_t rl_traj_field_bytes(const rl_traj *traj, int32_t field, uint64_t *bytes);
 int32_t rl_traj_read(rl_traj *traj, int32_t field, void *host, uint64_t bytes);

@@ -50,12 +50,12 @@ ABI_SYMBOLS = [
     "rl_last_error", "rl_engine_info", "rl_engine_set_kernel_variant", "rl_timer_begin", "rl_timer_end", "rl_profile_enable", "rl_profile_read",
     "rl_comm_available", "rl_comm_library_paths", "rl_comm_unique_id", "rl_comm_init", "rl_comm_destroy", "rl_comm_init_host",
     "rl_comm_ipc_handle", "rl_comm_init_ipc", "rl_comm_selftest",
-    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_create_tabular_mdp", "rl_random_mdps_config_default", "rl_random_mdps_sample", "rl_meta_mdp_config_default", "rl_env_create_meta_mdp", "rl_env_meta_mdp_read_tables", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
+    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_create_tabular_mdp", "rl_random_mdps_config_default", "rl_random_mdps_sample", "rl_meta_mdp_config_default", "rl_env_create_meta_mdp", "rl_env_create_meta_mdp_wide", "rl_env_meta_mdp_read_tables", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
-    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_chain_config_default", "rl_rnn_chain_create", "rl_rnn_chain_create_wide", "rl_rnn_mlp_init_with", "rl_seq_forward",
-    "rl_traj_create", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write",
+    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_chain_config_default", "rl_rnn_chain_create", "rl_rnn_chain_create_wide", "rl_rnn_chain_create_wide20", "rl_rnn_mlp_init_with", "rl_seq_forward",
+    "rl_traj_create", "rl_traj_create_wide", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write",
     "rl_rollout", "rl_gae",
     "rl_trpo_config_default", "rl_trpo_update", "rl_policy_gradient", "rl_policy_fvp", "rl_policy_loss_kl",
     "rl_adam_config_default", "rl_adam_create", "rl_adam_destroy", "rl_adam_step_host",
@@ -677,6 +677,8 @@ class MetaMdpEnv(ChainEnv):
     S + A + 4 features [inner is None] [one-hot(state)] [prev is None] [one-hot(prev action)] [prev reward]
     [episode_done]; S and A 2..8 with S + A + 4 <= 16.  `meta`: a MetaMdpConfig instead of the keyword fields."""
 
+    CREATE = "rl_env_create_meta_mdp"
+
     def __init__(self, engine, n_lanes, n_states=5, n_actions=5, max_inner_steps=10, episodes_per_trial=10, alpha=1.0,
                  reward_prior_mean=1.0, reward_prior_stddev=1.0, reward_stddev=1.0, discount_factor=1.0, lane_offset=0,
                  seed_env=0, seed_actor=1, limit=LIMIT_NONE, max_steps=0, meta=None):
@@ -698,7 +700,7 @@ class MetaMdpEnv(ChainEnv):
             meta.max_inner_steps, meta.episodes_per_trial = max_inner_steps, episodes_per_trial
         self.cfg, self.meta = cfg, meta
         self.h = C.c_void_p()
-        _check(lib().rl_env_create_meta_mdp(engine.h, C.byref(cfg), C.byref(meta), C.byref(self.h)), engine.h)
+        _check(getattr(lib(), self.CREATE)(engine.h, C.byref(cfg), C.byref(meta), C.byref(self.h)), engine.h)
         _register(self)
         self.n = n_lanes
         self.S, self.n_actions = int(meta.n_states), int(meta.n_actions)
@@ -719,6 +721,14 @@ class MetaMdpEnv(ChainEnv):
 
     get_state = CartPoleEnv.get_state  # (refused by the library: RL_ERR_UNSUPPORTED)
     set_state = CartPoleEnv.set_state
+
+
+class MetaMdpEnvWide(MetaMdpEnv):
+    """The same lanes at 2..10 states and 2..8 actions with S + A + 4 <= 20 observation features
+    (rl_env_create_meta_mdp_wide; wherever MetaMdpEnv builds, this builds the same handle): 10 x 5, the size of
+    DirichletRandomMdps::default, has 19.  Above 16 features: recurrent chains of RnnChainWide20 and TrajectoryWide."""
+
+    CREATE = "rl_env_create_meta_mdp_wide"
 
 
 class GruMlp(_Handle):
@@ -846,6 +856,13 @@ class RnnChainWide(RnnChain):
     CREATE = "rl_rnn_chain_create_wide"
 
 
+class RnnChainWide20(RnnChain):
+    """The same chain at in_dim 1..20 and out_dim 1..12 (rl_rnn_chain_create_wide20; at in_dim <= 16 it builds what
+    RnnChainWide builds): policy and critic of the RL2 experiment on random MDPs of 10 states and 5 actions (19 inputs)."""
+
+    CREATE = "rl_rnn_chain_create_wide20"
+
+
 ACTIVATIONS = ["Identity", "Relu", "Sigmoid", "Tanh"]  # rl_activation, in the reference enum's order
 INIT_KINDS = ["Zeros", "Constant", "Uniform", "Normal", "Orthogonal"]  # rl_init_kind
 VARIANCE_SCALES = ["Constant", "FanIn", "FanOut", "FanAvg"]             # rl_variance_scale
@@ -940,11 +957,13 @@ _TRAJ_DTYPES = {TRAJ_OBS: np.float32, TRAJ_ACTION: np.uint8, TRAJ_REWARD: np.flo
 
 
 class Trajectory(_Handle):
+    CREATE = "rl_traj_create"
+
     def __init__(self, engine, n_lanes, horizon, obs_dim):
         self.eng = engine
         self.h = C.c_void_p()
-        _check(lib().rl_traj_create(engine.h, C.c_uint64(n_lanes), C.c_uint64(horizon), C.c_uint32(obs_dim),
-                                    C.byref(self.h)), engine.h)
+        _check(getattr(lib(), self.CREATE)(engine.h, C.c_uint64(n_lanes), C.c_uint64(horizon), C.c_uint32(obs_dim),
+                                           C.byref(self.h)), engine.h)
         _register(self)
         self.n, self.T, self.D = n_lanes, horizon, obs_dim
 
@@ -980,6 +999,13 @@ class Trajectory(_Handle):
         self.write(TRAJ_REWARD, traj["reward"])
         self.write(TRAJ_FLAG, traj["flag"])
         self.write(TRAJ_TERM_OBS, traj["term_obs"])
+
+
+class TrajectoryWide(Trajectory):
+    """The same store with up to 20 observation planes (rl_traj_create_wide; up to 16 it builds what Trajectory builds):
+    the trajectories of MetaMdpEnvWide lanes."""
+
+    CREATE = "rl_traj_create_wide"
 
 
 def rollout(env, policy, traj):

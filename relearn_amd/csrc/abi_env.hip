@@ -67,10 +67,11 @@ static void env_build(rl_engine *e, const EnvSpec &spec, rl_env **out) {
     // every lane's own tables, written by the lanes' reset below: one allocation of the handle, the rows
     // of running sums first — 32 bytes each from an aligned base, so both 16-byte halves of a row are aligned — then the
     // f64 means
-    const size_t rows = n * spec.meta_mdp_rows;
-    uint8_t *tab = mem.alloc<uint8_t>(rows * 8 * sizeof(float) + rows * sizeof(double));
+    // (above eight states a row is sixteen floats, 64 bytes: meta_mdp_row_floats)
+    const size_t rows = n * spec.meta_mdp_rows, row_bytes = meta_mdp_row_floats(spec.dev.mm.states) * sizeof(float);
+    uint8_t *tab = mem.alloc<uint8_t>(rows * row_bytes + rows * sizeof(double));
     env->dev.mm.cum = reinterpret_cast<float *>(tab);
-    env->dev.mm.mean = reinterpret_cast<double *>(tab + rows * 8 * sizeof(float));
+    env->dev.mm.mean = reinterpret_cast<double *>(tab + rows * row_bytes);
   }
   RL_HIP_CHECK(hipMemsetAsync(env->st.reset_count, 0, n * sizeof(uint32_t), e->stream));
   for (double *p : {env->st.x, env->st.xdot, env->st.th, env->st.thdot})
@@ -147,8 +148,8 @@ int32_t rl_env_create_tabular_mdp(rl_engine *e, const rl_env_config *cfg, const 
   });
 }
 
-// DirichletRandomMdps::default (mdps.rs:111-122) but for the sizes — 10 x 5 has 19 observation features, the widest lanes
-// 16 — under a LatentStepLimit of 10 steps and TrialEpisodeLimit::default (meta.rs:557-564); reward stddev mdps.rs:163
+// DirichletRandomMdps::default (mdps.rs:111-122) but for the sizes — 10 x 5 has 19 observation features, this constructor
+// ends at 16 (rl_env_create_meta_mdp_wide takes it) — under a LatentStepLimit of 10 steps and TrialEpisodeLimit::default (meta.rs:557-564); reward stddev mdps.rs:163
 int32_t rl_meta_mdp_config_default(rl_meta_mdp_config *meta) {
   return guarded(nullptr, [&] {
     RL_REQUIRE(meta, "config is NULL");
@@ -173,7 +174,18 @@ int32_t rl_env_create_meta_mdp(rl_engine *e, const rl_env_config *cfg, const rl_
   });
 }
 
-// the current trial's tables as the lanes read them: the padding of the rows' eight floats is dropped
+// The same lanes at n_states 2..10 with S + A + 4 <= 20 features (DirichletRandomMdps::default is 10 x 5: 19).  Wherever
+// rl_env_create_meta_mdp builds, this is that handle; at nine and ten states the rows of running sums have sixteen floats
+// and the lanes run MetaMdpWideOps (env_lanes.hpp).
+int32_t rl_env_create_meta_mdp_wide(rl_engine *e, const rl_env_config *cfg, const rl_meta_mdp_config *meta, rl_env **out) {
+  return guarded(e, [&] {
+    RL_REQUIRE(e && cfg && meta && out, "rl_env_create_meta_mdp_wide: NULL argument");
+    *out = nullptr;
+    env_build(e, env_spec_meta_mdp_wide(*cfg, *meta), out);
+  });
+}
+
+// the current trial's tables as the lanes read them: the padding of the rows' eight (or sixteen) floats is dropped
 int32_t rl_env_meta_mdp_read_tables(rl_env *env, uint64_t first_lane, uint64_t n, float *cum_out, double *mean_out) {
   return guarded(env ? env->eng : nullptr, [&] {
     RL_REQUIRE(env, "env is NULL");
@@ -184,10 +196,11 @@ int32_t rl_env_meta_mdp_read_tables(rl_env *env, uint64_t first_lane, uint64_t n
     const size_t S = env->dev.mm.states, rows = S * env->dev.mm.actions;
     if (mean_out) d2h(env->eng, mean_out, env->dev.mm.mean + first_lane * rows, n * rows * sizeof(double));
     if (cum_out) {
-      std::vector<float> padded(n * rows * 8);
-      d2h(env->eng, padded.data(), env->dev.mm.cum + first_lane * rows * 8, padded.size() * sizeof(float));
+      const size_t W = meta_mdp_row_floats(env->dev.mm.states);
+      std::vector<float> padded(n * rows * W);
+      d2h(env->eng, padded.data(), env->dev.mm.cum + first_lane * rows * W, padded.size() * sizeof(float));
       for (size_t r = 0; r < n * rows; ++r)
-        for (size_t j = 0; j < S; ++j) cum_out[r * S + j] = padded[r * 8 + j];
+        for (size_t j = 0; j < S; ++j) cum_out[r * S + j] = padded[r * W + j];
     }
   });
 }

@@ -145,6 +145,17 @@ int32_t rl_rnn_chain_create_wide(rl_engine *e, const rl_rnn_chain_config *cfg, r
   });
 }
 
+// The same chain at in_dim 1..20 (the RL2 MDP experiment's model on 10 x 5 lanes: 19 inputs, five outputs for the policy,
+// one for the critic).  At in_dim <= 16: rl_rnn_chain_create_wide, the same handle.  The lane-per-thread kernels take the
+// input width at run time (StackNet::D): no kernel is built for these modules that the narrower ones do not run.
+int32_t rl_rnn_chain_create_wide20(rl_engine *e, const rl_rnn_chain_config *cfg, rl_mlp **out) {
+  return guarded(e, [&] {
+    RL_REQUIRE(e && cfg && out, "NULL argument");
+    *out = nullptr;
+    chain_create(e, *cfg, chain_limits_wide20(*cfg), out);
+  });
+}
+
 int32_t rl_mlp_destroy(rl_mlp *m) { return destroy_child(m); }
 
 int32_t rl_mlp_num_params(const rl_mlp *m, uint64_t *n) {

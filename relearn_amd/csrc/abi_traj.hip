@@ -53,11 +53,15 @@ void traj_plan(rl_traj *t, uint64_t B) {
 
 // `resizable`: the sample count changes between launches (DQN minibatches): slabs are sized for the largest grid
 // any B <= n_lanes * horizon can plan
-rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, bool resizable) {
+rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, bool resizable, bool wide) {
   RL_REQUIRE(n_lanes > 0 && n_lanes < (1ull << 31), "bad n_lanes");
   RL_REQUIRE(horizon > 0 && horizon < (1ull << 20), "bad horizon");
   // (up to 16 planes: the wide meta-bandit lanes; what reads a trajectory checks its own width against the planes')
-  RL_REQUIRE(obs_dim >= 1 && obs_dim <= RL_WIDE_MAX_OBS_DIM, "obs_dim must be in 1..16");
+  // `wide` (rl_traj_create_wide): up to 20, the meta-MDP lanes of rl_env_create_meta_mdp_wide
+  if (wide && obs_dim > RL_WIDE_MAX_OBS_DIM)
+    RL_REQUIRE(obs_dim <= RL_XWIDE_MAX_OBS_DIM, "rl_traj_create_wide: obs_dim must be in 1..20");
+  else
+    RL_REQUIRE(obs_dim >= 1 && obs_dim <= RL_WIDE_MAX_OBS_DIM, "obs_dim must be in 1..16");
   RL_REQUIRE(n_lanes * horizon < (1ull << 32), "T * n must fit 32 bits");
   RL_HIP_CHECK(hipSetDevice(e->device));
   std::unique_ptr<rl_traj> t(new rl_traj());
@@ -128,6 +132,15 @@ int32_t rl_traj_create(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_
     RL_REQUIRE(e && out, "NULL argument");
     *out = nullptr;
     *out = traj_alloc(e, n_lanes, horizon, obs_dim, false);
+  });
+}
+
+// The same trajectory with up to 20 observation planes; up to 16 it is rl_traj_create's, refusals and words included
+int32_t rl_traj_create_wide(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, rl_traj **out) {
+  return guarded(e, [&] {
+    RL_REQUIRE(e && out, "NULL argument");
+    *out = nullptr;
+    *out = traj_alloc(e, n_lanes, horizon, obs_dim, false, true);
   });
 }
 

@@ -481,11 +481,12 @@ struct MetaOps {
 // (MetaMdpOps).
 // s' = #{ j < bound - 1 : cum[j] <= u }: a compare-add per entry under the launch-uniform bound, no register indexing; the
 // count cannot leave 0 .. bound - 1, and u == cum[j] goes to the bucket after j.  `cum_at(j)` is entry j of the row.
-template <class CumAt>
+// ROW: the most entries a row has — 8, and 16 on the meta-MDP lanes of nine and ten states (MetaMdpWideOps).
+template <uint32_t ROW = 8, class CumAt>
 __device__ __forceinline__ uint32_t mdp_successor_count(CumAt cum_at, uint32_t bound, float u) {
   uint32_t next = 0;
 #pragma unroll
-  for (uint32_t j = 0; j < 7; ++j)
+  for (uint32_t j = 0; j < ROW - 1; ++j)
     if (j + 1 < bound) next += cum_at(j) <= u ? 1u : 0u;
   return next;
 }
@@ -596,36 +597,43 @@ __device__ __forceinline__ double lane_gamma_sample(double alpha, const uint32_t
 }
 
 // DirichletRandomMdps::sample_environment (mdps.rs:151-170) into the lane's tables, in rl_random_mdps_sample's order; moves
-// `pos` behind the last word read: S A (S + 1) variates, once per trial.  The row's S gammas stay in registers: every draw is selected into its place
-// (v_cndmask per entry), the loops over a row's entries are unrolled under the launch-uniform S.
+// `pos` behind the last word read: S A (S + 1) variates, once per trial.  The row's S gammas stay in registers: every draw
+// is selected into its place (v_cndmask per entry), the loops over a row's entries are unrolled under the launch-uniform S.
+// ROW: the floats of a stored row, the constant bound of every loop over a row's entries — 8 (one 32-byte sector, S <= 8)
+// or 16 (64 bytes, S = 9..10); a row is ROW / 4 aligned 16-byte stores.
+template <uint32_t ROW>
 __device__ __forceinline__ void meta_mdp_sample_tables(const CartPoleDev &c, uint64_t glane, uint64_t &pos) {
   const uint32_t S = c.mm.states, rows = S * c.mm.actions;
   const size_t local = (size_t)(glane - c.lane_offset);
-  float *cum = c.mm.cum + local * rows * 8;
+  float *cum = c.mm.cum + local * rows * ROW;
   double *mean = c.mm.mean + local * rows;
   const double alpha = c.mm_prior.alpha;
   for (uint32_t row = 0; row < rows; ++row) {
-    double g[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double g[ROW] = {};
     double sum = 0.0;
     for (uint32_t j = 0; j < S; ++j) {
       const double gj = lane_gamma_sample(alpha, c.key_env, glane, pos);
       sum = sum + gj;
 #pragma unroll
-      for (uint32_t k = 0; k < 8; ++k) g[k] = k == j ? gj : g[k];
+      for (uint32_t k = 0; k < ROW; ++k) g[k] = k == j ? gj : g[k];
     }
-    float p[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    float cs[8] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};  // behind S: the padding no draw reaches
-    rl_dirichlet_row_normalise(g, sum, S, 8, p);
-    rl_mdp_row_cumulative(p, S, 8, cs);
-    float4 *out = reinterpret_cast<float4 *>(cum + (size_t)row * 8);  // (hipMalloc'd and 32-byte rows: aligned)
-    out[0] = make_float4(cs[0], cs[1], cs[2], cs[3]);
-    out[1] = make_float4(cs[4], cs[5], cs[6], cs[7]);
+    float p[ROW] = {};
+    float cs[ROW];  // behind S: the padding no draw reaches
+#pragma unroll
+    for (uint32_t k = 0; k < ROW; ++k) cs[k] = 1.0f;
+    rl_dirichlet_row_normalise(g, sum, S, ROW, p);
+    rl_mdp_row_cumulative(p, S, ROW, cs);
+    float4 *out = reinterpret_cast<float4 *>(cum + (size_t)row * ROW);  // (hipMalloc'd and 32- or 64-byte rows: aligned)
+#pragma unroll
+    for (uint32_t q = 0; q < ROW / 4; ++q) out[q] = make_float4(cs[4 * q], cs[4 * q + 1], cs[4 * q + 2], cs[4 * q + 3]);
     // Normal::new(reward_prior_mean, reward_prior_stddev).sample: always drawn, as the host sampler does
     mean[row] = lane_normal_affine(c.key_env, glane, pos, c.mm_prior.reward_prior_mean, c.mm_prior.reward_prior_stddev);
   }
 }
 
-struct MetaMdpOps {
+// The lanes' ops at a row class: ROW = 8 is MetaMdpOps (S <= 8), ROW = 16 MetaMdpWideOps (S = 9..10), both below.
+template <uint32_t ROW>
+struct MetaMdpRowOps {
   using State = MetaMdpLane;
   // columns: x the inner state, thdot the inner steps remaining, xdot env_pos, th the prev reward; the byte as on MetaOps
   static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) {
@@ -689,11 +697,18 @@ struct MetaMdpOps {
     const size_t row = (size_t)(glane - c.lane_offset) * (S * A) + st * A + ac;
     const float u = rl_u32_to_unit_f32((uint32_t)lane_u64_at(c.key_env, glane, s.env_pos));
     s.env_pos += 2;
-    // the row is one 32-byte sector, padded with 1.0f: two 16-byte loads and no bound that depends on S
-    const float4 *rowp = reinterpret_cast<const float4 *>(c.mm.cum + row * 8);
-    const float4 lo = rowp[0], hi = rowp[1];
-    const float cs[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const uint32_t next = mdp_successor_count([&](uint32_t j) { return cs[j]; }, 8u, u);
+    // the row is one 32-byte sector (ROW 16: two), padded with 1.0f: ROW / 4 16-byte loads and no bound that depends on S
+    const float4 *rowp = reinterpret_cast<const float4 *>(c.mm.cum + row * ROW);
+    float cs[ROW];
+#pragma unroll
+    for (uint32_t q = 0; q < ROW / 4; ++q) {
+      const float4 v = rowp[q];
+      cs[4 * q] = v.x;
+      cs[4 * q + 1] = v.y;
+      cs[4 * q + 2] = v.z;
+      cs[4 * q + 3] = v.w;
+    }
+    const uint32_t next = mdp_successor_count<ROW>([&](uint32_t j) { return cs[j]; }, ROW, u);
     const double mean = c.mm.mean[row], stddev = c.mm_prior.reward_stddev;
     double rd = mean;  // a stddev of 0 draws nothing
     if (stddev != 0.0) rd = lane_normal_affine(c.key_env, glane, s.env_pos, mean, stddev);
@@ -714,7 +729,7 @@ struct MetaMdpOps {
   // TrialEpisodeLimit / MetaEnv::initial_state (meta.rs:580-589, 141-150): sample_environment, then the inner
   // initial_state (state 0, no draw)
   static __device__ __forceinline__ void reset(const CartPoleDev &c, State &s, uint64_t glane) {
-    meta_mdp_sample_tables(c, glane, s.env_pos);
+    meta_mdp_sample_tables<ROW>(c, glane, s.env_pos);
     s.state = 0;
     s.inner_left = c.mm.inner_steps;
     s.inner_done = 0;
@@ -725,6 +740,11 @@ struct MetaMdpOps {
     s.reset_count += 1;
   }
 };
+// S <= 8 (rl_env_create_meta_mdp): rows of eight floats.  A struct of its own name, so that its kernels keep theirs.
+struct MetaMdpOps : MetaMdpRowOps<8> {};
+// S = 9..10 (rl_env_create_meta_mdp_wide): rows of sixteen floats, 64 bytes in four 16-byte loads; the successor is the
+// count of cum[j] <= u over j < 15
+struct MetaMdpWideOps : MetaMdpRowOps<16> {};
 
 // ---------------------------------------------------------------- one step of a lane, recorded
 // Environment::step, the step's record, the successor observation of a cut episode, the auto-reset: the rule every

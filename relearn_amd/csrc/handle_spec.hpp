@@ -38,7 +38,11 @@ constexpr uint32_t RL_ENV_MIN_OBS_DIM = 4;   // narrowest observation the env ke
 // constants above keep guarding what they guard: feed-forward modules, MemoryGame, DQN, the older constructors.
 constexpr uint32_t RL_WIDE_MAX_OBS_DIM = 16;
 constexpr uint32_t RL_WIDE_MAX_OUT = 12;
-constexpr uint32_t RL_RNN_MAX_LAYERS = 4;   // RnnBaseConfig::num_layers of a recurrent chain
+// the widest entry points (rl_env_create_meta_mdp_wide, rl_rnn_chain_create_wide20, rl_traj_create_wide): meta-MDP lanes
+// of up to 10 states (S + A + 4 <= 20 features: DirichletRandomMdps::default's 10 x 5 has 19) and recurrent chains of up
+// to 20 inputs.  RL_WIDE_MAX_OBS_DIM keeps guarding the entry points it guards.
+constexpr uint32_t RL_XWIDE_MAX_OBS_DIM = 20;
+constexpr uint32_t RL_RNN_MAX_LAYERS = 4;  // RnnBaseConfig::num_layers of a recurrent chain
 
 // ---------------------------------------------------------------- env lanes: the struct every env kernel takes by value
 // RL_ENV_TABULAR_MDP (MdpOps, env_lanes.hpp): the tables of the one MDP all lanes share, in one device allocation of the
@@ -52,8 +56,9 @@ struct MdpTablesDev {
 };
 
 // RL_ENV_META_MDP (MetaMdpOps, env_lanes.hpp): every lane's own tables of the current trial, in one device allocation of
-// the env handle — cum f32 [n][S*A][8] (a row's running sums padded to eight floats with 1.0f: one 32-byte sector), mean f64
-// [n][S*A], both indexed by the LOCAL lane — with the sizes and the inner step limit (launch-uniform).  The lanes write the
+// the env handle — cum f32 [n][S*A][8] (a row's running sums padded to eight floats with 1.0f: one 32-byte sector; above
+// eight states [n][S*A][16], MetaMdpWideOps: meta_mdp_row_floats), mean f64 [n][S*A], both indexed by the LOCAL lane
+// — with the sizes and the inner step limit (launch-uniform).  The lanes write the
 // tables in their reset and read them in their steps: plain pointers, never const __restrict__.  32 bytes, over the
 // bandit's arm values like MdpTablesDev.
 struct MetaMdpDev {
@@ -342,30 +347,41 @@ inline EnvSpec env_spec_mdp(const rl_env_config &cfg_in, const rl_tabular_mdp_co
 
 // MetaEnv::new(DirichletRandomMdps{..}.wrap(LatentStepLimit::new(L))).wrap(TrialEpisodeLimit::new(E)) (meta.rs:128-203,
 // 541-617; mdps.rs:87-171; wrappers/step_limit.rs:13-89), whatever cfg.kind says.  Observations: MetaObservationSpace
-// with the inner state's one-hot, S + A + 4 features — the widest lanes have 16, so 10 x 5 (19) does not build.
+// with the inner state's one-hot, S + A + 4 features — at most 16 through rl_env_create_meta_mdp; 10 x 5 (19) builds
+// through rl_env_create_meta_mdp_wide.
 constexpr uint32_t RL_META_MDP_MAX = 8;  // states, and actions
-inline EnvSpec env_spec_meta_mdp(const rl_env_config &cfg_in, const rl_meta_mdp_config &meta) {
+// rl_env_create_meta_mdp_wide: up to 10 states (the second row class of MetaMdpWideOps, env_lanes.hpp) and 20 features
+constexpr uint32_t RL_META_MDP_WIDE_MAX_STATES = 10;
+// floats of a lane's row of running sums, padded with 1.0f: one 32-byte sector up to eight states, 64 bytes beyond
+inline uint32_t meta_mdp_row_floats(uint32_t S) { return S <= RL_META_MDP_MAX ? 8u : 16u; }
+// `wide`: rl_env_create_meta_mdp_wide's ranges and name; inside the older ranges the two build the same spec
+inline EnvSpec env_spec_meta_mdp_ranged(const rl_env_config &cfg_in, const rl_meta_mdp_config &meta, bool wide) {
   const rl_env_config cfg = env_config_of_kind(cfg_in, RL_ENV_META_MDP);
   const uint64_t S = meta.n_states, A = meta.n_actions;
-  if (S < 2 || S > RL_META_MDP_MAX || A < 2 || A > RL_META_MDP_MAX || S + A + 4 > RL_WIDE_MAX_OBS_DIM)
+  const std::string fn = wide ? "rl_env_create_meta_mdp_wide" : "rl_env_create_meta_mdp";
+  if (wide) {
+    if (S < 2 || S > RL_META_MDP_WIDE_MAX_STATES || A < 2 || A > RL_META_MDP_MAX || S + A + 4 > RL_XWIDE_MAX_OBS_DIM)
+      throw RlError(RL_ERR_BUILD_ENV, fn + ": n_states 2..10 and n_actions 2..8 with n_states + n_actions + 4 observation "
+                                           "features, at most 20");
+  } else if (S < 2 || S > RL_META_MDP_MAX || A < 2 || A > RL_META_MDP_MAX || S + A + 4 > RL_WIDE_MAX_OBS_DIM)
     throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: n_states 2..8 and n_actions 2..8 with n_states + n_actions "
                                     "+ 4 observation features, at most 16");
   if (meta.max_inner_steps == 0 || meta.max_inner_steps >= (1ull << 32))  // StepLimit::new asserts > 0
-    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: max_inner_steps must be positive and < 2^32");
+    throw RlError(RL_ERR_BUILD_ENV, fn + ": max_inner_steps must be positive and < 2^32");
   if (meta.episodes_per_trial == 0 || meta.episodes_per_trial >= (1ull << 32))  // TrialEpisodeLimit::new (meta.rs:548-553)
-    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: episodes_per_trial must be positive and < 2^32");
+    throw RlError(RL_ERR_BUILD_ENV, fn + ": episodes_per_trial must be positive and < 2^32");
   if (!std::isfinite(meta.alpha) || !(meta.alpha > 0.0))
-    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: alpha must be positive and finite");
+    throw RlError(RL_ERR_BUILD_ENV, fn + ": alpha must be positive and finite");
   if (!std::isfinite(meta.reward_prior_mean))
-    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: reward_prior_mean is not finite");
+    throw RlError(RL_ERR_BUILD_ENV, fn + ": reward_prior_mean is not finite");
   if (!std::isfinite(meta.reward_prior_stddev) || meta.reward_prior_stddev < 0.0)
-    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: reward_prior_stddev is negative or not finite");
+    throw RlError(RL_ERR_BUILD_ENV, fn + ": reward_prior_stddev is negative or not finite");
   if (!std::isfinite(meta.reward_stddev) || meta.reward_stddev < 0.0)
-    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: reward_stddev is negative or not finite");
+    throw RlError(RL_ERR_BUILD_ENV, fn + ": reward_stddev is negative or not finite");
   if (!std::isfinite(meta.discount_factor))
-    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: discount_factor is not finite");
+    throw RlError(RL_ERR_BUILD_ENV, fn + ": discount_factor is not finite");
   if (cfg.limit_kind != RL_LIMIT_NONE)
-    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_meta_mdp: the lanes take no step limit (the inner limit and the trial's "
+    throw RlError(RL_ERR_BUILD_ENV, fn + ": the lanes take no step limit (the inner limit and the trial's "
                                     "episode limit are this env's limits)");
   env_check_limit_and_lanes(cfg);
   EnvSpec s = env_spec_begin(cfg, (uint32_t)(S + A + 4), (uint32_t)A);
@@ -384,6 +400,13 @@ inline EnvSpec env_spec_meta_mdp(const rl_env_config &cfg_in, const rl_meta_mdp_
   s.meta_mdp_rows = (uint32_t)(S * A);
   return s;
 }
+inline EnvSpec env_spec_meta_mdp(const rl_env_config &cfg, const rl_meta_mdp_config &meta) {
+  return env_spec_meta_mdp_ranged(cfg, meta, false);
+}
+// rl_env_create_meta_mdp_wide: n_states 2..10, n_actions 2..8, at most 20 features; sizes first, as the older one checks
+inline EnvSpec env_spec_meta_mdp_wide(const rl_env_config &cfg, const rl_meta_mdp_config &meta) {
+  return env_spec_meta_mdp_ranged(cfg, meta, true);
+}
 
 // The (S, A) shapes of RL_ENV_META_MDP lanes whose recurrent rollout is one launch (k_stack_rollout<.., MetaMdpOps, ..>,
 // kernels_seq_stack.hip): the smallest, the odd widths, the default, the most features with the widest row, and the most
@@ -394,6 +417,14 @@ struct MetaMdpShape {
 constexpr MetaMdpShape META_MDP_FUSED_SHAPES[] = {{2, 2}, {3, 2}, {4, 3}, {5, 5}, {8, 4}, {4, 8}};
 inline bool meta_mdp_fused_shape(uint32_t S, uint32_t A) {
   for (const MetaMdpShape &m : META_MDP_FUSED_SHAPES)
+    if (m.S == S && m.A == A) return true;
+  return false;
+}
+// ... and of the lanes of rl_env_create_meta_mdp_wide above eight states (k_stack_rollout<.., MetaMdpWideOps, ..>): the
+// reference's default size alone
+constexpr MetaMdpShape META_MDP_WIDE_FUSED_SHAPES[] = {{10, 5}};
+inline bool meta_mdp_wide_fused_shape(uint32_t S, uint32_t A) {
+  for (const MetaMdpShape &m : META_MDP_WIDE_FUSED_SHAPES)
     if (m.S == S && m.A == A) return true;
   return false;
 }
@@ -541,9 +572,16 @@ constexpr ChainLimits CHAIN_NARROW{
 constexpr ChainLimits CHAIN_WIDE{
     RL_WIDE_MAX_OBS_DIM, RL_WIDE_MAX_OUT, 0,
     "rl_rnn_chain_create_wide: in_dim 1..16, recurrent hidden 1..256, mlp_hidden 0..256, out_dim 1..12"};
+constexpr ChainLimits CHAIN_WIDE20{
+    RL_XWIDE_MAX_OBS_DIM, RL_WIDE_MAX_OUT, 0,
+    "rl_rnn_chain_create_wide20: in_dim 1..20, recurrent hidden 1..256, mlp_hidden 0..256, out_dim 1..12"};
 // rl_rnn_chain_create_wide: within in_dim <= 8 and out_dim <= 8 it is rl_rnn_chain_create, bound and words
 inline const ChainLimits &chain_limits_wide(const rl_rnn_chain_config &cfg) {
   return cfg.in_dim <= RL_TRAJ_MAX_OBS_DIM && cfg.out_dim <= RL_MLP_MAX_OUT ? CHAIN_NARROW : CHAIN_WIDE;
+}
+// rl_rnn_chain_create_wide20: at in_dim <= 16 it is rl_rnn_chain_create_wide, bound and words
+inline const ChainLimits &chain_limits_wide20(const rl_rnn_chain_config &cfg) {
+  return cfg.in_dim <= RL_WIDE_MAX_OBS_DIM ? chain_limits_wide(cfg) : CHAIN_WIDE20;
 }
 
 // the module kind of a config's cell; its first two refusals (tested before a NULL handle is, by every constructor that

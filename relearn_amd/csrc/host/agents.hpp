@@ -146,10 +146,14 @@ class EnvLanes {
                                     stddev.empty() ? nullptr : stddev.data(), &h_), eng.handle());
     check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
   }
-  // meta-MDP lanes (rl_env_create_meta_mdp)
+  // meta-MDP lanes (rl_env_create_meta_mdp; rl_env_create_meta_mdp_wide where that one's range ends)
   EnvLanes(Engine &eng, const rl_env_config &cfg, const rl_meta_mdp_config &meta)
       : eng_(eng), cfg_(cfg), discount_(meta.discount_factor) {
-    check(rl_env_create_meta_mdp(eng.handle(), &cfg_, &meta, &h_), eng.handle());
+    // (above eight states or sixteen features — DirichletRandomMdps::default is 10 x 5 — the wide constructor)
+    const bool wide = meta.n_states > 8 || meta.n_states + meta.n_actions + 4 > 16;
+    check(wide ? rl_env_create_meta_mdp_wide(eng.handle(), &cfg_, &meta, &h_)
+               : rl_env_create_meta_mdp(eng.handle(), &cfg_, &meta, &h_),
+          eng.handle());
     check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
   }
   Engine &eng_;
@@ -317,9 +321,9 @@ class TabularMdpLanes : public EnvLanes {
 
 // `MetaEnv::new(DirichletRandomMdps{..}.wrap(LatentStepLimit::new(L))).wrap(TrialEpisodeLimit::new(E))` x n_lanes
 // (src/envs/meta.rs:128-203, 541-617 over mdps.rs:87-171): the second task of the RL^2 paper.  Every lane draws its own MDP
-// at each trial's start; S + A + 4 observation features, at most 16; a trial is E (L + 1) - 1 steps and ends in an
+// at each trial's start; S + A + 4 observation features, at most 20 (S up to 10); a trial is E (L + 1) - 1 steps and ends in an
 // Interrupt.  `dist`: the scalar mirror's distribution (host/envs.hpp), whose sample_environment(seed_env, g) is lane g's
-// first trial.  Policies: the recurrent chains of rl_rnn_chain_create_wide.
+// first trial.  Policies: the recurrent chains of rl_rnn_chain_create_wide, above 16 features rl_rnn_chain_create_wide20.
 class MetaMdpLanes : public EnvLanes {
  public:
   MetaMdpLanes(Engine &eng, uint64_t n_lanes, const DirichletRandomMdps &dist, uint64_t max_inner_steps = 10,
@@ -449,6 +453,8 @@ inline int32_t rnn_chain_create_multi(Engine &eng, int32_t cell, const RnnBaseCo
   cfg.mlp_hidden = mlp_hidden;
   cfg.out_dim = out_dim;
   // (more than eight inputs or outputs — the rl2-bandits experiment above four arms: the wide constructor)
+  // (more than sixteen inputs — the RL2 MDP experiment at 10 x 5, 19 features: rl_rnn_chain_create_wide20)
+  if (in_dim > 16) return rl_rnn_chain_create_wide20(eng.handle(), &cfg, h);
   return in_dim > 8 || out_dim > 8 ? rl_rnn_chain_create_wide(eng.handle(), &cfg, h)
                                    : rl_rnn_chain_create(eng.handle(), &cfg, h);
 }
@@ -662,7 +668,10 @@ struct AdamWConfig {  // optimizers/coptimizer.rs:170-205
 class DeviceHistory {
  public:
   DeviceHistory(Engine &eng, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim) : n_(n_lanes), T_(horizon) {
-    check(rl_traj_create(eng.handle(), n_lanes, horizon, obs_dim, &h_), eng.handle());
+    // (more than sixteen planes — the meta-MDP lanes of 10 x 5 — are rl_traj_create_wide's)
+    check(obs_dim > 16 ? rl_traj_create_wide(eng.handle(), n_lanes, horizon, obs_dim, &h_)
+                       : rl_traj_create(eng.handle(), n_lanes, horizon, obs_dim, &h_),
+          eng.handle());
   }
   ~DeviceHistory() { rl_traj_destroy(h_); }
   DeviceHistory(const DeviceHistory &) = delete;

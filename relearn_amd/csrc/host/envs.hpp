@@ -231,8 +231,8 @@ struct WithLatentStepLimit {
 // rl_env_create_meta_mdp state it (include/relearn_hip.h): a trial starts with sample_environment from the env generator
 // where it stands; an inner episode is max_inner_steps steps of TabularMdp::step and ends in the limit's Interrupt(state);
 // the step after it ignores its action, draws nothing and starts the next inner episode; the step that ends the trial's
-// last inner episode is an Interrupt.  The scalar env takes any size the sampler takes; the lanes end at 8 x 8 and 16
-// features.  One generator, seed_from_u64(seed_env) on stream g, gives lane g's trials.
+// last inner episode is an Interrupt.  The scalar env takes any size the sampler takes; the lanes end at 10 x 8 and 20
+// features (rl_env_create_meta_mdp_wide).  One generator, seed_from_u64(seed_env) on stream g, gives lane g's trials.
 struct MetaRandomMdps {
   using Action = uint64_t;
   using Observation = std::vector<float>;

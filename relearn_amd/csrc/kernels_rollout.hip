@@ -403,7 +403,7 @@ void launch_obs_range(rl_traj *traj) {
 // The standalone env kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature
 // count as types.  CartPole lanes have 4 or 5 features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame:
 // num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..16; tabular-MDP lanes states [+ 1] = 2..8;
-// meta-MDP lanes states + actions + 4 = 8..16.
+// meta-MDP lanes states + actions + 4 = 8..16, and 15..20 at nine and ten states (MetaMdpWideOps).
 template <int D>
 using FeatureCount = std::integral_constant<int, D>;
 template <class Go>
@@ -430,7 +430,20 @@ static void env_dispatch(const rl_env *env, Go &&go) {
     }
     return;
   }
-  if (env->kind == RL_ENV_META_MDP) {  // S + A + 4 features, S and A 2..8 with at most 16 in all
+  if (env->kind == RL_ENV_META_MDP && env->dev.mm.states > RL_META_MDP_MAX) {
+    // rl_env_create_meta_mdp_wide at 9 or 10 states: rows of sixteen floats; 9 x 2 has 15 features, 10 x 6 has 20
+    switch (env->D) {
+      case 15: go(MetaMdpWideOps{}, FeatureCount<15>{}); break;
+      case 16: go(MetaMdpWideOps{}, FeatureCount<16>{}); break;
+      case 17: go(MetaMdpWideOps{}, FeatureCount<17>{}); break;
+      case 18: go(MetaMdpWideOps{}, FeatureCount<18>{}); break;
+      case 19: go(MetaMdpWideOps{}, FeatureCount<19>{}); break;
+      case 20: go(MetaMdpWideOps{}, FeatureCount<20>{}); break;
+      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-MDP lanes of nine or ten states: 15..20 observation features");
+    }
+    return;
+  }
+  if (env->kind == RL_ENV_META_MDP) {  // S + A + 4 features, S and A 2..8: at most 16, through the wide constructor 20
     switch (env->D) {
       case 8: go(MetaMdpOps{}, FeatureCount<8>{}); break;
       case 9: go(MetaMdpOps{}, FeatureCount<9>{}); break;
@@ -441,7 +454,11 @@ static void env_dispatch(const rl_env *env, Go &&go) {
       case 14: go(MetaMdpOps{}, FeatureCount<14>{}); break;
       case 15: go(MetaMdpOps{}, FeatureCount<15>{}); break;
       case 16: go(MetaMdpOps{}, FeatureCount<16>{}); break;
-      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-MDP lanes: 8..16 observation features");
+      case 17: go(MetaMdpOps{}, FeatureCount<17>{}); break;  // 17..20: rl_env_create_meta_mdp_wide at up to 8 states
+      case 18: go(MetaMdpOps{}, FeatureCount<18>{}); break;
+      case 19: go(MetaMdpOps{}, FeatureCount<19>{}); break;
+      case 20: go(MetaMdpOps{}, FeatureCount<20>{}); break;
+      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-MDP lanes: 8..20 observation features");
     }
     return;
   }
@@ -480,6 +497,8 @@ void launch_env_reset(rl_env *env) {
     hipLaunchKernelGGL(k_env_reset<MetaOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else if (env->kind == RL_ENV_TABULAR_MDP)
     hipLaunchKernelGGL(k_env_reset<MdpOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  else if (env->kind == RL_ENV_META_MDP && env->dev.mm.states > RL_META_MDP_MAX)
+    hipLaunchKernelGGL(k_env_reset<MetaMdpWideOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else if (env->kind == RL_ENV_META_MDP)
     hipLaunchKernelGGL(k_env_reset<MetaMdpOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else if (env->kind != RL_ENV_CHAIN && env->kind != RL_ENV_MEMORY && env->kind != RL_ENV_BANDIT)

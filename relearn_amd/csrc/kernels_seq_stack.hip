@@ -1082,6 +1082,27 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     env->t_global += traj->d.T;
     return;
   }
+  if (env->kind == RL_ENV_META_MDP && env->eng->kernel_variant != 1 && env->dev.mm.states > RL_META_MDP_MAX &&
+      meta_mdp_wide_fused_shape(env->dev.mm.states, env->dev.mm.actions)) {
+    // the lanes of rl_env_create_meta_mdp_wide at META_MDP_WIDE_FUSED_SHAPES (10 x 5, the reference's default): rows of
+    // sixteen floats (MetaMdpWideOps), 19 features, five actions; 550 variates per lane in the trial's serial section
+    RL_REQUIRE(env->dev.mm.states == 10 && env->A == 5 && env->D == 19,
+               "fused recurrent rollout on wide meta-MDP lanes: built for 10 x 5");
+#define ROLL(CELL, LIN)                                                                                               \
+  hipLaunchKernelGGL((k_stack_rollout<CELL, MetaMdpWideOps, 19, LIN, 5>), grid, blk, 0, env->eng->stream, net, ws, \
+                     env->dev, env->st, traj->d, env->t_global)
+    if (lstm) {
+      if (lin) ROLL(LSTM, true);
+      else ROLL(LSTM, false);
+    } else {
+      if (lin) ROLL(GRU, true);
+      else ROLL(GRU, false);
+    }
+#undef ROLL
+    RL_HIP_CHECK(hipGetLastError());
+    env->t_global += traj->d.T;
+    return;
+  }
   launch_rollout_stepwise(env, traj, z, [&](uint32_t step) {
     const int first = step == 0 ? 1 : 0, parity = (int)(step & 1);
     // (the step before has been recorded by now: its successor codes are in the trajectory)

@@ -1,6 +1,7 @@
 """The second task of the RL^2 paper, random tabular MDPs, on the meta-MDP lanes:
 `MetaEnv::new(DirichletRandomMdps{..}.wrap(LatentStepLimit::new(inner))).wrap(TrialEpisodeLimit::new(episodes))`
-(ra.MetaMdpEnv: every lane draws its own MDP at each trial's start), a GRU chain as policy and one as critic — GRU(hidden)
+(ra.MetaMdpEnvWide: every lane draws its own MDP at each trial's start; up to 10 states, `--states 10 --actions 5` is the
+reference's default size), a GRU chain as policy and one as critic — GRU(hidden)
 -> Relu -> Linear (`linear`, the experiment's model) or with an MLP tail of one hidden layer (`mlp`) — TRPO at max KL
 0.01, the critic fitted with Adam steps per period, GAE with lambda 0.3, discount factor 0.99.  Every lane collects whole
 trials per period (horizon = trials_per_lane * (episodes * (inner + 1) - 1)).
@@ -60,13 +61,15 @@ def main():
     a = ap.parse_args()
 
     eng = ra.Engine(0)
-    env = ra.MetaMdpEnv(eng, a.lanes, a.states, a.actions, max_inner_steps=a.inner, episodes_per_trial=a.episodes,
-                        alpha=a.alpha, reward_prior_mean=a.prior_mean, reward_prior_stddev=a.prior_stddev,
-                        reward_stddev=a.reward_stddev, seed_env=a.seed, seed_actor=a.seed + 1)
+    # (MetaMdpEnvWide: up to 10 states and 20 features — `--states 10 --actions 5` is DirichletRandomMdps::default — and
+    # MetaMdpEnv's own handle inside that one's range; likewise the chains and the trajectory)
+    env = ra.MetaMdpEnvWide(eng, a.lanes, a.states, a.actions, max_inner_steps=a.inner, episodes_per_trial=a.episodes,
+                            alpha=a.alpha, reward_prior_mean=a.prior_mean, reward_prior_stddev=a.prior_stddev,
+                            reward_stddev=a.reward_stddev, seed_env=a.seed, seed_actor=a.seed + 1)
     T = a.trials_per_lane * env.trial_steps
     tail = a.hidden if a.model == "mlp" else None
-    pol = ra.RnnChainWide(eng, "gru", env.D, a.hidden, env.A, mlp_hidden=tail)
-    cri = ra.RnnChainWide(eng, "gru", env.D, a.hidden, 1, mlp_hidden=tail)
+    pol = ra.RnnChainWide20(eng, "gru", env.D, a.hidden, env.A, mlp_hidden=tail)
+    cri = ra.RnnChainWide20(eng, "gru", env.D, a.hidden, 1, mlp_hidden=tail)
     pol.init(a.seed + 2)  # input weights Uniform(FanAvg), hidden weights Orthogonal, biases Zeros; LinearConfig::default
     cri.init(a.seed + 3)
     opt = ra.Adam(cri)
@@ -75,7 +78,7 @@ def main():
     ccfg = ra.values_opt_config_default()
     ccfg.opt_steps_per_update = a.critic_steps
     ccfg.discount_factor = 0.99
-    traj = ra.Trajectory(eng, a.lanes, T, env.D)
+    traj = ra.TrajectoryWide(eng, a.lanes, T, env.D)
     summary = ra.StepsSummary(eng, a.lanes)
     lines = []
     for period in range(a.periods):
