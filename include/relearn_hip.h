@@ -72,7 +72,8 @@ enum { RL_OPT_OK = 0, RL_OPT_LOSS_NOT_IMPROVING = 1, RL_OPT_CONSTRAINT_VIOLATED 
 enum { RL_ENV_CARTPOLE = 0, RL_ENV_CHAIN = 1, RL_ENV_MEMORY = 2, RL_ENV_BANDIT = 3,
        RL_ENV_META_BANDIT = 4 /* rl_env_create_meta_bandit only (src/envs/meta.rs) */,
        RL_ENV_TABULAR_MDP = 5 /* rl_env_create_tabular_mdp only (src/envs/mdps.rs) */,
-       RL_ENV_META_MDP = 6 /* rl_env_create_meta_mdp only (src/envs/meta.rs over src/envs/mdps.rs) */ };
+       RL_ENV_META_MDP = 6 /* rl_env_create_meta_mdp only (src/envs/meta.rs over src/envs/mdps.rs) */,
+       RL_ENV_PARTITION = 7 /* rl_env_create_partition only (src/envs/partition.rs) */ };
 /* bandit distributions of a meta-bandit env (src/envs/bandits.rs:128-243, src/envs/testing.rs:108-160) */
 enum { RL_BANDITS_UNIFORM_BERNOULLI = 0, RL_BANDITS_ONE_HOT = 1, RL_BANDITS_ROUND_ROBIN = 2 };
 enum { RL_LIMIT_NONE = 0, RL_LIMIT_LATENT = 1, RL_LIMIT_VISIBLE = 2 };
@@ -381,6 +382,24 @@ int32_t rl_env_create_meta_mdp(rl_engine *engine, const rl_env_config *cfg, cons
  * rl_env_get_state / rl_env_set_state, rl_actor_to_cbor and rl_bandit_agent_* refuse every meta-MDP lane by name. */
 int32_t rl_env_create_meta_mdp_wide(rl_engine *engine, const rl_env_config *cfg, const rl_meta_mdp_config *meta,
                                     rl_env **out);
+/* PartitionGame lanes (src/envs/partition.rs:86-130) under the index lanes' step limit: `cfg` supplies the lanes, the lane
+ * offset, the seeds and the limit (RL_LIMIT_NONE, RL_LIMIT_LATENT or RL_LIMIT_VISIBLE with max_steps; the experiment's
+ * partition-game.rs wraps VisibleStepLimit::new(1000)); its kind is not read.  The handle's kind is RL_ENV_PARTITION;
+ * rl_env_dims returns (23, 2), (24, 2) under a visible limit; PartitionGame::discount_factor is 0.999.
+ * A lane: a supervisor axis 0..9, an element of ten booleans, the feedback Option<(previous element, its label)>.
+ * Reset: gen_range(0..10) over usize picks the axis, then ten gen::<bool>() in index order the element; feedback None.
+ * Step: label = element[axis] (Right when set); reward +1.0f when the action index (ClassifyLeft 0, ClassifyRight 1)
+ * equals the label index, else -1.0f; feedback = Some((element, label)); ten gen::<bool>() draw the next element.  The env
+ * never terminates itself; the step-limit tail is the index lanes'.  Every draw is taken sequentially from the lane's env
+ * stream (ChaCha8 of seed_env, stream = global lane); gen::<bool>() is one next_u32 whose sign bit is the value.
+ * Features: [element, 10] [feedback is None] [previous element, 10] [one-hot label: Left, Right] [+ remaining]; the 12
+ * entries behind a None marker are zero.
+ * The lanes serve rl_env_reset / _observe / _step, rl_rollout under a recurrent chain of rl_rnn_chain_create_wide24 into
+ * a trajectory of rl_traj_create_wide24 (one launch at 24 features unless the kernel variant is 1; a launch sequence per
+ * step otherwise), every update on what was collected, and rl_summary_push.  RL_ERR_UNSUPPORTED by name: feed-forward
+ * modules in rl_rollout (they have at most eight inputs), rl_dqn_create*, rl_env_get_state / rl_env_set_state,
+ * rl_actor_to_cbor, rl_bandit_agent_*. */
+int32_t rl_env_create_partition(rl_engine *engine, const rl_env_config *cfg, rl_env **out);
 /* The current trial's tables of lanes first_lane .. first_lane + n - 1 (local lanes) as the lanes read them; read-only.
  * cum_out [n][S*A][S] f32 running sums, mean_out [n][S*A] f64; either may be NULL. */
 int32_t rl_env_meta_mdp_read_tables(rl_env *env, uint64_t first_lane, uint64_t n, float *cum_out, double *mean_out);
@@ -609,6 +628,11 @@ int32_t rl_rnn_chain_create_wide(rl_engine *engine, const rl_rnn_chain_config *c
  * in_dim <= 16: rl_rnn_chain_create_wide, the same handle and the same refusals.  in_dim 0 or 21, out_dim 0 or 13 ->
  * RL_ERR_BUILD_AGENT; everything else as rl_rnn_chain_create.  Serves trajectories of rl_traj_create_wide. */
 int32_t rl_rnn_chain_create_wide20(rl_engine *engine, const rl_rnn_chain_config *cfg, rl_mlp **out);
+/* The same chain at in_dim 1..24: the model of the partition-game experiment (24 inputs under the visible limit; two
+ * outputs for the policy, one for the critic).  in_dim <= 20: rl_rnn_chain_create_wide20, the same handle and the same
+ * refusals.  in_dim 0 or 25, out_dim 0 or 13 -> RL_ERR_BUILD_AGENT; everything else as rl_rnn_chain_create.  Serves
+ * trajectories of rl_traj_create_wide24. */
+int32_t rl_rnn_chain_create_wide24(rl_engine *engine, const rl_rnn_chain_config *cfg, rl_mlp **out);
 
 /* ---------------------------------------------------------------------------------------------
  * Trajectory store (replaces VecBuffer + LazyHistoryFeatures: src/agents/buffers/vec.rs:15-143,
@@ -634,6 +658,8 @@ int32_t rl_traj_create(rl_engine *engine, uint64_t n_lanes, uint64_t horizon, ui
 /* The same store with up to 20 observation planes (the lanes of rl_env_create_meta_mdp_wide).  Up to the width
  * rl_traj_create takes it is rl_traj_create.  Whatever reads a trajectory checks its own width against the planes'. */
 int32_t rl_traj_create_wide(rl_engine *engine, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, rl_traj **out);
+/* ... with up to 24 observation planes (the lanes of rl_env_create_partition).  Up to 20 it is rl_traj_create_wide. */
+int32_t rl_traj_create_wide24(rl_engine *engine, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, rl_traj **out);
 int32_t rl_traj_destroy(rl_traj *traj);
 int32_t rl_traj_field_bytes(const rl_traj *traj, int32_t field, uint64_t *bytes);
 int32_t rl_traj_read(rl_traj *traj, int32_t field, void *host, uint64_t bytes);

@@ -27,6 +27,7 @@ SUCC_CONTINUE, SUCC_TERMINATE, SUCC_INTERRUPT = 0, 1, 2
 OPT_OK, OPT_LOSS_NOT_IMPROVING, OPT_CONSTRAINT_VIOLATED, OPT_NAN_LOSS, OPT_NAN_CONSTRAINT = range(5)
 ENV_CARTPOLE, ENV_CHAIN, ENV_MEMORY, ENV_BANDIT, ENV_META_BANDIT, ENV_TABULAR_MDP = 0, 1, 2, 3, 4, 5
 ENV_META_MDP = 6
+ENV_PARTITION = 7
 BANDITS_UNIFORM_BERNOULLI, BANDITS_ONE_HOT, BANDITS_ROUND_ROBIN = 0, 1, 2
 BANDIT_DISTRIBUTIONS = {"uniform_bernoulli": BANDITS_UNIFORM_BERNOULLI, "one_hot": BANDITS_ONE_HOT,
                         "round_robin": BANDITS_ROUND_ROBIN}
@@ -50,12 +51,12 @@ ABI_SYMBOLS = [
     "rl_last_error", "rl_engine_info", "rl_engine_set_kernel_variant", "rl_timer_begin", "rl_timer_end", "rl_profile_enable", "rl_profile_read",
     "rl_comm_available", "rl_comm_library_paths", "rl_comm_unique_id", "rl_comm_init", "rl_comm_destroy", "rl_comm_init_host",
     "rl_comm_ipc_handle", "rl_comm_init_ipc", "rl_comm_selftest",
-    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_create_tabular_mdp", "rl_random_mdps_config_default", "rl_random_mdps_sample", "rl_meta_mdp_config_default", "rl_env_create_meta_mdp", "rl_env_create_meta_mdp_wide", "rl_env_meta_mdp_read_tables", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
+    "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_create_tabular_mdp", "rl_random_mdps_config_default", "rl_random_mdps_sample", "rl_meta_mdp_config_default", "rl_env_create_meta_mdp", "rl_env_create_meta_mdp_wide", "rl_env_create_partition", "rl_env_meta_mdp_read_tables", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
-    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_chain_config_default", "rl_rnn_chain_create", "rl_rnn_chain_create_wide", "rl_rnn_chain_create_wide20", "rl_rnn_mlp_init_with", "rl_seq_forward",
-    "rl_traj_create", "rl_traj_create_wide", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write",
+    "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_chain_config_default", "rl_rnn_chain_create", "rl_rnn_chain_create_wide", "rl_rnn_chain_create_wide20", "rl_rnn_chain_create_wide24", "rl_rnn_mlp_init_with", "rl_seq_forward",
+    "rl_traj_create", "rl_traj_create_wide", "rl_traj_create_wide24", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write",
     "rl_rollout", "rl_gae",
     "rl_trpo_config_default", "rl_trpo_update", "rl_policy_gradient", "rl_policy_fvp", "rl_policy_loss_kl",
     "rl_adam_config_default", "rl_adam_create", "rl_adam_destroy", "rl_adam_step_host",
@@ -731,6 +732,41 @@ class MetaMdpEnvWide(MetaMdpEnv):
     CREATE = "rl_env_create_meta_mdp_wide"
 
 
+class PartitionEnv(ChainEnv):
+    """N PartitionGame lanes (src/envs/partition.rs) — `PartitionGame::default()`, optionally wrapped in a step limit
+    (the partition-game experiment wraps `VisibleStepLimit::new(1000)`, the default here).  A lane holds a supervisor
+    axis, drawn at reset, and an element of ten booleans, drawn afresh every step; the action classifies the element
+    Left (0) or Right (1) and earns +1 when that is element[axis], else -1; the next observation carries the element just
+    judged and its label.  Observations: 23 features [element, 10] [feedback is None] [previous element, 10] [one-hot
+    label, 2], 24 with `remaining` under a visible limit.  Two actions; the discount factor is 0.999.  Policies: the
+    recurrent chains of RnnChainWide24 into a TrajectoryWide24.  No get_state / set_state."""
+
+    DISCOUNT_FACTOR = 0.999
+
+    def __init__(self, engine, n_lanes, max_steps=1000, limit=LIMIT_VISIBLE, lane_offset=0, seed_env=0, seed_actor=1):
+        self.eng = engine
+        cfg = EnvConfig()
+        cfg.kind = ENV_PARTITION
+        cfg.limit_kind = limit
+        cfg.max_steps = max_steps
+        cfg.n_lanes = n_lanes
+        cfg.lane_offset = lane_offset
+        cfg.seed_env = seed_env
+        cfg.seed_actor = seed_actor
+        cfg.cartpole = cartpole_params_default()
+        self.cfg = cfg
+        self.h = C.c_void_p()
+        _check(lib().rl_env_create_partition(engine.h, C.byref(cfg), C.byref(self.h)), engine.h)
+        _register(self)
+        self.n = n_lanes
+        d, a = C.c_uint32(), C.c_uint32()
+        _check(lib().rl_env_dims(self.h, C.byref(d), C.byref(a)), engine.h)
+        self.D, self.A = d.value, a.value
+
+    get_state = CartPoleEnv.get_state  # (refused by name: RL_ERR_UNSUPPORTED)
+    set_state = CartPoleEnv.set_state
+
+
 class GruMlp(_Handle):
     """`GruMlpConfig::default().build_module(in, out)`: GRU(128) -> ReLU -> MLP([128]); flat reference order."""
 
@@ -861,6 +897,13 @@ class RnnChainWide20(RnnChain):
     RnnChainWide builds): policy and critic of the RL2 experiment on random MDPs of 10 states and 5 actions (19 inputs)."""
 
     CREATE = "rl_rnn_chain_create_wide20"
+
+
+class RnnChainWide24(RnnChain):
+    """The same chain at in_dim 1..24 (rl_rnn_chain_create_wide24; at in_dim <= 20 it builds what RnnChainWide20 builds):
+    policy and critic of the partition-game experiment (PartitionEnv under a visible limit: 24 inputs)."""
+
+    CREATE = "rl_rnn_chain_create_wide24"
 
 
 ACTIVATIONS = ["Identity", "Relu", "Sigmoid", "Tanh"]  # rl_activation, in the reference enum's order
@@ -1006,6 +1049,13 @@ class TrajectoryWide(Trajectory):
     the trajectories of MetaMdpEnvWide lanes."""
 
     CREATE = "rl_traj_create_wide"
+
+
+class TrajectoryWide24(Trajectory):
+    """The same store with up to 24 observation planes (rl_traj_create_wide24; up to 20 it builds what TrajectoryWide
+    builds): the trajectories of PartitionEnv lanes."""
+
+    CREATE = "rl_traj_create_wide24"
 
 
 def rollout(env, policy, traj):

@@ -225,6 +225,8 @@ int32_t rl_actor_to_cbor(rl_env *env, rl_mlp *module, int32_t actor_kind, double
       throw RlError(RL_ERR_UNSUPPORTED, "rl_actor_to_cbor is not built for RL_ENV_META_BANDIT lanes");
     if (env->kind == RL_ENV_META_MDP)  // (likewise)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_actor_to_cbor is not built for RL_ENV_META_MDP lanes");
+    if (env->kind == RL_ENV_PARTITION)  // (likewise)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_actor_to_cbor is not built for RL_ENV_PARTITION lanes");
     if (actor_kind == RL_ACTOR_DQN && rl_module_is_recurrent(module->kind))  // (no serde fixture of a recurrent DqnActor)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_actor_to_cbor is not built for the recurrent DqnActor of rl_dqn_create_recurrent");
     RL_REQUIRE(module->in_dim == env->D && module->out_dim == env->A, "module shape does not match the env");

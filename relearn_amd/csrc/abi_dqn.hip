@@ -108,6 +108,8 @@ static void dqn_check_env(const rl_env *env, bool recurrent) {
     throw RlError(RL_ERR_UNSUPPORTED, name + " is not built for RL_ENV_META_BANDIT lanes");
   if (env->kind == RL_ENV_META_MDP)
     throw RlError(RL_ERR_UNSUPPORTED, name + " is not built for RL_ENV_META_MDP lanes");
+  if (env->kind == RL_ENV_PARTITION)
+    throw RlError(RL_ERR_UNSUPPORTED, name + " is not built for RL_ENV_PARTITION lanes");
   const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
   if (env->kind != RL_ENV_CARTPOLE && !index_env)
     throw RlError(RL_ERR_UNSUPPORTED, (recurrent ? name + ": " : "") +
@@ -159,7 +161,7 @@ int32_t rl_dqn_create_recurrent(rl_env *env, rl_mlp *qnet, rl_adam *opt, const r
 // action (rl_rnn_chain_create: k_stack_collect_dqn<.., NA>).
 int32_t rl_dqn_create_finite(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_dqn_config *cfg, rl_dqn **out) {
   if (env && qnet && env->A <= 2 && qnet->out_dim <= 2 && env->kind != RL_ENV_META_BANDIT &&
-      env->kind != RL_ENV_TABULAR_MDP && env->kind != RL_ENV_META_MDP)
+      env->kind != RL_ENV_TABULAR_MDP && env->kind != RL_ENV_META_MDP && env->kind != RL_ENV_PARTITION)
     return rl_module_is_recurrent(qnet->kind) ? rl_dqn_create_recurrent(env, qnet, opt, cfg, out)
                                               : rl_dqn_create(env, qnet, opt, cfg, out);
   return guarded(env ? env->eng : nullptr, [&] {
@@ -168,6 +170,8 @@ int32_t rl_dqn_create_finite(rl_env *env, rl_mlp *qnet, rl_adam *opt, const rl_d
       throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite is not built for RL_ENV_META_BANDIT lanes");
     if (env->kind == RL_ENV_META_MDP)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite is not built for RL_ENV_META_MDP lanes");
+    if (env->kind == RL_ENV_PARTITION)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_dqn_create_finite is not built for RL_ENV_PARTITION lanes");
     RL_REQUIRE(qnet->in_dim == env->D && qnet->out_dim == env->A,
                "rl_dqn_create_finite: action-value module does not match the env's (obs_dim, n_actions)");
     if (env->kind == RL_ENV_TABULAR_MDP) {

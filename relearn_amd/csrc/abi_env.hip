@@ -185,6 +185,15 @@ int32_t rl_env_create_meta_mdp_wide(rl_engine *e, const rl_env_config *cfg, cons
   });
 }
 
+// PartitionGame (src/envs/partition.rs) under the index lanes' step limit: PartitionOps (env_lanes.hpp)
+int32_t rl_env_create_partition(rl_engine *e, const rl_env_config *cfg, rl_env **out) {
+  return guarded(e, [&] {
+    RL_REQUIRE(e && cfg && out, "rl_env_create_partition: NULL argument");
+    *out = nullptr;
+    env_build(e, env_spec_partition(*cfg), out);
+  });
+}
+
 // the current trial's tables as the lanes read them: the padding of the rows' eight (or sixteen) floats is dropped
 int32_t rl_env_meta_mdp_read_tables(rl_env *env, uint64_t first_lane, uint64_t n, float *cum_out, double *mean_out) {
   return guarded(env ? env->eng : nullptr, [&] {
@@ -339,6 +348,8 @@ int32_t rl_env_get_state(rl_env *env, double *state4, int32_t *nv_pos, uint64_t 
       throw RlError(RL_ERR_UNSUPPORTED, "rl_env_get_state is not built for RL_ENV_META_BANDIT lanes");
     if (env->kind == RL_ENV_META_MDP)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_env_get_state is not built for RL_ENV_META_MDP lanes");
+    if (env->kind == RL_ENV_PARTITION)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_env_get_state is not built for RL_ENV_PARTITION lanes");
     rl_engine *e = env->eng;
     size_t n = env->cfg.n_lanes;
     d2h(e, state4 + 0 * n, env->st.x, n * sizeof(double));
@@ -366,6 +377,8 @@ int32_t rl_env_set_state(rl_env *env, const double *state4, const int32_t *nv_po
       throw RlError(RL_ERR_UNSUPPORTED, "rl_env_set_state is not built for RL_ENV_META_BANDIT lanes");
     if (env->kind == RL_ENV_META_MDP)
       throw RlError(RL_ERR_UNSUPPORTED, "rl_env_set_state is not built for RL_ENV_META_MDP lanes");
+    if (env->kind == RL_ENV_PARTITION)
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_env_set_state is not built for RL_ENV_PARTITION lanes");
     rl_engine *e = env->eng;
     size_t n = env->cfg.n_lanes;
     if (env->kind == RL_ENV_TABULAR_MDP)  // the lane's state indexes the tables; its stream position is an even word

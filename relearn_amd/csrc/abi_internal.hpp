@@ -140,8 +140,9 @@ extern "C" {
 void engine_release_child(rl_engine *e);
 // abi_traj.hip
 void traj_plan(rl_traj *t, uint64_t B);
-// `wide`: rl_traj_create_wide, up to RL_XWIDE_MAX_OBS_DIM observation planes
-rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, bool resizable, bool wide = false);
+// `level`: the entry point (rl_traj_create, _wide, _wide24) and with it the most observation planes (traj_max_obs_dim)
+rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, bool resizable,
+                    TrajLevel level = TRAJ_LEVEL_BASE);
 void seq_ensure(rl_traj *t, const rl_mlp *mod, bool training);
 void traj_ensure_pvec(rl_traj *t, uint64_t P);
 // abi_module.hip

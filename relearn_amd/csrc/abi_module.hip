@@ -156,6 +156,17 @@ int32_t rl_rnn_chain_create_wide20(rl_engine *e, const rl_rnn_chain_config *cfg,
   });
 }
 
+// The same chain at in_dim 1..24 (the partition-game experiment's model: 24 inputs under the visible limit, two outputs
+// for the policy, one for the critic).  At in_dim <= 20: rl_rnn_chain_create_wide20, the same handle.  As there, no
+// kernel is built for these modules: the lane-per-thread kernels take the input width at run time.
+int32_t rl_rnn_chain_create_wide24(rl_engine *e, const rl_rnn_chain_config *cfg, rl_mlp **out) {
+  return guarded(e, [&] {
+    RL_REQUIRE(e && cfg && out, "NULL argument");
+    *out = nullptr;
+    chain_create(e, *cfg, chain_limits_wide24(*cfg), out);
+  });
+}
+
 int32_t rl_mlp_destroy(rl_mlp *m) { return destroy_child(m); }
 
 int32_t rl_mlp_num_params(const rl_mlp *m, uint64_t *n) {

@@ -53,15 +53,19 @@ void traj_plan(rl_traj *t, uint64_t B) {
 
 // `resizable`: the sample count changes between launches (DQN minibatches): slabs are sized for the largest grid
 // any B <= n_lanes * horizon can plan
-rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, bool resizable, bool wide) {
+rl_traj *traj_alloc(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, bool resizable, TrajLevel level) {
   RL_REQUIRE(n_lanes > 0 && n_lanes < (1ull << 31), "bad n_lanes");
   RL_REQUIRE(horizon > 0 && horizon < (1ull << 20), "bad horizon");
-  // (up to 16 planes: the wide meta-bandit lanes; what reads a trajectory checks its own width against the planes')
-  // `wide` (rl_traj_create_wide): up to 20, the meta-MDP lanes of rl_env_create_meta_mdp_wide
-  if (wide && obs_dim > RL_WIDE_MAX_OBS_DIM)
-    RL_REQUIRE(obs_dim <= RL_XWIDE_MAX_OBS_DIM, "rl_traj_create_wide: obs_dim must be in 1..20");
+  // (what reads a trajectory checks its own width against the planes')
+  // up to 16 planes (the wide meta-bandit lanes) every entry point is rl_traj_create, up to 20 (the meta-MDP lanes of
+  // rl_env_create_meta_mdp_wide) the two wider ones are rl_traj_create_wide, and rl_traj_create_wide24 ends at 24 (the
+  // PartitionGame lanes): the words are those of the level a width falls in
+  if (level >= TRAJ_LEVEL_WIDE24 && obs_dim > traj_max_obs_dim(TRAJ_LEVEL_WIDE))
+    RL_REQUIRE(obs_dim <= traj_max_obs_dim(TRAJ_LEVEL_WIDE24), "rl_traj_create_wide24: obs_dim must be in 1..24");
+  else if (level >= TRAJ_LEVEL_WIDE && obs_dim > traj_max_obs_dim(TRAJ_LEVEL_BASE))
+    RL_REQUIRE(obs_dim <= traj_max_obs_dim(TRAJ_LEVEL_WIDE), "rl_traj_create_wide: obs_dim must be in 1..20");
   else
-    RL_REQUIRE(obs_dim >= 1 && obs_dim <= RL_WIDE_MAX_OBS_DIM, "obs_dim must be in 1..16");
+    RL_REQUIRE(obs_dim >= 1 && obs_dim <= traj_max_obs_dim(TRAJ_LEVEL_BASE), "obs_dim must be in 1..16");
   RL_REQUIRE(n_lanes * horizon < (1ull << 32), "T * n must fit 32 bits");
   RL_HIP_CHECK(hipSetDevice(e->device));
   std::unique_ptr<rl_traj> t(new rl_traj());
@@ -140,7 +144,16 @@ int32_t rl_traj_create_wide(rl_engine *e, uint64_t n_lanes, uint64_t horizon, ui
   return guarded(e, [&] {
     RL_REQUIRE(e && out, "NULL argument");
     *out = nullptr;
-    *out = traj_alloc(e, n_lanes, horizon, obs_dim, false, true);
+    *out = traj_alloc(e, n_lanes, horizon, obs_dim, false, TRAJ_LEVEL_WIDE);
+  });
+}
+
+// ... with up to 24 (PartitionGame lanes under a visible limit); up to 20 it is rl_traj_create_wide's
+int32_t rl_traj_create_wide24(rl_engine *e, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim, rl_traj **out) {
+  return guarded(e, [&] {
+    RL_REQUIRE(e && out, "NULL argument");
+    *out = nullptr;
+    *out = traj_alloc(e, n_lanes, horizon, obs_dim, false, TRAJ_LEVEL_WIDE24);
   });
 }
 
@@ -260,6 +273,7 @@ int32_t rl_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     if (traj == env->eng->pending.traj || policy == env->eng->pending.critic) engine_settle(env->eng);
     traj->range_valid = traj->range_reset = false;  // new observations: the range guard has them measured again
     traj->rtg_scan_valid = false;                   // new rewards: the return plane belongs to the old ones
+    rollout_check_env_kind(env->kind, *policy);
     RL_REQUIRE(traj->d.n == env->cfg.n_lanes && traj->d.D == env->D, "trajectory shape does not match the env");
     rollout_check_shapes(env->D, env->A, *policy);
     traj->n_actions = env->A;

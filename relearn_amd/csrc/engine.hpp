@@ -32,6 +32,8 @@ struct EnvStateDev {
   // RL_ENV_TABULAR_MDP: x = state index, th = next unread word of the env stream (MemoryGame's columns; xdot unused)
   // RL_ENV_META_MDP: x = inner state index, thdot = inner steps remaining, xdot = next unread word of the env stream,
   // th = the previous inner step's reward; nv_pos and steps_remaining as on RL_ENV_META_BANDIT
+  // RL_ENV_PARTITION: x = one packed word (bits 0-9 the element, 10-19 the previous element, 20 its label, 21 feedback is
+  // Some, 22-25 the supervisor's axis; below 2^26), th = next unread word of the env stream; xdot, thdot, nv_pos unused
   uint8_t *nv_pos;                // [n] cached_normal_velocity_is_positive
   uint32_t *steps_remaining;      // [n]
   uint32_t *reset_count;          // [n]

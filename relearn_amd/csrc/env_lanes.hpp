@@ -746,6 +746,111 @@ struct MetaMdpOps : MetaMdpRowOps<8> {};
 // count of cum[j] <= u over j < 15
 struct MetaMdpWideOps : MetaMdpRowOps<16> {};
 
+// ---------------------------------------------------------------- PartitionGame lanes (RL_ENV_PARTITION)
+// PartitionGame (src/envs/partition.rs:86-130) under the index lanes' step limit.  A lane: the supervisor's axis (0..9),
+// the element ([bool; 10], bit j = element[j]), the feedback Option<(previous element, its label)>.  Every draw is taken
+// SEQUENTIALLY from the lane's env stream at `env_pos`, which stays even: initial_state takes gen_range(0..10) over usize
+// (lane_gen_range: whole u64s) and then the element; a step takes the next element.  An element is `rng.gen()` of
+// [bool; 10]: ten gen::<bool>() in index order, each one next_u32 whose sign bit is the value, `(x as i32) < 0` — ten
+// words.  rand's source is not at hand here: that this equals rand 0.8.5's Standard for bool and for arrays (index order,
+// one word per bool) rests on a check against its source (distributions/other.rs), as rl_beta.h says of its sampler.
+// The lane's columns: x = the packed word below (< 2^26, exact in a double), th = env_pos as on MemoryGame lanes,
+// steps_remaining and reset_count their own; xdot, thdot and nv_pos are not used.
+struct PartitionLane {
+  uint64_t env_pos;      // next unread word of the lane's env stream (always even)
+  uint32_t axis;         // Supervisor::AxisAligned(axis)
+  uint32_t element;      // bits 0-9
+  uint32_t fb_element;   // feedback: Some((fb_element, fb_label)) when fb_some
+  uint32_t fb_label;     // Classification: Left 0, Right 1
+  uint32_t fb_some;
+  uint32_t steps_remaining, reset_count;
+};
+
+// the sign bits of the sixteen words of block `block` of the lane's stream, bit k = word k: constant register indices only
+__device__ __forceinline__ uint32_t lane_block_signs(const uint32_t *key, uint64_t glane, uint64_t block) {
+  uint32_t w[16];
+  rl_chacha_block(key, block, glane, 4, w);
+  uint32_t m = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) m |= (w[k] >> 31) << k;
+  return m;
+}
+// [bool; 10] at word position `pos`: bit j = the sign of word pos + j.  The ten words lie in the block of `pos` when
+// (pos & 15) <= 6 and run into the next one otherwise: each block is taken from the position asked for, the two sign masks
+// are joined into one 32-bit word and the ten bits shifted out of it — no register array is indexed by the lane's position.
+__device__ __forceinline__ uint32_t lane_bool10_at(const uint32_t *key, uint64_t glane, uint64_t pos) {
+  const uint32_t k0 = (uint32_t)(pos & 15);
+  uint32_t signs = lane_block_signs(key, glane, pos >> 4);
+  if (k0 > 6) signs |= lane_block_signs(key, glane, (pos >> 4) + 1) << 16;
+  return (signs >> k0) & 0x3FFu;
+}
+
+struct PartitionOps {
+  using State = PartitionLane;
+  static __device__ __forceinline__ void load(const EnvStateDev &st, uint32_t i, State &s) {
+    const uint32_t p = (uint32_t)st.x[i];
+    s.element = p & 0x3FFu;
+    s.fb_element = (p >> 10) & 0x3FFu;
+    s.fb_label = (p >> 20) & 1u;
+    s.fb_some = (p >> 21) & 1u;
+    s.axis = (p >> 22) & 15u;
+    s.env_pos = (uint64_t)st.th[i];
+    s.steps_remaining = st.steps_remaining[i];
+    s.reset_count = st.reset_count[i];
+  }
+  static __device__ __forceinline__ void store(const EnvStateDev &st, uint32_t i, const State &s) {
+    st.x[i] = (double)(s.element | (s.fb_element << 10) | (s.fb_label << 20) | (s.fb_some << 21) | (s.axis << 22));
+    st.th[i] = (double)s.env_pos;  // exact below 2^53 words
+    st.steps_remaining[i] = s.steps_remaining;
+    st.reset_count[i] = s.reset_count;
+  }
+  // TupleSpace2<PowerSpace<BooleanSpace, 10>, OptionSpace<TupleSpace2<PowerSpace<..>, IndexedTypeSpace<Classification>>>>
+  // (spaces/tuple.rs, power.rs, option.rs:95-109, indexed_type.rs:175-187, boolean.rs:132-140), D = 23 [+ 1]:
+  //   [element, 10] [feedback is None] [previous element, 10] [one-hot label: Left, Right] [+ remaining]
+  // (the 12 entries behind a None marker are zero; `remaining` as the index lanes write it)
+  template <int D>
+  static __device__ __forceinline__ void features(const CartPoleDev &c, const State &s, float (&f)[D]) {
+    static_assert(D == 23 || D == 24, "PartitionGame lanes have 23 features, 24 under a visible limit");
+    const uint32_t fb = s.fb_some ? s.fb_element : 0u;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) {
+      f[j] = (s.element >> j) & 1u ? 1.0f : 0.0f;
+      f[11 + j] = (fb >> j) & 1u ? 1.0f : 0.0f;
+    }
+    f[10] = s.fb_some ? 0.0f : 1.0f;
+    f[21] = s.fb_some && s.fb_label == 0u ? 1.0f : 0.0f;
+    f[22] = s.fb_some && s.fb_label == 1u ? 1.0f : 0.0f;
+    if constexpr (D == 24) f[23] = (float)((double)s.steps_remaining / (double)c.max_steps);
+  }
+  // PartitionGame::step (partition.rs:107-129), then the step-limit tail.  `word` is unused: the draws are sequential.
+  static __device__ __forceinline__ int step(const CartPoleDev &c, State &s, int a, uint64_t glane, uint64_t,
+                                             float &reward) {
+    const uint32_t label = (s.element >> s.axis) & 1u;  // Supervisor::classify: Right when element[axis]
+    reward = (uint32_t)a == label ? 1.0f : -1.0f;
+    s.fb_some = 1;
+    s.fb_element = s.element;
+    s.fb_label = label;
+    s.element = lane_bool10_at(c.key_env, glane, s.env_pos);
+    s.env_pos += 10;
+    if (c.limit_kind != RL_LIMIT_NONE) {
+      s.steps_remaining -= 1;
+      if (s.steps_remaining == 0) return RL_SUCC_INTERRUPT;
+    }
+    return RL_SUCC_CONTINUE;
+  }
+  // PartitionGame::initial_state (partition.rs:93-101): the axis, then the element; feedback None
+  static __device__ __forceinline__ void reset(const CartPoleDev &c, State &s, uint64_t glane) {
+    s.axis = lane_gen_range(c.key_env, glane, s.env_pos, 10);
+    s.element = lane_bool10_at(c.key_env, glane, s.env_pos);
+    s.env_pos += 10;
+    s.fb_some = 0;
+    s.fb_element = 0;
+    s.fb_label = 0;
+    s.steps_remaining = c.max_steps;
+    s.reset_count += 1;
+  }
+};
+
 // ---------------------------------------------------------------- one step of a lane, recorded
 // Environment::step, the step's record, the successor observation of a cut episode, the auto-reset: the rule every
 // stepping kernel follows, in this order.  `sink` is the kernel's part — where the record goes:

@@ -42,6 +42,9 @@ constexpr uint32_t RL_WIDE_MAX_OUT = 12;
 // of up to 10 states (S + A + 4 <= 20 features: DirichletRandomMdps::default's 10 x 5 has 19) and recurrent chains of up
 // to 20 inputs.  RL_WIDE_MAX_OBS_DIM keeps guarding the entry points it guards.
 constexpr uint32_t RL_XWIDE_MAX_OBS_DIM = 20;
+// rl_env_create_partition, rl_rnn_chain_create_wide24, rl_traj_create_wide24: PartitionGame lanes (23 features, 24 under
+// a visible step limit) and recurrent chains of up to 24 inputs.  RL_XWIDE_MAX_OBS_DIM keeps guarding what it guards.
+constexpr uint32_t RL_PARTITION_MAX_OBS_DIM = 24;
 constexpr uint32_t RL_RNN_MAX_LAYERS = 4;  // RnnBaseConfig::num_layers of a recurrent chain
 
 // ---------------------------------------------------------------- env lanes: the struct every env kernel takes by value
@@ -175,6 +178,8 @@ inline void env_check_kind(const rl_env_config &cfg) {
     throw RlError(RL_ERR_BUILD_ENV, "RL_ENV_TABULAR_MDP lanes are created by rl_env_create_tabular_mdp");
   if (cfg.kind == RL_ENV_META_MDP)
     throw RlError(RL_ERR_BUILD_ENV, "RL_ENV_META_MDP lanes are created by rl_env_create_meta_mdp");
+  if (cfg.kind == RL_ENV_PARTITION)
+    throw RlError(RL_ERR_BUILD_ENV, "RL_ENV_PARTITION lanes are created by rl_env_create_partition");
   if (cfg.kind != RL_ENV_CARTPOLE && cfg.kind != RL_ENV_CHAIN && cfg.kind != RL_ENV_MEMORY && cfg.kind != RL_ENV_BANDIT)
     throw RlError(RL_ERR_BUILD_ENV, "unknown env kind");
 }
@@ -408,6 +413,28 @@ inline EnvSpec env_spec_meta_mdp_wide(const rl_env_config &cfg, const rl_meta_md
   return env_spec_meta_mdp_ranged(cfg, meta, true);
 }
 
+// PartitionGame (src/envs/partition.rs:11-130) under the index lanes' step limit, whatever cfg.kind says.  Observations
+// (the derived space's order — spaces/tuple.rs, power.rs, option.rs:95-109, indexed_type.rs:175-187, boolean.rs:132-140):
+// [element, 10] [feedback is None] [previous element, 10] [one-hot label, 2] [+ remaining]: 23 features, 24 under a
+// visible limit.  Two actions (ClassifyLeft, ClassifyRight).  The lanes read the stream key and the limit alone.
+constexpr uint32_t RL_PARTITION_FEATURES = 10;  // partition.rs:11 NUM_FEATURES
+constexpr uint32_t RL_PARTITION_OBS_DIM = 2 * RL_PARTITION_FEATURES + 3;
+inline EnvSpec env_spec_partition(const rl_env_config &cfg_in) {
+  const rl_env_config cfg = env_config_of_kind(cfg_in, RL_ENV_PARTITION);
+  if (cfg.limit_kind != RL_LIMIT_NONE && cfg.limit_kind != RL_LIMIT_LATENT && cfg.limit_kind != RL_LIMIT_VISIBLE)
+    throw RlError(RL_ERR_BUILD_ENV, "rl_env_create_partition: limit_kind is RL_LIMIT_NONE, RL_LIMIT_LATENT or "
+                                    "RL_LIMIT_VISIBLE");
+  env_check_limit_and_lanes(cfg);
+  EnvSpec s = env_spec_begin(cfg, RL_PARTITION_OBS_DIM + env_remaining_feature(cfg), 2);
+  static_assert(RL_PARTITION_OBS_DIM + 1 == RL_PARTITION_MAX_OBS_DIM, "the widest chain and trajectory take these lanes");
+  CartPoleDev &d = s.dev;
+  d.init_low = -0.05;  // (read by nothing on these lanes)
+  d.init_scale = rl_uniform_f64_inclusive_scale(-0.05, 0.05);
+  d.max_steps = env_step_limit(cfg);
+  d.chain_size = 0;  // (as on meta lanes: nothing takes these for an index env of five states)
+  return s;
+}
+
 // The (S, A) shapes of RL_ENV_META_MDP lanes whose recurrent rollout is one launch (k_stack_rollout<.., MetaMdpOps, ..>,
 // kernels_seq_stack.hip): the smallest, the odd widths, the default, the most features with the widest row, and the most
 // actions with two head passes.  Every other shape in range runs the launch sequence per step.
@@ -575,6 +602,9 @@ constexpr ChainLimits CHAIN_WIDE{
 constexpr ChainLimits CHAIN_WIDE20{
     RL_XWIDE_MAX_OBS_DIM, RL_WIDE_MAX_OUT, 0,
     "rl_rnn_chain_create_wide20: in_dim 1..20, recurrent hidden 1..256, mlp_hidden 0..256, out_dim 1..12"};
+constexpr ChainLimits CHAIN_WIDE24{
+    RL_PARTITION_MAX_OBS_DIM, RL_WIDE_MAX_OUT, 0,
+    "rl_rnn_chain_create_wide24: in_dim 1..24, recurrent hidden 1..256, mlp_hidden 0..256, out_dim 1..12"};
 // rl_rnn_chain_create_wide: within in_dim <= 8 and out_dim <= 8 it is rl_rnn_chain_create, bound and words
 inline const ChainLimits &chain_limits_wide(const rl_rnn_chain_config &cfg) {
   return cfg.in_dim <= RL_TRAJ_MAX_OBS_DIM && cfg.out_dim <= RL_MLP_MAX_OUT ? CHAIN_NARROW : CHAIN_WIDE;
@@ -582,6 +612,16 @@ inline const ChainLimits &chain_limits_wide(const rl_rnn_chain_config &cfg) {
 // rl_rnn_chain_create_wide20: at in_dim <= 16 it is rl_rnn_chain_create_wide, bound and words
 inline const ChainLimits &chain_limits_wide20(const rl_rnn_chain_config &cfg) {
   return cfg.in_dim <= RL_WIDE_MAX_OBS_DIM ? chain_limits_wide(cfg) : CHAIN_WIDE20;
+}
+// rl_rnn_chain_create_wide24: at in_dim <= 20 it is rl_rnn_chain_create_wide20, bound and words
+inline const ChainLimits &chain_limits_wide24(const rl_rnn_chain_config &cfg) {
+  return cfg.in_dim <= RL_XWIDE_MAX_OBS_DIM ? chain_limits_wide20(cfg) : CHAIN_WIDE24;
+}
+// rl_traj_create / _wide / _wide24: the entry point a trajectory came through, and the most observation planes it takes.
+// Inside the bound of the level below, a level is that level: bound and words (traj_alloc, abi_traj.hip).
+enum TrajLevel { TRAJ_LEVEL_BASE = 0, TRAJ_LEVEL_WIDE = 1, TRAJ_LEVEL_WIDE24 = 2 };
+inline uint32_t traj_max_obs_dim(TrajLevel level) {
+  return level == TRAJ_LEVEL_WIDE24 ? RL_PARTITION_MAX_OBS_DIM : level == TRAJ_LEVEL_WIDE ? RL_XWIDE_MAX_OBS_DIM : RL_WIDE_MAX_OBS_DIM;
 }
 
 // the module kind of a config's cell; its first two refusals (tested before a NULL handle is, by every constructor that
@@ -839,7 +879,16 @@ inline void rollout_check_shapes(uint32_t D, uint32_t A, const ModuleShape &m) {
   RL_REQUIRE(m.in_dim == D && m.out_dim == A, "policy shape does not match the env");
 }
 
+// ... and before either: PartitionGame lanes have 23 or 24 features and a feed-forward module at most eight inputs, so no
+// such pair matches; it is refused by name, before a shape is compared (rl_rollout tests this first of all)
+inline void rollout_check_env_kind(int env_kind, const ModuleShape &m) {
+  if (env_kind == RL_ENV_PARTITION && !rl_module_is_recurrent(m.kind))
+    throw RlError(RL_ERR_UNSUPPORTED, "rl_rollout: feed-forward modules are not built for RL_ENV_PARTITION lanes (a "
+                                      "recurrent chain of rl_rnn_chain_create_wide24 is)");
+}
+
 inline RolloutPath rollout_path(int env_kind, uint32_t D, uint32_t A, uint32_t chain_size, const ModuleShape &m) {
+  rollout_check_env_kind(env_kind, m);
   rollout_check_shapes(D, A, m);
   const bool recurrent = rl_module_is_recurrent(m.kind);
   // the fused index-env kernels are built for five states (Chain::default, MemoryGame::new(2, 3), the bandit's
@@ -852,6 +901,8 @@ inline RolloutPath rollout_path(int env_kind, uint32_t D, uint32_t A, uint32_t c
   // meta-MDP lanes likewise (one launch at the shapes of META_MDP_FUSED_SHAPES).  A feed-forward module has at most eight
   // inputs: it matches 2 x 2 alone, and went to ROLL_GENERAL above (chain_size is 0 on these lanes)
   if (env_kind == RL_ENV_META_MDP) return ROLL_STACK;
+  // PartitionGame lanes likewise: one launch at 24 features, the launch sequence per step at 23
+  if (env_kind == RL_ENV_PARTITION) return ROLL_STACK;
   if (!fused_index_env && !m.lane_kernels())
     throw RlError(RL_ERR_UNSUPPORTED, "the fused recurrent rollout is built for index envs of five states");
   if (recurrent && m.lane_kernels()) return ROLL_STACK;

@@ -156,6 +156,13 @@ class EnvLanes {
           eng.handle());
     check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
   }
+  // PartitionGame lanes (rl_env_create_partition); discount factor 0.999 (partition.rs:81-83)
+  struct PartitionGameTag {};
+  EnvLanes(Engine &eng, const rl_env_config &cfg, PartitionGameTag)
+      : eng_(eng), cfg_(cfg), discount_(PartitionGame{}.discount_factor) {
+    check(rl_env_create_partition(eng.handle(), &cfg_, &h_), eng.handle());
+    check(rl_env_dims(h_, &obs_dim_, &n_actions_), eng.handle());
+  }
   Engine &eng_;
   rl_env_config cfg_;
   rl_env *h_ = nullptr;
@@ -364,6 +371,31 @@ class MetaMdpLanes : public EnvLanes {
   }
 };
 
+// `PartitionGame::default().wrap(VisibleStepLimit::new(max_steps))` x n_lanes (src/envs/partition.rs; the env of
+// relearn_experiments/src/bin/partition-game.rs, whose limit is 1000): 23 observation features, 24 under a visible limit,
+// two actions, discount factor 0.999.  Lane g's episodes are the scalar mirror's (host/envs.hpp: PartitionGame) on the
+// generator seed_from_u64(seed_env), stream g.  Policies: the recurrent chains of rl_rnn_chain_create_wide24.
+class PartitionGameLanes : public EnvLanes {
+ public:
+  PartitionGameLanes(Engine &eng, uint64_t n_lanes, uint64_t max_steps = 1000, StepLimit limit = StepLimit::Visible,
+                     uint64_t seed_env = 0, uint64_t seed_actor = 1, uint64_t lane_offset = 0)
+      : EnvLanes(eng, config(n_lanes, max_steps, limit, seed_env, seed_actor, lane_offset), PartitionGameTag{}) {}
+
+ private:
+  static rl_env_config config(uint64_t n, uint64_t max_steps, StepLimit limit, uint64_t se, uint64_t sa, uint64_t off) {
+    rl_env_config c{};
+    c.kind = RL_ENV_PARTITION;
+    c.limit_kind = (int32_t)limit;
+    c.max_steps = max_steps;
+    c.n_lanes = n;
+    c.lane_offset = off;
+    c.seed_env = se;
+    c.seed_actor = sa;
+    check(rl_cartpole_params_default(&c.cartpole));
+    return c;
+  }
+};
+
 // ---------------------------------------------------------------- modules (BuildModule)
 class Module {
  public:
@@ -454,6 +486,8 @@ inline int32_t rnn_chain_create_multi(Engine &eng, int32_t cell, const RnnBaseCo
   cfg.out_dim = out_dim;
   // (more than eight inputs or outputs — the rl2-bandits experiment above four arms: the wide constructor)
   // (more than sixteen inputs — the RL2 MDP experiment at 10 x 5, 19 features: rl_rnn_chain_create_wide20)
+  // (more than twenty inputs — the partition-game experiment, 24 features: rl_rnn_chain_create_wide24)
+  if (in_dim > 20) return rl_rnn_chain_create_wide24(eng.handle(), &cfg, h);
   if (in_dim > 16) return rl_rnn_chain_create_wide20(eng.handle(), &cfg, h);
   return in_dim > 8 || out_dim > 8 ? rl_rnn_chain_create_wide(eng.handle(), &cfg, h)
                                    : rl_rnn_chain_create(eng.handle(), &cfg, h);
@@ -669,8 +703,10 @@ class DeviceHistory {
  public:
   DeviceHistory(Engine &eng, uint64_t n_lanes, uint64_t horizon, uint32_t obs_dim) : n_(n_lanes), T_(horizon) {
     // (more than sixteen planes — the meta-MDP lanes of 10 x 5 — are rl_traj_create_wide's)
-    check(obs_dim > 16 ? rl_traj_create_wide(eng.handle(), n_lanes, horizon, obs_dim, &h_)
-                       : rl_traj_create(eng.handle(), n_lanes, horizon, obs_dim, &h_),
+    // (more than twenty — the PartitionGame lanes — rl_traj_create_wide24's)
+    check(obs_dim > 20   ? rl_traj_create_wide24(eng.handle(), n_lanes, horizon, obs_dim, &h_)
+          : obs_dim > 16 ? rl_traj_create_wide(eng.handle(), n_lanes, horizon, obs_dim, &h_)
+                         : rl_traj_create(eng.handle(), n_lanes, horizon, obs_dim, &h_),
           eng.handle());
   }
   ~DeviceHistory() { rl_traj_destroy(h_); }

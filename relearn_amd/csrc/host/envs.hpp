@@ -202,6 +202,60 @@ struct DirichletRandomMdps {
   }
 };
 
+// PartitionGame (src/envs/partition.rs:11-130): a supervisor classifies elements of ten booleans by one axis, drawn at the
+// episode's start; the action classifies the current element (ClassifyLeft 0, ClassifyRight 1) and earns +1 when it is the
+// supervisor's label, else -1; the next observation carries the element just judged and its label.  Never terminates.
+// Draws, as the lanes of rl_env_create_partition state them (include/relearn_hip.h): gen_range(0..10) for the axis, then
+// ten gen::<bool>() — one next_u32 each, the sign bit is the value — per element, in index order.
+struct PartitionGame {
+  static constexpr uint64_t NUM_FEATURES = 10;
+  using Action = uint64_t;
+  using Observation = std::vector<float>;
+  struct State {
+    uint64_t axis = 0;      // Supervisor::AxisAligned(axis)
+    uint32_t element = 0;   // bit j = element[j]
+    bool feedback = false;  // Some((prev_element, label))
+    uint32_t prev_element = 0;
+    uint32_t label = 0;     // Classification: Left 0, Right 1
+  };
+  double discount_factor = 0.999;
+
+  uint64_t num_observation_features() const { return 2 * NUM_FEATURES + 3; }
+  uint64_t num_actions() const { return 2; }
+  static uint32_t gen_element(Prng &rng) {
+    uint32_t e = 0;
+    for (uint64_t j = 0; j < NUM_FEATURES; ++j) e |= (rng.next_u32() >> 31) << j;  // (x as i32) < 0
+    return e;
+  }
+  State initial_state(Prng &rng) const {
+    State s;
+    s.axis = rng.gen_range(0, NUM_FEATURES);
+    s.element = gen_element(rng);
+    return s;
+  }
+  // [element, 10] [feedback is None] [previous element, 10] [one-hot label: Left, Right]
+  Observation observe(const State &s, Prng &) const {
+    Observation f(num_observation_features(), 0.0f);
+    for (uint64_t j = 0; j < NUM_FEATURES; ++j) f[j] = (s.element >> j) & 1u ? 1.0f : 0.0f;
+    if (s.feedback) {
+      for (uint64_t j = 0; j < NUM_FEATURES; ++j) f[NUM_FEATURES + 1 + j] = (s.prev_element >> j) & 1u ? 1.0f : 0.0f;
+      f[2 * NUM_FEATURES + 1 + s.label] = 1.0f;
+    } else {
+      f[NUM_FEATURES] = 1.0f;
+    }
+    return f;
+  }
+  std::pair<Successor<State>, double> step(State s, Action a, Prng &rng) const {
+    const uint32_t label = (s.element >> s.axis) & 1u;
+    const double reward = a == label ? 1.0 : -1.0;
+    s.feedback = true;
+    s.prev_element = s.element;
+    s.label = label;
+    s.element = gen_element(rng);
+    return {Successor<State>::Continue(std::move(s)), reward};
+  }
+};
+
 // Wrapped<E, LatentStepLimit> (src/envs/wrappers/step_limit.rs:13-89): the limit is not observable
 template <typename E>
 struct WithLatentStepLimit {
@@ -223,6 +277,31 @@ struct WithLatentStepLimit {
     const uint64_t left = s.steps_remaining - 1;
     auto wrapped = std::move(succ).template map<State>([&](typename E::State in) { return State{std::move(in), left}; });
     return {std::move(wrapped).then_interrupt_if([](const State &n) { return n.steps_remaining == 0; }), reward};
+  }
+};
+
+// Wrapped<E, VisibleStepLimit> (src/envs/wrappers/step_limit.rs:97-222) over an env whose observation is its feature
+// vector: the observation carries `remaining / max` as one more feature (f64 quotient, then `as f32`), which is what the
+// lanes write under RL_LIMIT_VISIBLE.  partition-game.rs wraps PartitionGame in VisibleStepLimit::new(1000).
+template <typename E>
+struct WithVisibleStepLimit {
+  using State = typename WithLatentStepLimit<E>::State;
+  using Observation = std::vector<float>;
+  using Action = typename E::Action;
+  E inner;
+  uint64_t max_steps_per_episode = 100;
+
+  uint64_t num_observation_features() const { return inner.num_observation_features() + 1; }
+  uint64_t num_actions() const { return inner.num_actions(); }
+  State initial_state(Prng &rng) const { return {inner.initial_state(rng), max_steps_per_episode}; }
+  Observation observe(const State &s, Prng &rng) const {
+    Observation f = inner.observe(s.inner, rng);
+    f.push_back((float)((double)s.steps_remaining / (double)max_steps_per_episode));
+    return f;
+  }
+  // the latent wrapper's step: the two differ in what they show, not in when they cut
+  std::pair<Successor<State>, double> step(State s, Action a, Prng &rng) const {
+    return WithLatentStepLimit<E>{inner, max_steps_per_episode}.step(std::move(s), a, rng);
   }
 };
 

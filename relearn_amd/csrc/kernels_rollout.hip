@@ -403,7 +403,8 @@ void launch_obs_range(rl_traj *traj) {
 // The standalone env kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature
 // count as types.  CartPole lanes have 4 or 5 features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame:
 // num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..16; tabular-MDP lanes states [+ 1] = 2..8;
-// meta-MDP lanes states + actions + 4 = 8..16, and 15..20 at nine and ten states (MetaMdpWideOps).
+// meta-MDP lanes states + actions + 4 = 8..16, and 15..20 at nine and ten states (MetaMdpWideOps); PartitionGame lanes 23
+// or 24.
 template <int D>
 using FeatureCount = std::integral_constant<int, D>;
 template <class Go>
@@ -462,6 +463,14 @@ static void env_dispatch(const rl_env *env, Go &&go) {
     }
     return;
   }
+  if (env->kind == RL_ENV_PARTITION) {  // 23 features, 24 under a visible limit
+    switch (env->D) {
+      case 23: go(PartitionOps{}, FeatureCount<23>{}); break;
+      case 24: go(PartitionOps{}, FeatureCount<24>{}); break;
+      default: throw RlError(RL_ERR_UNSUPPORTED, "PartitionGame lanes: 23 or 24 observation features");
+    }
+    return;
+  }
   if (env->kind == RL_ENV_TABULAR_MDP) {  // n_states [+ 1] features, 2..8 states
     switch (env->D) {
       case 2: go(MdpOps{}, FeatureCount<2>{}); break;
@@ -497,6 +506,8 @@ void launch_env_reset(rl_env *env) {
     hipLaunchKernelGGL(k_env_reset<MetaOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else if (env->kind == RL_ENV_TABULAR_MDP)
     hipLaunchKernelGGL(k_env_reset<MdpOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  else if (env->kind == RL_ENV_PARTITION)
+    hipLaunchKernelGGL(k_env_reset<PartitionOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else if (env->kind == RL_ENV_META_MDP && env->dev.mm.states > RL_META_MDP_MAX)
     hipLaunchKernelGGL(k_env_reset<MetaMdpWideOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
   else if (env->kind == RL_ENV_META_MDP)

@@ -1103,6 +1103,25 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     env->t_global += traj->d.T;
     return;
   }
+  if (env->kind == RL_ENV_PARTITION && env->eng->kernel_variant != 1 && env->D == RL_PARTITION_MAX_OBS_DIM) {
+    // PartitionGame lanes under a visible limit (24 features, the partition-game experiment's shape): all T steps in one
+    // launch.  23 features (no or a latent limit) and kernel variant 1 keep the launch sequence per step, below.
+    RL_REQUIRE(env->A == 2, "fused recurrent rollout on PartitionGame lanes: two actions");
+#define ROLL(CELL, LIN)                                                                                             \
+  hipLaunchKernelGGL((k_stack_rollout<CELL, PartitionOps, 24, LIN, 2>), grid, blk, 0, env->eng->stream, net, ws, \
+                     env->dev, env->st, traj->d, env->t_global)
+    if (lstm) {
+      if (lin) ROLL(LSTM, true);
+      else ROLL(LSTM, false);
+    } else {
+      if (lin) ROLL(GRU, true);
+      else ROLL(GRU, false);
+    }
+#undef ROLL
+    RL_HIP_CHECK(hipGetLastError());
+    env->t_global += traj->d.T;
+    return;
+  }
   launch_rollout_stepwise(env, traj, z, [&](uint32_t step) {
     const int first = step == 0 ? 1 : 0, parity = (int)(step & 1);
     // (the step before has been recorded by now: its successor codes are in the trajectory)
