@@ -479,6 +479,18 @@ int32_t rl_mlp_create_layers(rl_engine *engine, uint32_t in_dim, const uint32_t 
  * modules run the per-layer kernels (also the 1 x <= 128 Relu shape the fused kernels would otherwise take). */
 int32_t rl_mlp_create_config(rl_engine *engine, uint32_t in_dim, const uint32_t *hidden_sizes, uint32_t n_hidden,
                              uint32_t out_dim, int32_t activation, int32_t output_activation, int32_t bias, rl_mlp **out);
+/* The same at in_dim up to 24 - the observation widths of the meta and PartitionGame lanes (rl_traj_create_wide and
+ * rl_traj_create_wide24 trajectories).  At in_dim <= 8 it builds what rl_mlp_create_config builds, bound and words.  At
+ * 9..24: 0..3 hidden layers of 1..256 units and out_dim 1 or 2 (anything else -> RL_ERR_BUILD_AGENT; out_dim 3..8 ->
+ * RL_ERR_UNSUPPORTED: the many-armed lanes' feed-forward policies are not built); flat parameters, initialisers,
+ * rl_params_get / _set and rl_mlp_forward as for any module of rl_mlp_create_config.  Such a module takes a trajectory of
+ * as many observation planes through rl_policy_gradient, rl_policy_fvp, rl_policy_loss_kl, rl_trpo_update, rl_ppo_update,
+ * rl_reinforce_update, rl_critic_gradient, rl_critic_update, rl_values_opt_update, rl_gae and rl_actor_critic_update
+ * (with _begin and _finish), and rl_rollout on RL_ENV_PARTITION lanes (on other lanes -> RL_ERR_UNSUPPORTED).  With bias
+ * vectors and one hidden layer of at most 64 units its update passes are single fused matrix-pipe launches
+ * (relearn_amd/csrc/kernels_wide_mfma.hip); other shapes run the per-layer kernels. */
+int32_t rl_mlp_create_wide(rl_engine *engine, uint32_t in_dim, const uint32_t *hidden_sizes, uint32_t n_hidden,
+                           uint32_t out_dim, int32_t activation, int32_t output_activation, int32_t bias, rl_mlp **out);
 int32_t rl_mlp_destroy(rl_mlp *mlp);
 int32_t rl_mlp_num_params(const rl_mlp *mlp, uint64_t *n);
 /* Linear::new Glorot-uniform init (ff/linear.rs:54-68) from the engine-defined stream ChaCha8(seed) */

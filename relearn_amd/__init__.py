@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "rl_cartpole_params_default", "rl_env_create", "rl_env_create_bandit", "rl_meta_bandit_config_default", "rl_env_create_meta_bandit", "rl_env_create_meta_bandit_wide", "rl_env_create_tabular_mdp", "rl_random_mdps_config_default", "rl_random_mdps_sample", "rl_meta_mdp_config_default", "rl_env_create_meta_mdp", "rl_env_create_meta_mdp_wide", "rl_env_create_partition", "rl_env_meta_mdp_read_tables", "rl_env_destroy", "rl_env_dims", "rl_env_reset",
     "rl_env_observe", "rl_env_step", "rl_env_upload_actions", "rl_env_step_resident", "rl_env_get_state",
     "rl_env_set_state",
-    "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
+    "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_create_wide", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
     "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_chain_config_default", "rl_rnn_chain_create", "rl_rnn_chain_create_wide", "rl_rnn_chain_create_wide20", "rl_rnn_chain_create_wide24", "rl_rnn_mlp_init_with", "rl_seq_forward",
     "rl_traj_create", "rl_traj_create_wide", "rl_traj_create_wide24", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write",
     "rl_rollout", "rl_gae",
@@ -945,6 +945,10 @@ class Mlp(_Handle):
         else:
             _check(lib().rl_mlp_create(engine.h, C.c_uint32(in_dim), C.c_uint32(hidden), C.c_uint32(out_dim),
                                        C.byref(self.h)), engine.h)
+        self._created(in_dim, hidden, out_dim)
+
+    def _created(self, in_dim, hidden, out_dim):
+        engine = self.eng
         _register(self)
         n = C.c_uint64()
         _check(lib().rl_mlp_num_params(self.h, C.byref(n)), engine.h)
@@ -997,6 +1001,24 @@ GruMlp.set_params = Mlp.set_params
 _TRAJ_DTYPES = {TRAJ_OBS: np.float32, TRAJ_ACTION: np.uint8, TRAJ_REWARD: np.float32, TRAJ_FLAG: np.uint8,
                 TRAJ_TERM_OBS: np.float32, TRAJ_VALUES: np.float32, TRAJ_ADVANTAGES: np.float32,
                 TRAJ_RETURNS: np.float32, TRAJ_TARGETS: np.float32}
+
+
+class MlpWide(Mlp):
+    """`MlpConfig.build_module(in, out)` at in_dim up to 24 (rl_mlp_create_wide): at in_dim <= 8 what `Mlp` builds from a
+    `hidden` list; at 9..24 a module of one or two outputs whose update passes run the fused wide matrix-pipe kernel
+    (bias vectors and one hidden layer of <= 64 units) or, at any other shape, the per-layer kernels."""
+
+    def __init__(self, engine, in_dim, hidden, out_dim, activation="Relu", output_activation="Identity", bias=True):
+        self.eng = engine
+        self.h = C.c_void_p()
+        self.activation, self.output_activation, self.bias = activation, output_activation, bias
+        hidden = list(hidden) if isinstance(hidden, (list, tuple)) else [hidden]
+        sizes = (C.c_uint32 * max(len(hidden), 1))(*hidden)
+        _check(lib().rl_mlp_create_wide(engine.h, C.c_uint32(in_dim), sizes, C.c_uint32(len(hidden)), C.c_uint32(out_dim),
+                                        C.c_int32(ACTIVATIONS.index(activation)),
+                                        C.c_int32(ACTIVATIONS.index(output_activation)), C.c_int32(1 if bias else 0),
+                                        C.byref(self.h)), engine.h)
+        self._created(in_dim, hidden, out_dim)
 
 
 class Trajectory(_Handle):

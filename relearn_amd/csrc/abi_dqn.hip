@@ -94,6 +94,8 @@ static void dqn_check_handles(const std::string &who, rl_env *env, rl_mlp *qnet,
   *out = nullptr;
   RL_REQUIRE(qnet->eng == env->eng && opt->eng == env->eng, who + "handles belong to different engines");
   RL_REQUIRE(opt->mod == qnet, who + "optimizer does not belong to the action-value module");
+  if (qnet->wide)  // (no lanes DQN collects on have more than eight features; by name, before any shape is compared)
+    throw RlError(RL_ERR_UNSUPPORTED, who + "DQN is not built for modules of rl_mlp_create_wide (more than 8 inputs)");
 }
 
 // The env table of the two-action constructors (relearn_hip.h): the collection kernels step CartPole lanes of 4 or 5

@@ -53,6 +53,15 @@ int32_t rl_mlp_create_layers(rl_engine *e, uint32_t in_dim, const uint32_t *hidd
   return rl_mlp_create_config(e, in_dim, hidden_sizes, n_hidden, out_dim, activation, output_activation, 1, out);
 }
 
+int32_t rl_mlp_create_wide(rl_engine *e, uint32_t in_dim, const uint32_t *hidden_sizes, uint32_t n_hidden, uint32_t out_dim,
+                           int32_t activation, int32_t output_activation, int32_t bias, rl_mlp **out) {
+  return guarded(e, [&] {
+    RL_REQUIRE(e && out && (hidden_sizes || n_hidden == 0), "NULL argument");
+    *out = nullptr;
+    module_build(e, wide_mlp_shape(in_dim, hidden_sizes, n_hidden, out_dim, activation, output_activation, bias != 0), out);
+  });
+}
+
 // Every recurrent constructor fills an rl_rnn_chain_config, names its limits (handle_spec.hpp, chain_shape) and ends here,
 // inside its guarded call.  An unknown cell or flag is refused before a NULL handle is, then the shape.
 static void chain_create(rl_engine *e, const rl_rnn_chain_config &cfg, const ChainLimits &lim, rl_mlp **out) {

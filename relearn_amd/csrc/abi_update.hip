@@ -86,7 +86,10 @@ SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
   // backward, and the slab rows of those two
   bool fused = false;
   if (traj->eng->kernel_variant == 0) {  // (1: the v1 reference kernels only)
-    if (row.fused == FUSED_POLICY)
+    if (mod->wide && row.fused != FUSED_NONE)  // (9 to 24 inputs: kernels_wide_mfma.hip, or the per-layer kernels)
+      fused = launch_wide_mfma(traj, mod, critic ? RL_GEN_CRITIC : (int)req.kind, req.tangent, Bt, req.skip, req.clip_lo,
+                               req.clip_hi);
+    else if (row.fused == FUSED_POLICY)
       fused = launch_policy_v2(traj, mod, req.kind, req.tangent, Bt, req.skip, req.clip_lo, req.clip_hi, req.keep);
     else if (row.fused == FUSED_CRITIC)
       fused = launch_critic_step_v2(traj, mod, Bt);

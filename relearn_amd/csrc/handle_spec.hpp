@@ -502,6 +502,9 @@ struct ModuleShape {
   uint32_t n_hidden = 1;
   uint32_t widths[RL_MLP_MAX_HIDDEN] = {0, 0, 0, 0};
   bool general = false;
+  // a general module of rl_mlp_create_wide above RL_TRAJ_MAX_OBS_DIM inputs (9 to 24: wide_mlp_shape): its update passes
+  // run the fused kernels of kernels_wide_mfma.hip where they fit, and rl_rollout takes it on PartitionGame lanes
+  bool wide = false;
   // MlpConfig::activation / output_activation (rl_activation); the fused kernels are built for Relu / Identity
   int act = 1, out_act = 0;
   // layer l (0 .. n_hidden; the last one is the output layer): fan-in, fan-out, offset of its kernel in the flat
@@ -575,6 +578,28 @@ inline ModuleShape mlp_shape(uint32_t in_dim, const uint32_t *hidden_sizes, uint
   m.act = activation;
   m.out_act = output_activation;
   m.has_bias = has_bias;
+  m.P = m.layer_offset(m.n_layers());
+  return m;
+}
+
+// rl_mlp_create_wide: at in_dim <= 8 it is rl_mlp_create_layers / _config, bound and words; at 9 to 24 inputs a general
+// module with the `wide` mark, of one or two outputs (a policy over the two classifications of the PartitionGame lanes,
+// a critic) — more are the many-armed meta lanes' policies, not built
+inline ModuleShape wide_mlp_shape(uint32_t in_dim, const uint32_t *hidden_sizes, uint32_t n_hidden, uint32_t out_dim,
+                                  int32_t activation, int32_t output_activation, bool has_bias) {
+  if (in_dim <= RL_TRAJ_MAX_OBS_DIM)
+    return mlp_shape(in_dim, hidden_sizes, n_hidden, out_dim, activation, output_activation, has_bias);
+  bool ok = in_dim <= RL_PARTITION_MAX_OBS_DIM && out_dim >= 1 && out_dim <= RL_MLP_MAX_OUT && n_hidden <= 3;
+  for (uint32_t l = 0; ok && l < n_hidden; ++l) ok = hidden_sizes[l] >= 1 && hidden_sizes[l] <= RL_MLP_MAX_WIDTH;
+  if (!ok)
+    throw RlError(RL_ERR_BUILD_AGENT, "rl_mlp_create_wide: in_dim 1..24, above 8 inputs at most 3 hidden layers of 1..256 "
+                                      "units and out_dim in {1,2}");
+  if (out_dim > 2)
+    throw RlError(RL_ERR_UNSUPPORTED, "rl_mlp_create_wide: modules of more than 8 inputs are built for one or two outputs");
+  // (the general module of eight inputs — no fused shape has eight — with its activation checks, then what differs)
+  ModuleShape m = mlp_shape(RL_TRAJ_MAX_OBS_DIM, hidden_sizes, n_hidden, out_dim, activation, output_activation, has_bias);
+  m.in_dim = in_dim;
+  m.wide = true;
   m.P = m.layer_offset(m.n_layers());
   return m;
 }
@@ -880,11 +905,16 @@ inline void rollout_check_shapes(uint32_t D, uint32_t A, const ModuleShape &m) {
 }
 
 // ... and before either: PartitionGame lanes have 23 or 24 features and a feed-forward module at most eight inputs, so no
-// such pair matches; it is refused by name, before a shape is compared (rl_rollout tests this first of all)
+// such pair matches; it is refused by name, before a shape is compared (rl_rollout tests this first of all).  A wide
+// module (rl_mlp_create_wide, 9 to 24 inputs) is taken: ROLL_GENERAL, like every general module
 inline void rollout_check_env_kind(int env_kind, const ModuleShape &m) {
-  if (env_kind == RL_ENV_PARTITION && !rl_module_is_recurrent(m.kind))
+  if (env_kind == RL_ENV_PARTITION && !rl_module_is_recurrent(m.kind) && !m.wide)
     throw RlError(RL_ERR_UNSUPPORTED, "rl_rollout: feed-forward modules are not built for RL_ENV_PARTITION lanes (a "
                                       "recurrent chain of rl_rnn_chain_create_wide24 is)");
+  // (the other lanes' feed-forward policies are not built: out of the wide constructor's scope, by name)
+  if (m.wide && env_kind != RL_ENV_PARTITION)
+    throw RlError(RL_ERR_UNSUPPORTED, "rl_rollout: a module of rl_mlp_create_wide (more than 8 inputs) is built for "
+                                      "RL_ENV_PARTITION lanes");
 }
 
 inline RolloutPath rollout_path(int env_kind, uint32_t D, uint32_t A, uint32_t chain_size, const ModuleShape &m) {

@@ -451,8 +451,10 @@ struct MlpConfig {  // MlpConfig { hidden_sizes, activation, output_activation, 
   }
   std::unique_ptr<Module> build_module(Engine &eng, uint32_t in_dim, uint32_t out_dim, uint64_t seed) const {
     rl_mlp *h = nullptr;
-    check(rl_mlp_create_config(eng.handle(), in_dim, hidden_sizes.data(), (uint32_t)hidden_sizes.size(), out_dim,
-                               (int32_t)activation, (int32_t)output_activation, linear_config.bias_init ? 1 : 0, &h),
+    // (more than eight inputs — the feed-forward baseline of the partition-game experiment, 24 features: the wide constructor)
+    check((in_dim > 8 ? rl_mlp_create_wide : rl_mlp_create_config)(
+              eng.handle(), in_dim, hidden_sizes.data(), (uint32_t)hidden_sizes.size(), out_dim, (int32_t)activation,
+              (int32_t)output_activation, linear_config.bias_init ? 1 : 0, &h),
           eng.handle());
     std::unique_ptr<Module> m(new Module(eng, h));
     check(rl_mlp_init_with(h, seed, &linear_config.kernel_init.raw,

@@ -181,6 +181,11 @@ constexpr int RL_GEN_CRITIC = 100;  // mode: mean((V - target)^2); else PASS_INI
 bool gen_mfma_fits(const rl_traj *t, const rl_mlp *m);
 bool launch_gen_mfma(rl_traj *t, const rl_mlp *m, int mode, const float *d_tangent, uint64_t B_total,
                      const int32_t *d_skip, float clip_lo, float clip_hi);
+// kernels_wide_mfma.hip: the same passes of a wide module (rl_mlp_create_wide, 9 to 24 inputs: ModuleShape::wide), layer
+// 0 as two k-steps over 32 padded input rows (false: shape not built — the per-layer kernels take it)
+bool wide_mfma_fits(const rl_traj *t, const rl_mlp *m);
+bool launch_wide_mfma(rl_traj *t, const rl_mlp *m, int mode, const float *d_tangent, uint64_t B_total,
+                      const int32_t *d_skip, float clip_lo, float clip_hi);
 const float *launch_gen_values(rl_traj *t, const rl_mlp *critic);  // -> seq.out / seq.succ (plane 0); returns V(obs[T]) [n]
 void launch_gen_rollout(rl_env *env, const rl_mlp *policy, rl_traj *t);
 void launch_rollout_stepwise(rl_env *env, rl_traj *t, const float *z, const std::function<void(uint32_t)> &forward);

@@ -4,13 +4,15 @@
 as policy (two outputs) and as critic (one), TRPO at its default max KL, the critic fitted with 80 Adam steps per period on
 reward-to-go targets, GAE with lambda 0.95, discount factor min(0.999, 0.99) — on `--lanes` lanes of `--horizon` steps per
 period (the reference collects at least 5,000 steps per worker thread; 256 lanes x 128 steps are 32,768).
+`--model mlp` is the memory-free baseline: `MlpConfig { hidden_sizes: [hidden] }` as policy and as critic (ra.MlpWide), what
+can be learned from the previous element and its label alone.
 
 Per period one JSON line: the device-side StepsSummary of the period (src/simulation/summary.rs) — mean step reward, and the
 episodes that ended in it with their mean reward and length — the update's statistics and the wall-clock times of the
 rollout and of the update.  A uniform-random policy's expected step reward is 0 by construction (either label is as
 likely as the other, whatever the axis); +1 is a policy that has found the axis, which takes the feedback of several steps.
 
-    python scripts/partition_game.py [--lanes 256] [--horizon 128] [--periods 20] [--max-steps 1000] [--hidden 128]
+    python scripts/partition_game.py [--lanes 256] [--horizon 128] [--periods 20] [--max-steps 1000] [--hidden 128] [--model gru|mlp]
         [--critic-steps 80] [--seed 0] [--json out.json] [--timing-json out.json]
 """
 import argparse
@@ -32,6 +34,7 @@ def main():
     ap.add_argument("--periods", type=int, default=20)
     ap.add_argument("--max-steps", type=int, default=1000, help="VisibleStepLimit::new(max_steps)")
     ap.add_argument("--hidden", type=int, default=128)
+    ap.add_argument("--model", choices=["gru", "mlp"], default="gru", help="GruMlpConfig (the experiment's) or MlpConfig")
     ap.add_argument("--critic-steps", type=int, default=80)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json", default=None, help="also write all lines to this file as one JSON list")
@@ -40,8 +43,11 @@ def main():
 
     eng = ra.Engine(0)
     env = ra.PartitionEnv(eng, a.lanes, max_steps=a.max_steps, limit=ra.LIMIT_VISIBLE, seed_env=a.seed, seed_actor=a.seed + 1)
-    pol = ra.RnnChainWide24(eng, "gru", env.D, a.hidden, env.A, mlp_hidden=a.hidden)
-    cri = ra.RnnChainWide24(eng, "gru", env.D, a.hidden, 1, mlp_hidden=a.hidden)
+    if a.model == "mlp":
+        pol, cri = ra.MlpWide(eng, env.D, [a.hidden], env.A), ra.MlpWide(eng, env.D, [a.hidden], 1)
+    else:
+        pol = ra.RnnChainWide24(eng, "gru", env.D, a.hidden, env.A, mlp_hidden=a.hidden)
+        cri = ra.RnnChainWide24(eng, "gru", env.D, a.hidden, 1, mlp_hidden=a.hidden)
     pol.init(a.seed + 2)  # input weights Uniform(FanAvg), hidden weights Orthogonal, biases Zeros; LinearConfig::default
     cri.init(a.seed + 3)
     opt = ra.Adam(cri)
@@ -66,7 +72,7 @@ def main():
         summary.clear()
         summary.push(traj)
         s = summary.read()
-        line = {"period": period, "lanes": a.lanes, "horizon": a.horizon, "max_steps": a.max_steps, "hidden": a.hidden,
+        line = {"period": period, "model": a.model, "lanes": a.lanes, "horizon": a.horizon, "max_steps": a.max_steps, "hidden": a.hidden,
                 "steps": s.step_reward.count, "mean_step_reward": s.step_reward.mean,
                 "uniform_random_step_reward": 0.0,
                 "episodes": s.episode_reward.count,
