@@ -1,6 +1,7 @@
-// env_lanes.hpp — one env per lane, device code only: the lane state of every env kind, the `Env` policy structs the
-// kernels are written over, the one statement of "step a lane and record it" (lane_step), the sinks a record goes to,
-// and word `w` of a lane's ChaCha stream (stream_word, LaneActorRng).  DESIGN.md §25 lists who calls what.
+// env_lanes.hpp — one env per lane, device code but for the last section: the lane state of every env kind, the `Env`
+// policy structs the kernels are written over, the one statement of "step a lane and record it" (lane_step), the sinks a
+// record goes to, and word `w` of a lane's ChaCha stream (stream_word, LaneActorRng).  DESIGN.md §25 lists who calls what.
+// Last, for the launchers: the ops struct of each lane family and env_dispatch.
 //
 // Adding an env to a kernel is one ops struct here and one instantiation there.  An ops struct gives
 //   State                              the lane's registers
@@ -18,6 +19,7 @@
 #include "../../include/rl_detmath.h"
 #include "../../include/rl_normal.h"
 #include "engine.hpp"
+#include "env_shape.hpp"
 
 // ---------------------------------------------------------------- word `w` of a lane's ChaCha stream
 // uncached: the block is recomputed on every call (kernels that take one word per launch or per step of a tile)
@@ -914,3 +916,28 @@ struct EnvBufSink {
     for (int d = 0; d < D; ++d) term_obs[(size_t)d * n + i] = f[d];
   }
 };
+
+// ---------------------------------------------------------------- host side: an env's kernels, picked once
+// the ops struct of a lane family (EnvLanes and the feature counts each family is built for: handle_spec.hpp)
+template <EnvLanes>
+struct LaneOps;
+template <> struct LaneOps<LANES_CARTPOLE> { using type = CartPoleOps; };
+template <> struct LaneOps<LANES_INDEX> { using type = IndexOps; };
+template <> struct LaneOps<LANES_META_BANDIT> { using type = MetaOps; };
+template <> struct LaneOps<LANES_META_MDP> { using type = MetaMdpOps; };
+template <> struct LaneOps<LANES_META_MDP_WIDE> { using type = MetaMdpWideOps; };
+template <> struct LaneOps<LANES_PARTITION> { using type = PartitionOps; };
+template <> struct LaneOps<LANES_TABULAR_MDP> { using type = MdpOps; };
+
+// go(Ops{}): the ops struct of the env's lanes
+template <class Go>
+static void env_lanes_dispatch(const rl_env *env, Go &&go) {
+  with_env_lanes(env->kind, env->dev.mm.states,
+                 [&](auto lanes) { go(typename LaneOps<(EnvLanes)decltype(lanes)::value>::type{}); });
+}
+// go(Ops{}, Int<D>{}): ... and the env's feature count, inside the family's range (ENV_LANE_FEATURES) or refused
+template <class Go>
+static void env_dispatch(const rl_env *env, Go &&go) {
+  with_env_shape(env->kind, env->dev.mm.states, env->D,
+                 [&](auto lanes, auto d) { go(typename LaneOps<(EnvLanes)decltype(lanes)::value>::type{}, d); });
+}

@@ -442,7 +442,7 @@ struct MetaMdpShape {
   uint32_t S, A;
 };
 constexpr MetaMdpShape META_MDP_FUSED_SHAPES[] = {{2, 2}, {3, 2}, {4, 3}, {5, 5}, {8, 4}, {4, 8}};
-inline bool meta_mdp_fused_shape(uint32_t S, uint32_t A) {
+constexpr bool meta_mdp_fused_shape(uint32_t S, uint32_t A) {
   for (const MetaMdpShape &m : META_MDP_FUSED_SHAPES)
     if (m.S == S && m.A == A) return true;
   return false;
@@ -450,10 +450,53 @@ inline bool meta_mdp_fused_shape(uint32_t S, uint32_t A) {
 // ... and of the lanes of rl_env_create_meta_mdp_wide above eight states (k_stack_rollout<.., MetaMdpWideOps, ..>): the
 // reference's default size alone
 constexpr MetaMdpShape META_MDP_WIDE_FUSED_SHAPES[] = {{10, 5}};
-inline bool meta_mdp_wide_fused_shape(uint32_t S, uint32_t A) {
+constexpr bool meta_mdp_wide_fused_shape(uint32_t S, uint32_t A) {
   for (const MetaMdpShape &m : META_MDP_WIDE_FUSED_SHAPES)
     if (m.S == S && m.A == A) return true;
   return false;
+}
+
+// ---------------------------------------------------------------- lane families: which env kernels an env runs
+// The env kernels are built per (ops struct of env_lanes.hpp, feature count D).  A lane family is the set of envs that
+// share an ops struct (LaneOps, env_lanes.hpp); ENV_LANE_FEATURES is the one statement of the feature counts each family
+// is built for, and of the words a count outside them is refused with.  env_dispatch (env_lanes.hpp) and every launcher
+// that picks an env kernel go through with_env_shape (env_shape.hpp).
+enum EnvLanes {
+  LANES_CARTPOLE = 0,
+  LANES_INDEX,          // Chain, bandit: 5 or 6 features; MemoryGame: num_actions + history_len [+ 1]
+  LANES_META_BANDIT,    // arms + 4, 2..12 arms (above four: rl_env_create_meta_bandit_wide)
+  LANES_META_MDP,       // S + A + 4 up to eight states: at most 16, through rl_env_create_meta_mdp_wide 20
+  LANES_META_MDP_WIDE,  // rl_env_create_meta_mdp_wide at nine or ten states (rows of sixteen floats): 9 x 2 .. 10 x 6
+  LANES_PARTITION,      // 23, 24 under a visible limit
+  LANES_TABULAR_MDP,    // states [+ 1], 2..8 states
+  ENV_LANES_COUNT
+};
+struct LaneFeatures {
+  int lo, hi;
+  const char *refusal;
+};
+constexpr LaneFeatures ENV_LANE_FEATURES[ENV_LANES_COUNT] = {
+    {4, 5, "CartPole lanes: 4 or 5 observation features"},
+    {4, 8, "index env lanes: 4..8 observation features"},
+    {6, 16, "meta-bandit lanes: 6..16 observation features"},
+    {8, 20, "meta-MDP lanes: 8..20 observation features"},
+    {15, 20, "meta-MDP lanes of nine or ten states: 15..20 observation features"},
+    {23, 24, "PartitionGame lanes: 23 or 24 observation features"},
+    {2, 8, "tabular-MDP lanes: 2..8 observation features"},
+};
+// (`meta_mdp_states` is read for RL_ENV_META_MDP alone; a kind nobody knows never runs another family's kernels)
+inline EnvLanes env_lanes_of(int kind, uint32_t meta_mdp_states) {
+  switch (kind) {
+    case RL_ENV_CARTPOLE: return LANES_CARTPOLE;
+    case RL_ENV_CHAIN:
+    case RL_ENV_MEMORY:
+    case RL_ENV_BANDIT: return LANES_INDEX;
+    case RL_ENV_META_BANDIT: return LANES_META_BANDIT;
+    case RL_ENV_META_MDP: return meta_mdp_states > RL_META_MDP_MAX ? LANES_META_MDP_WIDE : LANES_META_MDP;
+    case RL_ENV_PARTITION: return LANES_PARTITION;
+    case RL_ENV_TABULAR_MDP: return LANES_TABULAR_MDP;
+    default: throw RlError(RL_ERR_UNSUPPORTED, "env kernels: unknown env kind");
+  }
 }
 
 // ---------------------------------------------------------------- modules

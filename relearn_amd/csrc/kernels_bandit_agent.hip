@@ -270,39 +270,21 @@ __global__ void __launch_bounds__(BA_BLOCK) k_meta_agent_rollout(CartPoleDev c, 
   ag.pos[i] = pos;
 }
 
-template <int KIND>
-void launch_kind(rl_bandit_agent *agent, rl_env *env, rl_traj *traj) {
-  const dim3 grid((traj->d.n + BA_BLOCK - 1) / BA_BLOCK), blk(BA_BLOCK);
-#define ROLLOUT(D)                                                                                              \
-  hipLaunchKernelGGL((k_meta_agent_rollout<KIND, D>), grid, blk, 0, env->eng->stream, env->dev, env->st, traj->d, \
-                     agent->d, env->t_global)
-  switch (env->D) {
-    case 6: ROLLOUT(6); break;
-    case 7: ROLLOUT(7); break;
-    case 8: ROLLOUT(8); break;
-    case 9: ROLLOUT(9); break;  // 5..12 arms: rl_env_create_meta_bandit_wide
-    case 10: ROLLOUT(10); break;
-    case 11: ROLLOUT(11); break;
-    case 12: ROLLOUT(12); break;
-    case 13: ROLLOUT(13); break;
-    case 14: ROLLOUT(14); break;
-    case 15: ROLLOUT(15); break;
-    case 16: ROLLOUT(16); break;
-    default: throw RlError(RL_ERR_UNSUPPORTED, "rl_bandit_agent_rollout: built for 2..12 arms (6..16 features)");
-  }
-#undef ROLLOUT
-}
-
 }  // namespace
 
 void launch_bandit_agent_rollout(rl_bandit_agent *agent, rl_env *env, rl_traj *traj) {
   ProfScope ps(env->eng, RL_K_ROLLOUT);
-  switch (agent->cfg.kind) {
-    case RL_BANDIT_AGENT_RANDOM: launch_kind<RL_BANDIT_AGENT_RANDOM>(agent, env, traj); break;
-    case RL_BANDIT_AGENT_TABULAR_Q: launch_kind<RL_BANDIT_AGENT_TABULAR_Q>(agent, env, traj); break;
-    case RL_BANDIT_AGENT_THOMPSON: launch_kind<RL_BANDIT_AGENT_THOMPSON>(agent, env, traj); break;
-    default: launch_kind<RL_BANDIT_AGENT_UCB1>(agent, env, traj); break;
-  }
+  const dim3 grid((traj->d.n + BA_BLOCK - 1) / BA_BLOCK), blk(BA_BLOCK);
+  constexpr LaneFeatures F = ENV_LANE_FEATURES[LANES_META_BANDIT];  // arms + 4 (5..12 arms: rl_env_create_meta_bandit_wide)
+  const bool known = with_one_of<RL_BANDIT_AGENT_RANDOM, RL_BANDIT_AGENT_TABULAR_Q, RL_BANDIT_AGENT_THOMPSON,
+                                 RL_BANDIT_AGENT_UCB1>(agent->cfg.kind, [&](auto kind) {
+    if (!with_range<F.lo, F.hi>(env->D, [&](auto d) {
+          hipLaunchKernelGGL((k_meta_agent_rollout<decltype(kind)::value, decltype(d)::value>), grid, blk, 0,
+                             env->eng->stream, env->dev, env->st, traj->d, agent->d, env->t_global);
+        }))
+      throw RlError(RL_ERR_UNSUPPORTED, "rl_bandit_agent_rollout: built for 2..12 arms (6..16 features)");
+  });
+  if (!known) throw RlError(RL_ERR_UNSUPPORTED, "launch_bandit_agent_rollout: unknown agent kind");
   RL_HIP_CHECK(hipGetLastError());
   env->t_global += traj->d.T;
 }

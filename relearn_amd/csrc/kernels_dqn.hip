@@ -623,73 +623,17 @@ void launch_dqn_sample(rl_engine *eng, hipStream_t stream, const ReplayDev &rp, 
 
 static inline uint32_t cdiv_d(size_t a, size_t b) { return (uint32_t)((a + b - 1) / b); }
 
-// The collection kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature count
-// as types, as env_dispatch does for the standalone env kernels (kernels_rollout.hip).  CartPole lanes have 4 or 5
-// features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame(2, h): 2 + h [+ 1]) 4..`MAX_D`.
-template <int D>
-using FeatureCount = std::integral_constant<int, D>;
-template <int MAX_D, class Go>
-static void dqn_env_dispatch(const rl_env *env, const char *what, Go &&go) {
-  if (env->kind == RL_ENV_TABULAR_MDP) {  // states [+ 1] = 2..8 features; the step-wise collection alone
-    if constexpr (MAX_D >= 8) {
-      switch (env->D) {
-        case 2: go(MdpOps{}, FeatureCount<2>{}); return;
-        case 3: go(MdpOps{}, FeatureCount<3>{}); return;
-        case 4: go(MdpOps{}, FeatureCount<4>{}); return;
-        case 5: go(MdpOps{}, FeatureCount<5>{}); return;
-        case 6: go(MdpOps{}, FeatureCount<6>{}); return;
-        case 7: go(MdpOps{}, FeatureCount<7>{}); return;
-        case 8: go(MdpOps{}, FeatureCount<8>{}); return;
-      }
-    }
-    throw RlError(RL_ERR_UNSUPPORTED, what);
-  }
-  const bool cartpole = env->kind == RL_ENV_CARTPOLE;
-  // (meta lanes and any kind this function does not know are never collected by the index lanes' code)
-  if (!cartpole && env->kind != RL_ENV_CHAIN && env->kind != RL_ENV_MEMORY && env->kind != RL_ENV_BANDIT)
-    throw RlError(RL_ERR_UNSUPPORTED, what);
-  if (env->D < 4 || env->D > (cartpole ? 5u : (uint32_t)MAX_D)) throw RlError(RL_ERR_UNSUPPORTED, what);
-  if (cartpole) {
-    if (env->D == 5) go(CartPoleOps{}, FeatureCount<5>{});
-    else go(CartPoleOps{}, FeatureCount<4>{});
-    return;
-  }
-  switch (env->D) {
-    case 4: go(IndexOps{}, FeatureCount<4>{}); break;
-    case 5: go(IndexOps{}, FeatureCount<5>{}); break;
-    case 6: if constexpr (MAX_D >= 6) go(IndexOps{}, FeatureCount<6>{}); break;
-    case 7: if constexpr (MAX_D >= 7) go(IndexOps{}, FeatureCount<7>{}); break;
-    default: if constexpr (MAX_D >= 8) go(IndexOps{}, FeatureCount<8>{}); break;
-  }
-}
-// ... and the kernels that read the store per feature count alone
+// The collection kernels are built per (ops struct, D) through env_dispatch (env_lanes.hpp), each launcher for the
+// families and feature counts its `if constexpr` names.  The kernels that read the store are built per feature count alone
+// (2 and 3: tabular-MDP lanes of two or three features) ...
 template <class Go>
 static void dqn_features_dispatch(uint32_t D, Go &&go) {
-  switch (D) {
-    case 2: go(FeatureCount<2>{}); break;  // (2 and 3: tabular-MDP lanes of two or three features)
-    case 3: go(FeatureCount<3>{}); break;
-    case 4: go(FeatureCount<4>{}); break;
-    case 5: go(FeatureCount<5>{}); break;
-    case 6: go(FeatureCount<6>{}); break;
-    case 7: go(FeatureCount<7>{}); break;
-    case 8: go(FeatureCount<8>{}); break;
-    default: throw RlError(RL_ERR_UNSUPPORTED, "DQN replay store: 2..8 observation features");
-  }
+  if (!with_range<2, 8>(D, go)) throw RlError(RL_ERR_UNSUPPORTED, "DQN replay store: 2..8 observation features");
 }
-
-// ... and the kernels built per action count (FiniteSpace of 2..8 actions: rl_dqn_create_finite)
+// ... and others per action count (FiniteSpace of 2..8 actions: rl_dqn_create_finite)
 template <class Go>
 static void dqn_actions_dispatch(uint32_t A, Go &&go) {
-  switch (A) {
-    case 2: go(std::integral_constant<int, 2>{}); break;
-    case 3: go(std::integral_constant<int, 3>{}); break;
-    case 4: go(std::integral_constant<int, 4>{}); break;
-    case 5: go(std::integral_constant<int, 5>{}); break;
-    case 6: go(std::integral_constant<int, 6>{}); break;
-    case 7: go(std::integral_constant<int, 7>{}); break;
-    case 8: go(std::integral_constant<int, 8>{}); break;
-    default: throw RlError(RL_ERR_UNSUPPORTED, "DQN kernels: 2..8 actions");
-  }
+  if (!with_range<2, 8>(A, go)) throw RlError(RL_ERR_UNSUPPORTED, "DQN kernels: 2..8 actions");
 }
 
 void launch_rollout_dqn(rl_env *env, const rl_mlp *qnet, const ReplayDev &rp, uint32_t T, uint64_t p_int,
@@ -701,21 +645,21 @@ void launch_rollout_dqn(rl_env *env, const rl_mlp *qnet, const ReplayDev &rp, ui
   int G = 1;
   while (!always_explore && G < 16 && n * (uint64_t)(2 * G) <= simds * 64) G *= 2;
   if (env->eng->kernel_variant == 1) G = 1;
-  dqn_env_dispatch<5>(env, "fused DQN collection: 4 or 5 observation features", [&](auto ops, auto d) {
+  // CartPole and index-env lanes (Chain, bandit: 5; MemoryGame(2, h): 2 + h [+ 1]) of 4 or 5 features
+  env_dispatch(env, [&](auto ops, auto d) {
     using Env = decltype(ops);
     constexpr int D = decltype(d)::value, BLOCK = 64;
-#define ROLLOUT_DQN(GG)                                                                                                 \
-  hipLaunchKernelGGL((k_rollout_dqn<Env, D, BLOCK, GG>), dim3(cdiv_d((size_t)n * GG, BLOCK)), dim3(BLOCK), 0,          \
-                     env->eng->stream, env->dev, env->st, rp, qnet->d_params, (int)qnet->hidden, T, p_int,             \
-                     always_explore, d_flags, d_range, env->t_global)
-    switch (G) {
-      case 16: ROLLOUT_DQN(16); break;
-      case 8: ROLLOUT_DQN(8); break;
-      case 4: ROLLOUT_DQN(4); break;
-      case 2: ROLLOUT_DQN(2); break;
-      default: ROLLOUT_DQN(1); break;
+    if constexpr ((std::is_same_v<Env, CartPoleOps> || std::is_same_v<Env, IndexOps>) && D <= 5) {
+      const bool built = with_one_of<1, 2, 4, 8, 16>(G, [&](auto g) {
+        constexpr int GG = decltype(g)::value;
+        hipLaunchKernelGGL((k_rollout_dqn<Env, D, BLOCK, GG>), dim3(cdiv_d((size_t)n * GG, BLOCK)), dim3(BLOCK), 0,
+                           env->eng->stream, env->dev, env->st, rp, qnet->d_params, (int)qnet->hidden, T, p_int,
+                           always_explore, d_flags, d_range, env->t_global);
+      });
+      if (!built) throw RlError(RL_ERR_UNSUPPORTED, "launch_rollout_dqn: 1, 2, 4, 8 or 16 threads per lane");
+    } else {
+      throw RlError(RL_ERR_UNSUPPORTED, "fused DQN collection: 4 or 5 observation features");
     }
-#undef ROLLOUT_DQN
   });
   RL_HIP_CHECK(hipGetLastError());
 }
@@ -730,25 +674,23 @@ void launch_rollout_dqn_general(rl_env *env, const rl_mlp *qnet, rl_traj *ws, fl
       launch_env_observe(env, env->d_obs);                          // [D][n]
       launch_gen_forward(ws, qnet, env->d_obs, (size_t)n, n, d_q);  // [A][n]
     }
-    dqn_env_dispatch<8>(env, "step-wise DQN collection: 4..8 observation features", [&](auto ops, auto d) {
+    // CartPole lanes, index-env lanes of 4..8 features, tabular-MDP lanes of 2..8
+    env_dispatch(env, [&](auto ops, auto d) {
       using Env = decltype(ops);
       constexpr int D = decltype(d)::value;
-      // more than two actions: the index-env lanes (MemoryGame(k >= 3, h), the bandit of 3..8 arms) and tabular MDPs
-      if constexpr (std::is_same<Env, IndexOps>::value || std::is_same<Env, MdpOps>::value) {
-        if (env->A > 2) {
-          dqn_actions_dispatch(env->A, [&](auto na) {
-            constexpr int A = decltype(na)::value;
-            if constexpr (A > 2)
-              hipLaunchKernelGGL((k_dqn_lane_step<Env, D, BLOCK, A>), dim3(cdiv_d(n, BLOCK)), dim3(BLOCK), 0,
-                                 env->eng->stream, env->dev, env->st, rp, d_q, p_int, always_explore, t + 1 == T ? 1 : 0,
-                                 d_flags + (size_t)t * n, env->t_global + t);
-          });
-          return;
-        }
+      constexpr bool many_actions = std::is_same_v<Env, IndexOps> || std::is_same_v<Env, MdpOps>;
+      if constexpr (!std::is_same_v<Env, CartPoleOps> && !many_actions) {
+        throw RlError(RL_ERR_UNSUPPORTED, "step-wise DQN collection: 4..8 observation features");
+      } else {
+        // more than two actions: the index-env lanes (MemoryGame(k >= 3, h), the bandit of 3..8 arms) and tabular MDPs
+        dqn_actions_dispatch(many_actions ? env->A : 2, [&](auto na) {
+          constexpr int A = decltype(na)::value;
+          if constexpr (A == 2 || many_actions)
+            hipLaunchKernelGGL((k_dqn_lane_step<Env, D, BLOCK, A>), dim3(cdiv_d(n, BLOCK)), dim3(BLOCK), 0,
+                               env->eng->stream, env->dev, env->st, rp, d_q, p_int, always_explore, t + 1 == T ? 1 : 0,
+                               d_flags + (size_t)t * n, env->t_global + t);
+        });
       }
-      hipLaunchKernelGGL((k_dqn_lane_step<Env, D, BLOCK, 2>), dim3(cdiv_d(n, BLOCK)), dim3(BLOCK), 0, env->eng->stream,
-                         env->dev, env->st, rp, d_q, p_int, always_explore, t + 1 == T ? 1 : 0, d_flags + (size_t)t * n,
-                         env->t_global + t);
     });
   }
   RL_HIP_CHECK(hipGetLastError());

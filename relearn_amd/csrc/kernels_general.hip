@@ -718,29 +718,14 @@ void launch_gen_policy_pass(rl_traj *t, const rl_mlp *m, int mode, const float *
   float inv_B = 1.0f / (float)B_total;
   if (mode == PASS_DQN) inv_B = 2.0f / (float)B_total;
   dim3 grid(t->nbB), blk(256);
-#define TERMS(MM, AA)                                                                                                \
-  hipLaunchKernelGGL((k_gen_policy_terms<MM, AA>), grid, blk, 0, t->eng->stream, t->d, g.z, g.tz, t->lp0, t->dz, t->slabB, \
-                     inv_B, d_skip, clip_lo, clip_hi)
-#define TERMS_A(AA)                                  \
-  case AA:                                           \
-    if (mode == PASS_INIT) TERMS(PASS_INIT, AA);     \
-    else if (mode == PASS_EVAL) TERMS(PASS_EVAL, AA); \
-    else if (mode == PASS_PPO) TERMS(PASS_PPO, AA);  \
-    else if (mode == PASS_DQN) TERMS(PASS_DQN, AA);  \
-    else TERMS(PASS_JVP, AA);                        \
-    break
-  switch (m->out_dim) {
-    TERMS_A(2);
-    TERMS_A(3);
-    TERMS_A(4);
-    TERMS_A(5);
-    TERMS_A(6);
-    TERMS_A(7);
-    TERMS_A(8);
-    default: throw RlError(RL_ERR_UNSUPPORTED, "policy pass: policies and action values over 2..8 actions are built");
-  }
-#undef TERMS_A
-#undef TERMS
+  bool built = false;
+  with_range<PASS_INIT, PASS_PPO>(mode, [&](auto mm) {  // (every mode of PolicyPassMode)
+    built = with_range<2, (int)RL_MLP_MAX_OUT>(m->out_dim, [&](auto aa) {
+      hipLaunchKernelGGL((k_gen_policy_terms<decltype(mm)::value, decltype(aa)::value>), grid, blk, 0, t->eng->stream, t->d,
+                         g.z, g.tz, t->lp0, t->dz, t->slabB, inv_B, d_skip, clip_lo, clip_hi);
+    });
+  });
+  if (!built) throw RlError(RL_ERR_UNSUPPORTED, "policy pass: policies and action values over 2..8 actions are built");
   RL_HIP_CHECK(hipGetLastError());
   if (m->out_act != RL_ACT_IDENTITY && mode != PASS_EVAL) {
     // the loss terms above are functions of the module's OUTPUTS: one more factor back to the output layer's
@@ -871,12 +856,11 @@ void launch_rollout_stepwise(rl_env *env, rl_traj *t, const float *z, const std:
     hipLaunchKernelGGL(k_gen_record_obs, grid, blk, 0, e->stream, t->d, env->d_obs, 0u);
     for (uint32_t step = 0; step < T; ++step) {
       forward(step);
-      if (env->D == 5)
-        hipLaunchKernelGGL(k_gen_step_cartpole<5>, grid, blk, 0, e->stream, env->dev, env->st, t->d, z, env->t_global,
-                           step, env->d_obs);
-      else
-        hipLaunchKernelGGL(k_gen_step_cartpole<4>, grid, blk, 0, e->stream, env->dev, env->st, t->d, z, env->t_global,
-                           step, env->d_obs);
+      if (!with_one_of<4, 5>(env->D, [&](auto d) {
+            hipLaunchKernelGGL(k_gen_step_cartpole<decltype(d)::value>, grid, blk, 0, e->stream, env->dev, env->st, t->d, z,
+                               env->t_global, step, env->d_obs);
+          }))
+        throw RlError(RL_ERR_UNSUPPORTED, "launch_rollout_stepwise: CartPole lanes of 4 or 5 features");
       env->t_global += 1;
     }
     RL_HIP_CHECK(hipGetLastError());
@@ -885,25 +869,12 @@ void launch_rollout_stepwise(rl_env *env, rl_traj *t, const float *z, const std:
   for (uint32_t step = 0; step < T; ++step) {
     hipLaunchKernelGGL(k_gen_record_obs, grid, blk, 0, e->stream, t->d, env->d_obs, step);
     forward(step);
-    switch (env->A) {
-#define SAMPLE(AA)                                                                                                      \
-  case AA:                                                                                                              \
-    hipLaunchKernelGGL(k_gen_sample_actions<AA>, grid, blk, 0, e->stream, env->dev, z, n, env->t_global, env->d_actions); \
-    break
-      SAMPLE(2);
-      SAMPLE(3);
-      SAMPLE(4);
-      SAMPLE(5);
-      SAMPLE(6);
-      SAMPLE(7);
-      SAMPLE(8);
-      SAMPLE(9);  // 9..12: the wide meta-bandit lanes (rl_env_create_meta_bandit_wide) under a recurrent chain
-      SAMPLE(10);
-      SAMPLE(11);
-      SAMPLE(12);
-#undef SAMPLE
-      default: throw RlError(RL_ERR_UNSUPPORTED, "rollout: envs of 2..12 actions are built");
-    }
+    // 9..12: the wide meta-bandit lanes (rl_env_create_meta_bandit_wide) under a recurrent chain
+    if (!with_range<2, (int)RL_WIDE_MAX_OUT>(env->A, [&](auto aa) {
+          hipLaunchKernelGGL(k_gen_sample_actions<decltype(aa)::value>, grid, blk, 0, e->stream, env->dev, z, n,
+                             env->t_global, env->d_actions);
+        }))
+      throw RlError(RL_ERR_UNSUPPORTED, "rollout: envs of 2..12 actions are built");
     launch_env_step(env);  // leaves reward, flag, the next observation and the interrupted successor in the env's buffers
     env->t_global += 1;
     hipLaunchKernelGGL(k_gen_record_step, grid, blk, 0, e->stream, t->d, env->d_actions, env->d_reward, env->d_flag,

@@ -420,10 +420,6 @@ bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float
   hipStream_t s = traj->eng->stream;
   uint32_t P = (uint32_t)policy->P;
   const TrajDev d = fused_traj_dev(traj, traj->guard_next_policy);
-#define BLAUNCH(MM)                                                                                                  \
-  hipLaunchKernelGGL((k_policy_bf16<MM, V2_WAVES>), g, b, 0, s, d, policy->d_params, wimg, d_tangent, traj->lp0,       \
-                     traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo, clip_hi, bt::SHARE_OLD, bt::SHARE_YOUNG,      \
-                     traj->kept_mask, traj->kept_w)
   if (keep) {
     hipLaunchKernelGGL((k_policy_bf16<PASS_INIT, V2_WAVES, false, true>), g, b, 0, s, d, policy->d_params, wimg,
                        d_tangent, traj->lp0, traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo, clip_hi, bt::SHARE_OLD,
@@ -431,19 +427,21 @@ bool launch_policy_v2(rl_traj *traj, const rl_mlp *policy, int mode, const float
     traj->kept_epoch = traj->eng->call_epoch;
     traj->kept_policy = policy;
     traj->kept_samples = traj->B;
-  } else if (mode == PASS_INIT) {
-    traj->kept_epoch = 0;  // (log pi_0 is rewritten without the planes that go with it)
-    BLAUNCH(PASS_INIT);
-  } else if (mode == PASS_JVP) BLAUNCH(PASS_JVP);
-  else if (mode == PASS_PPO) BLAUNCH(PASS_PPO);
-  else {
+  } else if (mode == PASS_EVAL) {
     // the evaluation pass has no backward state: with the weight fragments in LDS it fits twelve waves per CU (152
     // VGPRs) — 0.155 ms per launch at 8.4 M samples against 0.206 ms at eight (sixteen waves: 17 spills, no gain)
     constexpr int EVAL_WAVES = 16;
     hipLaunchKernelGGL((k_policy_bf16<PASS_EVAL, EVAL_WAVES, true>), g, dim3(EVAL_WAVES * 64), 0, s, d,
                        policy->d_params, wimg, d_tangent, traj->lp0, traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo,
                        clip_hi, 1u, 1u, nullptr, nullptr);
+  } else {
+    if (mode == PASS_INIT) traj->kept_epoch = 0;  // (log pi_0 is rewritten without the planes that go with it)
+    const bool built = with_one_of<PASS_INIT, PASS_JVP, PASS_PPO>(mode, [&](auto mm) {
+      hipLaunchKernelGGL((k_policy_bf16<decltype(mm)::value, V2_WAVES>), g, b, 0, s, d, policy->d_params, wimg, d_tangent,
+                         traj->lp0, traj->slabA, traj->slabB, inv_B, P, d_skip, clip_lo, clip_hi, bt::SHARE_OLD,
+                         bt::SHARE_YOUNG, traj->kept_mask, traj->kept_w);
+    });
+    if (!built) throw RlError(RL_ERR_UNSUPPORTED, "launch_policy_v2: an unknown pass mode");
   }
-#undef BLAUNCH
   return true;
 }

@@ -400,122 +400,14 @@ void launch_obs_range(rl_traj *traj) {
                      traj->d.range);
 }
 
-// The standalone env kernels are built per (env kind, D): `go(Env{}, D)` receives the env's ops struct and its feature
-// count as types.  CartPole lanes have 4 or 5 features; index-env lanes (Chain, bandit: 5 or 6; MemoryGame:
-// num_actions + history_len [+ 1]) 4..8; meta-bandit lanes arms + 4 = 6..16; tabular-MDP lanes states [+ 1] = 2..8;
-// meta-MDP lanes states + actions + 4 = 8..16, and 15..20 at nine and ten states (MetaMdpWideOps); PartitionGame lanes 23
-// or 24.
-template <int D>
-using FeatureCount = std::integral_constant<int, D>;
-template <class Go>
-static void env_dispatch(const rl_env *env, Go &&go) {
-  if (env->kind == RL_ENV_CARTPOLE) {
-    if (env->D == 5) go(CartPoleOps{}, FeatureCount<5>{});
-    else go(CartPoleOps{}, FeatureCount<4>{});
-    return;
-  }
-  if (env->kind == RL_ENV_META_BANDIT) {  // k + 4 features, k = 2..12 arms (above four: rl_env_create_meta_bandit_wide)
-    switch (env->D) {
-      case 6: go(MetaOps{}, FeatureCount<6>{}); break;
-      case 7: go(MetaOps{}, FeatureCount<7>{}); break;
-      case 8: go(MetaOps{}, FeatureCount<8>{}); break;
-      case 9: go(MetaOps{}, FeatureCount<9>{}); break;
-      case 10: go(MetaOps{}, FeatureCount<10>{}); break;
-      case 11: go(MetaOps{}, FeatureCount<11>{}); break;
-      case 12: go(MetaOps{}, FeatureCount<12>{}); break;
-      case 13: go(MetaOps{}, FeatureCount<13>{}); break;
-      case 14: go(MetaOps{}, FeatureCount<14>{}); break;
-      case 15: go(MetaOps{}, FeatureCount<15>{}); break;
-      case 16: go(MetaOps{}, FeatureCount<16>{}); break;
-      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-bandit lanes: 6..16 observation features");
-    }
-    return;
-  }
-  if (env->kind == RL_ENV_META_MDP && env->dev.mm.states > RL_META_MDP_MAX) {
-    // rl_env_create_meta_mdp_wide at 9 or 10 states: rows of sixteen floats; 9 x 2 has 15 features, 10 x 6 has 20
-    switch (env->D) {
-      case 15: go(MetaMdpWideOps{}, FeatureCount<15>{}); break;
-      case 16: go(MetaMdpWideOps{}, FeatureCount<16>{}); break;
-      case 17: go(MetaMdpWideOps{}, FeatureCount<17>{}); break;
-      case 18: go(MetaMdpWideOps{}, FeatureCount<18>{}); break;
-      case 19: go(MetaMdpWideOps{}, FeatureCount<19>{}); break;
-      case 20: go(MetaMdpWideOps{}, FeatureCount<20>{}); break;
-      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-MDP lanes of nine or ten states: 15..20 observation features");
-    }
-    return;
-  }
-  if (env->kind == RL_ENV_META_MDP) {  // S + A + 4 features, S and A 2..8: at most 16, through the wide constructor 20
-    switch (env->D) {
-      case 8: go(MetaMdpOps{}, FeatureCount<8>{}); break;
-      case 9: go(MetaMdpOps{}, FeatureCount<9>{}); break;
-      case 10: go(MetaMdpOps{}, FeatureCount<10>{}); break;
-      case 11: go(MetaMdpOps{}, FeatureCount<11>{}); break;
-      case 12: go(MetaMdpOps{}, FeatureCount<12>{}); break;
-      case 13: go(MetaMdpOps{}, FeatureCount<13>{}); break;
-      case 14: go(MetaMdpOps{}, FeatureCount<14>{}); break;
-      case 15: go(MetaMdpOps{}, FeatureCount<15>{}); break;
-      case 16: go(MetaMdpOps{}, FeatureCount<16>{}); break;
-      case 17: go(MetaMdpOps{}, FeatureCount<17>{}); break;  // 17..20: rl_env_create_meta_mdp_wide at up to 8 states
-      case 18: go(MetaMdpOps{}, FeatureCount<18>{}); break;
-      case 19: go(MetaMdpOps{}, FeatureCount<19>{}); break;
-      case 20: go(MetaMdpOps{}, FeatureCount<20>{}); break;
-      default: throw RlError(RL_ERR_UNSUPPORTED, "meta-MDP lanes: 8..20 observation features");
-    }
-    return;
-  }
-  if (env->kind == RL_ENV_PARTITION) {  // 23 features, 24 under a visible limit
-    switch (env->D) {
-      case 23: go(PartitionOps{}, FeatureCount<23>{}); break;
-      case 24: go(PartitionOps{}, FeatureCount<24>{}); break;
-      default: throw RlError(RL_ERR_UNSUPPORTED, "PartitionGame lanes: 23 or 24 observation features");
-    }
-    return;
-  }
-  if (env->kind == RL_ENV_TABULAR_MDP) {  // n_states [+ 1] features, 2..8 states
-    switch (env->D) {
-      case 2: go(MdpOps{}, FeatureCount<2>{}); break;
-      case 3: go(MdpOps{}, FeatureCount<3>{}); break;
-      case 4: go(MdpOps{}, FeatureCount<4>{}); break;
-      case 5: go(MdpOps{}, FeatureCount<5>{}); break;
-      case 6: go(MdpOps{}, FeatureCount<6>{}); break;
-      case 7: go(MdpOps{}, FeatureCount<7>{}); break;
-      case 8: go(MdpOps{}, FeatureCount<8>{}); break;
-      default: throw RlError(RL_ERR_UNSUPPORTED, "tabular-MDP lanes: 2..8 observation features");
-    }
-    return;
-  }
-  // (a kind this function does not know never steps through the index lanes' code)
-  if (env->kind != RL_ENV_CHAIN && env->kind != RL_ENV_MEMORY && env->kind != RL_ENV_BANDIT)
-    throw RlError(RL_ERR_UNSUPPORTED, "env kernels: unknown env kind");
-  switch (env->D) {
-    case 4: go(IndexOps{}, FeatureCount<4>{}); break;
-    case 5: go(IndexOps{}, FeatureCount<5>{}); break;
-    case 6: go(IndexOps{}, FeatureCount<6>{}); break;
-    case 7: go(IndexOps{}, FeatureCount<7>{}); break;
-    case 8: go(IndexOps{}, FeatureCount<8>{}); break;
-    default: throw RlError(RL_ERR_UNSUPPORTED, "index env lanes: 4..8 observation features");
-  }
-}
-
+// The standalone env kernels are built per (ops struct, D): env_dispatch (env_lanes.hpp) hands both to `go` as types, from
+// the lane families and feature ranges of handle_spec.hpp (ENV_LANE_FEATURES).
 void launch_env_reset(rl_env *env) {
   ProfScope ps(env->eng, RL_K_SMALL);
   uint32_t n = (uint32_t)env->cfg.n_lanes;
-  if (env->kind == RL_ENV_CARTPOLE)
-    hipLaunchKernelGGL(k_env_reset<CartPoleOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
-  else if (env->kind == RL_ENV_META_BANDIT)
-    hipLaunchKernelGGL(k_env_reset<MetaOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
-  else if (env->kind == RL_ENV_TABULAR_MDP)
-    hipLaunchKernelGGL(k_env_reset<MdpOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
-  else if (env->kind == RL_ENV_PARTITION)
-    hipLaunchKernelGGL(k_env_reset<PartitionOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
-  else if (env->kind == RL_ENV_META_MDP && env->dev.mm.states > RL_META_MDP_MAX)
-    hipLaunchKernelGGL(k_env_reset<MetaMdpWideOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
-  else if (env->kind == RL_ENV_META_MDP)
-    hipLaunchKernelGGL(k_env_reset<MetaMdpOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
-  else if (env->kind != RL_ENV_CHAIN && env->kind != RL_ENV_MEMORY && env->kind != RL_ENV_BANDIT)
-    throw RlError(RL_ERR_UNSUPPORTED, "env kernels: unknown env kind");
-  else
-    hipLaunchKernelGGL(k_env_reset<IndexOps>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  env_lanes_dispatch(env, [&](auto ops) {
+    hipLaunchKernelGGL(k_env_reset<decltype(ops)>, dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n);
+  });
 }
 
 void launch_env_observe(rl_env *env, float *d_obs) {
@@ -532,18 +424,14 @@ void launch_env_step(rl_env *env) {
   uint32_t n = (uint32_t)env->cfg.n_lanes;
   env_dispatch(env, [&](auto ops, auto d) {
     using Env = decltype(ops);
-    constexpr int D = decltype(d)::value;
-#define ENV_STEP(FF)                                                                                                    \
-  hipLaunchKernelGGL((k_env_step<Env, D, FF>), dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream, env->dev, env->st, n, \
-                     env->d_actions, env->d_reward, env->d_flag, env->d_obs, env->d_term_obs, env->t_global)
-    if constexpr (std::is_same_v<Env, CartPoleOps>) {
-      if (n >= (1u << 20)) {
-        ENV_STEP(true);
-        return;
-      }
-    }
-    ENV_STEP(false);
-#undef ENV_STEP
+    // (FF, CartPole lanes alone: the build for a million lanes and more)
+    with_bool(std::is_same_v<Env, CartPoleOps> && n >= (1u << 20), [&](auto ff) {
+      constexpr bool FF = decltype(ff)::value;
+      if constexpr (!FF || std::is_same_v<Env, CartPoleOps>)
+        hipLaunchKernelGGL((k_env_step<Env, decltype(d)::value, FF>), dim3(cdiv(n, 256)), dim3(256), 0, env->eng->stream,
+                           env->dev, env->st, n, env->d_actions, env->d_reward, env->d_flag, env->d_obs, env->d_term_obs,
+                           env->t_global);
+    });
   });
 }
 
@@ -566,37 +454,32 @@ void launch_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   const uint64_t simds = 4ull * (uint64_t)env->eng->prop.multiProcessorCount, n = env->cfg.n_lanes;
   int G = 1;
   while (G < 16 && n * (uint64_t)(2 * G) <= (2 * G >= 8 ? 1 : 2) * simds * 64) G *= 2;
-#define ROLL(DD)                                                   \
-  switch (G) {                                                     \
-    case 16: launch_rollout_g<DD, 16>(env, policy, traj); break;   \
-    case 8: launch_rollout_g<DD, 8>(env, policy, traj); break;     \
-    case 4: launch_rollout_g<DD, 4>(env, policy, traj); break;     \
-    case 2: launch_rollout_g<DD, 2>(env, policy, traj); break;     \
-    default: launch_rollout_g<DD, 1>(env, policy, traj); break;    \
-  }
-  if (env->D == 5) {
-    ROLL(5)
-  } else {
-    ROLL(4)
-  }
-#undef ROLL
+  bool built = false;
+  with_one_of<4, 5>(env->D, [&](auto d) {
+    built = with_one_of<1, 2, 4, 8, 16>(G, [&](auto g) {
+      launch_rollout_g<decltype(d)::value, decltype(g)::value>(env, policy, traj);
+    });
+  });
+  if (!built) throw RlError(RL_ERR_UNSUPPORTED, "launch_rollout: 4 or 5 observation features, 1..16 threads per lane");
 }
 
 void launch_values(rl_traj *traj, const rl_mlp *critic) {
   ProfScope ps(traj->eng, RL_K_VALUES);
   size_t rows = (size_t)(traj->d.T + 1) * traj->d.n;
-  if (traj->d.D == 5 && traj->range_reset && !traj->range_valid && !traj->range_fixed) {
-    // the planes' magnitude range as a by-product of the pass that reads every observation anyway (no pass of its own)
-    hipLaunchKernelGGL((k_mlp_forward_rows<5, 1, true>), dim3(cdiv(rows, 256)), dim3(256), 0, traj->eng->stream,
-                       critic->d_params, (int)critic->hidden, traj->d.obs, rows, rows, traj->d.values, rows, traj->d.range);
+  // the planes' magnitude range as a by-product of the pass that reads every observation anyway (no pass of its own)
+  const bool range = traj->d.D == 5 && traj->range_reset && !traj->range_valid && !traj->range_fixed;
+  auto forward = [&](auto d, auto with_range_words) {
+    hipLaunchKernelGGL((k_mlp_forward_rows<decltype(d)::value, 1, decltype(with_range_words)::value>), dim3(cdiv(rows, 256)),
+                       dim3(256), 0, traj->eng->stream, critic->d_params, (int)critic->hidden, traj->d.obs, rows, rows,
+                       traj->d.values, rows, range ? traj->d.range : (uint32_t *)nullptr);
+  };
+  if (range) {
+    forward(Int<5>{}, std::true_type{});
     traj->range_valid = true;
     traj->range_reset = false;
-  } else if (traj->d.D == 5)
-    hipLaunchKernelGGL((k_mlp_forward_rows<5, 1>), dim3(cdiv(rows, 256)), dim3(256), 0, traj->eng->stream,
-                       critic->d_params, (int)critic->hidden, traj->d.obs, rows, rows, traj->d.values, rows, (uint32_t *)nullptr);
-  else
-    hipLaunchKernelGGL((k_mlp_forward_rows<4, 1>), dim3(cdiv(rows, 256)), dim3(256), 0, traj->eng->stream,
-                       critic->d_params, (int)critic->hidden, traj->d.obs, rows, rows, traj->d.values, rows, (uint32_t *)nullptr);
+  } else if (!with_one_of<4, 5>(traj->d.D, [&](auto d) { forward(d, std::false_type{}); })) {
+    throw RlError(RL_ERR_UNSUPPORTED, "launch_values: 4 or 5 observation features");
+  }
 }
 
 void launch_gae(rl_traj *traj, const rl_mlp *critic, float gamma, float lambda) {
@@ -604,14 +487,14 @@ void launch_gae(rl_traj *traj, const rl_mlp *critic, float gamma, float lambda) 
   uint32_t n = traj->d.n;
   traj->rtg_scan_valid = true;  // d.rtg <- the lane scan's reward-to-go at `gamma` (engine.hpp)
   traj->rtg_gamma = gamma;
-  if (traj->d.D == 5)
-    hipLaunchKernelGGL(k_gae_scan<5>, dim3(cdiv(n, 64)), dim3(64), 0, traj->eng->stream, traj->d,
+  // (without a critic the scan reads no observation: a trajectory of any other width takes the 4-feature build)
+  const uint32_t D = critic == nullptr && traj->d.D != 5 ? 4 : traj->d.D;
+  const bool built = with_one_of<4, 5>(D, [&](auto d) {
+    hipLaunchKernelGGL(k_gae_scan<decltype(d)::value>, dim3(cdiv(n, 64)), dim3(64), 0, traj->eng->stream, traj->d,
                        critic ? critic->d_params : (const float *)nullptr, critic ? (int)critic->hidden : 0, gamma, lambda,
                        critic ? 0 : 1);
-  else
-    hipLaunchKernelGGL(k_gae_scan<4>, dim3(cdiv(n, 64)), dim3(64), 0, traj->eng->stream, traj->d,
-                       critic ? critic->d_params : (const float *)nullptr, critic ? (int)critic->hidden : 0, gamma, lambda,
-                       critic ? 0 : 1);
+  });
+  if (!built) throw RlError(RL_ERR_UNSUPPORTED, "launch_gae: 4 or 5 observation features");
 }
 
 void launch_value_targets(rl_traj *traj, const rl_mlp *critic, float gamma) {
@@ -621,26 +504,22 @@ void launch_value_targets(rl_traj *traj, const rl_mlp *critic, float gamma) {
     return;
   }
   const size_t B = (size_t)traj->d.T * traj->d.n;
-  if (traj->d.D == 5)
-    hipLaunchKernelGGL(k_value_targets_td<5>, dim3(cdiv(B, 256)), dim3(256), 0, traj->eng->stream, traj->d,
+  const bool built = with_one_of<4, 5>(traj->d.D, [&](auto d) {
+    hipLaunchKernelGGL(k_value_targets_td<decltype(d)::value>, dim3(cdiv(B, 256)), dim3(256), 0, traj->eng->stream, traj->d,
                        critic->d_params, (int)critic->hidden, gamma);
-  else
-    hipLaunchKernelGGL(k_value_targets_td<4>, dim3(cdiv(B, 256)), dim3(256), 0, traj->eng->stream, traj->d,
-                       critic->d_params, (int)critic->hidden, gamma);
+  });
+  if (!built) throw RlError(RL_ERR_UNSUPPORTED, "launch_value_targets: 4 or 5 observation features");
 }
 
 void launch_mlp_forward_host_rows(rl_mlp *mlp, const float *d_in_soa, size_t rows, float *d_out_soa) {
   ProfScope ps(mlp->eng, RL_K_VALUES);
   dim3 g(cdiv(rows, 256)), b(256);
-  hipStream_t s = mlp->eng->stream;
-  int H = (int)mlp->hidden;
-#define FWD(DD, AA)                                                                                              \
-  hipLaunchKernelGGL((k_mlp_forward_rows<DD, AA, false>), g, b, 0, s, mlp->d_params, H, d_in_soa, rows, rows, d_out_soa, \
-                     rows)
-  if (mlp->in_dim == 5 && mlp->out_dim == 2) FWD(5, 2);
-  else if (mlp->in_dim == 5 && mlp->out_dim == 1) FWD(5, 1);
-  else if (mlp->in_dim == 4 && mlp->out_dim == 2) FWD(4, 2);
-  else if (mlp->in_dim == 4 && mlp->out_dim == 1) FWD(4, 1);
-  else throw RlError(RL_ERR_UNSUPPORTED, "mlp forward: unsupported (in_dim, out_dim)");
-#undef FWD
+  bool built = false;
+  with_one_of<4, 5>(mlp->in_dim, [&](auto d) {
+    built = with_one_of<1, 2>(mlp->out_dim, [&](auto a) {
+      hipLaunchKernelGGL((k_mlp_forward_rows<decltype(d)::value, decltype(a)::value, false>), g, b, 0, mlp->eng->stream,
+                         mlp->d_params, (int)mlp->hidden, d_in_soa, rows, rows, d_out_soa, rows);
+    });
+  });
+  if (!built) throw RlError(RL_ERR_UNSUPPORTED, "mlp forward: unsupported (in_dim, out_dim)");
 }

@@ -746,18 +746,14 @@ void launch_rollout_gru(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   ProfScope ps(env->eng, RL_K_ROLLOUT);
   RL_REQUIRE(env->D == 5, "recurrent rollout: built for 5 observation features");
   uint32_t tiles = traj->d.n / TL;
-#define ROLL(ENV, CELL)                                                                                           \
-  hipLaunchKernelGGL((k_rollout_gru<5, ENV, CELL>), dim3(tiles), dim3(W16 * 64), 0, env->eng->stream, env->dev, env->st, \
-                     traj->d, policy->d_params, env->t_global)
-  const bool lstm = policy->kind == RL_MODULE_LSTM_MLP;
-  if (env->kind != RL_ENV_CARTPOLE) {
-    if (lstm) ROLL(ChainOps, LstmCell16);
-    else ROLL(ChainOps, GruCell16);
-  } else {
-    if (lstm) ROLL(CartPoleOps, LstmCell16);
-    else ROLL(CartPoleOps, GruCell16);
-  }
-#undef ROLL
+  with_bool(policy->kind == RL_MODULE_LSTM_MLP, [&](auto lstm) {
+    using Cell = std::conditional_t<decltype(lstm)::value, LstmCell16, GruCell16>;
+    with_bool(env->kind == RL_ENV_CARTPOLE, [&](auto cartpole) {
+      using Env = std::conditional_t<decltype(cartpole)::value, CartPoleOps, ChainOps>;
+      hipLaunchKernelGGL((k_rollout_gru<5, Env, Cell>), dim3(tiles), dim3(W16 * 64), 0, env->eng->stream, env->dev, env->st,
+                         traj->d, policy->d_params, env->t_global);
+    });
+  });
 }
 
 void launch_rollout_chain_mlp(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
@@ -774,9 +770,6 @@ void launch_gru_seq_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, floa
   ProfScope ps(traj->eng, RL_K_POLICY_FUSED);
   RL_REQUIRE(traj->d.D == 5, "recurrent forward: built for 5 observation features");
   uint32_t tiles = traj->d.n / TL;
-#define FWD(AA, CELL)                                                                                        \
-  hipLaunchKernelGGL((k_gru_seq_forward<5, AA, CELL>), dim3(tiles), dim3(W16 * 64), 0, traj->eng->stream, traj->d, \
-                     mod->d_params, d_out, d_succ, d_act, d_skip)
   const bool lstm = mod->kind == RL_MODULE_LSTM_MLP;
   // training forward of the GRU chain (activation record, no successor evaluations): the bf16-pipe kernels of
   // kernels_seq_train.hip; kernel variant 1 keeps the f32 cell for A/B runs
@@ -789,12 +782,12 @@ void launch_gru_seq_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, floa
     launch_lstm_train_forward(traj, mod, d_out, d_act, d_skip);
     return;
   }
-  if (mod->out_dim == 2) {
-    if (lstm) FWD(2, LstmCell16);
-    else FWD(2, GruCell16);
-  } else {
-    if (lstm) FWD(1, LstmCell16);
-    else FWD(1, GruCell16);
-  }
-#undef FWD
+  with_bool(lstm, [&](auto is_lstm) {
+    using Cell = std::conditional_t<decltype(is_lstm)::value, LstmCell16, GruCell16>;
+    if (!with_one_of<1, 2>(mod->out_dim, [&](auto aa) {
+          hipLaunchKernelGGL((k_gru_seq_forward<5, decltype(aa)::value, Cell>), dim3(tiles), dim3(W16 * 64), 0,
+                             traj->eng->stream, traj->d, mod->d_params, d_out, d_succ, d_act, d_skip);
+        }))
+      throw RlError(RL_ERR_UNSUPPORTED, "launch_gru_seq_forward: one or two outputs");
+  });
 }

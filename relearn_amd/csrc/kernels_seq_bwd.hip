@@ -700,42 +700,24 @@ void launch_seq_policy_dlogits(rl_traj *traj, int mode, uint64_t B_total, float 
   ProfScope ps(traj->eng, RL_K_POLICY_PASS);
   float inv_B = 1.0f / (float)B_total;
   dim3 g(traj->nbB), b(256);
-  if (n_out > 2) {  // (lp0 / dz hold n_out planes: stack_ensure)
-    RL_REQUIRE(traj->act_planes >= n_out, "the trajectory's action planes are narrower than the policy");
-#define DLN(MM, AA)                                                                                                  \
-  hipLaunchKernelGGL((k_seq_policy_dlogits_n<MM, AA>), g, b, 0, traj->eng->stream, traj->d, traj->seq.out, traj->lp0, \
-                     traj->dz, traj->slabB, inv_B, clip_lo, clip_hi, d_skip)
-#define DLN_A(AA)                                     \
-  case AA:                                            \
-    if (mode == PASS_INIT) DLN(PASS_INIT, AA);        \
-    else if (mode == PASS_EVAL) DLN(PASS_EVAL, AA);   \
-    else DLN(PASS_PPO, AA);                           \
-    break
-    switch (n_out) {
-      DLN_A(3);
-      DLN_A(4);
-      DLN_A(5);
-      DLN_A(6);
-      DLN_A(7);
-      DLN_A(8);
-      DLN_A(9);  // 9..12: rl_rnn_chain_create_wide
-      DLN_A(10);
-      DLN_A(11);
-      DLN_A(12);
-      default: throw RlError(RL_ERR_UNSUPPORTED, "recurrent policy pass: categorical policies over 2..12 actions are built");
+  // (the recurrent passes: PASS_JVP is launch_gru_tangent's, PASS_DQN rdqn_gradient's)
+  const bool built = with_one_of<PASS_INIT, PASS_EVAL, PASS_PPO>(mode, [&](auto mm) {
+    constexpr int MM = decltype(mm)::value;
+    if (n_out > 2) {  // (lp0 / dz hold n_out planes: stack_ensure)
+      RL_REQUIRE(traj->act_planes >= n_out, "the trajectory's action planes are narrower than the policy");
+      // 3..8: rl_rnn_chain_create; 9..12: rl_rnn_chain_create_wide
+      if (!with_range<3, (int)RL_WIDE_MAX_OUT>(n_out, [&](auto aa) {
+            hipLaunchKernelGGL((k_seq_policy_dlogits_n<MM, decltype(aa)::value>), g, b, 0, traj->eng->stream, traj->d,
+                               traj->seq.out, traj->lp0, traj->dz, traj->slabB, inv_B, clip_lo, clip_hi, d_skip);
+          }))
+        throw RlError(RL_ERR_UNSUPPORTED, "recurrent policy pass: categorical policies over 2..12 actions are built");
+      RL_HIP_CHECK(hipGetLastError());
+      return;
     }
-#undef DLN_A
-#undef DLN
-    RL_HIP_CHECK(hipGetLastError());
-    return;
-  }
-#define DL(MM)                                                                                                     \
-  hipLaunchKernelGGL(k_seq_policy_dlogits<MM>, g, b, 0, traj->eng->stream, traj->d, traj->seq.out, traj->lp0, traj->dz, \
-                     traj->slabB, inv_B, clip_lo, clip_hi, d_skip)
-  if (mode == PASS_INIT) DL(PASS_INIT);
-  else if (mode == PASS_EVAL) DL(PASS_EVAL);
-  else DL(PASS_PPO);
-#undef DL
+    hipLaunchKernelGGL(k_seq_policy_dlogits<MM>, g, b, 0, traj->eng->stream, traj->d, traj->seq.out, traj->lp0, traj->dz,
+                       traj->slabB, inv_B, clip_lo, clip_hi, d_skip);
+  });
+  if (!built) throw RlError(RL_ERR_UNSUPPORTED, "launch_seq_policy_dlogits: PASS_INIT, PASS_EVAL or PASS_PPO");
 }
 
 void launch_seq_critic_dvalues(rl_traj *traj, uint64_t B_total) {
@@ -783,29 +765,25 @@ void launch_gru_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip
   }
   {
     ProfScope ps(e, RL_K_CRITIC_FUSED);
-#define WG(AA, NGT, G0, GN, W1)                                                                                   \
-  hipLaunchKernelGGL((k_gru_wgrad<5, AA, NGT, G0, GN, W1>), dim3(q.chunks), dim3(256), 0, e->stream, traj->d, traj->dz, \
-                     q.act, q.dpre, q.wg_slab, P, q.tiles, blocks, q.blocks_per_chunk, d_skip)
-    if (mod->out_dim == 2) {
-      if (gru_head) {
-        launch_gru_train_wgrad(traj, mod, d_skip);
-      } else if (lstm) {
-        WG(2, 4, 0, 2, true);
-        WG(2, 4, 2, 2, false);
-      } else {
-        WG(2, 3, 0, 3, true);
-      }
-    } else {
-      if (gru_head) {
-        launch_gru_train_wgrad(traj, mod, d_skip);
-      } else if (lstm) {
-        WG(1, 4, 0, 2, true);
-        WG(1, 4, 2, 2, false);
-      } else {
-        WG(1, 3, 0, 3, true);
-      }
+    // k_gru_wgrad<5, A, gates, first gate, gates of this launch, with the head's W1>
+    auto wgrad = [&](auto a, auto ngt, auto g0, auto gn, auto w1) {
+      hipLaunchKernelGGL((k_gru_wgrad<5, decltype(a)::value, decltype(ngt)::value, decltype(g0)::value, decltype(gn)::value,
+                                      decltype(w1)::value>),
+                         dim3(q.chunks), dim3(256), 0, e->stream, traj->d, traj->dz, q.act, q.dpre, q.wg_slab, P, q.tiles,
+                         blocks, q.blocks_per_chunk, d_skip);
+    };
+    if (gru_head) {
+      launch_gru_train_wgrad(traj, mod, d_skip);
+    } else if (!with_one_of<1, 2>(mod->out_dim, [&](auto a) {
+                 if (lstm) {
+                   wgrad(a, Int<4>{}, Int<0>{}, Int<2>{}, std::true_type{});
+                   wgrad(a, Int<4>{}, Int<2>{}, Int<2>{}, std::false_type{});
+                 } else {
+                   wgrad(a, Int<3>{}, Int<0>{}, Int<3>{}, std::true_type{});
+                 }
+               })) {
+      throw RlError(RL_ERR_UNSUPPORTED, "launch_gru_backward: one or two outputs");
     }
-#undef WG
   }
   {
     ProfScope ps(e, RL_K_REDUCE);

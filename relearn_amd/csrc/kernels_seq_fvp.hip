@@ -322,28 +322,14 @@ void launch_gru_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent
   }
   {
     ProfScope ps(e, RL_K_POLICY_PASS);
-#define FVN(AA)                                                                                                     \
-  case AA:                                                                                                          \
-    hipLaunchKernelGGL(k_seq_fvp_dlogits_n<AA>, dim3(traj->nbB), dim3(256), 0, e->stream, traj->d, q.out, traj->lp0, \
-                       traj->dz, 1.0f / (float)B_total, d_skip);                                                    \
-    break
-    switch (mod->out_dim) {
-      case 2:
-        hipLaunchKernelGGL(k_seq_fvp_dlogits, dim3(traj->nbB), dim3(256), 0, e->stream, traj->d, q.out, traj->lp0,
-                           traj->dz, 1.0f / (float)B_total, d_skip);
-        break;
-      FVN(3);
-      FVN(4);
-      FVN(5);
-      FVN(6);
-      FVN(7);
-      FVN(8);
-      FVN(9);  // 9..12: rl_rnn_chain_create_wide
-      FVN(10);
-      FVN(11);
-      FVN(12);
-      default: throw RlError(RL_ERR_UNSUPPORTED, "Fisher-vector products: 2..12 actions");
-    }
-#undef FVN
+    // two outputs have a kernel of their own; 3..8: rl_rnn_chain_create; 9..12: rl_rnn_chain_create_wide
+    if (mod->out_dim == 2)
+      hipLaunchKernelGGL(k_seq_fvp_dlogits, dim3(traj->nbB), dim3(256), 0, e->stream, traj->d, q.out, traj->lp0, traj->dz,
+                         1.0f / (float)B_total, d_skip);
+    else if (!with_range<3, (int)RL_WIDE_MAX_OUT>(mod->out_dim, [&](auto aa) {
+               hipLaunchKernelGGL(k_seq_fvp_dlogits_n<decltype(aa)::value>, dim3(traj->nbB), dim3(256), 0, e->stream,
+                                  traj->d, q.out, traj->lp0, traj->dz, 1.0f / (float)B_total, d_skip);
+             }))
+      throw RlError(RL_ERR_UNSUPPORTED, "Fisher-vector products: 2..12 actions");
   }
 }

@@ -928,6 +928,22 @@ inline int out_class(const rl_mlp *m) {
   return m->out_dim <= 2 ? 2 : (m->out_dim <= 8 ? 8 : 12);
 }
 
+// a module's cell and tail as constants: go(Int<GRU | LSTM>{}, is the tail linear)
+template <class Go>
+void with_cell(const rl_mlp *m, Go &&go) {
+  with_bool(m->kind == RL_MODULE_LSTM_MLP, [&](auto lstm) {
+    with_bool(m->linear_tail(), [&](auto lin) { go(Int<decltype(lstm)::value ? LSTM : GRU>{}, lin); });
+  });
+}
+// ... and the head's output-count class with them: go(cell, lin, Int<2 | 8 | 12>{})
+template <class Go>
+void with_cell_and_head(const rl_mlp *m, const char *refusal, Go &&go) {
+  const int nq = out_class(m);
+  with_cell(m, [&](auto cell, auto lin) {
+    if (!with_one_of<2, 8, 12>(nq, [&](auto q) { go(cell, lin, q); })) throw RlError(RL_ERR_UNSUPPORTED, refusal);
+  });
+}
+
 }  // namespace
 
 void stack_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
@@ -975,32 +991,13 @@ void launch_stack_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float 
   const StackNet net = stack_net(mod, mod->d_params);
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
-#define FWD(CELL, REC, LIN, NQ)                                                                                       \
-  hipLaunchKernelGGL((k_stack_forward<CELL, REC, LIN, NQ>), grid, blk, 0, traj->eng->stream, net, ws, traj->d, d_out, \
-                     d_succ, d_skip)
-#define FWD_TAIL(CELL, REC)                   \
-  do {                                        \
-    if (nq == 12) {                           \
-      if (lin) FWD(CELL, REC, true, 12);      \
-      else FWD(CELL, REC, false, 12);         \
-    } else if (nq == 8) {                     \
-      if (lin) FWD(CELL, REC, true, 8);       \
-      else FWD(CELL, REC, false, 8);          \
-    } else if (lin) FWD(CELL, REC, true, 2);  \
-    else FWD(CELL, REC, false, 2);            \
-  } while (0)
-  // (`nq`: the output-count class of the head, stack_head)
-  const bool lstm = mod->kind == RL_MODULE_LSTM_MLP, lin = mod->linear_tail();
-  const int nq = out_class(mod);
-  if (record) {
-    if (lstm) FWD_TAIL(LSTM, true);
-    else FWD_TAIL(GRU, true);
-  } else {
-    if (lstm) FWD_TAIL(LSTM, false);
-    else FWD_TAIL(GRU, false);
-  }
-#undef FWD_TAIL
-#undef FWD
+  with_cell_and_head(mod, "launch_stack_forward: head classes of 2, 8 and 12 outputs", [&](auto cell, auto lin, auto q) {
+    with_bool(record, [&](auto rec) {
+      hipLaunchKernelGGL((k_stack_forward<decltype(cell)::value, decltype(rec)::value, decltype(lin)::value,
+                                          decltype(q)::value>),
+                         grid, blk, 0, traj->eng->stream, net, ws, traj->d, d_out, d_succ, d_skip);
+    });
+  });
   RL_HIP_CHECK(hipGetLastError());
 }
 
@@ -1011,44 +1008,30 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
   float *z = traj->seq.stack.z;
-  const bool lstm = policy->kind == RL_MODULE_LSTM_MLP, lin = policy->linear_tail();
-  const int nq = out_class(policy);
+  out_class(policy);  // (1..12 outputs, asked before any env's own conditions)
+  // one launch for all T steps on lanes `Env` of D features and A actions
+  auto fused = [&](auto cell, auto lin, auto ops, auto d, auto a) {
+    hipLaunchKernelGGL((k_stack_rollout<decltype(cell)::value, decltype(ops), decltype(d)::value, decltype(lin)::value,
+                                        decltype(a)::value>),
+                       grid, blk, 0, env->eng->stream, net, ws, env->dev, env->st, traj->d, env->t_global);
+  };
+  auto fused_done = [&](bool built, const char *lanes) {
+    if (!built) throw RlError(RL_ERR_UNSUPPORTED, std::string("launch_stack_rollout: no fused kernel for these ") + lanes);
+    RL_HIP_CHECK(hipGetLastError());
+    env->t_global += traj->d.T;
+  };
   if (env->kind == RL_ENV_META_BANDIT && env->eng->kernel_variant != 1) {
     // meta-bandit lanes: all T steps in one launch (kernel variant 1 keeps the launch sequence per step, below).  Two to
     // twelve arms: k arms make k + 4 observation features (env_lanes.hpp, MetaOps).
     RL_REQUIRE(env->A >= 2 && env->A <= RL_WIDE_MAX_OUT && env->D == env->A + 4,
                "fused recurrent rollout on meta-bandit lanes: built for two to twelve arms (k + 4 features)");
-#define ROLL(CELL, LIN, DD, AA)                                                                                          \
-  hipLaunchKernelGGL((k_stack_rollout<CELL, MetaOps, DD, LIN, AA>), grid, blk, 0, env->eng->stream, net, ws, env->dev, \
-                     env->st, traj->d, env->t_global)
-#define ROLL_ARMS(CELL, LIN)                        \
-  do {                                              \
-    switch (env->A) {                               \
-      case 2: ROLL(CELL, LIN, 6, 2); break;         \
-      case 3: ROLL(CELL, LIN, 7, 3); break;         \
-      case 4: ROLL(CELL, LIN, 8, 4); break;         \
-      case 5: ROLL(CELL, LIN, 9, 5); break;         \
-      case 6: ROLL(CELL, LIN, 10, 6); break;        \
-      case 7: ROLL(CELL, LIN, 11, 7); break;        \
-      case 8: ROLL(CELL, LIN, 12, 8); break;        \
-      case 9: ROLL(CELL, LIN, 13, 9); break;        \
-      case 10: ROLL(CELL, LIN, 14, 10); break;      \
-      case 11: ROLL(CELL, LIN, 15, 11); break;      \
-      default: ROLL(CELL, LIN, 16, 12); break;      \
-    }                                               \
-  } while (0)
-    if (lstm) {
-      if (lin) ROLL_ARMS(LSTM, true);
-      else ROLL_ARMS(LSTM, false);
-    } else {
-      if (lin) ROLL_ARMS(GRU, true);
-      else ROLL_ARMS(GRU, false);
-    }
-#undef ROLL_ARMS
-#undef ROLL
-    RL_HIP_CHECK(hipGetLastError());
-    env->t_global += traj->d.T;
-    return;
+    bool built = false;
+    with_cell(policy, [&](auto cell, auto lin) {
+      built = with_range<2, (int)RL_WIDE_MAX_OUT>(env->A, [&](auto a) {
+        fused(cell, lin, MetaOps{}, Int<decltype(a)::value + 4>{}, a);
+      });
+    });
+    return fused_done(built, "meta-bandit lanes");
   }
   if (env->kind == RL_ENV_META_MDP && env->eng->kernel_variant != 1 &&
       meta_mdp_fused_shape(env->dev.mm.states, env->dev.mm.actions)) {
@@ -1057,30 +1040,19 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     // lanes of a run draw their tables at the same step: a serial section of wave 0, once per trial (MetaMdpOps::reset).
     const uint32_t S = env->dev.mm.states, A = env->dev.mm.actions;
     RL_REQUIRE(env->D == S + A + 4 && env->A == A, "fused recurrent rollout on meta-MDP lanes: S + A + 4 features");
-#define ROLL(CELL, LIN, SS, AA)                                                                                       \
-  hipLaunchKernelGGL((k_stack_rollout<CELL, MetaMdpOps, SS + AA + 4, LIN, AA>), grid, blk, 0, env->eng->stream, net, \
-                     ws, env->dev, env->st, traj->d, env->t_global)
-#define ROLL_SHAPES(CELL, LIN)                                  \
-  do {                                                          \
-    if (S == 2 && A == 2) ROLL(CELL, LIN, 2, 2);                \
-    else if (S == 3 && A == 2) ROLL(CELL, LIN, 3, 2);           \
-    else if (S == 4 && A == 3) ROLL(CELL, LIN, 4, 3);           \
-    else if (S == 5 && A == 5) ROLL(CELL, LIN, 5, 5);           \
-    else if (S == 8 && A == 4) ROLL(CELL, LIN, 8, 4);           \
-    else ROLL(CELL, LIN, 4, 8);                                 \
-  } while (0)
-    if (lstm) {
-      if (lin) ROLL_SHAPES(LSTM, true);
-      else ROLL_SHAPES(LSTM, false);
-    } else {
-      if (lin) ROLL_SHAPES(GRU, true);
-      else ROLL_SHAPES(GRU, false);
-    }
-#undef ROLL_SHAPES
-#undef ROLL
-    RL_HIP_CHECK(hipGetLastError());
-    env->t_global += traj->d.T;
-    return;
+    bool built = false;
+    with_cell(policy, [&](auto cell, auto lin) {
+      with_range<2, (int)RL_META_MDP_MAX>(S, [&](auto s) {
+        with_range<2, (int)RL_META_MDP_MAX>(A, [&](auto a) {
+          constexpr int SS = decltype(s)::value, AA = decltype(a)::value;
+          if constexpr (meta_mdp_fused_shape(SS, AA)) {  // (the table's shapes are the kernels that exist)
+            fused(cell, lin, MetaMdpOps{}, Int<SS + AA + 4>{}, a);
+            built = true;
+          }
+        });
+      });
+    });
+    return fused_done(built, "meta-MDP lanes");
   }
   if (env->kind == RL_ENV_META_MDP && env->eng->kernel_variant != 1 && env->dev.mm.states > RL_META_MDP_MAX &&
       meta_mdp_wide_fused_shape(env->dev.mm.states, env->dev.mm.actions)) {
@@ -1088,89 +1060,39 @@ void launch_stack_rollout(rl_env *env, const rl_mlp *policy, rl_traj *traj) {
     // sixteen floats (MetaMdpWideOps), 19 features, five actions; 550 variates per lane in the trial's serial section
     RL_REQUIRE(env->dev.mm.states == 10 && env->A == 5 && env->D == 19,
                "fused recurrent rollout on wide meta-MDP lanes: built for 10 x 5");
-#define ROLL(CELL, LIN)                                                                                               \
-  hipLaunchKernelGGL((k_stack_rollout<CELL, MetaMdpWideOps, 19, LIN, 5>), grid, blk, 0, env->eng->stream, net, ws, \
-                     env->dev, env->st, traj->d, env->t_global)
-    if (lstm) {
-      if (lin) ROLL(LSTM, true);
-      else ROLL(LSTM, false);
-    } else {
-      if (lin) ROLL(GRU, true);
-      else ROLL(GRU, false);
-    }
-#undef ROLL
-    RL_HIP_CHECK(hipGetLastError());
-    env->t_global += traj->d.T;
-    return;
+    bool built = false;
+    with_cell(policy, [&](auto cell, auto lin) {
+      with_range<(int)RL_META_MDP_MAX + 1, (int)RL_META_MDP_WIDE_MAX_STATES>(env->dev.mm.states, [&](auto s) {
+        with_range<2, (int)RL_META_MDP_MAX>(env->A, [&](auto a) {
+          constexpr int SS = decltype(s)::value, AA = decltype(a)::value;
+          if constexpr (meta_mdp_wide_fused_shape(SS, AA)) {
+            fused(cell, lin, MetaMdpWideOps{}, Int<SS + AA + 4>{}, a);
+            built = true;
+          }
+        });
+      });
+    });
+    return fused_done(built, "wide meta-MDP lanes");
   }
   if (env->kind == RL_ENV_PARTITION && env->eng->kernel_variant != 1 && env->D == RL_PARTITION_MAX_OBS_DIM) {
     // PartitionGame lanes under a visible limit (24 features, the partition-game experiment's shape): all T steps in one
     // launch.  23 features (no or a latent limit) and kernel variant 1 keep the launch sequence per step, below.
     RL_REQUIRE(env->A == 2, "fused recurrent rollout on PartitionGame lanes: two actions");
-#define ROLL(CELL, LIN)                                                                                             \
-  hipLaunchKernelGGL((k_stack_rollout<CELL, PartitionOps, 24, LIN, 2>), grid, blk, 0, env->eng->stream, net, ws, \
-                     env->dev, env->st, traj->d, env->t_global)
-    if (lstm) {
-      if (lin) ROLL(LSTM, true);
-      else ROLL(LSTM, false);
-    } else {
-      if (lin) ROLL(GRU, true);
-      else ROLL(GRU, false);
-    }
-#undef ROLL
-    RL_HIP_CHECK(hipGetLastError());
-    env->t_global += traj->d.T;
-    return;
+    with_cell(policy, [&](auto cell, auto lin) {
+      fused(cell, lin, PartitionOps{}, Int<(int)RL_PARTITION_MAX_OBS_DIM>{}, Int<2>{});
+    });
+    return fused_done(true, "PartitionGame lanes");
   }
   launch_rollout_stepwise(env, traj, z, [&](uint32_t step) {
     const int first = step == 0 ? 1 : 0, parity = (int)(step & 1);
     // (the step before has been recorded by now: its successor codes are in the trajectory)
     const uint8_t *flag_prev = traj->d.flag + (size_t)(step == 0 ? 0 : step - 1) * traj->d.n;
-#define STEP(CELL, LIN, NQ)                                                                                         \
-  hipLaunchKernelGGL((k_stack_step<CELL, LIN, NQ>), grid, blk, 0, env->eng->stream, net, ws, env->d_obs, flag_prev, \
-                     first, parity, z)
-#define STEP_OUT(CELL, LIN)              \
-  do {                                   \
-    if (nq == 12) STEP(CELL, LIN, 12);   \
-    else if (nq == 8) STEP(CELL, LIN, 8); \
-    else STEP(CELL, LIN, 2);             \
-  } while (0)
-    if (lstm) {
-      if (lin) STEP_OUT(LSTM, true);
-      else STEP_OUT(LSTM, false);
-    } else {
-      if (lin) STEP_OUT(GRU, true);
-      else STEP_OUT(GRU, false);
-    }
-#undef STEP_OUT
-#undef STEP
+    with_cell_and_head(policy, "launch_stack_rollout: head classes of 2, 8 and 12 outputs", [&](auto cell, auto lin, auto q) {
+      hipLaunchKernelGGL((k_stack_step<decltype(cell)::value, decltype(lin)::value, decltype(q)::value>), grid, blk, 0,
+                         env->eng->stream, net, ws, env->d_obs, flag_prev, first, parity, z);
+    });
   });
 }
-
-namespace {
-// k_stack_collect_dqn over more than two actions (rl_dqn_create_finite): index-env lanes alone.  The bandit of NA arms has
-// 5 features and MemoryGame(NA, h) has NA + h [+ 1]: the (NA, D) pairs no env has are not built.
-template <int CELL, bool LIN, int NA>
-void collect_dqn_actions(uint32_t D, dim3 grid, dim3 blk, hipStream_t stream, const StackNet &net, const StackWs &ws,
-                         const rl_env *env, const ReplayDev &rp, float *xobs, size_t xstride, uint32_t T, uint64_t p_int,
-                         int always_explore, uint8_t *d_flags) {
-  auto go = [&](auto d) {
-    constexpr int DD = decltype(d)::value;
-    if constexpr (DD == 5 || DD > NA)
-      hipLaunchKernelGGL((k_stack_collect_dqn<CELL, IndexOps, DD, LIN, NA>), grid, blk, 0, stream, net, ws, env->dev,
-                         env->st, rp, xobs, xstride, T, p_int, always_explore, d_flags, env->t_global);
-    else
-      throw RlError(RL_ERR_UNSUPPORTED, "recurrent DQN collection: no index env has this (actions, features) pair");
-  };
-  switch (D) {
-    case 4: go(std::integral_constant<int, 4>{}); break;
-    case 5: go(std::integral_constant<int, 5>{}); break;
-    case 6: go(std::integral_constant<int, 6>{}); break;
-    case 7: go(std::integral_constant<int, 7>{}); break;
-    default: go(std::integral_constant<int, 8>{}); break;
-  }
-}
-}  // namespace
 
 void launch_stack_collect_dqn(rl_env *env, const rl_mlp *qnet, rl_traj *roll, const ReplayDev &rp, uint32_t T,
                               uint64_t p_int, int always_explore, uint8_t *d_flags) {
@@ -1183,68 +1105,30 @@ void launch_stack_collect_dqn(rl_env *env, const rl_mlp *qnet, rl_traj *roll, co
   const StackWs ws = stack_ws(roll);
   const dim3 grid(cdiv_k(rp.N, SL)), blk(SL * SW);
   const size_t xstride = (size_t)(roll->d.T + 1) * roll->d.n;
-  const bool lstm = qnet->kind == RL_MODULE_LSTM_MLP, lin = qnet->linear_tail(), cartpole = env->kind == RL_ENV_CARTPOLE;
+  const bool cartpole = env->kind == RL_ENV_CARTPOLE;
   const bool index_env = env->kind == RL_ENV_CHAIN || env->kind == RL_ENV_MEMORY || env->kind == RL_ENV_BANDIT;
   if (!(cartpole ? env->D == 4 || env->D == 5 : index_env && env->D >= 4 && env->D <= 8))
     throw RlError(RL_ERR_UNSUPPORTED, "recurrent DQN collection: CartPole lanes of 4 or 5 features, index-env lanes of 4..8");
-  if (env->A > 2) {
-    RL_REQUIRE(index_env, "recurrent DQN collection over more than two actions: index-env lanes");
-#define COLLECT_NA(CELL, LIN, NA)                                                                                     \
-  case NA:                                                                                                            \
-    collect_dqn_actions<CELL, LIN, NA>(env->D, grid, blk, env->eng->stream, net, ws, env, rp, roll->d.obs, xstride, T, \
-                                       p_int, always_explore, d_flags);                                              \
-    break
-#define COLLECT_ACTIONS(CELL, LIN) \
-  do {                             \
-    switch (env->A) {              \
-      COLLECT_NA(CELL, LIN, 3);    \
-      COLLECT_NA(CELL, LIN, 4);    \
-      COLLECT_NA(CELL, LIN, 5);    \
-      COLLECT_NA(CELL, LIN, 6);    \
-      COLLECT_NA(CELL, LIN, 7);    \
-      default:                     \
-        COLLECT_NA(CELL, LIN, 8);  \
-    }                              \
-  } while (0)
-    if (lstm) {
-      if (lin) COLLECT_ACTIONS(LSTM, true);
-      else COLLECT_ACTIONS(LSTM, false);
-    } else {
-      if (lin) COLLECT_ACTIONS(GRU, true);
-      else COLLECT_ACTIONS(GRU, false);
-    }
-#undef COLLECT_ACTIONS
-#undef COLLECT_NA
-    RL_HIP_CHECK(hipGetLastError());
-    return;
-  }
-#define COLLECT(CELL, LIN, ENV, DD)                                                                                      \
-  hipLaunchKernelGGL((k_stack_collect_dqn<CELL, ENV, DD, LIN>), grid, blk, 0, env->eng->stream, net, ws, env->dev,      \
-                     env->st, rp, roll->d.obs, xstride, T, p_int, always_explore, d_flags, env->t_global)
-#define COLLECT_ENV(CELL, LIN)                            \
-  do {                                                    \
-    if (cartpole) {                                       \
-      if (env->D == 5) COLLECT(CELL, LIN, CartPoleOps, 5); \
-      else COLLECT(CELL, LIN, CartPoleOps, 4);            \
-    } else {                                              \
-      switch (env->D) {                                   \
-        case 4: COLLECT(CELL, LIN, IndexOps, 4); break;   \
-        case 5: COLLECT(CELL, LIN, IndexOps, 5); break;   \
-        case 6: COLLECT(CELL, LIN, IndexOps, 6); break;   \
-        case 7: COLLECT(CELL, LIN, IndexOps, 7); break;   \
-        default: COLLECT(CELL, LIN, IndexOps, 8); break;  \
-      }                                                   \
-    }                                                     \
-  } while (0)
-  if (lstm) {
-    if (lin) COLLECT_ENV(LSTM, true);
-    else COLLECT_ENV(LSTM, false);
-  } else {
-    if (lin) COLLECT_ENV(GRU, true);
-    else COLLECT_ENV(GRU, false);
-  }
-#undef COLLECT_ENV
-#undef COLLECT
+  if (env->A > 2) RL_REQUIRE(index_env, "recurrent DQN collection over more than two actions: index-env lanes");
+  with_cell(qnet, [&](auto cell, auto lin) {
+    env_dispatch(env, [&](auto ops, auto d) {  // (CartPole or index-env lanes, by the refusals above)
+      using Env = decltype(ops);
+      constexpr int D = decltype(d)::value;
+      // more than two actions (rl_dqn_create_finite): index-env lanes alone.  The bandit of NA arms has 5 features and
+      // MemoryGame(NA, h) has NA + h [+ 1]: the (NA, D) pairs no env has are not built.
+      const bool built = with_range<2, 8>(env->A, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        constexpr bool env_built = std::is_same_v<Env, CartPoleOps> || std::is_same_v<Env, IndexOps>;
+        if constexpr (env_built && (NA == 2 || (std::is_same_v<Env, IndexOps> && (D == 5 || D > NA))))
+          hipLaunchKernelGGL((k_stack_collect_dqn<decltype(cell)::value, Env, D, decltype(lin)::value, NA>), grid, blk, 0,
+                             env->eng->stream, net, ws, env->dev, env->st, rp, roll->d.obs, xstride, T, p_int,
+                             always_explore, d_flags, env->t_global);
+        else
+          throw RlError(RL_ERR_UNSUPPORTED, "recurrent DQN collection: no index env has this (actions, features) pair");
+      });
+      if (!built) throw RlError(RL_ERR_UNSUPPORTED, "launch_stack_collect_dqn: 2..8 actions");
+    });
+  });
   RL_HIP_CHECK(hipGetLastError());
 }
 
@@ -1261,16 +1145,10 @@ void launch_stack_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_sk
   {
     ProfScope ps(e, RL_K_POLICY_FUSED);
     const dim3 grid(cdiv_k(n, SL)), blk(SL * SW);
-#define BWD(CELL, LIN) \
-  hipLaunchKernelGGL((k_stack_backward<CELL, LIN>), grid, blk, 0, e->stream, net, ws, traj->d, traj->dz, d_skip)
-    if (mod->kind == RL_MODULE_LSTM_MLP) {
-      if (mod->linear_tail()) BWD(LSTM, true);
-      else BWD(LSTM, false);
-    } else {
-      if (mod->linear_tail()) BWD(GRU, true);
-      else BWD(GRU, false);
-    }
-#undef BWD
+    with_cell(mod, [&](auto cell, auto lin) {
+      hipLaunchKernelGGL((k_stack_backward<decltype(cell)::value, decltype(lin)::value>), grid, blk, 0, e->stream, net, ws,
+                         traj->d, traj->dz, d_skip);
+    });
   }
   {
     ProfScope ps(e, RL_K_BACKWARD);
@@ -1315,24 +1193,9 @@ void launch_stack_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tange
   const StackNet net = stack_net(mod, mod->d_params), tv = stack_net(mod, d_tangent);
   const StackWs ws = stack_ws(traj);
   const dim3 grid(cdiv_k(traj->d.n, SL)), blk(SL * SW);
-#define TAN(CELL, LIN, NQ)                                                                                  \
-  hipLaunchKernelGGL((k_stack_tangent<CELL, LIN, NQ>), grid, blk, 0, traj->eng->stream, net, tv, ws, traj->d, \
-                     traj->seq.out, d_skip)
-#define TAN_OUT(CELL, LIN)                \
-  do {                                    \
-    if (nq == 12) TAN(CELL, LIN, 12);     \
-    else if (nq == 8) TAN(CELL, LIN, 8);  \
-    else TAN(CELL, LIN, 2);               \
-  } while (0)
-  const int nq = out_class(mod);
-  if (mod->kind == RL_MODULE_LSTM_MLP) {
-    if (mod->linear_tail()) TAN_OUT(LSTM, true);
-    else TAN_OUT(LSTM, false);
-  } else {
-    if (mod->linear_tail()) TAN_OUT(GRU, true);
-    else TAN_OUT(GRU, false);
-  }
-#undef TAN_OUT
-#undef TAN
+  with_cell_and_head(mod, "launch_stack_tangent: head classes of 2, 8 and 12 outputs", [&](auto cell, auto lin, auto q) {
+    hipLaunchKernelGGL((k_stack_tangent<decltype(cell)::value, decltype(lin)::value, decltype(q)::value>), grid, blk, 0,
+                       traj->eng->stream, net, tv, ws, traj->d, traj->seq.out, d_skip);
+  });
   RL_HIP_CHECK(hipGetLastError());
 }

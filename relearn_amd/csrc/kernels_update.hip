@@ -692,24 +692,15 @@ void launch_policy_pass(rl_traj *traj, const rl_mlp *policy, int mode, const flo
   dim3 g(traj->nbB), b(256);
   hipStream_t s = traj->eng->stream;
   int H = (int)policy->hidden;
-#define PASS(DD, MM)                                                                                           \
-  hipLaunchKernelGGL((k_policy_pass<DD, MM>), g, b, 0, s, traj->d, policy->d_params, d_tangent, H, traj->lp0, \
-                     traj->dz, traj->slabB, inv_B, d_skip, clip_lo, clip_hi)
   if (mode == PASS_DQN) inv_B = 2.0f / (float)B_total;
-  if (traj->d.D == 5) {
-    if (mode == PASS_INIT) PASS(5, PASS_INIT);
-    else if (mode == PASS_EVAL) PASS(5, PASS_EVAL);
-    else if (mode == PASS_DQN) PASS(5, PASS_DQN);
-    else if (mode == PASS_PPO) PASS(5, PASS_PPO);
-    else PASS(5, PASS_JVP);
-  } else {
-    if (mode == PASS_INIT) PASS(4, PASS_INIT);
-    else if (mode == PASS_EVAL) PASS(4, PASS_EVAL);
-    else if (mode == PASS_DQN) PASS(4, PASS_DQN);
-    else if (mode == PASS_PPO) PASS(4, PASS_PPO);
-    else PASS(4, PASS_JVP);
-  }
-#undef PASS
+  bool built = false;
+  with_one_of<4, 5>(traj->d.D, [&](auto d) {
+    built = with_range<PASS_INIT, PASS_PPO>(mode, [&](auto mm) {  // (every mode of PolicyPassMode)
+      hipLaunchKernelGGL((k_policy_pass<decltype(d)::value, decltype(mm)::value>), g, b, 0, s, traj->d, policy->d_params,
+                         d_tangent, H, traj->lp0, traj->dz, traj->slabB, inv_B, d_skip, clip_lo, clip_hi);
+    });
+  });
+  if (!built) throw RlError(RL_ERR_UNSUPPORTED, "launch_policy_pass: 4 or 5 observation features, a mode of PolicyPassMode");
 }
 
 void launch_critic_fwd(rl_traj *traj, const rl_mlp *critic, uint64_t B_total) {
@@ -717,12 +708,11 @@ void launch_critic_fwd(rl_traj *traj, const rl_mlp *critic, uint64_t B_total) {
   if (critic->general) return launch_gen_critic_fwd(traj, critic, B_total);
   float two_over_B = 2.0f / (float)B_total;
   dim3 g(traj->nbB), b(256);
-  if (traj->d.D == 5)
-    hipLaunchKernelGGL(k_critic_fwd<5>, g, b, 0, traj->eng->stream, traj->d, critic->d_params, (int)critic->hidden,
-                       traj->dz, traj->slabB, two_over_B);
-  else
-    hipLaunchKernelGGL(k_critic_fwd<4>, g, b, 0, traj->eng->stream, traj->d, critic->d_params, (int)critic->hidden,
-                       traj->dz, traj->slabB, two_over_B);
+  const bool built = with_one_of<4, 5>(traj->d.D, [&](auto d) {
+    hipLaunchKernelGGL(k_critic_fwd<decltype(d)::value>, g, b, 0, traj->eng->stream, traj->d, critic->d_params,
+                       (int)critic->hidden, traj->dz, traj->slabB, two_over_B);
+  });
+  if (!built) throw RlError(RL_ERR_UNSUPPORTED, "launch_critic_fwd: 4 or 5 observation features");
 }
 
 void launch_mlp_backward(rl_traj *traj, const rl_mlp *mlp, const int32_t *d_skip) {
@@ -733,15 +723,15 @@ void launch_mlp_backward(rl_traj *traj, const rl_mlp *mlp, const int32_t *d_skip
   size_t plane = (size_t)(traj->d.T + 1) * traj->d.n;
   hipStream_t s = traj->eng->stream;
   uint32_t P = (uint32_t)mlp->P;
-#define BWD(DD, AA)                                                                                            \
-  hipLaunchKernelGGL((k_mlp_backward<DD, AA>), g, b, 0, s, mlp->d_params, (int)mlp->hidden, traj->d.obs, plane, \
-                     traj->dz, (size_t)traj->B, traj->bwd_chunk, traj->slabA, P, d_skip)
-  if (traj->d.D == 5 && mlp->out_dim == 2) BWD(5, 2);
-  else if (traj->d.D == 5 && mlp->out_dim == 1) BWD(5, 1);
-  else if (traj->d.D == 4 && mlp->out_dim == 2) BWD(4, 2);
-  else if (traj->d.D == 4 && mlp->out_dim == 1) BWD(4, 1);
-  else throw RlError(RL_ERR_UNSUPPORTED, "backward: unsupported (obs_dim, out_dim)");
-#undef BWD
+  bool built = false;
+  with_one_of<4, 5>(traj->d.D, [&](auto d) {
+    built = with_one_of<1, 2>(mlp->out_dim, [&](auto a) {
+      hipLaunchKernelGGL((k_mlp_backward<decltype(d)::value, decltype(a)::value>), g, b, 0, s, mlp->d_params,
+                         (int)mlp->hidden, traj->d.obs, plane, traj->dz, (size_t)traj->B, traj->bwd_chunk, traj->slabA, P,
+                         d_skip);
+    });
+  });
+  if (!built) throw RlError(RL_ERR_UNSUPPORTED, "backward: unsupported (obs_dim, out_dim)");
 }
 
 // columns of the reduced vector per workgroup of the slab reductions: 16 (57 - 65 workgroups pull the slab, a lane has
@@ -750,21 +740,19 @@ void launch_mlp_backward(rl_traj *traj, const rl_mlp *mlp, const int32_t *d_skip
 // (vectors of more than 2,048 entries — the recurrent chains, wide general MLPs — are bandwidth-, not latency-bound and
 // keep the wide form)
 static int reduce_width(uint32_t P) { return P + 4 > 2048 ? 64 : 16; }
-// the instantiation of a width (never a branch inside a kernel)
-#define RL_WITH_WIDTH(WIDTH, CALL)         \
-  if ((WIDTH) == 64) {                     \
-    constexpr int CW = 64;                 \
-    CALL;                                  \
-  } else {                                 \
-    constexpr int CW = 16;                 \
-    CALL;                                  \
-  }
+// the instantiation of a width (never a branch inside a kernel): go(Int<16 | 64>{})
+template <class Go>
+static void with_reduce_width(uint32_t P, Go &&go) {
+  if (!with_one_of<16, 64>(reduce_width(P), go)) throw RlError(RL_ERR_UNSUPPORTED, "slab reduction: widths of 16 and 64 columns");
+}
 
 void launch_reduce(rl_traj *traj, uint32_t P, bool useA, bool useB, uint32_t rowsA, uint32_t rowsB) {
   ProfScope ps(traj->eng, RL_K_REDUCE);
-  RL_WITH_WIDTH(reduce_width(P),
-                hipLaunchKernelGGL(k_reduce<CW>, dim3(cdiv(P + 4, CW)), dim3(1024), 0, traj->eng->stream, traj->slabA,
-                                   rowsA, P, traj->slabB, rowsB, traj->vec, useA ? 1 : 0, useB ? 1 : 0));
+  with_reduce_width(P, [&](auto cw) {
+    constexpr int CW = decltype(cw)::value;
+    hipLaunchKernelGGL(k_reduce<CW>, dim3(cdiv(P + 4, CW)), dim3(1024), 0, traj->eng->stream, traj->slabA, rowsA, P,
+                       traj->slabB, rowsB, traj->vec, useA ? 1 : 0, useB ? 1 : 0);
+  });
 }
 
 void launch_trpo_begin(rl_traj *traj, rl_mlp *policy, uint64_t B_total) {
@@ -873,15 +861,12 @@ static OptStep opt_next_step(rl_adam *opt) {
   return k;
 }
 
-// the instantiation of the optimiser's rule (the rule is never a branch inside a kernel)
-#define RL_WITH_RULE(KIND, CALL)                                                      \
-  switch (KIND) {                                                                     \
-    case RL_OPTIMIZER_ADAM: { constexpr int RULE = RL_OPTIMIZER_ADAM; CALL; } break;   \
-    case RL_OPTIMIZER_ADAMW: { constexpr int RULE = RL_OPTIMIZER_ADAMW; CALL; } break; \
-    case RL_OPTIMIZER_SGD: { constexpr int RULE = RL_OPTIMIZER_SGD; CALL; } break;     \
-    case RL_OPTIMIZER_RMSPROP: { constexpr int RULE = RL_OPTIMIZER_RMSPROP; CALL; } break; \
-    default: throw RlError(RL_ERR_INVALID_ARGUMENT, "optimizer: unknown kind");       \
-  }
+// the instantiation of the optimiser's rule (the rule is never a branch inside a kernel): go(Int<RL_OPTIMIZER_*>{})
+template <class Go>
+static void with_opt_rule(int kind, Go &&go) {
+  if (!with_one_of<RL_OPTIMIZER_ADAM, RL_OPTIMIZER_ADAMW, RL_OPTIMIZER_SGD, RL_OPTIMIZER_RMSPROP>(kind, go))
+    throw RlError(RL_ERR_INVALID_ARGUMENT, "optimizer: unknown kind");
+}
 
 void launch_reduce_opt(rl_traj *traj, rl_adam *opt, uint32_t rowsA, uint32_t rowsB, int loss_slot, uint64_t B_total) {
   ProfScope ps(traj->eng, RL_K_REDUCE);
@@ -892,20 +877,21 @@ void launch_reduce_opt(rl_traj *traj, rl_adam *opt, uint32_t rowsA, uint32_t row
   const OptStep k = opt_next_step(opt);
   const OptState st{opt->d_state[0], opt->d_state[1], opt->d_state[2]};
   float *loss_out = loss_slot >= 0 ? traj->losses + loss_slot : (float *)nullptr;
-  // (RULE and CW are constants where this is expanded)
-#define REDUCE_OPT(XCHG, PEERS)                                                                                          \
-  hipLaunchKernelGGL((k_reduce_opt<RULE, CW, XCHG>), dim3(cdiv(P + 4, CW)), dim3(1024), 0, e->stream, traj->slabA, rowsA, \
-                     P, traj->slabB, rowsB, traj->vec, opt->mod->d_params, st, opt->d_step, opt->host_step, k,            \
-                     1.0 / (double)B_total, loss_out, PEERS, wimg_if_current(opt->mod), (int)opt->mod->out_dim,           \
-                     veto_word(traj, opt->mod))
+  auto reduce_opt = [&](auto rule, auto cw, auto xchg, const IpcPeers &peers) {
+    constexpr int CW = decltype(cw)::value;
+    hipLaunchKernelGGL((k_reduce_opt<decltype(rule)::value, CW, decltype(xchg)::value>), dim3(cdiv(P + 4, CW)), dim3(1024), 0,
+                       e->stream, traj->slabA, rowsA, P, traj->slabB, rowsB, traj->vec, opt->mod->d_params, st, opt->d_step,
+                       opt->host_step, k, 1.0 / (double)B_total, loss_out, peers, wimg_if_current(opt->mod),
+                       (int)opt->mod->out_dim, veto_word(traj, opt->mod));
+  };
   if (e->ipc_active) {
     ProfScope pa(e, RL_K_ALLREDUCE);  // counted as a collective as well: the exchange runs inside this launch
-    constexpr int RULE = RL_OPTIMIZER_ADAM, CW = 64;  // (a chunk of the exchange is 64 columns)
-    REDUCE_OPT(true, ipc_peers_next(e));
+    reduce_opt(Int<RL_OPTIMIZER_ADAM>{}, Int<64>{}, std::true_type{}, ipc_peers_next(e));  // (a chunk of the exchange is 64 columns)
   } else {
-    RL_WITH_RULE(opt->cfg.kind, RL_WITH_WIDTH(reduce_width(P), REDUCE_OPT(false, IpcPeers{})));
+    with_opt_rule(opt->cfg.kind, [&](auto rule) {
+      with_reduce_width(P, [&](auto cw) { reduce_opt(rule, cw, std::false_type{}, IpcPeers{}); });
+    });
   }
-#undef REDUCE_OPT
 }
 
 static void enqueue_opt_step(rl_adam *opt, hipStream_t stream, const float *d_grad, const float *loss_sum, double inv_B,
@@ -913,10 +899,11 @@ static void enqueue_opt_step(rl_adam *opt, hipStream_t stream, const float *d_gr
   uint32_t P = (uint32_t)opt->mod->P;
   const OptStep k = opt_next_step(opt);
   const OptState st{opt->d_state[0], opt->d_state[1], opt->d_state[2]};
-  RL_WITH_RULE(opt->cfg.kind,
-               hipLaunchKernelGGL(k_opt_step<RULE>, dim3((P + SB - 1) / SB), dim3(SB), 0, stream, opt->mod->d_params,
-                                  d_grad, st, opt->d_step, P, opt->host_step, k, loss_sum, inv_B, loss_out, comm_err,
-                                  wimg_if_current(opt->mod), (int)opt->mod->out_dim, veto));
+  with_opt_rule(opt->cfg.kind, [&](auto rule) {
+    hipLaunchKernelGGL(k_opt_step<decltype(rule)::value>, dim3((P + SB - 1) / SB), dim3(SB), 0, stream, opt->mod->d_params,
+                       d_grad, st, opt->d_step, P, opt->host_step, k, loss_sum, inv_B, loss_out, comm_err,
+                       wimg_if_current(opt->mod), (int)opt->mod->out_dim, veto);
+  });
 }
 
 void launch_opt_step(rl_traj *traj, rl_adam *opt, int loss_slot, uint64_t B_total) {
