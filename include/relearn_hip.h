@@ -487,8 +487,9 @@ int32_t rl_mlp_create_config(rl_engine *engine, uint32_t in_dim, const uint32_t 
  * as many observation planes through rl_policy_gradient, rl_policy_fvp, rl_policy_loss_kl, rl_trpo_update, rl_ppo_update,
  * rl_reinforce_update, rl_critic_gradient, rl_critic_update, rl_values_opt_update, rl_gae and rl_actor_critic_update
  * (with _begin and _finish), and rl_rollout on RL_ENV_PARTITION lanes (on other lanes -> RL_ERR_UNSUPPORTED).  With bias
- * vectors and one hidden layer of at most 64 units its update passes are single fused matrix-pipe launches
- * (relearn_amd/csrc/kernels_wide_mfma.hip); other shapes run the per-layer kernels. */
+ * vectors and one hidden layer its update passes are single fused matrix-pipe launches: at most 64 units on
+ * relearn_amd/csrc/kernels_wide_mfma.hip, 65 to 128 (the reference's default hidden_sizes = [128]) on
+ * relearn_amd/csrc/kernels_wide_split.hip; other shapes run the per-layer kernels (rl_traj_last_pass_path tells). */
 int32_t rl_mlp_create_wide(rl_engine *engine, uint32_t in_dim, const uint32_t *hidden_sizes, uint32_t n_hidden,
                            uint32_t out_dim, int32_t activation, int32_t output_activation, int32_t bias, rl_mlp **out);
 int32_t rl_mlp_destroy(rl_mlp *mlp);
@@ -675,6 +676,14 @@ int32_t rl_traj_create_wide24(rl_engine *engine, uint64_t n_lanes, uint64_t hori
 int32_t rl_traj_destroy(rl_traj *traj);
 int32_t rl_traj_field_bytes(const rl_traj *traj, int32_t field, uint64_t *bytes);
 int32_t rl_traj_read(rl_traj *traj, int32_t field, void *host, uint64_t bytes);
+/* Which kernel family the last gradient / evaluation pass over this trajectory actually launched (every update entry
+ * point is made of such passes: rl_policy_gradient, rl_policy_fvp, rl_policy_loss_kl, rl_critic_gradient and the
+ * update loops built from them); NONE before any pass.  The reference's default MlpConfig is hidden_sizes = [128]
+ * (src/torch/modules/ff/mlp.rs:13-34): at 9 to 24 inputs that shape reports WIDE_SPLIT, at most 64 units WIDE_MFMA,
+ * and PER_LAYER says that no fused kernel is built for the shape (or that the engine runs kernel variant 1). */
+typedef enum { RL_PASS_PATH_NONE = 0, RL_PASS_PATH_PER_LAYER = 1, RL_PASS_PATH_FUSED_5_128 = 2, RL_PASS_PATH_GEN_MFMA = 3,
+               RL_PASS_PATH_WIDE_MFMA = 4, RL_PASS_PATH_WIDE_SPLIT = 5, RL_PASS_PATH_RECURRENT = 6 } rl_pass_path;
+int32_t rl_traj_last_pass_path(const rl_traj *traj, int32_t *path_out);
 /* upload (tests: feed oracle-generated trajectories / advantages to the update kernels) */
 int32_t rl_traj_write(rl_traj *traj, int32_t field, const void *host, uint64_t bytes);
 

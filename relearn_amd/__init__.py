@@ -40,6 +40,8 @@ BANDIT_AGENT_KINDS = {"random": BANDIT_AGENT_RANDOM, "tabular_q": BANDIT_AGENT_T
  BANDIT_STATE_LN_TABLE, BANDIT_STATE_LOW_COUNTS, BANDIT_STATE_HIGH_COUNTS) = range(7)
 (TRAJ_OBS, TRAJ_ACTION, TRAJ_REWARD, TRAJ_FLAG, TRAJ_TERM_OBS, TRAJ_VALUES, TRAJ_ADVANTAGES,
  TRAJ_RETURNS, TRAJ_TARGETS) = range(9)
+(PASS_PATH_NONE, PASS_PATH_PER_LAYER, PASS_PATH_FUSED_5_128, PASS_PATH_GEN_MFMA, PASS_PATH_WIDE_MFMA, PASS_PATH_WIDE_SPLIT,
+ PASS_PATH_RECURRENT) = range(7)
 VALUE_TARGET_REWARD_TO_GO, VALUE_TARGET_ONE_STEP_TD = 0, 1
 OPTIMIZER_ADAM, OPTIMIZER_ADAMW, OPTIMIZER_SGD, OPTIMIZER_RMSPROP = 0, 1, 2, 3
 KERNEL_CLASSES = ["env_step", "rollout", "values", "gae", "policy_pass", "backward", "reduce", "small",
@@ -56,7 +58,7 @@ ABI_SYMBOLS = [
     "rl_env_set_state",
     "rl_mlp_create", "rl_mlp_create_layers", "rl_mlp_create_config", "rl_mlp_create_wide", "rl_mlp_destroy", "rl_mlp_num_params", "rl_mlp_init", "rl_mlp_init_with", "rl_params_get", "rl_params_set",
     "rl_mlp_forward", "rl_gru_mlp_create", "rl_lstm_mlp_create", "rl_rnn_mlp_create", "rl_rnn_mlp_create_config", "rl_rnn_linear_create", "rl_rnn_chain_config_default", "rl_rnn_chain_create", "rl_rnn_chain_create_wide", "rl_rnn_chain_create_wide20", "rl_rnn_chain_create_wide24", "rl_rnn_mlp_init_with", "rl_seq_forward",
-    "rl_traj_create", "rl_traj_create_wide", "rl_traj_create_wide24", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write",
+    "rl_traj_create", "rl_traj_create_wide", "rl_traj_create_wide24", "rl_traj_destroy", "rl_traj_field_bytes", "rl_traj_read", "rl_traj_write", "rl_traj_last_pass_path",
     "rl_rollout", "rl_gae",
     "rl_trpo_config_default", "rl_trpo_update", "rl_policy_gradient", "rl_policy_fvp", "rl_policy_loss_kl",
     "rl_adam_config_default", "rl_adam_create", "rl_adam_destroy", "rl_adam_step_host",
@@ -1053,6 +1055,12 @@ class Trajectory(_Handle):
         arr, ap = _ptr(arr, _TRAJ_DTYPES[field])
         assert arr.shape == self.shape(field), (arr.shape, self.shape(field))
         _check(lib().rl_traj_write(self.h, C.c_int32(field), ap, C.c_uint64(arr.nbytes)), self.eng.h)
+
+    def last_pass_path(self):
+        """PASS_PATH_*: the kernel family the last gradient / evaluation pass over this trajectory launched"""
+        out = C.c_int32(-1)
+        _check(lib().rl_traj_last_pass_path(self.h, C.byref(out)), self.eng.h)
+        return out.value
 
     def read_all(self):
         return dict(obs=self.read(TRAJ_OBS), action=self.read(TRAJ_ACTION), reward=self.read(TRAJ_REWARD),

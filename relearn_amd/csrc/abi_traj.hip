@@ -170,6 +170,13 @@ int32_t rl_traj_field_bytes(const rl_traj *t, int32_t field, uint64_t *bytes) {
   });
 }
 
+int32_t rl_traj_last_pass_path(const rl_traj *t, int32_t *path_out) {
+  return guarded(t ? t->eng : nullptr, [&] {
+    RL_REQUIRE(t && path_out, "NULL argument");
+    *path_out = t->last_pass_path;
+  });
+}
+
 int32_t rl_traj_read(rl_traj *t, int32_t field, void *host, uint64_t bytes) {
   return guarded(t ? t->eng : nullptr, [&] {
     RL_REQUIRE(t && host, "NULL argument");

@@ -49,6 +49,7 @@ SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
     rl_allreduce_sum_f32(traj->eng, traj->vec + (grad ? 0 : P), (grad ? P : 0) + (row.sums ? 4 : 0));
   };
   if (rl_module_is_recurrent(mod->kind)) {
+    traj->last_pass_path = RL_PASS_PATH_RECURRENT;
     // teacher-forced forward (activation record) -> d loss / d outputs -> [backward through time -> weight gradients]
     // -> vec[0..P), and the per-sample sums through slab B.  A Fisher-vector product starts from the record of the last
     // pass with a backward instead: vec[0..P) <- J^T (diag(p) - p p^T) J v / B
@@ -86,15 +87,22 @@ SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
   // backward, and the slab rows of those two
   bool fused = false;
   if (traj->eng->kernel_variant == 0) {  // (1: the v1 reference kernels only)
-    if (mod->wide && row.fused != FUSED_NONE)  // (9 to 24 inputs: kernels_wide_mfma.hip, or the per-layer kernels)
-      fused = launch_wide_mfma(traj, mod, critic ? RL_GEN_CRITIC : (int)req.kind, req.tangent, Bt, req.skip, req.clip_lo,
-                               req.clip_hi);
-    else if (row.fused == FUSED_POLICY)
+    if (mod->wide && row.fused != FUSED_NONE) {
+      // (9 to 24 inputs: kernels_wide_mfma.hip, then kernels_wide_split.hip — which records its path itself — or the
+      // per-layer kernels)
+      const int mode = critic ? RL_GEN_CRITIC : (int)req.kind;
+      fused = launch_wide_mfma(traj, mod, mode, req.tangent, Bt, req.skip, req.clip_lo, req.clip_hi);
+      if (fused) traj->last_pass_path = RL_PASS_PATH_WIDE_MFMA;
+      else fused = launch_wide_split(traj, mod, mode, req.tangent, Bt, req.skip, req.clip_lo, req.clip_hi);
+    } else if (row.fused == FUSED_POLICY) {
       fused = launch_policy_v2(traj, mod, req.kind, req.tangent, Bt, req.skip, req.clip_lo, req.clip_hi, req.keep);
-    else if (row.fused == FUSED_CRITIC)
+    } else if (row.fused == FUSED_CRITIC) {
       fused = launch_critic_step_v2(traj, mod, Bt);
+    }
+    if (fused && !mod->wide) traj->last_pass_path = mod->general ? RL_PASS_PATH_GEN_MFMA : RL_PASS_PATH_FUSED_5_128;
   }
   if (!fused) {
+    traj->last_pass_path = RL_PASS_PATH_PER_LAYER;
     if (critic) launch_critic_fwd(traj, mod, Bt);
     else launch_policy_pass(traj, mod, req.kind, req.tangent, Bt, req.skip, req.clip_lo, req.clip_hi);
     if (row.backward) launch_mlp_backward(traj, mod, req.skip);

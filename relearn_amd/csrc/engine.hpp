@@ -342,6 +342,7 @@ struct rl_traj {
   TrpoStateDev *trpo = nullptr;
   uint32_t nbA = 0, nbB = 0, nbV2 = 0, nbC = 0, Pmax = 0, max_losses = 0;
   uint32_t last_rows = 0;   // slab rows the last fused pass (launch_policy_v2 / launch_critic_step_v2) wrote
+  int32_t last_pass_path = RL_PASS_PATH_NONE;  // kernel family of the last run_pass (rl_traj_last_pass_path)
   // the auxiliary chain's own copies (rl_actor_critic_update; swapped in by AuxChain, allocated on first use at the
   // sizes the main ones have then)
   double *aux_slabA = nullptr, *aux_slabB = nullptr;

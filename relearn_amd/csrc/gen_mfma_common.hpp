@@ -1,7 +1,7 @@
 // gen_mfma_common.hpp — what the fused matrix-pipe kernels of general MLPs share (kernels_gen_mfma.hip: at most seven
-// inputs; kernels_wide_mfma.hip: 9 to 24): the LDS weight image and its index functions, the exact-piece products, the
-// on-pipe transposition, the per-sample loss terms, and the tile walk, f32 -> f64 flush and epilogue of DESIGN 27.
-// Everything here has internal linkage: each of the two units compiles its own copy.
+// inputs; kernels_wide_mfma.hip and kernels_wide_split.hip: 9 to 24): the LDS weight image and its index functions, the
+// exact-piece products, the on-pipe transposition, the per-sample loss terms, and the tile walk, f32 -> f64 flush and
+// epilogue of DESIGN 27.  Everything here has internal linkage: each of the units compiles its own copy.
 #pragma once
 #include <mutex>
 #include <set>
@@ -399,6 +399,32 @@ __device__ __forceinline__ TileIn gm_load_tile(const TrajDev &tr, const GmArgs &
     }
   }
   return o;
+}
+
+// ---- layer 0 of a wide module (kernels_wide_mfma.hip, kernels_wide_split.hip): 32 padded input rows
+constexpr int WM_L0 = 2;  // k-steps of layer 0
+constexpr int WM_MAX_IN = 24;
+// the observation tile of tile t: feature urow(r, kb) of the lane's sample in register r.  The kernel reads it twice, for
+// the forward and again (from the cache) for layer 0's weight gradient, instead of keeping its 16 registers — or its 24
+// of packed pieces — alive across the tile's chains.  (The lane's column
+// through a register the optimiser cannot see through, or the two reads become one value that lives across the tile.)
+__device__ __forceinline__ f32x16 wm_load_obs(const TrajDev &tr, const GmArgs &g, const GmLane &w, size_t t) {
+  int mo = w.m;
+  asm volatile("" : "+v"(mo));
+  const uint32_t sidx = (uint32_t)t * 32u + (uint32_t)mo;
+  const bool valid = t < w.n_tiles && sidx < w.B32;
+  f32x16 x;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int k = urow(r, w.kb);
+    float v = 0.0f;
+    if (valid) {
+      if (k < g.in_dim) v = tr.obs[(uint32_t)k * w.plane32 + sidx];
+      else if (k == g.in_dim) v = 1.0f;
+    }
+    x[r] = v;
+  }
+  return x;
 }
 
 // the B operand pieces of the input tile: the lane's four inputs (bias input included), by truncation

@@ -187,6 +187,11 @@ bool launch_gen_mfma(rl_traj *t, const rl_mlp *m, int mode, const float *d_tange
 bool wide_mfma_fits(const rl_traj *t, const rl_mlp *m);
 bool launch_wide_mfma(rl_traj *t, const rl_mlp *m, int mode, const float *d_tangent, uint64_t B_total,
                       const int32_t *d_skip, float clip_lo, float clip_hi);
+// kernels_wide_split.hip: ... with one hidden layer of 65 to 128 units, a tile shared by a team of waves (records
+// RL_PASS_PATH_WIDE_SPLIT in t->last_pass_path; false: shape not built)
+bool wide_split_fits(const rl_traj *t, const rl_mlp *m);
+bool launch_wide_split(rl_traj *t, const rl_mlp *m, int mode, const float *d_tangent, uint64_t B_total,
+                       const int32_t *d_skip, float clip_lo, float clip_hi);
 const float *launch_gen_values(rl_traj *t, const rl_mlp *critic);  // -> seq.out / seq.succ (plane 0); returns V(obs[T]) [n]
 void launch_gen_rollout(rl_env *env, const rl_mlp *policy, rl_traj *t);
 void launch_rollout_stepwise(rl_env *env, rl_traj *t, const float *z, const std::function<void(uint32_t)> &forward);

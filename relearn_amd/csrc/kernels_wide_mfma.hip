@@ -23,42 +23,18 @@
 // Shape: ONE hidden layer of at most 64 units (two 32-unit tiles), with bias vectors; one wave per SIMD, a tile of 32
 // samples per wave and iteration.  The narrow kernel's other one-wave shapes — two layers of at most 64, one of at most
 // 128 — carry 144 accumulator registers, and with layer 0's second k-step the compiler puts 256 to 476 bytes per lane
-// of every gradient mode into scratch (profiles/wide_mlp_kernel_resources.json): they are not built, and such
-// modules, like three-layer and bias-less ones and planes of 2^30 elements, run the per-layer kernels.
+// of every gradient mode into scratch (profiles/wide_mlp_kernel_resources.json): they are not built here.
+// One hidden layer of 65 to 128 units goes on to kernels_wide_split.hip, where a team of waves shares the tile (DESIGN
+// 51); two-layer, three-layer and bias-less modules and planes of 2^30 elements run the per-layer kernels.
 #include "gen_mfma_common.hpp"
 
 namespace {
 
-constexpr int WM_L0 = 2;  // k-steps of layer 0
-constexpr int WM_MAX_IN = 24;
 constexpr int NL = 1, GW = 2;  // hidden layers, 32-unit tiles of the hidden layer
 
 // dynamic LDS: the weight image (PASS_JVP: the tangent's forward fragments beside the parameters')
 constexpr size_t wm_lds_bytes(bool jvp) { return gm_image_bytes(false, GW, NL, jvp, WM_L0); }
 static_assert(wm_lds_bytes(false) == 30976 && wm_lds_bytes(true) == 55808, "k_wide_mfma: LDS bytes");
-
-// the observation tile of tile t: feature urow(r, kb) of the lane's sample in register r.  The kernel reads it twice, for
-// the forward and again (from the cache) for layer 0's weight gradient, instead of keeping its 16 registers — or its 24
-// of packed pieces — alive across the tile's chains.  (The lane's column
-// through a register the optimiser cannot see through, or the two reads become one value that lives across the tile.)
-__device__ __forceinline__ f32x16 wm_load_obs(const TrajDev &tr, const GmArgs &g, const GmLane &w, size_t t) {
-  int mo = w.m;
-  asm volatile("" : "+v"(mo));
-  const uint32_t sidx = (uint32_t)t * 32u + (uint32_t)mo;
-  const bool valid = t < w.n_tiles && sidx < w.B32;
-  f32x16 x;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int k = urow(r, w.kb);
-    float v = 0.0f;
-    if (valid) {
-      if (k < g.in_dim) v = tr.obs[(uint32_t)k * w.plane32 + sidx];
-      else if (k == g.in_dim) v = 1.0f;
-    }
-    x[r] = v;
-  }
-  return x;
-}
 
 template <int MODE>
 __global__ void __launch_bounds__(GWAVES * 64)

@@ -80,6 +80,7 @@ def main():
                 "mean_episode_length": s.episode_length.mean if s.episode_length.count else None,
                 "trpo_status": pst.status, "kl": pst.constraint_val_final, "entropy": pst.entropy,
                 "critic_loss": [cst.loss_first, cst.loss_last],
+                "pass_path": traj.last_pass_path(),  # ra.PASS_PATH_*: the kernel family of the update's last pass
                 "rollout_ms": (t1 - t0) * 1e3, "update_ms": (t2 - t1) * 1e3}
         lines.append(line)
         print(json.dumps(line), flush=True)
