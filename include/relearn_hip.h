@@ -680,9 +680,13 @@ int32_t rl_traj_read(rl_traj *traj, int32_t field, void *host, uint64_t bytes);
  * point is made of such passes: rl_policy_gradient, rl_policy_fvp, rl_policy_loss_kl, rl_critic_gradient and the
  * update loops built from them); NONE before any pass.  The reference's default MlpConfig is hidden_sizes = [128]
  * (src/torch/modules/ff/mlp.rs:13-34): at 9 to 24 inputs that shape reports WIDE_SPLIT, at most 64 units WIDE_MFMA,
- * and PER_LAYER says that no fused kernel is built for the shape (or that the engine runs kernel variant 1). */
+ * and PER_LAYER says that no fused kernel is built for the shape (or that the engine runs kernel variant 1).
+ * RECURRENT_TILE: a GRU-MLP chain of 6 to 24 inputs at GRU 128 / MLP [128], one or two outputs, on a multiple of 32 lanes
+ * ran a gradient pass or a Fisher-vector product on the tile-resident matrix-pipe kernels (kernels_seq_train.hip with the
+ * input side in kernels_seq_in.hip); every other recurrent pass reports RECURRENT, as before. */
 typedef enum { RL_PASS_PATH_NONE = 0, RL_PASS_PATH_PER_LAYER = 1, RL_PASS_PATH_FUSED_5_128 = 2, RL_PASS_PATH_GEN_MFMA = 3,
-               RL_PASS_PATH_WIDE_MFMA = 4, RL_PASS_PATH_WIDE_SPLIT = 5, RL_PASS_PATH_RECURRENT = 6 } rl_pass_path;
+               RL_PASS_PATH_WIDE_MFMA = 4, RL_PASS_PATH_WIDE_SPLIT = 5, RL_PASS_PATH_RECURRENT = 6,
+               RL_PASS_PATH_RECURRENT_TILE = 7 } rl_pass_path;
 int32_t rl_traj_last_pass_path(const rl_traj *traj, int32_t *path_out);
 /* upload (tests: feed oracle-generated trajectories / advantages to the update kernels) */
 int32_t rl_traj_write(rl_traj *traj, int32_t field, const void *host, uint64_t bytes);

@@ -41,7 +41,7 @@ BANDIT_AGENT_KINDS = {"random": BANDIT_AGENT_RANDOM, "tabular_q": BANDIT_AGENT_T
 (TRAJ_OBS, TRAJ_ACTION, TRAJ_REWARD, TRAJ_FLAG, TRAJ_TERM_OBS, TRAJ_VALUES, TRAJ_ADVANTAGES,
  TRAJ_RETURNS, TRAJ_TARGETS) = range(9)
 (PASS_PATH_NONE, PASS_PATH_PER_LAYER, PASS_PATH_FUSED_5_128, PASS_PATH_GEN_MFMA, PASS_PATH_WIDE_MFMA, PASS_PATH_WIDE_SPLIT,
- PASS_PATH_RECURRENT) = range(7)
+ PASS_PATH_RECURRENT, PASS_PATH_RECURRENT_TILE) = range(8)
 VALUE_TARGET_REWARD_TO_GO, VALUE_TARGET_ONE_STEP_TD = 0, 1
 OPTIMIZER_ADAM, OPTIMIZER_ADAMW, OPTIMIZER_SGD, OPTIMIZER_RMSPROP = 0, 1, 2, 3
 KERNEL_CLASSES = ["env_step", "rollout", "values", "gae", "policy_pass", "backward", "reduce", "small",

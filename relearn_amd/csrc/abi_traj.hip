@@ -227,9 +227,15 @@ void traj_ensure_pvec(rl_traj *t, uint64_t P) {
 
 void seq_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
   RL_REQUIRE(rl_module_is_recurrent(mod->kind), "not a recurrent module");
-  if (mod->lane_kernels()) return stack_ensure(t, mod, training);  // lane-per-thread kernels: no tile or width condition
+  // (the wide tile shape needs both families' workspaces: its training passes run the tile kernels, its rollouts, value
+  // forwards and record-less evaluations the lane-per-thread ones)
+  const bool wide = seq_wide_tile_fits(t, mod);
+  if (mod->lane_kernels()) {
+    stack_ensure(t, mod, training);  // lane-per-thread kernels: no tile or width condition
+    if (!wide || !training) return;
+  }
   RL_REQUIRE(t->d.n % 32 == 0, "the recurrent kernels work on tiles of 32 lanes: n_lanes must be a multiple of 32");
-  RL_REQUIRE(t->d.D == 5 && mod->in_dim == 5, "recurrent path: built for 5 observation features");
+  RL_REQUIRE(wide || (t->d.D == 5 && mod->in_dim == 5), "recurrent path: built for 5 observation features");
   SeqDev &q = t->seq;
   uint64_t n = t->d.n, T = t->d.T;
   q.tiles = (uint32_t)(n / 32);  // (the output planes may already exist: the general-MLP path shares them)

@@ -36,7 +36,7 @@ static void seq_gradient_to_flat_order(const rl_mlp *mod, rl_traj *traj) {
 
 // where a training forward of `mod` keeps its activation record (non-NULL asks the forward for one)
 static float *seq_record(rl_traj *traj, const rl_mlp *mod) {
-  return mod->lane_kernels() ? traj->seq.stack.rec : traj->seq.act;
+  return mod->lane_kernels() && !seq_wide_tile_fits(traj, mod) ? traj->seq.stack.rec : traj->seq.act;
 }
 
 SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
@@ -64,7 +64,11 @@ SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
         tangent = mod->x_tan;
       }
       launch_gru_tangent(traj, sc.x, tangent, Bt, req.skip);
+      if (seq_wide_tile_fits(traj, sc.x)) traj->last_pass_path = RL_PASS_PATH_RECURRENT_TILE;
     } else {
+      // (the wide tile shape: every forward that keeps a record, and what follows from that record, on the tile kernels;
+      // an evaluation without one — the line search's — on the lane-per-thread f32 forward, as at five inputs)
+      if (row.backward && seq_wide_tile_fits(traj, sc.x)) traj->last_pass_path = RL_PASS_PATH_RECURRENT_TILE;
       // The record is asked for wherever the pass kind has a backward, also when this request stops before it
       // (forward_only): with a record the tile kernels run the bf16-pipe training forward, without one the f32 forward
       // (launch_gru_seq_forward), and the two round differently.  rl_ppo_update's log pi_0 must come from the forward

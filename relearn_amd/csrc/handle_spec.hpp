@@ -525,6 +525,13 @@ struct ModuleShape {
   bool lane_kernels() const {
     return rnn_layers > 1 || in_dim > 5 || gru_hidden > 128 || hidden > 128 || !has_bias || linear_tail() || out_dim > 2;
   }
+  // A lane-kernel module whose training passes fit the tile kernels with the input side computed apart
+  // (kernels_seq_in.hip): GruMlpConfig at the partition-game experiment's widths — one GRU layer of 128 units with bias
+  // vectors, 6 to 24 inputs, an MLP tail of 128 hidden units, one or two outputs (no twin: the widths are the kernels').
+  bool wide_tile_shape() const {
+    return kind == RL_MODULE_GRU_MLP && rnn_layers == 1 && in_dim >= 6 && in_dim <= 24 && gru_hidden == 128 &&
+           hidden == 128 && has_bias && (out_dim == 1 || out_dim == 2);
+  }
   // ChainConfig<GruConfig | LstmConfig, LinearConfig> (modules/chain.rs:12-54): the recurrent layers -> ReLU -> one
   // Linear(gru_hidden, out_dim).  Marked by `hidden` == 0 on a recurrent kind (the MLP-tail chains have hidden >= 1);
   // flat order [layers .., kernel [out_dim][gru_hidden], bias [out_dim]]: rnn_layer_offset(rnn_layers) is the kernel.

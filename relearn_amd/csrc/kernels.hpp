@@ -218,6 +218,19 @@ void launch_gru_train_head_backward(rl_traj *traj, const rl_mlp *mod, float *d_s
 void launch_gru_train_recur_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip);
 void launch_gru_train_wgrad(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip);
 constexpr uint32_t RL_SEQ_HEAD_ROWS = 512;  // rows of head-gradient partials behind the weight-gradient kernel's chunks
+// A lane-kernel module whose TRAINING passes (record-bearing forward, backward, weight gradients, tangent) run the tile
+// kernels above with the input side in kernels_seq_in.hip: ModuleShape::wide_tile_shape on whole tiles of 32 lanes under
+// engine kernel variant 0.  Rollouts, value forwards, evaluations without a record and every other shape stay on the
+// lane-per-thread kernels.
+inline bool seq_wide_tile_fits(const rl_traj *traj, const rl_mlp *mod) {
+  return mod->wide_tile_shape() && traj->d.n % 32 == 0 && traj->eng->kernel_variant == 0;
+}
+// kernels_seq_in.hip: the input side of those passes, block-parallel on the bf16 matrix pipe
+//   in_proj: planes 0 .. 2 of every block of `dst` (`arrays` planes per block) <- W_ih x + b_ih of the gates r, z, n, with
+//            W_ih / b_ih taken from the flat vector `vec` (the parameters, or a tangent)
+//   in_wgrad: the W_ih and b_ih columns of rows [0, chunks) of seq.wg_slab <- sums over dpre arrays 0 .. 2
+void launch_seq_in_proj(rl_traj *traj, const float *vec, float *dst, int arrays, const int32_t *d_skip);
+void launch_seq_in_wgrad(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip);
 // v_last: [n] V(obs[T]) of every lane for slot T of the value plane (a general critic's: launch_gen_values), or NULL
 void launch_seq_gae(rl_traj *traj, float gamma, float lambda, const float *v_last);
 // one-step TD targets from traj->seq.out / succ (plane 0) -> d.tgt

@@ -766,9 +766,11 @@ void launch_rollout_chain_mlp(rl_env *env, const rl_mlp *policy, rl_traj *traj) 
 
 void launch_gru_seq_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float *d_succ, float *d_act,
                             const int32_t *d_skip) {
-  if (mod->lane_kernels()) return launch_stack_forward(traj, mod, d_out, d_succ, d_act != nullptr, d_skip);
+  // (the wide tile shape: its training forward — a record, no successor evaluations — on the tile kernels)
+  const bool wide_train = d_act != nullptr && d_succ == nullptr && seq_wide_tile_fits(traj, mod);
+  if (mod->lane_kernels() && !wide_train) return launch_stack_forward(traj, mod, d_out, d_succ, d_act != nullptr, d_skip);
   ProfScope ps(traj->eng, RL_K_POLICY_FUSED);
-  RL_REQUIRE(traj->d.D == 5, "recurrent forward: built for 5 observation features");
+  RL_REQUIRE(traj->d.D == 5 || wide_train, "recurrent forward: built for 5 observation features");
   uint32_t tiles = traj->d.n / TL;
   const bool lstm = mod->kind == RL_MODULE_LSTM_MLP;
   // training forward of the GRU chain (activation record, no successor evaluations): the bf16-pipe kernels of

@@ -728,7 +728,8 @@ void launch_seq_critic_dvalues(rl_traj *traj, uint64_t B_total) {
 
 // backward through time + weight-gradient GEMMs + reduction: traj->vec[0..P) <- sum over this rank's samples
 void launch_gru_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip) {
-  if (mod->lane_kernels()) return launch_stack_backward(traj, mod, d_skip);
+  const bool wide = seq_wide_tile_fits(traj, mod);  // (variant 0, GRU: the gru_head branches below)
+  if (mod->lane_kernels() && !wide) return launch_stack_backward(traj, mod, d_skip);
   rl_engine *e = traj->eng;
   const SeqDev &q = traj->seq;
   uint32_t P = (uint32_t)mod->P, blocks = traj->d.T * q.tiles;
@@ -798,6 +799,12 @@ void launch_gru_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip
     if (gru_head && lstm) {
       // every recurrent column from the weight-gradient kernel's rows, the head from the head kernel's
       const uint32_t oW1 = 4 * GH * 5 + 4 * GH * GH + 8 * GH;
+      seg(0, oW1, q.wg_slab, q.chunks);
+      seg(oW1, P, q.wg_slab + (size_t)q.chunks * P, RL_SEQ_HEAD_ROWS);
+    } else if (wide) {
+      // every recurrent column from the chunk rows (W_ih and b_ih: k_seq_in_wgrad; W_hh and b_hh: the weight-gradient
+      // kernel), the head from the head kernel's
+      const uint32_t oW1 = 3 * GH * mod->in_dim + 3 * GH * GH + 6 * GH;
       seg(0, oW1, q.wg_slab, q.chunks);
       seg(oW1, P, q.wg_slab + (size_t)q.chunks * P, RL_SEQ_HEAD_ROWS);
     } else if (gru_head) {

@@ -84,7 +84,11 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_pre(TrajDev tr, const fl
                                                             uint32_t blocks, uint32_t blocks_per_chunk,
                                                             const int32_t *__restrict__ skip) {
   constexpr int NG = Cell::NG;
-  __shared__ float xS[TL][8];
+  // D = 0, "input side elsewhere": k_seq_in_proj (kernels_seq_in.hip) has left V_ih x + v_bih of every block in planes
+  // 0 .. 2 of `stat`; a thread reads its own entries before it writes the static terms over them
+  constexpr bool IN = D > 0;
+  constexpr int DX = IN ? D : 1;
+  __shared__ float xS[IN ? TL : 1][8];
   __shared__ float v2S[2][MH];
   // W1_LDS: the MLP layer's tangent operands, [k-step][thread] (read back by the thread that wrote them): the four gates'
   // 256 operand registers leave no room for these 64 next to the accumulators — the kernel spilt 45 registers with them
@@ -94,17 +98,19 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_pre(TrajDev tr, const fl
   const int n = lane & 31, hf = lane >> 5, j = 32 * wave + n;
   const uint32_t N = tr.n, T = tr.T;
   const size_t plane = (size_t)(T + 1) * N;
-  const GruParams v = seq_params(tangent, D, A, NG);
+  const GruParams v = seq_params(tangent, IN ? D : (int)tr.D, A, NG);
   // the forward's slicing (unit j = 32 * wave + (lane & 31), k parity = lane >> 5), applied to the tangent parameters
-  float whh[NG][GH / 2], wih[NG][D], bih[NG], bhh[NG], w1[Cell::W1_LDS ? 1 : GH / 2];
+  float whh[NG][GH / 2], wih[NG][DX], bih[NG], bhh[NG], w1[Cell::W1_LDS ? 1 : GH / 2];
 #pragma unroll
   for (int gte = 0; gte < NG; ++gte) {
     const int row = gte * GH + j;
 #pragma unroll
     for (int ks = 0; ks < GH / 2; ++ks) whh[gte][ks] = v.Whh[(size_t)row * GH + 2 * ks + hf];
+    if constexpr (IN) {
 #pragma unroll
-    for (int d = 0; d < D; ++d) wih[gte][d] = v.Wih[(size_t)row * D + d];
-    bih[gte] = v.bih[row];
+      for (int d = 0; d < D; ++d) wih[gte][d] = v.Wih[(size_t)row * D + d];
+      bih[gte] = v.bih[row];
+    }
     bhh[gte] = v.bhh[row];
   }
 #pragma unroll
@@ -123,7 +129,7 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_pre(TrajDev tr, const fl
     const float *__restrict__ ab = act + (size_t)blk * SEQ_ARR * GH * TL;
     float *__restrict__ sb = stat + (size_t)blk * DPRE_ARR * GH * TL;
     __syncthreads();
-    if (wave == 0 && lane < TL)
+    if (IN && wave == 0 && lane < TL)
 #pragma unroll
       for (int d = 0; d < D; ++d) xS[lane][d] = tr.obs[d * plane + (size_t)t * N + lane0 + lane];
     __syncthreads();
@@ -145,10 +151,14 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_pre(TrajDev tr, const fl
       float gh[NG], gi[NG];
 #pragma unroll
       for (int gte = 0; gte < NG; ++gte) {
-        float q = bih[gte];
+        if constexpr (IN) {
+          float q = bih[gte];
 #pragma unroll
-        for (int d = 0; d < D; ++d) q = __builtin_fmaf(xS[m][d], wih[gte][d], q);
-        gi[gte] = q;
+          for (int d = 0; d < D; ++d) q = __builtin_fmaf(xS[m][d], wih[gte][d], q);
+          gi[gte] = q;
+        } else {
+          gi[gte] = sb[(size_t)gte * GH * TL + rec_at(j, m)];
+        }
         gh[gte] = acc[gte][r];
       }
       Cell::store_static(sb, rec_at(j, m), gh, gi);
@@ -300,10 +310,16 @@ template <class Cell>
 static void launch_seq_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent, const int32_t *d_skip) {
   rl_engine *e = traj->eng;
   const SeqDev &q = traj->seq;
-  hipLaunchKernelGGL((k_seq_tangent_pre<5, 2, Cell>), dim3(q.chunks), dim3(256), 0, e->stream, traj->d, d_tangent, q.act,
-                     q.dpre, q.succ, q.tiles, traj->d.T * q.tiles, q.blocks_per_chunk, d_skip);
-  hipLaunchKernelGGL((k_seq_tangent_rec<2, Cell>), dim3(q.tiles), dim3(256), 0, e->stream, traj->d, mod->d_params, 5, q.act,
-                     q.dpre, q.succ, q.out, d_skip);
+  if (seq_wide_tile_fits(traj, mod)) {  // (GRU only: the predicate) the input-side tangent term of every block first
+    launch_seq_in_proj(traj, d_tangent, q.dpre, DPRE_ARR, d_skip);
+    hipLaunchKernelGGL((k_seq_tangent_pre<0, 2, GruTangent>), dim3(q.chunks), dim3(256), 0, e->stream, traj->d, d_tangent,
+                       q.act, q.dpre, q.succ, q.tiles, traj->d.T * q.tiles, q.blocks_per_chunk, d_skip);
+  } else {
+    hipLaunchKernelGGL((k_seq_tangent_pre<5, 2, Cell>), dim3(q.chunks), dim3(256), 0, e->stream, traj->d, d_tangent, q.act,
+                       q.dpre, q.succ, q.tiles, traj->d.T * q.tiles, q.blocks_per_chunk, d_skip);
+  }
+  hipLaunchKernelGGL((k_seq_tangent_rec<2, Cell>), dim3(q.tiles), dim3(256), 0, e->stream, traj->d, mod->d_params,
+                     (int)traj->d.D, q.act, q.dpre, q.succ, q.out, d_skip);
 }
 
 void launch_gru_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent, uint64_t B_total,
@@ -314,7 +330,8 @@ void launch_gru_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent
   // rl_rnn_chain_create_wide)
   RL_REQUIRE(mod->out_dim == 2 || (mod->lane_kernels() && mod->out_dim > 2 && mod->out_dim <= RL_WIDE_MAX_OUT),
              "Fisher-vector products are for policies of two actions (lane-per-thread kernels: 2..12)");
-  if (mod->lane_kernels()) launch_stack_tangent(traj, mod, d_tangent, d_skip);  // -> seq.out
+  // (the wide tile shape: the tangent starts from the tile record its gradient pass left)
+  if (mod->lane_kernels() && !seq_wide_tile_fits(traj, mod)) launch_stack_tangent(traj, mod, d_tangent, d_skip);  // -> seq.out
   else {
     ProfScope ps(e, RL_K_POLICY_FUSED);
     if (mod->kind == RL_MODULE_LSTM_MLP) launch_seq_tangent<LstmTangent>(traj, mod, d_tangent, d_skip);

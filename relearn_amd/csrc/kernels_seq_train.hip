@@ -30,21 +30,10 @@
 // step and the gate arithmetic.
 // Reference: gru_cell (src/torch/modules/seq/rnn/gru.rs:30-39), Chain (modules/chain.rs:127-186), and what libtorch's
 // autograd does for loss.backward() on them (src/torch/optimizers/coptimizer.rs:13-26).
-#include "bf16_tile.hpp"
-#include "seq_common.hpp"
+#include "seq_pieces.hpp"
 
 namespace {
 
-using bt::Frag;
-
-// An f32 value is the exact sum of three bf16 pieces (round to nearest: |p1| <= 2^-9 |v|, |p2| <= 2^-18 |v|).  Of the
-// nine piece pairs of a product a b the six with p + q < 3 are multiplied; the other three together are below
-// 2^-26 |a||b|, a quarter of the rounding of ONE f32 product, and under the f32 accumulator's own rounding they do not
-// change a single bit of the gradients the tests look at (tests/test_gpu_gru.py::test_piece_products_keep_f32_accuracy:
-// the same distance from the f64 oracle as with all nine, 6.7e-8 / 2.9e-8 of max |g|; the f32 fma kernels: 4.7e-8 /
-// 1.8e-8).  PIECE_ORDER 5 multiplies all nine.
-constexpr int PIECE_ORDER = 3;
-constexpr int PIECE_PAIRS = PIECE_ORDER == 3 ? 6 : PIECE_ORDER == 4 ? 8 : 9;
 constexpr int LSTM_VALU_PER_MFMA = 6;  // ... of the LSTM's (0, 4, 6, 8 measured: no difference; its schedule is decided by the order of its phases' jobs)
 constexpr int VALU_PER_MFMA = 4;  // vector instructions the forward's schedule places after each matrix instruction  // vector instructions the schedule of the forward places between two matrix instructions
 // Piece images [sample][unit] in LDS: rows of GH halfwords (256 bytes — the width of the LDS), the 16-byte chunk c of
@@ -80,27 +69,6 @@ __device__ __forceinline__ float sum16(float v) {
   v += dpp_lanes<0x141>(v);  // row_half_mirror: the other quad of the eight
   v += dpp_lanes<0x140>(v);  // row_mirror: the other eight
   return v;
-}
-
-// eight consecutive values of k -> the three operand fragments of their exact bf16 pieces
-__device__ __forceinline__ void frags_of8(const float (&v)[8], Frag (&f)[3]) {
-  uint32_t p[8][3];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) bt::split3(v[i], p[i][0], p[i][1], p[i][2]);
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-#pragma unroll
-    for (int h = 0; h < 4; ++h) f[q].u[h] = bt::pk(p[2 * h][q], p[2 * h + 1][q]);
-}
-
-// acc += sum over the piece pairs (p + q < PIECE_ORDER) of a (3 fragments of A) and b (3 fragments of B)
-__device__ __forceinline__ f32x4 mfma_pieces(const Frag (&a)[3], const Frag (&b)[3], f32x4 acc) {
-#pragma unroll
-  for (int p = 2; p >= 0; --p)  // small terms first
-#pragma unroll
-    for (int q = 2; q >= 0; --q)
-      if (p + q < PIECE_ORDER) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[p].v, b[q].v, acc, 0, 0, 0);
-  return acc;
 }
 
 // Gate functions of the training forward.  The vector ALU bounded this kernel (0.73 busy with rl_sigmoidf / rl_tanhf,
@@ -139,21 +107,26 @@ __device__ __forceinline__ float tanh_sel(float x) {
 }
 
 // ---------------------------------------------------------------- forward recurrence
+// D = 0, "input side elsewhere": k_seq_in_proj (kernels_seq_in.hip) has left gi = W_ih x + b_ih of every block in the
+// record's r, z and n arrays; a lane reads its 16 bytes per gate and M-tile a phase ahead and writes r, z, n over them.
+// No input loop, no xS / wiS, and the flat vector's offsets are formed from the trajectory's feature count.
 template <int D>
 __global__ void __launch_bounds__(W16 * 64, 2)
     k_gru_recur_fwd(TrajDev tr, const float *__restrict__ params, int A, float *__restrict__ act,
                     const int32_t *__restrict__ skip) {
+  constexpr bool IN = D > 0;        // the input projection is this kernel's
+  constexpr int DX = IN ? D : 1;
   __shared__ __attribute__((aligned(16))) unsigned short hP[3][TL * GH];  // h as pieces, [sample][unit] (img_at)
-  __shared__ float xS[2][TL][9];  // (9: the four samples a wave reads at once are 4 rows apart — 144 bytes, not 128)
+  __shared__ float xS[IN ? 2 : 1][IN ? TL : 1][9];  // (9: the four samples a wave reads at once are 4 rows apart — 144 bytes, not 128)
   __shared__ int endS[2][TL];
-  __shared__ float wiS[3][D + 1][GH];
+  __shared__ float wiS[IN ? 3 : 1][DX + 1][IN ? GH : 1];
   __shared__ uint4 wnS[GH / 32][3][W16][64];  // the n gate's W_hh fragments (96 KB): 48 registers the budget does not have
   if (skip != nullptr && *skip != 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n16 = lane & 15, g4 = lane >> 4, j = 16 * wave + n16;
   const uint32_t N = tr.n, T = tr.T;
   const uint32_t tile = blockIdx.x, tiles = gridDim.x, lane0 = tile * TL;
-  const GruParams g = gru_params(params, D, A);
+  const GruParams g = gru_params(params, IN ? D : (int)tr.D, A);
   Frag wf[2][GH / 32][3];  // [gate r, z][k-block][piece]: W_hh[gate * GH + j][32 kb + 8 g4 + 0..7]
   float bhh[3];
 #pragma unroll
@@ -176,10 +149,11 @@ __global__ void __launch_bounds__(W16 * 64, 2)
     bhh[gte] = g.bhh[row];
   }
   // the input projection's weights wait in LDS ([gate][feature | bias][unit]): 18 registers the products need more
-  for (int q = threadIdx.x; q < 3 * (D + 1) * GH; q += W16 * 64) {
-    const int gte = q / ((D + 1) * GH), d = (q / GH) % (D + 1), u = q % GH;
-    wiS[gte][d][u] = d < D ? g.Wih[(size_t)(gte * GH + u) * D + d] : g.bih[gte * GH + u];
-  }
+  if constexpr (IN)
+    for (int q = threadIdx.x; q < 3 * (D + 1) * GH; q += W16 * 64) {
+      const int gte = q / ((D + 1) * GH), d = (q / GH) % (D + 1), u = q % GH;
+      wiS[gte][d][u] = d < D ? g.Wih[(size_t)(gte * GH + u) * D + d] : g.bih[gte * GH + u];
+    }
   for (int q = threadIdx.x; q < (int)(sizeof(hP) / 4); q += W16 * 64) reinterpret_cast<uint32_t *>(&hP[0][0])[q] = 0u;
   float hown[8];
 #pragma unroll
@@ -187,22 +161,37 @@ __global__ void __launch_bounds__(W16 * 64, 2)
   const bool io_lane = wave == 0 && lane < TL;
   const uint32_t i_lane = lane0 + (uint32_t)(lane & (TL - 1));
   const size_t plane = (size_t)(T + 1) * N;
-  float xin[D];
+  float xin[DX];
   int fin = 0;
   auto fetch = [&](uint32_t tt) {  // io lanes: observation and successor code of step tt, into registers
+    if constexpr (IN)
 #pragma unroll
-    for (int d = 0; d < D; ++d) xin[d] = tr.obs[d * plane + (size_t)tt * N + i_lane];
+      for (int d = 0; d < D; ++d) xin[d] = tr.obs[d * plane + (size_t)tt * N + i_lane];
     fin = tr.flag[(size_t)tt * N + i_lane];
   };
   auto publish = [&](int buf) {
+    if constexpr (IN)
 #pragma unroll
-    for (int d = 0; d < D; ++d) xS[buf][lane][d] = xin[d];
+      for (int d = 0; d < D; ++d) xS[buf][lane][d] = xin[d];
     endS[buf][lane] = fin != RL_SUCC_CONTINUE;
   };
   if (io_lane) {
     fetch(0);
     publish(0);
   }
+  // input side elsewhere: gi of (step, M-tile) in registers, loaded while the phase before it runs
+  f32x4 gin[3][IN ? 1 : 2];
+  auto fetch_gi = [&](uint32_t tt, int mt) {
+    if constexpr (!IN) {
+      const float *__restrict__ ab = act + ((size_t)tt * tiles + tile) * SEQ_ARR * GH * TL;
+      const uint32_t row = rec_at(j, 16 * mt + 4 * g4);
+      gin[0][mt] = *reinterpret_cast<const f32x4 *>(ab + (uint32_t)(ACT_R * GH * TL) + row);
+      gin[1][mt] = *reinterpret_cast<const f32x4 *>(ab + (uint32_t)(ACT_Z * GH * TL) + row);
+      gin[2][mt] = *reinterpret_cast<const f32x4 *>(ab + (uint32_t)(ACT_N * GH * TL) + row);
+    }
+  };
+  fetch_gi(0, 0);
+  fetch_gi(0, 1);
   __syncthreads();
   // A step is two phases with a barrier after each, and in both the matrix pipe and the vector ALU work side by side:
   //   phase 1: products of M-tile 1 (step t)       | gate arithmetic of M-tile 0 (step t) -> rows 0-15 of h(t+1)
@@ -245,13 +234,14 @@ __global__ void __launch_bounds__(W16 * 64, 2)
     *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_GHN * GH * TL) + row) = acc[2][mt];
     *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_HPREV * GH * TL) + row) =
         (f32x4){hown[4 * mt], hown[4 * mt + 1], hown[4 * mt + 2], hown[4 * mt + 3]};
-    float wih[3][D], bih[3];
+    float wih[3][DX], bih[3];
+    if constexpr (IN)
 #pragma unroll
-    for (int gte = 0; gte < 3; ++gte) {
+      for (int gte = 0; gte < 3; ++gte) {
 #pragma unroll
-      for (int d = 0; d < D; ++d) wih[gte][d] = wiS[gte][d][j];
-      bih[gte] = wiS[gte][D][j];
-    }
+        for (int d = 0; d < D; ++d) wih[gte][d] = wiS[gte][d][j];
+        bih[gte] = wiS[gte][D][j];
+      }
     f32x4 rv, zv, nv, av;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -259,10 +249,14 @@ __global__ void __launch_bounds__(W16 * 64, 2)
       float gi[3];
 #pragma unroll
       for (int gte = 0; gte < 3; ++gte) {
-        float v = bih[gte];
+        if constexpr (IN) {
+          float v = bih[gte];
 #pragma unroll
-        for (int d = 0; d < D; ++d) v = __builtin_fmaf(xS[cur][m][d], wih[gte][d], v);
-        gi[gte] = v;
+          for (int d = 0; d < D; ++d) v = __builtin_fmaf(xS[cur][m][d], wih[gte][d], v);
+          gi[gte] = v;
+        } else {
+          gi[gte] = gin[gte][mt][i];
+        }
       }
       const float rr = sigmoid_sel(acc[0][mt][i] + gi[0]);
       const float zz = sigmoid_sel(acc[1][mt][i] + gi[1]);
@@ -288,6 +282,8 @@ __global__ void __launch_bounds__(W16 * 64, 2)
     *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_Z * GH * TL) + row) = zv;
     *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_N * GH * TL) + row) = nv;
     *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_A1 * GH * TL) + row) = av;
+    // (the last step reads its own block again: values nobody uses, no branch in the phase's block)
+    fetch_gi(t + 1 < T ? t + 1 : t, mt);
   };
   // the order asked of the scheduler for a phase: one matrix instruction, a few vector ones (PHASE: the two phases share
   // a basic block, and groups of one sync id are matched against the whole block)
@@ -661,21 +657,25 @@ __global__ void __launch_bounds__(W16 * 64, 2)
 //   d pre_z = dh (h_prev - n) z (1 - z),  d gh_n = d pre_n r
 //   d h_prev = dh z + W_hh[r]^T d pre_r + W_hh[z]^T d pre_z + W_hh[n]^T d gh_n          (K = 384 on the matrix pipe)
 // and writes the four per-step arrays the weight-gradient GEMMs read.
+// D = 0, "input side elsewhere": d pre_n goes to array 2 of dpre for k_seq_in_wgrad (kernels_seq_in.hip), which forms
+// the whole of dW_ih and db_ih; this kernel then reads no observation and writes no slab row.
+template <int D>
 __global__ void __launch_bounds__(W16 * 64, 2)
     k_gru_recur_bwd(TrajDev tr, const float *__restrict__ params, int A, const float *__restrict__ act,
                     float *__restrict__ dpre, float *__restrict__ slab, uint32_t P,
                     const int32_t *__restrict__ skip) {
-  constexpr int D = 5;
+  constexpr bool IN = D > 0;
+  constexpr int DX = IN ? D : 1;
   constexpr int KB = 3 * GH / 32, KBL = 3;  // k-blocks of the K = 384 product; the last KBL keep their weights in LDS
   __shared__ __attribute__((aligned(16))) unsigned short gP[3][TL][GROW];  // gate gradients as pieces, [sample][gate unit]
   __shared__ uint4 wTS[KBL][3][W16][64];  // 72 KB: 36 registers the budget does not have
-  __shared__ float xS[2][TL][9];          // observation features by step parity (the input side's weight gradients)
+  __shared__ float xS[IN ? 2 : 1][IN ? TL : 1][9];  // observation features by step parity (the input side's weight gradients)
   if (skip != nullptr && *skip != 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n16 = lane & 15, g4 = lane >> 4, j = 16 * wave + n16;
   const uint32_t N = tr.n, T = tr.T;
   const uint32_t tile = blockIdx.x, tiles = gridDim.x, lane0 = tile * TL;
-  const GruParams g = gru_params(params, D, A);
+  const GruParams g = gru_params(params, IN ? D : (int)tr.D, A);
   Frag wT[KB - KBL][3];  // [k-block][piece]: W_hh[32 kb + 8 g4 + 0..7][j]   (rows: gate units, r then z then n)
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
@@ -699,9 +699,9 @@ __global__ void __launch_bounds__(W16 * 64, 2)
   // input side of the n gate (dW_ih[n], db_ih[n]) for this lane's unit: sums of d pre_n over its eight samples of every
   // step — d pre_n exists only here (the hidden side stores d pre_n r), so it never goes to HBM; the other gates' input
   // side equals their hidden side and is summed where those arrays are staged (k_gru_wgrad_bf16)
-  float dwin[D], dbin = 0.0f;
+  float dwin[DX], dbin = 0.0f;
 #pragma unroll
-  for (int d = 0; d < D; ++d) dwin[d] = 0.0f;
+  for (int d = 0; d < DX; ++d) dwin[d] = 0.0f;
   const size_t plane = (size_t)(T + 1) * N;
   const uint32_t lo = rec_at(j, 4 * g4);  // + 16 mt: first of the lane's four contiguous samples (32-bit
                                                     // offsets from a uniform block base: no 64-bit address registers)
@@ -723,7 +723,7 @@ __global__ void __launch_bounds__(W16 * 64, 2)
   // 7.0 us: the waits move, the time does not.  What a phase waits for is the LDS: every wave's product reads the same
   // 36 KB of gate-gradient pieces plus its 9 KB of weights, 368 KB per phase and CU = 1.4 us at 128 B per cycle, twice
   // per step (a timing build, since removed: products 1.2 - 2.8 us, gate gradients 1.1 - 1.8 us per phase).)
-  const bool x_thread = threadIdx.x < TL * D;
+  const bool x_thread = IN && threadIdx.x < TL * D;
   auto load_x = [&](uint32_t t) {  // feature (tid / TL) of sample (tid % TL) of step t
     return tr.obs[(size_t)(threadIdx.x / TL) * plane + (size_t)t * N + lane0 + (threadIdx.x % TL)];
   };
@@ -734,7 +734,7 @@ __global__ void __launch_bounds__(W16 * 64, 2)
   // kernel reads, the direct term of d h_prev, the n gate's input-side sums
   auto gates = [&](const HalfIn &in, uint32_t t, int mt) {
     float *__restrict__ db = dpre + ((size_t)t * tiles + tile) * DPRE_ARR * GH * TL;
-    f32x4 grv, gzv, gnrv;
+    f32x4 grv, gzv, gnrv, gnv;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int m = 16 * mt + 4 * g4 + i;
@@ -749,9 +749,12 @@ __global__ void __launch_bounds__(W16 * 64, 2)
       gzv[i] = dzg * zz * (1.0f - zz);
       gnrv[i] = dpn * rr;
       acc[mt][i] = dh * zz;
-      dbin += dpn;
+      gnv[i] = dpn;
+      if constexpr (IN) {
+        dbin += dpn;
 #pragma unroll
-      for (int d = 0; d < D; ++d) dwin[d] = __builtin_fmaf(dpn, xS[t & 1][m][d], dwin[d]);
+        for (int d = 0; d < D; ++d) dwin[d] = __builtin_fmaf(dpn, xS[t & 1][m][d], dwin[d]);
+      }
       const float gv[3] = {grv[i], gzv[i], gnrv[i]};
 #pragma unroll
       for (int gte = 0; gte < 3; ++gte) {
@@ -766,6 +769,7 @@ __global__ void __launch_bounds__(W16 * 64, 2)
     *reinterpret_cast<f32x4 *>(db + (uint32_t)(0 * GH * TL) + o) = grv;
     *reinterpret_cast<f32x4 *>(db + (uint32_t)(1 * GH * TL) + o) = gzv;
     *reinterpret_cast<f32x4 *>(db + (uint32_t)(3 * GH * TL) + o) = gnrv;  // (array 2, d pre_n, stays on chip)
+    if constexpr (!IN) *reinterpret_cast<f32x4 *>(db + (uint32_t)(2 * GH * TL) + o) = gnv;  // (... or feeds k_seq_in_wgrad)
   };
   // acc[mt] += W_hh^T (gate gradients of M-tile mt): twelve k-blocks, the last three with their weights from LDS
   auto products = [&](int mt) {
@@ -833,6 +837,7 @@ __global__ void __launch_bounds__(W16 * 64, 2)
   }
   // ---- this tile's row of partials: the n gate's rows of W_ih and b_ih (the four lane groups of a wave hold
   // different samples of the same unit)
+  if constexpr (!IN) return;
   float *__restrict__ out = slab + (size_t)tile * P;
   const size_t obih = (size_t)3 * GH * D + (size_t)3 * GH * GH;
   auto over_groups = [](float v) {
@@ -1037,10 +1042,6 @@ __global__ void __launch_bounds__(W16 * 64, 2)
 // (their input side equals their hidden side), are sums the staging threads keep for the rows they stage (thread q
 // stages row q >> 2 of every gate in every half); the n gate's input side comes from the backward recurrence.  One row
 // of f32 partials per workgroup (columns of the recurrent parameters only; the head's come from k_gru_head_backward).
-// [row][16 samples] piece images: 32-byte rows, the two 16-byte chunks of rows 8 .. 15 (mod 16) swapped — operand reads
-// (lane = row, upper half-wave = upper chunk) and the staging writes (four lanes per row) are conflict-free
-// (scripts/lds_conflicts.py; the padded 48-byte rows before cost the writes twice their cycles)
-__device__ __forceinline__ int wimg_at(int row, int hw) { return row * 16 + (hw ^ (((row >> 3) & 1) << 3)); }
 // NG gate blocks: 3 = GRU (hidden-side deltas: d pre_r, d pre_z, d pre_n r = dpre arrays 0, 1, 3; the input side of r and z
 // equals the hidden side), 4 = LSTM (d pre_i, f, g, o = arrays 0 .. 3; input side = hidden side for all four: this kernel
 // then forms every recurrent column, eight 32x32 tiles per wave)
@@ -1052,7 +1053,9 @@ __global__ void __launch_bounds__(W16 * 64, 2)
   constexpr int NIN = NG == 3 ? 2 : NG;  // gates whose input-side sums are formed here
   __shared__ __attribute__((aligned(16))) unsigned short AP[2][3][NG * GH * 16];  // d gh pieces, by half parity (wimg_at)
   __shared__ __attribute__((aligned(16))) unsigned short BP[2][3][GH * 16];      // h_prev pieces
-  __shared__ float xS[2][TL][17];  // observations, by block parity: thread q holds column q / TL of sample q % TL (the
+  constexpr bool IN = D > 0;  // (D = 0, input side elsewhere: W_hh and b_hh only — k_seq_in_wgrad forms dW_ih and db_ih)
+  constexpr int DX = IN ? D : 1;
+  __shared__ float xS[IN ? 2 : 1][IN ? TL : 1][17];  // observations, by block parity: thread q holds column q / TL of sample q % TL (the
                                    // columns >= D are padding: every thread writes, no branch; 17: samples 4 rows apart
                                    // on different banks)
   if (skip != nullptr && *skip != 0) return;
@@ -1065,13 +1068,13 @@ __global__ void __launch_bounds__(W16 * 64, 2)
   // staging of a half: thread q takes the 16-byte piece (row q >> 2, samples 4 (q & 3) .. + 3 of the half) of each of
   // the three gate arrays and of h_prev
   const int srow = q >> 2, scol = 4 * (q & 3);
-  float dwih[NIN][D], dbh[NG];
+  float dwih[NIN][DX], dbh[NG];
 #pragma unroll
   for (int g3 = 0; g3 < NG; ++g3) dbh[g3] = 0.0f;
 #pragma unroll
   for (int g2 = 0; g2 < NIN; ++g2)
 #pragma unroll
-    for (int d = 0; d < D; ++d) dwih[g2][d] = 0.0f;
+    for (int d = 0; d < DX; ++d) dwih[g2][d] = 0.0f;
   const uint32_t N = tr.n, T = tr.T;
   const size_t plane = (size_t)(T + 1) * N;
   const uint32_t b0 = blockIdx.x * blocks_per_chunk;
@@ -1095,7 +1098,7 @@ __global__ void __launch_bounds__(W16 * 64, 2)
     for (int g3 = 0; g3 < NG; ++g3)  // (GRU: array 3 is the hidden side of the n gate)
       sl.g[g3] = *reinterpret_cast<const f32x4 *>(db + (uint32_t)((NG == 3 && g3 == 2 ? 3 : g3) * GH * TL) + o);
     sl.hB = *reinterpret_cast<const f32x4 *>(ab + (uint32_t)(ACT_HPREV * GH * TL) + o);
-    if ((h & 1) == 0 && (steady || blk + 1 < b1)) {  // feature q / TL of sample q % TL of the NEXT block (its sums run
+    if (IN && (h & 1) == 0 && (steady || blk + 1 < b1)) {  // feature q / TL of sample q % TL of the NEXT block (its sums run
       const uint32_t t = (blk + 1) / tiles, lane0 = ((blk + 1) % tiles) * TL;  // while its pieces are produced)
       const int xf = q / TL < D ? q / TL : D - 1;  // (threads beyond the D features load a value nobody reads)
       sl.xn = tr.obs[(size_t)xf * plane + (size_t)t * N + lane0 + (q % TL)];
@@ -1119,19 +1122,20 @@ __global__ void __launch_bounds__(W16 * 64, 2)
 #pragma unroll
     for (int g3 = 0; g3 < NG; ++g3) park(AP[buf], g3 * GH + srow, sl.g[g3]);
     park(BP[buf], srow, sl.hB);
-    if ((h & 1) == 0) xS[((h >> 1) + 1) & 1][q % TL][q / TL] = sl.xn;  // x of the next block
-    const int xb = (int)((h >> 1) & 1);
+    if (IN && (h & 1) == 0) xS[((h >> 1) + 1) & 1][q % TL][q / TL] = sl.xn;  // x of the next block
+    [[maybe_unused]] const int xb = (int)((h >> 1) & 1);
 #pragma unroll
     for (int g3 = 0; g3 < NG; ++g3)
 #pragma unroll
       for (int i = 0; i < 4; ++i) dbh[g3] += sl.g[g3][i];
+    if constexpr (IN)
 #pragma unroll
-    for (int g2 = 0; g2 < NIN; ++g2)
+      for (int g2 = 0; g2 < NIN; ++g2)
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int d = 0; d < D; ++d)
-          dwih[g2][d] = __builtin_fmaf(sl.g[g2][i], xS[xb][16 * (h & 1) + scol + i][d], dwih[g2][d]);
+          for (int d = 0; d < D; ++d)
+            dwih[g2][d] = __builtin_fmaf(sl.g[g2][i], xS[xb][16 * (h & 1) + scol + i][d], dwih[g2][d]);
   };
   auto products = [&](int buf) {  // contraction over the 16 samples of the half in buffer `buf`, two tiles interleaved
     Frag fb[3];
@@ -1177,7 +1181,7 @@ __global__ void __launch_bounds__(W16 * 64, 2)
   };
   // n_half is even (whole blocks)
   if (n_half > 0) {
-    {  // x of the first block
+    if constexpr (IN) {  // x of the first block
       const uint32_t t = b0 / tiles, lane0 = (b0 % tiles) * TL;
       const int xf = q / TL < D ? q / TL : D - 1;
       xS[0][q % TL][q / TL] = tr.obs[(size_t)xf * plane + (size_t)t * N + lane0 + (q % TL)];
@@ -1200,7 +1204,7 @@ __global__ void __launch_bounds__(W16 * 64, 2)
   }
   // ---- this workgroup's row of partials (recurrent columns)
   float *__restrict__ out = slab + (size_t)blockIdx.x * P;
-  const size_t oWhh = (size_t)NG * GH * D;
+  const size_t oWhh = (size_t)NG * GH * (IN ? D : (int)tr.D);
 #pragma unroll
   for (int i = 0; i < 2 * NG; ++i)
 #pragma unroll
@@ -1218,9 +1222,9 @@ __global__ void __launch_bounds__(W16 * 64, 2)
     const float vb = over4(dbh[g3]);
     if ((q & 3) == 0) {
       out[obhh + row] = vb;
-      if (g3 < NIN) out[obih + row] = vb;  // (the GRU's n gate: its input side comes from the backward recurrence)
+      if (IN && g3 < NIN) out[obih + row] = vb;  // (the GRU's n gate: its input side comes from the backward recurrence)
     }
-    if (g3 < NIN) {
+    if (IN && g3 < NIN) {
 #pragma unroll
       for (int d = 0; d < D; ++d) {
         const float v = over4(dwih[g3][d]);
@@ -1234,13 +1238,21 @@ __global__ void __launch_bounds__(W16 * 64, 2)
 
 // ---------------------------------------------------------------- launchers
 // teacher-forced training forward of the GRU chain: seq.act (all seven arrays) and d_out [A][T][n]
+// (6 to 24 features, seq_wide_tile_fits: the input projection of every block first, into the record's r, z, n arrays)
 void launch_gru_train_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float *d_act, const int32_t *d_skip) {
-  RL_REQUIRE(traj->d.D == 5, "recurrent forward: built for 5 observation features");
+  const bool wide = seq_wide_tile_fits(traj, mod);
+  RL_REQUIRE(traj->d.D == 5 || wide, "recurrent forward: built for 5 observation features (6 to 24: the wide tile shape)");
   rl_engine *e = traj->eng;
   const uint32_t tiles = traj->d.n / TL;
   const int A = (int)mod->out_dim;
-  hipLaunchKernelGGL(k_gru_recur_fwd<5>, dim3(tiles), dim3(W16 * 64), 0, e->stream, traj->d, mod->d_params, A, d_act,
-                     d_skip);
+  if (wide) {
+    launch_seq_in_proj(traj, mod->d_params, d_act, SEQ_ARR, d_skip);
+    hipLaunchKernelGGL(k_gru_recur_fwd<0>, dim3(tiles), dim3(W16 * 64), 0, e->stream, traj->d, mod->d_params, A, d_act,
+                       d_skip);
+  } else {
+    hipLaunchKernelGGL(k_gru_recur_fwd<5>, dim3(tiles), dim3(W16 * 64), 0, e->stream, traj->d, mod->d_params, A, d_act,
+                       d_skip);
+  }
   launch_seq_train_head_forward(traj, mod, d_out, d_act, d_skip);
 }
 
@@ -1260,11 +1272,11 @@ void launch_seq_train_head_forward(rl_traj *traj, const rl_mlp *mod, float *d_ou
   const uint32_t grid = blocks < 2048 ? blocks : 2048;
   const int NG = (int)rl_module_gates(mod->kind);
   if (mod->out_dim == 2)
-    hipLaunchKernelGGL(k_seq_head_forward<2>, dim3(grid), dim3(W16 * 64), 0, e->stream, traj->d, mod->d_params, 5, NG,
-                       d_act, d_out, tiles, blocks, d_skip);
+    hipLaunchKernelGGL(k_seq_head_forward<2>, dim3(grid), dim3(W16 * 64), 0, e->stream, traj->d, mod->d_params,
+                       (int)traj->d.D, NG, d_act, d_out, tiles, blocks, d_skip);
   else
-    hipLaunchKernelGGL(k_seq_head_forward<1>, dim3(grid), dim3(W16 * 64), 0, e->stream, traj->d, mod->d_params, 5, NG,
-                       d_act, d_out, tiles, blocks, d_skip);
+    hipLaunchKernelGGL(k_seq_head_forward<1>, dim3(grid), dim3(W16 * 64), 0, e->stream, traj->d, mod->d_params,
+                       (int)traj->d.D, NG, d_act, d_out, tiles, blocks, d_skip);
 }
 
 // head backward of the GRU chain with the head's weight gradients: rows [0, RL_SEQ_HEAD_ROWS) of `d_slab`
@@ -1277,17 +1289,21 @@ void launch_gru_train_head_backward(rl_traj *traj, const rl_mlp *mod, float *d_s
   const int NG = (int)rl_module_gates(mod->kind);
   if (mod->out_dim == 2)
     hipLaunchKernelGGL(k_gru_head_backward<2>, dim3(grid), dim3(W16 * 64), 0, traj->eng->stream, traj->d, mod->d_params,
-                       5, NG, traj->dz, q.act, q.dpre, d_slab, (uint32_t)mod->P, q.tiles, blocks, d_skip);
+                       (int)traj->d.D, NG, traj->dz, q.act, q.dpre, d_slab, (uint32_t)mod->P, q.tiles, blocks, d_skip);
   else
     hipLaunchKernelGGL(k_gru_head_backward<1>, dim3(grid), dim3(W16 * 64), 0, traj->eng->stream, traj->d, mod->d_params,
-                       5, NG, traj->dz, q.act, q.dpre, d_slab, (uint32_t)mod->P, q.tiles, blocks, d_skip);
+                       (int)traj->d.D, NG, traj->dz, q.act, q.dpre, d_slab, (uint32_t)mod->P, q.tiles, blocks, d_skip);
 }
 
 // weight gradients of the recurrent parameters: rows [0, chunks) of seq.wg_slab, columns [0, W1)
 void launch_gru_train_wgrad(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip) {
   const SeqDev &q = traj->seq;
   const uint32_t blocks = traj->d.T * q.tiles;
-  if (mod->kind == RL_MODULE_LSTM_MLP)
+  if (seq_wide_tile_fits(traj, mod)) {  // W_hh and b_hh here, the input side's columns of the same rows from k_seq_in_wgrad
+    hipLaunchKernelGGL((k_gru_wgrad_bf16<0, 3>), dim3(q.chunks), dim3(W16 * 64), 0, traj->eng->stream, traj->d, q.act,
+                       q.dpre, q.wg_slab, (uint32_t)mod->P, q.tiles, blocks, q.blocks_per_chunk, d_skip);
+    launch_seq_in_wgrad(traj, mod, d_skip);
+  } else if (mod->kind == RL_MODULE_LSTM_MLP)
     hipLaunchKernelGGL((k_gru_wgrad_bf16<5, 4>), dim3(q.chunks), dim3(W16 * 64), 0, traj->eng->stream, traj->d, q.act,
                        q.dpre, q.wg_slab, (uint32_t)mod->P, q.tiles, blocks, q.blocks_per_chunk, d_skip);
   else
@@ -1300,6 +1316,10 @@ void launch_gru_train_recur_backward(rl_traj *traj, const rl_mlp *mod, const int
   const SeqDev &q = traj->seq;
   // its W_ih / b_ih / b_hh partials: one row per tile behind the weight-gradient kernel's rows (the head kernel uses
   // the head columns of the same rows)
-  hipLaunchKernelGGL(k_gru_recur_bwd, dim3(q.tiles), dim3(W16 * 64), 0, traj->eng->stream, traj->d, mod->d_params,
-                     (int)mod->out_dim, q.act, q.dpre, q.wg_slab + (size_t)q.chunks * mod->P, (uint32_t)mod->P, d_skip);
+  if (seq_wide_tile_fits(traj, mod))  // (d pre_n goes to dpre for k_seq_in_wgrad: no slab row)
+    hipLaunchKernelGGL(k_gru_recur_bwd<0>, dim3(q.tiles), dim3(W16 * 64), 0, traj->eng->stream, traj->d, mod->d_params,
+                       (int)mod->out_dim, q.act, q.dpre, (float *)nullptr, (uint32_t)mod->P, d_skip);
+  else
+    hipLaunchKernelGGL(k_gru_recur_bwd<5>, dim3(q.tiles), dim3(W16 * 64), 0, traj->eng->stream, traj->d, mod->d_params,
+                       (int)mod->out_dim, q.act, q.dpre, q.wg_slab + (size_t)q.chunks * mod->P, (uint32_t)mod->P, d_skip);
 }

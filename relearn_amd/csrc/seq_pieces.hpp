@@ -1,0 +1,43 @@
+// seq_pieces.hpp — the exact three-piece bf16 products shared by the units of the recurrent training passes
+// (kernels_seq_train.hip: the recurrence, the head, the recurrent weight gradients; kernels_seq_in.hip: the input side).
+#pragma once
+#include "bf16_tile.hpp"
+#include "seq_common.hpp"
+
+using bt::Frag;
+
+// An f32 value is the exact sum of three bf16 pieces (round to nearest: |p1| <= 2^-9 |v|, |p2| <= 2^-18 |v|).  Of the
+// nine piece pairs of a product a b the six with p + q < 3 are multiplied; the other three together are below
+// 2^-26 |a||b|, a quarter of the rounding of ONE f32 product, and under the f32 accumulator's own rounding they do not
+// change a single bit of the gradients the tests look at (tests/test_gpu_gru.py::test_piece_products_keep_f32_accuracy:
+// the same distance from the f64 oracle as with all nine, 6.7e-8 / 2.9e-8 of max |g|; the f32 fma kernels: 4.7e-8 /
+// 1.8e-8).  PIECE_ORDER 5 multiplies all nine.
+constexpr int PIECE_ORDER = 3;
+constexpr int PIECE_PAIRS = PIECE_ORDER == 3 ? 6 : PIECE_ORDER == 4 ? 8 : 9;
+
+// eight consecutive values of k -> the three operand fragments of their exact bf16 pieces
+__device__ __forceinline__ void frags_of8(const float (&v)[8], Frag (&f)[3]) {
+  uint32_t p[8][3];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) bt::split3(v[i], p[i][0], p[i][1], p[i][2]);
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+#pragma unroll
+    for (int h = 0; h < 4; ++h) f[q].u[h] = bt::pk(p[2 * h][q], p[2 * h + 1][q]);
+}
+
+// acc += sum over the piece pairs (p + q < PIECE_ORDER) of a (3 fragments of A) and b (3 fragments of B)
+__device__ __forceinline__ f32x4 mfma_pieces(const Frag (&a)[3], const Frag (&b)[3], f32x4 acc) {
+#pragma unroll
+  for (int p = 2; p >= 0; --p)  // small terms first
+#pragma unroll
+    for (int q = 2; q >= 0; --q)
+      if (p + q < PIECE_ORDER) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[p].v, b[q].v, acc, 0, 0, 0);
+  return acc;
+}
+
+// [row][16 samples] piece images (the sample is the contraction index of the weight-gradient products): 32-byte rows,
+// the two 16-byte chunks of rows 8 .. 15 (mod 16) swapped — operand reads (lane = row, upper half-wave = upper chunk)
+// and the staging writes (four lanes per row) are conflict-free (scripts/lds_conflicts.py; the padded 48-byte rows
+// before cost the writes twice their cycles)
+__device__ __forceinline__ int wimg_at(int row, int hw) { return row * 16 + (hw ^ (((row >> 3) & 1) << 3)); }
