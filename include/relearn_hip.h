@@ -683,7 +683,9 @@ int32_t rl_traj_read(rl_traj *traj, int32_t field, void *host, uint64_t bytes);
  * and PER_LAYER says that no fused kernel is built for the shape (or that the engine runs kernel variant 1).
  * RECURRENT_TILE: a GRU-MLP chain of 6 to 24 inputs at GRU 128 / MLP [128], one or two outputs, on a multiple of 32 lanes
  * ran a gradient pass or a Fisher-vector product on the tile-resident matrix-pipe kernels (kernels_seq_train.hip with the
- * input side in kernels_seq_in.hip); every other recurrent pass reports RECURRENT, as before. */
+ * input side in kernels_seq_in.hip) — and so did a GRU-Linear chain of the same inputs and GRU width with 1 or 3 to 12
+ * outputs (the head in kernels_seq_lin.hip; two outputs with a linear tail stay on the lane-per-thread kernels); every
+ * other recurrent pass reports RECURRENT, as before. */
 typedef enum { RL_PASS_PATH_NONE = 0, RL_PASS_PATH_PER_LAYER = 1, RL_PASS_PATH_FUSED_5_128 = 2, RL_PASS_PATH_GEN_MFMA = 3,
                RL_PASS_PATH_WIDE_MFMA = 4, RL_PASS_PATH_WIDE_SPLIT = 5, RL_PASS_PATH_RECURRENT = 6,
                RL_PASS_PATH_RECURRENT_TILE = 7 } rl_pass_path;

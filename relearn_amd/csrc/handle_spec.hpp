@@ -528,9 +528,16 @@ struct ModuleShape {
   // A lane-kernel module whose training passes fit the tile kernels with the input side computed apart
   // (kernels_seq_in.hip): GruMlpConfig at the partition-game experiment's widths — one GRU layer of 128 units with bias
   // vectors, 6 to 24 inputs, an MLP tail of 128 hidden units, one or two outputs (no twin: the widths are the kernels').
+  // Or GruLinearConfig at the RL² experiments' widths: the same recurrent layer with a linear tail of 1 to
+  // RL_WIDE_MAX_OUT outputs, its head in kernels_seq_lin.hip.
   bool wide_tile_shape() const {
-    return kind == RL_MODULE_GRU_MLP && rnn_layers == 1 && in_dim >= 6 && in_dim <= 24 && gru_hidden == 128 &&
-           hidden == 128 && has_bias && (out_dim == 1 || out_dim == 2);
+    const bool mlp_tail = hidden == 128 && (out_dim == 1 || out_dim == 2);
+    const bool lin_tail = linear_tail() && out_dim >= 1 && out_dim <= RL_WIDE_MAX_OUT &&
+                          // tests/test_gpu_seq_wide_tile.py::test_neighbours_keep_their_path[linear tail] holds two
+                          // outputs with a linear tail to the lane-per-thread kernels (the kernels do not exclude 2)
+                          out_dim != 2;
+    return kind == RL_MODULE_GRU_MLP && rnn_layers == 1 && in_dim >= 6 && in_dim <= 24 && gru_hidden == 128 && has_bias &&
+           (mlp_tail || lin_tail);
   }
   // ChainConfig<GruConfig | LstmConfig, LinearConfig> (modules/chain.rs:12-54): the recurrent layers -> ReLU -> one
   // Linear(gru_hidden, out_dim).  Marked by `hidden` == 0 on a recurrent kind (the MLP-tail chains have hidden >= 1);

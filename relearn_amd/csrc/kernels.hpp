@@ -221,7 +221,8 @@ constexpr uint32_t RL_SEQ_HEAD_ROWS = 512;  // rows of head-gradient partials be
 // A lane-kernel module whose TRAINING passes (record-bearing forward, backward, weight gradients, tangent) run the tile
 // kernels above with the input side in kernels_seq_in.hip: ModuleShape::wide_tile_shape on whole tiles of 32 lanes under
 // engine kernel variant 0.  Rollouts, value forwards, evaluations without a record and every other shape stay on the
-// lane-per-thread kernels.
+// lane-per-thread kernels.  (A linear tail of that shape: the same input side and recurrence, the head in
+// kernels_seq_lin.hip.)
 inline bool seq_wide_tile_fits(const rl_traj *traj, const rl_mlp *mod) {
   return mod->wide_tile_shape() && traj->d.n % 32 == 0 && traj->eng->kernel_variant == 0;
 }
@@ -231,6 +232,19 @@ inline bool seq_wide_tile_fits(const rl_traj *traj, const rl_mlp *mod) {
 //   in_wgrad: the W_ih and b_ih columns of rows [0, chunks) of seq.wg_slab <- sums over dpre arrays 0 .. 2
 void launch_seq_in_proj(rl_traj *traj, const float *vec, float *dst, int arrays, const int32_t *d_skip);
 void launch_seq_in_wgrad(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip);
+// kernels_seq_lin.hip: the head of a linear-tail chain of that shape (ModuleShape::linear_tail, 1 to 12 outputs), block-parallel
+//   lin_head: d_out [A][T][n] <- init + M X over every block, M [A][128] row-contiguous, X plane `plane` of every block
+//             of a record with `arrays` planes per block, init the vector [A] or (init_planes) planes [A][T][n]
+//   lin_head_forward: the forward (kernel, bias, relu(h') of the record `d_act`)
+//   lin_head_backward: d relu(h') into seq.dpre, and the head's columns of rows [0, seq_lin_head_rows) of `d_slab`
+void launch_seq_lin_head(rl_traj *traj, const float *M, const float *init, bool init_planes, const float *X, int arrays,
+                         int plane, float *d_out, int A, const int32_t *d_skip);
+void launch_seq_lin_head_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, const float *d_act, const int32_t *d_skip);
+void launch_seq_lin_head_backward(rl_traj *traj, const rl_mlp *mod, float *d_slab, const int32_t *d_skip);
+inline uint32_t seq_lin_head_rows(const rl_traj *traj) {  // one row per workgroup, every workgroup at least one block
+  const uint32_t blocks = traj->d.T * (traj->d.n / 32);
+  return blocks < RL_SEQ_HEAD_ROWS ? blocks : RL_SEQ_HEAD_ROWS;
+}
 // v_last: [n] V(obs[T]) of every lane for slot T of the value plane (a general critic's: launch_gen_values), or NULL
 void launch_seq_gae(rl_traj *traj, float gamma, float lambda, const float *v_last);
 // one-step TD targets from traj->seq.out / succ (plane 0) -> d.tgt

@@ -803,10 +803,10 @@ void launch_gru_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip
       seg(oW1, P, q.wg_slab + (size_t)q.chunks * P, RL_SEQ_HEAD_ROWS);
     } else if (wide) {
       // every recurrent column from the chunk rows (W_ih and b_ih: k_seq_in_wgrad; W_hh and b_hh: the weight-gradient
-      // kernel), the head from the head kernel's
-      const uint32_t oW1 = 3 * GH * mod->in_dim + 3 * GH * GH + 6 * GH;
+      // kernel), the head from the head kernel's (a linear tail: one row per workgroup of k_seq_lin_head_backward)
+      const uint32_t oW1 = (uint32_t)mod->rnn_layer_offset(1);
       seg(0, oW1, q.wg_slab, q.chunks);
-      seg(oW1, P, q.wg_slab + (size_t)q.chunks * P, RL_SEQ_HEAD_ROWS);
+      seg(oW1, P, q.wg_slab + (size_t)q.chunks * P, mod->linear_tail() ? seq_lin_head_rows(traj) : RL_SEQ_HEAD_ROWS);
     } else if (gru_head) {
       // kernels_seq_train.hip: W_hh, the r / z rows of W_ih and b_ih, and b_hh from the weight-gradient kernel's rows;
       // the n rows of W_ih and b_ih from the backward recurrence's rows (one per tile); the head from the head kernel's

@@ -88,6 +88,9 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_pre(TrajDev tr, const fl
   // 0 .. 2 of `stat`; a thread reads its own entries before it writes the static terms over them
   constexpr bool IN = D > 0;
   constexpr int DX = IN ? D : 1;
+  // A = 0, "a linear tail": no MLP layer — no V1 product, no plane 4, no out_stat; the head's static term
+  // V relu(h') + v_b is a k_seq_lin_head launch (kernels_seq_lin.hip)
+  constexpr bool LIN = A == 0;
   __shared__ float xS[IN ? TL : 1][8];
   __shared__ float v2S[2][MH];
   // W1_LDS: the MLP layer's tangent operands, [k-step][thread] (read back by the thread that wrote them): the four gates'
@@ -113,13 +116,15 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_pre(TrajDev tr, const fl
     }
     bhh[gte] = v.bhh[row];
   }
+  if constexpr (!LIN)
 #pragma unroll
-  for (int ks = 0; ks < GH / 2; ++ks) {
-    const float w = v.W1[(size_t)j * GH + 2 * ks + hf];
-    if constexpr (Cell::W1_LDS) w1S[ks][threadIdx.x] = w;
-    else w1[ks] = w;
-  }
-  const float vb1 = v.b1[j];
+    for (int ks = 0; ks < GH / 2; ++ks) {
+      const float w = v.W1[(size_t)j * GH + 2 * ks + hf];
+      if constexpr (Cell::W1_LDS) w1S[ks][threadIdx.x] = w;
+      else w1[ks] = w;
+    }
+  [[maybe_unused]] float vb1 = 0.0f;
+  if constexpr (!LIN) vb1 = v.b1[j];
   for (int q = threadIdx.x; q < A * MH; q += 256) v2S[q / MH][q % MH] = v.W2[q];
   const float vb2 = hf < A ? v.b2[hf] : 0.0f;
   const uint32_t b0 = blockIdx.x * blocks_per_chunk;
@@ -163,18 +168,20 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_pre(TrajDev tr, const fl
       }
       Cell::store_static(sb, rec_at(j, m), gh, gi);
     }
-    f32x16 acc1;
+    if constexpr (!LIN) {
+      f32x16 acc1;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc1[r] = vb1;
+      for (int r = 0; r < 16; ++r) acc1[r] = vb1;
 #pragma unroll
-    for (int ks = 0; ks < GH / 2; ++ks) {
-      float w;
-      if constexpr (Cell::W1_LDS) w = w1S[ks][threadIdx.x];
-      else w = w1[ks];
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ab[(size_t)ACT_A1 * GH * TL + rec_at(2 * ks + hf, n)], w, acc1, 0, 0, 0);
+      for (int ks = 0; ks < GH / 2; ++ks) {
+        float w;
+        if constexpr (Cell::W1_LDS) w = w1S[ks][threadIdx.x];
+        else w = w1[ks];
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ab[(size_t)ACT_A1 * GH * TL + rec_at(2 * ks + hf, n)], w, acc1, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sb[(size_t)4 * GH * TL + rec_at(j, acc_row(r, hf))] = acc1[r];
     }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sb[(size_t)4 * GH * TL + rec_at(j, acc_row(r, hf))] = acc1[r];
     if (wave == 0 && hf < A) {
       float z = vb2;
 #pragma unroll 8
@@ -192,6 +199,10 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_rec(TrajDev tr, const fl
                                                             float *__restrict__ out_dot,
                                                             const int32_t *__restrict__ skip) {
   constexpr int NG = Cell::NG, NS = Cell::NS;
+  // A = 0, "a linear tail": the loop carries no head work — a1_dot = [relu(h') > 0] h'_dot of every step goes to plane
+  // DPRE_DU of the block (free without an MLP layer), addressed through `out_dot` (the base of the static terms), and
+  // k_seq_lin_head forms the outputs' tangent from it after this kernel
+  constexpr bool LIN = A == 0;
   __shared__ float hdT[GH][TL + 1];
   __shared__ float a1dT[GH][TL + 1];
   __shared__ float udS[TL][MH + 1];
@@ -208,8 +219,9 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_rec(TrajDev tr, const fl
   for (int gte = 0; gte < NG; ++gte)
 #pragma unroll
     for (int ks = 0; ks < GH / 2; ++ks) whh[gte][ks] = g.Whh[(size_t)(gte * GH + j) * GH + 2 * ks + hf];
+  if constexpr (!LIN)
 #pragma unroll
-  for (int ks = 0; ks < GH / 2; ++ks) w1[ks] = g.W1[(size_t)j * GH + 2 * ks + hf];
+    for (int ks = 0; ks < GH / 2; ++ks) w1[ks] = g.W1[(size_t)j * GH + 2 * ks + hf];
   for (int q = threadIdx.x; q < A * MH; q += 256) w2S[q / MH][q % MH] = g.W2[q];
   for (int q = threadIdx.x; q < GH * (TL + 1); q += 256) (&hdT[0][0])[q] = 0.0f;
   float st[16][NS];  // the carried tangents of the lane's 16 samples of unit j
@@ -243,9 +255,11 @@ __global__ void __launch_bounds__(256, 1) k_seq_tangent_rec(TrajDev tr, const fl
       for (int gte = 0; gte < NG; ++gte) accr[gte] = acc[gte][r];
       const float v = Cell::step(ab, sb, o, accr, st[r], endS[m] != 0);  // (an ended episode's next step starts from zero)
       hdT[j][m] = st[r][0];
-      a1dT[j][m] = a1 > 0.0f ? v : 0.0f;
+      if constexpr (LIN) out_dot[(blk * DPRE_ARR + DPRE_DU) * GH * TL + o] = a1 > 0.0f ? v : 0.0f;
+      else a1dT[j][m] = a1 > 0.0f ? v : 0.0f;
     }
     __syncthreads();
+    if constexpr (LIN) continue;
     f32x16 acc1 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int ks = 0; ks < GH / 2; ++ks)
@@ -310,6 +324,23 @@ template <class Cell>
 static void launch_seq_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent, const int32_t *d_skip) {
   rl_engine *e = traj->eng;
   const SeqDev &q = traj->seq;
+  if (seq_wide_tile_fits(traj, mod) && mod->linear_tail()) {
+    // the same input side and recurrence without an MLP layer; the head's two terms are block-parallel launches of
+    // k_seq_lin_head (kernels_seq_lin.hip) before and after the recurrence:
+    //   seq.succ <- V relu(h') + v_b                           (V, v_b: the tangent's kernel and bias slices)
+    //   seq.out  <- seq.succ + kernel [relu(h') > 0] h'_dot    (the masked h'_dot: plane DPRE_DU of every block)
+    const int A = (int)mod->out_dim;
+    const size_t ohead = mod->rnn_layer_offset(1);
+    launch_seq_in_proj(traj, d_tangent, q.dpre, DPRE_ARR, d_skip);
+    hipLaunchKernelGGL((k_seq_tangent_pre<0, 0, GruTangent>), dim3(q.chunks), dim3(256), 0, e->stream, traj->d, d_tangent,
+                       q.act, q.dpre, q.succ, q.tiles, traj->d.T * q.tiles, q.blocks_per_chunk, d_skip);
+    launch_seq_lin_head(traj, d_tangent + ohead, d_tangent + ohead + (size_t)A * GH, false, q.act, SEQ_ARR, ACT_A1, q.succ,
+                        A, d_skip);
+    hipLaunchKernelGGL((k_seq_tangent_rec<0, GruTangent>), dim3(q.tiles), dim3(256), 0, e->stream, traj->d, mod->d_params,
+                       (int)traj->d.D, q.act, q.dpre, q.succ, q.dpre, d_skip);
+    launch_seq_lin_head(traj, mod->d_params + ohead, q.succ, true, q.dpre, DPRE_ARR, DPRE_DU, q.out, A, d_skip);
+    return;
+  }
   if (seq_wide_tile_fits(traj, mod)) {  // (GRU only: the predicate) the input-side tangent term of every block first
     launch_seq_in_proj(traj, d_tangent, q.dpre, DPRE_ARR, d_skip);
     hipLaunchKernelGGL((k_seq_tangent_pre<0, 2, GruTangent>), dim3(q.chunks), dim3(256), 0, e->stream, traj->d, d_tangent,

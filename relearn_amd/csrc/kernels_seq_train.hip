@@ -1267,6 +1267,7 @@ void launch_lstm_train_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, f
 
 // the head of either chain over all (step, tile) blocks: u (recorded) and the outputs from the recorded relu(h')
 void launch_seq_train_head_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float *d_act, const int32_t *d_skip) {
+  if (mod->linear_tail()) return launch_seq_lin_head_forward(traj, mod, d_out, d_act, d_skip);  // (no u: kernels_seq_lin.hip)
   rl_engine *e = traj->eng;
   const uint32_t tiles = traj->d.n / TL, blocks = traj->d.T * tiles;
   const uint32_t grid = blocks < 2048 ? blocks : 2048;
@@ -1280,7 +1281,9 @@ void launch_seq_train_head_forward(rl_traj *traj, const rl_mlp *mod, float *d_ou
 }
 
 // head backward of the GRU chain with the head's weight gradients: rows [0, RL_SEQ_HEAD_ROWS) of `d_slab`
+// (a linear tail: rows [0, seq_lin_head_rows), kernels_seq_lin.hip)
 void launch_gru_train_head_backward(rl_traj *traj, const rl_mlp *mod, float *d_slab, const int32_t *d_skip) {
+  if (mod->linear_tail()) return launch_seq_lin_head_backward(traj, mod, d_slab, d_skip);
   const SeqDev &q = traj->seq;
   const uint32_t blocks = traj->d.T * q.tiles, grid = blocks < RL_SEQ_HEAD_ROWS ? blocks : RL_SEQ_HEAD_ROWS;
   if (grid < RL_SEQ_HEAD_ROWS)  // rows no workgroup writes

@@ -76,4 +76,5 @@ for period in range(periods):
                       "trial_reward_stddev": s.episode_reward.stddev(), "mean_step_reward": s.step_reward.mean,
                       "trpo_status": pst.status, "kl": pst.constraint_val_final, "entropy": pst.entropy,
                       "critic_loss": [cst.loss_first, cst.loss_last],
+                      "pass_path": traj.last_pass_path(),  # ra.PASS_PATH_*: the kernel family of the update's last pass
                       "rollout_ms": (t1 - t0) * 1e3, "update_ms": (t2 - t1) * 1e3}), flush=True)

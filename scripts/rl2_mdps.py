@@ -103,6 +103,7 @@ def main():
                 "uniform_random_trial_reward": float(uni_v.mean()), "optimal_trial_value": float(opt_v.mean()),
                 "trpo_status": pst.status, "kl": pst.constraint_val_final, "entropy": pst.entropy,
                 "critic_loss": [cst.loss_first, cst.loss_last],
+                "pass_path": traj.last_pass_path(),  # ra.PASS_PATH_*: the kernel family of the update's last pass
                 "rollout_ms": (t1 - t0) * 1e3, "update_ms": (t2 - t1) * 1e3}
         lines.append(line)
         print(json.dumps(line), flush=True)
