@@ -227,8 +227,8 @@ void traj_ensure_pvec(rl_traj *t, uint64_t P) {
 
 void seq_ensure(rl_traj *t, const rl_mlp *mod, bool training) {
   RL_REQUIRE(rl_module_is_recurrent(mod->kind), "not a recurrent module");
-  // (the wide tile shape needs both families' workspaces: its training passes run the tile kernels, its rollouts, value
-  // forwards and record-less evaluations the lane-per-thread ones)
+  // (the wide tile shape needs both families' workspaces: its update passes run the tile kernels, its rollouts, value
+  // forwards and rl_seq_forward the lane-per-thread ones)
   const bool wide = seq_wide_tile_fits(t, mod);
   if (mod->lane_kernels()) {
     stack_ensure(t, mod, training);  // lane-per-thread kernels: no tile or width condition

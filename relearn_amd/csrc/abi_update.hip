@@ -66,16 +66,22 @@ SlabRows run_pass(const rl_mlp *mod, rl_traj *traj, const PassRequest &req) {
       launch_gru_tangent(traj, sc.x, tangent, Bt, req.skip);
       if (seq_wide_tile_fits(traj, sc.x)) traj->last_pass_path = RL_PASS_PATH_RECURRENT_TILE;
     } else {
-      // (the wide tile shape: every forward that keeps a record, and what follows from that record, on the tile kernels;
-      // an evaluation without one — the line search's — on the lane-per-thread f32 forward, as at five inputs)
-      if (row.backward && seq_wide_tile_fits(traj, sc.x)) traj->last_pass_path = RL_PASS_PATH_RECURRENT_TILE;
+      // (the wide tile shape: every pass of an update on the tile kernels — the forward that keeps a record and what
+      // follows from it, and the evaluation without one, the line search's, by the same arithmetic: a candidate equal
+      // to theta_0 then has ratios of exactly 1 and a KL of exactly 0, as at five inputs, where both forwards are f32)
+      const bool wide_tile = seq_wide_tile_fits(traj, sc.x);
+      if (wide_tile) traj->last_pass_path = RL_PASS_PATH_RECURRENT_TILE;
       // The record is asked for wherever the pass kind has a backward, also when this request stops before it
       // (forward_only): with a record the tile kernels run the bf16-pipe training forward, without one the f32 forward
       // (launch_gru_seq_forward), and the two round differently.  rl_ppo_update's log pi_0 must come from the forward
       // its steps recompute log pi with: then the first step's ratios are exactly 1, as the reference's are — off by
       // an ulp they are clipped samples at clip_distance = 0.
-      launch_gru_seq_forward(traj, sc.x, traj->seq.out, nullptr, row.backward ? seq_record(traj, sc.x) : nullptr,
-                             req.skip);
+      // (The record-less tile forward is chosen HERE, where the pass kind is known: rl_seq_forward without successor
+      // values hands launch_gru_seq_forward the same two NULLs and stays bit-exact on the f32 forward.)
+      if (wide_tile && !row.backward) launch_gru_eval_forward(traj, sc.x, traj->seq.out, req.skip);
+      else
+        launch_gru_seq_forward(traj, sc.x, traj->seq.out, nullptr, row.backward ? seq_record(traj, sc.x) : nullptr,
+                               req.skip);
       if (critic) launch_seq_critic_dvalues(traj, Bt);
       else launch_seq_policy_dlogits(traj, req.kind, Bt, req.clip_lo, req.clip_hi, req.skip, sc.x->out_dim);
     }

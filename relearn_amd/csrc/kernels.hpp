@@ -213,15 +213,17 @@ void launch_seq_unpad(const rl_mlp *real, const float *exec_src, float *real_dst
 // kernels_seq_train.hip: the GRU chain's training passes with the recurrence on the bf16 matrix pipe
 void launch_gru_train_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float *d_act, const int32_t *d_skip);
 void launch_lstm_train_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float *d_act, const int32_t *d_skip);
+// ... the same forward without a record (seq_wide_tile_fits only): d_out, and planes 0 .. 2 and DPRE_DU of seq.dpre
+void launch_gru_eval_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, const int32_t *d_skip);
 void launch_seq_train_head_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float *d_act, const int32_t *d_skip);
 void launch_gru_train_head_backward(rl_traj *traj, const rl_mlp *mod, float *d_slab, const int32_t *d_skip);
 void launch_gru_train_recur_backward(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip);
 void launch_gru_train_wgrad(rl_traj *traj, const rl_mlp *mod, const int32_t *d_skip);
 constexpr uint32_t RL_SEQ_HEAD_ROWS = 512;  // rows of head-gradient partials behind the weight-gradient kernel's chunks
-// A lane-kernel module whose TRAINING passes (record-bearing forward, backward, weight gradients, tangent) run the tile
-// kernels above with the input side in kernels_seq_in.hip: ModuleShape::wide_tile_shape on whole tiles of 32 lanes under
-// engine kernel variant 0.  Rollouts, value forwards, evaluations without a record and every other shape stay on the
-// lane-per-thread kernels.  (A linear tail of that shape: the same input side and recurrence, the head in
+// A lane-kernel module whose UPDATE passes (record-bearing forward, backward, weight gradients, tangent, and the line
+// search's record-less evaluation) run the tile kernels above with the input side in kernels_seq_in.hip:
+// ModuleShape::wide_tile_shape on whole tiles of 32 lanes under engine kernel variant 0.  Rollouts, value forwards,
+// rl_seq_forward and every other shape stay on the lane-per-thread kernels.  (A linear tail of that shape: the same input side and recurrence, the head in
 // kernels_seq_lin.hip.)
 inline bool seq_wide_tile_fits(const rl_traj *traj, const rl_mlp *mod) {
   return mod->wide_tile_shape() && traj->d.n % 32 == 0 && traj->eng->kernel_variant == 0;

@@ -17,6 +17,8 @@
 // workgroup barriers and a 128-deep product less on the critical path of every step:
 //   k_gru_recur_fwd      t = 0 .. T-1: gates by MFMA, cell on the VALU; records r, z, n, gh_n, h_prev, relu(h')
 //   k_seq_head_forward   u = relu(W1 relu(h') + b1) (recorded), out = W2 u + b2          (all blocks in parallel)
+//   k_gru_recur_eval, k_seq_head_eval   the same two bodies without a record (the line search's evaluations at 6 to 24
+//                        features): relu(h') into one workspace plane, u on chip, the outputs
 //   k_gru_head_backward  d u_pre (on chip), d relu(h'), and the head's own weight gradients  (all blocks in parallel)
 //   k_gru_recur_bwd      t = T-1 .. 0: d gates on the VALU, d h_prev = sum_g W_hh[g]^T d gh_g by MFMA; the n gate's
 //                        input-side sums
@@ -110,215 +112,27 @@ __device__ __forceinline__ float tanh_sel(float x) {
 // D = 0, "input side elsewhere": k_seq_in_proj (kernels_seq_in.hip) has left gi = W_ih x + b_ih of every block in the
 // record's r, z and n arrays; a lane reads its 16 bytes per gate and M-tile a phase ahead and writes r, z, n over them.
 // No input loop, no xS / wiS, and the flat vector's offsets are formed from the trajectory's feature count.
+//
+// REC = false, "no record" (k_gru_recur_eval, D = 0 only: the line search's evaluations): `act` is a workspace of
+// DPRE_ARR planes per block whose planes 0 .. 2 hold gi; the gate arithmetic is the recording form's statement for
+// statement — the same bits of h — and of the seven arrays only a1 = relu(h') is stored, into plane `a1_plane`.
+// The two kernels are one body (seq_recur_fwd.inc, included into each): as a shared __device__ function the recording
+// instantiations came out with other register assignments and another instruction order than before.
 template <int D>
 __global__ void __launch_bounds__(W16 * 64, 2)
     k_gru_recur_fwd(TrajDev tr, const float *__restrict__ params, int A, float *__restrict__ act,
                     const int32_t *__restrict__ skip) {
-  constexpr bool IN = D > 0;        // the input projection is this kernel's
-  constexpr int DX = IN ? D : 1;
-  __shared__ __attribute__((aligned(16))) unsigned short hP[3][TL * GH];  // h as pieces, [sample][unit] (img_at)
-  __shared__ float xS[IN ? 2 : 1][IN ? TL : 1][9];  // (9: the four samples a wave reads at once are 4 rows apart — 144 bytes, not 128)
-  __shared__ int endS[2][TL];
-  __shared__ float wiS[IN ? 3 : 1][DX + 1][IN ? GH : 1];
-  __shared__ uint4 wnS[GH / 32][3][W16][64];  // the n gate's W_hh fragments (96 KB): 48 registers the budget does not have
-  if (skip != nullptr && *skip != 0) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n16 = lane & 15, g4 = lane >> 4, j = 16 * wave + n16;
-  const uint32_t N = tr.n, T = tr.T;
-  const uint32_t tile = blockIdx.x, tiles = gridDim.x, lane0 = tile * TL;
-  const GruParams g = gru_params(params, IN ? D : (int)tr.D, A);
-  Frag wf[2][GH / 32][3];  // [gate r, z][k-block][piece]: W_hh[gate * GH + j][32 kb + 8 g4 + 0..7]
-  float bhh[3];
-#pragma unroll
-  for (int gte = 0; gte < 3; ++gte) {
-    const int row = gte * GH + j;
-#pragma unroll
-    for (int kb = 0; kb < GH / 32; ++kb) {
-      float v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = g.Whh[(size_t)row * GH + 32 * kb + 8 * g4 + i];
-      if (gte < 2) {
-        frags_of8(v, wf[gte][kb]);
-      } else {
-        Frag f[3];
-        frags_of8(v, f);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) wnS[kb][q][wave][lane] = f[q].x;
-      }
-    }
-    bhh[gte] = g.bhh[row];
-  }
-  // the input projection's weights wait in LDS ([gate][feature | bias][unit]): 18 registers the products need more
-  if constexpr (IN)
-    for (int q = threadIdx.x; q < 3 * (D + 1) * GH; q += W16 * 64) {
-      const int gte = q / ((D + 1) * GH), d = (q / GH) % (D + 1), u = q % GH;
-      wiS[gte][d][u] = d < D ? g.Wih[(size_t)(gte * GH + u) * D + d] : g.bih[gte * GH + u];
-    }
-  for (int q = threadIdx.x; q < (int)(sizeof(hP) / 4); q += W16 * 64) reinterpret_cast<uint32_t *>(&hP[0][0])[q] = 0u;
-  float hown[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) hown[r] = 0.0f;
-  const bool io_lane = wave == 0 && lane < TL;
-  const uint32_t i_lane = lane0 + (uint32_t)(lane & (TL - 1));
-  const size_t plane = (size_t)(T + 1) * N;
-  float xin[DX];
-  int fin = 0;
-  auto fetch = [&](uint32_t tt) {  // io lanes: observation and successor code of step tt, into registers
-    if constexpr (IN)
-#pragma unroll
-      for (int d = 0; d < D; ++d) xin[d] = tr.obs[d * plane + (size_t)tt * N + i_lane];
-    fin = tr.flag[(size_t)tt * N + i_lane];
-  };
-  auto publish = [&](int buf) {
-    if constexpr (IN)
-#pragma unroll
-      for (int d = 0; d < D; ++d) xS[buf][lane][d] = xin[d];
-    endS[buf][lane] = fin != RL_SUCC_CONTINUE;
-  };
-  if (io_lane) {
-    fetch(0);
-    publish(0);
-  }
-  // input side elsewhere: gi of (step, M-tile) in registers, loaded while the phase before it runs
-  f32x4 gin[3][IN ? 1 : 2];
-  auto fetch_gi = [&](uint32_t tt, int mt) {
-    if constexpr (!IN) {
-      const float *__restrict__ ab = act + ((size_t)tt * tiles + tile) * SEQ_ARR * GH * TL;
-      const uint32_t row = rec_at(j, 16 * mt + 4 * g4);
-      gin[0][mt] = *reinterpret_cast<const f32x4 *>(ab + (uint32_t)(ACT_R * GH * TL) + row);
-      gin[1][mt] = *reinterpret_cast<const f32x4 *>(ab + (uint32_t)(ACT_Z * GH * TL) + row);
-      gin[2][mt] = *reinterpret_cast<const f32x4 *>(ab + (uint32_t)(ACT_N * GH * TL) + row);
-    }
-  };
-  fetch_gi(0, 0);
-  fetch_gi(0, 1);
-  __syncthreads();
-  // A step is two phases with a barrier after each, and in both the matrix pipe and the vector ALU work side by side:
-  //   phase 1: products of M-tile 1 (step t)       | gate arithmetic of M-tile 0 (step t) -> rows 0-15 of h(t+1)
-  //   phase 2: products of M-tile 0 (step t + 1)   | gate arithmetic of M-tile 1 (step t) -> rows 16-31 of h(t+1)
-  // (the products of an M-tile need its 16 samples of ALL units, i.e. that M-tile's gate arithmetic of every wave, and
-  // nothing of the other M-tile).  The barrier keeps the two waves of a SIMD in the same phase, so the overlap has to
-  // come from INSIDE a wave: each phase is one basic block, and the scheduler is asked to place a few vector
-  // instructions after every matrix instruction.  (One phase per step — both M-tiles' products, then both M-tiles'
-  // gates with M-tile 1's products between M-tile 0's — left the first products and the last gates uncovered: VALU
-  // busy 0.52 + matrix pipe 0.48 added up to the step time.)  Rows of the image are rewritten only after the barrier
-  // that follows their last read, so one image serves.
-  f32x4 acc[3][2];
-  auto start = [&](int mt) {
-#pragma unroll
-    for (int gte = 0; gte < 3; ++gte) acc[gte][mt] = (f32x4){bhh[gte], bhh[gte], bhh[gte], bhh[gte]};
-  };
-  // operand reads run one k-block ahead of the products
-  auto products = [&](int mt) {
-    auto frags = [&](int kb, Frag (&a)[3]) {
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-        a[p].x = *reinterpret_cast<const uint4 *>(&hP[p][img_at(16 * mt + n16, 32 * kb + 8 * g4)]);
-    };
-#pragma unroll
-    for (int kb = 0; kb < GH / 32; ++kb) {
-      Frag fa[3], wn[3];
-      frags(kb, fa);
-#pragma unroll
-      for (int q = 0; q < 3; ++q) wn[q].x = wnS[kb][q][wave][lane];
-#pragma unroll
-      for (int gte = 0; gte < 2; ++gte) acc[gte][mt] = mfma_pieces(fa, wf[gte][kb], acc[gte][mt]);
-      acc[2][mt] = mfma_pieces(fa, wn, acc[2][mt]);
-    }
-  };
-  auto gates = [&](int mt, uint32_t t) {
-    const int cur = (int)(t & 1);
-    float *__restrict__ store = act + ((size_t)t * tiles + tile) * SEQ_ARR * GH * TL;
-    // (uniform block base + 32-bit lane offsets: the addresses stay out of the vector registers)
-    const uint32_t row = rec_at(j, 16 * mt + 4 * g4);
-    *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_GHN * GH * TL) + row) = acc[2][mt];
-    *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_HPREV * GH * TL) + row) =
-        (f32x4){hown[4 * mt], hown[4 * mt + 1], hown[4 * mt + 2], hown[4 * mt + 3]};
-    float wih[3][DX], bih[3];
-    if constexpr (IN)
-#pragma unroll
-      for (int gte = 0; gte < 3; ++gte) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) wih[gte][d] = wiS[gte][d][j];
-        bih[gte] = wiS[gte][D][j];
-      }
-    f32x4 rv, zv, nv, av;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = acc16_row(mt, i, g4), r = 4 * mt + i;
-      float gi[3];
-#pragma unroll
-      for (int gte = 0; gte < 3; ++gte) {
-        if constexpr (IN) {
-          float v = bih[gte];
-#pragma unroll
-          for (int d = 0; d < D; ++d) v = __builtin_fmaf(xS[cur][m][d], wih[gte][d], v);
-          gi[gte] = v;
-        } else {
-          gi[gte] = gin[gte][mt][i];
-        }
-      }
-      const float rr = sigmoid_sel(acc[0][mt][i] + gi[0]);
-      const float zz = sigmoid_sel(acc[1][mt][i] + gi[1]);
-      const float rn = acc[2][mt][i] * rr;
-      const float nn = tanh_sel(gi[2] + rn);
-      const float dn = hown[r] - nn;
-      const float hz = dn * zz;
-      const float hv = hz + nn;
-      rv[i] = rr;
-      zv[i] = zz;
-      nv[i] = nn;
-      av[i] = hv > 0.0f ? hv : 0.0f;
-      // the state the next step starts from: zero after an episode end (SeqPacked restarts per episode)
-      const float hn = endS[cur][m] != 0 ? 0.0f : hv;
-      hown[r] = hn;
-      uint32_t p0, p1, p2;
-      bt::split3(hn, p0, p1, p2);
-      hP[0][img_at(m, j)] = (unsigned short)p0;
-      hP[1][img_at(m, j)] = (unsigned short)p1;
-      hP[2][img_at(m, j)] = (unsigned short)p2;
-    }
-    *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_R * GH * TL) + row) = rv;
-    *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_Z * GH * TL) + row) = zv;
-    *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_N * GH * TL) + row) = nv;
-    *reinterpret_cast<f32x4 *>(store + (uint32_t)(ACT_A1 * GH * TL) + row) = av;
-    // (the last step reads its own block again: values nobody uses, no branch in the phase's block)
-    fetch_gi(t + 1 < T ? t + 1 : t, mt);
-  };
-  // the order asked of the scheduler for a phase: one matrix instruction, a few vector ones (PHASE: the two phases share
-  // a basic block, and groups of one sync id are matched against the whole block)
-  auto interleave = [&](auto phase) {
-    constexpr int PHASE = decltype(phase)::value;
-#pragma unroll
-    for (int k = 0; k < (GH / 32) * 3 * PIECE_PAIRS; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, PHASE);              // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x002, VALU_PER_MFMA, PHASE);  // VALU
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  start(0);
-  products(0);  // (h = 0: the biases)
-  for (uint32_t t = 0; t < T; ++t) {
-    if (io_lane && t + 1 < T) fetch(t + 1);  // lands under the products
-    __builtin_amdgcn_sched_barrier(0);
-    start(1);
-    gates(0, t);
-    products(1);
-    interleave(std::integral_constant<int, 0>{});
-    __syncthreads();  // rows 0-15 of h(t+1) are complete; every wave has read rows 16-31 of h(t)
-    // (the branch, always taken, gives phase 2 a basic block of its own: with both phases in one block the scheduler
-    // honoured the requested order for one of them only)
-    int taken;
-    asm volatile("s_mov_b32 %0, 1" : "=s"(taken));
-    if (taken != 0) {
-      start(0);
-      products(0);  // (after the last step: products nobody reads — a branch on t here would split the phase's block)
-      gates(1, t);
-      interleave(std::integral_constant<int, 1>{});
-    }
-    if (io_lane && t + 1 < T) publish((int)((t + 1) & 1));
-    __syncthreads();  // rows 16-31 of h(t+1) and the inputs of step t + 1 are complete; rows 0-15 have been read
-  }
+  constexpr bool REC = true;
+  constexpr int a1_plane = ACT_A1;
+#include "seq_recur_fwd.inc"
+}
+
+template <int D>
+__global__ void __launch_bounds__(W16 * 64, 2)
+    k_gru_recur_eval(TrajDev tr, const float *__restrict__ params, int A, float *__restrict__ act, int a1_plane,
+                     const int32_t *__restrict__ skip) {
+  constexpr bool REC = false;
+#include "seq_recur_fwd.inc"
 }
 
 // ---------------------------------------------------------------- forward recurrence of the LSTM chain
@@ -561,93 +375,25 @@ __global__ void __launch_bounds__(256, 1)
 // u = relu(b1 + W1 relu(h')) on the bf16 pipe (A operand: the recorded relu(h') block, split into its pieces and laid
 // out [sample][unit] in LDS; B: this wave's 16 rows of W1 as register fragments), recorded for the backward;
 // out_a = b2_a + sum_q u_q W2[a][q]: the 16 units of a wave summed across its lanes (DPP), the eight waves through LDS.
+// REC = false, "no record" (k_seq_head_eval): relu(h') is plane `plane` of every block of `act`, a workspace of `arrays`
+// planes per block; u stays in registers and only the outputs are stored.
+// (one body, seq_head_fwd.inc, for the same reason as the recurrence's)
 template <int A>
 __global__ void __launch_bounds__(W16 * 64, 2)
     k_seq_head_forward(TrajDev tr, const float *__restrict__ params, int D, int NG, float *__restrict__ act,
                        float *__restrict__ out, uint32_t tiles, uint32_t blocks, const int32_t *__restrict__ skip) {
-  __shared__ __attribute__((aligned(16))) unsigned short aK[3][TL * GH];  // relu(h') as pieces (img_at)
-  __shared__ float vS[2][W16][TL];  // per output, wave and sample: the wave's 16 terms of W2 u
-  if (skip != nullptr && *skip != 0) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n16 = lane & 15, g4 = lane >> 4, j = 16 * wave + n16;
-  const uint32_t N = tr.n, T = tr.T;
-  const GruParams g = seq_params(params, D, A, NG);
-  Frag w1f[GH / 32][3];  // W1[j][32 kb + 8 g4 + 0..7]
-#pragma unroll
-  for (int kb = 0; kb < GH / 32; ++kb) {
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = g.W1[(size_t)j * GH + 32 * kb + 8 * g4 + i];
-    frags_of8(v, w1f[kb]);
-  }
-  const float b1 = g.b1[j];
-  float w2c[A];
-#pragma unroll
-  for (int a = 0; a < A; ++a) w2c[a] = g.W2[a * MH + j];
-  const int ha = (int)threadIdx.x / TL, hm = (int)threadIdx.x % TL;  // threads < A TL: output, sample
-  const float b2v = ha < A ? g.b2[ha] : 0.0f;
-  const uint32_t lo = rec_at(j, 4 * g4);
-  f32x4 a1n[2];
-  auto fetch = [&](uint32_t blk) {
-    const float *__restrict__ ab = act + (size_t)blk * SEQ_ARR * GH * TL;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-      a1n[mt] = *reinterpret_cast<const f32x4 *>(ab + (uint32_t)(ACT_A1 * GH * TL) + lo + REC_HALF * mt);
-  };
-  if (blockIdx.x < blocks) fetch(blockIdx.x);
-  for (uint32_t blk = blockIdx.x; blk < blocks; blk += gridDim.x) {
-    const uint32_t t = blk / tiles, lane0 = (blk % tiles) * TL;
-    float *__restrict__ ab = act + (size_t)blk * SEQ_ARR * GH * TL;
-    __syncthreads();  // the previous block's readers of aK / vS are done
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        uint32_t p0, p1, p2;
-        bt::split3(a1n[mt][i], p0, p1, p2);
-        const int m = 16 * mt + 4 * g4 + i;
-        aK[0][img_at(m, j)] = (unsigned short)p0;
-        aK[1][img_at(m, j)] = (unsigned short)p1;
-        aK[2][img_at(m, j)] = (unsigned short)p2;
-      }
-    if (blk + gridDim.x < blocks) fetch(blk + gridDim.x);  // the next block's operand lands under this block's products
-    __syncthreads();
-    f32x4 acc1[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) acc1[mt] = (f32x4){b1, b1, b1, b1};
-#pragma unroll
-    for (int kb = 0; kb < GH / 32; ++kb)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        Frag fa[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          fa[c].x = *reinterpret_cast<const uint4 *>(&aK[c][img_at(16 * mt + n16, 32 * kb + 8 * g4)]);
-        acc1[mt] = mfma_pieces(fa, w1f[kb], acc1[mt]);
-      }
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      f32x4 uv;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float u = acc1[mt][i] > 0.0f ? acc1[mt][i] : 0.0f;
-        uv[i] = u;
-#pragma unroll
-        for (int a = 0; a < A; ++a) {
-          const float part = sum16(u * w2c[a]);
-          if (n16 == 0) vS[a][wave][acc16_row(mt, i, g4)] = part;
-        }
-      }
-      *reinterpret_cast<f32x4 *>(ab + (uint32_t)(ACT_U * GH * TL) + lo + REC_HALF * mt) = uv;
-    }
-    __syncthreads();
-    if (ha < A) {
-      float v = b2v;
-#pragma unroll
-      for (int w = 0; w < W16; ++w) v += vS[ha][w][hm];
-      out[((size_t)ha * T + t) * N + lane0 + hm] = v;
-    }
-  }
+  constexpr bool REC = true;
+  [[maybe_unused]] constexpr int arrays = SEQ_ARR, plane = ACT_A1;
+#include "seq_head_fwd.inc"
+}
+
+template <int A>
+__global__ void __launch_bounds__(W16 * 64, 2)
+    k_seq_head_eval(TrajDev tr, const float *__restrict__ params, int D, int NG, float *__restrict__ act, int arrays,
+                    int plane, float *__restrict__ out, uint32_t tiles, uint32_t blocks,
+                    const int32_t *__restrict__ skip) {
+  constexpr bool REC = false;
+#include "seq_head_fwd.inc"
 }
 
 // ---------------------------------------------------------------- backward recurrence
@@ -1254,6 +1000,34 @@ void launch_gru_train_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, fl
                        d_skip);
   }
   launch_seq_train_head_forward(traj, mod, d_out, d_act, d_skip);
+}
+
+// teacher-forced forward WITHOUT a record of a chain of the wide tile shape (the line search's evaluations): the training
+// forward's arithmetic, and nothing written but d_out [A][T][n] and four planes of the tangent pass's static terms —
+// gi into planes 0 .. 2 of seq.dpre (where a Fisher-vector product puts the tangent's; every product rebuilds them), and
+// relu(h') into plane DPRE_DU, which no training pass of this shape reads and which a tangent pass writes before it
+// reads it (MLP tail: k_seq_tangent_pre; linear tail: k_seq_tangent_rec).  The record, lp0 and the kept masks stay
+// those of theta_0.  Every launch tests d_skip.
+void launch_gru_eval_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, const int32_t *d_skip) {
+  const SeqDev &q = traj->seq;
+  RL_REQUIRE(seq_wide_tile_fits(traj, mod) && q.dpre != nullptr, "record-less tile forward: the wide tile shape, after seq_ensure");
+  ProfScope ps(traj->eng, RL_K_POLICY_FUSED);
+  rl_engine *e = traj->eng;
+  const uint32_t tiles = traj->d.n / TL, blocks = traj->d.T * tiles;
+  const int A = (int)mod->out_dim;
+  launch_seq_in_proj(traj, mod->d_params, q.dpre, DPRE_ARR, d_skip);
+  hipLaunchKernelGGL(k_gru_recur_eval<0>, dim3(tiles), dim3(W16 * 64), 0, e->stream, traj->d, mod->d_params, A, q.dpre,
+                     (int)DPRE_DU, d_skip);
+  if (mod->linear_tail()) {
+    const float *kernel = mod->d_params + mod->rnn_layer_offset(1);
+    return launch_seq_lin_head(traj, kernel, kernel + (size_t)A * GH, false, q.dpre, DPRE_ARR, DPRE_DU, d_out, A, d_skip);
+  }
+  if (!with_one_of<2>(A, [&](auto aa) {  // (an evaluation is a policy's: two logits with an MLP tail)
+        hipLaunchKernelGGL(k_seq_head_eval<decltype(aa)::value>, dim3(blocks < 2048 ? blocks : 2048), dim3(W16 * 64), 0,
+                           e->stream, traj->d, mod->d_params, (int)traj->d.D, (int)rl_module_gates(mod->kind), q.dpre,
+                           DPRE_ARR, (int)DPRE_DU, d_out, tiles, blocks, d_skip);
+      }))
+    throw RlError(RL_ERR_UNSUPPORTED, "launch_gru_eval_forward: an MLP tail of two outputs");
 }
 
 // teacher-forced training forward of the LSTM chain: the recurrence on the bf16 pipe, then the head
