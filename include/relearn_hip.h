@@ -681,9 +681,10 @@ int32_t rl_traj_read(rl_traj *traj, int32_t field, void *host, uint64_t bytes);
  * update loops built from them); NONE before any pass.  The reference's default MlpConfig is hidden_sizes = [128]
  * (src/torch/modules/ff/mlp.rs:13-34): at 9 to 24 inputs that shape reports WIDE_SPLIT, at most 64 units WIDE_MFMA,
  * and PER_LAYER says that no fused kernel is built for the shape (or that the engine runs kernel variant 1).
- * RECURRENT_TILE: a GRU-MLP chain of 6 to 24 inputs at GRU 128 / MLP [128], one or two outputs, on a multiple of 32 lanes
- * ran a gradient pass or a Fisher-vector product on the tile-resident matrix-pipe kernels (kernels_seq_train.hip with the
- * input side in kernels_seq_in.hip) — and so did a GRU-Linear chain of the same inputs and GRU width with 1 or 3 to 12
+ * RECURRENT_TILE: a GRU-MLP chain of 6 to 24 inputs at GRU 128 / MLP [128], 1 to 12 outputs, on a multiple of 32 lanes
+ * ran a gradient pass, a Fisher-vector product or an evaluation on the tile-resident matrix-pipe kernels
+ * (kernels_seq_train.hip with the input side in kernels_seq_in.hip; 3 to 12 outputs: the head in kernels_seq_head_n.hip)
+ * — and so did a GRU-Linear chain of the same inputs and GRU width with 1 or 3 to 12
  * outputs (the head in kernels_seq_lin.hip; two outputs with a linear tail stay on the lane-per-thread kernels); every
  * other recurrent pass reports RECURRENT, as before. */
 typedef enum { RL_PASS_PATH_NONE = 0, RL_PASS_PATH_PER_LAYER = 1, RL_PASS_PATH_FUSED_5_128 = 2, RL_PASS_PATH_GEN_MFMA = 3,

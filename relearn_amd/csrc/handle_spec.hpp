@@ -521,17 +521,20 @@ struct ModuleShape {
   // (or recurrent weights without bias vectors, RnnBaseConfig::bias_init = None: `has_bias` false — the gate rows then
   // start from 4 x 256 zeros kept behind the P parameters, like the bias-less MLP layers; the chain's MLP keeps its own)
   // (or a chain whose second module is one Linear, `linear_tail`: at every shape, 5 -> 128 included, and never a twin)
-  // (or a chain of more than two outputs, rl_rnn_chain_create: the tile kernels and the twin stay two-action)
+  // (or a chain of more than two outputs, rl_rnn_chain_create: the 5-input tile kernels and the twin stay two-action;
+  // the update passes of the wide tile shape below take 3 to 12 outputs on either tail)
   bool lane_kernels() const {
     return rnn_layers > 1 || in_dim > 5 || gru_hidden > 128 || hidden > 128 || !has_bias || linear_tail() || out_dim > 2;
   }
   // A lane-kernel module whose training passes fit the tile kernels with the input side computed apart
   // (kernels_seq_in.hip): GruMlpConfig at the partition-game experiment's widths — one GRU layer of 128 units with bias
-  // vectors, 6 to 24 inputs, an MLP tail of 128 hidden units, one or two outputs (no twin: the widths are the kernels').
+  // vectors, 6 to 24 inputs, an MLP tail of 128 hidden units, one or two outputs (no twin: the widths are the kernels'),
+  // or 3 to RL_WIDE_MAX_OUT outputs — the RL² experiments' default chain as a categorical policy, its head in
+  // kernels_seq_head_n.hip.
   // Or GruLinearConfig at the RL² experiments' widths: the same recurrent layer with a linear tail of 1 to
   // RL_WIDE_MAX_OUT outputs, its head in kernels_seq_lin.hip.
   bool wide_tile_shape() const {
-    const bool mlp_tail = hidden == 128 && (out_dim == 1 || out_dim == 2);
+    const bool mlp_tail = hidden == 128 && out_dim >= 1 && out_dim <= RL_WIDE_MAX_OUT;
     const bool lin_tail = linear_tail() && out_dim >= 1 && out_dim <= RL_WIDE_MAX_OUT &&
                           // tests/test_gpu_seq_wide_tile.py::test_neighbours_keep_their_path[linear tail] holds two
                           // outputs with a linear tail to the lane-per-thread kernels (the kernels do not exclude 2)

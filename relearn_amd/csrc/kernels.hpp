@@ -247,6 +247,18 @@ inline uint32_t seq_lin_head_rows(const rl_traj *traj) {  // one row per workgro
   const uint32_t blocks = traj->d.T * (traj->d.n / 32);
   return blocks < RL_SEQ_HEAD_ROWS ? blocks : RL_SEQ_HEAD_ROWS;
 }
+// kernels_seq_head_n.hip: the head of an MLP-tail chain of that shape with 3 to 12 outputs, block-parallel, the output
+// layer as one 16-row tile of the matrix pipe
+//   head_n_forward: u and d_out [A][T][n] from relu(h') in plane `plane` of every block of `d_act` (`arrays` planes per
+//                   block); `record`: d_act is the training record and u goes to its ACT_U
+//   head_n_backward: d relu(h') into seq.dpre, and the head's columns of rows [0, RL_SEQ_HEAD_ROWS) of `d_slab`
+//   head_n_tangent: seq.out <- the outputs' tangent from the record and a1_dot in plane DPRE_DU of seq.dpre (left there
+//                   by k_seq_tangent_rec<0, ..>)
+void launch_seq_head_n_forward(rl_traj *traj, const rl_mlp *mod, float *d_out, float *d_act, int arrays, int plane,
+                               bool record, const int32_t *d_skip);
+void launch_seq_head_n_backward(rl_traj *traj, const rl_mlp *mod, float *d_slab, const int32_t *d_skip);
+void launch_seq_head_n_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent, const int32_t *d_skip);
+inline bool seq_head_n(const rl_mlp *mod) { return mod->out_dim > 2 && !mod->linear_tail(); }  // (of the wide tile shape)
 // v_last: [n] V(obs[T]) of every lane for slot T of the value plane (a general critic's: launch_gen_values), or NULL
 void launch_seq_gae(rl_traj *traj, float gamma, float lambda, const float *v_last);
 // one-step TD targets from traj->seq.out / succ (plane 0) -> d.tgt

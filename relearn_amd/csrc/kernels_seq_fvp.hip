@@ -341,6 +341,18 @@ static void launch_seq_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_
     launch_seq_lin_head(traj, mod->d_params + ohead, q.succ, true, q.dpre, DPRE_ARR, DPRE_DU, q.out, A, d_skip);
     return;
   }
+  if (seq_wide_tile_fits(traj, mod) && seq_head_n(mod)) {
+    // an MLP tail of 3 to 12 outputs: the linear tail's two instantiations again — with A = 0 their views of the flat
+    // vectors (seq_params) reach the recurrent slices only, and they carry no head term: the recurrence leaves a1_dot =
+    // [relu(h') > 0] h'_dot of every step in plane DPRE_DU — then the whole head's tangent as ONE block-parallel launch
+    // (kernels_seq_head_n.hip), out of the serial loop:  seq.out <- V2 u + v_b2 + W2 u_dot
+    launch_seq_in_proj(traj, d_tangent, q.dpre, DPRE_ARR, d_skip);
+    hipLaunchKernelGGL((k_seq_tangent_pre<0, 0, GruTangent>), dim3(q.chunks), dim3(256), 0, e->stream, traj->d, d_tangent,
+                       q.act, q.dpre, q.succ, q.tiles, traj->d.T * q.tiles, q.blocks_per_chunk, d_skip);
+    hipLaunchKernelGGL((k_seq_tangent_rec<0, GruTangent>), dim3(q.tiles), dim3(256), 0, e->stream, traj->d, mod->d_params,
+                       (int)traj->d.D, q.act, q.dpre, q.succ, q.dpre, d_skip);
+    return launch_seq_head_n_tangent(traj, mod, d_tangent, d_skip);
+  }
   if (seq_wide_tile_fits(traj, mod)) {  // (GRU only: the predicate) the input-side tangent term of every block first
     launch_seq_in_proj(traj, d_tangent, q.dpre, DPRE_ARR, d_skip);
     hipLaunchKernelGGL((k_seq_tangent_pre<0, 2, GruTangent>), dim3(q.chunks), dim3(256), 0, e->stream, traj->d, d_tangent,
@@ -357,10 +369,11 @@ void launch_gru_tangent(rl_traj *traj, const rl_mlp *mod, const float *d_tangent
                         const int32_t *d_skip) {
   rl_engine *e = traj->eng;
   const SeqDev &q = traj->seq;
-  // (the tile kernels are two-action; a lane-kernel module may have up to eight outputs, rl_rnn_chain_create, or twelve,
-  // rl_rnn_chain_create_wide)
+  // (the 5-input tile kernels are two-action; a lane-kernel module may have up to eight outputs, rl_rnn_chain_create, or
+  // twelve, rl_rnn_chain_create_wide — on the lane-per-thread kernels, or, the wide tile shape, on the tile kernels with
+  // the head of kernels_seq_lin.hip / kernels_seq_head_n.hip)
   RL_REQUIRE(mod->out_dim == 2 || (mod->lane_kernels() && mod->out_dim > 2 && mod->out_dim <= RL_WIDE_MAX_OUT),
-             "Fisher-vector products are for policies of two actions (lane-per-thread kernels: 2..12)");
+             "Fisher-vector products are for policies of two actions (lane-kernel modules, wide tile shape included: 2..12)");
   // (the wide tile shape: the tangent starts from the tile record its gradient pass left)
   if (mod->lane_kernels() && !seq_wide_tile_fits(traj, mod)) launch_stack_tangent(traj, mod, d_tangent, d_skip);  // -> seq.out
   else {
